@@ -15,11 +15,18 @@ assembly the operator needs, multi-RHS two-level PCG, axis evaluation, potential
 resistivity — FIVE contexts per GPU (streams + arenas, one host thread each; eight hardware queues: remo3d_amd/__init__.py) draw the
 batches one after the other, as `Model` does by default — then ONE all-reduce of the log slab across ranks (RCCL).  The timed span is
 SURVEY.md 8d's: H2D of the mesh arrays ... D2H of the potentials; mesh generation is excluded (8d) and
-reported beside it.  `value` comes from that span.  Per-kernel figures (`roofline`, `breakdown`) come
-from a second, single-context leg with the batches resident (kernels that share the chip cannot be
-timed in isolation); the line also carries that leg's points/s, further mesh sizes and the
-interface-conforming meshes `Model` builds (`sizes`), `Model.compute_synthetic_logs` end to end with
-meshing included (`model_end_to_end`), and the CPU oracle on the host cores (`cpu_baseline`).
+reported beside it.  `value` comes from that span.  A plain run measures only that: meshes, warm-up, the
+timed steps, the JSON line (its `roofline` and `breakdown` from the headline leg's own brackets).  With
+`--full` (N = 1), per-kernel figures (`roofline`, `breakdown`) come from a second, single-context leg
+with the batches resident (kernels that share the chip cannot be timed in isolation); the line then also
+carries that leg's points/s, further mesh sizes and the interface-conforming meshes `Model` builds
+(`sizes`), `Model.compute_synthetic_logs` end to end with meshing included (`model_end_to_end`), the
+box's own stream figures (`box`) and the CPU oracle on the host cores (`cpu_baseline`).
+
+`--dump-outputs DIR` writes what the timed path returned in its last step: `apparent_resistivity.npy`
+(the log slab, depths x tools, float64) and `potentials.npy` (the potentials of rank 0's batches in batch
+order, every right-hand side's evaluation points in turn, float64; NaN for a failed batch).  Meshes are
+seeded, so the same arguments give the same inputs in every run.
 
 Contract: `python bench.py --gpus N --steps K --warmup W`.  For N > 1 either launched by torchrun (one
 rank per GPU), or started plainly: the parent then spawns the N ranks itself (torch.distributed.run)
@@ -360,7 +367,8 @@ class Runner:
     h2d_inclusive (the headline span): every batch goes through remo_solve_batch - host arrays to the device, run,
     potentials back - inside the pass; otherwise the batches are made resident first (remo_batch_create) and a pass runs them."""
 
-    def __init__(self, work, n_depths, local, opts, streams=1, schedule="static", all_resident=False, resident=True, per_batch_opts=None):
+    def __init__(self, work, n_depths, local, opts, streams=1, schedule="static", all_resident=False, resident=True, per_batch_opts=None,
+                 keep_outs=False):
         import numpy as np
         from remo3d_amd import solver, sweep, tasks
         self.np, self.sweep, self.tasks = np, sweep, tasks
@@ -375,6 +383,7 @@ class Runner:
         if resident and not all_resident:
             self.resident = [self.ctxs[i % len(self.ctxs)].batch(w["mesh"], w["sigma"], w["sources"], w["evals"]) for i, w in enumerate(work)]
         self.first_outs = {}                          # potentials of batches 0 and 1 of the last pass (spot check against the oracle)
+        self.last_outs = {} if keep_outs else None    # potentials of every batch of the last pass (--dump-outputs)
         self.pool = None
         if len(self.ctxs) > 1:
             from concurrent.futures import ThreadPoolExecutor
@@ -398,10 +407,14 @@ class Runner:
             for rd in w["readers"]:
                 for (di, ti, K, o, m) in rd:
                     slab[di, ti] = np.nan
+            if self.last_outs is not None:
+                self.last_outs[i] = [np.full(len(e), np.nan) for e in w["evals"]]
             return
         agg["not_converged"] += int(rc == 1)
         if i < 2:
             self.first_outs[i] = [u.copy() for u in outs]
+        if self.last_outs is not None:
+            self.last_outs[i] = [np.array(u, dtype=np.float64) for u in outs]
         for u, rd in zip(outs, w["readers"]):
             for (di, ti, K, o, m) in rd:
                 slab[di, ti] = self.tasks.apparent_resistivity(u[o:o + m], m, K, w["mesh"].dim)
@@ -496,6 +509,15 @@ def timed(runner, steps, warmup, sync, **kw):
         busy += agg["busy_s"]
     sync()
     return time.time() - t0, slab, agg, busy
+
+
+def dump_outputs(directory, slab, outs):
+    """--dump-outputs: the log slab and the potentials of the last timed step as float64 .npy files (a few kB at the headline size)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "apparent_resistivity.npy"), np.asarray(slab, dtype=np.float64))
+    flat = [u for i in sorted(outs) for u in outs[i]]
+    np.save(os.path.join(directory, "potentials.npy"), np.concatenate(flat) if flat else np.zeros(0))
 
 
 # fp64 work of the patch operator per (element, right-hand side): 427 v_fmac_f64 + 90 v_add_f64 + 83 v_mul_f64 in the ISA of
@@ -625,13 +647,18 @@ def main():
     ap.add_argument("--overlap", default="all", choices=["prepare", "all"],
                     help="with --streams > 1: 'prepare' = only one batch is in its PCG at a time, the other contexts number / assemble "
                          "theirs beside it; 'all' = no restriction (default)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline leg, at N = 1: the kernel-timing leg, the box's stream figures, the --sizes legs, Model end to end "
+                         "and the CPU baseline (a plain run measures the headline leg only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path returned in its last step as DIR/apparent_resistivity.npy and DIR/potentials.npy (float64)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--sizes", default="L/csr:4,L/mixed:4,S:8,M:8,XL:2,XL/mixed:2,conforming-M:8,conforming-1.0:4,2D-BM1:8",
                     help="further workloads measured in the same run at N = 1 (SIZE:batches; SIZE = S / M / L / XL or a number = the multiplier itself; 'conforming-' prefix = "
                          "the interface-conforming meshes Model builds, with Model's Chebyshev degree per mesh (conforming-1.0 = Model's default scale), "
                          "'/mixed' = fp32 PCG in fp64 refinement, '/csr' = that operator instead of the choice by size; '2D-BM1' = BASELINE configs[1], "
                          "Benchmark model 1 in 2D, '/chebyshev' = polynomial instead of the multigrid cycle on the vertex block, '/2ctx' = two contexts (streams, host threads) share the batches), reported in the `sizes` array; '' = none")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline leg (no kernel-timing leg, sizes, end-to-end or CPU legs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the headline leg (no kernel-timing leg, sizes, end-to-end or CPU legs)")
     ap.add_argument("--mesh-workers", type=int, default=10, help="CPU processes that build the synthetic meshes side by side (before any GPU work)")
     ap.add_argument("--coarse", default="", metavar="DEGREE,RATIO", help="experiments only: Chebyshev degree and interval ratio of the P1 block (default: by vertex count)")
     ap.add_argument("--vertex-solver", default="auto", choices=["auto", "chebyshev", "amg", "amg_or_chebyshev"],
@@ -646,6 +673,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return self_launch(args, sys.argv[1:])        # nothing of torch / HIP has been loaded in this process
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -658,7 +687,7 @@ def main():
     strong = args.total_depths > 0
     dynamic = args.schedule == "dynamic" and world > 1
     profiled = under_profiler()
-    extras = ((world == 1) and not args.no_extras and not args.resident and args.precision == "fp64" and args.mesh == "lattice" and not args.tune
+    extras = (args.full and (world == 1) and not args.no_extras and not args.resident and args.precision == "fp64" and args.mesh == "lattice" and not args.tune
               and args.op == "auto" and not args.coarse and args.vertex_solver == "auto" and not args.batches and not profiled)
     extra_specs = []
     if extras and args.sizes:
@@ -764,7 +793,7 @@ def main():
         return [make_opts(streams=n_ctx, **kw, **_tuned(vertex_solver_options(w["mesh"].dim, w["mesh"].n_nodes, conforming, n_ctx))) for w in batches]
     per_batch = per_batch_opts(work, args.streams, args.mesh == "conforming")
     runner = Runner(work, n_depths, local, opts, streams=args.streams, schedule=args.schedule, all_resident=dynamic, resident=args.resident,
-                    per_batch_opts=per_batch)
+                    per_batch_opts=per_batch, keep_outs=bool(args.dump_outputs))
     h2d = not args.resident and not dynamic
 
     def sync():
@@ -780,7 +809,11 @@ def main():
     dt = sweep.max_over_ranks(dt_local)
     busy_ranks = sweep.gather_floats([1e3 * busy / args.steps, float(agg["batches"])])
     first_outs = dict(runner.first_outs)
+    last_outs = runner.last_outs
     runner.close()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, slab, last_outs)
+        log("outputs of the last timed step written to %s" % args.dump_outputs)
 
     n_points = n_depths * len(TOOLS) if not args.batches else sum(len(rd) for w in work for rd in w["readers"])
     value = n_points * args.steps / dt
@@ -815,7 +848,7 @@ def main():
         return dict(numbering_and_pattern_device=a["ms_symbolic"], h2d=a["ms_h2d"], assemble=a["ms_assemble"], solve=a["ms_solve"],
                     eval=a["ms_eval"], pcg_steps=int(a["pcg_steps"]), note="sums over the batches of one step of the per-batch device times (HIP events)")
 
-    if extras or (world == 1 and args.streams == 1):
+    if extras or (world == 1 and args.streams == 1 and (args.full or args.resident)):
         # ---- the kernel-timing leg: ONE context, batches resident - nothing else on the chip while a launch is bracketed ----
         if args.streams == 1 and args.resident:
             agg_k, dt_k, slab_k, k_steps = agg, dt, slab, args.steps            # the headline leg already is that leg
