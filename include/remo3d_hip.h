@@ -166,6 +166,20 @@ int remo_solve_batch(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, co
                      const remo_opts_t *opts, remo_stats_t *stats);
 
 /*
+ * The same for anisotropic materials (added within ABI 7: the change is additive - callers detect it by the
+ * presence of the symbol, and REMO_ABI_VERSION stays 7).  sigma_tensor[n_mat * nc] holds, per material, the upper
+ * triangle of a symmetric positive definite conductivity tensor, row-major, in the mesh's frame:
+ *   dim 2 (r, z): nc = 3, [rr, rz, zz];   dim 3 (x, y, z): nc = 6, [xx, xy, xz, yy, yz, zz].
+ * The element terms become |T| grad(l_a)^T S grad(l_b) (2D: weighted by 2 pi r as before); a tensor that is exactly
+ * sigma * I gives terms bit-identical to remo_solve_batch with sigma.  A material whose entries are not finite or
+ * whose leading principal minors are not all > 0 is rejected with REMO_ERR_ARG (outputs NaN).
+ */
+int remo_solve_batch_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor,
+                            int32_t n_rhs, const int32_t *src_ptr, const double *src_z, const double *src_I,
+                            const int32_t *eval_ptr, const double *eval_z, double *u_out,
+                            const remo_opts_t *opts, remo_stats_t *stats);
+
+/*
  * Staged form of the same work, for callers that keep a batch resident (bench.py: inputs are in
  * HBM before the timed region).  create = validate + upload; run = numbering, pattern, assembly,
  * PCG, evaluation, all RHS; fetch = potentials to the host.
@@ -217,6 +231,8 @@ int remo_batch_spmv(remo_ctx_t *ctx, remo_batch_t *batch, int32_t k, const doubl
  */
 int remo_host_element_matrix(int32_t dim, const double *vertex_coords /*[(dim+1)*dim], sorted vertices*/,
                              double sigma, double *K_out);
+/* The same with a conductivity tensor in the layout of remo_solve_batch_tensor (REMO_ERR_ARG if not finite and positive definite). */
+int remo_host_element_matrix_tensor(int32_t dim, const double *vertex_coords, const double *sigma_tensor, double *K_out);
 /* max |sum_m B_a[m][i] B_b[m][j] - M_ab[i][j]|: how well the factorised reference tensors of the patch operator
  * (remo_opts_t.op = 3) reproduce the tensors the CSR assembly contracts (both exact polynomial integrals). */
 double remo_host_factor_error(void);

@@ -11,6 +11,8 @@
 //   3D: t = (a,b), 1<=a<=b<=3:   C = sigma |T| grad(l_a).grad(l_b)
 //   2D: t = 3k + (a,b), k=0..2, 1<=a<=b<=2:  C = 2 pi sigma |T| r_k grad(l_a).grad(l_b)
 //       (axisymmetric weight 2 pi r, r = first coordinate, ngsolve_functions.py:34)
+//   anisotropic material (symmetric positive definite tensor S): sigma grad(l_a).grad(l_b) -> grad(l_a)^T S grad(l_b)
+//       (metric_terms_tensor); the terms stay symmetric in (a,b), so the layout and everything that reads C are unchanged
 //
 // Basis (hierarchical, barycentric; any basis of P3 gives the same Galerkin solution):
 //   vertex i: l_i | edge (a,b), a<b: l_a l_b and l_a l_b (l_b - l_a) | face/cell: l_a l_b l_c
@@ -119,6 +121,50 @@ template <int DIM> REMO_HD bool metric_terms(const double *X, double sigma, doub
         const double g11 = g[0][0] * g[0][0] + g[0][1] * g[0][1];
         const double g12 = g[0][0] * g[1][0] + g[0][1] * g[1][1];
         const double g22 = g[1][0] * g[1][0] + g[1][1] * g[1][1];
+        for (int k = 0; k < 3; ++k) {
+            const double r = X[2 * k];
+            C[3 * k + 0] = s * r * g11;
+            C[3 * k + 1] = s * r * g12;
+            C[3 * k + 2] = s * r * g22;
+        }
+    }
+    return true;
+}
+
+// Symmetric conductivity tensor of one material, upper triangle row-major: 2D (r, z) [rr, rz, zz], 3D [xx, xy, xz, yy, yz, zz].
+template <int DIM> struct SigmaTensor { static constexpr int N = (DIM == 2) ? 3 : 6; };
+
+// Metric terms of one element for an anisotropic material: C_ab = |T| g_a^T S g_b (2D: times 2 pi r_k, the same 3 x 3 layout
+// as metric_terms, so both 2D quadratures and every consumer of C are unchanged).  A tensor that is exactly sigma * I takes the
+// scalar formula, so its terms are bit-identical to metric_terms.  Returns false for a degenerate element.
+template <int DIM> REMO_HD bool metric_terms_tensor(const double *X, const double *S, double *C) {
+    if (DIM == 2) {
+        if (S[1] == 0.0 && S[0] == S[2]) return metric_terms<DIM>(X, S[0], C);
+    } else {
+        if (S[1] == 0.0 && S[2] == 0.0 && S[4] == 0.0 && S[0] == S[3] && S[0] == S[5]) return metric_terms<DIM>(X, S[0], C);
+    }
+    double g[DIM][DIM];
+    const double vol = bary_gradients<DIM>(X, g);
+    if (!(vol > 0.0)) return false;
+    if (DIM == 3) {
+        const double Sm[3][3] = {{S[0], S[1], S[2]}, {S[1], S[3], S[4]}, {S[2], S[4], S[5]}};
+        double h[3][3];   // h_b = S g_b
+        for (int b = 0; b < 3; ++b)
+            for (int i = 0; i < 3; ++i) h[b][i] = Sm[i][0] * g[b][0] + Sm[i][1] * g[b][1] + Sm[i][2] * g[b][2];
+        int t = 0;
+        for (int a = 0; a < 3; ++a)
+            for (int b = a; b < 3; ++b)
+                C[t++] = vol * (g[a][0] * h[b][0] + g[a][1] * h[b][1] + g[a][2] * h[b][2]);
+    } else {
+        const double s = 6.283185307179586476925286766559 * vol;
+        double h[2][2];
+        for (int b = 0; b < 2; ++b) {
+            h[b][0] = S[0] * g[b][0] + S[1] * g[b][1];
+            h[b][1] = S[1] * g[b][0] + S[2] * g[b][1];
+        }
+        const double g11 = g[0][0] * h[0][0] + g[0][1] * h[0][1];
+        const double g12 = g[0][0] * h[1][0] + g[0][1] * h[1][1];
+        const double g22 = g[1][0] * h[1][0] + g[1][1] * h[1][1];
         for (int k = 0; k < 3; ++k) {
             const double r = X[2 * k];
             C[3 * k + 0] = s * r * g11;

@@ -134,6 +134,9 @@ using CsrView = CsrViewT<double>;
 
 void launch_metric_terms(int dim, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat, const int32_t *eperm /* or null */,
                          const double *sigma, int nmat, double *C, int32_t *errflag, hipStream_t s);
+// anisotropic materials: sigma_tensor[nmat][3 (2D: rr, rz, zz) or 6 (3D: xx, xy, xz, yy, yz, zz)] (fem_p3.h metric_terms_tensor)
+void launch_metric_terms_tensor(int dim, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat, const int32_t *eperm /* or null */,
+                                const double *sigma_tensor, int nmat, double *C, int32_t *errflag, hipStream_t s);
 // rows [pair_begin, pair_end) (the two dofs of every free edge) get their values interleaved: entry e of the first row
 // at rowptr[row] + 2e, of the second at rowptr[row] + 2e + 1 (CsrViewT below); all other rows plain CSR
 void launch_diag_rows(int dim, int64_t row0, int64_t nfree, const int32_t *adjptr, const uint32_t *adj, const double *C, const double *M, double *dinv, hipStream_t s);

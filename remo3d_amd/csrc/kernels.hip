@@ -76,6 +76,49 @@ void launch_metric_terms(int dim, int64_t nt, const double *coords, const int32_
         hipLaunchKernelGGL(k_metric_terms<3>, dim3(grid), dim3(256), 0, s, nt, coords, conn, mat, eperm, sigma, nmat, C, errflag);
 }
 
+// the same for anisotropic materials: sigma_tensor[nmat][SigmaTensor<DIM>::N] (upper triangles, remo_solve_batch_tensor)
+template <int DIM>
+__global__ void __launch_bounds__(256) k_metric_terms_tensor(int64_t nt, const double *__restrict__ coords,
+                                                             const int32_t *__restrict__ conn, const int32_t *__restrict__ mat,
+                                                             const int32_t *__restrict__ eperm, const double *__restrict__ sigma_tensor,
+                                                             int nmat, double *__restrict__ C, int32_t *errflag) {
+    constexpr int NB = DIM + 1, NT = P3<DIM>::NTERM, NS = SigmaTensor<DIM>::N;
+    const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (t >= nt) return;
+    double X[NB * DIM];
+#pragma unroll
+    for (int a = 0; a < NB; ++a) {
+        const int64_t v = conn[t * NB + a];
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) X[a * DIM + k] = coords[v * DIM + k];
+    }
+    const int m = mat[eperm ? int64_t(eperm[t]) : t];
+    double c[NT];
+    bool ok = (m >= 0 && m < nmat);
+    if (ok) {
+        double S[NS];
+#pragma unroll
+        for (int i = 0; i < NS; ++i) S[i] = sigma_tensor[int64_t(m) * NS + i];
+        ok = metric_terms_tensor<DIM>(X, S, c);
+    }
+    if (!ok) {
+        atomicOr(errflag, 1);
+#pragma unroll
+        for (int i = 0; i < NT; ++i) c[i] = 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < NT; ++i) C[t * NT + i] = c[i];
+}
+
+void launch_metric_terms_tensor(int dim, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat, const int32_t *eperm,
+                                const double *sigma_tensor, int nmat, double *C, int32_t *errflag, hipStream_t s) {
+    const int grid = int((nt + 255) / 256);
+    if (dim == 2)
+        hipLaunchKernelGGL(k_metric_terms_tensor<2>, dim3(grid), dim3(256), 0, s, nt, coords, conn, mat, eperm, sigma_tensor, nmat, C, errflag);
+    else
+        hipLaunchKernelGGL(k_metric_terms_tensor<3>, dim3(grid), dim3(256), 0, s, nt, coords, conn, mat, eperm, sigma_tensor, nmat, C, errflag);
+}
+
 // ------------------------------------------------------------------------------------------
 // CSR value assembly, gather formulation (a.Assemble(), ngsolve_functions.py:47).
 // One wave owns one row; lane p owns stored entry p of the row and walks the row's incident

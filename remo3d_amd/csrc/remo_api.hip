@@ -99,6 +99,7 @@ struct remo_batch {
     int dim = 0;
     int64_t nv = 0, nt = 0, nbf = 0;
     int n_mat = 0;
+    int sigma_comp = 1;      // doubles per material in d_sigma: 1 = scalar; 3 (2D) / 6 (3D) = upper triangle of a tensor (remo_solve_batch_tensor)
     // points: per chunk [sources..., evals...]
     int n_rhs = 0;
     std::vector<int32_t> src_ptr, eval_ptr;
@@ -429,9 +430,21 @@ void remo_ctx_destroy(remo_ctx_t *ctx) {
 
 const char *remo_last_error(remo_ctx_t *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
+// Symmetric positive definite (leading principal minors > 0) and finite: the upper triangle of one material's tensor.
+static bool tensor_ok(int dim, const double *S) {
+    const int n = (dim == 2) ? 3 : 6;
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(S[i])) return false;
+    if (dim == 2) return S[0] > 0.0 && S[0] * S[2] - S[1] * S[1] > 0.0;
+    const double m2 = S[0] * S[3] - S[1] * S[1];
+    const double m3 = S[0] * (S[3] * S[5] - S[4] * S[4]) - S[1] * (S[1] * S[5] - S[4] * S[2]) + S[2] * (S[1] * S[4] - S[3] * S[2]);
+    return S[0] > 0.0 && m2 > 0.0 && m3 > 0.0 && std::isfinite(m3);
+}
+
+// tensor: sigma holds n_mat upper triangles (remo_solve_batch_tensor) instead of n_mat scalars
 static int batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
                         const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
-                        const double *eval_z, remo_batch_t **out, bool pooled) {
+                        const double *eval_z, remo_batch_t **out, bool pooled, bool tensor = false) {
     if (!ctx) return REMO_ERR_ARG;
     if (!mesh || !sigma || !out || n_mat <= 0 || n_rhs <= 0 || !src_ptr || !eval_ptr)
         return fail(ctx, REMO_ERR_ARG, "null or empty argument");
@@ -448,13 +461,21 @@ static int batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat,
     const int dim = mesh->dim, nb = dim + 1;
     for (int64_t i = 0; i < mesh->n_nodes * dim; ++i)
         if (!std::isfinite(mesh->coords[i])) return fail(ctx, REMO_ERR_MESH, "non-finite coordinate");
-    for (int i = 0; i < n_mat; ++i)
-        if (!(sigma[i] > 0.0) || !std::isfinite(sigma[i])) return fail(ctx, REMO_ERR_ARG, "sigma must be positive and finite");
+    const int ncomp = tensor ? ((dim == 2) ? 3 : 6) : 1;
+    if (tensor) {
+        for (int i = 0; i < n_mat; ++i)
+            if (!tensor_ok(dim, sigma + size_t(i) * ncomp))
+                return fail(ctx, REMO_ERR_ARG, "sigma_tensor of material " + std::to_string(i) + " is not finite and positive definite");
+    } else {
+        for (int i = 0; i < n_mat; ++i)
+            if (!(sigma[i] > 0.0) || !std::isfinite(sigma[i])) return fail(ctx, REMO_ERR_ARG, "sigma must be positive and finite");
+    }
     remo_batch *b = nullptr;
     try {
         HIP_TRY(hipSetDevice(ctx->device));
         b = new remo_batch();
         b->dim = dim; b->nv = mesh->n_nodes; b->nt = mesh->n_elems; b->nbf = mesh->n_bfacets; b->n_mat = n_mat;
+        b->sigma_comp = ncomp;
         b->n_rhs = n_rhs;
         b->src_ptr.assign(src_ptr, src_ptr + n_rhs + 1);
         b->eval_ptr.assign(eval_ptr, eval_ptr + n_rhs + 1);
@@ -466,7 +487,7 @@ static int batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat,
         size_t pool_at = 0;
         if (pooled) {     // one grow-only device buffer per context holds the inputs of the batch in hand
             const size_t need = align_up(sizeof(double) * size_t(b->nv) * dim) + align_up(sizeof(int32_t) * size_t(b->nt) * nb) + align_up(sizeof(int32_t) * size_t(b->nt)) +
-                                align_up(sizeof(double) * size_t(n_mat)) + align_up(sizeof(int32_t) * size_t(b->nbf) * dim + 4) + align_up(size_t(b->nbf) + 4) + 4096;
+                                align_up(sizeof(double) * size_t(n_mat) * ncomp) + align_up(sizeof(int32_t) * size_t(b->nbf) * dim + 4) + align_up(size_t(b->nbf) + 4) + 4096;
             if (need > ctx->in_cap) {
                 HIP_TRY(hipStreamSynchronize(s));
                 if (ctx->in_pool) HIP_TRY(hipFree(ctx->in_pool));
@@ -489,7 +510,7 @@ static int batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat,
         up(&b->d_coords, mesh->coords, size_t(b->nv) * dim);
         up(&b->d_conn, mesh->conn, size_t(b->nt) * nb);
         up(&b->d_mat, mesh->mat, size_t(b->nt));
-        up(&b->d_sigma, sigma, size_t(n_mat));
+        up(&b->d_sigma, sigma, size_t(n_mat) * ncomp);
         up(&b->d_bconn, mesh->bconn, size_t(b->nbf) * dim);
         up(&b->d_bdir, mesh->bdirichlet, size_t(b->nbf));
         HIP_TRY(hipStreamSynchronize(s));
@@ -660,7 +681,10 @@ int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_t *opts_in,
         // ---- assembly ---------------------------------------------------------------------
         const double *d_M = (dim == 2) ? (o.quadrature == 1 ? ctx->d_M2q : ctx->d_M2) : ctx->d_M3;
         b->d_M_last = d_M;
-        launch_metric_terms(dim, nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, b->d_sigma, b->n_mat, d_C, ctx->d_err, s);
+        if (b->sigma_comp > 1)
+            launch_metric_terms_tensor(dim, nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, b->d_sigma, b->n_mat, d_C, ctx->d_err, s);
+        else
+            launch_metric_terms(dim, nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, b->d_sigma, b->n_mat, d_C, ctx->d_err, s);
         int64_t pair_begin = 0, pair_end = 0;   // edge-dof rows: consecutive pairs with identical patterns, values interleaved
         if (sy.nvefree > sy.nvfree && ((sy.nvefree - sy.nvfree) & 1) == 0) { pair_begin = sy.nvfree; pair_end = sy.nvefree; }
         if (lite) {   // values of the P1 block (the generic row walk over the vertex rows: their columns are vertex dofs, other local dofs
@@ -953,19 +977,31 @@ int remo_batch_fetch(remo_ctx_t *ctx, remo_batch_t *b, double *u_out) {
     return REMO_OK;
 }
 
-int remo_solve_batch(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
-                     const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
-                     const double *eval_z, double *u_out, const remo_opts_t *opts, remo_stats_t *stats) {
+static int solve_batch(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
+                       const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                       const double *eval_z, double *u_out, const remo_opts_t *opts, remo_stats_t *stats, bool tensor) {
     if (!ctx) return REMO_ERR_ARG;
     if (u_out && eval_ptr && n_rhs > 0)
         for (int i = 0; i < eval_ptr[n_rhs]; ++i) u_out[i] = std::nan("");
     remo_batch_t *b = nullptr;
-    int rc = batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, &b, true);     // inputs into the context's pool: no hipMalloc / hipFree per batch
+    int rc = batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, &b, true, tensor);     // inputs into the context's pool: no hipMalloc / hipFree per batch
     if (rc != REMO_OK) return rc;
     rc = remo_batch_run(ctx, b, opts, stats);
     if (rc >= 0 && u_out) remo_batch_fetch(ctx, b, u_out);
     remo_batch_destroy(ctx, b);
     return rc;
+}
+
+int remo_solve_batch(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
+                     const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                     const double *eval_z, double *u_out, const remo_opts_t *opts, remo_stats_t *stats) {
+    return solve_batch(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, opts, stats, false);
+}
+
+int remo_solve_batch_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor, int32_t n_rhs,
+                            const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                            const double *eval_z, double *u_out, const remo_opts_t *opts, remo_stats_t *stats) {
+    return solve_batch(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, opts, stats, true);
 }
 
 int remo_batch_eval(remo_ctx_t *ctx, remo_batch_t *b, int32_t rhs, int32_t npts, const double *z, double *u_out) {
@@ -1543,6 +1579,24 @@ int remo_host_element_matrix(int32_t dim, const double *X, double sigma, double 
     } else {
         double C[6];
         if (!metric_terms<3>(X, sigma, C)) return REMO_ERR_MESH;
+        for (int i = 0; i < 20; ++i)
+            for (int j = 0; j < 20; ++j) K_out[i * 20 + j] = kentry<3>(C, M, i, j);
+    }
+    return REMO_OK;
+}
+
+int remo_host_element_matrix_tensor(int32_t dim, const double *X, const double *sigma_tensor, double *K_out) {
+    if ((dim != 2 && dim != 3) || !X || !sigma_tensor || !K_out) return REMO_ERR_ARG;
+    if (!tensor_ok(dim, sigma_tensor)) return REMO_ERR_ARG;
+    const double *M = ref_tables(dim);
+    if (dim == 2) {
+        double C[9];
+        if (!metric_terms_tensor<2>(X, sigma_tensor, C)) return REMO_ERR_MESH;
+        for (int i = 0; i < 10; ++i)
+            for (int j = 0; j < 10; ++j) K_out[i * 10 + j] = kentry<2>(C, M, i, j);
+    } else {
+        double C[6];
+        if (!metric_terms_tensor<3>(X, sigma_tensor, C)) return REMO_ERR_MESH;
         for (int i = 0; i < 20; ++i)
             for (int j = 0; j < 20; ++j) K_out[i * 20 + j] = kentry<3>(C, M, i, j);
     }

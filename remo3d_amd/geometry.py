@@ -135,6 +135,30 @@ def select_data_range(borehole_geometry, formation_parameters, dip, mud_resistiv
     return fg, bh, sigma
 
 
+def ti_conductivity(sigma_h, sigma_v, dip_rad, dim):
+    """[n, dim, dim] conductivity tensors of transversely isotropic materials: Sigma = sigma_h I + (sigma_v - sigma_h) n n^T with
+    n the bedding normal.  3D local frame: the bedding planes are z + x tan(dip) = const (meshgen.layered_material_fn), so
+    n = (sin dip, 0, cos dip); 2D (r, z), dip 0: diag(sigma_h, sigma_v).  A material with sigma_v == sigma_h is exactly sigma_h I."""
+    sh = np.atleast_1d(np.asarray(sigma_h, dtype=float))
+    sv = np.atleast_1d(np.asarray(sigma_v, dtype=float))
+    if sh.shape != sv.shape:
+        raise ValueError("sigma_h and sigma_v differ in length")
+    if dim == 2:
+        if dip_rad != 0:
+            raise ValueError("the axisymmetric (2D) model has no dip")
+        n = np.array([0.0, 1.0])
+    elif dim == 3:
+        n = np.array([np.sin(dip_rad), 0.0, np.cos(dip_rad)])
+    else:
+        raise ValueError("dim must be 2 or 3")
+    P = np.outer(n, n)
+    # sigma_h (I - n n^T) + sigma_v n n^T: the same tensor, with the principal values exact when the normal is a coordinate axis
+    S = sh[:, None, None] * (np.eye(dim) - P) + sv[:, None, None] * P
+    iso = sh == sv
+    S[iso] = sh[iso, None, None] * np.eye(dim)
+    return S
+
+
 # ---------------------------------------------------------------------------------------------
 # Netgen path (2D only): remo3d/netgen_functions.py:12-118
 

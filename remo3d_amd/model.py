@@ -205,7 +205,7 @@ class Model:
 
     def load_formation_parameters(self, formation_model_file):
         data, units = self._read_table(formation_model_file)
-        return self.set_formation_parameters(data, units[:-2])
+        return self.set_formation_parameters(data, units[:3])     # the geometry columns; resistivities (2 or 3 columns) are in ohm m
 
     def set_formation_parameters(self, formation_parameters, formation_units=["M", "M", "M"]):
         fp = np.array(formation_parameters, dtype=float)   # a copy (the reference converts the caller's array in place, remo3d.py:427)
@@ -217,7 +217,27 @@ class Model:
             raise ValueError("Uncorrect formation model geometry")
         if np.nanmin(fp[:, [3, 4]]) <= 0.0:
             raise ValueError("Formation resistivies have to be higher than 0 ohmm")
+        if fp.shape[1] > 6:
+            raise ValueError("Formation model has at most 6 columns: TOP, BOTTOM, RDFZ, RTFZ, RTUZ and RVUZ")
+        if fp.shape[1] == 6:     # RVUZ: vertical resistivity of the undisturbed zone (RTUZ is then the horizontal one); NaN = isotropic
+            rv = fp[:, 5]
+            if np.any(rv[~np.isnan(rv)] <= 0.0):
+                raise ValueError("Vertical resistivities (RVUZ) have to be higher than 0 ohmm")
         return fp
+
+    def _vertical_formation_model(self):
+        """The 5-column formation table with RTUZ replaced by RVUZ (NaN -> RTUZ), or None when the model is isotropic (no RVUZ
+        column, or RVUZ equal to RTUZ wherever it is given).  Windowed like the model itself, it gives the vertical conductivity
+        of every material in the same order (simulate_logs)."""
+        fm = self.formation_model
+        if fm is None or fm.shape[1] < 6:
+            return None
+        rv = np.where(np.isnan(fm[:, 5]), fm[:, 4], fm[:, 5])
+        if np.array_equal(rv, fm[:, 4]):
+            return None
+        fv = np.array(fm[:, :5], copy=True)
+        fv[:, 4] = rv
+        return fv
 
     def load_borehole_parameters(self, borehole_model_file, borehole_geometry_type="diameter"):
         data, units = self._read_table(borehole_model_file)
@@ -364,12 +384,29 @@ class Model:
         t_solve = t_mesh = 0.0
         n_points = 0
 
-        def window(bi):
+        formation_h = self.formation_model[:, :5]
+        formation_v = self._vertical_formation_model()
+
+        def window_of(formation, bi):
             if netgen_path:   # the reference's default 2D windowing (remo3d.py:776-779, worker.py:94)
-                return geometry.select_netgen_data_range(borehole_geometry, self.formation_model, mud[bi], simulation_depths[bi], domain_radius)
+                return geometry.select_netgen_data_range(borehole_geometry, formation, mud[bi], simulation_depths[bi], domain_radius)
             # Gmsh-path windowing (worker.py:84), the only one for dipping models
-            return geometry.select_data_range(borehole_geometry, self.formation_model, self.dip_rad if is3d else 0, mud[bi],
+            return geometry.select_data_range(borehole_geometry, formation, self.dip_rad if is3d else 0, mud[bi],
                                               simulation_depths[bi], domain_radius)
+
+        def window(bi):
+            """(geometry, borehole, sigma): sigma is 1-D as in the reference unless a material of the window is anisotropic; then
+            [n_mat, dim, dim] TI tensors.  The vertical conductivities come from windowing the RVUZ copy of the table the same way,
+            so that every quirk of the windowing (e.g. a dropped flushed zone: the layer takes RTFZ) applies to both alike."""
+            fg, bh, sigma = window_of(formation_h, bi)
+            if formation_v is None:
+                return fg, bh, sigma
+            sigma_v = window_of(formation_v, bi)[2]
+            if len(sigma_v) != len(sigma):
+                raise RuntimeError("windowing of RTUZ and RVUZ gave different materials")
+            if np.array_equal(np.asarray(sigma_v), np.asarray(sigma)):
+                return fg, bh, sigma
+            return fg, bh, geometry.ti_conductivity(sigma, sigma_v, self.dip_rad if is3d else 0.0, dim)
 
         # Which batches this rank takes: its block-cyclic share ("static"), or whatever it draws from the shared counter
         # while it is free ("dynamic", the reference's pull scheduling, remo3d.py:843-860) - sweep.BatchQueue.

@@ -21,8 +21,9 @@ def model_polygons(formation, borehole, dip_deg, depth_lim, rad_lim):
     """(polygons, resistivities): one quadrilateral per layer spanning the picture, sheared by the dip; on top of it the invaded
     zone of a layer that has one (columns of the formation table: top, bottom, invasion radius, flushed-zone and virgin
     resistivity - remo3d.py:344-548); last the borehole between the mirrored caliper curves, coloured by its mean mud resistivity.
-    The first and last layer are extended so that the sheared picture is filled (remo3d.py:1031-1032)."""
-    f = np.array(formation, dtype=float, copy=True)
+    The first and last layer are extended so that the sheared picture is filled (remo3d.py:1031-1032).  An optional sixth column
+    (RVUZ, the vertical resistivity of an anisotropic layer) is not drawn: the virgin zone shows RTUZ."""
+    f = np.array(np.asarray(formation, dtype=float)[:, :5], dtype=float, copy=True)
     slope = np.tan(np.deg2rad(dip_deg))
     f[0, 0] -= slope * rad_lim[1]
     f[-1, 1] += slope * rad_lim[1]

@@ -80,6 +80,23 @@ def _rhs_arrays(sources, evals):
     return src_ptr, cat(sz), cat(sI), eval_ptr, cat(ez)
 
 
+def sigma_table(sigma, dim=None):
+    """(table, tensor?) of a conductivity argument: [n_mat] scalars as they are, or [n_mat, d, d] symmetric tensors (d = 2:
+    (r, z), d = 3: (x, y, z)) as the upper triangles remo_solve_batch_tensor reads ([rr, rz, zz] / [xx, xy, xz, yy, yz, zz])."""
+    sigma = np.asarray(sigma, dtype=np.float64)
+    if sigma.ndim <= 1:
+        return np.ascontiguousarray(sigma), False
+    if sigma.ndim != 3 or sigma.shape[1] != sigma.shape[2] or sigma.shape[1] not in (2, 3):
+        raise ValueError("sigma must be [n_mat] or [n_mat, dim, dim], not {}".format(sigma.shape))
+    d = sigma.shape[1]
+    if dim is not None and d != dim:
+        raise ValueError("conductivity tensors are {0}x{0} but the mesh is {1}D".format(d, dim))
+    if np.all(np.isfinite(sigma)) and np.any(np.abs(sigma - sigma.transpose(0, 2, 1)) > 1e-12 * np.max(np.abs(sigma), initial=0.0)):
+        raise ValueError("conductivity tensors must be symmetric")     # (non-finite entries: the library rejects them, REMO_ERR_ARG)
+    iu = np.triu_indices(d)
+    return np.ascontiguousarray(sigma[:, iu[0], iu[1]]), True
+
+
 class Context:
     """One per GPU (remo_ctx_create)."""
 
@@ -111,17 +128,20 @@ class Context:
         return (self._L.remo_last_error(self._h) or b"").decode()
 
     def solve_batch(self, mesh, sigma, sources, evals, opts: Optional[RemoOpts] = None, raise_on_error=True):
-        """One-shot remo_solve_batch.  Returns (list of per-RHS potential arrays, stats dict, rc)."""
-        sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+        """One-shot remo_solve_batch.  Returns (list of per-RHS potential arrays, stats dict, rc).
+        sigma: [n_mat] conductivities, or [n_mat, dim, dim] symmetric positive definite tensors in the mesh's frame
+        (remo_solve_batch_tensor)."""
+        sigma, tensor = sigma_table(sigma, int(mesh.dim))
         src_ptr, sz, sI, eval_ptr, ez = _rhs_arrays(sources, evals)
         ms, keep = _lib.mesh_struct(mesh)
         out = np.full(int(eval_ptr[-1]), np.nan)
         st = RemoStats()
         o = opts if opts is not None else make_opts()
-        rc = self._L.remo_solve_batch(self._h, C.byref(ms), len(sigma), ptr(sigma, C.c_double), len(sources),
-                                      ptr(src_ptr, C.c_int32), ptr(sz, C.c_double), ptr(sI, C.c_double),
-                                      ptr(eval_ptr, C.c_int32), ptr(ez, C.c_double), ptr(out, C.c_double),
-                                      C.byref(o), C.byref(st))
+        entry = self._L.remo_solve_batch_tensor if tensor else self._L.remo_solve_batch
+        rc = entry(self._h, C.byref(ms), len(sigma), ptr(sigma, C.c_double), len(sources),
+                   ptr(src_ptr, C.c_int32), ptr(sz, C.c_double), ptr(sI, C.c_double),
+                   ptr(eval_ptr, C.c_int32), ptr(ez, C.c_double), ptr(out, C.c_double),
+                   C.byref(o), C.byref(st))
         if rc < 0 and raise_on_error:
             raise RemoError(rc, self.last_error())
         return [out[eval_ptr[k]:eval_ptr[k + 1]] for k in range(len(evals))], st.as_dict(), rc
@@ -136,7 +156,9 @@ class Batch:
     def __init__(self, ctx: Context, mesh, sigma, sources, evals):
         self.ctx = ctx
         self._L = ctx._L
-        sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+        sigma, tensor = sigma_table(sigma)
+        if tensor:
+            raise ValueError("resident batches take scalar conductivities; solve tensors with Context.solve_batch")
         self._arr = _rhs_arrays(sources, evals)
         src_ptr, sz, sI, eval_ptr, ez = self._arr
         ms, keep = _lib.mesh_struct(mesh)
@@ -261,13 +283,18 @@ class Batch:
             pass
 
 
-def host_element_matrix(dim: int, vertex_coords: np.ndarray, sigma: float) -> np.ndarray:
-    """Element matrix from the library's reference tensors (host code path shared with the kernels)."""
+def host_element_matrix(dim: int, vertex_coords: np.ndarray, sigma) -> np.ndarray:
+    """Element matrix from the library's reference tensors (host code path shared with the kernels).
+    sigma: a scalar, or a symmetric dim x dim tensor (remo_host_element_matrix_tensor)."""
     L = _lib.load()
     X = np.ascontiguousarray(vertex_coords, dtype=np.float64)
     n = 10 if dim == 2 else 20
     K = np.zeros((n, n))
-    rc = L.remo_host_element_matrix(dim, ptr(X, C.c_double), float(sigma), ptr(K, C.c_double))
+    if np.ndim(sigma) == 0:
+        rc = L.remo_host_element_matrix(dim, ptr(X, C.c_double), float(sigma), ptr(K, C.c_double))
+    else:
+        S, _ = sigma_table(np.asarray(sigma, dtype=np.float64)[None], dim)
+        rc = L.remo_host_element_matrix_tensor(dim, ptr(X, C.c_double), ptr(S, C.c_double), ptr(K, C.c_double))
     if rc != 0:
         raise RemoError(rc, "remo_host_element_matrix")
     return K
