@@ -187,6 +187,11 @@ int remo_solve_batch_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_
 int remo_batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma,
                       int32_t n_rhs, const int32_t *src_ptr, const double *src_z, const double *src_I,
                       const int32_t *eval_ptr, const double *eval_z, remo_batch_t **out);
+/* The same with the conductivity tensors of remo_solve_batch_tensor (same layout, same checks; added within ABI 7): the
+ * resident form, so that the inspection hooks below see tensor batches too. */
+int remo_batch_create_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor,
+                             int32_t n_rhs, const int32_t *src_ptr, const double *src_z, const double *src_I,
+                             const int32_t *eval_ptr, const double *eval_z, remo_batch_t **out);
 int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *batch, const remo_opts_t *opts, remo_stats_t *stats);
 int remo_batch_fetch(remo_ctx_t *ctx, remo_batch_t *batch, double *u_out);
 void remo_batch_destroy(remo_ctx_t *ctx, remo_batch_t *batch);

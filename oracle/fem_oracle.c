@@ -21,6 +21,8 @@
  *   condensation    : condense=True Schur complement + back-substitution  ngsolve_functions.py:31,53-56
  *   orc_eval        : gfu(mesh(0,z)) / gfu(mesh(0,0,z))           worker.py:124-131
  *   orc_solve_batch : the inner hot loop over the RHS of one batch worker.py:104-131
+ *   orc_create_tensor : orc_create with a full dim x dim conductivity tensor per material (the product's
+ *                     remo_solve_batch_tensor) and, in 2D, a choice of quadrature rule
  *
  * Discretisation: straight-sided simplices, order-3 H1.  The Galerkin solution does not depend
  * on the basis, so a hierarchical basis in barycentric coordinates is used (vertices of every
@@ -36,7 +38,9 @@
  * Element matrices are integrated HERE by numerical quadrature (collapsed Gauss-Legendre,
  * 4 points per direction, exact to total degree 5) on every element — deliberately a different
  * route from the product, which contracts per-element metric terms with pre-integrated
- * reference tensors.
+ * reference tensors.  orc_create_tensor integrates g_i^T S g_j on the same rule; in 2D it can take the
+ * 6-point degree-4 rule of Strang-Fix / Dunavant instead (the product's remo_opts_t.quadrature = 1),
+ * with its points and weights computed here from their closed forms.
  */
 #include <math.h>
 #include <stdint.h>
@@ -66,6 +70,7 @@ typedef struct {
     /* 2D condensation: per element K_ib (9) and K_ii */
     double *kib, *kii;
     double *sigma;
+    double *stens; /* [nmat*dim*dim] full row-major tensors (orc_create_tensor); NULL: scalar sigma */
     int nmat;
     /* quadrature */
     int nq;
@@ -138,6 +143,23 @@ static void gauss_legendre01(int n, double *x, double *w) {
         x[i] = 0.5 * (1.0 - t);
         w[i] = 1.0 / ((1.0 - t * t) * dp * dp); /* = (2/((1-t^2)dp^2))/2 */
     }
+}
+
+/* 6-point rule on the triangle, exact to degree 4 (Strang & Fix; Dunavant 1985, degree 4):
+ * barycentrics (1-2a, a, a) and permutations, a and the weights from their closed forms. */
+static void build_rule4(orc_t *o) {
+    const double s1 = sqrt(38.0 - 44.0 * sqrt(0.4)), s2 = sqrt(213125.0 - 53320.0 * sqrt(10.0));
+    const double a[2] = {(8.0 - sqrt(10.0) + s1) / 18.0, (8.0 - sqrt(10.0) - s1) / 18.0};
+    const double w[2] = {(620.0 + s2) / 3720.0, (620.0 - s2) / 3720.0};
+    o->nq = 6;
+    o->ql = (double *)malloc(sizeof(double) * 6 * 3);
+    o->qw = (double *)malloc(sizeof(double) * 6);
+    for (int g = 0; g < 2; g++)
+        for (int p = 0; p < 3; p++) {
+            int q = 3 * g + p;
+            for (int k = 0; k < 3; k++) o->ql[3 * q + k] = (k == p) ? 1.0 - 2.0 * a[g] : a[g];
+            o->qw[q] = w[g];
+        }
 }
 
 /* Collapsed (Duffy) rule on the unit simplex; weights normalised to sum 1. */
@@ -243,8 +265,48 @@ static double geom(const orc_t *o, long t, double gl[4][3]) {
     return fabs(det) / 6.0;
 }
 
+/* the same with the material's full tensor S: the integrand is wgt * g_i^T S g_j, for every tensor alike */
+static void element_matrix_tensor(const orc_t *o, long t, double *K) {
+    int d = o->dim, nb = d + 1, n = o->nld_full;
+    double gl[4][3];
+    double vol = geom(o, t, gl);
+    const double *S = o->stens + (long)o->mat[t] * d * d;
+    const int *c = o->conn + t * nb;
+    memset(K, 0, sizeof(double) * n * n);
+    double phi[MAXLD], dphi[MAXLD * 4], g[MAXLD][3], h[MAXLD][3];
+    for (int q = 0; q < o->nq; q++) {
+        const double *l = o->ql + q * nb;
+        shape(d, l, phi, dphi);
+        double wgt = o->qw[q] * vol;
+        if (d == 2) {
+            double r = 0;
+            for (int a = 0; a < nb; a++) r += l[a] * o->xyz[2 * c[a]];
+            wgt *= 2.0 * M_PI * r;
+        }
+        for (int i = 0; i < n; i++)
+            for (int k = 0; k < d; k++) {
+                double s = 0;
+                for (int a = 0; a < nb; a++) s += dphi[i * nb + a] * gl[a][k];
+                g[i][k] = s;
+            }
+        for (int i = 0; i < n; i++)
+            for (int k = 0; k < d; k++) {
+                double s = 0;
+                for (int m = 0; m < d; m++) s += S[k * d + m] * g[i][m];
+                h[i][k] = s;
+            }
+        for (int i = 0; i < n; i++)
+            for (int j = 0; j < n; j++) {
+                double s = 0;
+                for (int k = 0; k < d; k++) s += g[i][k] * h[j][k];
+                K[i * n + j] += wgt * s;
+            }
+    }
+}
+
 /* full element matrix (nld_full x nld_full) by quadrature; ngsolve_functions.py:33-36 */
 static void element_matrix(const orc_t *o, long t, double *K) {
+    if (o->stens) { element_matrix_tensor(o, t, K); return; }
     int d = o->dim, nb = d + 1, n = o->nld_full;
     double gl[4][3];
     double vol = geom(o, t, gl);
@@ -277,7 +339,7 @@ void orc_destroy(orc_t *o) {
     if (!o) return;
     free(o->xyz); free(o->conn); free(o->mat); free(o->ekeys); free(o->fkeys); free(o->eldof);
     free(o->freeid); free(o->rowptr); free(o->col); free(o->val); free(o->diag); free(o->kib);
-    free(o->kii); free(o->sigma); free(o->ql); free(o->qw);
+    free(o->kii); free(o->sigma); free(o->stens); free(o->ql); free(o->qw);
     free(o);
 }
 
@@ -289,9 +351,11 @@ static void sort_small(int *a, int n) {
     }
 }
 
-orc_t *orc_create(int dim, long nv, const double *xyz, long nt, const int *conn, const int *mat,
-                  long nbf, const int *bconn, const unsigned char *bdir, int nmat,
-                  const double *sigma, int condense) {
+/* sigma [nmat] scalars, or stens [nmat*dim*dim] full tensors (then sigma is NULL); quadrature 1: 2D 6-point rule */
+static orc_t *create(int dim, long nv, const double *xyz, long nt, const int *conn, const int *mat,
+                     long nbf, const int *bconn, const unsigned char *bdir, int nmat,
+                     const double *sigma, const double *stens, int condense, int quadrature) {
+    if (quadrature != 0 && !(quadrature == 1 && dim == 2)) return NULL;
     orc_t *o = (orc_t *)calloc(1, sizeof(orc_t));
     o->dim = dim; o->nv = nv; o->nt = nt; o->nmat = nmat;
     int nb = dim + 1;
@@ -307,13 +371,18 @@ orc_t *orc_create(int dim, long nv, const double *xyz, long nt, const int *conn,
     memcpy(o->conn, conn, sizeof(int) * nt * nb);
     o->mat = (int *)malloc(sizeof(int) * nt);
     memcpy(o->mat, mat, sizeof(int) * nt);
-    o->sigma = (double *)malloc(sizeof(double) * nmat);
-    memcpy(o->sigma, sigma, sizeof(double) * nmat);
+    if (stens) {
+        o->stens = (double *)malloc(sizeof(double) * nmat * dim * dim);
+        memcpy(o->stens, stens, sizeof(double) * nmat * dim * dim);
+    } else {
+        o->sigma = (double *)malloc(sizeof(double) * nmat);
+        memcpy(o->sigma, sigma, sizeof(double) * nmat);
+    }
     for (long t = 0; t < nt; t++) {
         sort_small(o->conn + t * nb, nb);
         if (o->mat[t] < 0 || o->mat[t] >= nmat) { orc_destroy(o); return NULL; }
     }
-    build_quadrature(o);
+    if (quadrature == 1) build_rule4(o); else build_quadrature(o);
 
     /* edges */
     long nek = nt * o->nel;
@@ -471,6 +540,33 @@ orc_t *orc_create(int dim, long nv, const double *xyz, long nt, const int *conn,
         for (long p = o->rowptr[r]; p < o->rowptr[r + 1]; p++)
             if (o->col[p] == r) o->diag[r] = o->val[p];
     return o;
+}
+
+orc_t *orc_create(int dim, long nv, const double *xyz, long nt, const int *conn, const int *mat,
+                  long nbf, const int *bconn, const unsigned char *bdir, int nmat,
+                  const double *sigma, int condense) {
+    return create(dim, nv, xyz, nt, conn, mat, nbf, bconn, bdir, nmat, sigma, NULL, condense, 0);
+}
+
+/* sigma_tensor[nmat * dim * dim]: per material the FULL dim x dim conductivity tensor, row-major, in the mesh's frame
+ * (2D: (r, z)).  quadrature: 0 = the collapsed Gauss rule of orc_create, 1 = the 6-point degree-4 rule (2D only). */
+orc_t *orc_create_tensor(int dim, long nv, const double *xyz, long nt, const int *conn, const int *mat,
+                         long nbf, const int *bconn, const unsigned char *bdir, int nmat,
+                         const double *sigma_tensor, int condense, int quadrature) {
+    return create(dim, nv, xyz, nt, conn, mat, nbf, bconn, bdir, nmat, NULL, sigma_tensor, condense, quadrature);
+}
+
+/* points (barycentrics [nq][dim+1]) and weights (sum 1) of the element rule: returns nq (-1: no such rule); l, w may be NULL */
+int orc_quadrature(int dim, int quadrature, double *l, double *w) {
+    if ((dim != 2 && dim != 3) || (quadrature != 0 && !(quadrature == 1 && dim == 2))) return -1;
+    orc_t q;
+    memset(&q, 0, sizeof(q));
+    q.dim = dim;
+    if (quadrature == 1) build_rule4(&q); else build_quadrature(&q);
+    if (l) memcpy(l, q.ql, sizeof(double) * q.nq * (dim + 1));
+    if (w) memcpy(w, q.qw, sizeof(double) * q.nq);
+    free(q.ql); free(q.qw);
+    return q.nq;
 }
 
 void orc_sizes(const orc_t *o, long *out /* [8] */) {

@@ -31,6 +31,10 @@ def lib():
         dp, ip, lp, bp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_ubyte)
         L.orc_create.restype = C.c_void_p
         L.orc_create.argtypes = [C.c_int, C.c_long, dp, C.c_long, ip, ip, C.c_long, ip, bp, C.c_int, dp, C.c_int]
+        L.orc_create_tensor.restype = C.c_void_p
+        L.orc_create_tensor.argtypes = [C.c_int, C.c_long, dp, C.c_long, ip, ip, C.c_long, ip, bp, C.c_int, dp, C.c_int, C.c_int]
+        L.orc_quadrature.restype = C.c_int
+        L.orc_quadrature.argtypes = [C.c_int, C.c_int, dp, dp]
         L.orc_destroy.argtypes = [C.c_void_p]
         L.orc_sizes.argtypes = [C.c_void_p, lp]
         L.orc_get_csr.argtypes = [C.c_void_p, lp, ip, dp]
@@ -66,14 +70,42 @@ def _mesh_args(mesh):
     return args, keep
 
 
-class Oracle:
-    """Assembled system for one mesh / sigma (orc_create)."""
+QUADRATURES = {"exact": 0, "degree4": 1}
 
-    def __init__(self, mesh, sigma, condense=True):
+
+def quadrature(dim, rule="exact"):
+    """(barycentrics [nq, dim + 1], weights [nq] summing to 1) of the oracle's element rule."""
+    q = QUADRATURES[rule]
+    n = lib().orc_quadrature(dim, q, None, None)
+    if n < 0:
+        raise ValueError("no {} rule in {}D".format(rule, dim))
+    l = np.zeros((n, dim + 1)); w = np.zeros(n)
+    lib().orc_quadrature(dim, q, _p(l, C.c_double), _p(w, C.c_double))
+    return l, w
+
+
+class Oracle:
+    """Assembled system for one mesh / sigma (orc_create).
+    sigma: [n_mat] scalars, or [n_mat, dim, dim] full conductivity tensors in the mesh's frame (orc_create_tensor, every tensor
+    integrated as g_i^T S g_j).  quadrature: "exact" (the collapsed Gauss rule, exact for the degree-5 integrand) or, in 2D,
+    "degree4" (the 6-point rule of remo_opts_t.quadrature = 1); a scalar sigma with "degree4" goes in as sigma I."""
+
+    def __init__(self, mesh, sigma, condense=True, quadrature="exact"):
         L = lib()
+        if quadrature not in QUADRATURES:
+            raise ValueError("quadrature must be 'exact' or 'degree4'")
         sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+        d = int(mesh.dim)
+        if sigma.ndim == 1 and quadrature != "exact":
+            sigma = np.ascontiguousarray(sigma[:, None, None] * np.eye(d))
         args, self._keep = _mesh_args(mesh)
-        self._h = L.orc_create(*args, len(sigma), _p(sigma, C.c_double), int(bool(condense)))
+        self._sigma = sigma
+        if sigma.ndim == 1:
+            self._h = L.orc_create(*args, len(sigma), _p(sigma, C.c_double), int(bool(condense)))
+        else:
+            if sigma.shape[1:] != (d, d):
+                raise ValueError("conductivity tensors must be [n_mat, {0}, {0}], not {1}".format(d, sigma.shape))
+            self._h = L.orc_create_tensor(*args, len(sigma), _p(sigma, C.c_double), int(bool(condense)), QUADRATURES[quadrature])
         if not self._h:
             raise RuntimeError("orc_create failed")
         s = np.zeros(8, dtype=np.int64)

@@ -50,7 +50,7 @@ class RemoStats(C.Structure):
 
 # include/remo3d_hip.h: the drop-in boundary + inspection hooks of the parity tests
 EXPORTS = ["remo_abi_version", "remo_opts_default", "remo_ctx_create", "remo_ctx_destroy", "remo_last_error",
-           "remo_solve_batch", "remo_solve_batch_tensor", "remo_batch_create", "remo_batch_run", "remo_batch_fetch", "remo_batch_destroy",
+           "remo_solve_batch", "remo_solve_batch_tensor", "remo_batch_create", "remo_batch_create_tensor", "remo_batch_run", "remo_batch_fetch", "remo_batch_destroy",
            "remo_batch_eval", "remo_batch_get_system", "remo_batch_get_vectors", "remo_batch_apply_coarse", "remo_batch_spmv",
            "remo_host_element_matrix", "remo_host_element_matrix_tensor", "remo_host_factor_error", "remo_host_symbolic"]
 # include/remo3d_hip_debug.h: probes and tuning knobs (tests, tools, bench.py's `box` record) - not part of the boundary
@@ -84,6 +84,8 @@ def load():
     L.remo_solve_batch_tensor.argtypes = batch_args + [dp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]
     L.remo_batch_create.restype = C.c_int
     L.remo_batch_create.argtypes = batch_args + [C.POINTER(vp)]
+    L.remo_batch_create_tensor.restype = C.c_int
+    L.remo_batch_create_tensor.argtypes = batch_args + [C.POINTER(vp)]
     L.remo_batch_run.restype = C.c_int
     L.remo_batch_run.argtypes = [vp, vp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]
     L.remo_batch_fetch.restype = C.c_int

@@ -529,6 +529,12 @@ int remo_batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, c
     return batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, out, false);
 }
 
+int remo_batch_create_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor, int32_t n_rhs,
+                             const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                             const double *eval_z, remo_batch_t **out) {
+    return batch_create(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, out, false, true);
+}
+
 void remo_batch_destroy(remo_ctx_t *ctx, remo_batch_t *b) {
     if (!b) return;
     if (ctx) (void)hipSetDevice(ctx->device);

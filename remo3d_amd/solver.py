@@ -151,21 +151,21 @@ class Context:
 
 
 class Batch:
-    """Resident batch (remo_batch_create / run / fetch)."""
+    """Resident batch (remo_batch_create / run / fetch).  sigma: [n_mat] conductivities, or [n_mat, dim, dim] symmetric positive
+    definite tensors (remo_batch_create_tensor), as for Context.solve_batch."""
 
     def __init__(self, ctx: Context, mesh, sigma, sources, evals):
         self.ctx = ctx
         self._L = ctx._L
-        sigma, tensor = sigma_table(sigma)
-        if tensor:
-            raise ValueError("resident batches take scalar conductivities; solve tensors with Context.solve_batch")
+        sigma, tensor = sigma_table(sigma, int(mesh.dim))
         self._arr = _rhs_arrays(sources, evals)
         src_ptr, sz, sI, eval_ptr, ez = self._arr
         ms, keep = _lib.mesh_struct(mesh)
         h = C.c_void_p()
-        rc = self._L.remo_batch_create(ctx._h, C.byref(ms), len(sigma), ptr(sigma, C.c_double), len(sources),
-                                       ptr(src_ptr, C.c_int32), ptr(sz, C.c_double), ptr(sI, C.c_double),
-                                       ptr(eval_ptr, C.c_int32), ptr(ez, C.c_double), C.byref(h))
+        create = self._L.remo_batch_create_tensor if tensor else self._L.remo_batch_create
+        rc = create(ctx._h, C.byref(ms), len(sigma), ptr(sigma, C.c_double), len(sources),
+                    ptr(src_ptr, C.c_int32), ptr(sz, C.c_double), ptr(sI, C.c_double),
+                    ptr(eval_ptr, C.c_int32), ptr(ez, C.c_double), C.byref(h))
         if rc != 0:
             raise RemoError(rc, ctx.last_error())
         self._h = h
