@@ -62,7 +62,9 @@ int remo_debug_grid_barrier(remo_ctx_t *ctx, int32_t nblocks, int32_t nbar, doub
  *   25  0 = x += alpha p formed by the update launch instead of the direction launch of the step (bit-identical x);
  *   29  0 = the update launch fetches four slab slots for every row and weights the ones the row does not have by zero;
  *   30  0 = the direction launch takes a k-wide row per lane instead of walking its vectors as flat arrays, 16 bytes per lane;
- *   31  0 = the update launch takes a k-wide row per lane instead of 64 rows per wave with a value per lane and pass (fp64 storage).
+ *   31  0 = the update launch takes a k-wide row per lane instead of 64 rows per wave with a value per lane and pass (fp64 storage);
+ *   39  0 = one-shot fp64 solves (remo_solve_batch[_tensor]) carry the whole solution block instead of only the values the
+ *       evaluation points read (default 1; bit-identical potentials on the CSR product).  Resident batches always keep the whole x.
  *
  * (b) ONLY IN A LIBRARY BUILT WITH -DREMO_PROBES (`make -C remo3d_amd/csrc probes` -> libremo3d_hip_probes.so, loaded by the tools
  * through REMO_LIB=...): rejected experiments and ablations, some of which give WRONG RESULTS ON PURPOSE.  The product ignores them:

@@ -64,7 +64,13 @@ template <class T> struct PcgBuffersT {
     // patch operator, with defer_q: the patches add their <p, A p> into kPqBins rows of part_pq themselves (atomic adds; two sets of
     // rows taken in turn by step parity, the update launch of a step clears the set of the next) - no launch that folds them
     bool pq_bins = false;
-    PcgProgress *progress;  // mapped host records [progress_len]: one per step, the last one is the "all columns frozen" record
+    // evaluated values only (one-shot fp64 solves, x = nullptr, x_in_direction): x_ev[j] carries x[x_ev_at[j]] (x_ev_at[j] = row * k +
+    // column, or -1: nothing), formed by the update launch with the direction launch's arithmetic, so it holds the bits the full
+    // x would.  The direction launch then neither reads nor writes x: two vectors of its ~five per step.  [x_ev_n]
+    const int64_t *x_ev_at = nullptr;
+    T *x_ev = nullptr;
+    int x_ev_n = 0;
+    PcgProgress *progress; // mapped host records [progress_len]: one per step, the last one is the "all columns frozen" record
     int progress_len;
     int nb_spmv, nb_vec;    // grid sizes actually used (partials valid for these many blocks)
 };
@@ -216,8 +222,12 @@ void launch_point_shapes(int dim, int npts, const double *pz, const int32_t *fou
 void launch_build_rhs(int dim, bool condense, int npts, const int32_t *pt_rhs, const double *pt_I,
                       const int32_t *found, const double *phi, const int32_t *eldof, const double *C,
                       const double *M, int k, double *f, double *fint, hipStream_t s);
+// x_ev != nullptr: the values of x that point q reads are x_ev[q * N + i] (PcgBuffersT::x_ev, laid out by launch_eval_slots)
 void launch_eval(int dim, bool condense, int npts, const int32_t *pt_rhs, const double *pt_I, const int32_t *found,
                  const double *phi, const int32_t *eldof, const double *C, const double *M, int k,
-                 const double *x, const double *fint, double *out, hipStream_t s);
+                 const double *x, const double *fint, double *out, hipStream_t s, const double *x_ev = nullptr);
+// at[q * N + i] = row * k + pt_rhs[q] of local dof i of point q's element (N = 20 in 3D, 10 in 2D), -1 where k_eval reads no x
+void launch_eval_slots(int dim, bool condense, int npts, const int32_t *pt_rhs, const int32_t *found, const int32_t *eldof, int k,
+                       int64_t *at, hipStream_t s);
 
 }  // namespace remo

@@ -704,6 +704,12 @@ template <class T> struct QViewT {
     const int32_t *row4 = nullptr;   // PatchTables::row4 (tile form)
     uint64_t slab_bytes = 0;   // != 0 (slab below 4 GB): the slots a row does not have are not fetched at all (buffer loads, offset out of range)
 };
+// x_ev[j] += alpha p[at[j]] (PcgBuffersT::x_ev): the values of x the evaluation points read, formed by the update launch
+template <class T> struct EvSlotsT {
+    const int64_t *at = nullptr;
+    T *x = nullptr;
+    int n = 0;
+};
 template <class T> struct FoldArgsT {
     int nb_flat = 0;             // workgroups [0, nb_flat) do the flat update of the rows >= nv, the rest the vertex rows
     const int32_t *rowptr = nullptr, *col = nullptr;
@@ -733,7 +739,7 @@ __global__ void __launch_bounds__(256) k_pcg_init(int64_t n, ChebArgsT<T> ch, co
         for (int c = 0; c < K; ++c) {
             const T ri = f[i * K + c];
             const T zi = d * ri;
-            x[i * K + c] = T(0);
+            if (x) x[i * K + c] = T(0);   // (evaluated values only: x_ev is cleared by the host)
             r[i * K + c] = ri;
             p[i * K + c] = coarse ? T(0) : zi;
             rz[c] += coarse ? 0.0 : double(ri) * double(zi);   // the vertex block's share comes from the Chebyshev kernels
@@ -749,7 +755,8 @@ __global__ void __launch_bounds__(256) k_pcg_update(int64_t n, int step, double 
                                                     double *__restrict__ part_rz_next, double *__restrict__ rz0,
                                                     PcgProgress *progress, int progress_len, const T *__restrict__ p,
                                                     const T *__restrict__ q, T *__restrict__ x, T *__restrict__ r,
-                                                    const T *__restrict__ dinv, FoldArgsT<T> fold, QViewT<T> qv, double *__restrict__ clear_bins = nullptr) {
+                                                    const T *__restrict__ dinv, FoldArgsT<T> fold, QViewT<T> qv, double *__restrict__ clear_bins = nullptr,
+                                                    EvSlotsT<T> ev = EvSlotsT<T>()) {
     // scal = rz0[8] | pq[8] | rz of even steps[8] | rz of odd steps[8]: totals forwarded between launches
     // by workgroup 0, so every launch re-reduces only the ONE partial array that is new to it
     __shared__ double smem[16 * 3 * K];
@@ -788,6 +795,18 @@ __global__ void __launch_bounds__(256) k_pcg_update(int64_t n, int step, double 
     }
     if (clear_bins) {     // the patch operator's <p, A p> bins of the NEXT step (PcgBuffersT::pq_bins): this launch is the last reader of that set
         for (int i = int(blockIdx.x) * int(blockDim.x) + int(threadIdx.x); i < kPqBins * K; i += int(gridDim.x) * int(blockDim.x)) clear_bins[i] = 0.0;
+    }
+    // the values of x the evaluation points read (a few thousand, PcgBuffersT::x_ev): p is not written before the direction launch,
+    // so this is x += alpha p of the step with the operands and the expression of k_pcg_direction
+    for (int j = int(blockIdx.x) * int(blockDim.x) + int(threadIdx.x); j < ev.n; j += int(gridDim.x) * int(blockDim.x)) {
+        const int64_t at = ev.at[j];
+        if (at < 0) continue;
+        const int col = int(at % K);
+        double a = 0.0;
+#pragma unroll
+        for (int c = 0; c < K; ++c) a = (c == col) ? alpha[c] : a;
+        const T xv = ev.x[j], pv = p[at];
+        ev.x[j] = xv + T(a) * pv;
     }
     if (x_only) {   // residual replacement step (mixed precision): r and the <Cr,r> partials come from k_mixed_replace
         for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) {
@@ -1845,7 +1864,8 @@ template <class T> void launch_pcg_update(const CsrViewT<T> &A, int k, int step,
     const double *pq_rows = bins ? b.part_pq + (step & 1) * (kPqBins * 8) : b.part_pq;
     double *pq_clear = bins ? b.part_pq + ((step + 1) & 1) * (kPqBins * 8) : nullptr;
     REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_update<T, KK>), dim3(grid), dim3(256), 0, s, n, step, tol2, 0, bins ? kPqBins : b.nb_spmv, nb_rz(b), ch, pq_rows, cur, nxt,
-                                        b.rz0, b.progress, b.progress_len, b.p, b.q, b.x, b.r, b.dinv, fold, qv, pq_clear));
+                                        b.rz0, b.progress, b.progress_len, b.p, b.q, b.x, b.r, b.dinv, fold, qv, pq_clear,
+                                        EvSlotsT<T>{b.x_ev_at, b.x_ev, b.x_ev_n}));
     launch_cheb(A, k, step, b, nxt, s, folded);
 }
 
@@ -2098,7 +2118,7 @@ template <int DIM, bool CONDENSE>
 __global__ void k_eval(int npts, const int32_t *__restrict__ pt_rhs, const double *__restrict__ pt_I,
                        const int32_t *__restrict__ found, const double *__restrict__ phi, const int32_t *__restrict__ eldof,
                        const double *__restrict__ C, const double *__restrict__ M, int k, const double *__restrict__ x,
-                       const double *__restrict__ fint, double *__restrict__ out) {
+                       const double *__restrict__ fint, double *__restrict__ out, const double *__restrict__ x_ev) {
     constexpr int N = P3<DIM>::NLD, NT = P3<DIM>::NTERM, NK = CONDENSE ? 9 : N;
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= npts) return;
@@ -2106,10 +2126,11 @@ __global__ void k_eval(int npts, const int32_t *__restrict__ pt_rhs, const doubl
     if (t == INT_MAX) { out[q] = nan(""); return; }
     const int c = pt_rhs[q];
     const int32_t *ed = eldof + int64_t(t) * N;
+    auto xval = [&](int i, int32_t row) { return x_ev ? x_ev[q * N + i] : x[int64_t(row) * k + c]; };
     double s = 0.0;
     for (int i = 0; i < NK; ++i) {
         const int32_t row = ed[i];
-        if (row >= 0) s += phi[q * N + i] * x[int64_t(row) * k + c];
+        if (row >= 0) s += phi[q * N + i] * xval(i, row);
     }
     if (CONDENSE) {
         const double pb = phi[q * N + 9];
@@ -2120,7 +2141,7 @@ __global__ void k_eval(int npts, const int32_t *__restrict__ pt_rhs, const doubl
                 if (pt_I[w] != 0.0 && found[w] == t && pt_rhs[w] == c) acc += fint[w];
             for (int j = 0; j < 9; ++j) {
                 const int32_t row = ed[j];
-                if (row >= 0) acc -= kentry<DIM>(ce, M, 9, j) * x[int64_t(row) * k + c];
+                if (row >= 0) acc -= kentry<DIM>(ce, M, 9, j) * xval(j, row);
             }
             s += pb * acc / kentry<DIM>(ce, M, 9, 9);
         }
@@ -2130,14 +2151,43 @@ __global__ void k_eval(int npts, const int32_t *__restrict__ pt_rhs, const doubl
 
 void launch_eval(int dim, bool condense, int npts, const int32_t *pt_rhs, const double *pt_I, const int32_t *found, const double *phi,
                  const int32_t *eldof, const double *C, const double *M, int k, const double *x, const double *fint, double *out,
-                 hipStream_t s) {
+                 hipStream_t s, const double *x_ev) {
     const int grid = (npts + 63) / 64;
     if (dim == 3)
-        hipLaunchKernelGGL((k_eval<3, false>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, x, fint, out);
+        hipLaunchKernelGGL((k_eval<3, false>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, x, fint, out, x_ev);
     else if (condense)
-        hipLaunchKernelGGL((k_eval<2, true>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, x, fint, out);
+        hipLaunchKernelGGL((k_eval<2, true>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, x, fint, out, x_ev);
     else
-        hipLaunchKernelGGL((k_eval<2, false>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, x, fint, out);
+        hipLaunchKernelGGL((k_eval<2, false>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, x, fint, out, x_ev);
+}
+
+// The entries of x that k_eval reads, one slot per (point, local dof): the slot of a row that several points read is repeated, and
+// every copy is formed by the same operations on the same operands (k_pcg_update), so each holds the bits of the full x
+template <int DIM>
+__global__ void k_eval_slots(int npts, int nk, const int32_t *__restrict__ pt_rhs, const int32_t *__restrict__ found,
+                             const int32_t *__restrict__ eldof, int k, int64_t *__restrict__ at) {
+    constexpr int N = P3<DIM>::NLD;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= npts * N) return;
+    const int q = j / N, i = j - q * N;
+    const int32_t t = found[q];
+    int64_t a = -1;
+    if (t != INT_MAX && i < nk) {
+        const int32_t row = eldof[int64_t(t) * N + i];
+        if (row >= 0) a = int64_t(row) * k + pt_rhs[q];
+    }
+    at[j] = a;
+}
+
+void launch_eval_slots(int dim, bool condense, int npts, const int32_t *pt_rhs, const int32_t *found, const int32_t *eldof, int k,
+                       int64_t *at, hipStream_t s) {
+    const int N = (dim == 3) ? 20 : 10, nk = (dim == 2 && condense) ? 9 : N;
+    const int grid = (npts * N + 255) / 256;
+    if (grid == 0) return;
+    if (dim == 3)
+        hipLaunchKernelGGL(k_eval_slots<3>, dim3(grid), dim3(256), 0, s, npts, nk, pt_rhs, found, eldof, k, at);
+    else
+        hipLaunchKernelGGL(k_eval_slots<2>, dim3(grid), dim3(256), 0, s, npts, nk, pt_rhs, found, eldof, k, at);
 }
 
 }  // namespace remo

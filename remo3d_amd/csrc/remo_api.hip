@@ -109,6 +109,7 @@ struct remo_batch {
     int32_t *d_mat = nullptr, *d_conn = nullptr, *d_bconn = nullptr;
     uint8_t *d_bdir = nullptr;
     bool pooled = false;     // the six arrays live in the context's input pool (remo_solve_batch): not freed with the batch
+    bool eval_only = false;  // remo_solve_batch: nothing reads the solution after the run but the evaluation points (PcgBuffersT::x_ev)
     // last system (pointers into the context arena; valid until the next run on the context)
     bool has_system = false;
     DeviceSymbolic sym;
@@ -153,6 +154,7 @@ int g_chain32 = 1;   // key 15: 1 = fp32 Chebyshev chain inside fp64 solves abov
 int g_ell = 1;        // key 24: 1 = the Chebyshev launches of 3D read the fixed-width image of the vertex block (default), 0 = its CSR form
 int g_dot_bins = 1;   // key 28: 1 = the patches add their <p, A p> straight into the update launch's rows (default), 0 = a row per patch + k_patch_dot
 int g_x_in_direction = 1;   // key 25: 1 = x += alpha p formed by the direction launch of the step (default), 0 = by the update launch
+int g_x_ev = 1;      // key 39: 1 = one-shot fp64 solves carry only the values of x the evaluation points read (default), 0 = the whole x
 int g_defer_q = 1;    // key 22: 1 = the PCG's update launch sums the patch operator's shared rows itself (default), 0 = k_patch_reduce does
 #ifdef REMO_PROBES
 int g_extra_apply = 0; // key 36 (probe builds): extra operator applications (apply + shared-row sums, results discarded) per PCG step: what a step with more applications would cost
@@ -568,6 +570,9 @@ int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_t *opts_in,
         const int dim = b->dim, N = (dim == 2) ? 10 : 20, NT = (dim == 2) ? 9 : 6;
         const int64_t nt = b->nt, nv = b->nv;
         const int kmax = std::min<int>(b->n_rhs, REMO_MAX_RHS);
+        // one-shot fp64 solve: no x, only the values the evaluation points read (PcgBuffersT::x_ev); the debug forms of the update
+        // (key 25 = 0 writes x there) and the mixed mode's refinement (x64 += x32) need the whole block
+        const bool x_ev_only = b->eval_only && g_x_ev && g_x_in_direction && o.precision == 0;
 
         // ---- points of all RHS, chunk by chunk: [sources..., evals...] -------------------
         std::vector<double> pz, pI;
@@ -597,6 +602,10 @@ int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_t *opts_in,
         const bool want_patch = dim == 3 && (o.op == 3 || o.op == 0);
         if (want_patch) need += patch_arena_bytes(nt, ndof_max, kmax) + (size_t(nt) * 21 + 64) * size_t(kmax) * 8;   // tables + slab (upper bound: a row per element dof, and every patch's block padded to 16 rows)
         need += size_t(kMaxPartialBlocks) * 8 * 8 * 3 + size_t(npts) * (N + 8) * 8 + (1 << 20);
+        if (x_ev_only) {   // slots + values instead of x
+            need -= size_t(ndof_max) * 8 * size_t(kmax);
+            need += size_t(npts + 1) * N * 16;
+        }
         need += size_t(nv + 64) * 200 * 20 + size_t(nv + 64) * 8;   // squared vertex block (paired Chebyshev steps)
         need += size_t(nv + 64) * kCompactPerRow * 16 + size_t(nv + 64) * 8;   // compact vertex block (+ its fp32 values)
         need += size_t(nv + 64) * kEllWidth * 12 + size_t(nv + 64) * 8;        // its fixed-width image
@@ -628,7 +637,8 @@ int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_t *opts_in,
         double *d_dinv = ctx->take<double>(n);
         double *d_f = ctx->take<double>(n * kmax);
         PcgBuffers buf{};
-        buf.x = ctx->take<double>(n * kmax); buf.r = ctx->take<double>(n * kmax);
+        buf.x = x_ev_only ? nullptr : ctx->take<double>(n * kmax);
+        buf.r = ctx->take<double>(n * kmax);
         buf.p = ctx->take<double>(n * kmax); buf.q = ctx->take<double>(n * kmax);
         buf.dinv = d_dinv;
         buf.part_pq = ctx->take<double>(kMaxPartialBlocks * 8);
@@ -663,6 +673,8 @@ int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_t *opts_in,
         double *d_pz = ctx->take<double>(npts + 1), *d_pI = ctx->take<double>(npts + 1);
         int32_t *d_prhs = ctx->take<int32_t>(npts + 1), *d_found = ctx->take<int32_t>(npts + 1);
         double *d_phi = ctx->take<double>(size_t(npts + 1) * N), *d_fint = ctx->take<double>(npts + 1), *d_out = ctx->take<double>(npts + 1);
+        int64_t *d_ev_at = x_ev_only ? ctx->take<int64_t>(size_t(npts + 1) * N) : nullptr;
+        double *d_x_ev = x_ev_only ? ctx->take<double>(size_t(npts + 1) * N) : nullptr;
         ctx->ensure_progress(o.maxsteps + 3);
         buf.progress = ctx->progress_dev;
         buf.progress_len = ctx->progress_len;
@@ -908,12 +920,17 @@ int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_t *opts_in,
             if (nq > 0)
                 launch_build_rhs(dim, sy.condense, nq, d_prhs + q0, d_pI + q0, d_found + q0, d_phi + size_t(q0) * N, sy.eldof, d_C, d_M, k,
                                  d_f, d_fint + q0, s);
+            if (x_ev_only) {   // the slots of this chunk's points (k and the columns change with the chunk)
+                launch_eval_slots(dim, sy.condense, nq, d_prhs + q0, d_found + q0, sy.eldof, k, d_ev_at, s);
+                if (nq > 0) HIP_TRY(hipMemsetAsync(d_x_ev, 0, sizeof(double) * size_t(nq) * N, s));
+                buf.x_ev_at = d_ev_at; buf.x_ev = d_x_ev; buf.x_ev_n = nq * N;
+            }
             HIP_TRY(hipEventRecord(ctx->ev[5], s));
             ChunkResult cr = mixed ? run_pcg_mixed(ctx, b->A, k, d_f, buf, mx, o, st, ev_used) : run_pcg(ctx, b->A, k, d_f, buf, o, st, ev_used);
             HIP_TRY(hipEventRecord(ctx->ev[6], s));
             if (nq > 0)
                 launch_eval(dim, sy.condense, nq, d_prhs + q0, d_pI + q0, d_found + q0, d_phi + size_t(q0) * N, sy.eldof, d_C, d_M, k, buf.x,
-                            d_fint + q0, d_out + q0, s);
+                            d_fint + q0, d_out + q0, s, buf.x_ev);
             HIP_TRY(hipEventRecord(ctx->ev[7], s));
             if (nq > 0) HIP_TRY(hipMemcpyAsync(h_out.data() + q0, d_out + q0, sizeof(double) * nq, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
@@ -992,6 +1009,7 @@ static int solve_batch(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, 
     remo_batch_t *b = nullptr;
     int rc = batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, &b, true, tensor);     // inputs into the context's pool: no hipMalloc / hipFree per batch
     if (rc != REMO_OK) return rc;
+    b->eval_only = true;
     rc = remo_batch_run(ctx, b, opts, stats);
     if (rc >= 0 && u_out) remo_batch_fetch(ctx, b, u_out);
     remo_batch_destroy(ctx, b);
@@ -1545,6 +1563,7 @@ int remo_debug_tune(int32_t key, int32_t value) {
         case 30: set_flat_direction(value); return 0;   // direction launch: flat arrays, 16 bytes per lane / a k-wide row per lane
         case 29: set_slab_masked(value); return 0;      // slab slots a row does not have: not fetched / fetched and weighted by zero
         case 25: g_x_in_direction = value; return 0;    // x += alpha p in the direction / in the update launch
+        case 39: g_x_ev = value; return 0;              // one-shot solves: only the values of x the evaluation points read / the whole x
         case 22: g_defer_q = value; return 0;           // shared rows summed by k_patch_reduce / by the update launch
         case 24: g_ell = value; return 0;               // fixed-width image of the vertex block
         default: break;
