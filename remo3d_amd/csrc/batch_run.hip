@@ -1,0 +1,717 @@
+// batch_run.hip — remo_batch_run: the host orchestration of one batch (numbering -> upload -> assembly -> multi-RHS PCG ->
+// evaluation) as a list of stages.  The orchestration mirrors the inner loop of remo3d/workers/worker.py:100-134 with one
+// difference the reference leaves on the table: the matrix of a batch is assembled once and all its
+// right-hand sides are solved together.
+//
+// The context's arena is a bump allocator: the addresses of a batch follow from the ORDER of the ctx->take calls (and of
+// build_patch_tables / amg_setup / amg_to_float, which take from it too).  The stages below keep one order; arena_estimate names
+// the buffers term by term so that the two can be compared by eye.
+#include <limits.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+
+#include "pcg_host.h"
+#include "patch.h"
+
+using namespace remo;
+
+namespace {
+
+std::mutex g_solve_mutex;   // remo_opts_t.serialize_solves
+constexpr int64_t kCompactPerRow = 48;   // capacity of the compact copy per vertex (3D P1 rows hold ~15 entries; a copy that does not fit is not used)
+
+// the handles every stage reads
+struct Run {
+    remo_ctx *ctx;
+    remo_batch *b;
+    const remo_opts_t &o;
+    remo_stats_t *st;
+    hipStream_t s;
+    int dim, N, NT;   // local dofs and metric terms per element
+};
+
+// ---- options ----------------------------------------------------------------------------------------------------------------
+int checked_opts(remo_ctx *ctx, const remo_opts_t *opts_in, remo_opts_t &o) {
+    if (opts_in) o = *opts_in; else remo_opts_default(&o);
+    if (o.maxsteps <= 0 || !(o.rtol > 0.0)) return fail(ctx, REMO_ERR_ARG, "maxsteps and rtol must be positive");
+    if (o.coarse < 0 || o.coarse > 3) return fail(ctx, REMO_ERR_ARG, "remo_opts_t.coarse must be 0 (by dimension), 1 (polynomial), 2 (multigrid cycle) or 3 (cycle, else polynomial)");
+    if (o.op != 0 && o.op != 2 && o.op != 3)
+        return fail(ctx, REMO_ERR_ARG, "remo_opts_t.op must be 0 (default), 2 (CSR product) or 3 (patch operator); 1, the round-2 element-wise operator, left the library with ABI 7");
+    return REMO_OK;
+}
+
+// ---- points of all RHS, chunk by chunk: [sources..., evals...] --------------------------------------------------------------
+struct Points {
+    std::vector<double> z, I;
+    std::vector<int32_t> rhs, chunk_begin, eval_slot;   // eval_slot: u_out index or -1
+    std::vector<int32_t> found_init;                    // INT_MAX per point: what launch_locate starts from
+    int n() const { return int(z.size()); }
+};
+
+Points gather_points(const remo_batch *b) {
+    Points p;
+    for (int c0 = 0; c0 < b->n_rhs; c0 += REMO_MAX_RHS) {
+        p.chunk_begin.push_back(int32_t(p.z.size()));
+        const int c1 = std::min(b->n_rhs, c0 + REMO_MAX_RHS);
+        for (int r = c0; r < c1; ++r)
+            for (int q = b->src_ptr[r]; q < b->src_ptr[r + 1]; ++q) {
+                p.z.push_back(b->src_z[q]); p.I.push_back(b->src_I[q]); p.rhs.push_back(r - c0); p.eval_slot.push_back(-1);
+            }
+        for (int r = c0; r < c1; ++r)
+            for (int q = b->eval_ptr[r]; q < b->eval_ptr[r + 1]; ++q) {
+                p.z.push_back(b->eval_z[q]); p.I.push_back(0.0); p.rhs.push_back(r - c0); p.eval_slot.push_back(q);
+            }
+    }
+    p.chunk_begin.push_back(int32_t(p.z.size()));
+    p.found_init.assign(p.z.size(), INT_MAX);
+    return p;
+}
+
+// ---- what the batch will build, and the arena it needs ------------------------------------------------------------------------
+struct Plan {
+    int kmax = 0;                       // right-hand sides per chunk
+    bool x_ev_only = false;             // no x, only the values the evaluation points read (PcgBuffersT::x_ev)
+    bool want_patch = false, want_amg = false;
+    int64_t vertex_block_above = -1;    // build_symbolic_gpu: element count above which only the P1 block gets a pattern
+    size_t arena_bytes = 0;
+};
+
+// Upper bounds of everything the stages take, in the order they take it.  (Generous in places - e.g. the squared, compact and
+// fixed-width images are never all built for one batch - and meant to stay as it is: reserve() only ever grows the arena.)
+size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, int npts) {
+    const int dim = b->dim, N = (dim == 2) ? 10 : 20, NT = (dim == 2) ? 9 : 6;
+    const int64_t nt = b->nt, nv = b->nv;
+    const size_t kmax = size_t(p.kmax);
+    const int64_t ndof_max = nv + (dim == 2 ? 7 : 16) * nt, nnz_max = nt * int64_t(N) * N;
+    size_t need = symbolic_gpu_arena_bytes(dim, nv, nt, b->nbf);    // numbering: DeviceSymbolic and its scratch
+    need += size_t(nt) * NT * 8;                                     // d_C
+    need += size_t(nnz_max) * 8;                                     // d_val
+    need += size_t(ndof_max) * 8 * (1 + 5 * kmax);                   // d_dinv; d_f, x, r, p, q
+    need += size_t(nv + 64) * 8 * 4 * kmax;                          // cz, cres, cd[0], cd[1]
+    if (p.want_patch)   // tables + slab (upper bound: a row per element dof, and every patch's block padded to 16 rows)
+        need += patch_arena_bytes(nt, ndof_max, p.kmax) + (size_t(nt) * 21 + 64) * kmax * 8;
+    need += size_t(kMaxPartialBlocks) * 8 * 8 * 3;                   // part_pq, part_rz (rz0, d_bound and the flags ride on the slack below)
+    need += size_t(npts) * (N + 8) * 8;                              // d_pz, d_pI, d_prhs, d_found, d_phi, d_fint, d_out
+    need += (1 << 20);                                               // alignment of every take + the small buffers
+    if (p.x_ev_only) {   // slots + values instead of x
+        need -= size_t(ndof_max) * 8 * kmax;                         // x, one of the five vectors above
+        need += size_t(npts + 1) * N * 16;                           // d_ev_at, d_x_ev
+    }
+    need += size_t(nv + 64) * 200 * 20 + size_t(nv + 64) * 8;        // squared vertex block (paired Chebyshev steps): sq_col, sq_a, sq_b; sq_rowptr
+    need += size_t(nv + 64) * kCompactPerRow * 16 + size_t(nv + 64) * 8;   // compact vertex block (+ its fp32 values): vb_col, vb_val, c32_val / vb32; vb_rowptr
+    need += size_t(nv + 64) * kEllWidth * 12 + size_t(nv + 64) * 8;  // its fixed-width image: ell_col, ell_val (or c32_ell_val); ell_tail
+    need += size_t(nv + 64) * (4 * 4 * kmax + 8);                    // fp32 Chebyshev chain of the fp64 solve: c32_z, c32_res, c32_d[0], c32_d[1]; c32_dinv
+    if (p.want_amg) need += size_t(nv + 64) * (dim == 2 ? 1536 : 3072) * 2 + (1 << 20);   // multigrid hierarchy of the vertex block + its scratch (amg_setup, amg_to_float)
+    if (o.precision == 1) {   // fp32 copies of the matrix values and of every PCG vector (mixed_buffers)
+        need += size_t(nv + 64) * 200 * 8;                           // fp32 sq_a, sq_b
+        need += size_t(nnz_max) * 4;                                 // v32
+        need += size_t(ndof_max) * 4 * (1 + 5 * kmax);               // dinv32; x, r, p, q, f32
+        need += size_t(nv + 64) * 4 * 4 * kmax + (1 << 16);          // cz, cres, cd[0], cd[1]
+    }
+    return need;
+}
+
+Plan plan_batch(const remo_batch *b, const remo_opts_t &o, int npts) {
+    Plan p;
+    const int dim = b->dim;
+    p.kmax = std::min<int>(b->n_rhs, REMO_MAX_RHS);
+    // one-shot fp64 solve: no x, only the values the evaluation points read (PcgBuffersT::x_ev); the debug forms of the update
+    // (key 25 = 0 writes x there) and the mixed mode's refinement (x64 += x32) need the whole block
+    p.x_ev_only = b->eval_only && g_tune.x_ev && g_tune.x_in_direction && o.precision == 0;
+    // the patch operator is 3D only; a 2D batch always runs on the CSR product, whatever `op` says
+    p.want_patch = dim == 3 && (o.op == 3 || o.op == 0);
+    p.want_amg = o.preconditioner != 0 && g_tune.amg != 1 &&
+                 (g_tune.amg == 2 || o.coarse == 2 || o.coarse == 3 || (o.coarse == 0 && dim == 2 && o.coarse_degree <= 0));   // coarse = 0: an explicit degree asks for the polynomial
+    // patch operator batches above 200 k tetrahedra (assemble = 2: any size) number only the P1 block of the matrix
+    p.vertex_block_above = (p.want_patch && o.assemble != 1) ? (o.assemble == 2 ? 0 : 200000) : -1;
+    p.arena_bytes = arena_estimate(b, o, p, npts);
+    return p;
+}
+
+// ---- dof numbering + CSR pattern (device) --------------------------------------------------------------------------------------
+int number_dofs(const Run &r, const Plan &plan, double t_start) {
+    remo_batch *b = r.b;
+    remo_stats_t *st = r.st;
+    std::string err;
+    DeviceSymbolic &sy = b->sym;
+    int rc = build_symbolic_gpu(r.ctx->ar, r.s, r.dim, b->nv, b->nt, b->d_conn, b->nbf, b->d_bconn, b->d_bdir, r.o.condense != 0, r.ctx->d_err, sy, err,
+                                plan.vertex_block_above);
+    if (rc != REMO_OK) return fail(r.ctx, rc, err);
+    st->ms_symbolic = now_ms() - t_start;
+    st->n_dof = sy.ndof; st->n_free = sy.nfree; st->nnz = sy.vertex_block_only ? 0 : sy.nnz; st->n_edges = sy.ne; st->n_faces = sy.nf;
+    st->n_rhs = b->n_rhs;
+    return REMO_OK;
+}
+
+// ---- the system: metric terms, matrix values, Jacobi factors, load vectors -----------------------------------------------------
+struct System {
+    int64_t n = 0;            // free dofs
+    bool lite = false;        // only the P1 block has a pattern: the operator is the patch operator
+    double *d_C = nullptr, *d_val = nullptr, *d_dinv = nullptr, *d_f = nullptr;
+    const double *d_M = nullptr;              // reference tensors (remo_opts_t.quadrature)
+    int64_t pair_begin = 0, pair_end = 0;     // edge-dof rows: consecutive pairs with identical patterns, values interleaved
+    CsrView view(const DeviceSymbolic &sy) const { return CsrView{n, sy.nnz, sy.rowptr, sy.col, d_val}; }
+};
+
+System take_system(const Run &r, const Plan &plan) {
+    const DeviceSymbolic &sy = r.b->sym;
+    System sys;
+    sys.n = sy.nfree;
+    sys.lite = sy.vertex_block_only;
+    sys.d_C = r.ctx->take<double>(r.b->nt * r.NT);
+    sys.d_val = r.ctx->take<double>(sy.nnz + 2);   // + 16 bytes: the SpMM reads single rows' values as 16-byte pairs (CsrViewT)
+    sys.d_dinv = r.ctx->take<double>(sys.n);
+    sys.d_f = r.ctx->take<double>(sys.n * plan.kmax);
+    return sys;
+}
+
+void assemble_system(const Run &r, System &sys) {
+    remo_batch *b = r.b;
+    const DeviceSymbolic &sy = b->sym;
+    const int dim = r.dim;
+    sys.d_M = (dim == 2) ? (r.o.quadrature == 1 ? r.ctx->d_M2q : r.ctx->d_M2) : r.ctx->d_M3;
+    b->d_M_last = sys.d_M;
+    if (b->sigma_comp > 1)
+        launch_metric_terms_tensor(dim, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, b->d_sigma, b->n_mat, sys.d_C, r.ctx->d_err, r.s);
+    else
+        launch_metric_terms(dim, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, b->d_sigma, b->n_mat, sys.d_C, r.ctx->d_err, r.s);
+    if (sys.lite) {   // values of the P1 block (the generic row walk over the vertex rows: their columns are vertex dofs, other local dofs
+                      // of an element fall behind the row's last column and are dropped) + the Jacobi factors of every other row
+        launch_assemble(dim, sy.condense, sy.nvfree, 0, 0, sy.rowptr, sy.col, sy.adjptr, sy.adj, sy.eldof, sys.d_C, sys.d_M, sys.d_val, sys.d_dinv, r.s);
+        launch_diag_rows(dim, sy.nvfree, sys.n, sy.adjptr, sy.adj, sys.d_C, sys.d_M, sys.d_dinv, r.s);
+    } else {
+        if (sy.nvefree > sy.nvfree && ((sy.nvefree - sy.nvfree) & 1) == 0) { sys.pair_begin = sy.nvfree; sys.pair_end = sy.nvefree; }
+        launch_assemble(dim, sy.condense, sys.n, sys.pair_begin, sys.pair_end, sy.rowptr, sy.col, sy.adjptr, sy.adj, sy.eldof, sys.d_C, sys.d_M, sys.d_val,
+                        sys.d_dinv, r.s);
+    }
+}
+
+// ---- the solve's buffers and its preconditioner's shape ------------------------------------------------------------------------
+struct ChebDefaults { int degree; double ratio; };
+
+// Degree of the Chebyshev polynomial on the vertex block and the ratio lmax / lmin of its interval, from GPU scans
+// (tools/scan_coarse2d.py, scan_coarse3d.py).
+ChebDefaults cheb_defaults(int dim, int64_t nvfree) {
+    // 3D: the best degree / interval grow with the
+    // vertex count (kappa of the P1 block ~ nv^(2/3), degree ~ sqrt(kappa)): (5, 90) at 12.6 k vertices, (8-10, 150-200) at
+    // 24 k, (12-16, 300-600) at 80 k; fine scan after the first / last step lost their launches (tools/scan_coarse3d_fine.py):
+    // (5, 70-90) at 12.8 k, (8, 120-160) at 27 k (7: +3 %, 9: +4.5 %).  2D (launch-bound steps, paired Chebyshev launches): (16, 600).
+    const double nv_rel = double(nvfree > 0 ? nvfree : 1) / 12600.0;
+    // 2D, round 2 (tools/run_2d_batches.py at the 80 k vertices of config 2 with the 0.35 default mesh scale): (16, 600) 173 ms per four
+    // batches, (24, 1200) 162, (32, 2400) 155, 752 / 561 / 446 steps - the product of degree and steps grows slowly, a launch pair costs
+    // 14 us; (16, 600) was the optimum at 25 k vertices: degree ~ sqrt(vertices), ratio ~ vertices, even degrees (paired launches).
+    // The paired (root-product) form must stay in fp64: in fp32 storage it needs MORE steps at degree 16 and breaks down above.
+    const double nv2 = double(nvfree > 0 ? nvfree : 1) / 25000.0;
+    const int deg2 = 2 * int(std::min(16.0, std::max(8.0, std::floor(8.0 * std::sqrt(nv2) + 0.5))));
+    // round 3, size L with the patch operator (83 k vertices, tools/scan_coarse3d_fine.py L, profiles/r03_scan_coarse_L.log): steps per
+    // four batches 675 / 637 / 638 / 630 / 601 at degrees 11 / 12 / 13 / 14 / 16 - an odd degree above 7 buys nothing over the even one
+    // below it (M: 8 best, 7 and 9 worse) - solve 300 / 289 / 295 / 297 / 294 ms: even degrees from 8 up
+    int deg3 = int(std::min(16.0, std::max(5.0, std::floor(5.0 * std::sqrt(nv_rel) + 0.9))));
+    if (deg3 > 8) deg3 &= ~1;
+    if (dim == 3) return {deg3, std::min(1200.0, std::max(60.0, 90.0 * std::pow(nv_rel, 2.0 / 3.0)))};
+    return {deg2, std::min(2400.0, std::max(600.0, 600.0 * nv2 * 1.25))};
+}
+
+struct Solve {
+    PcgBuffers buf{};
+    bool two_level = false;                  // vertex-block solver + Jacobi (remo_opts_t.preconditioner), else Jacobi alone
+    size_t nc = 0;                           // length of the vertex block's vectors
+    double ratio_default = 0.0;              // cheb_defaults of this batch
+    unsigned long long *d_bound = nullptr;   // spectrum bound of the vertex block (vertex_block_enqueue; taken here: its place in the arena)
+};
+
+void take_pcg_buffers(const Run &r, const Plan &plan, const System &sys, Solve &sv) {
+    remo_ctx *ctx = r.ctx;
+    const DeviceSymbolic &sy = r.b->sym;
+    const int64_t n = sys.n;
+    const int kmax = plan.kmax;
+    PcgBuffers &buf = sv.buf;
+    buf.x = plan.x_ev_only ? nullptr : ctx->take<double>(n * kmax);
+    buf.r = ctx->take<double>(n * kmax);
+    buf.p = ctx->take<double>(n * kmax); buf.q = ctx->take<double>(n * kmax);
+    buf.dinv = sys.d_dinv;
+    buf.part_pq = ctx->take<double>(kMaxPartialBlocks * 8);
+    buf.part_rz = ctx->take<double>(kMaxPartialBlocks * 8 * 2);
+    buf.rz0 = ctx->take<double>(kScalarSlots);
+    sv.two_level = (r.o.preconditioner != 0) && sy.nvfree > 0;
+    buf.nv_coarse = sv.two_level ? sy.nvfree : 0;
+    const ChebDefaults cd = cheb_defaults(r.dim, sy.nvfree);
+    sv.ratio_default = cd.ratio;
+    buf.cheb_degree = sv.two_level ? (r.o.coarse_degree > 0 ? r.o.coarse_degree : cd.degree) : 0;
+    buf.cheb_lmax = buf.cheb_lmin = 0.0;
+    sv.nc = size_t(buf.nv_coarse) * kmax + 2;
+    buf.cz = ctx->take<double>(sv.nc); buf.cres = ctx->take<double>(sv.nc);
+    buf.cd[0] = ctx->take<double>(sv.nc); buf.cd[1] = ctx->take<double>(sv.nc);
+    sv.d_bound = ctx->take<unsigned long long>(2);
+}
+
+// progress records of the PCG and the event pool of remo_opts_t.time_kernels (host objects of the context, grown on demand)
+void prepare_progress(const Run &r, PcgBuffers &buf) {
+    remo_ctx *ctx = r.ctx;
+    ctx->ensure_progress(r.o.maxsteps + 3);
+    buf.progress = ctx->progress_dev;
+    buf.progress_len = ctx->progress_len;
+    if (r.o.time_kernels && ctx->spmv_ev.size() < 8192) {
+        const size_t old = ctx->spmv_ev.size();
+        ctx->spmv_ev.resize(8192);
+        for (size_t i = old; i < ctx->spmv_ev.size(); ++i) HIP_TRY(hipEventCreate(&ctx->spmv_ev[i]));
+    }
+}
+
+// ---- the points on the device: upload, location, shape values ------------------------------------------------------------------
+struct DevicePoints {
+    int npts = 0;
+    double *d_pz = nullptr, *d_pI = nullptr;
+    int32_t *d_prhs = nullptr, *d_found = nullptr;
+    double *d_phi = nullptr, *d_fint = nullptr, *d_out = nullptr;
+    int64_t *d_ev_at = nullptr;   // x_ev_only: slots and values of the solution the points read
+    double *d_x_ev = nullptr;
+};
+
+DevicePoints take_points(const Run &r, const Plan &plan, int npts) {
+    remo_ctx *ctx = r.ctx;
+    DevicePoints p;
+    p.npts = npts;
+    p.d_pz = ctx->take<double>(npts + 1); p.d_pI = ctx->take<double>(npts + 1);
+    p.d_prhs = ctx->take<int32_t>(npts + 1); p.d_found = ctx->take<int32_t>(npts + 1);
+    p.d_phi = ctx->take<double>(size_t(npts + 1) * r.N); p.d_fint = ctx->take<double>(npts + 1); p.d_out = ctx->take<double>(npts + 1);
+    p.d_ev_at = plan.x_ev_only ? ctx->take<int64_t>(size_t(npts + 1) * r.N) : nullptr;
+    p.d_x_ev = plan.x_ev_only ? ctx->take<double>(size_t(npts + 1) * r.N) : nullptr;
+    return p;
+}
+
+void upload_points(const Run &r, const Points &pts, const DevicePoints &dp) {
+    const int npts = dp.npts;
+    HIP_TRY(hipMemsetAsync(r.ctx->d_err, 0, sizeof(int32_t), r.s));
+    if (npts > 0) {
+        HIP_TRY(hipMemcpyAsync(dp.d_pz, pts.z.data(), sizeof(double) * npts, hipMemcpyHostToDevice, r.s));
+        HIP_TRY(hipMemcpyAsync(dp.d_pI, pts.I.data(), sizeof(double) * npts, hipMemcpyHostToDevice, r.s));
+        HIP_TRY(hipMemcpyAsync(dp.d_prhs, pts.rhs.data(), sizeof(int32_t) * npts, hipMemcpyHostToDevice, r.s));
+        HIP_TRY(hipMemcpyAsync(dp.d_found, pts.found_init.data(), sizeof(int32_t) * npts, hipMemcpyHostToDevice, r.s));
+    }
+}
+
+// point location + shapes (all points at once)
+void locate_points(const Run &r, const DevicePoints &dp) {
+    const remo_batch *b = r.b;
+    const DeviceSymbolic &sy = b->sym;
+    if (dp.npts <= 0) return;
+    for (int q0 = 0; q0 < dp.npts; q0 += kMaxPoints)
+        launch_locate(r.dim, b->nt, b->d_coords, sy.conn, std::min(kMaxPoints, dp.npts - q0), dp.d_pz + q0, dp.d_found + q0, r.s);
+    launch_point_shapes(r.dim, dp.npts, dp.d_pz, dp.d_found, b->d_coords, sy.conn, dp.d_phi, r.ctx->d_err, r.s);
+}
+
+// ---- images of the vertex block for the preconditioner, and the patch tables ---------------------------------------------------
+// Everything that is enqueued before the batch's one synchronisation, with the small results it reads back.  The read-backs land
+// in this struct: it must stay where it is between vertex_block_enqueue and the synchronisation.
+struct VertexBlock {
+    bool want_square = false, want_compact = false;
+    int32_t h_err = 0;                  // ctx->d_err: 1 = mesh / material, 2 = point
+    unsigned long long h_bound = 0;     // bits of the spectrum bound
+    int32_t h_sq[2] = {1, 0};           // squared block: overflow flag, entries
+    int32_t h_vb[2] = {1, 0};           // compact block: overflow flag, entries
+    int32_t h_patch[3] = {1, 0, 0};     // patch tables: overflow flag, largest patch, slab slots
+    int32_t *sq_rowptr = nullptr, *sq_col = nullptr;
+    double *sq_a = nullptr, *sq_b = nullptr;
+    int32_t *vb_rowptr = nullptr, *vb_col = nullptr;
+    double *vb_val = nullptr;
+    PatchTables ptab{};
+    bool amg32_ready = false;
+    VertexBlock() = default;
+    VertexBlock(const VertexBlock &) = delete;
+};
+
+void vertex_block_enqueue(const Run &r, const Plan &plan, const System &sys, const Solve &sv, VertexBlock &vb) {
+    remo_ctx *ctx = r.ctx;
+    hipStream_t s = r.s;
+    const DeviceSymbolic &sy = r.b->sym;
+    const PcgBuffers &buf = sv.buf;
+    const CsrView A = sys.view(sy);
+    // paired steps pay off where B stays small: 2D (~19 entries per row: 81 vs 93 us per PCG step); in 3D B has ~65
+    // entries per row and three launches on it cost more than six on A_vv (153 vs 149 us) - forced by tune value 2
+    vb.want_square = sv.two_level && !plan.want_amg && (buf.cheb_degree % 2 == 0) && ((g_tune.square == 1 && r.dim == 2) || g_tune.square == 2);
+    // compact copy of the vertex block for the Chebyshev launches (remo_debug_tune key 13: 0 = read A in place)
+    // measured in the bench (--tune 13=0 against 13=1, one box): 538.9 -> 516.1 ms solve per step at 83 k vertices; at 12.8 k the
+    // launches are latency, not bytes (714 -> 710 ms) and building the copy costs what it saves: larger blocks only (2 forces it)
+    vb.want_compact = !sys.lite && sv.two_level && !vb.want_square && (g_tune.compact == 2 || (g_tune.compact == 1 && buf.nv_coarse > 16384));
+    if (sv.two_level) {  // spectrum bound of the Jacobi-scaled vertex block for the Chebyshev interval
+        HIP_TRY(hipMemsetAsync(sv.d_bound, 0, sizeof(unsigned long long), s));
+        launch_vblock_bound(buf.nv_coarse, A, sys.d_dinv, sv.d_bound, s);
+        HIP_TRY(hipMemcpyAsync(&vb.h_bound, sv.d_bound, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    }
+    if (vb.want_square) {   // B = A_vv D^-1 A_vv for the paired Chebyshev steps (kernels.hip)
+        const int64_t nvc = buf.nv_coarse, cap = nvc * 200;
+        vb.sq_rowptr = ctx->take<int32_t>(size_t(nvc) + 2);
+        vb.sq_col = ctx->take<int32_t>(size_t(cap));
+        vb.sq_a = ctx->take<double>(size_t(cap)); vb.sq_b = ctx->take<double>(size_t(cap));
+        int32_t *d_sqflag = ctx->take<int32_t>(1);
+        HIP_TRY(hipMemsetAsync(d_sqflag, 0, sizeof(int32_t), s));
+        launch_vblock_square(nvc, A, sys.d_dinv, vb.sq_rowptr, vb.sq_col, vb.sq_a, vb.sq_b, cap, d_sqflag, s);
+        HIP_TRY(hipMemcpyAsync(&vb.h_sq[0], d_sqflag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&vb.h_sq[1], vb.sq_rowptr + nvc, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    if (vb.want_compact) {
+        const int64_t nvc = buf.nv_coarse, cap = (nvc + 64) * kCompactPerRow;
+        vb.vb_rowptr = ctx->take<int32_t>(size_t(nvc) + 2);
+        vb.vb_col = ctx->take<int32_t>(size_t(cap));
+        vb.vb_val = ctx->take<double>(size_t(cap));
+        int32_t *d_vbflag = ctx->take<int32_t>(1);
+        HIP_TRY(hipMemsetAsync(d_vbflag, 0, sizeof(int32_t), s));
+        launch_vblock_compact(nvc, A, vb.vb_rowptr, vb.vb_col, vb.vb_val, cap, d_vbflag, s);
+        HIP_TRY(hipMemcpyAsync(&vb.h_vb[0], d_vbflag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&vb.h_vb[1], vb.vb_rowptr + nvc, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    // patch operator (patch.hip): its tables are built beside the assembly; their overflow flag and largest patch come
+    // back with the other small read-backs
+    if (plan.want_patch) {
+        int32_t *d_pflag = ctx->take<int32_t>(4);
+        build_patch_tables(ctx->ar, s, sy, sys.d_C, plan.kmax, vb.ptab, d_pflag);
+        HIP_TRY(hipMemcpyAsync(vb.h_patch, d_pflag, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipMemcpyAsync(&vb.h_err, ctx->d_err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+}
+
+// After the synchronisation: which images the solve uses (buf), and the ones that are built from the accepted ones.
+int vertex_block_accept(const Run &r, const Plan &plan, const System &sys, Solve &sv, VertexBlock &vb) {
+    remo_ctx *ctx = r.ctx;
+    remo_batch *b = r.b;
+    hipStream_t s = r.s;
+    const remo_opts_t &o = r.o;
+    const DeviceSymbolic &sy = b->sym;
+    PcgBuffers &buf = sv.buf;
+    const int kmax = plan.kmax;
+    if (vb.want_compact && vb.h_vb[0] == 0 && vb.h_vb[1] > 0) { buf.vb_rowptr = vb.vb_rowptr; buf.vb_col = vb.vb_col; buf.vb_val = vb.vb_val; }
+    if (sys.lite && sv.two_level) { buf.vb_rowptr = sy.rowptr; buf.vb_col = sy.col; buf.vb_val = sys.d_val; vb.h_vb[0] = 0; vb.h_vb[1] = int32_t(sy.nnz); }   // the assembled block IS the compact vertex block
+    // fp32 Chebyshev chain inside the fp64 solve (remo_debug_tune key 15: 0 = off): where the chain's launches are HBM streams
+    // (no folded first step: more than 32 k vertex rows) and the compact block exists
+    if (g_tune.chain32 && o.precision == 0 && buf.vb_rowptr && (buf.nv_coarse > 32768 || g_tune.chain32 == 2)) {   // 2: forced (tests)
+        float *v32c = ctx->take<float>(size_t(vb.h_vb[1]) + 4), *d32c = ctx->take<float>(size_t(buf.nv_coarse) + 4);
+        launch_to_float(vb.h_vb[1], buf.vb_val, v32c, s);
+        launch_to_float(buf.nv_coarse, sys.d_dinv, d32c, s);
+        buf.c32_val = v32c; buf.c32_dinv = d32c;
+        buf.c32_z = ctx->take<float>(sv.nc); buf.c32_res = ctx->take<float>(sv.nc);
+        buf.c32_d[0] = ctx->take<float>(sv.nc); buf.c32_d[1] = ctx->take<float>(sv.nc);
+    }
+    // fixed-width image of the vertex block for the polynomial's launches (kernels.hip k_vblock_ell; remo_debug_tune key 24: 0 = off)
+    if (g_tune.ell && sv.two_level && !plan.want_amg && !vb.want_square && r.dim == 3) {
+        const int64_t nvc = buf.nv_coarse;
+        const bool from_block = buf.vb_rowptr != nullptr;
+        int32_t *ell_col = ctx->take<int32_t>(size_t(nvc) * kEllWidth + 8);
+        int32_t *ell_tail = ctx->take<int32_t>(size_t(nvc) * 2 + 8);
+        double *e64 = (o.precision == 0 && !buf.c32_val) ? ctx->take<double>(size_t(nvc) * kEllWidth + 8) : nullptr;
+        float *e32 = (o.precision != 0 || buf.c32_val) ? ctx->take<float>(size_t(nvc) * kEllWidth + 8) : nullptr;
+        launch_vblock_ell(nvc, from_block ? buf.vb_rowptr : sy.rowptr, from_block ? buf.vb_col : sy.col, from_block ? buf.vb_val : sys.d_val,
+                          ell_col, ell_tail, e64, e32, s);
+        buf.ell_col = ell_col; buf.ell_tail = ell_tail; buf.ell_val = e64; buf.c32_ell_val = e32;
+    }
+    if (sv.two_level && plan.want_amg) {   // multigrid cycle on the vertex block instead of the polynomial (amg.hip)
+        std::string why;
+        if (amg_setup(ctx->ar, s, r.dim, buf.nv_coarse, sy.rowptr, sy.col, sys.d_val, kmax, b->amg64, why)) buf.amg = &b->amg64;
+        else if (o.coarse == 2 || g_tune.amg == 2) return fail(ctx, REMO_ERR_NUMERIC, "multigrid hierarchy of the vertex block: " + why);
+    }
+    if (buf.amg && (o.precision == 1 || g_tune.amg32)) {   // fp32 image of the hierarchy: the mixed mode's inner solver, or the cycle of an fp64 solve
+        amg_to_float(ctx->ar, s, b->amg64, kmax, b->amg32);
+        vb.amg32_ready = true;
+        if (o.precision == 0) buf.amg32 = &b->amg32;
+    }
+    r.st->coarse_used = !sv.two_level ? 0 : (buf.amg ? 2 : 1);
+    if (sv.two_level) {
+        double lmax;
+        std::memcpy(&lmax, &vb.h_bound, sizeof lmax);
+        if (!(lmax > 0.0) || !std::isfinite(lmax)) return fail(ctx, REMO_ERR_NUMERIC, "vertex block has no positive spectrum bound");
+        buf.cheb_lmax = lmax;
+        buf.cheb_lmin = lmax / (o.coarse_ratio > 0 ? double(o.coarse_ratio) : sv.ratio_default);
+    }
+    if (vb.want_square && vb.h_sq[0] == 0) {   // otherwise (a vertex of very high valence) the one-step launches stay
+        buf.sq_rowptr = vb.sq_rowptr; buf.sq_col = vb.sq_col; buf.sq_a = vb.sq_a; buf.sq_b = vb.sq_b;
+        const double avg = double(vb.h_sq[1]) / double(buf.nv_coarse > 0 ? buf.nv_coarse : 1);
+        buf.sq_lanes = g_tune.sq_lanes ? g_tune.sq_lanes : (avg > 40.0 ? 32 : (avg > 24.0 ? 16 : 8));   // 2D rows of B hold ~19 entries: 8 lanes (two passes in flight) 145 vs 150 ms with 16
+    }
+    return REMO_OK;
+}
+
+// ---- the operator: patch operator or CSR product --------------------------------------------------------------------------------
+// Leaves the system on the batch (b->A and the pointers the inspection entries read).
+int choose_operator(const Run &r, const Plan &plan, const System &sys, const Solve &sv, VertexBlock &vb, bool &patch_op) {
+    remo_ctx *ctx = r.ctx;
+    remo_batch *b = r.b;
+    const DeviceSymbolic &sy = b->sym;
+    const int64_t n = sys.n, nt = b->nt;
+    const int kmax = plan.kmax;
+    PatchTables &ptab = vb.ptab;
+    const int32_t *h_patch = vb.h_patch;
+    b->A = sys.view(sy);
+    b->A.pair_begin = sys.pair_begin; b->A.pair_end = sys.pair_end;
+    b->A.vertex_block_only = sys.lite;
+    // (the patch kernel's buffer descriptors address the slab and x with 32-bit byte offsets: beyond 4 GB the CSR product stays)
+    // (all_slab, the product's form: every patch addresses its own block of the slab through a descriptor of its own - only x is bound by this)
+    const bool slab_fits = (ptab.all_slab || uint64_t(nt) * 20 * uint64_t(kmax) * 8 < 0xFFFFF000ull) && uint64_t(n) * uint64_t(kmax) * 8 < 0xFFFFF000ull;
+    // patch operator: asked for, or (op = 0) whenever its tables fit; a patch with more distinct rows than the tables hold
+    // (an element list without locality) sends op = 0 on to the CSR product and fails op = 3
+    // (the kernel forms byte offsets of rows and slab slots with 24-bit multiplies and 32-bit buffer offsets)
+    const size_t patch_lds = ptab.block > 0 ? patch_lds_bytes(h_patch[1], kmax, ptab.block, ptab.all_slab != 0) : 0;   // what k_patch_apply asks for (kernels.hip patch_applies)
+    const bool patch_ok = plan.want_patch && h_patch[0] == 0 && h_patch[1] > 0 && slab_fits && n < (int64_t(1) << 24) && h_patch[2] < (ptab.all_slab ? 0x7FFFFFF0 : (1 << 24)) && patch_lds <= kPatchLdsLimit;
+    if (sys.lite && !patch_ok) return fail(ctx, REMO_ERR_ARG, "only the P1 block was assembled but the patch operator cannot run on this batch: rerun with remo_opts_t.assemble = 1");
+    if (r.o.op == 3 && r.dim == 3 && !patch_ok) return fail(ctx, REMO_ERR_ARG, "patch operator: a patch of the element list touches more distinct rows than its tables hold (or the mesh is too large)");
+    patch_op = patch_ok;
+    r.st->op_used = patch_op ? 3 : 0;
+    r.st->assembled = sys.lite ? 2 : 1;
+    if (patch_op) {
+        ptab.nslot_cap = h_patch[2] > 0 ? h_patch[2] : 1;     // the slab holds the slots in use
+        b->patch64 = PatchOpT<double>{ptab, ctx->take<double>(size_t(ptab.nslot_cap) * size_t(kmax) + 8), ctx->take<double>(size_t(ptab.npatch) * 8 + 8), h_patch[1]};
+        b->A.patch = &b->patch64;
+    }
+    b->d_val = sys.d_val;
+    b->d_dinv = sys.d_dinv;
+    b->d_x = sv.buf.x;
+    b->d_f = sys.d_f;
+    b->d_C = sys.d_C;
+    b->k_last = 0;
+    b->has_system = true;
+    return REMO_OK;
+}
+
+// grids of the PCG's launches and the forms of its update / direction launches
+void set_launch_shape(const Run &r, const System &sys, bool patch_op, PcgBuffers &buf) {
+    remo_batch *b = r.b;
+    const int lpr = choose_lanes_per_row(sys.n, b->sym.nnz);
+    buf.nb_spmv = spmv_grid(sys.n, lpr);
+    buf.nb_vec = vec_grid(sys.n);
+    buf.defer_q = patch_op && g_tune.defer_q && !pcg_update_folds(buf);     // the update launch sums the shared rows of q = A p itself
+    buf.x_in_direction = g_tune.x_in_direction != 0;
+    buf.pq_bins = buf.defer_q && g_tune.dot_bins != 0;
+    if (patch_op) b->patch64.dot_bins = buf.pq_bins;
+}
+
+// ---- mixed precision: the same solve in fp32 storage ----------------------------------------------------------------------------
+// Derived from the fp64 description: what does not depend on the storage type is copied, the fp32 vectors are taken from the arena
+// and the value arrays converted.
+MixedBuffers mixed_buffers(const Run &r, const Plan &plan, const System &sys, const Solve &sv, const VertexBlock &vb, bool patch_op) {
+    remo_ctx *ctx = r.ctx;
+    remo_batch *b = r.b;
+    hipStream_t s = r.s;
+    const DeviceSymbolic &sy = b->sym;
+    const PcgBuffers &buf = sv.buf;
+    const size_t nk = size_t(sys.n) * plan.kmax;
+    MixedBuffers mx;
+    float *v32 = ctx->take<float>(size_t(sy.nnz) + 2);   // same slack as d_val
+    float *dinv32 = ctx->take<float>(size_t(sys.n));
+    launch_to_float(sy.nnz, sys.d_val, v32, s);
+    launch_to_float(sys.n, sys.d_dinv, dinv32, s);
+    mx.A32 = CsrViewT<float>{sys.n, sy.nnz, sy.rowptr, sy.col, v32};
+    mx.A32.pair_begin = b->A.pair_begin; mx.A32.pair_end = b->A.pair_end; mx.A32.vertex_block_only = sys.lite;
+    PcgBuffersT<float> &f = mx.b32;
+    f.x = ctx->take<float>(nk); f.r = ctx->take<float>(nk);
+    f.p = ctx->take<float>(nk + 4); f.q = ctx->take<float>(nk);
+    mx.f32 = ctx->take<float>(nk);
+    f.dinv = dinv32;
+    f.part_pq = buf.part_pq; f.part_rz = buf.part_rz; f.rz0 = buf.rz0;
+    f.nv_coarse = buf.nv_coarse; f.cheb_degree = buf.cheb_degree; f.cheb_lmax = buf.cheb_lmax; f.cheb_lmin = buf.cheb_lmin;
+    f.cz = ctx->take<float>(sv.nc); f.cres = ctx->take<float>(sv.nc);
+    f.cd[0] = ctx->take<float>(sv.nc); f.cd[1] = ctx->take<float>(sv.nc);
+    f.progress = buf.progress; f.progress_len = buf.progress_len;
+    f.nb_spmv = buf.nb_spmv; f.nb_vec = buf.nb_vec;
+    if (buf.amg && vb.amg32_ready) f.amg = &b->amg32;
+    if (buf.vb_rowptr) {
+        float *vb32 = ctx->take<float>(size_t(vb.h_vb[1]) + 1);
+        launch_to_float(vb.h_vb[1], buf.vb_val, vb32, s);
+        f.vb_rowptr = buf.vb_rowptr; f.vb_col = buf.vb_col; f.vb_val = vb32;
+    }
+    f.ell_col = buf.ell_col; f.ell_tail = buf.ell_tail; f.ell_val = buf.c32_ell_val;
+    if (buf.sq_rowptr) {
+        float *a32 = ctx->take<float>(size_t(vb.h_sq[1]) + 1), *b32 = ctx->take<float>(size_t(vb.h_sq[1]) + 1);
+        launch_to_float(vb.h_sq[1], buf.sq_a, a32, s);
+        launch_to_float(vb.h_sq[1], buf.sq_b, b32, s);
+        f.sq_rowptr = buf.sq_rowptr; f.sq_col = buf.sq_col; f.sq_a = a32; f.sq_b = b32; f.sq_lanes = buf.sq_lanes;
+    }
+    // The forms of the update / direction launches are the fp64 solve's (set_launch_shape).  defer_q hangs on pcg_update_folds, which
+    // reads amg, cheb_degree, nv_coarse and sq_rowptr: all copied above, and f.amg is set exactly when buf.amg is (a mixed run always
+    // has the hierarchy's fp32 image) - the answer cannot differ between the two buffers, so it is not asked twice.
+    f.defer_q = buf.defer_q; f.x_in_direction = buf.x_in_direction; f.pq_bins = buf.pq_bins;
+    if (patch_op) {
+        b->patch32 = patch_view32(b->patch64);
+        b->patch32.dot_bins = f.pq_bins;
+        mx.A32.patch = &b->patch32;
+    }
+    return mx;
+}
+
+// ---- one chunk of right-hand sides: loads, PCG, evaluation ----------------------------------------------------------------------
+struct RunTotals {
+    int ret = REMO_OK;
+    size_t ev_used = 0;               // events of remo_opts_t.time_kernels
+    float ms_solve = 0.f, ms_eval = 0.f;
+};
+
+int solve_chunk(const Run &r, const Plan &plan, const System &sys, const DevicePoints &dp, Solve &sv, MixedBuffers *mx, int k, int q0, int nq,
+                std::vector<double> &h_out, RunTotals &tot) {
+    remo_ctx *ctx = r.ctx;
+    remo_batch *b = r.b;
+    remo_stats_t *st = r.st;
+    hipStream_t s = r.s;
+    const DeviceSymbolic &sy = b->sym;
+    const int dim = r.dim, N = r.N;
+    PcgBuffers &buf = sv.buf;
+    HIP_TRY(hipEventRecord(ctx->ev[4], s));
+    HIP_TRY(hipMemsetAsync(sys.d_f, 0, sizeof(double) * sys.n * k, s));
+    if (nq > 0)
+        launch_build_rhs(dim, sy.condense, nq, dp.d_prhs + q0, dp.d_pI + q0, dp.d_found + q0, dp.d_phi + size_t(q0) * N, sy.eldof, sys.d_C, sys.d_M, k,
+                         sys.d_f, dp.d_fint + q0, s);
+    if (plan.x_ev_only) {   // the slots of this chunk's points (k and the columns change with the chunk)
+        launch_eval_slots(dim, sy.condense, nq, dp.d_prhs + q0, dp.d_found + q0, sy.eldof, k, dp.d_ev_at, s);
+        if (nq > 0) HIP_TRY(hipMemsetAsync(dp.d_x_ev, 0, sizeof(double) * size_t(nq) * N, s));
+        buf.x_ev_at = dp.d_ev_at; buf.x_ev = dp.d_x_ev; buf.x_ev_n = nq * N;
+    }
+    HIP_TRY(hipEventRecord(ctx->ev[5], s));
+    ChunkResult cr = mx ? run_pcg_mixed(ctx, b->A, k, sys.d_f, buf, *mx, r.o, st, tot.ev_used) : run_pcg(ctx, b->A, k, sys.d_f, buf, r.o, st, tot.ev_used);
+    HIP_TRY(hipEventRecord(ctx->ev[6], s));
+    if (nq > 0)
+        launch_eval(dim, sy.condense, nq, dp.d_prhs + q0, dp.d_pI + q0, dp.d_found + q0, dp.d_phi + size_t(q0) * N, sy.eldof, sys.d_C, sys.d_M, k, buf.x,
+                    dp.d_fint + q0, dp.d_out + q0, s, buf.x_ev);
+    HIP_TRY(hipEventRecord(ctx->ev[7], s));
+    if (nq > 0) HIP_TRY(hipMemcpyAsync(h_out.data() + q0, dp.d_out + q0, sizeof(double) * nq, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float e1 = 0, e2 = 0, e3 = 0;
+    (void)hipEventElapsedTime(&e1, ctx->ev[4], ctx->ev[5]);
+    (void)hipEventElapsedTime(&e2, ctx->ev[5], ctx->ev[6]);
+    (void)hipEventElapsedTime(&e3, ctx->ev[6], ctx->ev[7]);
+    tot.ms_eval += e1 + e3;
+    tot.ms_solve += e2;
+    if (!cr.finite) return fail(ctx, REMO_ERR_NUMERIC, "non-finite residual in PCG");
+    b->k_last = k;
+    if (!cr.converged) tot.ret = REMO_NOT_CONVERGED;
+    for (int c = 0; c < k; ++c) {
+        st->iterations[c] = cr.iters[c];
+        st->relres[c] = cr.relres[c];
+        st->max_iterations = std::max(st->max_iterations, cr.iters[c]);
+    }
+    return REMO_OK;
+}
+
+// ---- events -> remo_stats_t -----------------------------------------------------------------------------------------------------
+void fill_timing_stats(const Run &r, const Plan &plan, const System &sys, bool mixed, bool patch_op, const RunTotals &tot) {
+    remo_ctx *ctx = r.ctx;
+    remo_stats_t *st = r.st;
+    hipStream_t s = r.s;
+    const DeviceSymbolic &sy = r.b->sym;
+    const int64_t n = sys.n;
+    const int kmax = plan.kmax;
+    float m = 0;
+    (void)hipEventElapsedTime(&m, ctx->ev[0], ctx->ev[1]); st->ms_h2d = m;
+    (void)hipEventElapsedTime(&m, ctx->ev[1], ctx->ev[2]); st->ms_assemble = m;
+    (void)hipEventElapsedTime(&m, ctx->ev[2], ctx->ev[3]); st->ms_eval = m + tot.ms_eval;
+    st->ms_solve = tot.ms_solve;
+    st->spmv_bytes = mixed ? 8.0 * double(sy.nnz) + 4.0 * double(n) + 8.0 * double(kmax) * double(n)   // fp32 values and vectors
+                           : 12.0 * double(sy.nnz) + 4.0 * double(n) + 16.0 * double(kmax) * double(n);
+    if (patch_op)   // the patch operator reads no stored entries: x and y once (k columns) + 40 bytes of local indices and 48 of metric terms per element
+        st->spmv_bytes = (mixed ? 8.0 : 16.0) * double(kmax) * double(n) + 88.0 * double(r.b->nt);
+    if (r.o.time_kernels) {
+        // what an event bracket measures beyond the enclosed kernel: an empty pair on the same stream
+        float overhead = 1e30f;
+        for (int rep = 0; rep < 16; ++rep) {
+            HIP_TRY(hipEventRecord(ctx->ev[0], s));
+            HIP_TRY(hipEventRecord(ctx->ev[1], s));
+            HIP_TRY(hipEventSynchronize(ctx->ev[1]));
+            float e = 0;
+            (void)hipEventElapsedTime(&e, ctx->ev[0], ctx->ev[1]);
+            if (e < overhead) overhead = e;
+        }
+        if (!(overhead < 1e29f) || overhead < 0.f) overhead = 0.f;
+        double sum = 0, raw = 0;
+        for (size_t i = 0; i + 1 < tot.ev_used; i += 2) {
+            float e = 0;
+            (void)hipEventElapsedTime(&e, ctx->spmv_ev[i], ctx->spmv_ev[i + 1]);
+            raw += e;
+            sum += (e > overhead) ? double(e - overhead) : 0.0;
+        }
+        st->spmv_ms = sum;
+        st->spmv_ms_raw = raw;
+        st->event_overhead_ms = overhead;
+        st->spmv_launches = int64_t(tot.ev_used / 2);
+    }
+}
+
+}  // namespace
+
+extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_t *opts_in, remo_stats_t *st) {
+    if (!ctx) return REMO_ERR_ARG;
+    if (!b) return fail(ctx, REMO_ERR_ARG, "null batch");
+    remo_opts_t o;
+    if (int rc = checked_opts(ctx, opts_in, o)) return rc;
+    remo_stats_t local;
+    if (!st) st = &local;
+    std::memset(st, 0, sizeof *st);
+    std::fill(b->u_out.begin(), b->u_out.end(), std::nan(""));
+    b->has_system = false;
+    b->amg64 = AmgT<double>{};
+    b->amg32 = AmgT<float>{};
+    b->run_id = ++ctx->run_id;
+    const double t_start = now_ms();
+    try {
+        HIP_TRY(hipSetDevice(ctx->device));
+        const Run r{ctx, b, o, st, ctx->stream, b->dim, (b->dim == 2) ? 10 : 20, (b->dim == 2) ? 9 : 6};
+        hipStream_t s = r.s;
+
+        // ---- host side: points, plan, arena -----------------------------------------------------------------------
+        const Points points = gather_points(b);
+        const int npts = points.n();
+        for (double z : points.z)
+            if (!std::isfinite(z)) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
+        const Plan plan = plan_batch(b, o, npts);
+        ctx->reserve(plan.arena_bytes);
+
+        // ---- numbering, then every buffer of the solve (arena order), then the device work up to the one sync --------
+        if (int rc = number_dofs(r, plan, t_start)) return rc;
+        System sys = take_system(r, plan);
+        Solve sv;
+        take_pcg_buffers(r, plan, sys, sv);
+        const DevicePoints dp = take_points(r, plan, npts);
+        prepare_progress(r, sv.buf);
+        HIP_TRY(hipEventRecord(ctx->ev[0], s));
+        upload_points(r, points, dp);
+        HIP_TRY(hipEventRecord(ctx->ev[1], s));
+        assemble_system(r, sys);
+        HIP_TRY(hipEventRecord(ctx->ev[2], s));
+        locate_points(r, dp);
+        HIP_TRY(hipEventRecord(ctx->ev[3], s));
+        VertexBlock vb;
+        vertex_block_enqueue(r, plan, sys, sv, vb);
+        HIP_TRY(hipStreamSynchronize(s));
+
+        // ---- what came back: preconditioner images, mesh / point errors, operator -------------------------------------
+        if (int rc = vertex_block_accept(r, plan, sys, sv, vb)) return rc;
+        if (vb.h_err & 1) return fail(ctx, REMO_ERR_MESH, "degenerate element or material index out of range");
+        if (vb.h_err & 2) return fail(ctx, REMO_ERR_POINT, "source or evaluation point outside the mesh");
+        bool patch_op = false;
+        if (int rc = choose_operator(r, plan, sys, sv, vb, patch_op)) return rc;
+
+        // ---- solve, chunk by chunk ----------------------------------------------------------------------------------
+        // serialize_solves: batches of other contexts may number and assemble beside this PCG, but not run theirs
+        std::unique_lock<std::mutex> solve_turn(g_solve_mutex, std::defer_lock);
+        if (o.serialize_solves) solve_turn.lock();
+        set_launch_shape(r, sys, patch_op, sv.buf);
+        const bool mixed = (o.precision == 1);
+        MixedBuffers mx;
+        if (mixed) mx = mixed_buffers(r, plan, sys, sv, vb, patch_op);   // fp32 images of the system for the inner solver
+        std::vector<double> h_out(npts, std::nan(""));
+        RunTotals tot;
+        int chunk = 0;
+        for (int c0 = 0; c0 < b->n_rhs; c0 += REMO_MAX_RHS, ++chunk) {
+            const int k = std::min(b->n_rhs - c0, REMO_MAX_RHS);
+            const int q0 = points.chunk_begin[chunk], nq = points.chunk_begin[chunk + 1] - q0;
+            if (int rc = solve_chunk(r, plan, sys, dp, sv, mixed ? &mx : nullptr, k, q0, nq, h_out, tot)) return rc;
+        }
+        for (int q = 0; q < npts; ++q)
+            if (points.eval_slot[q] >= 0) b->u_out[points.eval_slot[q]] = h_out[q];
+        fill_timing_stats(r, plan, sys, mixed, patch_op, tot);
+        st->ms_total = now_ms() - t_start;
+        if (tot.ret == REMO_NOT_CONVERGED) ctx->err = "PCG did not reach rtol within maxsteps";
+        return tot.ret;
+    } catch (const std::exception &ex) {
+        std::fill(b->u_out.begin(), b->u_out.end(), std::nan(""));
+        return fail(ctx, REMO_ERR_DEVICE, ex.what());
+    }
+}

@@ -1,0 +1,414 @@
+// remo_debug.hip — the probes of include/remo3d_hip_debug.h: bandwidth / clock / XCD / grid-barrier measurements, the phase clocks
+// of the patch kernel (probe builds), and remo_debug_tune with the tuning state it writes.
+#include <limits.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/remo3d_hip_debug.h"
+#include "remo_internal.h"
+#include "patch.h"
+
+using namespace remo;
+
+namespace remo {
+Tune g_tune;
+}
+
+extern "C" {
+
+namespace {
+__global__ void __launch_bounds__(256) k_stream_read(const double2 *__restrict__ x, int64_t n2, double *__restrict__ out) {
+    double a = 0.0, b = 0.0;
+    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n2; i += int64_t(gridDim.x) * blockDim.x) {
+        const double2 v = x[i];
+        a += v.x; b += v.y;
+    }
+    a += b;
+    for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
+    if ((threadIdx.x & 63) == 0) out[blockIdx.x * 4 + (threadIdx.x >> 6)] = a;
+}
+// scattered 16-byte reads from a 2 MiB buffer (resident in every XCD's 4 MiB L2 after the first touch): the L2 -> L1 -> lane path
+// the SpMM's x gather lives on
+__global__ void __launch_bounds__(256) k_l2_gather(const double2 *__restrict__ x, uint32_t mask, int iters, double *__restrict__ out) {
+    uint32_t idx = (blockIdx.x * 256u + threadIdx.x) * 2654435761u;
+    double a = 0.0;
+    for (int i = 0; i < iters; ++i) {
+        const double2 v = x[idx & mask];
+        a += v.x + v.y;
+        idx = idx * 1664525u + 1013904223u;
+    }
+    if (a == 1.2345e300) out[0] = a;
+}
+
+// a chain of dependent fp32 multiply-adds per wave, one wave per SIMD-sized slice of the chip: its rate follows the shader clock
+__global__ void __launch_bounds__(64) k_clock_probe(int iters, float *__restrict__ out) {
+    float a = float(threadIdx.x) * 1e-3f;
+    for (int i = 0; i < iters; ++i) {
+#pragma unroll
+        for (int u = 0; u < 16; ++u) a = __builtin_fmaf(a, 0.999999f, 0.5f);
+    }
+    if (a == 123.456f) out[blockIdx.x] = a;
+}
+}  // namespace
+
+int remo_debug_cache_gather(remo_ctx_t *ctx, int64_t bytes, double *gbs) {
+    if (!ctx || !gbs || bytes < (1 << 20) || bytes > (int64_t(1) << 32) || (bytes & (bytes - 1)) != 0) return REMO_ERR_ARG;   // a power of two
+    try {
+        HIP_TRY(hipSetDevice(ctx->device));
+        const int64_t n2 = bytes / 16;   // 16-byte elements
+        DeviceTemp tmp;
+        double *a = tmp.alloc<double>(size_t(n2) * 2), *o = tmp.alloc<double>(8);
+        HIP_TRY(hipMemsetAsync(a, 0, size_t(n2) * 16, ctx->stream));
+        const int blocks = 4096, iters = 64;
+        float best = 1e30f;
+        for (int rep = 0; rep < 5; ++rep) {
+            HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+            hipLaunchKernelGGL(k_l2_gather, dim3(blocks), dim3(256), 0, ctx->stream, reinterpret_cast<const double2 *>(a), uint32_t(n2 - 1), iters, o);
+            HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
+            if (ms < best) best = ms;
+        }
+        *gbs = double(blocks) * 256.0 * iters * 16.0 / (double(best) * 1e6);
+        return REMO_OK;
+    } catch (const std::exception &ex) {
+        return fail(ctx, REMO_ERR_DEVICE, ex.what());
+    }
+}
+
+int remo_debug_clock(remo_ctx_t *ctx, double *gfma_per_wave) {
+    if (!ctx || !gfma_per_wave) return REMO_ERR_ARG;
+    try {
+        HIP_TRY(hipSetDevice(ctx->device));
+        DeviceTemp tmp;
+        float *o = tmp.alloc<float>(1024);
+        const int iters = 1 << 16;   // x 16 dependent multiply-adds
+        float best = 1e30f;
+        for (int rep = 0; rep < 4; ++rep) {
+            HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+            hipLaunchKernelGGL(k_clock_probe, dim3(1024), dim3(64), 0, ctx->stream, iters, o);
+            HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
+            if (ms < best) best = ms;
+        }
+        *gfma_per_wave = double(iters) * 16.0 / (double(best) * 1e6);
+        return REMO_OK;
+    } catch (const std::exception &ex) {
+        return fail(ctx, REMO_ERR_DEVICE, ex.what());
+    }
+}
+
+namespace {
+// which XCD (accelerator die) a workgroup runs on: hardware register XCC_ID (id 20, 4 bits) - the SpMM's row schedule assumes
+// workgroup b runs on XCD b mod 8
+__global__ void __launch_bounds__(64) k_xcc_probe(int32_t *__restrict__ out) {
+    const int32_t id = __builtin_amdgcn_s_getreg((3 << 11) | 20);
+    if (threadIdx.x == 0) out[blockIdx.x] = id;
+}
+}  // namespace
+
+int remo_debug_xcc(remo_ctx_t *ctx, int32_t *out, int32_t nblocks) {
+    if (!ctx || !out || nblocks < 1 || nblocks > 65536) return REMO_ERR_ARG;
+    try {
+        HIP_TRY(hipSetDevice(ctx->device));
+        DeviceTemp tmp;
+        int32_t *d = tmp.alloc<int32_t>(nblocks);
+        hipLaunchKernelGGL(k_xcc_probe, dim3(nblocks), dim3(64), 0, ctx->stream, d);
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(hipMemcpy(out, d, sizeof(int32_t) * nblocks, hipMemcpyDeviceToHost));
+        return REMO_OK;
+    } catch (const std::exception &ex) {
+        return fail(ctx, REMO_ERR_DEVICE, ex.what());
+    }
+}
+
+int remo_debug_device(remo_ctx_t *ctx, int64_t *out8) {
+    if (!ctx || !out8) return REMO_ERR_ARG;
+    hipDeviceProp_t pr;
+    if (hipGetDeviceProperties(&pr, ctx->device) != hipSuccess) return fail(ctx, REMO_ERR_DEVICE, "hipGetDeviceProperties failed");
+    out8[0] = pr.multiProcessorCount;
+    out8[1] = pr.clockRate;          // kHz
+    out8[2] = pr.memoryClockRate;    // kHz
+    out8[3] = pr.memoryBusWidth;
+    out8[4] = pr.l2CacheSize;
+    out8[5] = int64_t(pr.totalGlobalMem >> 20);
+    out8[6] = pr.maxSharedMemoryPerMultiProcessor;
+    out8[7] = pr.asicRevision;
+    return REMO_OK;
+}
+
+int remo_debug_stream(remo_ctx_t *ctx, int64_t bytes, double *read_gbs, double *copy_gbs) {
+    if (!ctx || bytes < (1 << 20)) return REMO_ERR_ARG;
+    try {
+        HIP_TRY(hipSetDevice(ctx->device));
+        const int64_t n = bytes / 16 * 2;
+        DeviceTemp tmp;
+        double *a = tmp.alloc<double>(n), *b = tmp.alloc<double>(n), *o = tmp.alloc<double>(4096 * 4);
+        HIP_TRY(hipMemsetAsync(a, 0, sizeof(double) * n, ctx->stream));
+        HIP_TRY(hipMemsetAsync(b, 0, sizeof(double) * n, ctx->stream));
+        float best_r = 1e30f, best_c = 1e30f;
+        for (int rep = 0; rep < 6; ++rep) {
+            HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+            hipLaunchKernelGGL(k_stream_read, dim3(4096), dim3(256), 0, ctx->stream, reinterpret_cast<const double2 *>(a), n / 2, o);
+            HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+            HIP_TRY(hipMemcpyAsync(b, a, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
+            HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            float r = 0, c = 0;
+            (void)hipEventElapsedTime(&r, ctx->ev[0], ctx->ev[1]);
+            (void)hipEventElapsedTime(&c, ctx->ev[1], ctx->ev[2]);
+            if (r < best_r) best_r = r;
+            if (c < best_c) best_c = c;
+        }
+        if (read_gbs) *read_gbs = double(n) * 8.0 / (double(best_r) * 1e6);
+        if (copy_gbs) *copy_gbs = 2.0 * double(n) * 8.0 / (double(best_c) * 1e6);
+        if (bytes <= (int64_t(192) << 20) && read_gbs) {   // a buffer that fits the 256 MB Infinity Cache: re-read it back to back
+            float best = 1e30f;
+            for (int rep = 0; rep < 6; ++rep) {
+                hipLaunchKernelGGL(k_stream_read, dim3(4096), dim3(256), 0, ctx->stream, reinterpret_cast<const double2 *>(a), n / 2, o);   // refill
+                HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+                for (int k = 0; k < 4; ++k)
+                    hipLaunchKernelGGL(k_stream_read, dim3(4096), dim3(256), 0, ctx->stream, reinterpret_cast<const double2 *>(a), n / 2, o);
+                HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+                HIP_TRY(hipStreamSynchronize(ctx->stream));
+                float r = 0;
+                (void)hipEventElapsedTime(&r, ctx->ev[0], ctx->ev[1]);
+                if (r < best) best = r;
+            }
+            *read_gbs = 4.0 * double(n) * 8.0 / (double(best) * 1e6);
+        }
+        return REMO_OK;
+    } catch (const std::exception &ex) {
+        return fail(ctx, REMO_ERR_DEVICE, ex.what());
+    }
+}
+
+int remo_debug_grid_barrier(remo_ctx_t *ctx, int32_t nblocks, int32_t nbar, double *out3) {
+    if (!ctx || !out3 || nblocks < 1 || nblocks > 2048 || nbar < 1 || nbar > 100000) return REMO_ERR_ARG;
+    try {
+        HIP_TRY(hipSetDevice(ctx->device));
+        DeviceTemp tmp;
+        unsigned *counter = tmp.alloc<unsigned>(16);
+        float *buf = tmp.alloc<float>(size_t(nblocks) * 256);
+        int *fail_flag = reinterpret_cast<int *>(counter) + 4, *mismatch = reinterpret_cast<int *>(counter) + 8;
+        hipEvent_t e0, e1;
+        HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+        float ms = 0.f;
+        for (int rep = 0; rep < 2; ++rep) {     // the second run is the measurement
+            HIP_TRY(hipMemsetAsync(counter, 0, 64, ctx->stream));
+            HIP_TRY(hipMemsetAsync(buf, 0, sizeof(float) * size_t(nblocks) * 256, ctx->stream));
+            HIP_TRY(hipEventRecord(e0, ctx->stream));
+            launch_barrier_probe(nblocks, nbar, counter, fail_flag, buf, mismatch, ctx->stream);
+            HIP_TRY(hipEventRecord(e1, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        }
+        int h[12];
+        HIP_TRY(hipMemcpy(h, counter, sizeof h, hipMemcpyDeviceToHost));
+        out3[0] = 1e3 * double(ms) / (2.0 * nbar);    // two barriers per iteration
+        out3[1] = h[4]; out3[2] = h[8];
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        return REMO_OK;
+    } catch (const std::exception &e) {
+        return fail(ctx, REMO_ERR_DEVICE, e.what());
+    }
+}
+
+#ifdef REMO_PROBES
+namespace {
+// What the two phase probes of the patch kernel share: 5 columns of pseudo-random x, a stamp buffer, and the operator of the
+// batch's last run in fp64 or as the fp32 instantiation on the same tables (vectors reinterpreted: timing only).
+struct PatchProbe {
+    static constexpr int k = 5;
+    remo_ctx *ctx;
+    remo_batch *b;
+    bool fp32;
+    DeviceTemp tmp;
+    double *dx, *dy;
+    long long *st;
+    size_t stamp_words;
+    int nb;
+    CsrViewT<float> A32;
+    PatchOpT<float> P32;
+    PatchProbe(remo_ctx *ctx_, remo_batch *b_, bool fp32_, size_t stamp_words_)
+        : ctx(ctx_), b(b_), fp32(fp32_), stamp_words(stamp_words_), A32{b_->A.n, 0, nullptr, nullptr, nullptr}, P32(patch_view32(b_->patch64)) {
+        const int64_t n = b->A.n;
+        dx = tmp.alloc<double>(n * k + 2);
+        dy = tmp.alloc<double>(n * k + 2);
+        st = tmp.alloc<long long>(stamp_words);
+        std::vector<double> hx(size_t(n) * k);
+        for (size_t i = 0; i < hx.size(); ++i) hx[i] = double((i * 2654435761u) % 1000) * 1e-3 - 0.5;
+        HIP_TRY(hipMemcpy(dx, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(st, 0, sizeof(long long) * stamp_words));
+        nb = spmv_grid(n, choose_lanes_per_row(n, b->A.nnz));
+        A32.patch = &P32; A32.vertex_block_only = true;
+    }
+    void once() {
+        if (fp32) launch_spmm(A32, k, reinterpret_cast<const float *>(dx), reinterpret_cast<float *>(dy), nullptr, nullptr, nb, ctx->stream);
+        else launch_spmm(b->A, k, dx, dy, nullptr, nullptr, nb, ctx->stream);
+    }
+    void stamped_runs() {     // three applications that leave their phase stamps (patch mode 4)
+        set_patch_stamps(st); set_patch_mode(4);
+        for (int rep = 0; rep < 3; ++rep) once();
+        set_patch_mode(0); set_patch_stamps(nullptr);
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    double timed_us() {       // the whole application (apply + reduce launches), microseconds per application
+        once();
+        HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+        for (int rep = 0; rep < 10; ++rep) once();
+        HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
+        return 1e3 * double(ms) / 10.0;
+    }
+    std::vector<long long> stamps() {
+        std::vector<long long> h(stamp_words);
+        HIP_TRY(hipMemcpy(h.data(), st, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
+        return h;
+    }
+};
+
+// the argument errors both probes answer with (REMO_OK: go on)
+int patch_probe_check(remo_ctx *ctx, remo_batch *b) {
+    if (!b->has_system || b->run_id != ctx->run_id || !b->A.patch) return fail(ctx, REMO_ERR_ARG, "the last run on this batch did not use the patch operator");
+    if (PatchProbe::k * b->patch64.t.E > b->patch64.t.block) return fail(ctx, REMO_ERR_ARG, "the batch's patch tables are laid out for fewer than 5 columns");
+    return REMO_OK;
+}
+}  // namespace
+#endif
+
+int remo_debug_patch_phases(remo_ctx_t *ctx, remo_batch_t *b, int32_t fp32, double *out16) {
+    if (!ctx || !b || !out16) return REMO_ERR_ARG;
+#ifndef REMO_PROBES
+    (void)fp32;
+    return fail(ctx, REMO_ERR_ARG, "remo_debug_patch_phases: the library was built without -DREMO_PROBES (make -C remo3d_amd/csrc probes)");
+#else
+    if (int rc = patch_probe_check(ctx, b)) return rc;
+    try {
+        HIP_TRY(hipSetDevice(ctx->device));
+        const int64_t grid = (b->patch64.t.npatch + 7) / 8 * 8;
+        std::vector<long long> h;
+        {
+            PatchProbe pr(ctx, b, fp32 != 0, size_t(grid) * 8);
+            set_patch_persist(0);     // (this probe is about the one-workgroup-per-patch form; remo_debug_patch_phases_p is the persistent one's)
+            pr.stamped_runs();
+            for (int mode = 0; mode <= 3; ++mode) {     // the ablation modes 0 .. 3
+                set_patch_mode(mode);
+                out16[10 + mode] = pr.timed_us();
+            }
+            set_patch_mode(0);
+            h = pr.stamps();
+        }
+        for (int i = 0; i < 10; ++i) out16[i] = 0.0;
+        long long lo = LLONG_MAX, hi = 0;
+        int64_t cnt = 0;
+        for (int64_t w = 0; w < grid; ++w) {
+            const long long *s8 = h.data() + w * 8;
+            if (s8[0] == 0 || s8[7] == 0) continue;
+            for (int q = 0; q < 7; ++q) out16[q] += double(s8[q + 1] - s8[q]);
+            out16[7] += double(s8[7] - s8[0]);
+            lo = std::min(lo, s8[0]); hi = std::max(hi, s8[7]);
+            ++cnt;
+        }
+        for (int q = 0; q < 8; ++q) out16[q] /= double(cnt > 0 ? cnt : 1);
+        out16[8] = double(hi - lo);     // first start to last end, clock ticks
+        out16[9] = double(cnt);
+        set_patch_persist(1);
+        return REMO_OK;
+    } catch (const std::exception &ex) {
+        set_patch_mode(0); set_patch_stamps(nullptr); set_patch_persist(1);
+        return fail(ctx, REMO_ERR_DEVICE, ex.what());
+    }
+#endif
+}
+
+int remo_debug_patch_phases_p(remo_ctx_t *ctx, remo_batch_t *b, int32_t fp32, double *out16) {
+    if (!ctx || !b || !out16) return REMO_ERR_ARG;
+#ifndef REMO_PROBES
+    (void)fp32;
+    return fail(ctx, REMO_ERR_ARG, "remo_debug_patch_phases_p: the library was built without -DREMO_PROBES (make -C remo3d_amd/csrc probes)");
+#else
+    if (int rc = patch_probe_check(ctx, b)) return rc;
+    const int64_t slots = 8192;      // workgroups the stamp buffer holds
+    try {
+        HIP_TRY(hipSetDevice(ctx->device));
+        std::vector<long long> h;
+        double us = 0.0;
+        {
+            PatchProbe pr(ctx, b, fp32 != 0, size_t(slots) * 12);
+            pr.stamped_runs();
+            us = pr.timed_us();
+            h = pr.stamps();
+        }
+        for (int i = 0; i < 16; ++i) out16[i] = 0.0;
+        double patches = 0, wgs = 0, longest = 0;
+        for (int64_t w = 0; w < slots; ++w) {
+            const long long *s12 = h.data() + w * 12;
+            if (s12[10] <= 0) continue;
+            double tot = 0;
+            for (int q = 0; q < 10; ++q) { out16[q] += double(s12[q]); tot += double(s12[q]); }
+            patches += double(s12[10]); wgs += 1; longest = std::max(longest, tot);
+        }
+        for (int q = 0; q < 10; ++q) out16[q] /= (patches > 0 ? patches : 1);     // clock ticks per patch, phase by phase
+        out16[10] = patches; out16[11] = wgs; out16[12] = longest; out16[13] = us;
+        return REMO_OK;
+    } catch (const std::exception &ex) {
+        set_patch_mode(0); set_patch_stamps(nullptr);
+        return fail(ctx, REMO_ERR_DEVICE, ex.what());
+    }
+#endif
+}
+
+int remo_debug_tune(int32_t key, int32_t value) {
+    // Keys that force ONE OF THE PRODUCT'S OWN PATHS - a choice the library makes by size or dimension, forced so that a small test
+    // mesh reaches the code a large batch runs; every setting gives the same operator / preconditioner to rounding: always there.
+    switch (key) {
+        case 3: set_spmm_tuning(3, value); return 0;    // row schedule of the CSR product
+        case 6: g_tune.square = value; return 0;             // paired Chebyshev steps
+        case 9: set_fold_first(value); return 0;        // first Chebyshev step inside the update launch
+        case 13: g_tune.compact = value; return 0;           // compact copy of the vertex block
+        case 15: g_tune.chain32 = value; return 0;           // fp32 Chebyshev chain inside fp64 solves
+        case 16: g_tune.amg = value; return 0;               // multigrid cycle on the vertex block
+        case 17: g_tune.amg32 = value; return 0;             // ... in fp32 storage
+        case 18: set_element_order(value); return 0;    // elements in the caller's order
+        case 31: set_tile_update(value); return 0;      // update launch: 64 rows per wave, a value per lane and pass / a k-wide row per lane
+        case 30: set_flat_direction(value); return 0;   // direction launch: flat arrays, 16 bytes per lane / a k-wide row per lane
+        case 29: set_slab_masked(value); return 0;      // slab slots a row does not have: not fetched / fetched and weighted by zero
+        case 25: g_tune.x_in_direction = value; return 0;    // x += alpha p in the direction / in the update launch
+        case 39: g_tune.x_ev = value; return 0;              // one-shot solves: only the values of x the evaluation points read / the whole x
+        case 22: g_tune.defer_q = value; return 0;           // shared rows summed by k_patch_reduce / by the update launch
+        case 24: g_tune.ell = value; return 0;               // fixed-width image of the vertex block
+        default: break;
+    }
+#ifdef REMO_PROBES
+    // Keys of rejected experiments and ablations (some give wrong results on purpose): tools/ builds only (make probes)
+    if (key == 7) g_tune.sq_lanes = value;
+    else if (key == 8) set_symbolic_tuning(value);
+    else if (key == 19) set_patch_block(value);
+    else if (key == 21) set_patch_mode(value);
+    else if (key == 23) set_patch_slab_rows(value);
+    else if (key == 26) set_patch_lean(value);
+    else if (key == 27) set_slab_ahead(value);
+    else if (key == 28) g_tune.dot_bins = value;
+    else if (key == 32) set_patch_spread(value);
+    else if (key == 33) set_patch_trim(value);
+    else if (key == 34) set_patch_persist(value);
+    else if (key == 35) set_patch_wgs_per_xcd(value);
+    else if (key == 36) g_tune.extra_apply = value;
+    else if (key == 37) set_patch_all_slab(value);
+    else if (key == 38) set_patch_stagger(value);
+    else set_spmm_tuning(key, value);
+    return 0;
+#else
+    (void)value;
+    return -1;      // not in this build
+#endif
+}
+
+}  // extern "C"

@@ -1,0 +1,80 @@
+// remo_host.cpp — the CPU hooks of include/remo3d_hip.h (remo_host_*): element matrices from the exact reference tensors, the
+// host numbering, and the material-tensor check they share with batch creation.  No device code, no device calls.
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "remo_internal.h"
+#include "fem_p3.h"
+#include "symbolic.h"
+
+namespace remo {
+
+// Symmetric positive definite (leading principal minors > 0) and finite: the upper triangle of one material's tensor.
+bool tensor_ok(int dim, const double *S) {
+    const int n = (dim == 2) ? 3 : 6;
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(S[i])) return false;
+    if (dim == 2) return S[0] > 0.0 && S[0] * S[2] - S[1] * S[1] > 0.0;
+    const double m2 = S[0] * S[3] - S[1] * S[1];
+    const double m3 = S[0] * (S[3] * S[5] - S[4] * S[4]) - S[1] * (S[1] * S[5] - S[4] * S[2]) + S[2] * (S[1] * S[4] - S[3] * S[2]);
+    return S[0] > 0.0 && m2 > 0.0 && m3 > 0.0 && std::isfinite(m3);
+}
+
+}  // namespace remo
+
+using namespace remo;
+
+extern "C" {
+
+int remo_host_element_matrix(int32_t dim, const double *X, double sigma, double *K_out) {
+    if ((dim != 2 && dim != 3) || !X || !K_out) return REMO_ERR_ARG;
+    const double *M = ref_tables(dim);
+    if (dim == 2) {
+        double C[9];
+        if (!metric_terms<2>(X, sigma, C)) return REMO_ERR_MESH;
+        for (int i = 0; i < 10; ++i)
+            for (int j = 0; j < 10; ++j) K_out[i * 10 + j] = kentry<2>(C, M, i, j);
+    } else {
+        double C[6];
+        if (!metric_terms<3>(X, sigma, C)) return REMO_ERR_MESH;
+        for (int i = 0; i < 20; ++i)
+            for (int j = 0; j < 20; ++j) K_out[i * 20 + j] = kentry<3>(C, M, i, j);
+    }
+    return REMO_OK;
+}
+
+int remo_host_element_matrix_tensor(int32_t dim, const double *X, const double *sigma_tensor, double *K_out) {
+    if ((dim != 2 && dim != 3) || !X || !sigma_tensor || !K_out) return REMO_ERR_ARG;
+    if (!tensor_ok(dim, sigma_tensor)) return REMO_ERR_ARG;
+    const double *M = ref_tables(dim);
+    if (dim == 2) {
+        double C[9];
+        if (!metric_terms_tensor<2>(X, sigma_tensor, C)) return REMO_ERR_MESH;
+        for (int i = 0; i < 10; ++i)
+            for (int j = 0; j < 10; ++j) K_out[i * 10 + j] = kentry<2>(C, M, i, j);
+    } else {
+        double C[6];
+        if (!metric_terms_tensor<3>(X, sigma_tensor, C)) return REMO_ERR_MESH;
+        for (int i = 0; i < 20; ++i)
+            for (int j = 0; j < 20; ++j) K_out[i * 20 + j] = kentry<3>(C, M, i, j);
+    }
+    return REMO_OK;
+}
+
+double remo_host_factor_error(void) { return ref_factors3_error(); }
+
+int remo_host_symbolic(const remo_mesh_t *mesh, int32_t condense, int64_t *sizes, int32_t *rowptr, int32_t *col, int32_t *freeid) {
+    if (!mesh || !sizes) return REMO_ERR_ARG;
+    Symbolic sy;
+    std::string err;
+    const int rc = build_symbolic(*mesh, condense != 0, true, sy, err);
+    if (rc != REMO_OK) { g_create_error = err; return rc; }
+    sizes[0] = sy.ndof; sizes[1] = sy.nfree; sizes[2] = sy.nnz; sizes[3] = sy.ne; sizes[4] = sy.nf; sizes[5] = sy.nld;
+    if (rowptr) std::memcpy(rowptr, sy.rowptr.data(), sizeof(int32_t) * (sy.nfree + 1));
+    if (col) std::memcpy(col, sy.col.data(), sizeof(int32_t) * sy.nnz);
+    if (freeid) std::memcpy(freeid, sy.freeid.data(), sizeof(int32_t) * sy.ndof);
+    return REMO_OK;
+}
+
+}  // extern "C"

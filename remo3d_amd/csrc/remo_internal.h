@@ -1,0 +1,167 @@
+// remo_internal.h — what the translation units behind the C ABI share: the context and batch objects, error plumbing, the
+// process-wide tuning state of remo_debug_tune, and a holder for temporary device memory.  Not installed, not a public header.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <chrono>
+#include <cstdio>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/remo3d_hip.h"
+#include "kernels.h"
+#include "amg.h"
+#include "symbolic_gpu.h"
+
+#define HIP_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t e__ = (expr);                                                                        \
+        if (e__ != hipSuccess) {                                                                        \
+            char buf__[512];                                                                            \
+            snprintf(buf__, sizeof buf__, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+            throw std::runtime_error(buf__);                                                            \
+        }                                                                                               \
+    } while (0)
+
+namespace remo {
+
+inline double now_ms() {
+    using namespace std::chrono;
+    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+}
+
+inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+// what remo_last_error(NULL) returns: why the last remo_ctx_create / remo_host_symbolic of this thread failed (remo_api.hip)
+extern thread_local std::string g_create_error;
+
+// Symmetric positive definite (leading principal minors > 0) and finite: the upper triangle of one material's tensor (remo_host.cpp)
+bool tensor_ok(int dim, const double *S);
+
+// Process-wide switches of remo_debug_tune, their only writer (remo_debug.hip); a batch reads them when it is planned and run.
+// The keys that live beside the kernels they steer (the set_* of kernels.h / symbolic_gpu.h) are listed in remo_debug_tune.
+struct Tune {
+    int square = 1;          // key 6: 0 = one launch per Chebyshev step, 1 = paired steps in 2D (default), 2 = paired steps always
+    int sq_lanes = 0;        // key 7 (probe builds): lanes per row of the paired kernel (0 = by row length)
+    int compact = 1;         // key 13: 1 = Chebyshev launches read a compact copy of the vertex block above 16 k vertex rows (default), 2 = at any size, 0 = the leading entries of A's rows in place
+    int chain32 = 1;         // key 15: 1 = fp32 Chebyshev chain inside fp64 solves above 32 k vertex rows (default), 2 = at any size, 0 = chain in fp64
+    int amg = 0;             // key 16: 0 = remo_opts_t.coarse decides, 1 = never the multigrid cycle, 2 = always (any dimension)
+    int amg32 = 1;           // key 17: 1 = fp64 solves run the multigrid cycle in fp32 storage (default), 0 = in fp64
+    int defer_q = 1;         // key 22: 1 = the PCG's update launch sums the patch operator's shared rows itself (default), 0 = k_patch_reduce does
+    int ell = 1;             // key 24: 1 = the Chebyshev launches of 3D read the fixed-width image of the vertex block (default), 0 = its CSR form
+    int x_in_direction = 1;  // key 25: 1 = x += alpha p formed by the direction launch of the step (default), 0 = by the update launch
+    int dot_bins = 1;        // key 28 (probe builds): 1 = the patches add their <p, A p> straight into the update launch's rows (default), 0 = a row per patch + k_patch_dot
+    int x_ev = 1;            // key 39: 1 = one-shot fp64 solves carry only the values of x the evaluation points read (default), 0 = the whole x
+#ifdef REMO_PROBES
+    int extra_apply = 0;     // key 36 (probe builds): extra operator applications (apply + shared-row sums, results discarded) per PCG step: what a step with more applications would cost
+#endif
+};
+extern Tune g_tune;
+
+// Temporary device memory of one entry point, freed when the holder leaves scope (normal and error path alike).  hipFree
+// synchronises the device: the holder's scope ends where the call has drained its stream.
+struct DeviceTemp {
+    std::vector<void *> held;
+    DeviceTemp() = default;
+    DeviceTemp(const DeviceTemp &) = delete;
+    ~DeviceTemp() { for (void *p : held) (void)hipFree(p); }
+    template <class T> T *alloc(size_t count) {
+        held.push_back(nullptr);
+        HIP_TRY(hipMalloc(&held.back(), sizeof(T) * count));
+        return static_cast<T *>(held.back());
+    }
+};
+
+// the fp32 instantiation of a patch operator on the same tables: the slab and the partial sums are scratch of one application, so
+// both storage types share them (dot_bins is the applying solve's to set)
+inline PatchOpT<float> patch_view32(const PatchOpT<double> &p) {
+    return PatchOpT<float>{p.t, reinterpret_cast<float *>(p.Yb), p.ppart, p.lds_rows};
+}
+
+}  // namespace remo
+
+struct remo_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    remo::Arena ar;
+    double *d_M2 = nullptr, *d_M3 = nullptr, *d_M2q = nullptr;   // reference tensors: exact 2D / 3D, 2D by the degree-4 rule
+    remo::PcgProgress *progress = nullptr;  // mapped, coherent host memory
+    remo::PcgProgress *progress_dev = nullptr;
+    int progress_len = 0;
+    int32_t *d_err = nullptr;
+    hipEvent_t ev[8] = {};
+    std::vector<hipEvent_t> spmv_ev;
+    uint64_t run_id = 0;  // the arena holds the system / solution of the batch that ran last
+    // input pool of the one-shot entry (remo_solve_batch): the mesh arrays of the batch in hand, grow-only - a sweep of thousands of
+    // batches then makes no hipMalloc / hipFree per batch (hipFree synchronises the whole device, i.e. the other contexts' streams)
+    char *in_pool = nullptr;
+    size_t in_cap = 0;
+    double floor_stage[REMO_MAX_RHS] = {};   // host staging of the mixed mode's <Cr,r> floors (outlives the async copy)
+
+    template <class T> T *take(size_t count) { return ar.lo<T>(count); }
+    void reserve(size_t bytes) {
+        ar.reset();
+        if (bytes <= ar.cap) return;
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (ar.base) HIP_TRY(hipFree(ar.base));
+        ar.base = nullptr;
+        ar.cap = 0;
+        const size_t want = remo::align_up(bytes + bytes / 4, 4096);  // the top-down end must stay aligned too
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ar.base), want));
+        ar.cap = want;
+    }
+    void ensure_progress(int len) {
+        if (len <= progress_len) return;
+        if (progress) HIP_TRY(hipHostFree(progress));
+        progress = nullptr;
+        progress_len = 0;
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&progress), sizeof(remo::PcgProgress) * size_t(len),
+                              hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&progress_dev), progress, 0));
+        progress_len = len;
+    }
+};
+
+struct remo_batch {
+    int dim = 0;
+    int64_t nv = 0, nt = 0, nbf = 0;
+    int n_mat = 0;
+    int sigma_comp = 1;      // doubles per material in d_sigma: 1 = scalar; 3 (2D) / 6 (3D) = upper triangle of a tensor (remo_solve_batch_tensor)
+    // points: per chunk [sources..., evals...]
+    int n_rhs = 0;
+    std::vector<int32_t> src_ptr, eval_ptr;
+    std::vector<double> src_z, src_I, eval_z;
+    // resident device inputs (everything the path reads is in HBM before remo_batch_run)
+    double *d_coords = nullptr, *d_sigma = nullptr;
+    int32_t *d_mat = nullptr, *d_conn = nullptr, *d_bconn = nullptr;
+    uint8_t *d_bdir = nullptr;
+    bool pooled = false;     // the six arrays live in the context's input pool (remo_solve_batch): not freed with the batch
+    bool eval_only = false;  // remo_solve_batch: nothing reads the solution after the run but the evaluation points (PcgBuffersT::x_ev)
+    // last system (pointers into the context arena; valid until the next run on the context)
+    bool has_system = false;
+    remo::DeviceSymbolic sym;
+    remo::CsrView A{};
+    double *d_val = nullptr, *d_dinv = nullptr;
+    double *d_x = nullptr, *d_C = nullptr;  // solution block [n][k_last] and metric terms of the last run
+    double *d_f = nullptr;                  // load vectors [n][k_last] of the last chunk
+    remo::PatchOpT<double> patch64{};       // patch operator of the last run (remo_opts_t.op = 3), pointers into the arena
+    remo::PatchOpT<float> patch32{};
+    remo::AmgT<double> amg64{};             // multigrid hierarchy of the vertex block of the last run (arena)
+    remo::AmgT<float> amg32{};
+    int k_last = 0;
+    const double *d_M_last = nullptr;       // reference tensors of the last run (remo_opts_t.quadrature)
+    uint64_t run_id = 0;
+    std::vector<double> u_out;
+};
+
+namespace remo {
+
+inline int fail(remo_ctx *ctx, int code, const std::string &msg) {
+    if (ctx) ctx->err = msg;
+    return code;
+}
+
+}  // namespace remo
