@@ -180,6 +180,37 @@ int remo_solve_batch_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_
                             const remo_opts_t *opts, remo_stats_t *stats);
 
 /*
+ * The same solves plus the derivatives of linear measurement functionals of the potentials with respect to the material
+ * conductivities, by adjoint solves (added within ABI 7: additive, detected by the presence of the symbols).  Functional j reads
+ * right-hand side fun_rhs[j] at the axis points fun_z[fun_ptr[j] .. fun_ptr[j+1]) with weights fun_w:
+ *     J_j = sum_i fun_w[i] * u_rhs(fun_z[i])
+ * - the reading of worker.py:113-131 (u_N - u_M, or u_M alone) before the geometric factor.  With A u = f, J = g^T u and
+ * A lambda = g, dJ/dsigma_m = -lambda^T (dA/dsigma_m) u: one extra block of solves (the adjoint columns, chunks of REMO_MAX_RHS,
+ * same operator, preconditioner and stopping rule as the forward columns) and one pass over the elements per functional.
+ * J_out[n_fun]; dJ_out[n_fun * n_mat * nc], functional-major: nc = 1 and dJ_j/dsigma_m for the scalar entry; for the tensor entry
+ * nc = 3 (2D) or 6 (3D) in the upper-triangle layout of sigma_tensor, the derivative with respect to the parameter that sets both
+ * S_ab and S_ba (off-diagonal entries carry both halves).  In 2D with condense = 1 the derivative is that of the full system (the
+ * cell bubbles of u and lambda are recovered).  The sums have a fixed order (no floating-point atomics): with op = 2 dJ_out is
+ * reproducible bit for bit.  u_out is filled as by remo_solve_batch; stats cover the forward and the adjoint solves
+ * (iterations / relres: the last chunk solved).  n_fun = 0 is allowed (the functional arrays may then be NULL).
+ * Errors: as remo_solve_batch, all three outputs NaN-filled; a functional point outside the mesh gives REMO_ERR_POINT;
+ * precision = 1 (mixed) gives REMO_ERR_ARG (the derivatives are formed in fp64), as does a fun_rhs outside [0, n_rhs).
+ */
+int remo_solve_batch_sens(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma,
+                          int32_t n_rhs, const int32_t *src_ptr, const double *src_z, const double *src_I,
+                          const int32_t *eval_ptr, const double *eval_z, double *u_out,
+                          int32_t n_fun, const int32_t *fun_rhs /*[n_fun]: which right-hand side it reads*/,
+                          const int32_t *fun_ptr /*[n_fun+1]*/, const double *fun_z, const double *fun_w,
+                          double *J_out /*[n_fun]*/, double *dJ_out /*[n_fun * n_mat]*/,
+                          const remo_opts_t *opts, remo_stats_t *stats);
+int remo_solve_batch_sens_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor,
+                                 int32_t n_rhs, const int32_t *src_ptr, const double *src_z, const double *src_I,
+                                 const int32_t *eval_ptr, const double *eval_z, double *u_out,
+                                 int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr, const double *fun_z, const double *fun_w,
+                                 double *J_out /*[n_fun]*/, double *dJ_out /*[n_fun * n_mat * nc]*/,
+                                 const remo_opts_t *opts, remo_stats_t *stats);
+
+/*
  * Staged form of the same work, for callers that keep a batch resident (bench.py: inputs are in
  * HBM before the timed region).  create = validate + upload; run = numbering, pattern, assembly,
  * PCG, evaluation, all RHS; fetch = potentials to the host.
@@ -238,6 +269,9 @@ int remo_host_element_matrix(int32_t dim, const double *vertex_coords /*[(dim+1)
                              double sigma, double *K_out);
 /* The same with a conductivity tensor in the layout of remo_solve_batch_tensor (REMO_ERR_ARG if not finite and positive definite). */
 int remo_host_element_matrix_tensor(int32_t dim, const double *vertex_coords, const double *sigma_tensor, double *K_out);
+/* The element contraction of remo_solve_batch_sens on the host (the code the kernel runs): out[nc] = x_l^T (dK_e / d component) x_u
+ * for element vectors x_l, x_u [nld]; tensor = 0: nc = 1 (d/dsigma), else nc = 3 / 6 (upper triangle, off-diagonal both halves). */
+int remo_host_sens_element(int32_t dim, const double *vertex_coords, int32_t tensor, const double *x_l, const double *x_u, double *out);
 /* max |sum_m B_a[m][i] B_b[m][j] - M_ab[i][j]|: how well the factorised reference tensors of the patch operator
  * (remo_opts_t.op = 3) reproduce the tensors the CSR assembly contracts (both exact polynomial integrals). */
 double remo_host_factor_error(void);

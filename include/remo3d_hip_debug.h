@@ -45,6 +45,11 @@ int remo_debug_patch_phases_p(remo_ctx_t *ctx, remo_batch_t *batch, int32_t fp32
  * barrier, [1] = 1 if a wait gave up, [2] = loads that did not see the store. */
 int remo_debug_grid_barrier(remo_ctx_t *ctx, int32_t nblocks, int32_t nbar, double *out3);
 
+/* The contraction launches of the last remo_solve_batch_sens on this context: out2[0] = their time in ms (HIP events around the
+ * launches of all functionals and the reduction), [1] = their algorithmic bytes (per functional the x rows of the forward and the
+ * adjoint column once, per element its dof numbers, vertices and material). */
+int remo_debug_sens_timing(remo_ctx_t *ctx, double *out2);
+
 /* Process-global knobs, two kinds.  Returns 0, or -1 for a key this build does not have.
  *
  * (a) ALWAYS THERE - keys that force one of the product's own paths, i.e. a choice the library makes by size or dimension, so that

@@ -15,6 +15,7 @@
 
 #include "pcg_host.h"
 #include "patch.h"
+#include "sens.h"
 
 using namespace remo;
 
@@ -47,6 +48,8 @@ int checked_opts(remo_ctx *ctx, const remo_opts_t *opts_in, remo_opts_t &o) {
 struct Points {
     std::vector<double> z, I;
     std::vector<int32_t> rhs, chunk_begin, eval_slot;   // eval_slot: u_out index or -1
+    std::vector<std::pair<int32_t, int32_t>> fun_reads; // remo_solve_batch_sens: (point, index into fun_z) of the points the functionals read
+    int forward_chunks = 0;                             // chunks [0, forward_chunks) are the batch's right-hand sides, the rest adjoint columns
     std::vector<int32_t> found_init;                    // INT_MAX per point: what launch_locate starts from
     int n() const { return int(z.size()); }
 };
@@ -64,7 +67,23 @@ Points gather_points(const remo_batch *b) {
             for (int q = b->eval_ptr[r]; q < b->eval_ptr[r + 1]; ++q) {
                 p.z.push_back(b->eval_z[q]); p.I.push_back(0.0); p.rhs.push_back(r - c0); p.eval_slot.push_back(q);
             }
+        if (const remo_sens_request *sn = b->sens)   // J_j = sum_i w_i u(z_i): the functionals' points are read like evaluation points
+            for (int j = 0; j < sn->n_fun; ++j)
+                if (sn->fun_rhs[j] >= c0 && sn->fun_rhs[j] < c1)
+                    for (int q = sn->fun_ptr[j]; q < sn->fun_ptr[j + 1]; ++q) {
+                        p.fun_reads.emplace_back(int32_t(p.z.size()), q);
+                        p.z.push_back(sn->fun_z[q]); p.I.push_back(0.0); p.rhs.push_back(sn->fun_rhs[j] - c0); p.eval_slot.push_back(-1);
+                    }
     }
+    p.forward_chunks = int(p.chunk_begin.size());
+    if (const remo_sens_request *sn = b->sens)   // adjoint right-hand sides g_j = sum_i w_i phi(z_i): the same points as sources of strength w_i
+        for (int a0 = 0; a0 < sn->n_fun; a0 += REMO_MAX_RHS) {
+            p.chunk_begin.push_back(int32_t(p.z.size()));
+            for (int j = a0; j < std::min(sn->n_fun, a0 + REMO_MAX_RHS); ++j)
+                for (int q = sn->fun_ptr[j]; q < sn->fun_ptr[j + 1]; ++q) {
+                    p.z.push_back(sn->fun_z[q]); p.I.push_back(sn->fun_w[q]); p.rhs.push_back(j - a0); p.eval_slot.push_back(-1);
+                }
+        }
     p.chunk_begin.push_back(int32_t(p.z.size()));
     p.found_init.assign(p.z.size(), INT_MAX);
     return p;
@@ -105,6 +124,11 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
     need += size_t(nv + 64) * kEllWidth * 12 + size_t(nv + 64) * 8;  // its fixed-width image: ell_col, ell_val (or c32_ell_val); ell_tail
     need += size_t(nv + 64) * (4 * 4 * kmax + 8);                    // fp32 Chebyshev chain of the fp64 solve: c32_z, c32_res, c32_d[0], c32_d[1]; c32_dinv
     if (p.want_amg) need += size_t(nv + 64) * (dim == 2 ? 1536 : 3072) * 2 + (1 << 20);   // multigrid hierarchy of the vertex block + its scratch (amg_setup, amg_to_float)
+    if (b->sens) {   // every forward and adjoint solution stays (sens_take), and the contraction's partial sums
+        const size_t ncomp = size_t(b->sigma_comp);
+        need += size_t(ndof_max) * 8 * size_t(b->n_rhs + b->sens->n_fun);                                 // keep
+        need += size_t(b->sens->n_fun) * size_t(b->n_mat) * ncomp * 8 * (size_t(sens_grid(nt)) + 1);     // part, d_dJ
+    }
     if (o.precision == 1) {   // fp32 copies of the matrix values and of every PCG vector (mixed_buffers)
         need += size_t(nv + 64) * 200 * 8;                           // fp32 sq_a, sq_b
         need += size_t(nnz_max) * 4;                                 // v32
@@ -117,10 +141,10 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
 Plan plan_batch(const remo_batch *b, const remo_opts_t &o, int npts) {
     Plan p;
     const int dim = b->dim;
-    p.kmax = std::min<int>(b->n_rhs, REMO_MAX_RHS);
+    p.kmax = std::min<int>(std::max(b->n_rhs, b->sens ? b->sens->n_fun : 0), REMO_MAX_RHS);   // the adjoint columns run through the same buffers
     // one-shot fp64 solve: no x, only the values the evaluation points read (PcgBuffersT::x_ev); the debug forms of the update
     // (key 25 = 0 writes x there) and the mixed mode's refinement (x64 += x32) need the whole block
-    p.x_ev_only = b->eval_only && g_tune.x_ev && g_tune.x_in_direction && o.precision == 0;
+    p.x_ev_only = b->eval_only && !b->sens && g_tune.x_ev && g_tune.x_in_direction && o.precision == 0;
     // the patch operator is 3D only; a 2D batch always runs on the CSR product, whatever `op` says
     p.want_patch = dim == 3 && (o.op == 3 || o.op == 0);
     p.want_amg = o.preconditioner != 0 && g_tune.amg != 1 &&
@@ -591,6 +615,63 @@ int solve_chunk(const Run &r, const Plan &plan, const System &sys, const DeviceP
     return REMO_OK;
 }
 
+// ---- sensitivities: where the solutions stay, and the contraction ----------------------------------------------------------------
+// Chunk c of the forward columns lies at keep + n * REMO_MAX_RHS * c as a block [n][k_c]; the adjoint chunks follow the n * n_rhs
+// forward values in the same way.
+struct Sens {
+    double *keep = nullptr, *part = nullptr, *d_dJ = nullptr;
+    int grid = 0, nmc = 0;
+    double *block(int64_t n, int n_rhs, bool adjoint, int chunk) const {   // (the adjoint part starts on a 256-byte boundary like every taken buffer)
+        return keep + (adjoint ? (size_t(n) * n_rhs + 31) / 32 * 32 : size_t(0)) + size_t(n) * REMO_MAX_RHS * chunk;
+    }
+};
+
+Sens sens_take(const Run &r, const System &sys) {
+    const remo_batch *b = r.b;
+    Sens sn;
+    sn.grid = sens_grid(b->nt);
+    sn.nmc = b->n_mat * b->sigma_comp;
+    sn.keep = r.ctx->take<double>(size_t(sys.n) * size_t(b->n_rhs + b->sens->n_fun) + 64);
+    sn.part = r.ctx->take<double>(size_t(b->sens->n_fun) * sn.grid * sn.nmc + 1);
+    sn.d_dJ = r.ctx->take<double>(size_t(b->sens->n_fun) * sn.nmc + 1);
+    return sn;
+}
+
+// dJ_j/d(component of material m) = -lambda_j^T A_m u_rhs(j): one pass over the elements per functional, then the workgroups' sums
+void sens_contract(const Run &r, const System &sys, const DevicePoints &dp, const Points &pts, const Sens &sn, std::vector<double> &h_dJ) {
+    remo_ctx *ctx = r.ctx;
+    const remo_batch *b = r.b;
+    const remo_sens_request *rq = b->sens;
+    const DeviceSymbolic &sy = b->sym;
+    hipStream_t s = r.s;
+    if (r.dim == 3 && !ctx->d_B3) {
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->d_B3), sizeof(double) * 600));
+        HIP_TRY(hipMemcpyAsync(ctx->d_B3, ref_factors3(), sizeof(double) * 600, hipMemcpyHostToDevice, s));
+    }
+    const double *tab = (r.dim == 3) ? ctx->d_B3 : sys.d_M;
+    HIP_TRY(hipEventRecord(ctx->ev[4], s));
+    for (int j = 0; j < rq->n_fun; ++j) {
+        const int cf = rq->fun_rhs[j] / REMO_MAX_RHS, ca = j / REMO_MAX_RHS, fa = pts.forward_chunks + ca;
+        SensColumns col;
+        col.xu = sn.block(sys.n, b->n_rhs, false, cf); col.ku = std::min(b->n_rhs - cf * REMO_MAX_RHS, REMO_MAX_RHS); col.cu = rq->fun_rhs[j] % REMO_MAX_RHS;
+        col.xl = sn.block(sys.n, b->n_rhs, true, ca); col.kl = std::min(rq->n_fun - ca * REMO_MAX_RHS, REMO_MAX_RHS); col.cl = j % REMO_MAX_RHS;
+        col.qu0 = pts.chunk_begin[cf]; col.nqu = pts.chunk_begin[cf + 1] - col.qu0;
+        col.ql0 = pts.chunk_begin[fa]; col.nql = pts.chunk_begin[fa + 1] - col.ql0;
+        launch_sens_contract(r.dim, sy.condense, b->sigma_comp > 1, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, sy.eldof, sys.d_C, sys.d_M, tab, col,
+                             dp.d_prhs, dp.d_pI, dp.d_found, dp.d_fint, b->n_mat, sn.part + size_t(j) * sn.grid * sn.nmc, s);
+    }
+    launch_sens_reduce(rq->n_fun, sn.grid, sn.nmc, sn.part, sn.d_dJ, s);
+    HIP_TRY(hipEventRecord(ctx->ev[5], s));
+    h_dJ.assign(size_t(rq->n_fun) * sn.nmc, std::nan(""));
+    if (!h_dJ.empty()) HIP_TRY(hipMemcpyAsync(h_dJ.data(), sn.d_dJ, sizeof(double) * h_dJ.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]);
+    ctx->sens_ms = ms;
+    // per functional: the x rows of both columns once (8 n each), and per element its dof numbers, vertices, material and (2D) metric terms
+    ctx->sens_bytes = double(rq->n_fun) * (16.0 * double(sys.n) + double(b->nt) * (4.0 * r.N + 4.0 * (r.dim + 1) + 4.0 + (r.dim == 2 ? 8.0 * r.NT : 0.0)));
+}
+
 // ---- events -> remo_stats_t -----------------------------------------------------------------------------------------------------
 void fill_timing_stats(const Run &r, const Plan &plan, const System &sys, bool mixed, bool patch_op, const RunTotals &tot) {
     remo_ctx *ctx = r.ctx;
@@ -645,6 +726,10 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
     if (!st) st = &local;
     std::memset(st, 0, sizeof *st);
     std::fill(b->u_out.begin(), b->u_out.end(), std::nan(""));
+    if (b->sens) {
+        if (o.precision == 1) return fail(ctx, REMO_ERR_ARG, "sensitivities are computed in fp64: remo_opts_t.precision = 1 (mixed) is not supported by remo_solve_batch_sens");
+        if (int64_t(b->n_mat) * b->sigma_comp > kSensMaxAcc) return fail(ctx, REMO_ERR_ARG, "too many materials for the sensitivity contraction");
+    }
     b->has_system = false;
     b->amg64 = AmgT<double>{};
     b->amg32 = AmgT<float>{};
@@ -687,6 +772,7 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         if (vb.h_err & 2) return fail(ctx, REMO_ERR_POINT, "source or evaluation point outside the mesh");
         bool patch_op = false;
         if (int rc = choose_operator(r, plan, sys, sv, vb, patch_op)) return rc;
+        const Sens sens = b->sens ? sens_take(r, sys) : Sens{};
 
         // ---- solve, chunk by chunk ----------------------------------------------------------------------------------
         // serialize_solves: batches of other contexts may number and assemble beside this PCG, but not run theirs
@@ -702,10 +788,28 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         for (int c0 = 0; c0 < b->n_rhs; c0 += REMO_MAX_RHS, ++chunk) {
             const int k = std::min(b->n_rhs - c0, REMO_MAX_RHS);
             const int q0 = points.chunk_begin[chunk], nq = points.chunk_begin[chunk + 1] - q0;
+            if (b->sens) b->d_x = sv.buf.x = sens.block(sys.n, b->n_rhs, false, chunk);   // the solution is formed where it stays
             if (int rc = solve_chunk(r, plan, sys, dp, sv, mixed ? &mx : nullptr, k, q0, nq, h_out, tot)) return rc;
         }
         for (int q = 0; q < npts; ++q)
             if (points.eval_slot[q] >= 0) b->u_out[points.eval_slot[q]] = h_out[q];
+        if (const remo_sens_request *rq = b->sens) {   // adjoint columns: same operator, preconditioner and stopping rule; then the contraction
+            for (int a0 = 0, ca = 0; a0 < rq->n_fun; a0 += REMO_MAX_RHS, ++ca, ++chunk) {
+                const int k = std::min(rq->n_fun - a0, REMO_MAX_RHS);
+                const int q0 = points.chunk_begin[chunk], nq = points.chunk_begin[chunk + 1] - q0;
+                b->d_x = sv.buf.x = sens.block(sys.n, b->n_rhs, true, ca);
+                if (int rc = solve_chunk(r, plan, sys, dp, sv, nullptr, k, q0, nq, h_out, tot)) return rc;
+            }
+            std::vector<double> h_dJ;
+            sens_contract(r, sys, dp, points, sens, h_dJ);
+            for (int j = 0; j < rq->n_fun; ++j) rq->J_out[j] = 0.0;
+            for (const auto &fr : points.fun_reads) {   // (fun_reads is ordered by functional within a chunk and fun_ptr ascends: a fixed order of additions)
+                int j = 0;
+                while (fr.second >= rq->fun_ptr[j + 1]) ++j;
+                rq->J_out[j] += rq->fun_w[fr.second] * h_out[fr.first];
+            }
+            if (!h_dJ.empty()) std::memcpy(rq->dJ_out, h_dJ.data(), sizeof(double) * h_dJ.size());
+        }
         fill_timing_stats(r, plan, sys, mixed, patch_op, tot);
         st->ms_total = now_ms() - t_start;
         if (tot.ret == REMO_NOT_CONVERGED) ctx->err = "PCG did not reach rtol within maxsteps";

@@ -82,6 +82,7 @@ void remo_ctx_destroy(remo_ctx_t *ctx) {
     if (ctx->d_M2) hipFree(ctx->d_M2);
     if (ctx->d_M3) hipFree(ctx->d_M3);
     if (ctx->d_M2q) hipFree(ctx->d_M2q);
+    if (ctx->d_B3) hipFree(ctx->d_B3);
     if (ctx->d_err) hipFree(ctx->d_err);
     if (ctx->progress) hipHostFree(ctx->progress);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
@@ -227,6 +228,65 @@ int remo_solve_batch_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_
                             const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
                             const double *eval_z, double *u_out, const remo_opts_t *opts, remo_stats_t *stats) {
     return solve_batch(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, opts, stats, true);
+}
+
+// remo_solve_batch_sens / _tensor: the same one-shot batch with the functionals attached (batch_run.hip solves the adjoint columns
+// after the forward ones and contracts them, sens.hip)
+static int solve_batch_sens(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
+                            const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                            const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
+                            const double *fun_z, const double *fun_w, double *J_out, double *dJ_out, const remo_opts_t *opts,
+                            remo_stats_t *stats, bool tensor) {
+    if (!ctx) return REMO_ERR_ARG;
+    const int ncomp = (tensor && mesh) ? ((mesh->dim == 2) ? 3 : 6) : 1;
+    auto nan_fill = [&]() {
+        if (u_out && eval_ptr && n_rhs > 0)
+            for (int i = 0; i < eval_ptr[n_rhs]; ++i) u_out[i] = std::nan("");
+        for (int j = 0; j < n_fun && J_out; ++j) J_out[j] = std::nan("");
+        if (dJ_out && n_fun > 0 && n_mat > 0)
+            for (size_t i = 0; i < size_t(n_fun) * size_t(n_mat) * ncomp; ++i) dJ_out[i] = std::nan("");
+    };
+    nan_fill();
+    if (n_fun < 0 || (n_fun > 0 && (!fun_rhs || !fun_ptr || !J_out || !dJ_out))) return fail(ctx, REMO_ERR_ARG, "functional arrays missing");
+    if (n_fun > 0) {
+        if (fun_ptr[0] != 0) return fail(ctx, REMO_ERR_ARG, "fun_ptr must start at 0");
+        for (int j = 0; j < n_fun; ++j) {
+            if (fun_ptr[j + 1] < fun_ptr[j]) return fail(ctx, REMO_ERR_ARG, "fun_ptr not monotone");
+            if (fun_rhs[j] < 0 || fun_rhs[j] >= n_rhs) return fail(ctx, REMO_ERR_ARG, "fun_rhs names no right-hand side of the batch");
+        }
+        if (fun_ptr[n_fun] > 0 && (!fun_z || !fun_w)) return fail(ctx, REMO_ERR_ARG, "functional arrays missing");
+        for (int q = 0; q < fun_ptr[n_fun]; ++q)
+            if (!std::isfinite(fun_w[q])) return fail(ctx, REMO_ERR_ARG, "non-finite functional weight");
+    }
+    remo_batch_t *b = nullptr;
+    int rc = batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, &b, true, tensor);
+    if (rc != REMO_OK) return rc;
+    const remo_sens_request rq{n_fun, fun_rhs, fun_ptr, fun_z, fun_w, J_out, dJ_out};
+    b->sens = &rq;
+    b->eval_only = true;
+    rc = remo_batch_run(ctx, b, opts, stats);
+    if (rc >= 0 && u_out) remo_batch_fetch(ctx, b, u_out);
+    if (rc < 0) nan_fill();
+    remo_batch_destroy(ctx, b);
+    return rc;
+}
+
+int remo_solve_batch_sens(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
+                          const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                          const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
+                          const double *fun_z, const double *fun_w, double *J_out, double *dJ_out, const remo_opts_t *opts,
+                          remo_stats_t *stats) {
+    return solve_batch_sens(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_fun, fun_rhs, fun_ptr, fun_z, fun_w,
+                            J_out, dJ_out, opts, stats, false);
+}
+
+int remo_solve_batch_sens_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor, int32_t n_rhs,
+                                 const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                                 const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
+                                 const double *fun_z, const double *fun_w, double *J_out, double *dJ_out, const remo_opts_t *opts,
+                                 remo_stats_t *stats) {
+    return solve_batch_sens(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_fun, fun_rhs, fun_ptr, fun_z,
+                            fun_w, J_out, dJ_out, opts, stats, true);
 }
 
 int remo_batch_eval(remo_ctx_t *ctx, remo_batch_t *b, int32_t rhs, int32_t npts, const double *z, double *u_out) {

@@ -411,4 +411,11 @@ int remo_debug_tune(int32_t key, int32_t value) {
 #endif
 }
 
+int remo_debug_sens_timing(remo_ctx_t *ctx, double *out2) {
+    if (!ctx || !out2) return REMO_ERR_ARG;
+    out2[0] = ctx->sens_ms;
+    out2[1] = ctx->sens_bytes;
+    return REMO_OK;
+}
+
 }  // extern "C"

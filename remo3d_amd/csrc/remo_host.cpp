@@ -7,6 +7,7 @@
 #include "remo_internal.h"
 #include "fem_p3.h"
 #include "symbolic.h"
+#include "sens.h"
 
 namespace remo {
 
@@ -60,6 +61,14 @@ int remo_host_element_matrix_tensor(int32_t dim, const double *X, const double *
             for (int j = 0; j < 20; ++j) K_out[i * 20 + j] = kentry<3>(C, M, i, j);
     }
     return REMO_OK;
+}
+
+int remo_host_sens_element(int32_t dim, const double *X, int32_t tensor, const double *xl, const double *xu, double *out) {
+    if ((dim != 2 && dim != 3) || !X || !xl || !xu || !out) return REMO_ERR_ARG;
+    bool ok;
+    if (dim == 2) ok = tensor ? sens_element<2, true>(X, ref_tables(2), xl, xu, out) : sens_element<2, false>(X, ref_tables(2), xl, xu, out);
+    else ok = tensor ? sens_element<3, true>(X, ref_factors3(), xl, xu, out) : sens_element<3, false>(X, ref_factors3(), xl, xu, out);
+    return ok ? REMO_OK : REMO_ERR_MESH;
 }
 
 double remo_host_factor_error(void) { return ref_factors3_error(); }

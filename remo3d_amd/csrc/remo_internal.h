@@ -88,6 +88,8 @@ struct remo_ctx {
     std::string err;
     remo::Arena ar;
     double *d_M2 = nullptr, *d_M3 = nullptr, *d_M2q = nullptr;   // reference tensors: exact 2D / 3D, 2D by the degree-4 rule
+    double *d_B3 = nullptr;                  // factors of the 3D tensors (ref_factors3) for the sensitivity contraction, uploaded by its first use
+    double sens_ms = 0.0, sens_bytes = 0.0;  // last remo_solve_batch_sens: HIP-event time and algorithmic bytes of the contraction launches (remo_debug_sens_timing)
     remo::PcgProgress *progress = nullptr;  // mapped, coherent host memory
     remo::PcgProgress *progress_dev = nullptr;
     int progress_len = 0;
@@ -125,6 +127,15 @@ struct remo_ctx {
     }
 };
 
+// What remo_solve_batch_sens adds to a batch: linear functionals J_j = sum_i w[i] u_rhs[j](z[i]) and where their values and
+// derivatives go (host pointers of the caller, valid for the duration of the call only).
+struct remo_sens_request {
+    int n_fun = 0;
+    const int32_t *fun_rhs = nullptr, *fun_ptr = nullptr;
+    const double *fun_z = nullptr, *fun_w = nullptr;
+    double *J_out = nullptr, *dJ_out = nullptr;
+};
+
 struct remo_batch {
     int dim = 0;
     int64_t nv = 0, nt = 0, nbf = 0;
@@ -139,6 +150,7 @@ struct remo_batch {
     int32_t *d_mat = nullptr, *d_conn = nullptr, *d_bconn = nullptr;
     uint8_t *d_bdir = nullptr;
     bool pooled = false;     // the six arrays live in the context's input pool (remo_solve_batch): not freed with the batch
+    const remo_sens_request *sens = nullptr;   // remo_solve_batch_sens: adjoint solves + contraction after the forward solves (batch_run.hip)
     bool eval_only = false;  // remo_solve_batch: nothing reads the solution after the run but the evaluation points (PcgBuffersT::x_ev)
     // last system (pointers into the context arena; valid until the next run on the context)
     bool has_system = false;

@@ -160,6 +160,70 @@ def ti_conductivity(sigma_h, sigma_v, dip_rad, dim):
 
 
 # ---------------------------------------------------------------------------------------------
+# Materials of a window <-> entries of the formation table (sensitivities, Model.simulate_logs)
+
+
+def entry_id_table(formation_parameters):
+    """5-column copy of the formation table whose resistivity columns hold entry identifiers 1 + 2 * layer (RTFZ) and
+    2 + 2 * layer (RTUZ) instead of resistivities, NaN kept where the table has NaN.  Windowed like the table itself
+    (select_data_range / select_netgen_data_range) it names the table entry behind every material: see material_entries."""
+    fp = np.asarray(formation_parameters, dtype=float)
+    ids = np.array(fp[:, :5], copy=True)
+    layer = np.arange(fp.shape[0], dtype=float)
+    for c in (3, 4):
+        ids[:, c] = np.where(np.isnan(fp[:, c]), np.nan, 1.0 + 2.0 * layer + (c - 3))
+    return ids
+
+
+def material_entries(sigma_of_ids):
+    """(layer, table column) of every material, from the `sigma` list a windowing function returned for entry_id_table(...):
+    None for the mud (material 0), else (layer, 3) for RTFZ or (layer, 4) for RTUZ.  Every quirk of the windowing applies to the
+    identifiers as it does to the resistivities (a dropped flushed zone: the layer's one material is its RTFZ entry)."""
+    out = [None]
+    for s in list(sigma_of_ids)[1:]:
+        k = int(round(1.0 / float(s))) - 1
+        out.append((k // 2, 3 + k % 2))
+    return out
+
+
+def resistivity_sensitivity(dJ, entries, formation_parameters, scale, normal=None):
+    """Chain rule from dJ/dsigma of the materials of one window to the table's resistivities, for one functional:
+    returns (dRa/dR [n_layers, n_cols], dRa/dRm) with dRa/dR = scale * sum_{materials of the entry} dJ/dsigma * (-1 / R^2) and
+    scale = sign(K J) K (/ 2 in 3D).  The columns follow the table from column 2 on (RDFZ, RTFZ, RTUZ, and RVUZ when present): RDFZ
+    is a radius, not a resistivity, and stays NaN; entries no material of the window holds are 0, NaN where the table has NaN.
+    dJ: [n_mat] (scalar sigma) or [n_mat, dim, dim] symmetric G with dJ = G : dSigma (tensor sigma).  For a tensor material
+    dJ/dsigma_h = G : (I - n n^T) and dJ/dsigma_v = G : n n^T with `normal` the bedding normal of ti_conductivity; with an RVUZ
+    column the undisturbed zone's sigma_h = 1 / RTUZ and sigma_v = 1 / RVUZ (RVUZ NaN: isotropic, all of it goes to RTUZ)."""
+    fp = np.asarray(formation_parameters, dtype=float)
+    dJ = np.asarray(dJ, dtype=float)
+    out = np.where(np.isnan(fp[:, 2:]), np.nan, 0.0)
+    out[:, 0] = np.nan
+    has_rv = fp.shape[1] >= 6
+
+    def parts(g):
+        if g.ndim == 0:
+            return float(g), 0.0, float(g)     # (d/dsigma_h, d/dsigma_v, d/dsigma of an isotropic material)
+        n = np.asarray(normal, dtype=float)
+        P = np.outer(n, n)
+        gv = float(np.sum(g * P))
+        return float(np.trace(g)) - gv, gv, float(np.trace(g))
+
+    mud = scale * parts(dJ[0])[2]              # d/dsigma_mud; the caller applies -1 / Rm^2
+    for m, e in enumerate(entries):
+        if e is None:
+            continue
+        layer, col = e
+        gh, gv, giso = parts(dJ[m])
+        R = fp[layer, col]
+        if col == 4 and has_rv and not np.isnan(fp[layer, 5]):
+            out[layer, 2] += scale * gh * (-1.0 / R ** 2)
+            out[layer, 3] += scale * gv * (-1.0 / fp[layer, 5] ** 2)
+        else:
+            out[layer, col - 2] += scale * giso * (-1.0 / R ** 2)
+    return out, mud
+
+
+# ---------------------------------------------------------------------------------------------
 # Netgen path (2D only): remo3d/netgen_functions.py:12-118
 
 

@@ -156,6 +156,8 @@ class Model:
         self.ctx = None
         self.extra_ctx = []
         self.logs = None
+        self.sensitivities = None      # simulate_logs(sensitivities=True): per tool dRa/dR [n_depths, n_layers, n_cols]
+        self.mud_sensitivity = None    # ... and dRa/dRm [n_depths]
         self.timing = {}
 
     # -- complete procedure (remo3d.py:65-174) ---------------------------------------------------
@@ -334,8 +336,13 @@ class Model:
     def simulate_logs(self, measurement_depths, domain_radius=50, batch_size=5, mesh_generator="auto", preconditioner="multigrid",
                       condense=True, mesh_provider: Optional[Callable] = None, mesh_scale: Optional[float] = None, rtol: float = 1e-8,
                       maxsteps: int = 1000, verbose: bool = True, mesh_workers: Optional[int] = None, precision: str = "fp64",
-                      schedule: str = "static", solver_options: Optional[dict] = None):
-        """solver_options: further keywords of solver.make_opts for every batch (op, coarse, quadrature, assemble, ...)."""
+                      schedule: str = "static", solver_options: Optional[dict] = None, sensitivities: bool = False):
+        """solver_options: further keywords of solver.make_opts for every batch (op, coarse, quadrature, assemble, ...).
+        sensitivities: also fill self.sensitivities[tool] = dRa/dR in ohm m per ohm m, [n_depths, n_layers, n_cols] with the
+        columns of the formation table from column 2 on (RDFZ - a radius, always NaN -, RTFZ, RTUZ, and RVUZ when present; 0 where
+        the batch's window does not hold the entry, NaN where the table has NaN or the batch failed), and self.mud_sensitivity[tool]
+        = dRa/dRm [n_depths] (Rm: the mud resistivity of the record's batch), by adjoint solves (remo_solve_batch_sens: about twice
+        the solves of the plain sweep); fp64 only."""
         from . import solver, sweep
         extra = dict(solver_options or {})
         start = time.time()
@@ -386,6 +393,12 @@ class Model:
 
         formation_h = self.formation_model[:, :5]
         formation_v = self._vertical_formation_model()
+        formation_ids = geometry.entry_id_table(self.formation_model) if sensitivities else None
+        n_layers, n_cols = self.formation_model.shape[0], self.formation_model.shape[1] - 2
+        sens_res = np.zeros((len(measurement_depths), n_tools, n_layers, n_cols)) if sensitivities else None
+        mud_res = np.zeros((len(measurement_depths), n_tools)) if sensitivities else None
+        sens_ti = sensitivities and self.formation_model.shape[1] >= 6 and bool(np.any(~np.isnan(self.formation_model[:, 5])))
+        ti_normal = (np.array([np.sin(self.dip_rad), 0.0, np.cos(self.dip_rad)]) if is3d else np.array([0.0, 1.0]))   # geometry.ti_conductivity
 
         def window_of(formation, bi):
             if netgen_path:   # the reference's default 2D windowing (remo3d.py:776-779, worker.py:94)
@@ -497,12 +510,27 @@ class Model:
                     vs = vertex_solver_options(3, mesh.n_nodes, conforming_default, n_ctx_total)
                     if vs:
                         bopts = solver.make_opts(**dict(base_kw, **vs))
+                if sensitivities:     # the table entry behind every material: the identifier table through the same windowing
+                    functionals, fun_readers = tasks.batch_functionals(batch, self.tools)
+                    entries = geometry.material_entries(window_of(formation_ids, bi)[2])
+                    if len(entries) != len(sigma):
+                        raise RuntimeError("windowing of the entry identifiers gave different materials")
+                    if sens_ti and np.ndim(sigma) == 1:     # dRa/dRTUZ and dRa/dRVUZ apart need the tensor derivative, also where the window is isotropic
+                        sigma = geometry.ti_conductivity(sigma, sigma, self.dip_rad if is3d else 0.0, dim)
                 c = free_ctx.get()
                 try:
-                    outs, st, rc = c.solve_batch(mesh, sigma, sources, evals, bopts)
+                    if sensitivities:
+                        outs, J, dJ, st, rc = c.solve_batch_sens(mesh, sigma, sources, evals, functionals, bopts)
+                    else:
+                        outs, st, rc = c.solve_batch(mesh, sigma, sources, evals, bopts)
                 finally:
                     free_ctx.put(c)
                 t2 = time.time()
+                if sensitivities:     # Ra = |K J| (/ 2 in 3D): dRa/dR = sign(K J) K (/ 2) * dJ/dsigma * (-1 / R^2)
+                    for j, (di, ti, K) in enumerate(fun_readers):
+                        scale = np.sign(K * J[j]) * K / (2.0 if dim == 3 else 1.0)
+                        sens_res[di, ti], dmud = geometry.resistivity_sensitivity(dJ[j], entries, self.formation_model, scale, ti_normal)
+                        mud_res[di, ti] = dmud * (-1.0 / mud[bi] ** 2)
                 n = 0
                 for u, rd in zip(outs, readers):
                     for (di, ti, K, o, m) in rd:
@@ -514,6 +542,9 @@ class Model:
             except Exception as ex:
                 for di, ti in rows:      # any failure in a batch -> NaN for its records (worker.py:135-138: a bare except)
                     results[di, ti] = np.nan
+                    if sensitivities:
+                        sens_res[di, ti] = np.nan
+                        mud_res[di, ti] = np.nan
                 with lock:               # ... but not silently: the reference's worker at least shows it on stderr
                     acc["failed_batches"] += 1
                     if acc["first_error"] is None:
@@ -548,6 +579,12 @@ class Model:
         t_mesh, t_solve, n_points = acc["mesh"], acc["solve"], acc["points"]
         bq.check_complete()          # collective: every batch was taken exactly once over the ranks
         results = sweep.combine(results)
+        if sensitivities:     # the same pattern as the logs: every rank has zeros outside its own records
+            sens_res, mud_res = sweep.combine(sens_res), sweep.combine(mud_res)
+            self.sensitivities = {name: sens_res[:, i] for i, name in enumerate(self.tools.keys())}
+            self.mud_sensitivity = {name: mud_res[:, i] for i, name in enumerate(self.tools.keys())}
+        else:
+            self.sensitivities = self.mud_sensitivity = None
         self.logs = {name: np.vstack([measurement_depths, results[:, i]]).T for i, name in enumerate(self.tools.keys())}
         self.timing = dict(total_s=time.time() - start, mesh_s=t_mesh, solve_s=t_solve, points=n_points, batches=len(batches),
                            my_batches=len(mine), world_size=sweep.world_size(), schedule=schedule, busy_s=t_busy,

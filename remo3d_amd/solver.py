@@ -146,6 +146,58 @@ class Context:
             raise RemoError(rc, self.last_error())
         return [out[eval_ptr[k]:eval_ptr[k + 1]] for k in range(len(evals))], st.as_dict(), rc
 
+    def solve_batch_sens(self, mesh, sigma, sources, evals, functionals, opts: Optional[RemoOpts] = None, raise_on_error=True):
+        """One-shot remo_solve_batch_sens: the batch of solve_batch plus linear functionals of the potentials and their derivatives
+        with respect to the materials' conductivities (adjoint solves).  functionals: list of (rhs, z array, w array),
+        J = sum_i w[i] * u_rhs(z[i]).  Returns (potentials, J [n_fun], dJ, stats, rc) with dJ [n_fun, n_mat] for sigma [n_mat] and
+        [n_fun, n_mat, dim, dim] for tensors: symmetric G with dJ = G : dSigma for symmetric dSigma (the library's triangle holds
+        both halves of an off-diagonal pair; each half gets half of it here)."""
+        sigma, tensor = sigma_table(sigma, int(mesh.dim))
+        src_ptr, sz, sI, eval_ptr, ez = _rhs_arrays(sources, evals)
+        n_fun = len(functionals)
+        fun_rhs = np.ascontiguousarray([f[0] for f in functionals], dtype=np.int32)
+        fun_ptr = np.zeros(n_fun + 1, dtype=np.int32)
+        fz, fw = [], []
+        for j, (_, z, w) in enumerate(functionals):
+            z = np.atleast_1d(np.asarray(z, dtype=np.float64)); w = np.atleast_1d(np.asarray(w, dtype=np.float64))
+            if z.shape != w.shape:
+                raise ValueError("functional points and weights differ in length")
+            fz.append(z); fw.append(w); fun_ptr[j + 1] = fun_ptr[j] + z.size
+        cat = lambda xs: np.ascontiguousarray(np.concatenate(xs) if xs else np.zeros(0), dtype=np.float64)
+        fz, fw = cat(fz), cat(fw)
+        ms, keep = _lib.mesh_struct(mesh)
+        d = int(mesh.dim)
+        n_mat, nc = len(sigma), (sigma.shape[1] if tensor else 1)
+        out = np.full(int(eval_ptr[-1]), np.nan)
+        J = np.full(n_fun, np.nan)
+        dJ = np.full((n_fun, n_mat, nc), np.nan)
+        st = RemoStats()
+        o = opts if opts is not None else make_opts()
+        entry = self._L.remo_solve_batch_sens_tensor if tensor else self._L.remo_solve_batch_sens
+        rc = entry(self._h, C.byref(ms), n_mat, ptr(sigma, C.c_double), len(sources),
+                   ptr(src_ptr, C.c_int32), ptr(sz, C.c_double), ptr(sI, C.c_double),
+                   ptr(eval_ptr, C.c_int32), ptr(ez, C.c_double), ptr(out, C.c_double),
+                   n_fun, ptr(fun_rhs, C.c_int32), ptr(fun_ptr, C.c_int32), ptr(fz, C.c_double), ptr(fw, C.c_double),
+                   ptr(J, C.c_double), ptr(dJ, C.c_double), C.byref(o), C.byref(st))
+        if rc < 0 and raise_on_error:
+            raise RemoError(rc, self.last_error())
+        if tensor:
+            iu = np.triu_indices(d)
+            G = np.zeros((n_fun, n_mat, d, d))
+            half = np.where(iu[0] == iu[1], 1.0, 0.5)
+            G[:, :, iu[0], iu[1]] = dJ * half
+            G[:, :, iu[1], iu[0]] = dJ * half
+            dJ = G
+        else:
+            dJ = dJ[:, :, 0]
+        return [out[eval_ptr[k]:eval_ptr[k + 1]] for k in range(len(evals))], J, dJ, st.as_dict(), rc
+
+    def sens_timing(self):
+        """(ms, algorithmic bytes) of the contraction launches of the last solve_batch_sens on this context (remo_debug_sens_timing)."""
+        out = np.zeros(2)
+        self._L.remo_debug_sens_timing(self._h, ptr(out, C.c_double))
+        return float(out[0]), float(out[1])
+
     def batch(self, mesh, sigma, sources, evals) -> "Batch":
         return Batch(self, mesh, sigma, sources, evals)
 

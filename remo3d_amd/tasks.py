@@ -135,6 +135,29 @@ def batch_rhs(batch: Batch, tools: Dict[str, np.ndarray]):
     return sources, evals, readers
 
 
+def batch_functionals(batch: Batch, tools: Dict[str, np.ndarray]):
+    """The linear functional behind every record of a batch (worker.py:113-131), in the form remo_solve_batch_sens takes:
+    returns (functionals, readers) with functionals[j] = (rhs, z array, w array) - J = u_N - u_M (two measuring electrodes, in the
+    order of the tool table) or u_M (one) of right-hand side `rhs` - and readers[j] = (depth_index, tool_index, K), so that
+    Ra = |K J| (/ 2 in 3D), the value apparent_resistivity gives.  Records with another electrode count get no functional."""
+    names = list(tools.keys())
+    functionals, readers = [], []
+    for k, s in enumerate(batch.solves):
+        for r in s.records:
+            t = tools[names[r.tool_index]]
+            geo = t[0, :3] + r.offset
+            meas = geo[t[1, :3] == 0]
+            if len(meas) == 2:
+                w = np.array([-1.0, 1.0])
+            elif len(meas) == 1:
+                w = np.array([1.0])
+            else:
+                continue
+            functionals.append((k, np.asarray(meas, dtype=float), w))
+            readers.append((r.depth_index, r.tool_index, float(t[0, 3])))
+    return functionals, readers
+
+
 def apparent_resistivity(u: np.ndarray, n_meas: int, K: float, dim: int) -> float:
     """Ra from potentials at the measuring electrodes (worker.py:124-131): |K (u2 - u1)| or
     |K u1|, halved in 3D because only a half-space is meshed."""
