@@ -211,6 +211,34 @@ int remo_solve_batch_sens_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32
                                  const remo_opts_t *opts, remo_stats_t *stats);
 
 /*
+ * The same call plus the derivatives with respect to caller-defined GROUPS of elements - a pixel of a grid, one element, anything
+ * (added within ABI 7: additive, detected by the presence of the symbols).  group[mesh->n_elems] labels every element, in the
+ * caller's element order, with an id in [0, n_group), or -1 for "in no group".  With sigma_e = sigma_mat(e) + p_group(e),
+ *     dJg_out[(j * n_group + g) * nc + c] = dJ_j/dp_g = -sum_{e in g} lambda_e^T (dK_e / d component c) u_e,
+ * components as in dJ_out (nc = 1, or 3 / 6 for the tensor entry, off-diagonal entries carrying both halves).  A group may mix
+ * materials; a group without elements gets 0; n_group is bounded by memory only (n_group = n_elems with group[e] = e is the
+ * per-element map).  Every group's sum has a fixed order that depends only on the mesh and the grouping (no floating-point
+ * atomics): with op = 2 dJg_out is reproducible bit for bit.  u_out, J_out and dJ_out are exactly what remo_solve_batch_sens
+ * returns for the same inputs (the material pass runs as it does there).
+ * Errors: n_group < 1, group == NULL or an id outside [-1, n_group) give REMO_ERR_ARG before any device work, all outputs
+ * NaN-filled; everything else as remo_solve_batch_sens (precision = 1 gives REMO_ERR_ARG).
+ */
+int remo_solve_batch_sens_groups(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma,
+                                 int32_t n_rhs, const int32_t *src_ptr, const double *src_z, const double *src_I,
+                                 const int32_t *eval_ptr, const double *eval_z, double *u_out,
+                                 int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr, const double *fun_z, const double *fun_w,
+                                 int32_t n_group, const int32_t *group /*[mesh->n_elems], caller's element order, -1 = in no group*/,
+                                 double *J_out /*[n_fun]*/, double *dJ_out /*[n_fun * n_mat]*/, double *dJg_out /*[n_fun * n_group]*/,
+                                 const remo_opts_t *opts, remo_stats_t *stats);
+int remo_solve_batch_sens_groups_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor,
+                                        int32_t n_rhs, const int32_t *src_ptr, const double *src_z, const double *src_I,
+                                        const int32_t *eval_ptr, const double *eval_z, double *u_out,
+                                        int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr, const double *fun_z, const double *fun_w,
+                                        int32_t n_group, const int32_t *group,
+                                        double *J_out /*[n_fun]*/, double *dJ_out /*[n_fun * n_mat * nc]*/, double *dJg_out /*[n_fun * n_group * nc]*/,
+                                        const remo_opts_t *opts, remo_stats_t *stats);
+
+/*
  * Staged form of the same work, for callers that keep a batch resident (bench.py: inputs are in
  * HBM before the timed region).  create = validate + upload; run = numbering, pattern, assembly,
  * PCG, evaluation, all RHS; fetch = potentials to the host.

@@ -49,6 +49,11 @@ int remo_debug_grid_barrier(remo_ctx_t *ctx, int32_t nblocks, int32_t nbar, doub
  * launches of all functionals and the reduction), [1] = their algorithmic bytes (per functional the x rows of the forward and the
  * adjoint column once, per element its dof numbers, vertices and material). */
 int remo_debug_sens_timing(remo_ctx_t *ctx, double *out2);
+/* The group path of the last remo_solve_batch_sens_groups on this context, ms by HIP events: out4[0] = the group order (upload of the
+ * group array, keys, radix sort, offsets; once per batch); and, only from a run with remo_opts_t.time_kernels set (it then
+ * synchronises after every functional), summed over the functionals: [1] = the material pass, [2] = the per-element pass,
+ * [3] = the group sums.  0 where not measured. */
+int remo_debug_sens_group_timing(remo_ctx_t *ctx, double *out4);
 
 /* Process-global knobs, two kinds.  Returns 0, or -1 for a key this build does not have.
  *

@@ -50,11 +50,13 @@ class RemoStats(C.Structure):
 
 # include/remo3d_hip.h: the drop-in boundary + inspection hooks of the parity tests
 EXPORTS = ["remo_abi_version", "remo_opts_default", "remo_ctx_create", "remo_ctx_destroy", "remo_last_error",
-           "remo_solve_batch", "remo_solve_batch_tensor", "remo_solve_batch_sens", "remo_solve_batch_sens_tensor", "remo_batch_create", "remo_batch_create_tensor", "remo_batch_run", "remo_batch_fetch", "remo_batch_destroy",
+           "remo_solve_batch", "remo_solve_batch_tensor", "remo_solve_batch_sens", "remo_solve_batch_sens_tensor", "remo_solve_batch_sens_groups", "remo_solve_batch_sens_groups_tensor", "remo_batch_create", "remo_batch_create_tensor", "remo_batch_run", "remo_batch_fetch", "remo_batch_destroy",
            "remo_batch_eval", "remo_batch_get_system", "remo_batch_get_vectors", "remo_batch_apply_coarse", "remo_batch_spmv",
            "remo_host_element_matrix", "remo_host_element_matrix_tensor", "remo_host_sens_element", "remo_host_factor_error", "remo_host_symbolic"]
 # include/remo3d_hip_debug.h: probes and tuning knobs (tests, tools, bench.py's `box` record) - not part of the boundary
-DEBUG_EXPORTS = ["remo_debug_stream", "remo_debug_clock", "remo_debug_device", "remo_debug_cache_gather", "remo_debug_xcc", "remo_debug_tune", "remo_debug_patch_phases", "remo_debug_patch_phases_p", "remo_debug_grid_barrier", "remo_debug_sens_timing"]
+DEBUG_EXPORTS = ["remo_debug_stream", "remo_debug_clock", "remo_debug_device", "remo_debug_cache_gather", "remo_debug_xcc", "remo_debug_tune", "remo_debug_patch_phases", "remo_debug_patch_phases_p", "remo_debug_grid_barrier", "remo_debug_sens_timing", "remo_debug_sens_group_timing"]
+
+SENS_GROUPS_ARGTYPES = []     # argument list of remo_solve_batch_sens_groups / _tensor, filled by load()
 
 _lib = None
 
@@ -87,6 +89,14 @@ def load():
     L.remo_solve_batch_sens.argtypes = batch_args + sens_args
     L.remo_solve_batch_sens_tensor.restype = C.c_int
     L.remo_solve_batch_sens_tensor.argtypes = batch_args + sens_args
+    # ... fun_z, fun_w, n_group, group, J_out, dJ_out, dJg_out, opts, stats
+    SENS_GROUPS_ARGTYPES[:] = batch_args + [dp, C.c_int32, ip, ip, dp, dp, C.c_int32, ip, dp, dp, dp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]
+    L.remo_solve_batch_sens_groups.restype = C.c_int
+    L.remo_solve_batch_sens_groups.argtypes = list(SENS_GROUPS_ARGTYPES)
+    L.remo_solve_batch_sens_groups_tensor.restype = C.c_int
+    L.remo_solve_batch_sens_groups_tensor.argtypes = list(SENS_GROUPS_ARGTYPES)
+    L.remo_debug_sens_group_timing.restype = C.c_int
+    L.remo_debug_sens_group_timing.argtypes = [vp, dp]
     L.remo_host_sens_element.restype = C.c_int
     L.remo_host_sens_element.argtypes = [C.c_int32, dp, C.c_int32, dp, dp, dp]
     L.remo_debug_sens_timing.restype = C.c_int

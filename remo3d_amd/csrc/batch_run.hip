@@ -128,6 +128,13 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
         const size_t ncomp = size_t(b->sigma_comp);
         need += size_t(ndof_max) * 8 * size_t(b->n_rhs + b->sens->n_fun);                                 // keep
         need += size_t(b->sens->n_fun) * size_t(b->n_mat) * ncomp * 8 * (size_t(sens_grid(nt)) + 1);     // part, d_dJ
+        if (b->sens->group) {   // sums per group of elements (sens_take)
+            const size_t ng = size_t(b->sens->n_group);
+            need += size_t(nt) * 4 * 5 + (ng + 2) * 4;                                                    // d_group, keys_in, ids, keys, perm; off
+            need += sens_group_sort_bytes(nt, b->sens->n_group) + 256;                                    // rocPRIM's temporary storage
+            need += size_t(nt) * ncomp * 8 + size_t(sens_group_chunks(nt)) * 2 * ncomp * 8;               // ev (one functional at a time), cpart
+            need += size_t(b->sens->n_fun) * ng * ncomp * 8 + 16 * 256;                                   // d_dJg (+ the alignment of these takes)
+        }
     }
     if (o.precision == 1) {   // fp32 copies of the matrix values and of every PCG vector (mixed_buffers)
         need += size_t(nv + 64) * 200 * 8;                           // fp32 sq_a, sq_b
@@ -621,6 +628,13 @@ int solve_chunk(const Run &r, const Plan &plan, const System &sys, const DeviceP
 struct Sens {
     double *keep = nullptr, *part = nullptr, *d_dJ = nullptr;
     int grid = 0, nmc = 0;
+    // groups of elements: the caller's array, the sort's input and output, the segment offsets, one functional's element values,
+    // the chunk sums of long segments, and every functional's sums
+    int32_t *d_group = nullptr, *ids = nullptr, *perm = nullptr, *off = nullptr;
+    uint32_t *keys_in = nullptr, *keys = nullptr;
+    void *sort_tmp = nullptr;
+    size_t sort_bytes = 0;
+    double *ev = nullptr, *cpart = nullptr, *d_dJg = nullptr;
     double *block(int64_t n, int n_rhs, bool adjoint, int chunk) const {   // (the adjoint part starts on a 256-byte boundary like every taken buffer)
         return keep + (adjoint ? (size_t(n) * n_rhs + 31) / 32 * 32 : size_t(0)) + size_t(n) * REMO_MAX_RHS * chunk;
     }
@@ -634,10 +648,23 @@ Sens sens_take(const Run &r, const System &sys) {
     sn.keep = r.ctx->take<double>(size_t(sys.n) * size_t(b->n_rhs + b->sens->n_fun) + 64);
     sn.part = r.ctx->take<double>(size_t(b->sens->n_fun) * sn.grid * sn.nmc + 1);
     sn.d_dJ = r.ctx->take<double>(size_t(b->sens->n_fun) * sn.nmc + 1);
+    if (b->sens->group) {
+        const size_t nt = size_t(b->nt), ng = size_t(b->sens->n_group);
+        sn.d_group = r.ctx->take<int32_t>(nt); sn.keys_in = r.ctx->take<uint32_t>(nt); sn.ids = r.ctx->take<int32_t>(nt);
+        sn.keys = r.ctx->take<uint32_t>(nt); sn.perm = r.ctx->take<int32_t>(nt);
+        sn.off = r.ctx->take<int32_t>(ng + 2);
+        sn.sort_bytes = sens_group_sort_bytes(b->nt, b->sens->n_group);
+        sn.sort_tmp = r.ctx->take<char>(sn.sort_bytes + 256);
+        sn.ev = r.ctx->take<double>(nt * size_t(b->sigma_comp));
+        sn.cpart = r.ctx->take<double>(size_t(sens_group_chunks(b->nt)) * 2 * size_t(b->sigma_comp));
+        sn.d_dJg = r.ctx->take<double>(size_t(b->sens->n_fun) * ng * size_t(b->sigma_comp) + 1);
+    }
     return sn;
 }
 
 // dJ_j/d(component of material m) = -lambda_j^T A_m u_rhs(j): one pass over the elements per functional, then the workgroups' sums
+// With groups: the elements are ordered by group once, then per functional the material pass as before (dJ_out has the bits of
+// remo_solve_batch_sens), the per-element pass into the one ev buffer, and the sums of its segments.
 void sens_contract(const Run &r, const System &sys, const DevicePoints &dp, const Points &pts, const Sens &sn, std::vector<double> &h_dJ) {
     remo_ctx *ctx = r.ctx;
     const remo_batch *b = r.b;
@@ -649,8 +676,26 @@ void sens_contract(const Run &r, const System &sys, const DevicePoints &dp, cons
         HIP_TRY(hipMemcpyAsync(ctx->d_B3, ref_factors3(), sizeof(double) * 600, hipMemcpyHostToDevice, s));
     }
     const double *tab = (r.dim == 3) ? ctx->d_B3 : sys.d_M;
+    const bool groups = rq->group != nullptr && rq->n_fun > 0;
+    const bool split_times = groups && r.o.time_kernels != 0;   // one synchronisation per functional: measuring runs only
+    const size_t ngc = size_t(rq->n_group) * size_t(b->sigma_comp);
+    for (double &m : ctx->sens_group_ms) m = 0.0;
+    if (groups) {
+        HIP_TRY(hipEventRecord(ctx->ev[6], s));
+        HIP_TRY(hipMemcpyAsync(sn.d_group, rq->group, sizeof(int32_t) * size_t(b->nt), hipMemcpyHostToDevice, s));
+        sens_group_order(b->nt, sn.d_group, sy.eperm, rq->n_group, sn.keys_in, sn.ids, sn.keys, sn.perm, sn.off, sn.sort_tmp, sn.sort_bytes, s);
+        HIP_TRY(hipEventRecord(ctx->ev[7], s));
+        HIP_TRY(hipEventSynchronize(ctx->ev[7]));
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]);
+        ctx->sens_group_ms[0] = ms;
+    }
+    hipEvent_t tev[4] = {};
+    if (split_times)
+        for (hipEvent_t &e : tev) HIP_TRY(hipEventCreate(&e));
     HIP_TRY(hipEventRecord(ctx->ev[4], s));
     for (int j = 0; j < rq->n_fun; ++j) {
+        if (split_times) HIP_TRY(hipEventRecord(tev[0], s));
         const int cf = rq->fun_rhs[j] / REMO_MAX_RHS, ca = j / REMO_MAX_RHS, fa = pts.forward_chunks + ca;
         SensColumns col;
         col.xu = sn.block(sys.n, b->n_rhs, false, cf); col.ku = std::min(b->n_rhs - cf * REMO_MAX_RHS, REMO_MAX_RHS); col.cu = rq->fun_rhs[j] % REMO_MAX_RHS;
@@ -659,11 +704,29 @@ void sens_contract(const Run &r, const System &sys, const DevicePoints &dp, cons
         col.ql0 = pts.chunk_begin[fa]; col.nql = pts.chunk_begin[fa + 1] - col.ql0;
         launch_sens_contract(r.dim, sy.condense, b->sigma_comp > 1, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, sy.eldof, sys.d_C, sys.d_M, tab, col,
                              dp.d_prhs, dp.d_pI, dp.d_found, dp.d_fint, b->n_mat, sn.part + size_t(j) * sn.grid * sn.nmc, s);
+        if (!groups) continue;
+        if (split_times) HIP_TRY(hipEventRecord(tev[1], s));
+        launch_sens_contract(r.dim, sy.condense, b->sigma_comp > 1, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, sy.eldof, sys.d_C, sys.d_M, tab, col,
+                             dp.d_prhs, dp.d_pI, dp.d_found, dp.d_fint, b->n_mat, sn.ev, s, true);
+        if (split_times) HIP_TRY(hipEventRecord(tev[2], s));
+        launch_sens_group_sum(b->sigma_comp, b->nt, rq->n_group, sn.keys, sn.perm, sn.off, sn.ev, sn.cpart, sn.d_dJg + size_t(j) * ngc, s);
+        if (split_times) {
+            HIP_TRY(hipEventRecord(tev[3], s));
+            HIP_TRY(hipEventSynchronize(tev[3]));
+            for (int k = 0; k < 3; ++k) {
+                float e = 0;
+                (void)hipEventElapsedTime(&e, tev[k], tev[k + 1]);
+                ctx->sens_group_ms[1 + k] += e;
+            }
+        }
     }
+    for (hipEvent_t e : tev)
+        if (e) (void)hipEventDestroy(e);
     launch_sens_reduce(rq->n_fun, sn.grid, sn.nmc, sn.part, sn.d_dJ, s);
     HIP_TRY(hipEventRecord(ctx->ev[5], s));
     h_dJ.assign(size_t(rq->n_fun) * sn.nmc, std::nan(""));
     if (!h_dJ.empty()) HIP_TRY(hipMemcpyAsync(h_dJ.data(), sn.d_dJ, sizeof(double) * h_dJ.size(), hipMemcpyDeviceToHost, s));
+    if (groups) HIP_TRY(hipMemcpyAsync(rq->dJg_out, sn.d_dJg, sizeof(double) * size_t(rq->n_fun) * ngc, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     float ms = 0;
     (void)hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]);

@@ -236,7 +236,8 @@ static int solve_batch_sens(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_
                             const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
                             const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
                             const double *fun_z, const double *fun_w, double *J_out, double *dJ_out, const remo_opts_t *opts,
-                            remo_stats_t *stats, bool tensor) {
+                            remo_stats_t *stats, bool tensor, bool groups = false, int32_t n_group = 0, const int32_t *group = nullptr,
+                            double *dJg_out = nullptr) {
     if (!ctx) return REMO_ERR_ARG;
     const int ncomp = (tensor && mesh) ? ((mesh->dim == 2) ? 3 : 6) : 1;
     auto nan_fill = [&]() {
@@ -245,8 +246,17 @@ static int solve_batch_sens(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_
         for (int j = 0; j < n_fun && J_out; ++j) J_out[j] = std::nan("");
         if (dJ_out && n_fun > 0 && n_mat > 0)
             for (size_t i = 0; i < size_t(n_fun) * size_t(n_mat) * ncomp; ++i) dJ_out[i] = std::nan("");
+        if (dJg_out && n_fun > 0 && n_group > 0)
+            for (size_t i = 0; i < size_t(n_fun) * size_t(n_group) * ncomp; ++i) dJg_out[i] = std::nan("");
     };
     nan_fill();
+    if (groups) {   // on the host array, before any device work
+        if (n_group < 1 || !group) return fail(ctx, REMO_ERR_ARG, "n_group must be at least 1 and group must be given");
+        if (!mesh || mesh->n_elems <= 0) return fail(ctx, REMO_ERR_ARG, "empty mesh");
+        if (n_fun > 0 && !dJg_out) return fail(ctx, REMO_ERR_ARG, "dJg_out missing");
+        for (int64_t e = 0; e < mesh->n_elems; ++e)
+            if (group[e] < -1 || group[e] >= n_group) return fail(ctx, REMO_ERR_ARG, "group id of element " + std::to_string(e) + " outside [-1, n_group)");
+    }
     if (n_fun < 0 || (n_fun > 0 && (!fun_rhs || !fun_ptr || !J_out || !dJ_out))) return fail(ctx, REMO_ERR_ARG, "functional arrays missing");
     if (n_fun > 0) {
         if (fun_ptr[0] != 0) return fail(ctx, REMO_ERR_ARG, "fun_ptr must start at 0");
@@ -261,7 +271,7 @@ static int solve_batch_sens(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_
     remo_batch_t *b = nullptr;
     int rc = batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, &b, true, tensor);
     if (rc != REMO_OK) return rc;
-    const remo_sens_request rq{n_fun, fun_rhs, fun_ptr, fun_z, fun_w, J_out, dJ_out};
+    const remo_sens_request rq{n_fun, fun_rhs, fun_ptr, fun_z, fun_w, J_out, dJ_out, groups ? n_group : 0, groups ? group : nullptr, groups ? dJg_out : nullptr};
     b->sens = &rq;
     b->eval_only = true;
     rc = remo_batch_run(ctx, b, opts, stats);
@@ -287,6 +297,24 @@ int remo_solve_batch_sens_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32
                                  remo_stats_t *stats) {
     return solve_batch_sens(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_fun, fun_rhs, fun_ptr, fun_z,
                             fun_w, J_out, dJ_out, opts, stats, true);
+}
+
+int remo_solve_batch_sens_groups(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
+                                 const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                                 const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
+                                 const double *fun_z, const double *fun_w, int32_t n_group, const int32_t *group, double *J_out, double *dJ_out,
+                                 double *dJg_out, const remo_opts_t *opts, remo_stats_t *stats) {
+    return solve_batch_sens(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_fun, fun_rhs, fun_ptr, fun_z, fun_w,
+                            J_out, dJ_out, opts, stats, false, true, n_group, group, dJg_out);
+}
+
+int remo_solve_batch_sens_groups_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor, int32_t n_rhs,
+                                        const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                                        const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
+                                        const double *fun_z, const double *fun_w, int32_t n_group, const int32_t *group, double *J_out,
+                                        double *dJ_out, double *dJg_out, const remo_opts_t *opts, remo_stats_t *stats) {
+    return solve_batch_sens(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_fun, fun_rhs, fun_ptr, fun_z,
+                            fun_w, J_out, dJ_out, opts, stats, true, true, n_group, group, dJg_out);
 }
 
 int remo_batch_eval(remo_ctx_t *ctx, remo_batch_t *b, int32_t rhs, int32_t npts, const double *z, double *u_out) {

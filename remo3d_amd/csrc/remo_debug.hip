@@ -418,4 +418,10 @@ int remo_debug_sens_timing(remo_ctx_t *ctx, double *out2) {
     return REMO_OK;
 }
 
+int remo_debug_sens_group_timing(remo_ctx_t *ctx, double *out4) {
+    if (!ctx || !out4) return REMO_ERR_ARG;
+    for (int i = 0; i < 4; ++i) out4[i] = ctx->sens_group_ms[i];
+    return REMO_OK;
+}
+
 }  // extern "C"

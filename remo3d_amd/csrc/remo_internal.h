@@ -90,6 +90,7 @@ struct remo_ctx {
     double *d_M2 = nullptr, *d_M3 = nullptr, *d_M2q = nullptr;   // reference tensors: exact 2D / 3D, 2D by the degree-4 rule
     double *d_B3 = nullptr;                  // factors of the 3D tensors (ref_factors3) for the sensitivity contraction, uploaded by its first use
     double sens_ms = 0.0, sens_bytes = 0.0;  // last remo_solve_batch_sens: HIP-event time and algorithmic bytes of the contraction launches (remo_debug_sens_timing)
+    double sens_group_ms[4] = {};            // last remo_solve_batch_sens_groups: group order; with time_kernels also the material pass, the per-element pass and the group sums, each over all functionals (remo_debug_sens_group_timing)
     remo::PcgProgress *progress = nullptr;  // mapped, coherent host memory
     remo::PcgProgress *progress_dev = nullptr;
     int progress_len = 0;
@@ -134,6 +135,10 @@ struct remo_sens_request {
     const int32_t *fun_rhs = nullptr, *fun_ptr = nullptr;
     const double *fun_z = nullptr, *fun_w = nullptr;
     double *J_out = nullptr, *dJ_out = nullptr;
+    // remo_solve_batch_sens_groups: the caller's group of every element (host array, checked by the entry) and where the sums go
+    int32_t n_group = 0;
+    const int32_t *group = nullptr;
+    double *dJg_out = nullptr;
 };
 
 struct remo_batch {

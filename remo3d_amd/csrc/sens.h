@@ -1,5 +1,6 @@
 // sens.h — adjoint sensitivities of linear measurement functionals to the material conductivities (remo_solve_batch_sens):
-// the element contraction shared by host and gfx950 code, and the launchers of sens.hip.
+// the element contraction shared by host and gfx950 code, and the launchers of sens.hip (per material, and per caller-defined
+// group of elements: remo_solve_batch_sens_groups).
 //
 // With A(sigma) u = f, J = g^T u and A lambda = g:  dJ/dsigma_m = -lambda^T (dA/dsigma_m) u, and dA/dsigma_m is the sum of the
 // element matrices of material m with their sigma taken out.  Per element (fem_p3.h: K_e = sum_t C_e[t] M[t], C = sigma-free
@@ -107,8 +108,21 @@ int sens_grid(int64_t nt);
 // part[grid][nmat * nc]: per-workgroup sums of lambda_e^T (dK_e/d component) u_e by material, every entry written
 void launch_sens_contract(int dim, bool condense, bool tensor, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat,
                           const int32_t *eperm, const int32_t *eldof, const double *C, const double *M, const double *tab, const SensColumns &col,
-                          const int32_t *pt_rhs, const double *pt_I, const int32_t *found, const double *fint, int nmat, double *part, hipStream_t s);
+                          const int32_t *pt_rhs, const double *pt_I, const int32_t *found, const double *fint, int nmat, double *part, hipStream_t s,
+                          bool per_elem = false);   // per_elem: part = ev[nt][nc], the values of every device element instead (no material sums)
 // dJ[j][nmat * nc] = -(sum over the workgroups, in index order) for n_fun functionals whose partials lie one after the other
 void launch_sens_reduce(int n_fun, int grid, int nmc, const double *part, double *dJ, hipStream_t s);
+
+// ---- sums per group of elements (remo_solve_batch_sens_groups) ------------------------------------------------------------------
+constexpr int kSensChunk = 1024;      // sorted positions per workgroup of the chunk pass; longer segments are summed in two levels
+size_t sens_group_sort_bytes(int64_t nt, int32_t n_group);   // temporary storage of the radix sort (no device work)
+int64_t sens_group_chunks(int64_t nt);                        // cpart holds 2 * nc doubles per chunk
+// Once per batch: keys_in[t] = group[eperm ? eperm[t] : t] (-1 -> n_group), ids[t] = t, sorted (stable) into keys / perm, and
+// off[0 .. n_group]: the segment of group g is perm[off[g] .. off[g + 1]); the elements in no group lie behind off[n_group].
+void sens_group_order(int64_t nt, const int32_t *group, const int32_t *eperm, int32_t n_group, uint32_t *keys_in, int32_t *ids, uint32_t *keys, int32_t *perm,
+                      int32_t *off, void *tmp, size_t tmp_bytes, hipStream_t s);
+// dJg[n_group][nc] = -(sum of ev over the group's segment), fixed order, every entry written (an empty group: 0)
+void launch_sens_group_sum(int nc, int64_t nt, int32_t n_group, const uint32_t *keys, const int32_t *perm, const int32_t *off, const double *ev,
+                           double *cpart, double *dJg, hipStream_t s);
 
 }  // namespace remo

@@ -224,6 +224,51 @@ def resistivity_sensitivity(dJ, entries, formation_parameters, scale, normal=Non
 
 
 # ---------------------------------------------------------------------------------------------
+# Sensitivity maps: the elements of a batch's mesh binned on an (r, z) grid (Model.simulate_logs(sensitivity_grid=...))
+
+
+def sensitivity_cells(mesh, mat, grid, z_offset=0.0):
+    """Groups of elements for Context.solve_batch_sens_groups: one group per (material, grid cell) pair that occurs.
+    grid: dict with the edges, in metres, of the depth axis `z` and of one lateral axis: `r`, the distance from the borehole axis
+    (2D: the mesh's r; 3D: hypot(x, y)), or in 3D `x`, the signed x of the dip plane (y summed).  z is absolute depth in the
+    formation table's sense, measured along the borehole axis: the mesh lives in the frame of its batch (depth relative to the
+    batch's combined depth), and z_offset - that combined depth - undoes it, so one grid serves every batch of a sweep.
+    An element belongs to the cell that holds its centroid (cells are half-open, [lo, hi)); elements whose centroid lies outside
+    the grid go to one "rest" pseudo-cell with index n_z * n_r.  mat: the material of every element (None: mesh.mat).
+    Returns (group [n_elems] int32 - compact ids 0 .. n_group - 1 -, group_material [n_group], group_cell [n_group]) with
+    cell = iz * n_r + ir; every group is material-pure."""
+    coords = np.asarray(mesh.coords, dtype=float)
+    conn = np.asarray(mesh.conn)
+    mat = np.asarray(mesh.mat if mat is None else mat, dtype=np.int64)
+    dim = coords.shape[1]
+    if mat.shape != (conn.shape[0],):
+        raise ValueError("mat must hold one material per element")
+    lateral = [k for k in ("r", "x") if k in grid]
+    if len(lateral) != 1 or "z" not in grid:
+        raise ValueError("grid must hold the edges of 'z' and of one of 'r' and 'x'")
+    if lateral[0] == "x" and dim != 3:
+        raise ValueError("the 'x' axis exists in 3D only")
+    ez = np.asarray(grid["z"], dtype=float)
+    eh = np.asarray(grid[lateral[0]], dtype=float)
+    for e in (ez, eh):
+        if e.ndim != 1 or e.size < 2 or np.any(np.diff(e) <= 0):
+            raise ValueError("grid edges must be increasing, two at least")
+    cen = coords[conn].mean(axis=1)
+    z = cen[:, dim - 1] + float(z_offset)
+    if lateral[0] == "x":
+        h = cen[:, 0]
+    else:
+        h = np.abs(cen[:, 0]) if dim == 2 else np.hypot(cen[:, 0], cen[:, 1])
+    n_z, n_h = ez.size - 1, eh.size - 1
+    iz = np.searchsorted(ez, z, side="right") - 1
+    ih = np.searchsorted(eh, h, side="right") - 1
+    inside = (iz >= 0) & (iz < n_z) & (ih >= 0) & (ih < n_h)
+    cell = np.where(inside, iz * n_h + ih, n_z * n_h)
+    pair, group = np.unique(mat * (n_z * n_h + 1) + cell, return_inverse=True)
+    return group.astype(np.int32).ravel(), pair // (n_z * n_h + 1), pair % (n_z * n_h + 1)
+
+
+# ---------------------------------------------------------------------------------------------
 # Netgen path (2D only): remo3d/netgen_functions.py:12-118
 
 

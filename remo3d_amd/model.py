@@ -158,6 +158,9 @@ class Model:
         self.logs = None
         self.sensitivities = None      # simulate_logs(sensitivities=True): per tool dRa/dR [n_depths, n_layers, n_cols]
         self.mud_sensitivity = None    # ... and dRa/dRm [n_depths]
+        self.sensitivity_maps = None   # simulate_logs(sensitivity_grid=...): per tool d ln Ra / d ln R of every grid cell [n_depths, n_z, n_r]
+        self.sensitivity_map_rest = None   # ... and of everything outside the grid [n_depths]
+        self.sensitivity_grid = None   # the grid of the last maps
         self.timing = {}
 
     # -- complete procedure (remo3d.py:65-174) ---------------------------------------------------
@@ -336,13 +339,19 @@ class Model:
     def simulate_logs(self, measurement_depths, domain_radius=50, batch_size=5, mesh_generator="auto", preconditioner="multigrid",
                       condense=True, mesh_provider: Optional[Callable] = None, mesh_scale: Optional[float] = None, rtol: float = 1e-8,
                       maxsteps: int = 1000, verbose: bool = True, mesh_workers: Optional[int] = None, precision: str = "fp64",
-                      schedule: str = "static", solver_options: Optional[dict] = None, sensitivities: bool = False):
+                      schedule: str = "static", solver_options: Optional[dict] = None, sensitivities: bool = False,
+                      sensitivity_grid: Optional[dict] = None):
         """solver_options: further keywords of solver.make_opts for every batch (op, coarse, quadrature, assemble, ...).
         sensitivities: also fill self.sensitivities[tool] = dRa/dR in ohm m per ohm m, [n_depths, n_layers, n_cols] with the
         columns of the formation table from column 2 on (RDFZ - a radius, always NaN -, RTFZ, RTUZ, and RVUZ when present; 0 where
         the batch's window does not hold the entry, NaN where the table has NaN or the batch failed), and self.mud_sensitivity[tool]
         = dRa/dRm [n_depths] (Rm: the mud resistivity of the record's batch), by adjoint solves (remo_solve_batch_sens: about twice
-        the solves of the plain sweep); fp64 only."""
+        the solves of the plain sweep); fp64 only.
+        sensitivity_grid: dict(r=edges, z=edges) in metres (3D also x=edges instead of r; z: absolute depth along the borehole axis;
+        geometry.sensitivity_cells): also fill self.sensitivity_maps[tool] [n_depths, n_z, n_r] with the dimensionless
+        d ln Ra / d ln R of every cell - every resistivity inside the cell (mud, flushed zones, Rh and Rv alike) scaled by a common
+        factor - and self.sensitivity_map_rest[tool] [n_depths] with the same for everything outside the grid (the two sum to 1);
+        NaN where the batch failed.  Implies the adjoint solves (remo_solve_batch_sens_groups); may be combined with sensitivities."""
         from . import solver, sweep
         extra = dict(solver_options or {})
         start = time.time()
@@ -399,6 +408,12 @@ class Model:
         mud_res = np.zeros((len(measurement_depths), n_tools)) if sensitivities else None
         sens_ti = sensitivities and self.formation_model.shape[1] >= 6 and bool(np.any(~np.isnan(self.formation_model[:, 5])))
         ti_normal = (np.array([np.sin(self.dip_rad), 0.0, np.cos(self.dip_rad)]) if is3d else np.array([0.0, 1.0]))   # geometry.ti_conductivity
+        maps = sensitivity_grid is not None
+        adjoint = sensitivities or maps
+        if maps:
+            lateral = "x" if "x" in sensitivity_grid else "r"
+            n_cells = (len(sensitivity_grid["z"]) - 1) * (len(sensitivity_grid[lateral]) - 1)
+            map_res = np.zeros((len(measurement_depths), n_tools, n_cells + 1))     # the last entry: the rest pseudo-cell
 
         def window_of(formation, bi):
             if netgen_path:   # the reference's default 2D windowing (remo3d.py:776-779, worker.py:94)
@@ -510,16 +525,21 @@ class Model:
                     vs = vertex_solver_options(3, mesh.n_nodes, conforming_default, n_ctx_total)
                     if vs:
                         bopts = solver.make_opts(**dict(base_kw, **vs))
-                if sensitivities:     # the table entry behind every material: the identifier table through the same windowing
+                if adjoint:
                     functionals, fun_readers = tasks.batch_functionals(batch, self.tools)
+                if sensitivities:     # the table entry behind every material: the identifier table through the same windowing
                     entries = geometry.material_entries(window_of(formation_ids, bi)[2])
                     if len(entries) != len(sigma):
                         raise RuntimeError("windowing of the entry identifiers gave different materials")
                     if sens_ti and np.ndim(sigma) == 1:     # dRa/dRTUZ and dRa/dRVUZ apart need the tensor derivative, also where the window is isotropic
                         sigma = geometry.ti_conductivity(sigma, sigma, self.dip_rad if is3d else 0.0, dim)
+                if maps:
+                    groups, group_mat, group_cell = geometry.sensitivity_cells(mesh, None, sensitivity_grid, simulation_depths[bi])
                 c = free_ctx.get()
                 try:
-                    if sensitivities:
+                    if maps:
+                        outs, J, dJ, dJg, st, rc = c.solve_batch_sens_groups(mesh, sigma, sources, evals, functionals, groups, len(group_mat), bopts)
+                    elif sensitivities:
                         outs, J, dJ, st, rc = c.solve_batch_sens(mesh, sigma, sources, evals, functionals, bopts)
                     else:
                         outs, st, rc = c.solve_batch(mesh, sigma, sources, evals, bopts)
@@ -531,6 +551,13 @@ class Model:
                         scale = np.sign(K * J[j]) * K / (2.0 if dim == 3 else 1.0)
                         sens_res[di, ti], dmud = geometry.resistivity_sensitivity(dJ[j], entries, self.formation_model, scale, ti_normal)
                         mud_res[di, ti] = dmud * (-1.0 / mud[bi] ** 2)
+                if maps:     # d ln Ra / d ln R of a cell: every sigma inside it scaled by 1 / s, d sigma / d ln s = -sigma
+                    sig = np.asarray(sigma, dtype=float)
+                    for j, (di, ti, K) in enumerate(fun_readers):
+                        scale = np.sign(K * J[j]) * K / (2.0 if dim == 3 else 1.0)
+                        Ra = abs(K * J[j]) / (2.0 if dim == 3 else 1.0)
+                        w = sig[group_mat] * dJg[j] if sig.ndim == 1 else np.sum(sig[group_mat] * dJg[j], axis=(1, 2))
+                        map_res[di, ti] = -(scale / Ra) * np.bincount(group_cell, weights=w, minlength=n_cells + 1)
                 n = 0
                 for u, rd in zip(outs, readers):
                     for (di, ti, K, o, m) in rd:
@@ -545,6 +572,8 @@ class Model:
                     if sensitivities:
                         sens_res[di, ti] = np.nan
                         mud_res[di, ti] = np.nan
+                    if maps:
+                        map_res[di, ti] = np.nan
                 with lock:               # ... but not silently: the reference's worker at least shows it on stderr
                     acc["failed_batches"] += 1
                     if acc["first_error"] is None:
@@ -585,6 +614,14 @@ class Model:
             self.mud_sensitivity = {name: mud_res[:, i] for i, name in enumerate(self.tools.keys())}
         else:
             self.sensitivities = self.mud_sensitivity = None
+        if maps:
+            map_res = sweep.combine(map_res)
+            shape = (len(measurement_depths), len(sensitivity_grid["z"]) - 1, len(sensitivity_grid[lateral]) - 1)
+            self.sensitivity_maps = {name: map_res[:, i, :n_cells].reshape(shape) for i, name in enumerate(self.tools.keys())}
+            self.sensitivity_map_rest = {name: map_res[:, i, n_cells] for i, name in enumerate(self.tools.keys())}
+            self.sensitivity_grid = {k: np.asarray(v, dtype=float) for k, v in sensitivity_grid.items()}
+        else:
+            self.sensitivity_maps = self.sensitivity_map_rest = self.sensitivity_grid = None
         self.logs = {name: np.vstack([measurement_depths, results[:, i]]).T for i, name in enumerate(self.tools.keys())}
         self.timing = dict(total_s=time.time() - start, mesh_s=t_mesh, solve_s=t_solve, points=n_points, batches=len(batches),
                            my_batches=len(mine), world_size=sweep.world_size(), schedule=schedule, busy_s=t_busy,

@@ -97,6 +97,34 @@ def sigma_table(sigma, dim=None):
     return np.ascontiguousarray(sigma[:, iu[0], iu[1]]), True
 
 
+def _functional_arrays(functionals):
+    """functionals: list of (rhs, z array, w array) -> (fun_rhs, fun_ptr, fun_z, fun_w) of remo_solve_batch_sens."""
+    n_fun = len(functionals)
+    fun_rhs = np.ascontiguousarray([f[0] for f in functionals], dtype=np.int32)
+    fun_ptr = np.zeros(n_fun + 1, dtype=np.int32)
+    fz, fw = [], []
+    for j, (_, z, w) in enumerate(functionals):
+        z = np.atleast_1d(np.asarray(z, dtype=np.float64)); w = np.atleast_1d(np.asarray(w, dtype=np.float64))
+        if z.shape != w.shape:
+            raise ValueError("functional points and weights differ in length")
+        fz.append(z); fw.append(w); fun_ptr[j + 1] = fun_ptr[j] + z.size
+    cat = lambda xs: np.ascontiguousarray(np.concatenate(xs) if xs else np.zeros(0), dtype=np.float64)
+    return fun_rhs, fun_ptr, cat(fz), cat(fw)
+
+
+def _symmetric_gradient(dJ, d, tensor):
+    """The library's [n_fun, n, nc] derivatives as the caller sees them: [n_fun, n] for scalar sigma; for tensors the symmetric
+    G [n_fun, n, d, d] with dJ = G : dSigma (the triangle's off-diagonal entries hold both halves; each half gets half)."""
+    if not tensor:
+        return dJ[:, :, 0]
+    iu = np.triu_indices(d)
+    G = np.zeros(dJ.shape[:2] + (d, d))
+    half = np.where(iu[0] == iu[1], 1.0, 0.5)
+    G[:, :, iu[0], iu[1]] = dJ * half
+    G[:, :, iu[1], iu[0]] = dJ * half
+    return G
+
+
 class Context:
     """One per GPU (remo_ctx_create)."""
 
@@ -155,16 +183,7 @@ class Context:
         sigma, tensor = sigma_table(sigma, int(mesh.dim))
         src_ptr, sz, sI, eval_ptr, ez = _rhs_arrays(sources, evals)
         n_fun = len(functionals)
-        fun_rhs = np.ascontiguousarray([f[0] for f in functionals], dtype=np.int32)
-        fun_ptr = np.zeros(n_fun + 1, dtype=np.int32)
-        fz, fw = [], []
-        for j, (_, z, w) in enumerate(functionals):
-            z = np.atleast_1d(np.asarray(z, dtype=np.float64)); w = np.atleast_1d(np.asarray(w, dtype=np.float64))
-            if z.shape != w.shape:
-                raise ValueError("functional points and weights differ in length")
-            fz.append(z); fw.append(w); fun_ptr[j + 1] = fun_ptr[j] + z.size
-        cat = lambda xs: np.ascontiguousarray(np.concatenate(xs) if xs else np.zeros(0), dtype=np.float64)
-        fz, fw = cat(fz), cat(fw)
+        fun_rhs, fun_ptr, fz, fw = _functional_arrays(functionals)
         ms, keep = _lib.mesh_struct(mesh)
         d = int(mesh.dim)
         n_mat, nc = len(sigma), (sigma.shape[1] if tensor else 1)
@@ -181,16 +200,51 @@ class Context:
                    ptr(J, C.c_double), ptr(dJ, C.c_double), C.byref(o), C.byref(st))
         if rc < 0 and raise_on_error:
             raise RemoError(rc, self.last_error())
-        if tensor:
-            iu = np.triu_indices(d)
-            G = np.zeros((n_fun, n_mat, d, d))
-            half = np.where(iu[0] == iu[1], 1.0, 0.5)
-            G[:, :, iu[0], iu[1]] = dJ * half
-            G[:, :, iu[1], iu[0]] = dJ * half
-            dJ = G
-        else:
-            dJ = dJ[:, :, 0]
-        return [out[eval_ptr[k]:eval_ptr[k + 1]] for k in range(len(evals))], J, dJ, st.as_dict(), rc
+        return [out[eval_ptr[k]:eval_ptr[k + 1]] for k in range(len(evals))], J, _symmetric_gradient(dJ, d, tensor), st.as_dict(), rc
+
+    def solve_batch_sens_groups(self, mesh, sigma, sources, evals, functionals, groups, n_group=None, opts: Optional[RemoOpts] = None,
+                                raise_on_error=True):
+        """One-shot remo_solve_batch_sens_groups: solve_batch_sens plus the derivatives with respect to caller-defined groups of
+        elements.  groups: [n_elems] int, the group of every element of mesh.conn (-1: in no group); n_group: the number of groups
+        (default: largest id + 1).  With sigma_e = sigma_mat(e) + p_group(e), dJg[j, g] = dJ_j/dp_g.  Returns
+        (potentials, J, dJ, dJg, stats, rc); dJg is [n_fun, n_group] for sigma [n_mat] and [n_fun, n_group, dim, dim] for tensors,
+        with the symmetric-G convention of dJ."""
+        sigma, tensor = sigma_table(sigma, int(mesh.dim))
+        src_ptr, sz, sI, eval_ptr, ez = _rhs_arrays(sources, evals)
+        fun_rhs, fun_ptr, fz, fw = _functional_arrays(functionals)
+        n_fun = len(functionals)
+        ms, keep = _lib.mesh_struct(mesh)
+        groups = np.ascontiguousarray(groups, dtype=np.int32).ravel()
+        if groups.size != keep[1].shape[0]:
+            raise ValueError("groups must hold one id per element")
+        if n_group is None:
+            n_group = int(groups.max(initial=-1)) + 1
+        n_group = int(n_group)
+        d = int(mesh.dim)
+        n_mat, nc = len(sigma), (sigma.shape[1] if tensor else 1)
+        out = np.full(int(eval_ptr[-1]), np.nan)
+        J = np.full(n_fun, np.nan)
+        dJ = np.full((n_fun, n_mat, nc), np.nan)
+        dJg = np.full((n_fun, max(n_group, 0), nc), np.nan)
+        st = RemoStats()
+        o = opts if opts is not None else make_opts()
+        entry = self._L.remo_solve_batch_sens_groups_tensor if tensor else self._L.remo_solve_batch_sens_groups
+        rc = entry(self._h, C.byref(ms), n_mat, ptr(sigma, C.c_double), len(sources),
+                   ptr(src_ptr, C.c_int32), ptr(sz, C.c_double), ptr(sI, C.c_double),
+                   ptr(eval_ptr, C.c_int32), ptr(ez, C.c_double), ptr(out, C.c_double),
+                   n_fun, ptr(fun_rhs, C.c_int32), ptr(fun_ptr, C.c_int32), ptr(fz, C.c_double), ptr(fw, C.c_double),
+                   n_group, ptr(groups, C.c_int32), ptr(J, C.c_double), ptr(dJ, C.c_double), ptr(dJg, C.c_double), C.byref(o), C.byref(st))
+        if rc < 0 and raise_on_error:
+            raise RemoError(rc, self.last_error())
+        return ([out[eval_ptr[k]:eval_ptr[k + 1]] for k in range(len(evals))], J, _symmetric_gradient(dJ, d, tensor),
+                _symmetric_gradient(dJg, d, tensor), st.as_dict(), rc)
+
+    def sens_group_timing(self):
+        """ms of the group path of the last solve_batch_sens_groups on this context (remo_debug_sens_group_timing): (group order,
+        material pass, per-element pass, group sums); the last three are measured only with make_opts(time_kernels=True)."""
+        out = np.zeros(4)
+        self._L.remo_debug_sens_group_timing(self._h, ptr(out, C.c_double))
+        return tuple(float(v) for v in out)
 
     def sens_timing(self):
         """(ms, algorithmic bytes) of the contraction launches of the last solve_batch_sens on this context (remo_debug_sens_timing)."""
