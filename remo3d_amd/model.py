@@ -15,14 +15,21 @@ What differs, by design:
 """
 from __future__ import annotations
 
+import collections
 import datetime
+import multiprocessing
 import os
+import queue
+import sys
+import threading
 import time
+import types
+from concurrent.futures import ProcessPoolExecutor, ThreadPoolExecutor
 from typing import Callable, Dict, Optional
 
 import numpy as np
 
-from . import geometry, meshgen, tasks, tools as tools_mod
+from . import geometry, meshgen, solver, sweep, tasks, tools as tools_mod
 
 CONVERSION = {"M": 1.0, "DM": 0.1, "CM": 0.01, "MM": 0.001, "IN": 0.0254, "FT": 0.3048}
 
@@ -137,9 +144,353 @@ def _mesh_worker_init(provider_kwargs):
 
 
 def _mesh_worker_run(job):
-    import types
     dim, domain_radius, electrodes, fg, bh, dip_rad = job
     return _WORKER_PROVIDER(dim, domain_radius, types.SimpleNamespace(electrodes=electrodes), fg, bh, dip_rad)
+
+
+# -- the stages of Model.simulate_logs, in the order a sweep goes through them ---------------------------
+class _Plan:
+    """Stage 1, before any batch is drawn: the arguments checked, the batches, the solver options."""
+
+    def __init__(self, model, measurement_depths, domain_radius, batch_size, mesh_generator, mesh_provider, mesh_scale, solver_kw,
+                 solver_options, verbose):
+        extra = dict(solver_options or {})
+        self.model, self.domain_radius, self.mesh_scale = model, domain_radius, mesh_scale
+        self.depths = np.asarray(measurement_depths, dtype=float)
+        alert = False
+        for t in model.tools.values():
+            far = np.max(np.abs(t[0, :3]))
+            if far > domain_radius:
+                raise ValueError("Some electrodes are locate outside the simulation domain. Domain size have to be increased")
+            alert |= far > 0.75 * domain_radius
+        if alert and verbose:
+            print("Some electrodes are located close to the boundary of the simulation domain. This may cause problems during simulation. "
+                  "Consider increase of the domain size")
+        if mesh_generator not in ("auto", "gmsh", "netgen"):
+            raise ValueError("mesh_generator has to be 'auto', 'gmsh' or 'netgen'")
+        is3d = not np.isclose(model.dip_deg, 0)
+        if is3d and mesh_generator == "netgen":
+            raise ValueError("The only mesh generator supported in 3D models is gmsh")
+        if solver_kw["preconditioner"] not in ("local", "multigrid"):
+            raise ValueError("preconditioner has to be 'local' or 'multigrid'")
+        if model.ctx is None:
+            raise RuntimeError("initialize_workers() has to be called before simulate_logs()")
+        if model.dip_deg != 0:
+            model.borehole_model = model._add_points_to_borehole()
+        self.dim, self.window_dip = (3, model.dip_rad) if is3d else (2, 0.0)
+        self.netgen_path = (not is3d) and mesh_generator in ("auto", "netgen")
+        self.default_provider = mesh_provider is None     # its 3D meshes are the conforming revolved ones; only it runs in the mesh pool
+        self.provider = mesh_provider or default_mesh_provider(scale=mesh_scale)
+        self.simulation_depths, self.batches = model._prepare_simulation_depths_and_tasks(self.depths, batch_size)
+        self.borehole_geometry = np.ascontiguousarray(model.borehole_model[:, :2])
+        self.mud = np.interp(self.simulation_depths, model.borehole_model[:, 0], model.borehole_model[:, 2])
+        if verbose and sweep.rank() == 0:
+            print("{} simulation tasks prepared".format(len(self.batches)))
+        # ONE dictionary of solver keywords: the explicit arguments, over-ridden by solver_options (a key given in both places used
+        # to raise "multiple values" inside every batch, i.e. a sweep of NaNs); unknown keys fail here, before any batch is drawn,
+        # on every rank alike
+        self.base_kw = dict(solver_kw, **extra)
+        self.opts = solver.make_opts(**self.base_kw)
+        # the solver of the P1 block follows the mesh kind and the number of contexts (vertex_solver_options) unless the caller chose one
+        self.tuned_coarse = self.base_kw["preconditioner"] == "multigrid" and not any(k in extra for k in ("coarse", "coarse_degree", "coarse_ratio"))
+        self.contexts = [model.ctx] + list(getattr(model, "extra_ctx", []))
+        self.share_len = len(list(sweep.my_share(len(self.batches))))
+
+    def batch_opts(self, mesh):
+        if self.tuned_coarse and getattr(mesh, "dim", 0) == 3:
+            vs = vertex_solver_options(3, mesh.n_nodes, self.default_provider, len(self.contexts))
+            if vs:
+                return solver.make_opts(**dict(self.base_kw, **vs))
+        return self.opts
+
+    def slab(self, *tail):
+        """Zeros per (depth, tool): every rank fills its own records and sweep.combine sums over the ranks."""
+        return np.zeros((len(self.depths), len(self.model.tools)) + tail)
+
+
+class _Windowing:
+    """Stage 2: the part of the model a batch sees."""
+
+    def __init__(self, plan):
+        self.plan, fm = plan, plan.model.formation_model
+        self.formation_h, self.formation_v, self.formation_ids = fm[:, :5], plan.model._vertical_formation_model(), geometry.entry_id_table(fm)
+        self.ti_table = fm.shape[1] >= 6 and bool(np.any(~np.isnan(fm[:, 5])))
+
+    def _of(self, formation, bi):
+        p = self.plan
+        if p.netgen_path:   # the reference's default 2D windowing (remo3d.py:776-779, worker.py:94)
+            return geometry.select_netgen_data_range(p.borehole_geometry, formation, p.mud[bi], p.simulation_depths[bi], p.domain_radius)
+        # Gmsh-path windowing (worker.py:84), the only one for dipping models
+        return geometry.select_data_range(p.borehole_geometry, formation, p.window_dip, p.mud[bi], p.simulation_depths[bi], p.domain_radius)
+
+    def window(self, bi):
+        """(geometry, borehole, sigma): sigma is 1-D as in the reference unless a material of the window is anisotropic; then
+        [n_mat, dim, dim] TI tensors.  The vertical conductivities come from windowing the RVUZ copy of the table the same way,
+        so that every quirk of the windowing (e.g. a dropped flushed zone: the layer takes RTFZ) applies to both alike."""
+        fg, bh, sigma = self._of(self.formation_h, bi)
+        if self.formation_v is None:
+            return fg, bh, sigma
+        sigma_v = self._of(self.formation_v, bi)[2]
+        if len(sigma_v) != len(sigma):
+            raise RuntimeError("windowing of RTUZ and RVUZ gave different materials")
+        if np.array_equal(np.asarray(sigma_v), np.asarray(sigma)):
+            return fg, bh, sigma
+        return fg, bh, geometry.ti_conductivity(sigma, sigma_v, self.plan.window_dip, self.plan.dim)
+
+    def entries(self, bi, sigma):
+        """For the layer sensitivities: (the table entry behind every material - the identifier table through the same windowing -,
+        sigma as TI tensors when the table has an RVUZ: dRa/dRTUZ and dRa/dRVUZ apart need the tensor derivative, also where the
+        window is isotropic)."""
+        entries = geometry.material_entries(self._of(self.formation_ids, bi)[2])
+        if len(entries) != len(sigma):
+            raise RuntimeError("windowing of the entry identifiers gave different materials")
+        if self.ti_table and np.ndim(sigma) == 1:
+            sigma = geometry.ti_conductivity(sigma, sigma, self.plan.window_dip, self.plan.dim)
+        return entries, sigma
+
+
+class _MeshAhead:
+    """Stage 3: which batches this rank takes - its block-cyclic share ("static"), or whatever it draws from the shared counter while
+    it is free ("dynamic", the reference's pull scheduling, remo3d.py:843-860; sweep.BatchQueue) - and their meshes.  mesh_workers > 0:
+    the default mesher runs ahead of the solver in that many spawned processes (the reference meshes inside its MPI workers, i.e. in
+    parallel too: worker.py:84-97), on batches drawn ahead: the whole share at once when it is fixed anyway, a few (they are OWNED once
+    drawn) under the pull schedule."""
+
+    def __init__(self, plan, windowing, bq, schedule, mesh_workers):
+        self.plan, self.windowing, self.bq, self.schedule = plan, windowing, bq, schedule
+        self.pool, self.pending, self.ahead = None, {}, collections.deque()
+        if mesh_workers is None:    # default: the reference's cpu_workers mesh (and solve) in parallel; here they mesh, for sweeps long
+            mesh_workers = min(int(plan.model.cpu_workers or 0), 8) if (plan.default_provider and plan.share_len >= 16) else 0   # enough to pay for the start-up
+        if mesh_workers > 0 and plan.default_provider and plan.share_len > 1:
+            self.pool = self._start_pool(int(mesh_workers), plan.mesh_scale)
+        self.depth = 1 if self.pool is None else (plan.share_len if schedule == "static" else int(mesh_workers) + len(plan.contexts))
+        self.draw, self.lock = iter(bq), threading.Lock()
+
+    @staticmethod
+    def _start_pool(n, mesh_scale):
+        main_mod = sys.modules.get("__main__")
+        hidden = {}
+        try:
+            # spawned children re-import the caller's __main__ (and would re-run a script without an
+            # `if __name__ == "__main__"` guard, GPU contexts and all): hide its path while the workers start -
+            # the worker functions live in this module, nothing of __main__ is needed over there
+            for attr in ("__file__", "__spec__"):
+                if main_mod is not None and getattr(main_mod, attr, None) is not None:
+                    hidden[attr] = getattr(main_mod, attr)
+                    setattr(main_mod, attr, None)
+            pool = ProcessPoolExecutor(max_workers=n, mp_context=multiprocessing.get_context("spawn"),
+                                       initializer=_mesh_worker_init, initargs=(dict(scale=mesh_scale),))
+            # the executor starts a process per submit while none is idle: start them ALL here, while __main__ is hidden
+            for fut in [pool.submit(time.sleep, 0.25) for _ in range(n)]:
+                fut.result()
+            return pool
+        except Exception:     # no worker processes here: mesh inline
+            return None
+        finally:
+            for attr, v in hidden.items():
+                setattr(main_mod, attr, v)
+
+    def next_batch(self):
+        p = self.plan
+        with self.lock:
+            # under the pull schedule a drawn batch is OWNED: near the end of the sweep a rank must not sit on a queue of
+            # batches the other ranks are idle for - draw ahead no further than its fair part of what is left
+            cap = self.depth if self.schedule == "static" else max(1, min(self.depth, 1 + self.bq.remaining_hint() // (2 * max(1, sweep.world_size()))))
+            while len(self.ahead) < cap:
+                try:
+                    bi = next(self.draw)
+                except StopIteration:
+                    break
+                if self.pool is not None:
+                    try:
+                        fg, bh, _ = self.windowing.window(bi)
+                        self.pending[bi] = self.pool.submit(_mesh_worker_run, (p.dim, p.domain_radius, p.batches[bi].electrodes, fg, bh, p.model.dip_rad))
+                    except Exception:
+                        pass      # reported when the batch's turn comes
+                self.ahead.append(bi)
+            return self.ahead.popleft() if self.ahead else None
+
+    def mesh(self, bi, fg, bh):
+        p, mesh = self.plan, None
+        if bi in self.pending:
+            try:
+                mesh = self.pending.pop(bi).result()
+            except Exception:     # a worker process died: mesh this batch here
+                mesh = None
+        return mesh if mesh is not None else p.provider(p.dim, p.domain_radius, p.batches[bi], fg, bh, p.model.dip_rad)
+
+    def shutdown(self):
+        if self.pool is not None:     # whatever happened in the sweep, the mesh processes do not outlive it
+            self.pool.shutdown(wait=False, cancel_futures=True)
+
+
+def _ra_scale(K, J, dim):
+    """Ra = |K J| (/ 2 in 3D, where a half-space is meshed), so dRa = scale * dJ with scale = sign(K J) K (/ 2)."""
+    return np.sign(K * J) * K / (2.0 if dim == 3 else 1.0)
+
+
+class _Output:
+    """Stage 4: one thing a sweep produces.  Its slabs (_Plan.slab) are written by several host threads at disjoint (depth, tool)
+    rows without a lock.  A new output is a subclass listed in Model.simulate_logs, with store(job) - after the solve: the records of the
+    job's batch into the slabs - and publish(model) - the combined slabs as attributes of the model, one array per tool; if it needs more of
+    the solver than potentials, also adjoint = True and a prepare."""
+    adjoint = False     # needs the functionals of the records and J, dJ of the adjoint solves
+
+    def prepare(self, job):
+        """Before the solve: add to the job what this output needs the solver to be given (it may replace job.sigma)."""
+
+    def fail(self, rows):
+        for slab in self.slabs:
+            for di, ti in rows:
+                slab[di, ti] = np.nan
+
+    def combine(self):
+        self.slabs = [sweep.combine(slab) for slab in self.slabs]
+
+
+def _per_tool(model, of):
+    return {name: of(i) for i, name in enumerate(model.tools.keys())}
+
+
+class _Logs(_Output):
+    def __init__(self, plan):
+        self.plan, self.slabs = plan, [plan.slab()]
+
+    def store(self, job):
+        for u, rd in zip(job.outs, job.readers):
+            for (di, ti, K, o, m) in rd:
+                self.slabs[0][di, ti] = tasks.apparent_resistivity(u[o:o + m], m, K, self.plan.dim)
+
+    def publish(self, model):
+        model.logs = _per_tool(model, lambda i: np.vstack([self.plan.depths, self.slabs[0][:, i]]).T)
+
+
+class _LayerSensitivities(_Output):
+    """dRa/dR of every entry of the formation table and dRa/dRm: Ra = |K J| (/ 2 in 3D), dRa/dR = sign(K J) K (/ 2) * dJ/dsigma * (-1 / R^2)."""
+    adjoint = True
+
+    def __init__(self, plan, windowing):
+        fm = plan.model.formation_model
+        self.plan, self.windowing = plan, windowing
+        self.slabs = [plan.slab(fm.shape[0], fm.shape[1] - 2), plan.slab()]
+        dip = plan.model.dip_rad
+        self.ti_normal = np.array([np.sin(dip), 0.0, np.cos(dip)]) if plan.dim == 3 else np.array([0.0, 1.0])   # geometry.ti_conductivity
+
+    def prepare(self, job):
+        job.entries, job.sigma = self.windowing.entries(job.bi, job.sigma)
+
+    def store(self, job):
+        p = self.plan
+        for j, (di, ti, K) in enumerate(job.fun_readers):
+            self.slabs[0][di, ti], dmud = geometry.resistivity_sensitivity(job.dJ[j], job.entries, p.model.formation_model,
+                                                                           _ra_scale(K, job.J[j], p.dim), self.ti_normal)
+            self.slabs[1][di, ti] = dmud * (-1.0 / p.mud[job.bi] ** 2)
+
+    def publish(self, model):
+        model.sensitivities = _per_tool(model, lambda i: self.slabs[0][:, i])
+        model.mud_sensitivity = _per_tool(model, lambda i: self.slabs[1][:, i])
+
+
+class _Maps(_Output):
+    """d ln Ra / d ln R of every cell of the grid - every sigma inside it scaled by 1 / s, d sigma / d ln s = -sigma - and of the
+    rest pseudo-cell, the last entry of a record."""
+    adjoint = True
+
+    def __init__(self, plan, grid):
+        self.plan, self.grid = plan, grid
+        self.lateral = "x" if "x" in grid else "r"
+        self.n_cells = (len(grid["z"]) - 1) * (len(grid[self.lateral]) - 1)
+        self.slabs = [plan.slab(self.n_cells + 1)]
+
+    def prepare(self, job):
+        job.groups, job.group_mat, job.group_cell = geometry.sensitivity_cells(job.mesh, None, self.grid, self.plan.simulation_depths[job.bi])
+
+    def store(self, job):
+        half = 2.0 if self.plan.dim == 3 else 1.0
+        sig = np.asarray(job.sigma, dtype=float)
+        for j, (di, ti, K) in enumerate(job.fun_readers):
+            Ra = abs(K * job.J[j]) / half
+            w = sig[job.group_mat] * job.dJg[j] if sig.ndim == 1 else np.sum(sig[job.group_mat] * job.dJg[j], axis=(1, 2))
+            self.slabs[0][di, ti] = -(_ra_scale(K, job.J[j], self.plan.dim) / Ra) * np.bincount(job.group_cell, weights=w, minlength=self.n_cells + 1)
+
+    def publish(self, model):
+        n = self.n_cells
+        shape = (len(self.plan.depths), len(self.grid["z"]) - 1, len(self.grid[self.lateral]) - 1)
+        model.sensitivity_maps = _per_tool(model, lambda i: self.slabs[0][:, i, :n].reshape(shape))
+        model.sensitivity_map_rest = _per_tool(model, lambda i: self.slabs[0][:, i, n])
+        model.sensitivity_grid = {k: np.asarray(v, dtype=float) for k, v in self.grid.items()}
+
+
+class _BatchRunner:
+    """Stages 5 and 6: one batch from its window to every output, and the host threads that do so batch after batch."""
+
+    def __init__(self, plan, windowing, meshes, outputs):
+        self.plan, self.windowing, self.meshes, self.outputs = plan, windowing, meshes, outputs
+        self.free_ctx = queue.Queue()
+        for c in plan.contexts:
+            self.free_ctx.put(c)
+        self.acc = dict(mesh=0.0, solve=0.0, points=0, failed_batches=0, not_converged=0, first_error=None, pcg_steps=0, programming_error=None)
+        self.lock = threading.Lock()     # of acc
+
+    def run_batch(self, bi):
+        p, acc = self.plan, self.acc
+        batch = p.batches[bi]
+        try:
+            t0 = time.time()
+            fg, bh, sigma = self.windowing.window(bi)
+            job = types.SimpleNamespace(bi=bi, sigma=sigma, mesh=self.meshes.mesh(bi, fg, bh), groups=None, functionals=None)
+            sources, evals, job.readers = tasks.batch_rhs(batch, p.model.tools)
+            t1 = time.time()
+            opts = p.batch_opts(job.mesh)
+            if any(o.adjoint for o in self.outputs):
+                job.functionals, job.fun_readers = tasks.batch_functionals(batch, p.model.tools)
+            for o in self.outputs:
+                o.prepare(job)
+            c = self.free_ctx.get()
+            try:     # the solver entry follows from what the outputs asked for
+                if job.groups is not None:
+                    job.outs, job.J, job.dJ, job.dJg, st, rc = c.solve_batch_sens_groups(job.mesh, job.sigma, sources, evals, job.functionals,
+                                                                                         job.groups, len(job.group_mat), opts)
+                elif job.functionals is not None:
+                    job.outs, job.J, job.dJ, st, rc = c.solve_batch_sens(job.mesh, job.sigma, sources, evals, job.functionals, opts)
+                else:
+                    job.outs, st, rc = c.solve_batch(job.mesh, job.sigma, sources, evals, opts)
+            finally:
+                self.free_ctx.put(c)
+            t2 = time.time()
+            for o in self.outputs:
+                o.store(job)
+            n = sum(len(rd) for _, rd in zip(job.outs, job.readers))
+            with self.lock:
+                acc["mesh"] += t1 - t0; acc["solve"] += t2 - t1; acc["points"] += n
+                acc["not_converged"] += int(rc == solver.REMO_NOT_CONVERGED); acc["pcg_steps"] += int(st.get("pcg_steps", 0))
+        except Exception as ex:
+            rows = [(r.depth_index, r.tool_index) for s in batch.solves for r in s.records]
+            for o in self.outputs:      # any failure in a batch -> NaN for its records (worker.py:135-138: a bare except)
+                o.fail(rows)
+            with self.lock:             # ... but not silently: the reference's worker at least shows it on stderr
+                acc["failed_batches"] += 1
+                if acc["first_error"] is None:
+                    acc["first_error"] = "batch {}: {}: {}".format(bi, type(ex).__name__, ex)
+                # a programming error (e.g. in a custom mesh_provider) is recorded like any other failure HERE - a rank that
+                # raised now would miss the collectives of the report and leave the other ranks waiting in the all-reduce - and is
+                # raised once they are through
+                if isinstance(ex, (TypeError, AttributeError, NameError)) and acc["programming_error"] is None:
+                    acc["programming_error"] = ex
+
+    def _drive(self):
+        for bi in iter(self.meshes.next_batch, None):
+            self.run_batch(bi)
+
+    def drive(self):
+        """One host thread per context (ctypes calls release the GIL) when there is more than one of both, contexts and batches."""
+        n = len(self.plan.contexts)
+        if n > 1 and self.plan.share_len > 1:
+            with ThreadPoolExecutor(max_workers=n) as tp:
+                for fut in [tp.submit(self._drive) for _ in range(n)]:
+                    fut.result()
+        else:
+            self._drive()
 
 
 class Model:
@@ -309,7 +660,6 @@ class Model:
         if gpu_workers < 0:
             raise ValueError("Minimal number of gpu workers is 0")
         self.cpu_workers, self.gpu_workers = cpu_workers, gpu_workers
-        from . import solver, sweep
         # under torchrun (WORLD_SIZE > 1) the ranks share the sweep: join the process group here, as the reference
         # brings its farm up in initialize_workers (remo3d.py:592-599); without it every rank would compute every batch
         sweep.init_from_env()
@@ -352,285 +702,41 @@ class Model:
         d ln Ra / d ln R of every cell - every resistivity inside the cell (mud, flushed zones, Rh and Rv alike) scaled by a common
         factor - and self.sensitivity_map_rest[tool] [n_depths] with the same for everything outside the grid (the two sum to 1);
         NaN where the batch failed.  Implies the adjoint solves (remo_solve_batch_sens_groups); may be combined with sensitivities."""
-        from . import solver, sweep
-        extra = dict(solver_options or {})
         start = time.time()
-        measurement_depths = np.asarray(measurement_depths, dtype=float)
-        alert = False
-        for t in self.tools.values():
-            far = np.max(np.abs(t[0, :3]))
-            if far > domain_radius:
-                raise ValueError("Some electrodes are locate outside the simulation domain. Domain size have to be increased")
-            alert |= far > 0.75 * domain_radius
-        if alert and verbose:
-            print("Some electrodes are located close to the boundary of the simulation domain. This may cause problems during simulation. "
-                  "Consider increase of the domain size")
-        if mesh_generator not in ("auto", "gmsh", "netgen"):
-            raise ValueError("mesh_generator has to be 'auto', 'gmsh' or 'netgen'")
-        is3d = not np.isclose(self.dip_deg, 0)
-        if is3d and mesh_generator == "netgen":
-            raise ValueError("The only mesh generator supported in 3D models is gmsh")
-        if preconditioner not in ("local", "multigrid"):
-            raise ValueError("preconditioner has to be 'local' or 'multigrid'")
-        if self.ctx is None:
-            raise RuntimeError("initialize_workers() has to be called before simulate_logs()")
-        if self.dip_deg != 0:
-            self.borehole_model = self._add_points_to_borehole()
-        dim = 3 if is3d else 2
-        netgen_path = (not is3d) and mesh_generator in ("auto", "netgen")
-        provider = mesh_provider or default_mesh_provider(scale=mesh_scale)
-
-        simulation_depths, batches = self._prepare_simulation_depths_and_tasks(measurement_depths, batch_size)
-        borehole_geometry = np.ascontiguousarray(self.borehole_model[:, :2])
-        mud = np.interp(simulation_depths, self.borehole_model[:, 0], self.borehole_model[:, 2])
-        if verbose and sweep.rank() == 0:
-            print("{} simulation tasks prepared".format(len(batches)))
-        # ONE dictionary of solver keywords: the explicit arguments, over-ridden by solver_options (a key given in both places used
-        # to raise "multiple values" inside every batch, i.e. a sweep of NaNs); unknown keys fail here, before any batch is drawn,
-        # on every rank alike
-        base_kw = dict(preconditioner=preconditioner, condense=condense, rtol=rtol, maxsteps=maxsteps, precision=precision)
-        base_kw.update(extra)
-        opts = solver.make_opts(**base_kw)
-        # the solver of the P1 block follows the mesh kind and the number of contexts (vertex_solver_options) unless the caller chose one
-        tuned_coarse = base_kw["preconditioner"] == "multigrid" and not any(k in extra for k in ("coarse", "coarse_degree", "coarse_ratio"))
-        conforming_default = mesh_provider is None     # the default 3D provider = conforming revolved meshes
-
-        n_tools = len(self.tools)
-        results = np.zeros((len(measurement_depths), n_tools))
-        t_solve = t_mesh = 0.0
-        n_points = 0
-
-        formation_h = self.formation_model[:, :5]
-        formation_v = self._vertical_formation_model()
-        formation_ids = geometry.entry_id_table(self.formation_model) if sensitivities else None
-        n_layers, n_cols = self.formation_model.shape[0], self.formation_model.shape[1] - 2
-        sens_res = np.zeros((len(measurement_depths), n_tools, n_layers, n_cols)) if sensitivities else None
-        mud_res = np.zeros((len(measurement_depths), n_tools)) if sensitivities else None
-        sens_ti = sensitivities and self.formation_model.shape[1] >= 6 and bool(np.any(~np.isnan(self.formation_model[:, 5])))
-        ti_normal = (np.array([np.sin(self.dip_rad), 0.0, np.cos(self.dip_rad)]) if is3d else np.array([0.0, 1.0]))   # geometry.ti_conductivity
-        maps = sensitivity_grid is not None
-        adjoint = sensitivities or maps
-        if maps:
-            lateral = "x" if "x" in sensitivity_grid else "r"
-            n_cells = (len(sensitivity_grid["z"]) - 1) * (len(sensitivity_grid[lateral]) - 1)
-            map_res = np.zeros((len(measurement_depths), n_tools, n_cells + 1))     # the last entry: the rest pseudo-cell
-
-        def window_of(formation, bi):
-            if netgen_path:   # the reference's default 2D windowing (remo3d.py:776-779, worker.py:94)
-                return geometry.select_netgen_data_range(borehole_geometry, formation, mud[bi], simulation_depths[bi], domain_radius)
-            # Gmsh-path windowing (worker.py:84), the only one for dipping models
-            return geometry.select_data_range(borehole_geometry, formation, self.dip_rad if is3d else 0, mud[bi],
-                                              simulation_depths[bi], domain_radius)
-
-        def window(bi):
-            """(geometry, borehole, sigma): sigma is 1-D as in the reference unless a material of the window is anisotropic; then
-            [n_mat, dim, dim] TI tensors.  The vertical conductivities come from windowing the RVUZ copy of the table the same way,
-            so that every quirk of the windowing (e.g. a dropped flushed zone: the layer takes RTFZ) applies to both alike."""
-            fg, bh, sigma = window_of(formation_h, bi)
-            if formation_v is None:
-                return fg, bh, sigma
-            sigma_v = window_of(formation_v, bi)[2]
-            if len(sigma_v) != len(sigma):
-                raise RuntimeError("windowing of RTUZ and RVUZ gave different materials")
-            if np.array_equal(np.asarray(sigma_v), np.asarray(sigma)):
-                return fg, bh, sigma
-            return fg, bh, geometry.ti_conductivity(sigma, sigma_v, self.dip_rad if is3d else 0.0, dim)
-
-        # Which batches this rank takes: its block-cyclic share ("static"), or whatever it draws from the shared counter
-        # while it is free ("dynamic", the reference's pull scheduling, remo3d.py:843-860) - sweep.BatchQueue.
-        # mesh_workers > 0: the default mesher runs ahead of the solver in that many spawned processes (the
-        # reference meshes inside its MPI workers, i.e. in parallel too: worker.py:84-97)
-        import collections
-        import queue
-        import threading
-        bq = sweep.BatchQueue(len(batches), schedule)
-        share_len = len(list(sweep.my_share(len(batches))))
-        pool, pending = None, {}
-        if mesh_workers is None:    # default: the reference's cpu_workers mesh (and solve) in parallel; here they mesh, for sweeps long
-            mesh_workers = min(int(self.cpu_workers or 0), 8) if (mesh_provider is None and share_len >= 16) else 0   # enough to pay for the start-up
-        if mesh_workers > 0 and mesh_provider is None and share_len > 1:
-            import sys
-            main_mod = sys.modules.get("__main__")
-            hidden = {}
-            try:
-                import multiprocessing
-                from concurrent.futures import ProcessPoolExecutor
-                # spawned children re-import the caller's __main__ (and would re-run a script without an
-                # `if __name__ == "__main__"` guard, GPU contexts and all): hide its path while the workers start -
-                # the worker functions live in this module, nothing of __main__ is needed over there
-                for attr in ("__file__", "__spec__"):
-                    if main_mod is not None and getattr(main_mod, attr, None) is not None:
-                        hidden[attr] = getattr(main_mod, attr)
-                        setattr(main_mod, attr, None)
-                pool = ProcessPoolExecutor(max_workers=int(mesh_workers), mp_context=multiprocessing.get_context("spawn"),
-                                           initializer=_mesh_worker_init, initargs=(dict(scale=mesh_scale),))
-                # the executor starts a process per submit while none is idle: start them ALL here, while __main__ is hidden
-                for fut in [pool.submit(time.sleep, 0.25) for _ in range(int(mesh_workers))]:
-                    fut.result()
-            except Exception:     # no worker processes here: mesh inline
-                pool, pending = None, {}
-            finally:
-                for attr, v in hidden.items():
-                    setattr(main_mod, attr, v)
-        ctxs = [self.ctx] + list(getattr(self, "extra_ctx", []))
-        n_ctx_total = len(ctxs)
-        free_ctx = queue.Queue()
-        for c in ctxs:
-            free_ctx.put(c)
-        acc = dict(mesh=0.0, solve=0.0, points=0, failed_batches=0, not_converged=0, first_error=None, pcg_steps=0, programming_error=None)
-        lock = threading.Lock()
-        # batches drawn ahead of the solver so that their meshes are in the making: the whole share at once when it is
-        # fixed anyway, a few (they are OWNED once drawn) under the pull schedule
-        ahead = collections.deque()
-        depth = 1 if pool is None else (share_len if schedule == "static" else int(mesh_workers) + len(ctxs))
-        draw, draw_lock = iter(bq), threading.Lock()
-
-        def next_batch():
-            with draw_lock:
-                # under the pull schedule a drawn batch is OWNED: near the end of the sweep a rank must not sit on a queue of
-                # batches the other ranks are idle for - draw ahead no further than its fair part of what is left
-                cap = depth if schedule == "static" else max(1, min(depth, 1 + bq.remaining_hint() // (2 * max(1, sweep.world_size()))))
-                while len(ahead) < cap:
-                    try:
-                        bi = next(draw)
-                    except StopIteration:
-                        break
-                    if pool is not None:
-                        try:
-                            fg, bh, _ = window(bi)
-                            pending[bi] = pool.submit(_mesh_worker_run, (dim, domain_radius, batches[bi].electrodes, fg, bh, self.dip_rad))
-                        except Exception:
-                            pass      # reported when the batch's turn comes
-                    ahead.append(bi)
-                return ahead.popleft() if ahead else None
-
-        def run_batch(bi):
-            batch = batches[bi]
-            rows = [(r.depth_index, r.tool_index) for s in batch.solves for r in s.records]
-            try:
-                t0 = time.time()
-                fg, bh, sigma = window(bi)
-                mesh = None
-                if bi in pending:
-                    try:
-                        mesh = pending.pop(bi).result()
-                    except Exception:     # a worker process died: mesh this batch here
-                        mesh = None
-                if mesh is None:
-                    mesh = provider(dim, domain_radius, batch, fg, bh, self.dip_rad)
-                sources, evals, readers = tasks.batch_rhs(batch, self.tools)
-                t1 = time.time()
-                bopts = opts
-                if tuned_coarse and getattr(mesh, "dim", 0) == 3:
-                    vs = vertex_solver_options(3, mesh.n_nodes, conforming_default, n_ctx_total)
-                    if vs:
-                        bopts = solver.make_opts(**dict(base_kw, **vs))
-                if adjoint:
-                    functionals, fun_readers = tasks.batch_functionals(batch, self.tools)
-                if sensitivities:     # the table entry behind every material: the identifier table through the same windowing
-                    entries = geometry.material_entries(window_of(formation_ids, bi)[2])
-                    if len(entries) != len(sigma):
-                        raise RuntimeError("windowing of the entry identifiers gave different materials")
-                    if sens_ti and np.ndim(sigma) == 1:     # dRa/dRTUZ and dRa/dRVUZ apart need the tensor derivative, also where the window is isotropic
-                        sigma = geometry.ti_conductivity(sigma, sigma, self.dip_rad if is3d else 0.0, dim)
-                if maps:
-                    groups, group_mat, group_cell = geometry.sensitivity_cells(mesh, None, sensitivity_grid, simulation_depths[bi])
-                c = free_ctx.get()
-                try:
-                    if maps:
-                        outs, J, dJ, dJg, st, rc = c.solve_batch_sens_groups(mesh, sigma, sources, evals, functionals, groups, len(group_mat), bopts)
-                    elif sensitivities:
-                        outs, J, dJ, st, rc = c.solve_batch_sens(mesh, sigma, sources, evals, functionals, bopts)
-                    else:
-                        outs, st, rc = c.solve_batch(mesh, sigma, sources, evals, bopts)
-                finally:
-                    free_ctx.put(c)
-                t2 = time.time()
-                if sensitivities:     # Ra = |K J| (/ 2 in 3D): dRa/dR = sign(K J) K (/ 2) * dJ/dsigma * (-1 / R^2)
-                    for j, (di, ti, K) in enumerate(fun_readers):
-                        scale = np.sign(K * J[j]) * K / (2.0 if dim == 3 else 1.0)
-                        sens_res[di, ti], dmud = geometry.resistivity_sensitivity(dJ[j], entries, self.formation_model, scale, ti_normal)
-                        mud_res[di, ti] = dmud * (-1.0 / mud[bi] ** 2)
-                if maps:     # d ln Ra / d ln R of a cell: every sigma inside it scaled by 1 / s, d sigma / d ln s = -sigma
-                    sig = np.asarray(sigma, dtype=float)
-                    for j, (di, ti, K) in enumerate(fun_readers):
-                        scale = np.sign(K * J[j]) * K / (2.0 if dim == 3 else 1.0)
-                        Ra = abs(K * J[j]) / (2.0 if dim == 3 else 1.0)
-                        w = sig[group_mat] * dJg[j] if sig.ndim == 1 else np.sum(sig[group_mat] * dJg[j], axis=(1, 2))
-                        map_res[di, ti] = -(scale / Ra) * np.bincount(group_cell, weights=w, minlength=n_cells + 1)
-                n = 0
-                for u, rd in zip(outs, readers):
-                    for (di, ti, K, o, m) in rd:
-                        results[di, ti] = tasks.apparent_resistivity(u[o:o + m], m, K, dim)
-                        n += 1
-                with lock:
-                    acc["mesh"] += t1 - t0; acc["solve"] += t2 - t1; acc["points"] += n
-                    acc["not_converged"] += int(rc == solver.REMO_NOT_CONVERGED); acc["pcg_steps"] += int(st.get("pcg_steps", 0))
-            except Exception as ex:
-                for di, ti in rows:      # any failure in a batch -> NaN for its records (worker.py:135-138: a bare except)
-                    results[di, ti] = np.nan
-                    if sensitivities:
-                        sens_res[di, ti] = np.nan
-                        mud_res[di, ti] = np.nan
-                    if maps:
-                        map_res[di, ti] = np.nan
-                with lock:               # ... but not silently: the reference's worker at least shows it on stderr
-                    acc["failed_batches"] += 1
-                    if acc["first_error"] is None:
-                        acc["first_error"] = "batch {}: {}: {}".format(bi, type(ex).__name__, ex)
-                    # a programming error (e.g. in a custom mesh_provider) is recorded like any other failure HERE - a rank that
-                    # raised now would miss the collectives below and leave the other ranks waiting in the all-reduce - and is
-                    # raised once they are through
-                    if isinstance(ex, (TypeError, AttributeError, NameError)) and acc["programming_error"] is None:
-                        acc["programming_error"] = ex
-
-        def drive():
-            while True:
-                bi = next_batch()
-                if bi is None:
-                    return
-                run_batch(bi)
-
+        plan = _Plan(self, measurement_depths, domain_radius, batch_size, mesh_generator, mesh_provider, mesh_scale,
+                     dict(preconditioner=preconditioner, condense=condense, rtol=rtol, maxsteps=maxsteps, precision=precision),
+                     solver_options, verbose)
+        windowing = _Windowing(plan)
+        outputs = [_Logs(plan)]     # the ONE place where the keywords of the further outputs are looked at
+        if sensitivities:
+            outputs.append(_LayerSensitivities(plan, windowing))
+        if sensitivity_grid is not None:
+            outputs.append(_Maps(plan, sensitivity_grid))
+        bq = sweep.BatchQueue(len(plan.batches), schedule)
+        meshes = _MeshAhead(plan, windowing, bq, schedule, mesh_workers)
+        runner = _BatchRunner(plan, windowing, meshes, outputs)
         t_busy = time.time()
         try:
-            if len(ctxs) > 1 and share_len > 1:
-                from concurrent.futures import ThreadPoolExecutor
-                with ThreadPoolExecutor(max_workers=len(ctxs)) as tp:     # one host thread per context; ctypes calls release the GIL
-                    for fut in [tp.submit(drive) for _ in ctxs]:
-                        fut.result()
-            else:
-                drive()
+            runner.drive()
         finally:
-            if pool is not None:     # whatever happened above, the mesh processes do not outlive the sweep
-                pool.shutdown(wait=False, cancel_futures=True)
+            meshes.shutdown()
         t_busy = time.time() - t_busy
-        mine = list(bq.taken)
-        t_mesh, t_solve, n_points = acc["mesh"], acc["solve"], acc["points"]
-        bq.check_complete()          # collective: every batch was taken exactly once over the ranks
-        results = sweep.combine(results)
-        if sensitivities:     # the same pattern as the logs: every rank has zeros outside its own records
-            sens_res, mud_res = sweep.combine(sens_res), sweep.combine(mud_res)
-            self.sensitivities = {name: sens_res[:, i] for i, name in enumerate(self.tools.keys())}
-            self.mud_sensitivity = {name: mud_res[:, i] for i, name in enumerate(self.tools.keys())}
-        else:
-            self.sensitivities = self.mud_sensitivity = None
-        if maps:
-            map_res = sweep.combine(map_res)
-            shape = (len(measurement_depths), len(sensitivity_grid["z"]) - 1, len(sensitivity_grid[lateral]) - 1)
-            self.sensitivity_maps = {name: map_res[:, i, :n_cells].reshape(shape) for i, name in enumerate(self.tools.keys())}
-            self.sensitivity_map_rest = {name: map_res[:, i, n_cells] for i, name in enumerate(self.tools.keys())}
-            self.sensitivity_grid = {k: np.asarray(v, dtype=float) for k, v in sensitivity_grid.items()}
-        else:
-            self.sensitivity_maps = self.sensitivity_map_rest = self.sensitivity_grid = None
-        self.logs = {name: np.vstack([measurement_depths, results[:, i]]).T for i, name in enumerate(self.tools.keys())}
-        self.timing = dict(total_s=time.time() - start, mesh_s=t_mesh, solve_s=t_solve, points=n_points, batches=len(batches),
-                           my_batches=len(mine), world_size=sweep.world_size(), schedule=schedule, busy_s=t_busy,
+        # the report.  Collectives, in this order on every rank - also one that drew nothing or whose batches failed
+        acc = runner.acc
+        bq.check_complete()          # every batch was taken exactly once over the ranks
+        for o in outputs:            # the same pattern for every slab: every rank has zeros outside its own records
+            o.combine()
+        self.sensitivities = self.mud_sensitivity = self.sensitivity_maps = self.sensitivity_map_rest = self.sensitivity_grid = None
+        for o in outputs:
+            o.publish(self)
+        self.timing = dict(total_s=time.time() - start, mesh_s=acc["mesh"], solve_s=acc["solve"], points=acc["points"], batches=len(plan.batches),
+                           my_batches=len(bq.taken), world_size=sweep.world_size(), schedule=schedule, busy_s=t_busy,
                            busy_s_per_rank=[b[0] for b in sweep.gather_floats([t_busy])], failed_batches=acc["failed_batches"],
                            not_converged=acc["not_converged"], first_error=acc["first_error"], pcg_steps=acc["pcg_steps"])
         if acc["programming_error"] is not None:     # every rank is through the collectives: now it may raise
             raise acc["programming_error"]
         if verbose and acc["failed_batches"]:
-            print("rank {}: {} of {} batches failed (NaN in the logs); first: {}".format(sweep.rank(), acc["failed_batches"], len(mine), acc["first_error"]))
+            print("rank {}: {} of {} batches failed (NaN in the logs); first: {}".format(sweep.rank(), acc["failed_batches"], len(bq.taken), acc["first_error"]))
         if verbose and acc["not_converged"]:
             print("rank {}: PCG stopped at maxsteps in {} batches".format(sweep.rank(), acc["not_converged"]))
         if verbose and sweep.rank() == 0:

@@ -63,21 +63,22 @@ def make_opts(preconditioner="multigrid", condense=True, maxsteps=1000, rtol=1e-
     return o
 
 
+def _ragged(mismatch, *columns):
+    """columns: lists of 1-D sequences, item k of every list equally long -> [item pointer int32 [n + 1], the float64 concatenation
+    of every list]: the CSR-like form in which the library takes sources, evaluation points and functionals."""
+    cols = [[np.atleast_1d(np.asarray(a, dtype=np.float64)) for a in col] for col in columns]
+    if any(a.shape != b.shape for col in cols[1:] for a, b in zip(cols[0], col)):
+        raise ValueError(mismatch)
+    item_ptr = np.zeros(len(cols[0]) + 1, dtype=np.int32)
+    item_ptr[1:] = np.cumsum([a.size for a in cols[0]])
+    return [item_ptr] + [np.ascontiguousarray(np.concatenate(col) if col else np.zeros(0), dtype=np.float64) for col in cols]
+
+
 def _rhs_arrays(sources, evals):
     """sources: list (per RHS) of (z array, I array); evals: list (per RHS) of z arrays."""
-    src_ptr = np.zeros(len(sources) + 1, dtype=np.int32)
-    eval_ptr = np.zeros(len(evals) + 1, dtype=np.int32)
-    sz, sI, ez = [], [], []
-    for k, (z, I) in enumerate(sources):
-        z = np.atleast_1d(np.asarray(z, dtype=np.float64)); I = np.atleast_1d(np.asarray(I, dtype=np.float64))
-        if z.shape != I.shape:
-            raise ValueError("source positions and strengths differ in length")
-        sz.append(z); sI.append(I); src_ptr[k + 1] = src_ptr[k] + z.size
-    for k, z in enumerate(evals):
-        z = np.atleast_1d(np.asarray(z, dtype=np.float64))
-        ez.append(z); eval_ptr[k + 1] = eval_ptr[k] + z.size
-    cat = lambda xs: np.ascontiguousarray(np.concatenate(xs) if xs else np.zeros(0), dtype=np.float64)
-    return src_ptr, cat(sz), cat(sI), eval_ptr, cat(ez)
+    src_ptr, sz, sI = _ragged("source positions and strengths differ in length", [z for (z, I) in sources], [I for (z, I) in sources])
+    eval_ptr, ez = _ragged(None, list(evals))
+    return src_ptr, sz, sI, eval_ptr, ez
 
 
 def sigma_table(sigma, dim=None):
@@ -99,17 +100,19 @@ def sigma_table(sigma, dim=None):
 
 def _functional_arrays(functionals):
     """functionals: list of (rhs, z array, w array) -> (fun_rhs, fun_ptr, fun_z, fun_w) of remo_solve_batch_sens."""
-    n_fun = len(functionals)
-    fun_rhs = np.ascontiguousarray([f[0] for f in functionals], dtype=np.int32)
-    fun_ptr = np.zeros(n_fun + 1, dtype=np.int32)
-    fz, fw = [], []
-    for j, (_, z, w) in enumerate(functionals):
-        z = np.atleast_1d(np.asarray(z, dtype=np.float64)); w = np.atleast_1d(np.asarray(w, dtype=np.float64))
-        if z.shape != w.shape:
-            raise ValueError("functional points and weights differ in length")
-        fz.append(z); fw.append(w); fun_ptr[j + 1] = fun_ptr[j] + z.size
-    cat = lambda xs: np.ascontiguousarray(np.concatenate(xs) if xs else np.zeros(0), dtype=np.float64)
-    return fun_rhs, fun_ptr, cat(fz), cat(fw)
+    fun_ptr, fz, fw = _ragged("functional points and weights differ in length", [z for (_, z, w) in functionals], [w for (_, z, w) in functionals])
+    return np.ascontiguousarray([f[0] for f in functionals], dtype=np.int32), fun_ptr, fz, fw
+
+
+def _batch_args(handle, mesh, sigma, sources, evals):
+    """The arguments every batch entry begins with (remo_solve_batch*, remo_batch_create*): handle, mesh, conductivity table, sources
+    and evaluation points.  Returns (args, sigma table, tensor?, eval_ptr, keep); keep holds what the pointers in args look at."""
+    sigma, tensor = sigma_table(sigma, int(mesh.dim))
+    src_ptr, sz, sI, eval_ptr, ez = _rhs_arrays(sources, evals)
+    ms, keep = _lib.mesh_struct(mesh)
+    args = [handle, C.byref(ms), len(sigma), ptr(sigma, C.c_double), len(sources), ptr(src_ptr, C.c_int32), ptr(sz, C.c_double),
+            ptr(sI, C.c_double), ptr(eval_ptr, C.c_int32), ptr(ez, C.c_double)]
+    return args, sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez)
 
 
 def _symmetric_gradient(dJ, d, tensor):
@@ -155,24 +158,41 @@ class Context:
     def last_error(self) -> str:
         return (self._L.remo_last_error(self._h) or b"").decode()
 
+    def _one_shot(self, kind, mesh, sigma, sources, evals, opts, raise_on_error, functionals=None, groups=None, n_group=None):
+        """The one marshalling path of the one-shot entries remo_solve_batch<kind>[_tensor], kind "", "_sens" or "_sens_groups":
+        the common arguments, then the functionals and the groups with their outputs where the kind has them.  Returns
+        (potentials, [J, dJ, [dJg],] stats, rc)."""
+        args, sigma, tensor, eval_ptr, keep = _batch_args(self._h, mesh, sigma, sources, evals)
+        d, nc = int(mesh.dim), (sigma.shape[1] if tensor else 1)
+        out = np.full(int(eval_ptr[-1]), np.nan)
+        args.append(ptr(out, C.c_double))
+        J, grads = [], []
+        if kind:
+            n_fun = len(functionals)
+            fun_rhs, fun_ptr, fz, fw = _functional_arrays(functionals)
+            args += [n_fun, ptr(fun_rhs, C.c_int32), ptr(fun_ptr, C.c_int32), ptr(fz, C.c_double), ptr(fw, C.c_double)]
+            J, grads = [np.full(n_fun, np.nan)], [np.full((n_fun, len(sigma), nc), np.nan)]
+            if kind == "_sens_groups":
+                groups = np.ascontiguousarray(groups, dtype=np.int32).ravel()
+                if groups.size != keep[1][1].shape[0]:
+                    raise ValueError("groups must hold one id per element")
+                n_group = int(groups.max(initial=-1)) + 1 if n_group is None else int(n_group)
+                args += [n_group, ptr(groups, C.c_int32)]
+                grads.append(np.full((n_fun, max(n_group, 0), nc), np.nan))
+            args += [ptr(a, C.c_double) for a in J + grads]
+        st = RemoStats()
+        o = opts if opts is not None else make_opts()
+        rc = getattr(self._L, "remo_solve_batch" + kind + ("_tensor" if tensor else ""))(*args, C.byref(o), C.byref(st))
+        if rc < 0 and raise_on_error:
+            raise RemoError(rc, self.last_error())
+        potentials = [out[eval_ptr[k]:eval_ptr[k + 1]] for k in range(len(evals))]
+        return (potentials, *J, *[_symmetric_gradient(g, d, tensor) for g in grads], st.as_dict(), rc)
+
     def solve_batch(self, mesh, sigma, sources, evals, opts: Optional[RemoOpts] = None, raise_on_error=True):
         """One-shot remo_solve_batch.  Returns (list of per-RHS potential arrays, stats dict, rc).
         sigma: [n_mat] conductivities, or [n_mat, dim, dim] symmetric positive definite tensors in the mesh's frame
         (remo_solve_batch_tensor)."""
-        sigma, tensor = sigma_table(sigma, int(mesh.dim))
-        src_ptr, sz, sI, eval_ptr, ez = _rhs_arrays(sources, evals)
-        ms, keep = _lib.mesh_struct(mesh)
-        out = np.full(int(eval_ptr[-1]), np.nan)
-        st = RemoStats()
-        o = opts if opts is not None else make_opts()
-        entry = self._L.remo_solve_batch_tensor if tensor else self._L.remo_solve_batch
-        rc = entry(self._h, C.byref(ms), len(sigma), ptr(sigma, C.c_double), len(sources),
-                   ptr(src_ptr, C.c_int32), ptr(sz, C.c_double), ptr(sI, C.c_double),
-                   ptr(eval_ptr, C.c_int32), ptr(ez, C.c_double), ptr(out, C.c_double),
-                   C.byref(o), C.byref(st))
-        if rc < 0 and raise_on_error:
-            raise RemoError(rc, self.last_error())
-        return [out[eval_ptr[k]:eval_ptr[k + 1]] for k in range(len(evals))], st.as_dict(), rc
+        return self._one_shot("", mesh, sigma, sources, evals, opts, raise_on_error)
 
     def solve_batch_sens(self, mesh, sigma, sources, evals, functionals, opts: Optional[RemoOpts] = None, raise_on_error=True):
         """One-shot remo_solve_batch_sens: the batch of solve_batch plus linear functionals of the potentials and their derivatives
@@ -180,27 +200,7 @@ class Context:
         J = sum_i w[i] * u_rhs(z[i]).  Returns (potentials, J [n_fun], dJ, stats, rc) with dJ [n_fun, n_mat] for sigma [n_mat] and
         [n_fun, n_mat, dim, dim] for tensors: symmetric G with dJ = G : dSigma for symmetric dSigma (the library's triangle holds
         both halves of an off-diagonal pair; each half gets half of it here)."""
-        sigma, tensor = sigma_table(sigma, int(mesh.dim))
-        src_ptr, sz, sI, eval_ptr, ez = _rhs_arrays(sources, evals)
-        n_fun = len(functionals)
-        fun_rhs, fun_ptr, fz, fw = _functional_arrays(functionals)
-        ms, keep = _lib.mesh_struct(mesh)
-        d = int(mesh.dim)
-        n_mat, nc = len(sigma), (sigma.shape[1] if tensor else 1)
-        out = np.full(int(eval_ptr[-1]), np.nan)
-        J = np.full(n_fun, np.nan)
-        dJ = np.full((n_fun, n_mat, nc), np.nan)
-        st = RemoStats()
-        o = opts if opts is not None else make_opts()
-        entry = self._L.remo_solve_batch_sens_tensor if tensor else self._L.remo_solve_batch_sens
-        rc = entry(self._h, C.byref(ms), n_mat, ptr(sigma, C.c_double), len(sources),
-                   ptr(src_ptr, C.c_int32), ptr(sz, C.c_double), ptr(sI, C.c_double),
-                   ptr(eval_ptr, C.c_int32), ptr(ez, C.c_double), ptr(out, C.c_double),
-                   n_fun, ptr(fun_rhs, C.c_int32), ptr(fun_ptr, C.c_int32), ptr(fz, C.c_double), ptr(fw, C.c_double),
-                   ptr(J, C.c_double), ptr(dJ, C.c_double), C.byref(o), C.byref(st))
-        if rc < 0 and raise_on_error:
-            raise RemoError(rc, self.last_error())
-        return [out[eval_ptr[k]:eval_ptr[k + 1]] for k in range(len(evals))], J, _symmetric_gradient(dJ, d, tensor), st.as_dict(), rc
+        return self._one_shot("_sens", mesh, sigma, sources, evals, opts, raise_on_error, functionals)
 
     def solve_batch_sens_groups(self, mesh, sigma, sources, evals, functionals, groups, n_group=None, opts: Optional[RemoOpts] = None,
                                 raise_on_error=True):
@@ -209,35 +209,7 @@ class Context:
         (default: largest id + 1).  With sigma_e = sigma_mat(e) + p_group(e), dJg[j, g] = dJ_j/dp_g.  Returns
         (potentials, J, dJ, dJg, stats, rc); dJg is [n_fun, n_group] for sigma [n_mat] and [n_fun, n_group, dim, dim] for tensors,
         with the symmetric-G convention of dJ."""
-        sigma, tensor = sigma_table(sigma, int(mesh.dim))
-        src_ptr, sz, sI, eval_ptr, ez = _rhs_arrays(sources, evals)
-        fun_rhs, fun_ptr, fz, fw = _functional_arrays(functionals)
-        n_fun = len(functionals)
-        ms, keep = _lib.mesh_struct(mesh)
-        groups = np.ascontiguousarray(groups, dtype=np.int32).ravel()
-        if groups.size != keep[1].shape[0]:
-            raise ValueError("groups must hold one id per element")
-        if n_group is None:
-            n_group = int(groups.max(initial=-1)) + 1
-        n_group = int(n_group)
-        d = int(mesh.dim)
-        n_mat, nc = len(sigma), (sigma.shape[1] if tensor else 1)
-        out = np.full(int(eval_ptr[-1]), np.nan)
-        J = np.full(n_fun, np.nan)
-        dJ = np.full((n_fun, n_mat, nc), np.nan)
-        dJg = np.full((n_fun, max(n_group, 0), nc), np.nan)
-        st = RemoStats()
-        o = opts if opts is not None else make_opts()
-        entry = self._L.remo_solve_batch_sens_groups_tensor if tensor else self._L.remo_solve_batch_sens_groups
-        rc = entry(self._h, C.byref(ms), n_mat, ptr(sigma, C.c_double), len(sources),
-                   ptr(src_ptr, C.c_int32), ptr(sz, C.c_double), ptr(sI, C.c_double),
-                   ptr(eval_ptr, C.c_int32), ptr(ez, C.c_double), ptr(out, C.c_double),
-                   n_fun, ptr(fun_rhs, C.c_int32), ptr(fun_ptr, C.c_int32), ptr(fz, C.c_double), ptr(fw, C.c_double),
-                   n_group, ptr(groups, C.c_int32), ptr(J, C.c_double), ptr(dJ, C.c_double), ptr(dJg, C.c_double), C.byref(o), C.byref(st))
-        if rc < 0 and raise_on_error:
-            raise RemoError(rc, self.last_error())
-        return ([out[eval_ptr[k]:eval_ptr[k + 1]] for k in range(len(evals))], J, _symmetric_gradient(dJ, d, tensor),
-                _symmetric_gradient(dJg, d, tensor), st.as_dict(), rc)
+        return self._one_shot("_sens_groups", mesh, sigma, sources, evals, opts, raise_on_error, functionals, groups, n_group)
 
     def sens_group_timing(self):
         """ms of the group path of the last solve_batch_sens_groups on this context (remo_debug_sens_group_timing): (group order,
@@ -263,15 +235,9 @@ class Batch:
     def __init__(self, ctx: Context, mesh, sigma, sources, evals):
         self.ctx = ctx
         self._L = ctx._L
-        sigma, tensor = sigma_table(sigma, int(mesh.dim))
-        self._arr = _rhs_arrays(sources, evals)
-        src_ptr, sz, sI, eval_ptr, ez = self._arr
-        ms, keep = _lib.mesh_struct(mesh)
+        args, _, tensor, self._eval_ptr, keep = _batch_args(ctx._h, mesh, sigma, sources, evals)
         h = C.c_void_p()
-        create = self._L.remo_batch_create_tensor if tensor else self._L.remo_batch_create
-        rc = create(ctx._h, C.byref(ms), len(sigma), ptr(sigma, C.c_double), len(sources),
-                    ptr(src_ptr, C.c_int32), ptr(sz, C.c_double), ptr(sI, C.c_double),
-                    ptr(eval_ptr, C.c_int32), ptr(ez, C.c_double), C.byref(h))
+        rc = (self._L.remo_batch_create_tensor if tensor else self._L.remo_batch_create)(*args, C.byref(h))
         if rc != 0:
             raise RemoError(rc, ctx.last_error())
         self._h = h
@@ -293,7 +259,7 @@ class Batch:
         return rc
 
     def fetch(self):
-        eval_ptr = self._arr[3]
+        eval_ptr = self._eval_ptr
         out = np.full(int(eval_ptr[-1]), np.nan)
         rc = self._L.remo_batch_fetch(self.ctx._h, self._h, ptr(out, C.c_double))
         if rc != 0:
