@@ -239,6 +239,45 @@ int remo_solve_batch_sens_groups_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh
                                         const remo_opts_t *opts, remo_stats_t *stats);
 
 /*
+ * Solutions that survive a call (added within ABI 7: additive, detected by the presence of the symbols).  A remo_warm_t owns one
+ * device allocation on device_id (plain hipMalloc, grow-only) that after a successful remo_solve_batch_sens_warm holds the solutions
+ * of all its forward and adjoint columns, n_free * (n_rhs + n_fun) doubles.  It is tied to the device, not to a context: any context
+ * of that device may use it, one call at a time.  Meant for repeated calls on one mesh with slowly changing conductivities (an
+ * inversion's iterations): the next call solves A d = f - A x_prev for a correction of the stored solutions instead of starting every
+ * column from zero.
+ *   warm == NULL                 exactly remo_solve_batch_sens.
+ *   empty or mismatched object   (dim, n_nodes, n_elems, n_bfacets, condense, n_free, n_rhs or n_fun differs from what was stored:
+ *                                a memory-safety check, nothing more) the solve runs cold - with op = 2 u_out, J_out and dJ_out
+ *                                carry the bits of remo_solve_batch_sens - and the object is filled afterwards.
+ *   matching object              per chunk of columns: q = A x_prev, f' = f - q, the unchanged PCG from zero on A d = f' down to the
+ *                                absolute threshold the cold solve would have used (rtol^2 <C f, f> of the current system and
+ *                                preconditioner, measured by one PCG step on f), x = x_prev + d.  A chunk whose f' is already below
+ *                                it takes no further step.  Correctness never depends on the match: a stale guess only costs steps.
+ *                                stats: relres is relative to <C f, f>; pcg_steps counts the measuring step of every chunk.
+ * A call that returns < 0 leaves the object cleared; REMO_NOT_CONVERGED stores what it has.  precision = 1 gives REMO_ERR_ARG, an
+ * object of another device than the context's too.  remo_warm_create returns NULL (text: remo_last_error(NULL)) without a device.
+ * remo_warm_info: rows and columns stored (0 when empty), bytes allocated, and whether the last call that was handed the object
+ * started from its solutions (used_last); any pointer may be NULL.
+ */
+typedef struct remo_warm remo_warm_t;
+remo_warm_t *remo_warm_create(int device_id);
+void remo_warm_destroy(remo_warm_t *w);
+void remo_warm_clear(remo_warm_t *w); /* forget the stored solutions, keep the allocation */
+int remo_warm_info(const remo_warm_t *w, int64_t *n_free, int32_t *n_cols, int64_t *bytes, int32_t *used_last);
+int remo_solve_batch_sens_warm(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma,
+                               int32_t n_rhs, const int32_t *src_ptr, const double *src_z, const double *src_I,
+                               const int32_t *eval_ptr, const double *eval_z, double *u_out,
+                               int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr, const double *fun_z, const double *fun_w,
+                               double *J_out /*[n_fun]*/, double *dJ_out /*[n_fun * n_mat]*/, remo_warm_t *warm,
+                               const remo_opts_t *opts, remo_stats_t *stats);
+int remo_solve_batch_sens_warm_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor,
+                                      int32_t n_rhs, const int32_t *src_ptr, const double *src_z, const double *src_I,
+                                      const int32_t *eval_ptr, const double *eval_z, double *u_out,
+                                      int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr, const double *fun_z, const double *fun_w,
+                                      double *J_out /*[n_fun]*/, double *dJ_out /*[n_fun * n_mat * nc]*/, remo_warm_t *warm,
+                                      const remo_opts_t *opts, remo_stats_t *stats);
+
+/*
  * Staged form of the same work, for callers that keep a batch resident (bench.py: inputs are in
  * HBM before the timed region).  create = validate + upload; run = numbering, pattern, assembly,
  * PCG, evaluation, all RHS; fetch = potentials to the host.

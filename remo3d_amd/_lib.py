@@ -50,7 +50,8 @@ class RemoStats(C.Structure):
 
 # include/remo3d_hip.h: the drop-in boundary + inspection hooks of the parity tests
 EXPORTS = ["remo_abi_version", "remo_opts_default", "remo_ctx_create", "remo_ctx_destroy", "remo_last_error",
-           "remo_solve_batch", "remo_solve_batch_tensor", "remo_solve_batch_sens", "remo_solve_batch_sens_tensor", "remo_solve_batch_sens_groups", "remo_solve_batch_sens_groups_tensor", "remo_batch_create", "remo_batch_create_tensor", "remo_batch_run", "remo_batch_fetch", "remo_batch_destroy",
+           "remo_solve_batch", "remo_solve_batch_tensor", "remo_solve_batch_sens", "remo_solve_batch_sens_tensor", "remo_solve_batch_sens_groups", "remo_solve_batch_sens_groups_tensor",
+           "remo_warm_create", "remo_warm_destroy", "remo_warm_clear", "remo_warm_info", "remo_solve_batch_sens_warm", "remo_solve_batch_sens_warm_tensor", "remo_batch_create", "remo_batch_create_tensor", "remo_batch_run", "remo_batch_fetch", "remo_batch_destroy",
            "remo_batch_eval", "remo_batch_get_system", "remo_batch_get_vectors", "remo_batch_apply_coarse", "remo_batch_spmv",
            "remo_host_element_matrix", "remo_host_element_matrix_tensor", "remo_host_sens_element", "remo_host_factor_error", "remo_host_symbolic"]
 # include/remo3d_hip_debug.h: probes and tuning knobs (tests, tools, bench.py's `box` record) - not part of the boundary
@@ -89,6 +90,20 @@ def load():
     L.remo_solve_batch_sens.argtypes = batch_args + sens_args
     L.remo_solve_batch_sens_tensor.restype = C.c_int
     L.remo_solve_batch_sens_tensor.argtypes = batch_args + sens_args
+    # ... J_out, dJ_out, warm, opts, stats
+    warm_args = batch_args + [dp, C.c_int32, ip, ip, dp, dp, dp, dp, vp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]
+    L.remo_solve_batch_sens_warm.restype = C.c_int
+    L.remo_solve_batch_sens_warm.argtypes = warm_args
+    L.remo_solve_batch_sens_warm_tensor.restype = C.c_int
+    L.remo_solve_batch_sens_warm_tensor.argtypes = list(warm_args)
+    L.remo_warm_create.restype = vp
+    L.remo_warm_create.argtypes = [C.c_int]
+    L.remo_warm_destroy.restype = None
+    L.remo_warm_destroy.argtypes = [vp]
+    L.remo_warm_clear.restype = None
+    L.remo_warm_clear.argtypes = [vp]
+    L.remo_warm_info.restype = C.c_int
+    L.remo_warm_info.argtypes = [vp, i64p, ip, i64p, ip]
     # ... fun_z, fun_w, n_group, group, J_out, dJ_out, dJg_out, opts, stats
     SENS_GROUPS_ARGTYPES[:] = batch_args + [dp, C.c_int32, ip, ip, dp, dp, C.c_int32, ip, dp, dp, dp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]
     L.remo_solve_batch_sens_groups.restype = C.c_int

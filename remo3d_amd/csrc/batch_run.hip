@@ -16,6 +16,7 @@
 #include "pcg_host.h"
 #include "patch.h"
 #include "sens.h"
+#include "warm.h"
 
 using namespace remo;
 
@@ -577,8 +578,9 @@ struct RunTotals {
     float ms_solve = 0.f, ms_eval = 0.f;
 };
 
+// x_prev != nullptr: the chunk's columns of the previous call (remo_warm_t) - the solve starts from them (run_pcg_warm)
 int solve_chunk(const Run &r, const Plan &plan, const System &sys, const DevicePoints &dp, Solve &sv, MixedBuffers *mx, int k, int q0, int nq,
-                std::vector<double> &h_out, RunTotals &tot) {
+                std::vector<double> &h_out, RunTotals &tot, double *x_prev = nullptr) {
     remo_ctx *ctx = r.ctx;
     remo_batch *b = r.b;
     remo_stats_t *st = r.st;
@@ -597,7 +599,8 @@ int solve_chunk(const Run &r, const Plan &plan, const System &sys, const DeviceP
         buf.x_ev_at = dp.d_ev_at; buf.x_ev = dp.d_x_ev; buf.x_ev_n = nq * N;
     }
     HIP_TRY(hipEventRecord(ctx->ev[5], s));
-    ChunkResult cr = mx ? run_pcg_mixed(ctx, b->A, k, sys.d_f, buf, *mx, r.o, st, tot.ev_used) : run_pcg(ctx, b->A, k, sys.d_f, buf, r.o, st, tot.ev_used);
+    ChunkResult cr = mx ? run_pcg_mixed(ctx, b->A, k, sys.d_f, buf, *mx, r.o, st, tot.ev_used)
+                        : (x_prev ? run_pcg_warm(ctx, b->A, k, sys.d_f, buf, x_prev, r.o, st, tot.ev_used) : run_pcg(ctx, b->A, k, sys.d_f, buf, r.o, st, tot.ev_used));
     HIP_TRY(hipEventRecord(ctx->ev[6], s));
     if (nq > 0)
         launch_eval(dim, sy.condense, nq, dp.d_prhs + q0, dp.d_pI + q0, dp.d_found + q0, dp.d_phi + size_t(q0) * N, sy.eldof, sys.d_C, sys.d_M, k, buf.x,
@@ -836,6 +839,18 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         bool patch_op = false;
         if (int rc = choose_operator(r, plan, sys, sv, vb, patch_op)) return rc;
         const Sens sens = b->sens ? sens_take(r, sys) : Sens{};
+        // remo_solve_batch_sens_warm: the previous call's solutions, in the layout of `sens` (same block offsets in another allocation).
+        // Until this run ends well the object counts as empty; a hit keeps its contents, a miss makes room for this run's.
+        remo_warm *warm = b->sens ? b->warm : nullptr;
+        Sens prev{};
+        bool warm_hit = false;
+        if (warm) {
+            warm_hit = warm_matches(warm, b, o.condense != 0, sys.n);
+            warm->filled = false;
+            warm->used_last = warm_hit ? 1 : 0;
+            if (!warm_hit) warm_reserve(warm, warm_doubles(sys.n, b->n_rhs, b->sens->n_fun));
+            prev.keep = warm->d;
+        }
 
         // ---- solve, chunk by chunk ----------------------------------------------------------------------------------
         // serialize_solves: batches of other contexts may number and assemble beside this PCG, but not run theirs
@@ -852,7 +867,8 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
             const int k = std::min(b->n_rhs - c0, REMO_MAX_RHS);
             const int q0 = points.chunk_begin[chunk], nq = points.chunk_begin[chunk + 1] - q0;
             if (b->sens) b->d_x = sv.buf.x = sens.block(sys.n, b->n_rhs, false, chunk);   // the solution is formed where it stays
-            if (int rc = solve_chunk(r, plan, sys, dp, sv, mixed ? &mx : nullptr, k, q0, nq, h_out, tot)) return rc;
+            if (int rc = solve_chunk(r, plan, sys, dp, sv, mixed ? &mx : nullptr, k, q0, nq, h_out, tot,
+                                     warm_hit ? prev.block(sys.n, b->n_rhs, false, chunk) : nullptr)) return rc;
         }
         for (int q = 0; q < npts; ++q)
             if (points.eval_slot[q] >= 0) b->u_out[points.eval_slot[q]] = h_out[q];
@@ -861,7 +877,11 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
                 const int k = std::min(rq->n_fun - a0, REMO_MAX_RHS);
                 const int q0 = points.chunk_begin[chunk], nq = points.chunk_begin[chunk + 1] - q0;
                 b->d_x = sv.buf.x = sens.block(sys.n, b->n_rhs, true, ca);
-                if (int rc = solve_chunk(r, plan, sys, dp, sv, nullptr, k, q0, nq, h_out, tot)) return rc;
+                if (int rc = solve_chunk(r, plan, sys, dp, sv, nullptr, k, q0, nq, h_out, tot, warm_hit ? prev.block(sys.n, b->n_rhs, true, ca) : nullptr)) return rc;
+            }
+            if (warm) {   // a warm chunk left its sum in the object already; a cold run's solutions are copied there whole
+                if (!warm_hit) HIP_TRY(hipMemcpyAsync(warm->d, sens.keep, sizeof(double) * (warm_doubles(sys.n, b->n_rhs, rq->n_fun) - 64), hipMemcpyDeviceToDevice, s));
+                warm_label(warm, b, o.condense != 0, sys.n);
             }
             std::vector<double> h_dJ;
             sens_contract(r, sys, dp, points, sens, h_dJ);

@@ -1959,7 +1959,7 @@ __global__ void __launch_bounds__(256) k_mixed_accumulate(int64_t n, double *__r
         if (zero) e[i] = 0.f;
     }
 }
-static int stream_grid(int64_t n) {
+int stream_grid(int64_t n) {   // (also warm.hip's streams)
     int64_t g = (n + 255) / 256;
     if (g > 2048) g = 2048;
     return int(g < 1 ? 1 : g);

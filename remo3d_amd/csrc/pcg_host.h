@@ -26,4 +26,9 @@ ChunkResult run_pcg(remo_ctx *ctx, const CsrView &A, int k, const double *d_f, P
 ChunkResult run_pcg_mixed(remo_ctx *ctx, const CsrView &A, int k, const double *d_f, PcgBuffers &buf, MixedBuffers &mx, const remo_opts_t &o,
                           remo_stats_t *st, size_t &ev_used);
 
+// Warm-started chunk (remo_solve_batch_sens_warm): x_prev holds the previous call's solutions of these k columns.  d_f is
+// overwritten with f - A x_prev; buf.x ends as x_prev + d, and so does x_prev.  warm.h
+ChunkResult run_pcg_warm(remo_ctx *ctx, const CsrView &A, int k, double *d_f, PcgBuffers &buf, double *x_prev, const remo_opts_t &o,
+                         remo_stats_t *st, size_t &ev_used);
+
 }  // namespace remo

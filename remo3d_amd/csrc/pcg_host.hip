@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "pcg_host.h"
+#include "warm.h"
 
 namespace remo {
 
@@ -147,6 +148,31 @@ ChunkResult run_pcg(remo_ctx *ctx, const CsrView &A, int k, const double *d_f, P
                     remo_stats_t *st, size_t &ev_used) {
     return run_pcg_t<double>(ctx, A, k, d_f, buf, o.rtol * o.rtol, nullptr, o.maxsteps, o.check_every, o.time_kernels, st, ev_used, nullptr,
                              nullptr);
+}
+
+// Warm start: the shape of the mixed mode's outer cycle below, once, in fp64.  The stopping threshold is the one the cold solve
+// would have used, rtol^2 <C f, f> of THIS system and preconditioner: one PCG step on A d = f publishes <C f, f> as its step-0 record
+// (its x is discarded: the solve below starts from zero again).  Then q = A x_prev (launch_spmm as the mixed mode calls it: the
+// patch operator's shared rows are folded, not left in the slab), f' = f - q, and the unchanged PCG from zero on A d = f' with no
+// relative target (tol2 = 0) and that threshold as the absolute per-column floor (kFloorSlot: read by k_pcg_update and
+// k_pcg_direction alike, whatever the storage type; the host's iters / converged accounting takes max(tol2 r0, floor)).  A chunk
+// whose f' is below the floor freezes every column in the update launch of step 0: zero steps.
+ChunkResult run_pcg_warm(remo_ctx *ctx, const CsrView &A, int k, double *d_f, PcgBuffers &buf, double *x_prev, const remo_opts_t &o,
+                         remo_stats_t *st, size_t &ev_used) {
+    hipStream_t s = ctx->stream;
+    const double tol2 = o.rtol * o.rtol;
+    double rzf[REMO_MAX_RHS] = {0}, floor[REMO_MAX_RHS] = {0}, last[REMO_MAX_RHS] = {0};
+    ChunkResult probe = run_pcg_t<double>(ctx, A, k, d_f, buf, tol2, nullptr, 1, o.check_every, 0, st, ev_used, rzf, nullptr);
+    if (!probe.finite) return probe;
+    for (int c = 0; c < k; ++c) floor[c] = tol2 * rzf[c];
+    launch_spmm(A, k, (const double *)x_prev, buf.q, (double *)nullptr, (const double *)nullptr, buf.nb_spmv, s);
+    launch_warm_residual(A.n, k, d_f, buf.q, s);
+    ChunkResult out = run_pcg_t<double>(ctx, A, k, d_f, buf, 0.0, floor, o.maxsteps, o.check_every, o.time_kernels, st, ev_used, nullptr, last);
+    launch_warm_add(A.n, k, buf.x, x_prev, s);
+    for (int c = 0; c < k; ++c) out.relres[c] = rzf[c] > 0.0 ? std::sqrt(last[c] / rzf[c]) : 0.0;
+    out.steps += probe.steps;
+    HIP_TRY(hipStreamSynchronize(s));
+    return out;
 }
 
 // Mixed precision (BASELINE config 5): PCG runs in fp32 storage (matrix values, vectors,

@@ -9,6 +9,7 @@
 
 #include "remo_internal.h"
 #include "fem_p3.h"
+#include "warm.h"
 
 using namespace remo;
 
@@ -237,8 +238,16 @@ static int solve_batch_sens(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_
                             const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
                             const double *fun_z, const double *fun_w, double *J_out, double *dJ_out, const remo_opts_t *opts,
                             remo_stats_t *stats, bool tensor, bool groups = false, int32_t n_group = 0, const int32_t *group = nullptr,
-                            double *dJg_out = nullptr) {
+                            double *dJg_out = nullptr, remo_warm *warm = nullptr) {
     if (!ctx) return REMO_ERR_ARG;
+    // whatever goes wrong below, the object does not keep solutions of an earlier call (remo_batch_run labels it again on success)
+    struct WarmGuard {
+        remo_warm *w;
+        int rc = REMO_ERR_ARG;
+        ~WarmGuard() { if (w && rc < 0) remo_warm_clear(w); }
+    } guard{warm};
+    if (warm) warm->used_last = 0;
+    if (warm && warm->device != ctx->device) return fail(ctx, REMO_ERR_ARG, "the warm object belongs to another device than the context");
     const int ncomp = (tensor && mesh) ? ((mesh->dim == 2) ? 3 : 6) : 1;
     auto nan_fill = [&]() {
         if (u_out && eval_ptr && n_rhs > 0)
@@ -273,11 +282,13 @@ static int solve_batch_sens(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_
     if (rc != REMO_OK) return rc;
     const remo_sens_request rq{n_fun, fun_rhs, fun_ptr, fun_z, fun_w, J_out, dJ_out, groups ? n_group : 0, groups ? group : nullptr, groups ? dJg_out : nullptr};
     b->sens = &rq;
+    b->warm = warm;
     b->eval_only = true;
     rc = remo_batch_run(ctx, b, opts, stats);
     if (rc >= 0 && u_out) remo_batch_fetch(ctx, b, u_out);
     if (rc < 0) nan_fill();
     remo_batch_destroy(ctx, b);
+    guard.rc = rc;
     return rc;
 }
 
@@ -297,6 +308,24 @@ int remo_solve_batch_sens_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32
                                  remo_stats_t *stats) {
     return solve_batch_sens(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_fun, fun_rhs, fun_ptr, fun_z,
                             fun_w, J_out, dJ_out, opts, stats, true);
+}
+
+int remo_solve_batch_sens_warm(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
+                               const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                               const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
+                               const double *fun_z, const double *fun_w, double *J_out, double *dJ_out, remo_warm_t *warm,
+                               const remo_opts_t *opts, remo_stats_t *stats) {
+    return solve_batch_sens(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_fun, fun_rhs, fun_ptr, fun_z, fun_w,
+                            J_out, dJ_out, opts, stats, false, false, 0, nullptr, nullptr, warm);
+}
+
+int remo_solve_batch_sens_warm_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor, int32_t n_rhs,
+                                      const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                                      const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
+                                      const double *fun_z, const double *fun_w, double *J_out, double *dJ_out, remo_warm_t *warm,
+                                      const remo_opts_t *opts, remo_stats_t *stats) {
+    return solve_batch_sens(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_fun, fun_rhs, fun_ptr, fun_z,
+                            fun_w, J_out, dJ_out, opts, stats, true, false, 0, nullptr, nullptr, warm);
 }
 
 int remo_solve_batch_sens_groups(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,

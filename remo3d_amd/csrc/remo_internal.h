@@ -141,6 +141,8 @@ struct remo_sens_request {
     double *dJg_out = nullptr;
 };
 
+struct remo_warm;   // warm.h
+
 struct remo_batch {
     int dim = 0;
     int64_t nv = 0, nt = 0, nbf = 0;
@@ -156,6 +158,7 @@ struct remo_batch {
     uint8_t *d_bdir = nullptr;
     bool pooled = false;     // the six arrays live in the context's input pool (remo_solve_batch): not freed with the batch
     const remo_sens_request *sens = nullptr;   // remo_solve_batch_sens: adjoint solves + contraction after the forward solves (batch_run.hip)
+    remo_warm *warm = nullptr;                 // remo_solve_batch_sens_warm: where the solutions of the previous call are, and where these go (warm.h)
     bool eval_only = false;  // remo_solve_batch: nothing reads the solution after the run but the evaluation points (PcgBuffersT::x_ev)
     // last system (pointers into the context arena; valid until the next run on the context)
     bool has_system = false;

@@ -256,9 +256,12 @@ class _MeshAhead:
     parallel too: worker.py:84-97), on batches drawn ahead: the whole share at once when it is fixed anyway, a few (they are OWNED once
     drawn) under the pull schedule."""
 
-    def __init__(self, plan, windowing, bq, schedule, mesh_workers):
+    def __init__(self, plan, windowing, bq, schedule, mesh_workers, cache=None):
         self.plan, self.windowing, self.bq, self.schedule = plan, windowing, bq, schedule
         self.pool, self.pending, self.ahead = None, {}, collections.deque()
+        self.cache = cache      # inversion.SweepCache (simulate_logs(reuse=...)): the meshes of an earlier sweep of the same geometry
+        if cache is not None and cache.keep_meshes and cache.meshes and all(cache.has_mesh(bi) for bi in sweep.my_share(len(plan.batches))):
+            mesh_workers = 0    # nothing to mesh: no worker pool
         if mesh_workers is None:    # default: the reference's cpu_workers mesh (and solve) in parallel; here they mesh, for sweeps long
             mesh_workers = min(int(plan.model.cpu_workers or 0), 8) if (plan.default_provider and plan.share_len >= 16) else 0   # enough to pay for the start-up
         if mesh_workers > 0 and plan.default_provider and plan.share_len > 1:
@@ -301,7 +304,7 @@ class _MeshAhead:
                     bi = next(self.draw)
                 except StopIteration:
                     break
-                if self.pool is not None:
+                if self.pool is not None and not (self.cache is not None and self.cache.has_mesh(bi)):
                     try:
                         fg, bh, _ = self.windowing.window(bi)
                         self.pending[bi] = self.pool.submit(_mesh_worker_run, (p.dim, p.domain_radius, p.batches[bi].electrodes, fg, bh, p.model.dip_rad))
@@ -311,6 +314,15 @@ class _MeshAhead:
             return self.ahead.popleft() if self.ahead else None
 
     def mesh(self, bi, fg, bh):
+        if self.cache is not None:      # a hit is served without the worker pool; a miss is meshed as ever and kept
+            mesh = self.cache.mesh(bi)
+            if mesh is None:
+                mesh = self._make(bi, fg, bh)
+                self.cache.store_mesh(bi, mesh)
+            return mesh
+        return self._make(bi, fg, bh)
+
+    def _make(self, bi, fg, bh):
         p, mesh = self.plan, None
         if bi in self.pending:
             try:
@@ -424,8 +436,8 @@ class _Maps(_Output):
 class _BatchRunner:
     """Stages 5 and 6: one batch from its window to every output, and the host threads that do so batch after batch."""
 
-    def __init__(self, plan, windowing, meshes, outputs):
-        self.plan, self.windowing, self.meshes, self.outputs = plan, windowing, meshes, outputs
+    def __init__(self, plan, windowing, meshes, outputs, cache=None):
+        self.plan, self.windowing, self.meshes, self.outputs, self.cache = plan, windowing, meshes, outputs, cache
         self.free_ctx = queue.Queue()
         for c in plan.contexts:
             self.free_ctx.put(c)
@@ -452,7 +464,14 @@ class _BatchRunner:
                     job.outs, job.J, job.dJ, job.dJg, st, rc = c.solve_batch_sens_groups(job.mesh, job.sigma, sources, evals, job.functionals,
                                                                                          job.groups, len(job.group_mat), opts)
                 elif job.functionals is not None:
-                    job.outs, job.J, job.dJ, st, rc = c.solve_batch_sens(job.mesh, job.sigma, sources, evals, job.functionals, opts)
+                    warm = self.cache.warm_state(bi) if self.cache is not None else None      # the batch's solutions of the previous sweep
+                    if warm is not None:
+                        try:
+                            job.outs, job.J, job.dJ, st, rc = c.solve_batch_sens(job.mesh, job.sigma, sources, evals, job.functionals, opts, warm=warm)
+                        finally:
+                            self.cache.after_solve(bi, warm)
+                    else:
+                        job.outs, job.J, job.dJ, st, rc = c.solve_batch_sens(job.mesh, job.sigma, sources, evals, job.functionals, opts)
                 else:
                     job.outs, st, rc = c.solve_batch(job.mesh, job.sigma, sources, evals, opts)
             finally:
@@ -512,6 +531,7 @@ class Model:
         self.sensitivity_maps = None   # simulate_logs(sensitivity_grid=...): per tool d ln Ra / d ln R of every grid cell [n_depths, n_z, n_r]
         self.sensitivity_map_rest = None   # ... and of everything outside the grid [n_depths]
         self.sensitivity_grid = None   # the grid of the last maps
+        self.inversion = None          # invert_logs: what the last inversion found (inversion.invert_model)
         self.timing = {}
 
     # -- complete procedure (remo3d.py:65-174) ---------------------------------------------------
@@ -690,7 +710,7 @@ class Model:
                       condense=True, mesh_provider: Optional[Callable] = None, mesh_scale: Optional[float] = None, rtol: float = 1e-8,
                       maxsteps: int = 1000, verbose: bool = True, mesh_workers: Optional[int] = None, precision: str = "fp64",
                       schedule: str = "static", solver_options: Optional[dict] = None, sensitivities: bool = False,
-                      sensitivity_grid: Optional[dict] = None):
+                      sensitivity_grid: Optional[dict] = None, reuse=None):
         """solver_options: further keywords of solver.make_opts for every batch (op, coarse, quadrature, assemble, ...).
         sensitivities: also fill self.sensitivities[tool] = dRa/dR in ohm m per ohm m, [n_depths, n_layers, n_cols] with the
         columns of the formation table from column 2 on (RDFZ - a radius, always NaN -, RTFZ, RTUZ, and RVUZ when present; 0 where
@@ -701,7 +721,10 @@ class Model:
         geometry.sensitivity_cells): also fill self.sensitivity_maps[tool] [n_depths, n_z, n_r] with the dimensionless
         d ln Ra / d ln R of every cell - every resistivity inside the cell (mud, flushed zones, Rh and Rv alike) scaled by a common
         factor - and self.sensitivity_map_rest[tool] [n_depths] with the same for everything outside the grid (the two sum to 1);
-        NaN where the batch failed.  Implies the adjoint solves (remo_solve_batch_sens_groups); may be combined with sensitivities."""
+        NaN where the batch failed.  Implies the adjoint solves (remo_solve_batch_sens_groups); may be combined with sensitivities.
+        reuse: an inversion.SweepCache shared by sweeps of one geometry (the iterations of invert_logs): the batch meshes come from it
+        after the first sweep, and with sensitivities=True every batch's solves start from its solutions of the previous sweep
+        (solver.WarmState); self.timing then also reports mesh_hits and warm_hits.  None (default): nothing is kept."""
         start = time.time()
         plan = _Plan(self, measurement_depths, domain_radius, batch_size, mesh_generator, mesh_provider, mesh_scale,
                      dict(preconditioner=preconditioner, condense=condense, rtol=rtol, maxsteps=maxsteps, precision=precision),
@@ -713,8 +736,11 @@ class Model:
         if sensitivity_grid is not None:
             outputs.append(_Maps(plan, sensitivity_grid))
         bq = sweep.BatchQueue(len(plan.batches), schedule)
-        meshes = _MeshAhead(plan, windowing, bq, schedule, mesh_workers)
-        runner = _BatchRunner(plan, windowing, meshes, outputs)
+        if reuse is not None:
+            from . import inversion
+            reuse.begin(inversion.sweep_signature(plan))
+        meshes = _MeshAhead(plan, windowing, bq, schedule, mesh_workers, reuse)
+        runner = _BatchRunner(plan, windowing, meshes, outputs, reuse)
         t_busy = time.time()
         try:
             runner.drive()
@@ -733,6 +759,8 @@ class Model:
                            my_batches=len(bq.taken), world_size=sweep.world_size(), schedule=schedule, busy_s=t_busy,
                            busy_s_per_rank=[b[0] for b in sweep.gather_floats([t_busy])], failed_batches=acc["failed_batches"],
                            not_converged=acc["not_converged"], first_error=acc["first_error"], pcg_steps=acc["pcg_steps"])
+        if reuse is not None:
+            self.timing.update(mesh_hits=reuse.mesh_hits, warm_hits=reuse.warm_hits)
         if acc["programming_error"] is not None:     # every rank is through the collectives: now it may raise
             raise acc["programming_error"]
         if verbose and acc["failed_batches"]:
@@ -741,6 +769,29 @@ class Model:
             print("rank {}: PCG stopped at maxsteps in {} batches".format(sweep.rank(), acc["not_converged"]))
         if verbose and sweep.rank() == 0:
             print("\nProcessed in: ", datetime.timedelta(seconds=self.timing["total_s"]))
+
+    # -- inversion (no counterpart in the reference) -----------------------------------------------
+    def invert_logs(self, observed, measurement_depths, free="RTUZ", **kw):
+        """Fit the resistivities of the formation table to observed apparent resistivities.  observed: dict tool -> [n_depths] in
+        ohm m on the grid of measurement_depths (or the [n_depths, 2] arrays of self.logs); NaN = no datum.  Unknowns: ln R of the
+        free table entries - free = "RTUZ" (default: every finite RTUZ), "RTUZ+RTFZ", "all", or a boolean mask [n_layers, n_cols]
+        over RTFZ, RTUZ, RVUZ; radii and boundaries are never free, a free NaN entry is an error.  Residuals ln Ra_sim - ln Ra_obs
+        weighted by 1 / data_std (relative standard deviation, a scalar or a dict per tool, default 0.05); records where either value
+        is NaN or not positive are left out of that evaluation and counted.  Levenberg-Marquardt (inversion.lm_loop) with
+        J^T W J + mu diag(J^T W J) + beta L^T L (L: first differences of ln R between vertically adjacent free entries of a column;
+        beta default 0) and an optional pull beta_ref toward a `reference` table; steps clipped to bounds = (0.01, 1e5) ohm m and to
+        max_step = ln 3.  Every evaluation is one simulate_logs(sensitivities=True) sweep at the trial table.  Stops: max_iterations
+        (15), ftol, xtol, target_rms.  Further keywords: mu, reuse_meshes (default True: the meshes of the first sweep serve all),
+        warm_start (default False; True: every batch's solves start from its solutions of the previous sweep - about half the PCG steps
+        over an inversion, but on the short 3D span measured the solve time of sweeps two onward did not beat cached meshes alone:
+        DESIGN.md section 3.4), warm_bytes, and solver_kw: a dict of
+        simulate_logs keywords (domain_radius, batch_size, rtol, mesh_scale, solver_options, ...).
+        On return the formation table holds the result, self.logs / self.sensitivities are those of the accepted table and
+        self.inversion (also returned) holds start_table, final_table, free, jacobian, singular_values, parameter_std (ln units; NaN
+        for an entry no datum sees, listed in `unseen`), resolution, history (one record per sweep: objective, rms, mu, accepted,
+        excluded, seconds, pcg_steps, warm_hits, mesh_hits, ...) and stop."""
+        from . import inversion
+        return inversion.invert_model(self, observed, measurement_depths, free=free, **kw)
 
     # -- results (remo3d.py:902-1147): Results_<n>.txt per group of logs on one depth grid + Results_plot.png ------------------
     def save_results(self, output_folder=None, measurements_to_save="auto", plot_layout="auto", plot_depth_lim="auto", plot_aspect_ratio="auto",

@@ -170,3 +170,49 @@ def plot_sensitivity_map(model, tool, depth_index, path=None):
     if path is not None:
         fig.savefig(path, dpi=120)
     return fig
+
+
+def plot_inversion(model, path=None, true_table=None):
+    """One picture of model.inversion (Model.invert_logs): the resistivity columns of the start, final and - if given - true
+    formation table against depth (one panel per column with a free entry), and beside them the observed and the fitted logs per
+    tool.  Returns the figure; `path`: also written there."""
+    import matplotlib
+    if not os.environ.get("MPLBACKEND") and not os.environ.get("DISPLAY"):
+        matplotlib.use("Agg", force=False)
+    import matplotlib.pyplot as plt
+    inv = model.inversion
+    names = ["RTFZ", "RTUZ", "RVUZ"]
+    cols = [c for c in range(inv.free.shape[1]) if inv.free[:, c].any()]
+    fig, axes = plt.subplots(1, len(cols) + len(inv.tools), figsize=(3.2 * (len(cols) + len(inv.tools)), 7), sharey=True, squeeze=False)
+    axes = axes[0]
+
+    def stairs(ax, table, c, **kw):
+        t = np.asarray(table, dtype=float)
+        z = np.column_stack([t[:, 0], t[:, 1]]).ravel()
+        ax.plot(np.repeat(t[:, 3 + c], 2), z, **kw)
+    for ax, c in zip(axes, cols):
+        stairs(ax, inv.start_table, c, color="0.6", lw=1.0, label="start")
+        if true_table is not None:
+            stairs(ax, true_table, c, color="k", lw=2.2, alpha=0.5, label="true")
+        stairs(ax, inv.final_table, c, color="C3", lw=1.2, label="final")
+        ax.set_xscale("log")
+        ax.set_xlabel("{} [ohmm]".format(names[c]))
+        ax.grid(True, which="both", lw=0.3)
+        ax.legend(loc="lower right", fontsize=8)
+    for ax, tool in zip(axes[len(cols):], inv.tools):
+        obs = np.asarray(inv.observed[tool], dtype=float)
+        obs = obs[:, 1] if obs.ndim == 2 else obs
+        ax.plot(obs, inv.depths, "k.", ms=4, label="observed")
+        ax.plot(model.logs[tool][:, 1], model.logs[tool][:, 0], color="C3", lw=1.0, label="fitted")
+        ax.set_xscale("log")
+        ax.set_xlabel("{} [ohmm]".format(tool))
+        ax.grid(True, which="both", lw=0.3)
+        ax.legend(loc="lower right", fontsize=8)
+    lo, hi = float(np.min(inv.depths)), float(np.max(inv.depths))
+    pad = 0.1 * max(hi - lo, 1.0)
+    axes[0].set_ylim(hi + pad, lo - pad)
+    axes[0].set_ylabel("depth [m]")
+    fig.suptitle("inversion: rms {:.3g} after {} sweeps ({})".format(inv.rms, len(inv.history), inv.stop))
+    if path is not None:
+        fig.savefig(path, dpi=120)
+    return fig

@@ -128,6 +128,47 @@ def _symmetric_gradient(dJ, d, tensor):
     return G
 
 
+class WarmState:
+    """Solutions that survive a call (remo_warm_t): hand it to Context.solve_batch_sens(..., warm=state) on one mesh again and again -
+    the iterations of an inversion - and every call after the first solves for a correction of the previous call's forward and
+    adjoint solutions.  One device allocation, grow-only; any context of the device may use it, one call at a time."""
+
+    def __init__(self, device_id: int = 0):
+        self._L = _lib.load()
+        self._h = self._L.remo_warm_create(int(device_id))
+        if not self._h:
+            raise RemoError(-2, (self._L.remo_last_error(None) or b"").decode())
+        self.device_id = device_id
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.remo_warm_destroy(self._h)
+            self._h = None
+
+    def clear(self):
+        """Forget the stored solutions (the next call runs cold); the allocation stays."""
+        self._L.remo_warm_clear(self._h)
+
+    def info(self) -> dict:
+        """n_free, n_cols: rows and columns (forward + adjoint) stored, 0 when empty; bytes: device memory held; used_last: 1 when the
+        last call that was handed this state started from its solutions."""
+        n_free, n_cols, nbytes, used = C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int32(0)
+        self._L.remo_warm_info(self._h, C.byref(n_free), C.byref(n_cols), C.byref(nbytes), C.byref(used))
+        return dict(n_free=n_free.value, n_cols=n_cols.value, bytes=nbytes.value, used_last=used.value)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """One per GPU (remo_ctx_create)."""
 
@@ -158,8 +199,8 @@ class Context:
     def last_error(self) -> str:
         return (self._L.remo_last_error(self._h) or b"").decode()
 
-    def _one_shot(self, kind, mesh, sigma, sources, evals, opts, raise_on_error, functionals=None, groups=None, n_group=None):
-        """The one marshalling path of the one-shot entries remo_solve_batch<kind>[_tensor], kind "", "_sens" or "_sens_groups":
+    def _one_shot(self, kind, mesh, sigma, sources, evals, opts, raise_on_error, functionals=None, groups=None, n_group=None, warm=None):
+        """The one marshalling path of the one-shot entries remo_solve_batch<kind>[_tensor], kind "", "_sens", "_sens_warm" or "_sens_groups":
         the common arguments, then the functionals and the groups with their outputs where the kind has them.  Returns
         (potentials, [J, dJ, [dJg],] stats, rc)."""
         args, sigma, tensor, eval_ptr, keep = _batch_args(self._h, mesh, sigma, sources, evals)
@@ -180,6 +221,8 @@ class Context:
                 args += [n_group, ptr(groups, C.c_int32)]
                 grads.append(np.full((n_fun, max(n_group, 0), nc), np.nan))
             args += [ptr(a, C.c_double) for a in J + grads]
+            if kind == "_sens_warm":
+                args.append(warm._h)
         st = RemoStats()
         o = opts if opts is not None else make_opts()
         rc = getattr(self._L, "remo_solve_batch" + kind + ("_tensor" if tensor else ""))(*args, C.byref(o), C.byref(st))
@@ -194,12 +237,17 @@ class Context:
         (remo_solve_batch_tensor)."""
         return self._one_shot("", mesh, sigma, sources, evals, opts, raise_on_error)
 
-    def solve_batch_sens(self, mesh, sigma, sources, evals, functionals, opts: Optional[RemoOpts] = None, raise_on_error=True):
+    def solve_batch_sens(self, mesh, sigma, sources, evals, functionals, opts: Optional[RemoOpts] = None, raise_on_error=True,
+                         warm: Optional[WarmState] = None):
         """One-shot remo_solve_batch_sens: the batch of solve_batch plus linear functionals of the potentials and their derivatives
         with respect to the materials' conductivities (adjoint solves).  functionals: list of (rhs, z array, w array),
         J = sum_i w[i] * u_rhs(z[i]).  Returns (potentials, J [n_fun], dJ, stats, rc) with dJ [n_fun, n_mat] for sigma [n_mat] and
         [n_fun, n_mat, dim, dim] for tensors: symmetric G with dJ = G : dSigma for symmetric dSigma (the library's triangle holds
-        both halves of an off-diagonal pair; each half gets half of it here)."""
+        both halves of an off-diagonal pair; each half gets half of it here).
+        warm: a WarmState of this device (remo_solve_batch_sens_warm): the solves start from the solutions it holds when they belong
+        to a batch of the same sizes, and it holds this call's afterwards; stats["pcg_steps"] then counts one measuring step per chunk."""
+        if warm is not None:
+            return self._one_shot("_sens_warm", mesh, sigma, sources, evals, opts, raise_on_error, functionals, warm=warm)
         return self._one_shot("_sens", mesh, sigma, sources, evals, opts, raise_on_error, functionals)
 
     def solve_batch_sens_groups(self, mesh, sigma, sources, evals, functionals, groups, n_group=None, opts: Optional[RemoOpts] = None,
