@@ -61,7 +61,7 @@ int remo_debug_sens_group_timing(remo_ctx_t *ctx, double *out4);
  * a small test mesh reaches the code a large batch runs.  Every setting gives the same operator / preconditioner to rounding:
  *    3  row schedule of the CSR product (0 grid-stride, 1 XCD windows, 16 * nc XCD regions of nc chunks; -1 = by size);
  *    6  0 = one launch per Chebyshev step, 1 = paired steps on the squared vertex block in 2D (default), 2 = also in 3D;
- *    9  0 = first Chebyshev step as a launch of its own instead of inside the update launch;
+ *    9  0 = first Chebyshev step as a launch of its own instead of inside the update launch (k_pcg_update_folded);
  *   13  0 = Chebyshev launches read the vertex block inside A, 1 = from a compact copy above 16 k vertices (default), 2 = always;
  *   15  0 = the Chebyshev chain of an fp64 solve stays in fp64 also above 32 k vertex rows (default there: fp32 storage), 2 = fp32 always;
  *   16  1 = never the multigrid cycle on the vertex block, 2 = always, any dimension (0: remo_opts_t.coarse decides);
@@ -70,9 +70,12 @@ int remo_debug_sens_group_timing(remo_ctx_t *ctx, double *out4);
  *   22  0 = rows shared by patches summed by k_patch_reduce instead of the PCG's update launch;
  *   24  0 = Chebyshev launches walk the vertex block as CSR instead of its fixed-width image;
  *   25  0 = x += alpha p formed by the update launch instead of the direction launch of the step (bit-identical x);
- *   29  0 = the update launch fetches four slab slots for every row and weights the ones the row does not have by zero;
- *   30  0 = the direction launch takes a k-wide row per lane instead of walking its vectors as flat arrays, 16 bytes per lane;
- *   31  0 = the update launch takes a k-wide row per lane instead of 64 rows per wave with a value per lane and pass (fp64 storage);
+ *   29  0 = the update launch fetches four slab slots for every row and weights the ones the row does not have by zero
+ *          (k_pcg_update without MASKED; also keeps the tile form away);
+ *   30  0 = the direction launch takes a k-wide row per lane (k_pcg_direction_row) instead of walking its vectors as flat arrays,
+ *          16 bytes per lane (k_pcg_direction_flat);
+ *   31  0 = the update launch takes a k-wide row per lane (k_pcg_update) instead of 64 rows per wave with a value per lane and
+ *          pass (k_pcg_update_tile, fp64 storage);
  *   39  0 = one-shot fp64 solves (remo_solve_batch[_tensor]) carry the whole solution block instead of only the values the
  *       evaluation points read (default 1; bit-identical potentials on the CSR product).  Resident batches always keep the whole x.
  *

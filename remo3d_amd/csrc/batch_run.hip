@@ -374,7 +374,7 @@ void vertex_block_enqueue(const Run &r, const Plan &plan, const System &sys, con
         launch_vblock_bound(buf.nv_coarse, A, sys.d_dinv, sv.d_bound, s);
         HIP_TRY(hipMemcpyAsync(&vb.h_bound, sv.d_bound, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     }
-    if (vb.want_square) {   // B = A_vv D^-1 A_vv for the paired Chebyshev steps (kernels.hip)
+    if (vb.want_square) {   // B = A_vv D^-1 A_vv for the paired Chebyshev steps (pcg_kernels.hip k_cheb_pair)
         const int64_t nvc = buf.nv_coarse, cap = nvc * 200;
         vb.sq_rowptr = ctx->take<int32_t>(size_t(nvc) + 2);
         vb.sq_col = ctx->take<int32_t>(size_t(cap));

@@ -1,4 +1,4 @@
-// kernels.h — launchers of the gfx950 kernels (kernels.hip).  All launches are asynchronous on
+// kernels.h — launchers of the gfx950 kernels (kernels.hip; the PCG step's: pcg_kernels.hip).  All launches are asynchronous on
 // the given stream; no launcher allocates or synchronises.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -77,7 +77,7 @@ template <class T> struct PcgBuffersT {
 using PcgBuffers = PcgBuffersT<double>;
 constexpr int kPqBins = 256;       // rows of a set of <p, A p> bins (PcgBuffersT::pq_bins); set s starts at part_pq + s * kPqBins * 8
 constexpr int kScalarSlots = 48;   // doubles behind PcgBuffersT::rz0
-constexpr int kDoneSlot = 4 * 8;   // rz0[kDoneSlot] (as int): step + 1 of the update launch that froze every column (kernels.hip solve_done)
+constexpr int kDoneSlot = 4 * 8;   // rz0[kDoneSlot] (as int): step + 1 of the update launch that froze every column (kutil.h solve_done)
 
 // Patch operator (3D, remo_opts_t.op = 3; patch.hip): the element list cut into runs of E elements, one workgroup each
 struct PatchTables {
@@ -152,7 +152,7 @@ void launch_assemble(int dim, bool condense, int64_t nfree, int64_t pair_begin, 
 
 int spmv_grid(int64_t n, int lanes_per_row);
 int vec_grid(int64_t n);
-void set_fold_first(int v);                 // 1 (default): FIRST Chebyshev step inside the update launch
+void set_fold_first(int v);                 // 1 (default): FIRST Chebyshev step inside the update launch (k_pcg_update_folded)
 void set_spmm_tuning(int key, int value);  // 0 variant, 1 lanes per row, 2 threads, 3 mapping, 4 grid (0 = default)
 int choose_lanes_per_row(int64_t n, int64_t nnz);
 // y = A x for k interleaved columns; if part != nullptr also leaves per-block partial sums of <x_c, y_c>
@@ -169,9 +169,9 @@ void set_patch_all_slab(int on);   // remo_debug_tune key 37 (probe builds): 0 =
 void set_patch_persist(int on);   // remo_debug_tune key 34 (patch.hip k_patch_apply_p)
 void set_patch_wgs_per_xcd(int n);   // key 35
 void set_patch_block(int threads);   // 256 (default) or 512
-void set_slab_masked(int v);         // key 29
-void set_flat_direction(int v);      // key 30
-void set_tile_update(int v);         // key 31
+void set_slab_masked(int v);         // key 29: k_pcg_update<.., MASKED = true> (1) / <.., false> (0)
+void set_flat_direction(int v);      // key 30: k_pcg_direction_flat (1) / k_pcg_direction_row (0)
+void set_tile_update(int v);         // key 31: k_pcg_update_tile (1) / k_pcg_update (0)
 void set_slab_ahead(int v);          // 0: slab slots of a shared row one by one in the update launch (default 1: four in flight)
 void set_patch_trim(int v);
 void set_patch_spread(int v);

@@ -1,12 +1,12 @@
-// kernels.hip — hand-written gfx950 (CDNA4, wave64) kernels of the ReMo3D hot path:
-//   metric terms -> CSR value gather-assembly -> multi-RHS PCG (edge-pair SpMM, fused vector kernels,
-//   two-level preconditioner: Chebyshev on the P1 vertex block + Jacobi; fp64 or fp32 storage with fp64
-//   residual replacement) -> axis point location / RHS build / evaluation.
+// kernels.hip — hand-written gfx950 (CDNA4, wave64) kernels of the ReMo3D hot path around the PCG step:
+//   metric terms -> CSR value gather-assembly -> the CSR product q = A p (edge-pair SpMM) -> set-up of the preconditioner's
+//   P1 vertex block (bound, square, compact copy, fixed-width image) -> conversions of the mixed-precision mode ->
+//   axis point location / RHS build / evaluation.
+// The vector kernels of the PCG step and the Chebyshev steps are pcg_kernels.hip, the patch operator patch.hip.
 // All of it is HBM/L2-bound sparse work: no MFMA (a sparse row is not a dense contraction); the levers are
-// coalesced CSR streams, DPP (not LDS) cross-lane reductions, XCD-aware row placement, LDS-staged reference
-// tensors and few launches per PCG step.  Reference lines each kernel replaces are cited at the kernel.
+// coalesced CSR streams, DPP (not LDS) cross-lane reductions, XCD-aware row placement and LDS-staged reference
+// tensors.  Reference lines each kernel replaces are cited at the kernel.
 #include "kernels.h"
-#include "amg.h"
 
 #include <limits.h>
 
@@ -15,16 +15,6 @@
 #include "kutil.h"
 
 namespace remo {
-
-// Progress records live in mapped, coherent host memory: the stores bypass the caches (sc0 sc1).  A system-scope RELEASE
-// store would also write back the whole L2 of the XCD (buffer_wbl2) on every PCG step; the record only needs its data to
-// land before its step number, so the data stores are relaxed, the wave waits for their acknowledgement, then stores the
-// step number.
-__device__ __forceinline__ void publish_progress(PcgProgress *pr, const double *rz, int k, int step) {
-    for (int c = 0; c < k; ++c) __hip_atomic_store(&pr->rz[c], rz[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_store(&pr->step, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // Storage position of stored entry e of `row` (rows of an edge pair keep their values INTERLEAVED: the two rows have the
 // same column pattern and the SpMM reads both values of an entry with one 16-byte load; every other row is plain CSR).
@@ -556,32 +546,30 @@ struct SpmmTuning {
     int mapping = -1;
     int grid = 0;
 };
-static SpmmTuning g_tune;
-static int g_fold_first = 1;   // remo_debug_tune key 9: FIRST Chebyshev step inside the update launch (0 = own launch)
-void set_fold_first(int v) { g_fold_first = v; }
+static SpmmTuning g_spmm_tune;
 void set_spmm_tuning(int key, int value) {
     switch (key) {
-        case 0: g_tune.variant = value; break;
-        case 1: g_tune.lpr = value; break;
-        case 2: g_tune.threads = value; break;
-        case 3: g_tune.mapping = value; break;
-        case 4: g_tune.grid = value; break;
-        case 5: g_tune.mode = value; break;
+        case 0: g_spmm_tune.variant = value; break;
+        case 1: g_spmm_tune.lpr = value; break;
+        case 2: g_spmm_tune.threads = value; break;
+        case 3: g_spmm_tune.mapping = value; break;
+        case 4: g_spmm_tune.grid = value; break;
+        case 5: g_spmm_tune.mode = value; break;
         default: break;
     }
 }
 
 int choose_lanes_per_row(int64_t n, int64_t nnz) {
-    if (g_tune.lpr) return g_tune.lpr;
+    if (g_spmm_tune.lpr) return g_spmm_tune.lpr;
     const double avg = double(nnz) / double(n > 0 ? n : 1);
     if (avg > 40) return 16;
     if (avg > 20) return 8;
     return 4;
 }
-static int spmm_threads() { return g_tune.threads ? g_tune.threads : 256; }
+static int spmm_threads() { return g_spmm_tune.threads ? g_spmm_tune.threads : 256; }
 
 int spmv_grid(int64_t n, int lpr) {
-    if (g_tune.grid) return g_tune.grid;
+    if (g_spmm_tune.grid) return g_spmm_tune.grid;
     const int64_t rpb = spmm_threads() / lpr;
     int64_t g = (n + rpb - 1) / rpb;
     g = (g + 7) / 8 * 8;  // whole residue classes mod 8 (one per XCD)
@@ -597,7 +585,7 @@ int spmv_grid(int64_t n, int lpr) {
 template <class T, int K> static void spmm_dispatch(const CsrViewT<T> &A, const T *x, T *y, double *part, const double *scal, int step, int nb, hipStream_t s) {
     int lpr = choose_lanes_per_row(A.n, A.nnz);
     const int threads = spmm_threads();
-    int variant = g_tune.variant ? g_tune.variant : 3;
+    int variant = g_spmm_tune.variant ? g_spmm_tune.variant : 3;
     if (variant == 3 && !(A.pair_end > A.pair_begin)) variant = 1;
     // default row schedule of the pair kernel: XCD windows (measured 69 -> 60 us at 334k rows, k = 5); once the matrix no
     // longer stays in the 256 MB of MALL between launches (3D, more than ~20 M stored entries), XCD regions (4 chunks
@@ -607,7 +595,7 @@ template <class T, int K> static void spmm_dispatch(const CsrViewT<T> &A, const 
     // chunks per XCD: about 0.4 MB of x per chunk, 4 ... 64 (bench at 5.4 M rows: 4 chunks 1257 us, 16: 1227, 64: 1216)
     int64_t nc = (A.n * int64_t(K) * int64_t(sizeof(T)) / 8 + 210000) / 420000;
     nc = nc < 4 ? 4 : (nc > 64 ? 64 : nc);
-    const int mapping = (g_tune.mapping >= 0) ? g_tune.mapping : ((lpr == 16 && A.nnz > 20000000) ? int(16 * nc) : 1);
+    const int mapping = (g_spmm_tune.mapping >= 0) ? g_spmm_tune.mapping : ((lpr == 16 && A.nnz > 20000000) ? int(16 * nc) : 1);
 #define REMO_SPMM(L)                                                                                                        \
     if (part)                                                                                                               \
         hipLaunchKernelGGL((k_spmm<T, K, L, true>), dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, A.rowptr, A.col, A.val, x, y, part, scal, step); \
@@ -619,10 +607,10 @@ template <class T, int K> static void spmm_dispatch(const CsrViewT<T> &A, const 
     else                                                                                                                                \
         hipLaunchKernelGGL((k_spmm_pair<T, K, L, false>), dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, mapping, A.rowptr, A.col, A.val, x, y, part, scal, step)
     if constexpr (K == 5 && sizeof(T) == 8) {   // ablation modes of tools/probe_ablate.py
-        if (variant == 3 && lpr == 16 && g_tune.mode >= 1 && g_tune.mode <= 3 && !part) {
-            if (g_tune.mode == 1) hipLaunchKernelGGL((k_spmm_pair<T, 5, 16, false, 1>), dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, mapping, A.rowptr, A.col, A.val, x, y, part, scal, step);
-            if (g_tune.mode == 2) hipLaunchKernelGGL((k_spmm_pair<T, 5, 16, false, 2>), dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, mapping, A.rowptr, A.col, A.val, x, y, part, scal, step);
-            if (g_tune.mode == 3) hipLaunchKernelGGL((k_spmm_pair<T, 5, 16, false, 3>), dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, mapping, A.rowptr, A.col, A.val, x, y, part, scal, step);
+        if (variant == 3 && lpr == 16 && g_spmm_tune.mode >= 1 && g_spmm_tune.mode <= 3 && !part) {
+            if (g_spmm_tune.mode == 1) hipLaunchKernelGGL((k_spmm_pair<T, 5, 16, false, 1>), dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, mapping, A.rowptr, A.col, A.val, x, y, part, scal, step);
+            if (g_spmm_tune.mode == 2) hipLaunchKernelGGL((k_spmm_pair<T, 5, 16, false, 2>), dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, mapping, A.rowptr, A.col, A.val, x, y, part, scal, step);
+            if (g_spmm_tune.mode == 3) hipLaunchKernelGGL((k_spmm_pair<T, 5, 16, false, 3>), dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, mapping, A.rowptr, A.col, A.val, x, y, part, scal, step);
             return;
         }
     }
@@ -669,660 +657,7 @@ template void launch_spmm<double>(const CsrViewT<double> &, int, const double *,
 template void launch_spmm<float>(const CsrViewT<float> &, int, const float *, float *, double *, const double *, int, hipStream_t, int, bool);
 
 // ------------------------------------------------------------------------------------------
-// Jacobi-PCG vector kernels (CGSolver(a.mat, c.mat), ngsolve_functions.py:50-51), K columns at
-// once with per-column step lengths.  Three launches per step:
-//   spmm      q = A p, partials of <p,q>
-//   update    alpha = <Cr,r>/<p,q>;  x += alpha p;  r -= alpha q;  partials of <C r, r>
-//   direction beta = <Cr,r>_new/<Cr,r>_old;  p = C r + beta p
-// Scalars never visit the host: every block re-reduces the (<= 1024 x K) per-block partials of
-// the previous launch in a fixed order, so results are bit-reproducible and there is no atomic.
-// A column whose <Cr,r> has dropped below tol^2 <Cr0,r0> (or that broke down) is frozen
-// (alpha = beta = 0), which makes post-convergence steps harmless.
-
-// Two-level preconditioner ("multigrid" of the reference, ngsolve_functions.py:46: a lowest-order
-// coarse space plus a smoother on the high-order dofs).  In the hierarchical basis the vertex
-// functions ARE the P1 space and vertex dofs are numbered first, so the coarse problem is the leading
-// nv x nv block of the assembled matrix, read in place (columns are sorted: the block's entries
-// lead every row).  C = blockdiag( q_d(A_vv), D_hh^-1 ): a fixed Chebyshev polynomial of degree d in
-// the Jacobi-scaled vertex block (spectrum bounds [lmax/ratio, lmax], lmax = Gershgorin bound, so
-// q_d is positive definite on the whole spectrum and plain PCG stays valid) and Jacobi on edge/face
-// dofs.  nv = 0 gives plain Jacobi ("local").
-template <class T> struct ChebArgsT {
-    int64_t nv;       // free vertex dofs (0: Jacobi)
-    double inv_theta; // 1 / theta, theta = (lmax + lmin) / 2
-    T *z, *res;       // [nv][K] polynomial value so far / residual of the vertex block system
-    T *d0;            // [nv][K] first Chebyshev direction
-};
-// FIRST Chebyshev step folded into the update launch (k_pcg_update): nb_flat = 0 switches it off
-// q = A p of the patch operator with the rows shared by several patches still in the boundary slab (PcgBuffersT::defer_q)
-template <class T> struct QViewT {
-    const int32_t *bptr = nullptr, *bslot = nullptr;
-    const T *Yb = nullptr;
-    int ahead = 1;      // 0: the slots of a shared row one by one (remo_debug_tune key 27)
-    int skip_x = 0;     // 1: x += alpha p is left to the direction launch of the step (PcgBuffersT::x_in_direction)
-    int tile = 0;              // 1: the tile form of the update launch (k_pcg_update; remo_debug_tune key 31)
-    const int32_t *row4 = nullptr;   // PatchTables::row4 (tile form)
-    uint64_t slab_bytes = 0;   // != 0 (slab below 4 GB): the slots a row does not have are not fetched at all (buffer loads, offset out of range)
-};
-// x_ev[j] += alpha p[at[j]] (PcgBuffersT::x_ev): the values of x the evaluation points read, formed by the update launch
-template <class T> struct EvSlotsT {
-    const int64_t *at = nullptr;
-    T *x = nullptr;
-    int n = 0;
-};
-template <class T> struct FoldArgsT {
-    int nb_flat = 0;             // workgroups [0, nb_flat) do the flat update of the rows >= nv, the rest the vertex rows
-    const int32_t *rowptr = nullptr, *col = nullptr;
-    const T *val = nullptr;
-    T *d_new = nullptr, *stage = nullptr;
-    double c1 = 0.0, c2 = 0.0;
-};
-// All PCG kernels are templates on the storage type T of matrix values and vectors: double = the
-// product path, float = the inner solver of the mixed-precision mode (BASELINE config 5).  Scalars,
-// partial sums and the convergence test are double in both.
-// scal[kFloorSlot + c]: absolute floor of <Cr,r> below which column c is frozen as well (0 in the plain
-// fp64 solve; the outer target of the refinement in the mixed mode)
-constexpr int kFloorSlot = 5 * 8;
-
-template <class T, int K>
-__global__ void __launch_bounds__(256) k_pcg_init(int64_t n, ChebArgsT<T> ch, const T *__restrict__ f, const T *__restrict__ dinv,
-                                                  T *__restrict__ x, T *__restrict__ r, T *__restrict__ p,
-                                                  double *__restrict__ part_rz) {
-    __shared__ double smem[16 * K];
-    double rz[K];
-#pragma unroll
-    for (int c = 0; c < K; ++c) rz[c] = 0.0;
-    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) {
-        const T d = dinv[i];
-        const bool coarse = i < ch.nv;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            const T ri = f[i * K + c];
-            const T zi = d * ri;
-            if (x) x[i * K + c] = T(0);   // (evaluated values only: x_ev is cleared by the host)
-            r[i * K + c] = ri;
-            p[i * K + c] = coarse ? T(0) : zi;
-            rz[c] += coarse ? 0.0 : double(ri) * double(zi);   // the vertex block's share comes from the Chebyshev kernels
-        }
-    }
-    block_sum<K>(rz, smem);
-    if (threadIdx.x < K) part_rz[blockIdx.x * K + threadIdx.x] = rz[threadIdx.x];
-}
-
-template <class T, int K>
-__global__ void __launch_bounds__(256) k_pcg_update(int64_t n, int step, double tol2, int x_only, int nb_spmv, int nb_rz, ChebArgsT<T> ch,
-                                                    const double *__restrict__ part_pq, const double *__restrict__ part_rz_cur,
-                                                    double *__restrict__ part_rz_next, double *__restrict__ rz0,
-                                                    PcgProgress *progress, int progress_len, const T *__restrict__ p,
-                                                    const T *__restrict__ q, T *__restrict__ x, T *__restrict__ r,
-                                                    const T *__restrict__ dinv, FoldArgsT<T> fold, QViewT<T> qv, double *__restrict__ clear_bins = nullptr,
-                                                    EvSlotsT<T> ev = EvSlotsT<T>()) {
-    // scal = rz0[8] | pq[8] | rz of even steps[8] | rz of odd steps[8]: totals forwarded between launches
-    // by workgroup 0, so every launch re-reduces only the ONE partial array that is new to it
-    __shared__ double smem[16 * 3 * K];
-    double *scal = rz0;
-    if (solve_done(scal, step)) return;
-    double pq[K], rz[K], unused[K], alpha[K], acc[K];
-    if (step == 0) {
-        reduce_partials3<K>(part_pq, nb_spmv, part_rz_cur, nb_rz, nullptr, 0, pq, rz, unused, smem);
-    } else {
-        reduce_partials<K>(part_pq, nb_spmv, pq, smem);
-#pragma unroll
-        for (int c = 0; c < K; ++c) rz[c] = scal[16 + 8 * (step & 1) + c];
-    }
-#pragma unroll
-    for (int c = 0; c < K; ++c) {
-        const double r0 = (step == 0) ? rz[c] : rz0[c];
-        const bool live = (rz[c] > tol2 * r0) && (rz[c] > scal[kFloorSlot + c]) && (pq[c] > 0.0);
-        alpha[c] = live ? rz[c] / pq[c] : 0.0;
-        acc[c] = 0.0;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        bool any_live = false;
-#pragma unroll
-        for (int c = 0; c < K; ++c) any_live |= (alpha[c] != 0.0);
-        if (!any_live) {   // every column frozen: later launches of this solve are no-ops; tell the host where it ended
-            reinterpret_cast<int *>(scal + kDoneSlot)[0] = step + 1;   // acts on the launches of steps > step only (solve_done)
-            publish_progress(progress + (progress_len - 1), rz, K, step);
-        }
-#pragma unroll
-        for (int c = 0; c < K; ++c) scal[8 + c] = pq[c];
-        if (step == 0)
-#pragma unroll
-            for (int c = 0; c < K; ++c) { rz0[c] = rz[c]; scal[16 + c] = rz[c]; }
-        // progress record in mapped host memory: data first, then the step number (system scope)
-        publish_progress(progress + (step % (progress_len - 1)), rz, K, step);   // the last slot is the "done" record
-    }
-    if (clear_bins) {     // the patch operator's <p, A p> bins of the NEXT step (PcgBuffersT::pq_bins): this launch is the last reader of that set
-        for (int i = int(blockIdx.x) * int(blockDim.x) + int(threadIdx.x); i < kPqBins * K; i += int(gridDim.x) * int(blockDim.x)) clear_bins[i] = 0.0;
-    }
-    // the values of x the evaluation points read (a few thousand, PcgBuffersT::x_ev): p is not written before the direction launch,
-    // so this is x += alpha p of the step with the operands and the expression of k_pcg_direction
-    for (int j = int(blockIdx.x) * int(blockDim.x) + int(threadIdx.x); j < ev.n; j += int(gridDim.x) * int(blockDim.x)) {
-        const int64_t at = ev.at[j];
-        if (at < 0) continue;
-        const int col = int(at % K);
-        double a = 0.0;
-#pragma unroll
-        for (int c = 0; c < K; ++c) a = (c == col) ? alpha[c] : a;
-        const T xv = ev.x[j], pv = p[at];
-        ev.x[j] = xv + T(a) * pv;
-    }
-    if (x_only) {   // residual replacement step (mixed precision): r and the <Cr,r> partials come from k_mixed_replace
-        for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) {
-#pragma unroll
-            for (int c = 0; c < K; ++c) x[i * K + c] += T(alpha[c]) * p[i * K + c];
-        }
-        return;
-    }
-    // fold.nb_flat > 0: the workgroups behind the first nb_flat take the vertex rows, 8 lanes per row, and run the FIRST
-    // Chebyshev step on them in the same pass (its operand D^-1 (r - alpha q) / theta is formed per gathered entry from
-    // the OLD r and q, both complete at this point).  The new vertex residual goes to a staging vector (fold.stage =
-    // the free one of the two direction buffers): r itself is still being gathered by the neighbours' rows; the next
-    // Chebyshev launch commits it.  One launch less per PCG step.
-    const int nb_flat = fold.nb_flat > 0 ? fold.nb_flat : int(gridDim.x);
-    if (int(blockIdx.x) >= nb_flat) {
-        constexpr int LPR = 8, RPB = 256 / LPR;
-        static_assert(K <= LPR, "one column per lane after the transposing reduction");
-        const int sub = threadIdx.x % LPR, grp = threadIdx.x / LPR;
-        int idx[K], own[K];
-        towner_init<K, LPR>(idx, own, sub);
-        const int mycol = idx[0];
-        const bool mine = own[0] != 0;
-        const T inv_theta = T(ch.inv_theta), c1 = T(fold.c1), c2 = T(fold.c2);
-        T al[K], a_mine = T(0);
-#pragma unroll
-        for (int c = 0; c < K; ++c) { al[c] = T(alpha[c]); a_mine = (c == mycol) ? al[c] : a_mine; }
-        const int64_t nv = ch.nv;
-        for (int64_t row = int64_t(int(blockIdx.x) - nb_flat) * RPB + grp; row < nv; row += int64_t(int(gridDim.x) - nb_flat) * RPB) {
-            const int32_t rs = fold.rowptr[row], re = fold.rowptr[row + 1];
-            const int64_t at = row * K + mycol;
-            T di = T(0), rn = T(0);
-            if (mine) {
-                di = dinv[row];
-                if (!qv.skip_x) x[at] += a_mine * p[at];
-                rn = r[at] - a_mine * q[at];
-            }
-            T t[K];
-#pragma unroll
-            for (int c = 0; c < K; ++c) t[c] = T(0);
-            for (int32_t pp = rs + sub; pp < re; pp += LPR) {
-                const int32_t j = fold.col[pp];
-                if (j >= nv) break;  // columns ascend: the vertex block leads the row
-                const T v = fold.val[pp] * dinv[j] * inv_theta;
-                const T *rj = r + int64_t(j) * K, *qj = q + int64_t(j) * K;
-#pragma unroll
-                for (int c = 0; c < K; ++c) t[c] += v * (rj[c] - al[c] * qj[c]);
-            }
-            TReduce<K, LPR>::run(t, sub);
-            if (mine) {
-                const T dold = di * rn * inv_theta;
-                const T ri = rn - t[0];
-                ch.z[at] = dold;
-                ch.res[at] = ri;
-                fold.d_new[at] = c1 * dold + c2 * di * ri;
-                fold.stage[at] = rn;
-            }
-        }
-        return;
-    }
-    if (qv.tile) {
-        // TILE form (launcher: patch operator with every row in the slab and its row4 table, x left to the direction launch, no folded
-        // Chebyshev step, n K sizeof(T) and the slab below 4 GB).  A wave takes 64 rows = 64 K values at a time.  Lane l fetches the
-        // four slots of row l of the tile (ONE 16-byte load per lane: 1 KB per wave); then, pass by pass, lane l handles value
-        // 64 t + l of the tile: r as 512 consecutive bytes per wave and instruction, the slots of the value's row from the lane that
-        // holds them (ds_bpermute), and ITS column of each slab slot - the K lanes of a row read a slot's 40 bytes side by side.
-        // All 6 K loads of a lane are in flight together.  Same sums, same order as the row form (rows of five or more patches, the
-        // first vertex rows: their further slots are summed by the row's lane and handed over through LDS - another association).
-        constexpr uint32_t S = sizeof(T);
-        __shared__ double ex_lds[4 * 64 * K];
-        __syncthreads();          // (the reductions' last reads of smem)
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int c = 0; c < K; ++c) smem[c] = alpha[c];
-        }
-        __syncthreads();
-        const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const uint32_t N = uint32_t(n) * K, NV = uint32_t(ch.nv) * K;
-        const rsrc_t rr = make_rsrc(r, uint64_t(N) * S), rd = make_rsrc(dinv, uint64_t(n) * S), rs = make_rsrc(qv.Yb, qv.slab_bytes),
-                     r4 = make_rsrc(qv.row4, uint64_t(n) * 16);
-        uint32_t rowof[K], colof[K];      // pass t: this lane's value is (row rowof[t] of the tile, column colof[t]) - the same for every tile
-        T al[K];
-        double accv[K];
-#pragma unroll
-        for (int t = 0; t < K; ++t) {
-            const uint32_t v = 64u * t + lane;
-            rowof[t] = v / uint32_t(K); colof[t] = v - rowof[t] * uint32_t(K);
-            al[t] = T(smem[colof[t]]); accv[t] = 0.0;
-        }
-        double *exw = ex_lds + wave * (64 * K);
-        const uint32_t nwaves = uint32_t(gridDim.x) * 4u;
-        // (the slots of the NEXT tile are requested before this tile's values: one memory round trip per tile on a wave's critical path, not two)
-        int32_t w4n[4];
-        {
-            const uint32_t row0 = (uint32_t(blockIdx.x) * 4u + wave) * 64u + lane;
-            buf_load<int32_t, 4>(r4, row0 < uint32_t(n) ? row0 * 16u : kOutOfRange, w4n);
-        }
-        for (uint32_t R0 = (uint32_t(blockIdx.x) * 4u + wave) * 64u; R0 < uint32_t(n); R0 += nwaves * 64u) {
-            const uint32_t myrow = R0 + lane;
-            int32_t w4[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) w4[j] = myrow < uint32_t(n) ? w4n[j] : -1;
-            {
-                const uint32_t nrow = myrow + nwaves * 64u;
-                buf_load<int32_t, 4>(r4, nrow < uint32_t(n) ? nrow * 16u : kOutOfRange, w4n);
-            }
-            const uint32_t e0 = R0 * uint32_t(K);
-            T rv[K], dv[K], part[K][4];
-#pragma unroll
-            for (int t = 0; t < K; ++t) {
-                const uint32_t e = e0 + 64u * t + lane;
-                T one[1];
-                buf_load<T, 1>(rr, e < N ? e * S : kOutOfRange, one);
-                rv[t] = one[0];
-                buf_load<T, 1>(rd, e < N ? (R0 + rowof[t]) * S : kOutOfRange, one);
-                dv[t] = one[0];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int32_t sj = __builtin_amdgcn_ds_bpermute(int(rowof[t] << 2), w4[j]);
-                    buf_load<T, 1>(rs, sj >= 0 ? (uint32_t(sj) * uint32_t(K) + colof[t]) * S : kOutOfRange, one);
-                    part[t][j] = one[0];
-                }
-            }
-            const bool more = w4[3] == -2;
-            const bool any_more = __builtin_amdgcn_ballot_w64(more) != 0;
-            if (any_more) {       // (wave-uniform) rows of five or more patches in this tile: their lanes sum the slots from the fourth on
-#pragma unroll
-                for (int c = 0; c < K; ++c) exw[lane * K + c] = 0.0;
-                if (more) {
-                    const int32_t c0 = qv.bptr[myrow], c1 = qv.bptr[myrow + 1];
-                    for (int32_t sl = c0 + 3; sl < c1; ++sl) {
-                        const int64_t a2 = qv.bslot[sl];
-#pragma unroll
-                        for (int c = 0; c < K; ++c) exw[lane * K + c] += double(qv.Yb[a2 * K + c]);
-                    }
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's LDS writes are done before its lanes read each other's
-            }
-#pragma unroll
-            for (int t = 0; t < K; ++t) {
-                const uint32_t e = e0 + 64u * t + lane;
-                T qi = part[t][0];
-#pragma unroll
-                for (int j = 1; j < 4; ++j) qi += part[t][j];
-                if (any_more) qi += T(exw[64 * t + lane]);
-                const T ri = rv[t] - al[t] * qi;
-                T one[1] = {ri};
-                buf_store<T, 1>(rr, e < N ? e * S : kOutOfRange, one);
-                accv[t] += (e < NV || e >= N) ? 0.0 : double(ri) * double(ri) * double(dv[t]);
-            }
-            if (any_more) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads done before the next tile's zeros
-        }
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            double tsum = 0.0;
-#pragma unroll
-            for (int t = 0; t < K; ++t) tsum += (colof[t] == uint32_t(c)) ? accv[t] : 0.0;
-            acc[c] = tsum;
-        }
-        __syncthreads();
-        const double mine = block_sum_column<K>(acc, smem);
-        if (threadIdx.x < K) part_rz_next[blockIdx.x * K + threadIdx.x] = mine;
-        return;
-    }
-    const int64_t i0 = fold.nb_flat > 0 ? ch.nv : 0;
-#ifndef REMO_UPD_UNROLL
-#define REMO_UPD_UNROLL 2
-#endif
-#pragma unroll REMO_UPD_UNROLL
-    for (int64_t i = i0 + int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(nb_flat) * blockDim.x) {
-        const T d = dinv[i];
-        const bool coarse = i < ch.nv;
-        T qi[K];
-        int32_t b0 = 0, b1 = 0;
-        if (qv.bptr) { b0 = qv.bptr[i]; b1 = qv.bptr[i + 1]; }
-        // x, p and r of the row are requested HERE, with the row's slab pointers, not behind the branch that gathers q: three more
-        // vectors in flight while the slab slots make their two round trips
-        T xv[K], pv[K], rv[K];
-        if (qv.skip_x) {      // x += alpha p rides on the direction launch, which reads p anyway: neither x nor p is touched here
-#pragma unroll
-            for (int c = 0; c < K; ++c) { xv[c] = T(0); pv[c] = T(0); rv[c] = r[i * K + c]; }
-        } else {
-#pragma unroll
-            for (int c = 0; c < K; ++c) { xv[c] = x[i * K + c]; pv[c] = p[i * K + c]; rv[c] = r[i * K + c]; }
-        }
-        if (b1 > b0) {      // a row shared by several patches: its q is still spread over the slab, one slot per patch, ascending
-            // the first kSlabAhead slots without a branch and with all their loads in flight together (slot numbers, then slab
-            // rows: two round trips; the plain loop made two per slot, and a wave waits for its row with the most slots) - a
-            // missing slot reads slot 0 and counts for nothing; further slots (rare) one by one
-            constexpr int kSlabAhead = 4;
-            if (qv.ahead) {
-            int32_t at[kSlabAhead];
-#pragma unroll
-            for (int j = 0; j < kSlabAhead; ++j) at[j] = qv.bslot[b0 + j < b1 ? b0 + j : b0];
-            T part[kSlabAhead][K];
-            if (qv.slab_bytes) {
-                // a row has 1.84 slots on average (44 % of the rows exactly one, now that every row goes through the slab): a lane asks
-                // only for the slots its row has - the others get an offset beyond the buffer, which sends no request and returns 0
-                const rsrc_t rs = make_rsrc(qv.Yb, qv.slab_bytes);
-#pragma unroll
-                for (int j = 0; j < kSlabAhead; ++j)
-                    buf_load<T, K>(rs, b0 + j < b1 ? uint32_t(at[j]) * uint32_t(K * sizeof(T)) : kOutOfRange, part[j]);
-#pragma unroll
-                for (int c = 0; c < K; ++c) qi[c] = part[0][c];
-#pragma unroll
-                for (int j = 1; j < kSlabAhead; ++j)
-#pragma unroll
-                    for (int c = 0; c < K; ++c) qi[c] += part[j][c];
-            } else {
-#pragma unroll
-            for (int j = 0; j < kSlabAhead; ++j)
-#pragma unroll
-                for (int c = 0; c < K; ++c) part[j][c] = qv.Yb[int64_t(at[j]) * K + c];
-#pragma unroll
-            for (int c = 0; c < K; ++c) qi[c] = part[0][c];
-#pragma unroll
-            for (int j = 1; j < kSlabAhead; ++j) {
-                const T w = b0 + j < b1 ? T(1) : T(0);
-#pragma unroll
-                for (int c = 0; c < K; ++c) qi[c] += w * part[j][c];
-            }
-            }
-            } else {
-#pragma unroll
-                for (int c = 0; c < K; ++c) qi[c] = T(0);
-            }
-            for (int32_t sl = b0 + (qv.ahead ? kSlabAhead : 0); sl < b1; ++sl) {
-                const int64_t a2 = qv.bslot[sl];
-#pragma unroll
-                for (int c = 0; c < K; ++c) qi[c] += qv.Yb[a2 * K + c];
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < K; ++c) qi[c] = q[i * K + c];
-        }
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            const T a = T(alpha[c]);
-            const T xi = xv[c] + a * pv[c];
-            const T ri = rv[c] - a * qi[c];
-            if (!qv.skip_x) x[i * K + c] = xi;
-            r[i * K + c] = ri;
-            acc[c] += coarse ? 0.0 : double(ri) * double(ri) * double(d);   // the vertex block's share comes from the Chebyshev kernels
-        }
-    }
-    __syncthreads();
-    block_sum<K>(acc, smem);
-    if (threadIdx.x < K) part_rz_next[blockIdx.x * K + threadIdx.x] = acc[threadIdx.x];
-}
-
-// One Chebyshev step on the vertex block, 8 lanes per row:
-//   z += d;  res -= A_vv d;  d' = c1 d + c2 D^-1 res
-// FIRST: z = 0, res = r, d = D^-1 r / theta are formed on the fly from the PCG residual (no set-up
-// pass).  LAST = 1 (degree 1 only): z = d, nothing else.  LAST = 2: the polynomial's last term needs no
-// product of its own (z_final = z + d + d'), so the launch that forms d' also finishes z and leaves the
-// <r, z> partial sums for the PCG scalars: a polynomial of `degree` terms costs degree - 1 launches.
-// TC = storage type of the chain (block values, Jacobi factors, directions, residual, running z): T, or float inside an fp64
-// solve (large vertex blocks: the launches are HBM streams there, and a preconditioner may be applied inexactly - the
-// recurrences of x and r never see it).  r (read) and the finished z (written for the direction kernel) stay in T.
-// ELL: the first kEllWidth entries of a row come from the fixed-width image (ecol, eval; k_vblock_ell) and `rowptr` holds the
-// begin / end PAIRS of the entries beyond them in (col, val).
-template <class T, class TC, int K, bool FIRST, int LAST, bool ELL = false>
-__global__ void __launch_bounds__(256) k_cheb_step(int64_t nv, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                                                   const TC *__restrict__ val, const TC *__restrict__ dinv,
-                                                   const TC *__restrict__ d_old, TC *__restrict__ d_new,
-                                                   TC *__restrict__ zc, TC *__restrict__ res, T *__restrict__ z, double c1_, double c2_, double inv_theta_,
-                                                   T *__restrict__ r, double *__restrict__ part, const double *__restrict__ scal, int commit, int step,
-                                                   const int32_t *__restrict__ ecol = nullptr, const TC *__restrict__ eval = nullptr) {
-    const TC c1 = TC(c1_), c2 = TC(c2_), inv_theta = TC(inv_theta_);
-    constexpr int LPR = 8, RPB = 256 / LPR;
-    constexpr bool SAME = sizeof(T) == sizeof(TC);
-    static_assert(K <= LPR, "one column per lane after the transposing reduction");
-    if (solve_done(scal, step)) return;
-    const int sub = threadIdx.x % LPR, grp = threadIdx.x / LPR;
-    // the kernel is a chain of dependent round trips on a tiny block (launch-latency class): after the
-    // transposing reduction lane `sub` owns column mycol of its row, so the vectors of the update are
-    // requested per lane BEFORE the row is walked and need no round trip of their own
-    int idx[K], own[K];
-    towner_init<K, LPR>(idx, own, sub);
-    const int mycol = idx[0];
-    const bool mine = own[0] != 0;
-    double dot = 0.0;
-    for (int64_t row = int64_t(blockIdx.x) * RPB + grp; row < nv; row += int64_t(gridDim.x) * RPB) {
-        constexpr int NE = ELL ? kEllWidth / LPR : 1;
-        int32_t ej[NE];
-        TC ev[NE];
-        int32_t rs, re;
-        if constexpr (ELL) {
-            const int64_t eb = row * kEllWidth + sub;
-#pragma unroll
-            for (int u = 0; u < NE; ++u) { ej[u] = ecol[eb + u * LPR]; ev[u] = eval[eb + u * LPR]; }
-            rs = rowptr[2 * row]; re = rowptr[2 * row + 1];
-        } else {
-            rs = rowptr[row]; re = rowptr[row + 1];
-        }
-        const int64_t at = row * K + mycol;
-        TC di = TC(0), dold_in = TC(0), z_in = TC(0), res_in = TC(0);
-        T rr = T(0);
-        if (mine) {
-            di = dinv[row];
-            if (SAME && commit) {   // the update launch ran the FIRST step and left the new vertex residual in d_new (free until this
-                rr = T(d_new[at]);  // launch writes it): r could not take it while the neighbours' rows were still gathering r
-                r[at] = rr;
-            } else {
-                rr = r[at];
-            }
-            if (!FIRST) { dold_in = d_old[at]; z_in = zc[at]; res_in = res[at]; }
-        }
-        TC t[K];
-#pragma unroll
-        for (int c = 0; c < K; ++c) t[c] = TC(0);
-        if constexpr (ELL) {
-#pragma unroll
-            for (int u = 0; u < NE; ++u) {
-                const int32_t j = ej[u];
-                const TC v = FIRST ? ev[u] * dinv[j] * inv_theta : ev[u];
-                if (FIRST) {
-                    const T *dj = r + int64_t(j) * K;
-#pragma unroll
-                    for (int c = 0; c < K; ++c) t[c] += v * TC(dj[c]);
-                } else {
-                    const TC *dj = d_old + int64_t(j) * K;
-#pragma unroll
-                    for (int c = 0; c < K; ++c) t[c] += v * dj[c];
-                }
-            }
-        }
-        for (int32_t p = rs + sub; p < re; p += LPR) {
-            const int32_t j = col[p];
-            if (j >= nv) break;  // columns ascend: the vertex block leads the row
-            const TC v = FIRST ? val[p] * dinv[j] * inv_theta : val[p];
-            if (FIRST) {
-                const T *dj = r + int64_t(j) * K;
-#pragma unroll
-                for (int c = 0; c < K; ++c) t[c] += v * TC(dj[c]);
-            } else {
-                const TC *dj = d_old + int64_t(j) * K;
-#pragma unroll
-                for (int c = 0; c < K; ++c) t[c] += v * dj[c];
-            }
-        }
-        TReduce<K, LPR>::run(t, sub);
-        if (mine) {
-            const TC dold = FIRST ? di * TC(rr) * inv_theta : dold_in;
-            TC zi = FIRST ? dold : z_in + dold;
-            const TC ri = (FIRST ? TC(rr) : res_in) - t[0];
-            const TC dn = c1 * dold + c2 * di * ri;
-            if (LAST == 2) zi += dn;
-            if (LAST) z[at] = T(zi / di);   // LAST: stored pre-divided by dinv so the direction kernel treats it like r
-            else {
-                zc[at] = zi;
-                res[at] = ri;
-                d_new[at] = dn;
-            }
-            if (LAST) dot += double(rr) * double(zi);
-        }
-    }
-    if (LAST) {
-        __shared__ double smem[16 * K];
-        double dcol[K];
-#pragma unroll
-        for (int c = 0; c < K; ++c) dcol[c] = (mine && c == mycol) ? dot : 0.0;
-        block_sum<K>(dcol, smem);
-#pragma unroll
-        for (int c = 0; c < K; ++c)
-            if (threadIdx.x == c) part[blockIdx.x * K + c] = dcol[c];
-    }
-}
-
-template <class T, int K>
-__global__ void __launch_bounds__(256) k_pcg_direction(int64_t n, int first, int step, double tol2, int nb_rz, ChebArgsT<T> ch,
-                                                       const double *__restrict__ part_rz_new, double *__restrict__ scal,
-                                                       const T *__restrict__ r, T *__restrict__ p,
-                                                       const T *__restrict__ dinv, T *__restrict__ x = nullptr, int flat = 0) {
-    __shared__ double smem[16 * K];
-    if (solve_done(scal, step)) return;
-    double beta[K], alpha[K];
-#pragma unroll
-    for (int c = 0; c < K; ++c) alpha[c] = 0.0;
-    if (first) {  // p0 = C r0
-#pragma unroll
-        for (int c = 0; c < K; ++c) beta[c] = 0.0;
-    } else {
-        double rzn[K];
-        reduce_partials<K>(part_rz_new, nb_rz, rzn, smem);
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            const double pq = scal[8 + c], rzo = scal[16 + 8 * (step & 1) + c];   // forwarded by the update launch
-            const bool live = (rzo > tol2 * scal[c]) && (rzo > scal[kFloorSlot + c]) && (pq > 0.0);
-            beta[c] = live ? rzn[c] / rzo : 0.0;
-            alpha[c] = live ? rzo / pq : 0.0;      // the step's alpha, from the same operands as in its update launch: the same bits
-        }
-        if (blockIdx.x == 0 && threadIdx.x == 0)
-#pragma unroll
-            for (int c = 0; c < K; ++c) scal[16 + 8 * ((step + 1) & 1) + c] = rzn[c];   // read by the next update launch
-    }
-    if (flat) {
-        // FLAT form (launcher: n K sizeof(T) below 4 GB): the vectors as arrays of n K values, 16 bytes per lane and access, consecutive
-        // lanes on consecutive bytes - every load and store instruction of a wave covers 1 KB of whole lines (the row form's cover 1 KB
-        // out of a 2.5 KB span, three instructions per line).  The column of a value is its index mod K: beta and alpha come from LDS
-        // (an index into registers would put them into scratch memory); the Jacobi factor of its row is an 8-byte load (an L1 hit for
-        // four of five).  Buffer accesses: the range check drops what lies behind the last value, dword by dword.
-        constexpr int VEC = 16 / int(sizeof(T));
-        constexpr uint32_t S = sizeof(T);
-        constexpr int UF = 4;
-        __syncthreads();          // (block_sum's last reads of smem)
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int c = 0; c < K; ++c) { smem[c] = beta[c]; smem[K + c] = alpha[c]; }
-        }
-        __syncthreads();
-        const uint32_t N = uint32_t(n) * K, NV = uint32_t(ch.nv) * K;
-        const rsrc_t rr = make_rsrc(r, uint64_t(N) * S), rz = make_rsrc(ch.z, uint64_t(NV) * S), rp = make_rsrc(p, uint64_t(N) * S),
-                     rd = make_rsrc(dinv, uint64_t(n) * S), rx = make_rsrc(x ? x : p, uint64_t(N) * S);
-        const bool with_x = x != nullptr && !first;
-        const uint32_t span = uint32_t(gridDim.x) * blockDim.x * VEC;
-        for (uint32_t g0 = (uint32_t(blockIdx.x) * blockDim.x + threadIdx.x) * VEC; g0 < N; g0 += UF * span) {
-            T zv[UF][VEC], pv[UF][VEC], xv[UF][VEC], dv[UF][VEC];
-#pragma unroll
-            for (int u = 0; u < UF; ++u) {
-                const uint32_t e0 = g0 + u * span;
-                const uint32_t off = e0 < N ? e0 * S : kOutOfRange;
-                buf_load<T, VEC>(rr, off, zv[u]);
-                {                   // vertex rows: the vertex-block solver's result (stored pre-divided by the Jacobi factor) instead of r
-                    T zz[VEC];      // (no branch: the other lanes hand over an offset out of range and send no request)
-                    buf_load<T, VEC>(rz, e0 < NV ? e0 * S : kOutOfRange, zz);
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) zv[u][v] = (e0 + v < NV) ? zz[v] : zv[u][v];
-                }
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) {
-                    T one[1];
-                    buf_load<T, 1>(rd, e0 < N ? ((e0 + v) / uint32_t(K)) * S : kOutOfRange, one);
-                    dv[u][v] = one[0];
-                }
-                if (!first) buf_load<T, VEC>(rp, off, pv[u]);
-                else {
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) pv[u][v] = T(0);
-                }
-                if (with_x) buf_load<T, VEC>(rx, off, xv[u]);
-                else {
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) xv[u][v] = T(0);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < UF; ++u) {
-                const uint32_t e0 = g0 + u * span;
-                const uint32_t off = e0 < N ? e0 * S : kOutOfRange;
-                T pn[VEC], xn[VEC];
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) {
-                    const uint32_t c = (e0 + v) % uint32_t(K);
-                    const T zi = dv[u][v] * zv[u][v];
-                    pn[v] = first ? zi : zi + T(smem[c]) * pv[u][v];
-                    xn[v] = xv[u][v] + T(smem[K + c]) * pv[u][v];
-                }
-                buf_store<T, VEC>(rp, off, pn);
-                if (with_x) buf_store<T, VEC>(rx, off, xn);
-            }
-        }
-        return;
-    }
-    // U rows per thread are loaded before any of them is stored: p is read and written through the same pointer, and a store
-    // of one row otherwise holds back the loads of the next (one row in flight per thread: 2.7 TB/s at 5.4 M rows in fp32)
-#ifndef REMO_DIR_U
-#define REMO_DIR_U 4
-#endif
-    constexpr int U = REMO_DIR_U;
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    for (int64_t i0 = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i0 < n; i0 += U * stride) {
-        T d[U], zv[U][K], pv[U][K], xv[U][K];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t i = i0 + u * stride;
-            d[u] = T(0);
-#pragma unroll
-            for (int c = 0; c < K; ++c) { zv[u][c] = T(0); pv[u][c] = T(0); xv[u][c] = T(0); }
-            if (i < n) {
-                d[u] = dinv[i];
-                const T *src = (i < ch.nv) ? ch.z : r;   // C r: Chebyshev result on the vertex block (stored as z / dinv), Jacobi elsewhere
-#pragma unroll
-                for (int c = 0; c < K; ++c) zv[u][c] = src[i * K + c];
-                if (!first)
-#pragma unroll
-                    for (int c = 0; c < K; ++c) pv[u][c] = p[i * K + c];
-                if (x && !first)
-#pragma unroll
-                    for (int c = 0; c < K; ++c) xv[u][c] = x[i * K + c];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t i = i0 + u * stride;
-            if (i < n)
-#pragma unroll
-                for (int c = 0; c < K; ++c) {
-                    const T zi = d[u] * zv[u][c];
-                    p[i * K + c] = first ? zi : zi + T(beta[c]) * pv[u][c];
-                    // x += alpha p of THIS step, with the old direction that is in registers anyway (PcgBuffersT::x_in_direction):
-                    // the update launch then neither reads p nor touches x - one pass over p less per step
-                    if (x && !first) x[i * K + c] = xv[u][c] + T(alpha[c]) * pv[u][c];
-                }
-        }
-    }
-}
-
-template <int K>
-__global__ void __launch_bounds__(256) k_pcg_final(int step, int nb_rz, const double *__restrict__ part_rz, const double *__restrict__ scal,
-                                                   PcgProgress *progress, int progress_len) {
-    __shared__ double smem[16 * K];
-    if (solve_done(scal, step)) return;   // the "done" record already holds the final <Cr,r>
-    double rz[K];
-    reduce_partials<K>(part_rz, nb_rz, rz, smem);
-    if (threadIdx.x == 0) publish_progress(progress + (step % (progress_len - 1)), rz, K, step);
-}
+// set-up of the two-level preconditioner's vertex block (the PCG's own kernels and launchers: pcg_kernels.hip)
 
 // Gershgorin bound of the Jacobi-scaled vertex block: max_i dinv_i * sum_j |a_ij|, j < nv
 __global__ void __launch_bounds__(256) k_vblock_bound(int64_t nv, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
@@ -1595,351 +930,6 @@ void launch_vblock_square(int64_t nv, const CsrView &A, const double *dinv, int3
                        capacity, flag);
 }
 
-// Two Chebyshev (Richardson) factors per launch, 16 lanes per row of B's pattern.  State: z and w = D^-1 res.
-//   t1 = A w, t2 = B w;   z += (a + b) w - a b D^-1 t1;   w' = w - (a + b) D^-1 t1 + a b D^-1 t2
-// FIRST: z = 0, w = D^-1 r formed on the fly; LAST: z is stored divided by dinv (the direction kernel treats it like
-// r) and the <r, z> partial sums are left for the PCG scalars.
-template <class T, int K, int LPR, bool FIRST, bool LAST>
-__global__ void __launch_bounds__(256) k_cheb_pair(int64_t nv, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                                                   const T *__restrict__ va, const T *__restrict__ vb, const T *__restrict__ dinv,
-                                                   const T *__restrict__ w_old, T *__restrict__ w_new, T *__restrict__ z, double ab_sum_, double ab_prod_,
-                                                   const T *__restrict__ r, double *__restrict__ part, const double *__restrict__ scal, int step) {
-    constexpr int RPB = 256 / LPR, U = 2;
-    static_assert(K <= LPR, "one column per lane after the transposing reduction");
-    if (solve_done(scal, step)) return;
-    const T ab_sum = T(ab_sum_), ab_prod = T(ab_prod_);
-    const int sub = threadIdx.x % LPR, grp = threadIdx.x / LPR;
-    int idx[K], own[K];
-    towner_init<K, LPR>(idx, own, sub);
-    const int mycol = idx[0];
-    const bool mine = own[0] != 0;
-    double dot = 0.0;
-    for (int64_t row = int64_t(blockIdx.x) * RPB + grp; row < nv; row += int64_t(gridDim.x) * RPB) {
-        const int32_t rs = rowptr[row], re = rowptr[row + 1];
-        const int64_t at = row * K + mycol;
-        T di = T(0), wi = T(0), zi = T(0), rr = T(0);
-        if (mine) {
-            di = dinv[row];
-            if (FIRST || LAST) rr = r[at];
-            wi = FIRST ? di * rr : w_old[at];
-            if (!FIRST) zi = z[at];
-        }
-        T t1[K], t2[K];
-#pragma unroll
-        for (int c = 0; c < K; ++c) { t1[c] = T(0); t2[c] = T(0); }
-        for (int32_t p0 = rs + sub; p0 < re; p0 += U * LPR) {   // U passes of loads in flight, as in the SpMM
-            int32_t j[U];
-            T a[U], b[U], w[U][K];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int32_t p = p0 + u * LPR;
-                j[u] = -1; a[u] = T(0); b[u] = T(0);
-                if (p < re) { j[u] = col[p]; a[u] = va[p]; b[u] = vb[p]; }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int c = 0; c < K; ++c) w[u][c] = T(0);
-                if (j[u] >= 0) {
-                    const T *wj = (FIRST ? r : w_old) + int64_t(j[u]) * K;
-                    const T dj = FIRST ? dinv[j[u]] : T(1);
-#pragma unroll
-                    for (int c = 0; c < K; ++c) w[u][c] = FIRST ? dj * wj[c] : wj[c];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int c = 0; c < K; ++c) { t1[c] += a[u] * w[u][c]; t2[c] += b[u] * w[u][c]; }
-        }
-        TReduce<K, LPR>::run(t1, sub);
-        TReduce<K, LPR>::run(t2, sub);
-        if (mine) {
-            const T zn = zi + ab_sum * wi - ab_prod * di * t1[0];
-            z[at] = LAST ? zn / di : zn;
-            if (!LAST) w_new[at] = wi - ab_sum * di * t1[0] + ab_prod * di * t2[0];
-            if (LAST) dot += double(rr) * double(zn);
-        }
-    }
-    if (LAST) {
-        __shared__ double smem[16 * K];
-        double dcol[K];
-#pragma unroll
-        for (int c = 0; c < K; ++c) dcol[c] = (mine && c == mycol) ? dot : 0.0;
-        block_sum<K>(dcol, smem);
-#pragma unroll
-        for (int c = 0; c < K; ++c)
-            if (threadIdx.x == c) part[blockIdx.x * K + c] = dcol[c];
-    }
-}
-
-int g_slab_ahead = 1;      // remo_debug_tune key 27: 0 = the update launch walks the slab slots of a shared row one by one
-int g_slab_masked = 1;   // remo_debug_tune key 29: 0 = every row fetches four slab slots and weights the ones it does not have by zero (the form before)
-int g_flat_direction = 1;   // remo_debug_tune key 30: 1 (default) = the direction launch walks its vectors as flat arrays, 16 bytes per lane; 0 = a k-wide row per lane
-int g_tile_update = 1;      // remo_debug_tune key 31: 1 (default, fp64 storage) = the update launch takes 64 rows per wave, a value per lane and pass (k_pcg_update, tile form)
-void set_tile_update(int v) { g_tile_update = v ? 1 : 0; }
-void set_flat_direction(int v) { g_flat_direction = v ? 1 : 0; }
-void set_slab_masked(int v) { g_slab_masked = v ? 1 : 0; }
-void set_slab_ahead(int v) { g_slab_ahead = v ? 1 : 0; }
-int vec_grid(int64_t n) {
-    int64_t g = (n + 255) / 256;
-    if (g > kMaxPartialBlocks / 2) g = kMaxPartialBlocks / 2;
-    if (g < 1) g = 1;
-    return int(g);
-}
-
-int cheb_grid(int64_t nv) {
-    if (nv <= 0) return 0;
-    int64_t g = (nv + 31) / 32;
-    if (g > kMaxPartialBlocks / 2) g = kMaxPartialBlocks / 2;
-    return int(g);
-}
-#define REMO_K_SWITCH(k, CALL) \
-    switch (k) {               \
-        case 1: { constexpr int KK = 1; CALL; } break; \
-        case 2: { constexpr int KK = 2; CALL; } break; \
-        case 3: { constexpr int KK = 3; CALL; } break; \
-        case 4: { constexpr int KK = 4; CALL; } break; \
-        case 5: { constexpr int KK = 5; CALL; } break; \
-        case 6: { constexpr int KK = 6; CALL; } break; \
-        case 7: { constexpr int KK = 7; CALL; } break; \
-        default: { constexpr int KK = 8; CALL; } break; \
-    }
-
-template <class T> static ChebArgsT<T> cheb_args(const PcgBuffersT<T> &b) {
-    ChebArgsT<T> c;
-    c.nv = b.cheb_degree > 0 ? b.nv_coarse : 0;
-    c.inv_theta = b.cheb_degree > 0 ? 1.0 / (0.5 * (b.cheb_lmax + b.cheb_lmin)) : 0.0;
-    c.z = b.cz; c.res = b.cres; c.d0 = b.cd[0];
-    return c;
-}
-
-// C r for the vertex block: `degree` Chebyshev steps; the last one leaves the <r_v, z_v> partials
-// behind the nb_vec partials of the high-order part (slot = even / odd step buffer)
-// the update launch can take the FIRST step along when the polynomial has launches of its own left to commit the
-// vertex residual (degree >= 3) and is not applied through the squared block (2D)
-template <class T> static bool cheb_first_folds(const PcgBuffersT<T> &b);
-template <class T> bool pcg_update_folds(const PcgBuffersT<T> &b) { return cheb_first_folds(b); }
-template bool pcg_update_folds<double>(const PcgBuffersT<double> &);
-template bool pcg_update_folds<float>(const PcgBuffersT<float> &);
-template <class T> static bool cheb_first_folds(const PcgBuffersT<T> &b) {
-    // measured in the bench, fold on vs off on one box: -2.3 % solve time at 12.8 k vertices, -0.9 % at 27 k, +0.4 % at 83 k
-    // (there the step is real work, not launch latency): small vertex blocks only
-    return g_fold_first && !b.amg && b.cheb_degree >= 3 && b.nv_coarse > 0 && b.nv_coarse <= 32768 && !(b.sq_rowptr && (b.cheb_degree & 1) == 0);
-}
-
-template <class T> static void launch_cheb(const CsrViewT<T> &A, int k, int step, const PcgBuffersT<T> &b, double *part_slot, hipStream_t s, bool first_done = false) {
-    if (b.cheb_degree <= 0 || b.nv_coarse <= 0) return;
-    if (b.amg) {   // multigrid cycle instead of the polynomial (amg.hip)
-        if constexpr (sizeof(T) == 8) {
-            if (b.amg32) {
-                launch_amg_cycle<float, double>(*b.amg32, k, step, (const double *)b.r, b.cz, part_slot + int64_t(b.nb_vec) * k, cheb_grid(b.nv_coarse), (const double *)b.rz0, s);
-                return;
-            }
-        }
-        launch_amg_cycle<T, T>(*b.amg, k, step, (const T *)b.r, b.cz, part_slot + int64_t(b.nb_vec) * k, cheb_grid(b.nv_coarse), (const double *)b.rz0, s);
-        return;
-    }
-    if (b.sq_rowptr && (b.cheb_degree & 1) == 0) {   // two Richardson factors of the Chebyshev polynomial per launch
-        const double theta = 0.5 * (b.cheb_lmax + b.cheb_lmin), delta = 0.5 * (b.cheb_lmax - b.cheb_lmin);
-        const int m = b.cheb_degree, np = m / 2;
-        // 3D rows of B hold ~65 entries (32 lanes per row), 2D rows ~19 (8 lanes)
-        const int g_last = cheb_grid(b.nv_coarse);
-        double *part = part_slot + int64_t(b.nb_vec) * k;
-        for (int j = 0; j < np; ++j) {
-            // roots of the shifted Chebyshev polynomial, paired from the two ends of the interval inwards
-            const double r1 = theta - delta * cos(M_PI * (2.0 * (j + 1) - 1.0) / (2.0 * m));
-            const double r2 = theta - delta * cos(M_PI * (2.0 * (m - j) - 1.0) / (2.0 * m));
-            const double a = 1.0 / r1, bb = 1.0 / r2;
-            const T *wold = b.cd[j & 1];
-            T *wnew = b.cd[(j + 1) & 1];
-            const bool first = (j == 0), last = (j + 1 == np);
-            // only the LAST launch leaves partial sums, so only it is tied to the cheb_grid slots
-            auto grid_for = [&](int lpr) { int64_t gg = (b.nv_coarse + 256 / lpr - 1) / (256 / lpr); if (last && gg > g_last) gg = g_last; if (gg > 4096) gg = 4096; return int(gg); };
-#define REMO_CHEB2(LPRV, F, L)                                                                                                                        \
-    REMO_K_SWITCH(k, hipLaunchKernelGGL((k_cheb_pair<T, KK, LPRV, F, L>), dim3(grid_for(LPRV)), dim3(256), 0, s, b.nv_coarse, b.sq_rowptr, b.sq_col, b.sq_a, \
-                                        b.sq_b, b.dinv, wold, wnew, b.cz, a + bb, a * bb, b.r, part, b.rz0, step))
-#define REMO_CHEB2_FL(LPRV)                                 \
-    if (first && last) { REMO_CHEB2(LPRV, true, true); }    \
-    else if (first) { REMO_CHEB2(LPRV, true, false); }      \
-    else if (last) { REMO_CHEB2(LPRV, false, true); }       \
-    else { REMO_CHEB2(LPRV, false, false); }
-            if (b.sq_lanes >= 32) { REMO_CHEB2_FL(32) }
-            else if (b.sq_lanes >= 16) { REMO_CHEB2_FL(16) }
-            else { REMO_CHEB2_FL(8) }
-#undef REMO_CHEB2_FL
-#undef REMO_CHEB2
-        }
-        return;
-    }
-    const double theta = 0.5 * (b.cheb_lmax + b.cheb_lmin), delta = 0.5 * (b.cheb_lmax - b.cheb_lmin);
-    const double sig = theta / delta, inv_theta = 1.0 / theta;
-    double rho = 1.0 / sig;
-    const int g = cheb_grid(b.nv_coarse);
-    double *part = part_slot + int64_t(b.nb_vec) * k;
-    const int launches = b.cheb_degree > 1 ? b.cheb_degree - 1 : 1;   // the last term rides on the launch before it
-    const int32_t *vrow = b.vb_rowptr ? b.vb_rowptr : A.rowptr, *vcol = b.vb_rowptr ? b.vb_col : A.col;   // compact vertex block if there is one
-    const T *vval = b.vb_rowptr ? b.vb_val : A.val;
-    // fp32 chain inside an fp64 solve: needs the compact block (its float copy), never together with the folded first step
-    const bool chain32 = sizeof(T) == 8 && b.c32_val != nullptr && b.vb_rowptr != nullptr && !first_done;
-    // the fixed-width image of the block (k_vblock_ell) in the storage type of the chain, if the host made one
-    const bool ell = b.ell_col != nullptr && b.ell_tail != nullptr && (chain32 ? b.c32_ell_val != nullptr : b.ell_val != nullptr);
-    for (int j = 0; j < launches; ++j) {
-        const double rho_new = 1.0 / (2.0 * sig - rho);
-        const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
-        rho = rho_new;
-        const T *dold = b.cd[j & 1];
-        T *dnew = b.cd[(j + 1) & 1];
-        const bool first = (j == 0), last = (j + 1 == launches);
-        if (first && first_done) continue;        // k_pcg_update did it (with the c1, c2 of cheb_first_coefficients)
-        const int commit = (first_done && j == 1) ? 1 : 0;
-        // only the launch that leaves partial sums is tied to the cheb_grid slots; the others take one row group per
-        // workgroup slot (at 83 k vertices 512 workgroups walk five row groups each, a chain of five dependent round trips:
-        // 17.9 us per launch under rocprofv3, profiles/r01_f_kernel_stats_sizeL_10depths_before_grid_fix.csv; after: 14.2 us, …_after_grid_fix.csv)
-        const int64_t g_rows = (b.nv_coarse + 31) / 32;
-        const int gl = last ? g : int(g_rows < 8192 ? g_rows : 8192);
-#define REMO_CHEB_E(F, L, E)                                                                                                                        \
-    if (chain32) {                                                                                                                                  \
-        REMO_K_SWITCH(k, hipLaunchKernelGGL((k_cheb_step<T, float, KK, F, L, E>), dim3(gl), dim3(256), 0, s, b.nv_coarse, E ? b.ell_tail : vrow, vcol, b.c32_val, b.c32_dinv, \
-                                            (const float *)b.c32_d[j & 1], b.c32_d[(j + 1) & 1], b.c32_z, b.c32_res, b.cz, c1, c2, inv_theta, b.r, part, b.rz0, 0, step, \
-                                            b.ell_col, b.c32_ell_val));                                                                             \
-    } else {                                                                                                                                        \
-        REMO_K_SWITCH(k, hipLaunchKernelGGL((k_cheb_step<T, T, KK, F, L, E>), dim3(gl), dim3(256), 0, s, b.nv_coarse, E ? b.ell_tail : vrow, vcol, vval, b.dinv, dold, dnew, \
-                                            b.cz, b.cres, b.cz, c1, c2, inv_theta, b.r, part, b.rz0, commit, step, b.ell_col, b.ell_val));               \
-    }
-#define REMO_CHEB(F, L)                \
-    if (ell) { REMO_CHEB_E(F, L, true) } \
-    else { REMO_CHEB_E(F, L, false) }
-        if (first && last) { if (b.cheb_degree == 1) { REMO_CHEB(true, 1); } else { REMO_CHEB(true, 2); } }
-        else if (first) { REMO_CHEB(true, 0); }
-        else if (last) { REMO_CHEB(false, 2); }
-        else { REMO_CHEB(false, 0); }
-#undef REMO_CHEB
-#undef REMO_CHEB_E
-    }
-}
-
-template <class T> static int nb_rz(const PcgBuffersT<T> &b) { return b.nb_vec + ((b.cheb_degree > 0 && b.nv_coarse > 0) ? cheb_grid(b.nv_coarse) : 0); }
-
-template <class T> void launch_pcg_init(const CsrViewT<T> &A, int k, const T *f, const PcgBuffersT<T> &b, hipStream_t s) {
-    const int64_t n = A.n;
-    const int g = b.nb_vec;
-    const ChebArgsT<T> ch = cheb_args(b);
-    REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_init<T, KK>), dim3(g), dim3(256), 0, s, n, ch, f, b.dinv, b.x, b.r, b.p, b.part_rz));
-    launch_cheb(A, k, 0, b, b.part_rz, s);
-    if (ch.nv > 0)
-        REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction<T, KK>), dim3(g), dim3(256), 0, s, n, 1, 0, 0.0, nb_rz(b), ch, b.part_rz, b.rz0, b.r, b.p, b.dinv));
-}
-
-template <class T> void launch_pcg_update(const CsrViewT<T> &A, int k, int step, double tol2, const PcgBuffersT<T> &b, hipStream_t s) {
-    const int64_t n = A.n;
-    const int g = b.nb_vec;
-    double *cur = b.part_rz + (step & 1) * (kMaxPartialBlocks * 8);
-    double *nxt = b.part_rz + ((step + 1) & 1) * (kMaxPartialBlocks * 8);
-    const ChebArgsT<T> ch = cheb_args(b);
-    FoldArgsT<T> fold;
-    int grid = g;
-    const bool folded = cheb_first_folds(b);
-    if (folded) {
-        const double theta = 0.5 * (b.cheb_lmax + b.cheb_lmin), delta = 0.5 * (b.cheb_lmax - b.cheb_lmin);
-        const double sig = theta / delta, rho = 1.0 / sig, rho_new = 1.0 / (2.0 * sig - rho);
-        fold.nb_flat = g;
-        fold.rowptr = b.vb_rowptr ? b.vb_rowptr : A.rowptr; fold.col = b.vb_rowptr ? b.vb_col : A.col; fold.val = b.vb_rowptr ? b.vb_val : A.val;
-        fold.d_new = b.cd[1]; fold.stage = b.cd[0];
-        fold.c1 = rho_new * rho; fold.c2 = 2.0 * rho_new / delta;      // the j = 0 coefficients of launch_cheb
-        grid = g + int((b.nv_coarse + 31) / 32);   // the vertex workgroups leave no partial sums: one row group each
-    }
-    QViewT<T> qv;
-    if (b.defer_q && A.patch && !folded) { qv.bptr = A.patch->t.bptr; qv.bslot = A.patch->t.bslot; qv.Yb = A.patch->Yb; qv.ahead = g_slab_ahead; }
-    qv.skip_x = b.x_in_direction ? 1 : 0;
-    if (qv.bptr && g_slab_masked) {
-        const uint64_t bytes = uint64_t(A.patch->t.nslot_cap) * uint64_t(k) * sizeof(T);
-        qv.slab_bytes = bytes < 0xFFFFF000ull ? bytes : 0;
-        qv.row4 = A.patch->t.row4;
-        qv.tile = (g_tile_update && sizeof(T) == 8 && qv.slab_bytes && qv.row4 && qv.skip_x &&     // (fp32 storage: 256 bytes per wave and access - the row form is ahead there, 74.7 against 76.3 ms)
-                   uint64_t(n) * uint64_t(k) * sizeof(T) < 0xFFFFF000ull &&
-                   uint64_t(n) * 16 < 0xFFFFF000ull) ? 1 : 0;
-    }
-    const bool bins = b.pq_bins && b.defer_q && A.patch && !folded;
-    const double *pq_rows = bins ? b.part_pq + (step & 1) * (kPqBins * 8) : b.part_pq;
-    double *pq_clear = bins ? b.part_pq + ((step + 1) & 1) * (kPqBins * 8) : nullptr;
-    REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_update<T, KK>), dim3(grid), dim3(256), 0, s, n, step, tol2, 0, bins ? kPqBins : b.nb_spmv, nb_rz(b), ch, pq_rows, cur, nxt,
-                                        b.rz0, b.progress, b.progress_len, b.p, b.q, b.x, b.r, b.dinv, fold, qv, pq_clear,
-                                        EvSlotsT<T>{b.x_ev_at, b.x_ev, b.x_ev_n}));
-    launch_cheb(A, k, step, b, nxt, s, folded);
-}
-
-// Residual replacement of the mixed mode, in place of launch_pcg_update at the chosen steps:
-//   x32 += alpha p;  x64 += x32, x32 = 0;  r32 = float(f - A64 x64);  C r;  <Cr,r> partials
-// The search direction and the scalars carry on, so the Krylov process is not restarted; what is
-// removed is the drift of the fp32 recurrence residual from the true one.
-template <int K>
-__global__ void __launch_bounds__(256) k_mixed_replace(int64_t n, int64_t nv, const double *__restrict__ f, const double *__restrict__ q64,
-                                                       float *__restrict__ r, const float *__restrict__ dinv, double *__restrict__ part_rz_next,
-                                                       const double *__restrict__ scal, int step) {
-    __shared__ double smem[16 * K];
-    if (solve_done(scal, step)) return;
-    double acc[K];
-#pragma unroll
-    for (int c = 0; c < K; ++c) acc[c] = 0.0;
-    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) {
-        const float d = dinv[i];
-        const bool coarse = i < nv;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            const float ri = float(f[i * K + c] - q64[i * K + c]);
-            r[i * K + c] = ri;
-            acc[c] += coarse ? 0.0 : double(ri) * double(ri) * double(d);
-        }
-    }
-    block_sum<K>(acc, smem);
-    if (threadIdx.x < K) part_rz_next[blockIdx.x * K + threadIdx.x] = acc[threadIdx.x];
-}
-
-void launch_pcg_replace(const CsrViewT<float> &A, const CsrViewT<double> &A64, int k, int step, double tol2, const PcgBuffersT<float> &b,
-                        const double *f64, double *x64, double *q64, hipStream_t s) {
-    const int64_t n = A.n;
-    const int g = b.nb_vec;
-    double *cur = b.part_rz + (step & 1) * (kMaxPartialBlocks * 8);
-    double *nxt = b.part_rz + ((step + 1) & 1) * (kMaxPartialBlocks * 8);
-    const ChebArgsT<float> ch = cheb_args(b);
-    const bool bins = b.pq_bins && b.defer_q && A.patch && !pcg_update_folds(b);
-    const double *pq_rows = bins ? b.part_pq + (step & 1) * (kPqBins * 8) : b.part_pq;
-    double *pq_clear = bins ? b.part_pq + ((step + 1) & 1) * (kPqBins * 8) : nullptr;
-    REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_update<float, KK>), dim3(g), dim3(256), 0, s, n, step, tol2, 1, bins ? kPqBins : b.nb_spmv, nb_rz(b), ch, pq_rows, cur, nxt,
-                                        b.rz0, b.progress, b.progress_len, b.p, b.q, b.x, b.r, b.dinv, FoldArgsT<float>(), QViewT<float>(), pq_clear));
-    launch_mixed_accumulate(n * k, x64, b.x, 1, s);
-    launch_spmm(A64, k, (const double *)x64, q64, (double *)nullptr, (const double *)nullptr, b.nb_spmv, s, 0);
-    REMO_K_SWITCH(k, hipLaunchKernelGGL((k_mixed_replace<KK>), dim3(g), dim3(256), 0, s, n, ch.nv, f64, q64, b.r, b.dinv, nxt, b.rz0, step));
-    launch_cheb(A, k, step, b, nxt, s);
-}
-
-// add_x: this launch also forms x += alpha p of the step (b.x_in_direction and the step's update launch left x alone; a residual
-// replacement of the mixed mode updates x itself)
-template <class T> void launch_pcg_direction(const CsrViewT<T> &A, int k, int step, double tol2, const PcgBuffersT<T> &b, hipStream_t s, bool add_x) {
-    const int64_t n = A.n;
-    const int g = b.nb_vec;
-    const double *nw = b.part_rz + ((step + 1) & 1) * (kMaxPartialBlocks * 8);
-    const ChebArgsT<T> ch = cheb_args(b);
-    T *xp = (add_x && b.x_in_direction) ? b.x : nullptr;
-    const int flat = (g_flat_direction && uint64_t(n) * uint64_t(k) * sizeof(T) < 0xFFFFF000ull) ? 1 : 0;
-    REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction<T, KK>), dim3(g), dim3(256), 0, s, n, 0, step, tol2, nb_rz(b), ch, nw, b.rz0, b.r, b.p, b.dinv, xp, flat));
-}
-
-template <class T> void launch_pcg_final(int k, int step, const PcgBuffersT<T> &b, hipStream_t s) {
-    const double *cur = b.part_rz + (step & 1) * (kMaxPartialBlocks * 8);
-    REMO_K_SWITCH(k, hipLaunchKernelGGL(k_pcg_final<KK>, dim3(1), dim3(256), 0, s, step, nb_rz(b), cur, b.rz0, b.progress, b.progress_len));
-}
-
-#define REMO_INSTANTIATE_PCG(T)                                                                                          \
-    template void launch_pcg_init<T>(const CsrViewT<T> &, int, const T *, const PcgBuffersT<T> &, hipStream_t);          \
-    template void launch_pcg_update<T>(const CsrViewT<T> &, int, int, double, const PcgBuffersT<T> &, hipStream_t);      \
-    template void launch_pcg_direction<T>(const CsrViewT<T> &, int, int, double, const PcgBuffersT<T> &, hipStream_t, bool);   \
-    template void launch_pcg_final<T>(int, int, const PcgBuffersT<T> &, hipStream_t);
-REMO_INSTANTIATE_PCG(double)
-REMO_INSTANTIATE_PCG(float)
-#undef REMO_INSTANTIATE_PCG
-
 // ------------------------------------------------------------------------------------------
 // mixed precision (BASELINE config 5): fp32 inner PCG, fp64 residual refinement.  The outer loop is
 //   r = f - A x (fp64 SpMM)  ->  r32 = (float) r  ->  inner PCG on A32 e = r32  ->  x += e
@@ -2162,7 +1152,7 @@ void launch_eval(int dim, bool condense, int npts, const int32_t *pt_rhs, const 
 }
 
 // The entries of x that k_eval reads, one slot per (point, local dof): the slot of a row that several points read is repeated, and
-// every copy is formed by the same operations on the same operands (k_pcg_update), so each holds the bits of the full x
+// every copy is formed by the same operations on the same operands (pcg_kernels.hip pcg_update_head), so each holds the bits of the full x
 template <int DIM>
 __global__ void k_eval_slots(int npts, int nk, const int32_t *__restrict__ pt_rhs, const int32_t *__restrict__ found,
                              const int32_t *__restrict__ eldof, int k, int64_t *__restrict__ at) {

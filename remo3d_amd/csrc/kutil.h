@@ -1,4 +1,4 @@
-// kutil.h — device helpers shared by the kernel files (kernels.hip, patch.hip): fixed-order block reductions, the early-exit
+// kutil.h — device helpers shared by the kernel files (kernels.hip, pcg_kernels.hip, patch.hip): fixed-order block reductions, the early-exit
 // test of queued PCG launches, and buffer accesses with the hardware range check.
 #pragma once
 #include <hip/hip_runtime.h>

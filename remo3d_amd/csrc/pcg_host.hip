@@ -154,8 +154,9 @@ ChunkResult run_pcg(remo_ctx *ctx, const CsrView &A, int k, const double *d_f, P
 // would have used, rtol^2 <C f, f> of THIS system and preconditioner: one PCG step on A d = f publishes <C f, f> as its step-0 record
 // (its x is discarded: the solve below starts from zero again).  Then q = A x_prev (launch_spmm as the mixed mode calls it: the
 // patch operator's shared rows are folded, not left in the slab), f' = f - q, and the unchanged PCG from zero on A d = f' with no
-// relative target (tol2 = 0) and that threshold as the absolute per-column floor (kFloorSlot: read by k_pcg_update and
-// k_pcg_direction alike, whatever the storage type; the host's iters / converged accounting takes max(tol2 r0, floor)).  A chunk
+// relative target (tol2 = 0) and that threshold as the absolute per-column floor (kFloorSlot: read by the update and the direction
+// launch (pcg_kernels.hip pcg_update_head, pcg_direction_head) alike, whatever the storage type; the host's iters / converged
+// accounting takes max(tol2 r0, floor)).  A chunk
 // whose f' is below the floor freezes every column in the update launch of step 0: zero steps.
 ChunkResult run_pcg_warm(remo_ctx *ctx, const CsrView &A, int k, double *d_f, PcgBuffers &buf, double *x_prev, const remo_opts_t &o,
                          remo_stats_t *st, size_t &ev_used) {

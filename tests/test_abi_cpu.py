@@ -115,6 +115,10 @@ def test_no_kernel_of_the_library_uses_scratch_memory():
     names = code_objects.demangle([k["name"] for k in ks])
     ours = [(k, d) for k, d in zip(ks, names) if d.startswith("remo::")]
     assert len(ours) > 100, len(ours)
-    assert any("k_patch_apply<double, 5" in d for _, d in ours) and any("k_pcg_update<double, 5" in d for _, d in ours)
+    assert any("k_patch_apply<double, 5" in d for _, d in ours)
+    # one kernel per form of the PCG step's update and direction launches (pcg_kernels.hip)
+    for form in ("k_pcg_update<double, 5, true", "k_pcg_update<double, 5, false", "k_pcg_update_tile<double, 5", "k_pcg_update_folded<double, 5",
+                 "k_pcg_update_x<float, 5", "k_pcg_direction_flat<double, 5", "k_pcg_direction_row<double, 5"):
+        assert any(form in d for _, d in ours), form
     bad = ["%s: %d bytes per lane" % (d, k["scratch"]) for k, d in ours if k["scratch"] != 0]
     assert not bad, bad

@@ -469,9 +469,9 @@ def test_compact_vertex_block_is_the_same_operator(precision, mesh3d, gpu_ctx):
         b.close()
 
 
-def _hub_mesh():
-    """A ball of tetrahedra around a HUB vertex with ~45 neighbours (a shell of points with nothing else inside it): vertex rows of
-    the P1 block far longer than the 24 entries of the fixed-width image, next to ordinary ones."""
+def _hub_mesh(shell=44):
+    """A ball of tetrahedra around a HUB vertex with ~45 neighbours (a shell of `shell` points with nothing else inside it): vertex
+    rows of the P1 block far longer than the 24 entries of the fixed-width image, next to ordinary ones."""
     from scipy.spatial import Delaunay
     from remo3d_amd.meshgen import Mesh, _boundary_facets
     rng = np.random.default_rng(11)
@@ -480,7 +480,7 @@ def _hub_mesh():
         v = rng.standard_normal((m, 3))
         return radius * v / np.linalg.norm(v, axis=1)[:, None]
     hub = np.array([[0.0, 0.0, 0.05]])
-    pts = np.concatenate([hub, hub + sphere(44, 1.0), sphere(160, 2.2) * rng.uniform(0.85, 1.0, (160, 1)),
+    pts = np.concatenate([hub, hub + sphere(shell, 1.0), sphere(160, 2.2) * rng.uniform(0.85, 1.0, (160, 1)),
                           sphere(300, 4.0) * rng.uniform(0.7, 1.0, (300, 1)), sphere(260, 6.0)])
     conn = Delaunay(pts).simplices.astype(np.int32)
     p = pts[conn]

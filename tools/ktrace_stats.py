@@ -2,7 +2,7 @@
 """Per-kernel statistics from a rocprofv3 --kernel-trace run with the EARLY-EXIT launches left out.
 
 The host queues PCG launches a few steps ahead of the device; once every column of a solve is frozen the launches that are
-already queued return at once (kernels.hip solve_done: 3-4 us instead of 50).  rocprofv3 --stats averages them in, which
+already queued return at once (kutil.h solve_done: 3-4 us instead of 50).  rocprofv3 --stats averages them in, which
 understates the working kernel.  This script reads the per-dispatch trace (*_kernel_trace.csv), drops, kernel by kernel,
 the dispatches shorter than `--floor` (default 0.35) of that kernel's MEDIAN duration, and prints / writes both views.
 
