@@ -278,6 +278,38 @@ int remo_solve_batch_sens_warm_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, 
                                       const remo_opts_t *opts, remo_stats_t *stats);
 
 /*
+ * The same solves plus the solution AWAY from the borehole axis: the potential, its gradient and the current density at arbitrary
+ * points of the mesh (added within ABI 7: additive, detected by the presence of the symbols).  pts[n_pts * dim] are points in the
+ * mesh's frame, (r, z) in 2D and (x, y, z) in 3D; field_rhs[n_frhs] names the right-hand sides that are read there - any subset of
+ * [0, n_rhs), in any order.  Outputs, each of which may be NULL, column-major over the entries of field_rhs:
+ *     u_f[j * n_pts + q]                 u_h of right-hand side field_rhs[j] at point q (the raw FE potential, as u_out);
+ *     grad_f[(j * n_pts + q) * dim + c]  grad u_h there, (d/dr, d/dz) or (d/dx, d/dy, d/dz): the gradient of the element the point
+ *                                        was found in - grad u_h jumps across element faces;
+ *     J_f[(j * n_pts + q) * dim + c]     J = -Sigma grad u_h with the conductivity (scalar or tensor) of that element's material;
+ *     elem_f[q]                          the element the point was found in, numbered as in mesh->conn.
+ * Among several elements that hold a point (shared faces, edges and vertices; in 3D the whole plane y = 0) the choice is
+ * deterministic: two calls give the same elem_f.  A point in no element - a rectangular section may stick out of the domain - is no
+ * error: elem_f = -1 and NaN in the three values.  The points are located once per batch through a cell grid over their bounding box
+ * (no n_pts * n_elems pass), and every chunk of REMO_MAX_RHS right-hand sides is read right after its solve.  In 2D with
+ * condense = 1 the cell bubbles are recovered as for u_out.  n_pts = 0 and n_frhs = 0 are allowed.
+ * u_out and stats are what remo_solve_batch returns for the same inputs: bit for bit with op = 2, to rounding with op = 3.
+ * Errors: as remo_solve_batch, all outputs NaN-filled and elem_f = -1; a field_rhs outside [0, n_rhs) gives REMO_ERR_ARG before any
+ * device work, as does precision = 1 (the field is formed from the fp64 solution); a non-finite point gives REMO_ERR_POINT.
+ */
+int remo_solve_batch_field(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma,
+                           int32_t n_rhs, const int32_t *src_ptr, const double *src_z, const double *src_I,
+                           const int32_t *eval_ptr, const double *eval_z, double *u_out,
+                           int32_t n_pts, const double *pts /*[n_pts * dim]*/, int32_t n_frhs, const int32_t *field_rhs /*[n_frhs]*/,
+                           double *u_f /*[n_frhs * n_pts]*/, double *grad_f /*[n_frhs * n_pts * dim]*/, double *J_f /*[n_frhs * n_pts * dim]*/,
+                           int32_t *elem_f /*[n_pts]*/, const remo_opts_t *opts, remo_stats_t *stats);
+int remo_solve_batch_field_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor,
+                                  int32_t n_rhs, const int32_t *src_ptr, const double *src_z, const double *src_I,
+                                  const int32_t *eval_ptr, const double *eval_z, double *u_out,
+                                  int32_t n_pts, const double *pts, int32_t n_frhs, const int32_t *field_rhs,
+                                  double *u_f, double *grad_f, double *J_f, int32_t *elem_f,
+                                  const remo_opts_t *opts, remo_stats_t *stats);
+
+/*
  * Staged form of the same work, for callers that keep a batch resident (bench.py: inputs are in
  * HBM before the timed region).  create = validate + upload; run = numbering, pattern, assembly,
  * PCG, evaluation, all RHS; fetch = potentials to the host.
@@ -302,6 +334,14 @@ void remo_batch_destroy(remo_ctx_t *ctx, remo_batch_t *batch);
  * NaN and REMO_ERR_POINT.
  */
 int remo_batch_eval(remo_ctx_t *ctx, remo_batch_t *batch, int32_t rhs, int32_t n_points, const double *z, double *u_out);
+
+/*
+ * The same for arbitrary points of the mesh, with the outputs of remo_solve_batch_field for the one right-hand side `rhs`:
+ * u[n_points], grad[n_points * dim], J[n_points * dim], elem[n_points] (any may be NULL).  Scalar and tensor batches alike; valid
+ * as long as remo_batch_eval is.  Points outside the mesh give NaN / elem = -1 and are no error.
+ */
+int remo_batch_field(remo_ctx_t *ctx, remo_batch_t *batch, int32_t rhs, int32_t n_points, const double *pts,
+                     double *u, double *grad, double *J, int32_t *elem);
 
 /*
  * Inspection hooks used by the parity tests (tests/): the assembled system of the last
@@ -339,6 +379,11 @@ int remo_host_element_matrix_tensor(int32_t dim, const double *vertex_coords, co
 /* The element contraction of remo_solve_batch_sens on the host (the code the kernel runs): out[nc] = x_l^T (dK_e / d component) x_u
  * for element vectors x_l, x_u [nld]; tensor = 0: nc = 1 (d/dsigma), else nc = 3 / 6 (upper triangle, off-diagonal both halves). */
 int remo_host_sens_element(int32_t dim, const double *vertex_coords, int32_t tensor, const double *x_l, const double *x_u, double *out);
+/* The per-point arithmetic of remo_solve_batch_field on the host (the code the kernel runs): out[1 + 2 * dim] = u, grad u, J at
+ * `point` [dim] of the element with sorted vertices vertex_coords and element vector x_e [nld].  sigma_tensor != NULL: the upper
+ * triangle of the material's tensor (REMO_ERR_ARG if not finite and positive definite), else the scalar sigma. */
+int remo_host_field_element(int32_t dim, const double *vertex_coords, const double *sigma_tensor, double sigma, const double *x_e,
+                            const double *point, double *out);
 /* max |sum_m B_a[m][i] B_b[m][j] - M_ab[i][j]|: how well the factorised reference tensors of the patch operator
  * (remo_opts_t.op = 3) reproduce the tensors the CSR assembly contracts (both exact polynomial integrals). */
 double remo_host_factor_error(void);

@@ -54,6 +54,9 @@ int remo_debug_sens_timing(remo_ctx_t *ctx, double *out2);
  * synchronises after every functional), summed over the functionals: [1] = the material pass, [2] = the per-element pass,
  * [3] = the group sums.  0 where not measured. */
 int remo_debug_sens_group_timing(remo_ctx_t *ctx, double *out4);
+/* The field path of the last remo_solve_batch_field / remo_batch_field on this context, ms by HIP events: out2[0] = the location of
+ * the points (cells, radix sort, offsets, both element passes; once per batch), out2[1] = the evaluation launches of all chunks. */
+int remo_debug_field_timing(remo_ctx_t *ctx, double *out2);
 
 /* Process-global knobs, two kinds.  Returns 0, or -1 for a key this build does not have.
  *

@@ -51,11 +51,12 @@ class RemoStats(C.Structure):
 # include/remo3d_hip.h: the drop-in boundary + inspection hooks of the parity tests
 EXPORTS = ["remo_abi_version", "remo_opts_default", "remo_ctx_create", "remo_ctx_destroy", "remo_last_error",
            "remo_solve_batch", "remo_solve_batch_tensor", "remo_solve_batch_sens", "remo_solve_batch_sens_tensor", "remo_solve_batch_sens_groups", "remo_solve_batch_sens_groups_tensor",
+           "remo_solve_batch_field", "remo_solve_batch_field_tensor", "remo_batch_field", "remo_host_field_element",
            "remo_warm_create", "remo_warm_destroy", "remo_warm_clear", "remo_warm_info", "remo_solve_batch_sens_warm", "remo_solve_batch_sens_warm_tensor", "remo_batch_create", "remo_batch_create_tensor", "remo_batch_run", "remo_batch_fetch", "remo_batch_destroy",
            "remo_batch_eval", "remo_batch_get_system", "remo_batch_get_vectors", "remo_batch_apply_coarse", "remo_batch_spmv",
            "remo_host_element_matrix", "remo_host_element_matrix_tensor", "remo_host_sens_element", "remo_host_factor_error", "remo_host_symbolic"]
 # include/remo3d_hip_debug.h: probes and tuning knobs (tests, tools, bench.py's `box` record) - not part of the boundary
-DEBUG_EXPORTS = ["remo_debug_stream", "remo_debug_clock", "remo_debug_device", "remo_debug_cache_gather", "remo_debug_xcc", "remo_debug_tune", "remo_debug_patch_phases", "remo_debug_patch_phases_p", "remo_debug_grid_barrier", "remo_debug_sens_timing", "remo_debug_sens_group_timing"]
+DEBUG_EXPORTS = ["remo_debug_stream", "remo_debug_clock", "remo_debug_device", "remo_debug_cache_gather", "remo_debug_xcc", "remo_debug_tune", "remo_debug_patch_phases", "remo_debug_patch_phases_p", "remo_debug_grid_barrier", "remo_debug_sens_timing", "remo_debug_sens_group_timing", "remo_debug_field_timing"]
 
 SENS_GROUPS_ARGTYPES = []     # argument list of remo_solve_batch_sens_groups / _tensor, filled by load()
 
@@ -110,6 +111,18 @@ def load():
     L.remo_solve_batch_sens_groups.argtypes = list(SENS_GROUPS_ARGTYPES)
     L.remo_solve_batch_sens_groups_tensor.restype = C.c_int
     L.remo_solve_batch_sens_groups_tensor.argtypes = list(SENS_GROUPS_ARGTYPES)
+    # ... u_out, n_pts, pts, n_frhs, field_rhs, u_f, grad_f, J_f, elem_f, opts, stats
+    field_args = batch_args + [dp, C.c_int32, dp, C.c_int32, ip, dp, dp, dp, ip, C.POINTER(RemoOpts), C.POINTER(RemoStats)]
+    L.remo_solve_batch_field.restype = C.c_int
+    L.remo_solve_batch_field.argtypes = field_args
+    L.remo_solve_batch_field_tensor.restype = C.c_int
+    L.remo_solve_batch_field_tensor.argtypes = list(field_args)
+    L.remo_batch_field.restype = C.c_int
+    L.remo_batch_field.argtypes = [vp, vp, C.c_int32, C.c_int32, dp, dp, dp, dp, ip]
+    L.remo_host_field_element.restype = C.c_int
+    L.remo_host_field_element.argtypes = [C.c_int32, dp, dp, C.c_double, dp, dp, dp]
+    L.remo_debug_field_timing.restype = C.c_int
+    L.remo_debug_field_timing.argtypes = [vp, dp]
     L.remo_debug_sens_group_timing.restype = C.c_int
     L.remo_debug_sens_group_timing.argtypes = [vp, dp]
     L.remo_host_sens_element.restype = C.c_int

@@ -16,6 +16,7 @@
 #include "pcg_host.h"
 #include "patch.h"
 #include "sens.h"
+#include "field.h"
 #include "warm.h"
 
 using namespace remo;
@@ -96,6 +97,7 @@ struct Plan {
     bool x_ev_only = false;             // no x, only the values the evaluation points read (PcgBuffersT::x_ev)
     bool want_patch = false, want_amg = false;
     int64_t vertex_block_above = -1;    // build_symbolic_gpu: element count above which only the P1 block gets a pattern
+    size_t field_bytes = 0;             // remo_solve_batch_field: everything field_take takes (Field::bytes)
     size_t arena_bytes = 0;
 };
 
@@ -115,6 +117,7 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
         need += patch_arena_bytes(nt, ndof_max, p.kmax) + (size_t(nt) * 21 + 64) * kmax * 8;
     need += size_t(kMaxPartialBlocks) * 8 * 8 * 3;                   // part_pq, part_rz (rz0, d_bound and the flags ride on the slack below)
     need += size_t(npts) * (N + 8) * 8;                              // d_pz, d_pI, d_prhs, d_found, d_phi, d_fint, d_out
+    need += p.field_bytes;                                           // field sections: d_pts, d_found, d_elem, d_u, d_grad, d_J and the location's buffers
     need += (1 << 20);                                               // alignment of every take + the small buffers
     if (p.x_ev_only) {   // slots + values instead of x
         need -= size_t(ndof_max) * 8 * kmax;                         // x, one of the five vectors above
@@ -146,13 +149,15 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
     return need;
 }
 
-Plan plan_batch(const remo_batch *b, const remo_opts_t &o, int npts) {
+Plan plan_batch(const remo_batch *b, const remo_opts_t &o, int npts, size_t field_bytes) {
     Plan p;
     const int dim = b->dim;
+    p.field_bytes = field_bytes;
     p.kmax = std::min<int>(std::max(b->n_rhs, b->sens ? b->sens->n_fun : 0), REMO_MAX_RHS);   // the adjoint columns run through the same buffers
     // one-shot fp64 solve: no x, only the values the evaluation points read (PcgBuffersT::x_ev); the debug forms of the update
     // (key 25 = 0 writes x there) and the mixed mode's refinement (x64 += x32) need the whole block
-    p.x_ev_only = b->eval_only && !b->sens && g_tune.x_ev && g_tune.x_in_direction && o.precision == 0;
+    // (field sections read whole element vectors at points that are only located on the device: the whole block, as with sensitivities)
+    p.x_ev_only = b->eval_only && !b->sens && !b->field && g_tune.x_ev && g_tune.x_in_direction && o.precision == 0;
     // the patch operator is 3D only; a 2D batch always runs on the CSR product, whatever `op` says
     p.want_patch = dim == 3 && (o.op == 3 || o.op == 0);
     p.want_amg = o.preconditioner != 0 && g_tune.amg != 1 &&
@@ -334,6 +339,104 @@ void locate_points(const Run &r, const DevicePoints &dp) {
     for (int q0 = 0; q0 < dp.npts; q0 += kMaxPoints)
         launch_locate(r.dim, b->nt, b->d_coords, sy.conn, std::min(kMaxPoints, dp.npts - q0), dp.d_pz + q0, dp.d_found + q0, r.s);
     launch_point_shapes(r.dim, dp.npts, dp.d_pz, dp.d_found, b->d_coords, sy.conn, dp.d_phi, r.ctx->d_err, r.s);
+}
+
+// ---- field sections: points anywhere in the mesh, located once per batch; every chunk's solutions are read there while they exist ----
+struct Field {
+    int64_t n = 0;          // points
+    int n_frhs = 0;
+    FieldGrid grid{};
+    size_t sort_bytes = 0, locate_bytes = 0;
+    double *d_pts = nullptr, *d_u = nullptr, *d_grad = nullptr, *d_J = nullptr;
+    int32_t *d_found = nullptr, *d_elem = nullptr;
+    FieldLocate loc{};
+    float ms_locate = 0.f, ms_eval = 0.f;
+    size_t values() const { return size_t(n) * size_t(n_frhs); }
+    size_t bytes(int dim) const {   // of field_take, every take rounded up
+        if (n <= 0) return 0;
+        return align_up(size_t(n) * dim * 8) + 2 * align_up(size_t(n) * 4) + align_up(values() * 8 + 8) + 2 * align_up(values() * dim * 8 + 8) + align_up(locate_bytes);
+    }
+};
+
+// host part: the cell grid of the points and what the location needs
+Field field_plan(const remo_batch *b) {
+    Field f;
+    const remo_field_request *rq = b->field;
+    if (!rq || rq->n_pts <= 0) return f;
+    f.n = rq->n_pts;
+    f.n_frhs = rq->n_frhs;
+    f.grid = field_grid(b->dim, f.n, rq->pts);
+    f.sort_bytes = field_sort_bytes(f.n, f.grid.ncell);
+    f.locate_bytes = field_locate_bytes(f.n, b->nt, f.grid.ncell, f.sort_bytes);
+    return f;
+}
+
+void field_take(const Run &r, Field &f) {
+    if (f.n <= 0) return;
+    remo_ctx *ctx = r.ctx;
+    f.d_pts = ctx->take<double>(size_t(f.n) * r.dim);
+    f.d_found = ctx->take<int32_t>(size_t(f.n)); f.d_elem = ctx->take<int32_t>(size_t(f.n));
+    f.d_u = ctx->take<double>(f.values() + 1); f.d_grad = ctx->take<double>(f.values() * r.dim + 1); f.d_J = ctx->take<double>(f.values() * r.dim + 1);
+    f.loc = field_locate_carve(ctx->take<char>(f.locate_bytes), f.n, r.b->nt, f.grid.ncell, f.sort_bytes);
+    for (hipEvent_t &e : ctx->fev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+}
+
+void field_locate_points(const Run &r, Field &f) {
+    if (f.n <= 0) return;
+    const remo_batch *b = r.b;
+    HIP_TRY(hipEventRecord(r.ctx->fev[0], r.s));
+    HIP_TRY(hipMemcpyAsync(f.d_pts, b->field->pts, sizeof(double) * size_t(f.n) * r.dim, hipMemcpyHostToDevice, r.s));
+    field_locate(r.dim, b->nt, b->d_coords, b->sym.conn, f.n, f.d_pts, f.grid, f.loc, f.d_found, r.s);
+    launch_field_elem(f.n, f.d_found, b->sym.eperm, f.d_elem, r.s);
+    HIP_TRY(hipEventRecord(r.ctx->fev[1], r.s));
+}
+
+// the columns of chunk `chunk` (right-hand sides c0 .. c0 + k - 1, solution in x[n][k]) that field_rhs names, into their slots
+void field_eval_chunk(const Run &r, const System &sys, const DevicePoints &dp, const double *x, Field &f, int c0, int k, int q0, int nq) {
+    if (f.n <= 0 || f.n_frhs <= 0) return;
+    const remo_batch *b = r.b;
+    const DeviceSymbolic &sy = b->sym;
+    const FieldSources src{dp.d_prhs + q0, dp.d_pI + q0, dp.d_found + q0, dp.d_fint + q0, nq};
+    FieldCols cols;
+    bool any = false;
+    auto flush = [&]() {
+        if (cols.n == 0) return;
+        if (!any) HIP_TRY(hipEventRecord(r.ctx->fev[2], r.s));
+        any = true;
+        launch_field_eval(r.dim, sy.condense, b->sigma_comp > 1, f.n, f.d_pts, f.d_found, b->d_coords, sy.conn, b->d_mat, sy.eperm, b->d_sigma, b->n_mat,
+                          sy.eldof, sys.d_C, sys.d_M, k, x, cols, src, f.d_u, f.d_grad, f.d_J, r.s);
+        cols.n = 0;
+    };
+    for (int j = 0; j < f.n_frhs; ++j) {
+        const int rhs = b->field->field_rhs[j];
+        if (rhs < c0 || rhs >= c0 + k) continue;
+        cols.col[cols.n] = rhs - c0; cols.slot[cols.n] = j;
+        if (++cols.n == REMO_MAX_RHS) flush();   // (a right-hand side named more than once)
+    }
+    flush();
+    if (!any) return;
+    HIP_TRY(hipEventRecord(r.ctx->fev[3], r.s));
+    HIP_TRY(hipEventSynchronize(r.ctx->fev[3]));
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, r.ctx->fev[2], r.ctx->fev[3]);
+    f.ms_eval += ms;
+}
+
+void field_fetch(const Run &r, Field &f) {
+    const remo_field_request *rq = r.b->field;
+    if (f.n <= 0) return;
+    hipStream_t s = r.s;
+    if (rq->elem) HIP_TRY(hipMemcpyAsync(rq->elem, f.d_elem, sizeof(int32_t) * size_t(f.n), hipMemcpyDeviceToHost, s));
+    if (f.values() > 0) {
+        if (rq->u) HIP_TRY(hipMemcpyAsync(rq->u, f.d_u, sizeof(double) * f.values(), hipMemcpyDeviceToHost, s));
+        if (rq->grad) HIP_TRY(hipMemcpyAsync(rq->grad, f.d_grad, sizeof(double) * f.values() * r.dim, hipMemcpyDeviceToHost, s));
+        if (rq->J) HIP_TRY(hipMemcpyAsync(rq->J, f.d_J, sizeof(double) * f.values() * r.dim, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&f.ms_locate, r.ctx->fev[0], r.ctx->fev[1]);
+    r.ctx->field_ms[0] = f.ms_locate;
+    r.ctx->field_ms[1] = f.ms_eval;
 }
 
 // ---- images of the vertex block for the preconditioner, and the patch tables ---------------------------------------------------
@@ -616,6 +719,7 @@ int solve_chunk(const Run &r, const Plan &plan, const System &sys, const DeviceP
     tot.ms_solve += e2;
     if (!cr.finite) return fail(ctx, REMO_ERR_NUMERIC, "non-finite residual in PCG");
     b->k_last = k;
+    b->d_prhs_last = dp.d_prhs + q0; b->d_pI_last = dp.d_pI + q0; b->d_found_last = dp.d_found + q0; b->d_fint_last = dp.d_fint + q0; b->nq_last = nq;
     if (!cr.converged) tot.ret = REMO_NOT_CONVERGED;
     for (int c = 0; c < k; ++c) {
         st->iterations[c] = cr.iters[c];
@@ -796,6 +900,8 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         if (o.precision == 1) return fail(ctx, REMO_ERR_ARG, "sensitivities are computed in fp64: remo_opts_t.precision = 1 (mixed) is not supported by remo_solve_batch_sens");
         if (int64_t(b->n_mat) * b->sigma_comp > kSensMaxAcc) return fail(ctx, REMO_ERR_ARG, "too many materials for the sensitivity contraction");
     }
+    if (b->field && o.precision == 1)
+        return fail(ctx, REMO_ERR_ARG, "field sections are formed from the fp64 solution: remo_opts_t.precision = 1 (mixed) is not supported by remo_solve_batch_field");
     b->has_system = false;
     b->amg64 = AmgT<double>{};
     b->amg32 = AmgT<float>{};
@@ -811,7 +917,8 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         const int npts = points.n();
         for (double z : points.z)
             if (!std::isfinite(z)) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
-        const Plan plan = plan_batch(b, o, npts);
+        Field fld = field_plan(b);
+        const Plan plan = plan_batch(b, o, npts, fld.bytes(b->dim));
         ctx->reserve(plan.arena_bytes);
 
         // ---- numbering, then every buffer of the solve (arena order), then the device work up to the one sync --------
@@ -820,6 +927,7 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         Solve sv;
         take_pcg_buffers(r, plan, sys, sv);
         const DevicePoints dp = take_points(r, plan, npts);
+        field_take(r, fld);
         prepare_progress(r, sv.buf);
         HIP_TRY(hipEventRecord(ctx->ev[0], s));
         upload_points(r, points, dp);
@@ -827,6 +935,7 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         assemble_system(r, sys);
         HIP_TRY(hipEventRecord(ctx->ev[2], s));
         locate_points(r, dp);
+        field_locate_points(r, fld);
         HIP_TRY(hipEventRecord(ctx->ev[3], s));
         VertexBlock vb;
         vertex_block_enqueue(r, plan, sys, sv, vb);
@@ -869,7 +978,9 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
             if (b->sens) b->d_x = sv.buf.x = sens.block(sys.n, b->n_rhs, false, chunk);   // the solution is formed where it stays
             if (int rc = solve_chunk(r, plan, sys, dp, sv, mixed ? &mx : nullptr, k, q0, nq, h_out, tot,
                                      warm_hit ? prev.block(sys.n, b->n_rhs, false, chunk) : nullptr)) return rc;
+            if (b->field) field_eval_chunk(r, sys, dp, sv.buf.x, fld, c0, k, q0, nq);   // while the chunk's solutions are there
         }
+        if (b->field) field_fetch(r, fld);
         for (int q = 0; q < npts; ++q)
             if (points.eval_slot[q] >= 0) b->u_out[points.eval_slot[q]] = h_out[q];
         if (const remo_sens_request *rq = b->sens) {   // adjoint columns: same operator, preconditioner and stopping rule; then the contraction

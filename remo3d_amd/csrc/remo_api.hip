@@ -9,6 +9,7 @@
 
 #include "remo_internal.h"
 #include "fem_p3.h"
+#include "field.h"
 #include "warm.h"
 
 using namespace remo;
@@ -77,6 +78,8 @@ void remo_ctx_destroy(remo_ctx_t *ctx) {
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     for (auto &ev : ctx->spmv_ev) hipEventDestroy(ev);
     for (auto &ev : ctx->ev)
+        if (ev) hipEventDestroy(ev);
+    for (auto &ev : ctx->fev)
         if (ev) hipEventDestroy(ev);
     if (ctx->ar.base) hipFree(ctx->ar.base);
     if (ctx->in_pool) hipFree(ctx->in_pool);
@@ -344,6 +347,123 @@ int remo_solve_batch_sens_groups_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh
                                         double *dJ_out, double *dJg_out, const remo_opts_t *opts, remo_stats_t *stats) {
     return solve_batch_sens(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_fun, fun_rhs, fun_ptr, fun_z,
                             fun_w, J_out, dJ_out, opts, stats, true, true, n_group, group, dJg_out);
+}
+
+// remo_solve_batch_field / _tensor: the same one-shot batch with the points attached (batch_run.hip locates them once and reads every
+// chunk's solutions there, field.hip)
+static int solve_batch_field(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
+                             const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                             const double *eval_z, double *u_out, int32_t n_pts, const double *pts, int32_t n_frhs, const int32_t *field_rhs,
+                             double *u_f, double *grad_f, double *J_f, int32_t *elem_f, const remo_opts_t *opts, remo_stats_t *stats, bool tensor) {
+    if (!ctx) return REMO_ERR_ARG;
+    const int dim = (mesh && mesh->dim == 2) ? 2 : 3;
+    auto nan_fill = [&]() {
+        if (u_out && eval_ptr && n_rhs > 0)
+            for (int i = 0; i < eval_ptr[n_rhs]; ++i) u_out[i] = std::nan("");
+        const size_t nv = (n_pts > 0 && n_frhs > 0) ? size_t(n_pts) * size_t(n_frhs) : 0;
+        for (size_t i = 0; i < nv && u_f; ++i) u_f[i] = std::nan("");
+        for (size_t i = 0; i < nv * dim && grad_f; ++i) grad_f[i] = std::nan("");
+        for (size_t i = 0; i < nv * dim && J_f; ++i) J_f[i] = std::nan("");
+        for (int32_t i = 0; i < n_pts && elem_f; ++i) elem_f[i] = -1;
+    };
+    nan_fill();
+    if (n_pts < 0 || n_frhs < 0 || (n_pts > 0 && !pts) || (n_frhs > 0 && !field_rhs)) return fail(ctx, REMO_ERR_ARG, "field points or field_rhs missing");
+    if (n_pts >= (1 << 28)) return fail(ctx, REMO_ERR_ARG, "too many field points");
+    for (int j = 0; j < n_frhs; ++j)
+        if (field_rhs[j] < 0 || field_rhs[j] >= n_rhs) return fail(ctx, REMO_ERR_ARG, "field_rhs names no right-hand side of the batch");
+    if (opts && opts->precision == 1)
+        return fail(ctx, REMO_ERR_ARG, "field sections are formed from the fp64 solution: remo_opts_t.precision = 1 (mixed) is not supported by remo_solve_batch_field");
+    if (mesh && (mesh->dim == 2 || mesh->dim == 3))
+        for (int64_t i = 0; i < int64_t(n_pts) * mesh->dim; ++i)
+            if (!std::isfinite(pts[i])) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
+    remo_batch_t *b = nullptr;
+    int rc = batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, &b, true, tensor);
+    if (rc != REMO_OK) return rc;
+    const remo_field_request rq{n_pts, pts, n_frhs, field_rhs, u_f, grad_f, J_f, elem_f};
+    b->field = &rq;
+    b->eval_only = true;
+    rc = remo_batch_run(ctx, b, opts, stats);
+    if (rc >= 0 && u_out) remo_batch_fetch(ctx, b, u_out);
+    if (rc < 0) nan_fill();
+    remo_batch_destroy(ctx, b);
+    return rc;
+}
+
+int remo_solve_batch_field(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
+                           const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                           const double *eval_z, double *u_out, int32_t n_pts, const double *pts, int32_t n_frhs, const int32_t *field_rhs,
+                           double *u_f, double *grad_f, double *J_f, int32_t *elem_f, const remo_opts_t *opts, remo_stats_t *stats) {
+    return solve_batch_field(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_pts, pts, n_frhs, field_rhs, u_f, grad_f,
+                             J_f, elem_f, opts, stats, false);
+}
+
+int remo_solve_batch_field_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor, int32_t n_rhs,
+                                  const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                                  const double *eval_z, double *u_out, int32_t n_pts, const double *pts, int32_t n_frhs,
+                                  const int32_t *field_rhs, double *u_f, double *grad_f, double *J_f, int32_t *elem_f, const remo_opts_t *opts,
+                                  remo_stats_t *stats) {
+    return solve_batch_field(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_pts, pts, n_frhs, field_rhs, u_f,
+                             grad_f, J_f, elem_f, opts, stats, true);
+}
+
+int remo_batch_field(remo_ctx_t *ctx, remo_batch_t *b, int32_t rhs, int32_t n_pts, const double *pts, double *u, double *grad, double *J,
+                     int32_t *elem) {
+    if (!ctx) return REMO_ERR_ARG;
+    if (!b || n_pts < 0 || (n_pts > 0 && !pts) || n_pts >= (1 << 28)) return fail(ctx, REMO_ERR_ARG, "bad argument");
+    const int dim = b->dim;
+    for (int32_t i = 0; i < n_pts; ++i) {
+        if (u) u[i] = std::nan("");
+        if (elem) elem[i] = -1;
+        for (int d = 0; d < dim; ++d) {
+            if (grad) grad[size_t(i) * dim + d] = std::nan("");
+            if (J) J[size_t(i) * dim + d] = std::nan("");
+        }
+    }
+    if (!b->has_system || b->run_id != ctx->run_id || b->k_last <= 0 || b->n_rhs > REMO_MAX_RHS || !b->d_x)
+        return fail(ctx, REMO_ERR_ARG, "no resident solution for this batch (another batch ran on the context since)");
+    if (rhs < 0 || rhs >= b->k_last) return fail(ctx, REMO_ERR_ARG, "rhs index out of range");
+    for (int64_t i = 0; i < int64_t(n_pts) * dim; ++i)
+        if (!std::isfinite(pts[i])) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
+    if (n_pts == 0) return REMO_OK;
+    try {
+        HIP_TRY(hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        const DeviceSymbolic &sy = b->sym;
+        const size_t np = size_t(n_pts);
+        const FieldGrid grid = field_grid(dim, n_pts, pts);
+        const size_t sort_bytes = field_sort_bytes(n_pts, grid.ncell), loc_bytes = field_locate_bytes(n_pts, b->nt, grid.ncell, sort_bytes);
+        DeviceTemp tmp;
+        double *d_pts = tmp.alloc<double>(np * dim), *d_out = tmp.alloc<double>(np * (1 + 2 * dim));
+        int32_t *d_found = tmp.alloc<int32_t>(np * 2), *d_elem = d_found + np;
+        const FieldLocate loc = field_locate_carve(tmp.alloc<char>(loc_bytes), n_pts, b->nt, grid.ncell, sort_bytes);
+        for (hipEvent_t &e : ctx->fev)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipEventRecord(ctx->fev[0], s));
+        HIP_TRY(hipMemcpyAsync(d_pts, pts, sizeof(double) * np * dim, hipMemcpyHostToDevice, s));
+        field_locate(dim, b->nt, b->d_coords, sy.conn, n_pts, d_pts, grid, loc, d_found, s);
+        launch_field_elem(n_pts, d_found, sy.eperm, d_elem, s);
+        HIP_TRY(hipEventRecord(ctx->fev[1], s));
+        FieldCols cols;
+        cols.n = 1; cols.col[0] = rhs; cols.slot[0] = 0;
+        const FieldSources src{b->d_prhs_last, b->d_pI_last, b->d_found_last, b->d_fint_last, b->nq_last};
+        const double *d_M = b->d_M_last ? b->d_M_last : ((dim == 2) ? ctx->d_M2 : ctx->d_M3);
+        double *d_u = d_out, *d_grad = d_out + np, *d_J = d_grad + np * dim;
+        HIP_TRY(hipEventRecord(ctx->fev[2], s));
+        launch_field_eval(dim, sy.condense, b->sigma_comp > 1, n_pts, d_pts, d_found, b->d_coords, sy.conn, b->d_mat, sy.eperm, b->d_sigma, b->n_mat, sy.eldof,
+                          b->d_C, d_M, b->k_last, b->d_x, cols, src, d_u, d_grad, d_J, s);
+        HIP_TRY(hipEventRecord(ctx->fev[3], s));
+        if (u) HIP_TRY(hipMemcpyAsync(u, d_u, sizeof(double) * np, hipMemcpyDeviceToHost, s));
+        if (grad) HIP_TRY(hipMemcpyAsync(grad, d_grad, sizeof(double) * np * dim, hipMemcpyDeviceToHost, s));
+        if (J) HIP_TRY(hipMemcpyAsync(J, d_J, sizeof(double) * np * dim, hipMemcpyDeviceToHost, s));
+        if (elem) HIP_TRY(hipMemcpyAsync(elem, d_elem, sizeof(int32_t) * np, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ctx->fev[0], ctx->fev[1]); ctx->field_ms[0] = ms;
+        (void)hipEventElapsedTime(&ms, ctx->fev[2], ctx->fev[3]); ctx->field_ms[1] = ms;
+        return REMO_OK;
+    } catch (const std::exception &ex) {
+        return fail(ctx, REMO_ERR_DEVICE, ex.what());
+    }
 }
 
 int remo_batch_eval(remo_ctx_t *ctx, remo_batch_t *b, int32_t rhs, int32_t npts, const double *z, double *u_out) {

@@ -424,4 +424,11 @@ int remo_debug_sens_group_timing(remo_ctx_t *ctx, double *out4) {
     return REMO_OK;
 }
 
+int remo_debug_field_timing(remo_ctx_t *ctx, double *out2) {
+    if (!ctx || !out2) return REMO_ERR_ARG;
+    out2[0] = ctx->field_ms[0];
+    out2[1] = ctx->field_ms[1];
+    return REMO_OK;
+}
+
 }  // extern "C"

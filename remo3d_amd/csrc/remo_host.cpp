@@ -8,6 +8,7 @@
 #include "fem_p3.h"
 #include "symbolic.h"
 #include "sens.h"
+#include "field.h"
 
 namespace remo {
 
@@ -68,6 +69,15 @@ int remo_host_sens_element(int32_t dim, const double *X, int32_t tensor, const d
     bool ok;
     if (dim == 2) ok = tensor ? sens_element<2, true>(X, ref_tables(2), xl, xu, out) : sens_element<2, false>(X, ref_tables(2), xl, xu, out);
     else ok = tensor ? sens_element<3, true>(X, ref_factors3(), xl, xu, out) : sens_element<3, false>(X, ref_factors3(), xl, xu, out);
+    return ok ? REMO_OK : REMO_ERR_MESH;
+}
+
+int remo_host_field_element(int32_t dim, const double *X, const double *sigma_tensor, double sigma, const double *x_e, const double *point, double *out) {
+    if ((dim != 2 && dim != 3) || !X || !x_e || !point || !out) return REMO_ERR_ARG;
+    if (sigma_tensor && !tensor_ok(dim, sigma_tensor)) return REMO_ERR_ARG;
+    bool ok;
+    if (dim == 2) ok = sigma_tensor ? field_point<2, true>(X, point, x_e, sigma_tensor, out) : field_point<2, false>(X, point, x_e, &sigma, out);
+    else ok = sigma_tensor ? field_point<3, true>(X, point, x_e, sigma_tensor, out) : field_point<3, false>(X, point, x_e, &sigma, out);
     return ok ? REMO_OK : REMO_ERR_MESH;
 }
 

@@ -91,6 +91,8 @@ struct remo_ctx {
     double *d_B3 = nullptr;                  // factors of the 3D tensors (ref_factors3) for the sensitivity contraction, uploaded by its first use
     double sens_ms = 0.0, sens_bytes = 0.0;  // last remo_solve_batch_sens: HIP-event time and algorithmic bytes of the contraction launches (remo_debug_sens_timing)
     double sens_group_ms[4] = {};            // last remo_solve_batch_sens_groups: group order; with time_kernels also the material pass, the per-element pass and the group sums, each over all functionals (remo_debug_sens_group_timing)
+    double field_ms[2] = {};                 // last remo_solve_batch_field / remo_batch_field: HIP-event time of the location of the points and of the evaluation launches (remo_debug_field_timing)
+    hipEvent_t fev[4] = {};                  // their events, created by the first use
     remo::PcgProgress *progress = nullptr;  // mapped, coherent host memory
     remo::PcgProgress *progress_dev = nullptr;
     int progress_len = 0;
@@ -141,6 +143,17 @@ struct remo_sens_request {
     double *dJg_out = nullptr;
 };
 
+// What remo_solve_batch_field adds to a batch: points of the mesh, the right-hand sides whose solution is read there and where the
+// values go (host pointers of the caller, valid for the duration of the call only; every output may be NULL).
+struct remo_field_request {
+    int64_t n_pts = 0;
+    const double *pts = nullptr;          // [n_pts * dim]
+    int32_t n_frhs = 0;
+    const int32_t *field_rhs = nullptr;   // [n_frhs], each in [0, n_rhs)
+    double *u = nullptr, *grad = nullptr, *J = nullptr;
+    int32_t *elem = nullptr;
+};
+
 struct remo_warm;   // warm.h
 
 struct remo_batch {
@@ -159,6 +172,7 @@ struct remo_batch {
     bool pooled = false;     // the six arrays live in the context's input pool (remo_solve_batch): not freed with the batch
     const remo_sens_request *sens = nullptr;   // remo_solve_batch_sens: adjoint solves + contraction after the forward solves (batch_run.hip)
     remo_warm *warm = nullptr;                 // remo_solve_batch_sens_warm: where the solutions of the previous call are, and where these go (warm.h)
+    const remo_field_request *field = nullptr; // remo_solve_batch_field: the solution at arbitrary points, chunk by chunk (batch_run.hip, field.hip)
     bool eval_only = false;  // remo_solve_batch: nothing reads the solution after the run but the evaluation points (PcgBuffersT::x_ev)
     // last system (pointers into the context arena; valid until the next run on the context)
     bool has_system = false;
@@ -172,6 +186,10 @@ struct remo_batch {
     remo::AmgT<double> amg64{};             // multigrid hierarchy of the vertex block of the last run (arena)
     remo::AmgT<float> amg32{};
     int k_last = 0;
+    // the axis points of the last chunk (arena): what the recovery of a condensed cell bubble reads (remo_batch_field)
+    const int32_t *d_prhs_last = nullptr, *d_found_last = nullptr;
+    const double *d_pI_last = nullptr, *d_fint_last = nullptr;
+    int nq_last = 0;
     const double *d_M_last = nullptr;       // reference tensors of the last run (remo_opts_t.quadrature)
     uint64_t run_id = 0;
     std::vector<double> u_out;

@@ -268,6 +268,31 @@ def sensitivity_cells(mesh, mat, grid, z_offset=0.0):
     return group.astype(np.int32).ravel(), pair // (n_z * n_h + 1), pair % (n_z * n_h + 1)
 
 
+def field_points(grid, dim, z_offset=0.0):
+    """Points of a section for Context.solve_batch_field, in the frame of a batch.  grid: dict with the point COORDINATES (not edges),
+    in metres, of the depth axis `z` and of one lateral axis: `r` (2D: the mesh's r; 3D: x >= 0 in the dip plane y = 0) or in 3D `x`,
+    the signed x of the dip plane.  z is absolute depth along the borehole axis as in sensitivity_cells; z_offset - the batch's
+    combined depth - takes it to the batch's frame.  Returns [n_z * n_h, dim], z outermost: point iz * n_h + ih."""
+    if dim not in (2, 3):
+        raise ValueError("dim must be 2 or 3")
+    lateral = [k for k in ("r", "x") if k in grid]
+    if len(lateral) != 1 or "z" not in grid:
+        raise ValueError("grid must hold the coordinates of 'z' and of one of 'r' and 'x'")
+    if lateral[0] == "x" and dim != 3:
+        raise ValueError("the 'x' axis exists in 3D only")
+    z = np.asarray(grid["z"], dtype=float)
+    h = np.asarray(grid[lateral[0]], dtype=float)
+    for c in (z, h):
+        if c.ndim != 1 or c.size < 1 or not np.all(np.isfinite(c)):
+            raise ValueError("grid coordinates must be finite 1-D arrays, one point at least")
+    if lateral[0] == "r" and np.any(h < 0):
+        raise ValueError("'r' is a distance from the borehole axis: it cannot be negative")
+    pts = np.zeros((z.size, h.size, dim))
+    pts[:, :, 0] = h[None, :]
+    pts[:, :, dim - 1] = (z - float(z_offset))[:, None]
+    return pts.reshape(-1, dim)
+
+
 # ---------------------------------------------------------------------------------------------
 # Netgen path (2D only): remo3d/netgen_functions.py:12-118
 

@@ -433,6 +433,73 @@ class _Maps(_Output):
         model.sensitivity_grid = {k: np.asarray(v, dtype=float) for k, v in self.grid.items()}
 
 
+class _FieldSections(_Output):
+    """The potential and the current density of the right-hand side behind a record - the electrode configuration actually
+    energised - on a section grid of points: physical values (3D: the half-space FE field halved, as tasks.apparent_resistivity
+    halves its potentials).  Only the records of the kept measurement depths are stored; a batch that holds none takes the plain
+    solver entry."""
+    MAX_SOURCES = 4     # point sources of one right-hand side
+
+    def __init__(self, plan, grid, depths):
+        self.plan, self.grid = plan, grid
+        self.lateral = "x" if "x" in grid else "r"
+        geometry.field_points(grid, plan.dim, 0.0)     # a malformed grid fails here, before any batch is drawn
+        kept = np.arange(len(plan.depths)) if depths is None else np.asarray(depths, dtype=int).ravel()
+        if kept.size != np.unique(kept).size or np.any(kept < 0) or np.any(kept >= len(plan.depths)):
+            raise ValueError("field_depths must be distinct indices into measurement_depths")
+        self.kept, self.slot = kept, {int(d): i for i, d in enumerate(kept)}
+        self.n_z, self.n_h = len(grid["z"]), len(grid[self.lateral])
+        n_tools, n_pts = len(plan.model.tools), self.n_z * self.n_h
+        self.slabs = [np.zeros((kept.size, n_tools, n_pts)), np.zeros((kept.size, n_tools, n_pts, plan.dim)),
+                      np.zeros((kept.size, n_tools, 1 + 2 * self.MAX_SOURCES))]
+
+    def prepare(self, job):
+        solves = self.plan.batches[job.bi].solves
+        rhs = [k for k, s in enumerate(solves) if any(r.depth_index in self.slot for r in s.records)]
+        if rhs:
+            job.field_rhs = rhs
+            job.field_points = geometry.field_points(self.grid, self.plan.dim, self.plan.simulation_depths[job.bi])
+
+    def store(self, job):
+        if job.field_rhs is None:
+            return
+        half = 0.5 if self.plan.dim == 3 else 1.0
+        for j, k in enumerate(job.field_rhs):
+            z, I = job.sources[k]
+            if len(z) > self.MAX_SOURCES:
+                raise ValueError("a right-hand side with more than {} point sources".format(self.MAX_SOURCES))
+            src = np.zeros(1 + 2 * self.MAX_SOURCES)
+            src[0] = len(z)
+            src[1:1 + len(z)] = np.asarray(z) + self.plan.simulation_depths[job.bi]
+            src[1 + self.MAX_SOURCES:1 + self.MAX_SOURCES + len(z)] = I
+            for (di, ti, K, o, m) in job.readers[k]:
+                if di in self.slot:
+                    i = self.slot[di]
+                    self.slabs[0][i, ti] = half * job.field["u"][j]
+                    self.slabs[1][i, ti] = half * job.field["J"][j]
+                    self.slabs[2][i, ti] = src
+
+    def fail(self, rows):
+        for slab in self.slabs:
+            for di, ti in rows:
+                if di in self.slot:
+                    slab[self.slot[di], ti] = np.nan
+
+    def publish(self, model):
+        shape = (self.kept.size, self.n_z, self.n_h)
+        model.field_sections = _per_tool(model, lambda i: dict(u=self.slabs[0][:, i].reshape(shape), J=self.slabs[1][:, i].reshape(shape + (self.plan.dim,))))
+
+        def sources(i):
+            out = []
+            for rec in self.slabs[2][:, i]:
+                n = 0 if np.isnan(rec[0]) else int(rec[0])
+                out.append((rec[1:1 + n].copy(), rec[1 + self.MAX_SOURCES:1 + self.MAX_SOURCES + n].copy()))
+            return out
+        model.field_sources = _per_tool(model, sources)
+        model.field_grid = {k: np.asarray(v, dtype=float) for k, v in self.grid.items()}
+        model.field_depth_index = self.kept.copy()
+
+
 class _BatchRunner:
     """Stages 5 and 6: one batch from its window to every output, and the host threads that do so batch after batch."""
 
@@ -450,8 +517,10 @@ class _BatchRunner:
         try:
             t0 = time.time()
             fg, bh, sigma = self.windowing.window(bi)
-            job = types.SimpleNamespace(bi=bi, sigma=sigma, mesh=self.meshes.mesh(bi, fg, bh), groups=None, functionals=None)
+            job = types.SimpleNamespace(bi=bi, sigma=sigma, mesh=self.meshes.mesh(bi, fg, bh), groups=None, functionals=None,
+                                        field_rhs=None, field_points=None)
             sources, evals, job.readers = tasks.batch_rhs(batch, p.model.tools)
+            job.sources = sources
             t1 = time.time()
             opts = p.batch_opts(job.mesh)
             if any(o.adjoint for o in self.outputs):
@@ -472,6 +541,8 @@ class _BatchRunner:
                             self.cache.after_solve(bi, warm)
                     else:
                         job.outs, job.J, job.dJ, st, rc = c.solve_batch_sens(job.mesh, job.sigma, sources, evals, job.functionals, opts)
+                elif job.field_rhs is not None:
+                    job.outs, job.field, st, rc = c.solve_batch_field(job.mesh, job.sigma, sources, evals, job.field_points, job.field_rhs, opts)
                 else:
                     job.outs, st, rc = c.solve_batch(job.mesh, job.sigma, sources, evals, opts)
             finally:
@@ -531,6 +602,10 @@ class Model:
         self.sensitivity_maps = None   # simulate_logs(sensitivity_grid=...): per tool d ln Ra / d ln R of every grid cell [n_depths, n_z, n_r]
         self.sensitivity_map_rest = None   # ... and of everything outside the grid [n_depths]
         self.sensitivity_grid = None   # the grid of the last maps
+        self.field_sections = None     # simulate_logs(field_grid=...): per tool dict(u [n_kept, n_z, n_h] in V, J [n_kept, n_z, n_h, dim] in A/m2)
+        self.field_sources = None      # ... per tool and kept record the energised point sources (absolute z, I)
+        self.field_grid = None         # the grid of the last sections
+        self.field_depth_index = None  # ... and the indices into measurement_depths they were kept for
         self.inversion = None          # invert_logs: what the last inversion found (inversion.invert_model)
         self.timing = {}
 
@@ -710,7 +785,8 @@ class Model:
                       condense=True, mesh_provider: Optional[Callable] = None, mesh_scale: Optional[float] = None, rtol: float = 1e-8,
                       maxsteps: int = 1000, verbose: bool = True, mesh_workers: Optional[int] = None, precision: str = "fp64",
                       schedule: str = "static", solver_options: Optional[dict] = None, sensitivities: bool = False,
-                      sensitivity_grid: Optional[dict] = None, reuse=None):
+                      sensitivity_grid: Optional[dict] = None, reuse=None, field_grid: Optional[dict] = None,
+                      field_depths=None):
         """solver_options: further keywords of solver.make_opts for every batch (op, coarse, quadrature, assemble, ...).
         sensitivities: also fill self.sensitivities[tool] = dRa/dR in ohm m per ohm m, [n_depths, n_layers, n_cols] with the
         columns of the formation table from column 2 on (RDFZ - a radius, always NaN -, RTFZ, RTUZ, and RVUZ when present; 0 where
@@ -722,10 +798,27 @@ class Model:
         d ln Ra / d ln R of every cell - every resistivity inside the cell (mud, flushed zones, Rh and Rv alike) scaled by a common
         factor - and self.sensitivity_map_rest[tool] [n_depths] with the same for everything outside the grid (the two sum to 1);
         NaN where the batch failed.  Implies the adjoint solves (remo_solve_batch_sens_groups); may be combined with sensitivities.
+        field_grid: dict(r=coordinates, z=coordinates) in metres (3D also x= instead of r: the signed x of the dip plane y = 0; r
+        there means x >= 0; z: absolute depth along the borehole axis; geometry.field_points): also fill
+        self.field_sections[tool] = dict(u [n_kept, n_z, n_r] in V, J [n_kept, n_z, n_r, dim] in A/m2) with the potential and the
+        current density J = -Sigma grad u of the right-hand side the record's reading comes from (remo_solve_batch_field) -
+        physical values: in 3D the half-space FE field halved -, self.field_sources[tool] with that right-hand side's point sources
+        (absolute z, I) per kept record (with a reciprocal configuration: the electrode actually energised), self.field_grid and
+        self.field_depth_index.  NaN outside the batch's mesh and where the batch failed.  field_depths: the indices into
+        measurement_depths for which sections are kept (default: all).  fp64 only; not together with sensitivities,
+        sensitivity_grid or reuse (there are no field variants of the adjoint entries).
         reuse: an inversion.SweepCache shared by sweeps of one geometry (the iterations of invert_logs): the batch meshes come from it
         after the first sweep, and with sensitivities=True every batch's solves start from its solutions of the previous sweep
         (solver.WarmState); self.timing then also reports mesh_hits and warm_hits.  None (default): nothing is kept."""
         start = time.time()
+        if field_grid is not None:
+            if sensitivities or sensitivity_grid is not None or reuse is not None:
+                raise ValueError("field_grid cannot be combined with sensitivities, sensitivity_grid or an inversion's sweeps: "
+                                 "there are no field sections with the adjoint solver entries")
+            if precision != "fp64" or (solver_options or {}).get("precision", "fp64") != "fp64":
+                raise ValueError("field sections are formed from the fp64 solution: precision has to be 'fp64'")
+        elif field_depths is not None:
+            raise ValueError("field_depths needs a field_grid")
         plan = _Plan(self, measurement_depths, domain_radius, batch_size, mesh_generator, mesh_provider, mesh_scale,
                      dict(preconditioner=preconditioner, condense=condense, rtol=rtol, maxsteps=maxsteps, precision=precision),
                      solver_options, verbose)
@@ -735,6 +828,8 @@ class Model:
             outputs.append(_LayerSensitivities(plan, windowing))
         if sensitivity_grid is not None:
             outputs.append(_Maps(plan, sensitivity_grid))
+        if field_grid is not None:
+            outputs.append(_FieldSections(plan, field_grid, field_depths))
         bq = sweep.BatchQueue(len(plan.batches), schedule)
         if reuse is not None:
             from . import inversion
@@ -753,6 +848,7 @@ class Model:
         for o in outputs:            # the same pattern for every slab: every rank has zeros outside its own records
             o.combine()
         self.sensitivities = self.mud_sensitivity = self.sensitivity_maps = self.sensitivity_map_rest = self.sensitivity_grid = None
+        self.field_sections = self.field_sources = self.field_grid = self.field_depth_index = None
         for o in outputs:
             o.publish(self)
         self.timing = dict(total_s=time.time() - start, mesh_s=acc["mesh"], solve_s=acc["solve"], points=acc["points"], batches=len(plan.batches),

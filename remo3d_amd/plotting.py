@@ -172,6 +172,76 @@ def plot_sensitivity_map(model, tool, depth_index, path=None):
     return fig
 
 
+def _uniform_axis(c):
+    c = np.asarray(c, dtype=float)
+    return c.size < 3 or np.allclose(np.diff(c), (c[-1] - c[0]) / (c.size - 1), rtol=1e-6, atol=0.0)
+
+
+def _resample(values, src, dst, axis):
+    """Linear interpolation of `values` along `axis` from the coordinates src to dst (NaN stays NaN where it is met)."""
+    moved = np.moveaxis(values, axis, -1)
+    out = np.empty(moved.shape[:-1] + (dst.size,))
+    for idx in np.ndindex(moved.shape[:-1]):
+        out[idx] = np.interp(dst, src, moved[idx])
+    return np.moveaxis(out, -1, axis)
+
+
+def plot_field_section(model, tool, depth_index, path=None):
+    """One picture of model.field_sections[tool] for the record at measurement depth `depth_index`
+    (Model.simulate_logs(field_grid=...)): filled contours of log10 |u| and the streamlines of the current density J over the
+    resistivity model (model_polygons), the energised electrodes marked.  matplotlib's streamplot needs an evenly spaced grid: a
+    section on other coordinates (e.g. geometric in r) is resampled linearly to as many evenly spaced points for the streamlines.
+    Returns the figure; `path`: also written there."""
+    import matplotlib
+    if not os.environ.get("MPLBACKEND") and not os.environ.get("DISPLAY"):
+        matplotlib.use("Agg", force=False)
+    import matplotlib.pyplot as plt
+    from matplotlib.collections import PolyCollection
+    from matplotlib.colors import LogNorm
+    if getattr(model, "field_sections", None) is None:
+        raise ValueError("the model holds no field sections: run simulate_logs(field_grid=...) first")
+    kept = [int(i) for i in model.field_depth_index]
+    if int(depth_index) not in kept:
+        raise ValueError("no field section was kept for depth index {} (field_depths = {})".format(depth_index, kept))
+    k = kept.index(int(depth_index))
+    grid = model.field_grid
+    lateral = "x" if "x" in grid else "r"
+    h, z = np.asarray(grid[lateral], dtype=float), np.asarray(grid["z"], dtype=float)
+    if h.size < 2 or z.size < 2 or np.any(np.diff(h) <= 0) or np.any(np.diff(z) <= 0):
+        raise ValueError("a picture needs increasing grid coordinates, two at least along both axes")
+    u = np.asarray(model.field_sections[tool]["u"][k], dtype=float)
+    J = np.asarray(model.field_sections[tool]["J"][k], dtype=float)
+    dim = J.shape[-1]
+    fig, ax = plt.subplots(figsize=(5, 7))
+    polys, res = model_polygons(model.formation_model, model.borehole_model, model.dip_deg if lateral == "x" else 0.0, (z[0], z[-1]), (h[0], h[-1]))
+    ax.add_collection(PolyCollection(polys, array=res, cmap="Greys", norm=LogNorm(vmin=max(res.min(), 1e-3) / 2, vmax=res.max() * 2), alpha=0.35, edgecolors="k",
+                                     linewidths=0.4))
+    lu = np.ma.masked_invalid(np.log10(np.where(np.abs(u) > 0, np.abs(u), np.nan)))
+    cs = ax.contourf(h, z, lu, levels=20, cmap="viridis", alpha=0.75)
+    Jh, Jz = J[..., 0], J[..., dim - 1]
+    hs, zs = h, z
+    if not _uniform_axis(h):
+        hs = np.linspace(h[0], h[-1], h.size)
+        Jh, Jz = _resample(Jh, h, hs, 1), _resample(Jz, h, hs, 1)
+    if not _uniform_axis(z):
+        zs = np.linspace(z[0], z[-1], z.size)
+        Jh, Jz = _resample(Jh, z, zs, 0), _resample(Jz, z, zs, 0)
+    if np.any(np.isfinite(Jh) & np.isfinite(Jz)):
+        ax.streamplot(hs, zs, np.ma.masked_invalid(Jh), np.ma.masked_invalid(Jz), color="w", linewidth=0.7, density=1.2, arrowsize=0.7)
+    src_z, src_I = model.field_sources[tool][k]
+    for zq, Iq in zip(np.atleast_1d(src_z), np.atleast_1d(src_I)):
+        ax.plot([0.0], [zq], marker="o" if Iq > 0 else "s", color="r" if Iq > 0 else "b", ms=6, mec="k", zorder=5)
+    ax.set_xlim(h[0], h[-1])
+    ax.set_ylim(z[-1], z[0])
+    ax.set_xlabel("{} [m]".format(lateral))
+    ax.set_ylabel("depth [m]")
+    ax.set_title("{} at {:.2f} m: log10 |u / V|, streamlines of J".format(tool, float(model.logs[tool][int(depth_index), 0])))
+    fig.colorbar(cs, ax=ax)
+    if path is not None:
+        fig.savefig(path, dpi=120)
+    return fig
+
+
 def plot_inversion(model, path=None, true_table=None):
     """One picture of model.inversion (Model.invert_logs): the resistivity columns of the start, final and - if given - true
     formation table against depth (one panel per column with a free entry), and beside them the observed and the fitted logs per

@@ -115,6 +115,16 @@ def _batch_args(handle, mesh, sigma, sources, evals):
     return args, sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez)
 
 
+def _field_points(points, dim):
+    """[n_pts, dim] float64, contiguous (an empty list gives [0, dim])."""
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    if points.size == 0:
+        return np.zeros((0, dim))
+    if points.ndim != 2 or points.shape[1] != dim:
+        raise ValueError("points must be [n_pts, {}], not {}".format(dim, points.shape))
+    return points
+
+
 def _symmetric_gradient(dJ, d, tensor):
     """The library's [n_fun, n, nc] derivatives as the caller sees them: [n_fun, n] for scalar sigma; for tensors the symmetric
     G [n_fun, n, d, d] with dJ = G : dSigma (the triangle's off-diagonal entries hold both halves; each half gets half)."""
@@ -199,16 +209,25 @@ class Context:
     def last_error(self) -> str:
         return (self._L.remo_last_error(self._h) or b"").decode()
 
-    def _one_shot(self, kind, mesh, sigma, sources, evals, opts, raise_on_error, functionals=None, groups=None, n_group=None, warm=None):
-        """The one marshalling path of the one-shot entries remo_solve_batch<kind>[_tensor], kind "", "_sens", "_sens_warm" or "_sens_groups":
-        the common arguments, then the functionals and the groups with their outputs where the kind has them.  Returns
-        (potentials, [J, dJ, [dJg],] stats, rc)."""
+    def _one_shot(self, kind, mesh, sigma, sources, evals, opts, raise_on_error, functionals=None, groups=None, n_group=None, warm=None,
+                  points=None, field_rhs=None):
+        """The one marshalling path of the one-shot entries remo_solve_batch<kind>[_tensor], kind "", "_sens", "_sens_warm", "_sens_groups"
+        or "_field": the common arguments, then the functionals and the groups - or the field points - with their outputs where the kind
+        has them.  Returns (potentials, [J, dJ, [dJg] | field dict,] stats, rc)."""
         args, sigma, tensor, eval_ptr, keep = _batch_args(self._h, mesh, sigma, sources, evals)
         d, nc = int(mesh.dim), (sigma.shape[1] if tensor else 1)
         out = np.full(int(eval_ptr[-1]), np.nan)
         args.append(ptr(out, C.c_double))
-        J, grads = [], []
-        if kind:
+        J, grads, field = [], [], []
+        if kind == "_field":
+            points = _field_points(points, d)
+            field_rhs = np.ascontiguousarray(np.arange(len(sources)) if field_rhs is None else field_rhs, dtype=np.int32).ravel()
+            n_pts, n_f = points.shape[0], field_rhs.size
+            field = [dict(u=np.full((n_f, n_pts), np.nan), grad=np.full((n_f, n_pts, d), np.nan), J=np.full((n_f, n_pts, d), np.nan),
+                          elem=np.full(n_pts, -1, dtype=np.int32))]
+            args += [n_pts, ptr(points, C.c_double), n_f, ptr(field_rhs, C.c_int32), ptr(field[0]["u"], C.c_double), ptr(field[0]["grad"], C.c_double),
+                     ptr(field[0]["J"], C.c_double), ptr(field[0]["elem"], C.c_int32)]
+        elif kind:
             n_fun = len(functionals)
             fun_rhs, fun_ptr, fz, fw = _functional_arrays(functionals)
             args += [n_fun, ptr(fun_rhs, C.c_int32), ptr(fun_ptr, C.c_int32), ptr(fz, C.c_double), ptr(fw, C.c_double)]
@@ -229,7 +248,7 @@ class Context:
         if rc < 0 and raise_on_error:
             raise RemoError(rc, self.last_error())
         potentials = [out[eval_ptr[k]:eval_ptr[k + 1]] for k in range(len(evals))]
-        return (potentials, *J, *[_symmetric_gradient(g, d, tensor) for g in grads], st.as_dict(), rc)
+        return (potentials, *J, *[_symmetric_gradient(g, d, tensor) for g in grads], *field, st.as_dict(), rc)
 
     def solve_batch(self, mesh, sigma, sources, evals, opts: Optional[RemoOpts] = None, raise_on_error=True):
         """One-shot remo_solve_batch.  Returns (list of per-RHS potential arrays, stats dict, rc).
@@ -258,6 +277,21 @@ class Context:
         (potentials, J, dJ, dJg, stats, rc); dJg is [n_fun, n_group] for sigma [n_mat] and [n_fun, n_group, dim, dim] for tensors,
         with the symmetric-G convention of dJ."""
         return self._one_shot("_sens_groups", mesh, sigma, sources, evals, opts, raise_on_error, functionals, groups, n_group)
+
+    def solve_batch_field(self, mesh, sigma, sources, evals, points, field_rhs=None, opts: Optional[RemoOpts] = None, raise_on_error=True):
+        """One-shot remo_solve_batch_field: the batch of solve_batch plus the solution away from the axis.  points: [n_pts, dim] in the
+        mesh's frame ((r, z) / (x, y, z)); field_rhs: the right-hand sides read there, any subset in any order (None: all).  Returns
+        (potentials, field, stats, rc) with field = dict(u [n_frhs, n_pts], grad [n_frhs, n_pts, dim], J = -Sigma grad u
+        [n_frhs, n_pts, dim], elem [n_pts]: the element of mesh.conn every point was found in).  A point outside the mesh is no error:
+        elem -1, NaN in the values."""
+        return self._one_shot("_field", mesh, sigma, sources, evals, opts, raise_on_error, points=points, field_rhs=field_rhs)
+
+    def field_timing(self):
+        """ms of the field path of the last solve_batch_field / Batch.field on this context (remo_debug_field_timing): (location of
+        the points, evaluation launches)."""
+        out = np.zeros(2)
+        self._L.remo_debug_field_timing(self._h, ptr(out, C.c_double))
+        return float(out[0]), float(out[1])
 
     def sens_group_timing(self):
         """ms of the group path of the last solve_batch_sens_groups on this context (remo_debug_sens_group_timing): (group order,
@@ -289,6 +323,7 @@ class Batch:
         if rc != 0:
             raise RemoError(rc, ctx.last_error())
         self._h = h
+        self.dim = int(mesh.dim)
         self.n_rhs = len(sources)
         self.stats = None
 
@@ -319,6 +354,19 @@ class Batch:
         z = np.ascontiguousarray(np.atleast_1d(z), dtype=np.float64)
         out = np.full(z.size, np.nan)
         rc = self._L.remo_batch_eval(self.ctx._h, self._h, int(rhs), z.size, ptr(z, C.c_double), ptr(out, C.c_double))
+        if rc != 0:
+            raise RemoError(rc, self.ctx.last_error())
+        return out
+
+    def field(self, rhs: int, points):
+        """u_h, grad u_h, J = -Sigma grad u_h and the element of right-hand side `rhs` of the last run at arbitrary points [n_pts, dim]
+        of the mesh (remo_batch_field): dict(u [n_pts], grad [n_pts, dim], J [n_pts, dim], elem [n_pts]); outside the mesh NaN / -1."""
+        d = self.dim
+        points = _field_points(points, d)
+        n = points.shape[0]
+        out = dict(u=np.full(n, np.nan), grad=np.full((n, d), np.nan), J=np.full((n, d), np.nan), elem=np.full(n, -1, dtype=np.int32))
+        rc = self._L.remo_batch_field(self.ctx._h, self._h, int(rhs), n, ptr(points, C.c_double), ptr(out["u"], C.c_double),
+                                      ptr(out["grad"], C.c_double), ptr(out["J"], C.c_double), ptr(out["elem"], C.c_int32))
         if rc != 0:
             raise RemoError(rc, self.ctx.last_error())
         return out
@@ -418,6 +466,24 @@ def host_element_matrix(dim: int, vertex_coords: np.ndarray, sigma) -> np.ndarra
     if rc != 0:
         raise RemoError(rc, "remo_host_element_matrix")
     return K
+
+
+def host_field_element(dim: int, vertex_coords: np.ndarray, sigma, x_e, point) -> np.ndarray:
+    """[u, grad u (dim), J (dim)] at `point` of one element from its sorted vertices and element vector (remo_host_field_element: the
+    code the evaluation kernel runs).  sigma: a scalar, or a symmetric dim x dim tensor."""
+    L = _lib.load()
+    X = np.ascontiguousarray(vertex_coords, dtype=np.float64)
+    xe = np.ascontiguousarray(x_e, dtype=np.float64)
+    P = np.ascontiguousarray(point, dtype=np.float64)
+    out = np.zeros(1 + 2 * dim)
+    if np.ndim(sigma) == 0:
+        rc = L.remo_host_field_element(dim, ptr(X, C.c_double), None, float(sigma), ptr(xe, C.c_double), ptr(P, C.c_double), ptr(out, C.c_double))
+    else:
+        S, _ = sigma_table(np.asarray(sigma, dtype=np.float64)[None], dim)
+        rc = L.remo_host_field_element(dim, ptr(X, C.c_double), ptr(S, C.c_double), 0.0, ptr(xe, C.c_double), ptr(P, C.c_double), ptr(out, C.c_double))
+    if rc != 0:
+        raise RemoError(rc, "remo_host_field_element")
+    return out
 
 
 def host_symbolic(mesh, condense=True):
