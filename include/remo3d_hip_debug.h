@@ -85,15 +85,15 @@ int remo_debug_field_timing(remo_ctx_t *ctx, double *out2);
  * (b) ONLY IN A LIBRARY BUILT WITH -DREMO_PROBES (`make -C remo3d_amd/csrc probes` -> libremo3d_hip_probes.so, loaded by the tools
  * through REMO_LIB=...): rejected experiments and ablations, some of which give WRONG RESULTS ON PURPOSE.  The product ignores them:
  *    0 SpMM variant, 1 lanes per row, 2 threads per workgroup, 4 grid size, 5 ablation mode of the pair kernel; 7 lanes per row of
- *    the paired Chebyshev kernel; 8: 0 = CSR pattern by the global sort; 19 threads per workgroup of the patch kernel (512); 21 ablation
- *    mode of the patch kernel (1 no LDS atomics, 2 no arithmetic, 3 no output); 23: 1 = boundary slab row-major; 26 register-lean order
+ *    the paired Chebyshev kernel; 8: 0 = CSR pattern by the global sort; 21 ablation
+ *    mode of the patch kernel (1 no LDS atomics, 2 no arithmetic, 3 no output); 26 register-lean order
  *    of the patch kernel (0 never, 1 always; product: fp32 storage only); 27: 0 = slab slots of a shared row fetched one by one;
  *    28: 0 = a row of <p, A p> per patch + a folding launch; 32 runs of the patch's list per wave (product: 4); 33: 0 = every
  *    workgroup walks the largest patch's row count; 34: 1 / 2 = the patch operator as persistent workgroups that prefetch the next patch by
  *    LDS-DMA / through registers (round 4: parity-green, 138 / 111.5 us against 112 at size L: DESIGN.md section 8), 35 their number per XCD
- *    (0 = as many as stay resident); 36 extra operator applications per PCG step (results discarded: what more applications would cost);
- *    37: 0 = only the rows shared by several patches go through the slab, the others straight to y (the form before round 4's last build).
- *    38: the workgroups of the patch kernel's first round start (slot on the CU) x this many 64-clock units apart (de-phasing probe: no gain).
+ *    (0 = as many as stay resident); 36 extra operator applications per PCG step (results discarded: what more applications would cost).
+ *    (Keys 19, 23, 37 and 38 - 512-thread workgroups, a row-major slab, unshared rows straight to y, staggered starts of the patch
+ *    kernel - left with their code; DESIGN.md section 8 keeps the measurements.)
  *    remo_debug_patch_phases[_p] and remo_debug_grid_barrier also need that build. */
 int remo_debug_tune(int32_t key, int32_t value);
 

@@ -574,21 +574,21 @@ int choose_operator(const Run &r, const Plan &plan, const System &sys, const Sol
     remo_ctx *ctx = r.ctx;
     remo_batch *b = r.b;
     const DeviceSymbolic &sy = b->sym;
-    const int64_t n = sys.n, nt = b->nt;
+    const int64_t n = sys.n;
     const int kmax = plan.kmax;
     PatchTables &ptab = vb.ptab;
     const int32_t *h_patch = vb.h_patch;
     b->A = sys.view(sy);
     b->A.pair_begin = sys.pair_begin; b->A.pair_end = sys.pair_end;
     b->A.vertex_block_only = sys.lite;
-    // (the patch kernel's buffer descriptors address the slab and x with 32-bit byte offsets: beyond 4 GB the CSR product stays)
-    // (all_slab, the product's form: every patch addresses its own block of the slab through a descriptor of its own - only x is bound by this)
-    const bool slab_fits = (ptab.all_slab || uint64_t(nt) * 20 * uint64_t(kmax) * 8 < 0xFFFFF000ull) && uint64_t(n) * uint64_t(kmax) * 8 < 0xFFFFF000ull;
+    // (the patch kernel's buffer descriptor addresses x with 32-bit byte offsets: beyond 4 GB the CSR product stays; every patch
+    // addresses its own block of the slab through a descriptor of its own, so the slab is not bound by this)
+    const bool x_fits = uint64_t(n) * uint64_t(kmax) * 8 < 0xFFFFF000ull;
     // patch operator: asked for, or (op = 0) whenever its tables fit; a patch with more distinct rows than the tables hold
     // (an element list without locality) sends op = 0 on to the CSR product and fails op = 3
     // (the kernel forms byte offsets of rows and slab slots with 24-bit multiplies and 32-bit buffer offsets)
-    const size_t patch_lds = ptab.block > 0 ? patch_lds_bytes(h_patch[1], kmax, ptab.block, ptab.all_slab != 0) : 0;   // what k_patch_apply asks for (kernels.hip patch_applies)
-    const bool patch_ok = plan.want_patch && h_patch[0] == 0 && h_patch[1] > 0 && slab_fits && n < (int64_t(1) << 24) && h_patch[2] < (ptab.all_slab ? 0x7FFFFFF0 : (1 << 24)) && patch_lds <= kPatchLdsLimit;
+    const size_t patch_lds = patch_lds_bytes(h_patch[1], kmax);   // what k_patch_apply asks for (kernels.hip patch_applies)
+    const bool patch_ok = plan.want_patch && h_patch[0] == 0 && h_patch[1] > 0 && x_fits && n < (int64_t(1) << 24) && h_patch[2] < 0x7FFFFFF0 && patch_lds <= kPatchLdsLimit;
     if (sys.lite && !patch_ok) return fail(ctx, REMO_ERR_ARG, "only the P1 block was assembled but the patch operator cannot run on this batch: rerun with remo_opts_t.assemble = 1");
     if (r.o.op == 3 && r.dim == 3 && !patch_ok) return fail(ctx, REMO_ERR_ARG, "patch operator: a patch of the element list touches more distinct rows than its tables hold (or the mesh is too large)");
     patch_op = patch_ok;

@@ -82,25 +82,25 @@ constexpr int kDoneSlot = 4 * 8;   // rz0[kDoneSlot] (as int): step + 1 of the u
 // Patch operator (3D, remo_opts_t.op = 3; patch.hip): the element list cut into runs of E elements, one workgroup each
 struct PatchTables {
     int64_t nt = 0, n = 0, npatch = 0;
-    int E = 0;                         // elements per patch = block / right-hand sides of the batch (one lane per element and column)
+    int E = 0;                         // elements per patch = kPatchBlock / right-hand sides of the batch (one lane per element and column)
     int rows_cap = 0;                  // rows of prow / pout per patch
-    int block = 256;                   // threads per workgroup the tables were laid out for (256 or 512)
+    // block, all_slab, stagger: CONSTANTS (build_patch_tables sets 256 / 1 / 0) that no code reads, kept where they are because the
+    // struct is a by-value argument of every patch kernel: dropping them shifts every argument load (a follow-up)
+    int block = 256;
     int trim = 1;                      // 1: a workgroup's staging / output phases stop at its own patch's row count
     int spread = 4;                    // the lanes of a wave take their elements from this many runs of the patch's list (k_patch_apply; <= 1: one run)
     const uint16_t *lidx = nullptr;    // [nt][20] local row of every element dof inside its patch, 0xFFFF = constrained
     const int32_t *pcount = nullptr;   // [npatch] distinct free rows of the patch
     const int32_t *prow = nullptr;     // [npatch][rows_cap] matrix row of local row m, ascending
-    const int32_t *pout = nullptr;     // [npatch][rows_cap] -1: the row belongs to this patch alone (result goes to y); else its slot in the boundary slab
+    const int32_t *pout = nullptr;     // [npatch][rows_cap] slot of local row m in the slab: pboff[p] + m
     const int32_t *pboff = nullptr;    // [npatch + 1] first slab slot of every patch (its rows' slots are consecutive, in ascending row order)
-    int all_slab = 1;                  // 1 (default): EVERY row of a patch goes to the patch's block of the slab, also the rows no other patch touches
-                                       //   (pout[p][m] = pboff[p] + m: the kernel stores one contiguous block and y is written by whoever sums the slab);
-                                       //   0 (remo_debug_tune key 37, probe builds): only the rows shared by several patches
-    const int32_t *row4 = nullptr;     // [n][4] all_slab: the first four slab slots of every row (-1 none, [3] = -2: five or more, the rest in bslot)
-    const int32_t *bptr = nullptr;     // [n + 1] entries [bptr[r], bptr[r + 1]) of bslot belong to row r, one per patch that touches it (none: not shared)
+    int all_slab = 1;                  // (layout only, see block)
+    const int32_t *row4 = nullptr;     // [n][4] the first four slab slots of every row (-1 none, [3] = -2: five or more, the rest in bslot)
+    const int32_t *bptr = nullptr;     // [n + 1] entries [bptr[r], bptr[r + 1]) of bslot belong to row r, one per patch that touches it
     const int32_t *bslot = nullptr;    // slab slot of each (row, patch) pair; the slab itself is patch-major (a patch's shared rows are one block)
     const double *C = nullptr;         // [nt][6] metric terms (launch_metric_terms)
     int64_t nslot_cap = 0;             // upper bound of bptr[n]: rows of the slab
-    int stagger = 0;                   // probe builds (remo_debug_tune key 38)
+    int stagger = 0;                   // (layout only, see block)
 };
 template <class T> struct PatchOpT {
     PatchTables t;
@@ -113,14 +113,11 @@ template <class T> struct PatchOpT {
 #define REMO_PATCH_PASSES 12
 #endif
 constexpr int kPatchPasses = REMO_PATCH_PASSES;   // staging passes a lane's registers hold (k_patch_apply)
-// dynamic LDS of k_patch_apply: staged k-wide rows (later the fp64 accumulators; + the zero row and one of slack) and the two
-// row tables padded to whole staging passes; a workgroup may ask for 64 KB less the kernel's static 128 k bytes
-// (all_slab, the product's form: no row tables in LDS - the row numbers go straight into registers - so five workgroups of a 700-row batch
-// share a CU's 160 KB instead of four)
-inline size_t patch_lds_bytes(int lds_rows, int k, int block, bool all_slab) {
-    const int pass = kPatchPasses * (block / k);
-    return size_t(lds_rows + 2) * size_t(k) * 8 + (all_slab ? size_t(0) : size_t((lds_rows + pass - 1) / pass) * pass * 8);
-}
+constexpr int kPatchBlock = 256;                  // threads per workgroup of k_patch_apply; the tables are laid out for it
+// dynamic LDS of k_patch_apply: staged k-wide rows (later the fp64 accumulators; + the zero row and one of slack); a workgroup may
+// ask for 64 KB less the kernel's static 128 k bytes.  (No row tables in LDS - the row numbers go straight into registers - so five
+// workgroups of a 700-row batch share a CU's 160 KB.)
+inline size_t patch_lds_bytes(int lds_rows, int k) { return size_t(lds_rows + 2) * size_t(k) * 8; }
 constexpr size_t kPatchLdsLimit = 63 * 1024;
 
 
@@ -163,22 +160,10 @@ template <class T> void launch_spmm(const CsrViewT<T> &A, int k, const T *x, T *
 
 template <class T> void launch_patch_spmm(const CsrViewT<T> &A, int k, const T *x, T *y, double *part, const double *scal, int nblocks, hipStream_t s, int step, bool defer);   // patch.hip
 template <class T> bool pcg_update_folds(const PcgBuffersT<T> &b);   // the update launch takes the first Chebyshev step along (and gathers q)
-void set_patch_mode(int mode);
-void set_patch_stagger(int units);   // key 38 (probe builds)
-void set_patch_all_slab(int on);   // remo_debug_tune key 37 (probe builds): 0 = only the shared rows go through the slab (the form of rounds 3-4)
-void set_patch_persist(int on);   // remo_debug_tune key 34 (patch.hip k_patch_apply_p)
-void set_patch_wgs_per_xcd(int n);   // key 35
-void set_patch_block(int threads);   // 256 (default) or 512
 void set_slab_masked(int v);         // key 29: k_pcg_update<.., MASKED = true> (1) / <.., false> (0)
 void set_flat_direction(int v);      // key 30: k_pcg_direction_flat (1) / k_pcg_direction_row (0)
 void set_tile_update(int v);         // key 31: k_pcg_update_tile (1) / k_pcg_update (0)
 void set_slab_ahead(int v);          // 0: slab slots of a shared row one by one in the update launch (default 1: four in flight)
-void set_patch_trim(int v);
-void set_patch_spread(int v);
-void set_patch_lean(int v);          // register-lean arithmetic phase of the patch kernel: -1 fp32 only (default), 0 never, 1 always
-void set_patch_slab_rows(int v);     // 1: boundary slab row-major (0: patch-major)
-void set_patch_stamps(long long *device_buffer);   // mode 4: [workgroups][8] phase time stamps
-int patch_elements_per_group(int kmax);
 
 template <class T> void launch_pcg_init(const CsrViewT<T> &A, int k, const T *f, const PcgBuffersT<T> &b, hipStream_t s);       // + C r0, p0
 template <class T> void launch_pcg_update(const CsrViewT<T> &A, int k, int step, double tol2, const PcgBuffersT<T> &b, hipStream_t s);  // + C r (Chebyshev steps)

@@ -277,7 +277,7 @@ struct PatchProbe {
 // the argument errors both probes answer with (REMO_OK: go on)
 int patch_probe_check(remo_ctx *ctx, remo_batch *b) {
     if (!b->has_system || b->run_id != ctx->run_id || !b->A.patch) return fail(ctx, REMO_ERR_ARG, "the last run on this batch did not use the patch operator");
-    if (PatchProbe::k * b->patch64.t.E > b->patch64.t.block) return fail(ctx, REMO_ERR_ARG, "the batch's patch tables are laid out for fewer than 5 columns");
+    if (PatchProbe::k * b->patch64.t.E > kPatchBlock) return fail(ctx, REMO_ERR_ARG, "the batch's patch tables are laid out for fewer than 5 columns");
     return REMO_OK;
 }
 }  // namespace
@@ -290,13 +290,14 @@ int remo_debug_patch_phases(remo_ctx_t *ctx, remo_batch_t *b, int32_t fp32, doub
     return fail(ctx, REMO_ERR_ARG, "remo_debug_patch_phases: the library was built without -DREMO_PROBES (make -C remo3d_amd/csrc probes)");
 #else
     if (int rc = patch_probe_check(ctx, b)) return rc;
+    // (this probe is about the one-workgroup-per-patch form; remo_debug_patch_phases_p is the persistent one's: key 34 is put back on every way out)
+    struct PersistOff { int was = set_patch_persist(0); ~PersistOff() { set_patch_persist(was); } } persist_off;
     try {
         HIP_TRY(hipSetDevice(ctx->device));
         const int64_t grid = (b->patch64.t.npatch + 7) / 8 * 8;
         std::vector<long long> h;
         {
             PatchProbe pr(ctx, b, fp32 != 0, size_t(grid) * 8);
-            set_patch_persist(0);     // (this probe is about the one-workgroup-per-patch form; remo_debug_patch_phases_p is the persistent one's)
             pr.stamped_runs();
             for (int mode = 0; mode <= 3; ++mode) {     // the ablation modes 0 .. 3
                 set_patch_mode(mode);
@@ -319,10 +320,9 @@ int remo_debug_patch_phases(remo_ctx_t *ctx, remo_batch_t *b, int32_t fp32, doub
         for (int q = 0; q < 8; ++q) out16[q] /= double(cnt > 0 ? cnt : 1);
         out16[8] = double(hi - lo);     // first start to last end, clock ticks
         out16[9] = double(cnt);
-        set_patch_persist(1);
         return REMO_OK;
     } catch (const std::exception &ex) {
-        set_patch_mode(0); set_patch_stamps(nullptr); set_patch_persist(1);
+        set_patch_mode(0); set_patch_stamps(nullptr);
         return fail(ctx, REMO_ERR_DEVICE, ex.what());
     }
 #endif
@@ -390,9 +390,7 @@ int remo_debug_tune(int32_t key, int32_t value) {
     // Keys of rejected experiments and ablations (some give wrong results on purpose): tools/ builds only (make probes)
     if (key == 7) g_tune.sq_lanes = value;
     else if (key == 8) set_symbolic_tuning(value);
-    else if (key == 19) set_patch_block(value);
     else if (key == 21) set_patch_mode(value);
-    else if (key == 23) set_patch_slab_rows(value);
     else if (key == 26) set_patch_lean(value);
     else if (key == 27) set_slab_ahead(value);
     else if (key == 28) g_tune.dot_bins = value;
@@ -401,9 +399,8 @@ int remo_debug_tune(int32_t key, int32_t value) {
     else if (key == 34) set_patch_persist(value);
     else if (key == 35) set_patch_wgs_per_xcd(value);
     else if (key == 36) g_tune.extra_apply = value;
-    else if (key == 37) set_patch_all_slab(value);
-    else if (key == 38) set_patch_stagger(value);
-    else set_spmm_tuning(key, value);
+    else if (key == 0 || key == 1 || key == 2 || key == 4 || key == 5) set_spmm_tuning(key, value);
+    else return -1;     // no such key
     return 0;
 #else
     (void)value;

@@ -13,7 +13,6 @@ def main():
     only = None
     coarse = "auto"
     precision = "fp64"
-    block = 256
     tunes = []
     for a in sys.argv[1:]:
         if a.startswith("--ops="):
@@ -22,8 +21,6 @@ def main():
             coarse = a[9:]
         if a.startswith("--precision="):
             precision = a[12:]
-        if a.startswith("--block="):
-            block = int(a[8:])
         if a.startswith("--tune="):
             tunes.append(tuple(int(v) for v in a[7:].split("=")))
     sizes = args or ["S"]
@@ -35,7 +32,6 @@ def main():
         print("mesh %s: T=%d built in %.1f s" % (sz, work[sz]["mesh"].n_elems, time.time() - t0), flush=True)
     from remo3d_amd import _lib, solver
     L = _lib.load()
-    L.remo_debug_tune(19, block)
     for key, val in tunes:
         L.remo_debug_tune(key, val)
     out = []

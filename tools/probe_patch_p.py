@@ -38,7 +38,6 @@ def main():
             if L.remo_debug_patch_phases(ctx._h, b._h, fp32, ph) == 0:
                 n2 = ["tables", "stage x", "x->regs", "zero", "arith+accumulate", "output", "partials", "workgroup"]
                 print("%s one workgroup per patch: " % ("fp32" if fp32 else "fp64") + "  ".join("%s %.0f" % (nm, ph[i]) for i, nm in enumerate(n2)) + "  | application %.1f us" % ph[10], flush=True)
-            L.remo_debug_tune(34, 1)
         b.close()
 
 
