@@ -310,6 +310,42 @@ int remo_solve_batch_field_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int3
                                   const remo_opts_t *opts, remo_stats_t *stats);
 
 /*
+ * One entry for all of the above, with sources and readings ANYWHERE in the mesh (added within ABI 7: additive, detected by the
+ * presence of the symbols).  The caller describes the work in a struct instead of an argument list; every point is a full
+ * coordinate in the mesh's frame, (r, z) in 2D and (x, y, z) in 3D, where the entries above take axis positions z.
+ *   Zero-initialise the struct, set size = sizeof(remo_job_t), then sigma, the sources and the evaluation points: that is
+ *   remo_solve_batch (tensor = 1: remo_solve_batch_tensor).  n_fun > 0 adds the functionals of remo_solve_batch_sens (their points
+ *   fun_p), n_group > 0 the groups of remo_solve_batch_sens_groups, warm != NULL the object of remo_solve_batch_sens_warm; n_pts or
+ *   n_frhs != 0 adds the field points of remo_solve_batch_field.  Each part follows the rules of the entry it comes from: argument
+ *   checks, NaN-filled outputs (elem_f -1) on a negative return, stats, the warm object cleared on a negative return.
+ *   Refused with REMO_ERR_ARG, as there is no entry above that does it: field points together with functionals; groups or a warm
+ *   object without functionals; precision = 1 with functionals or field points.
+ *   size: the struct may grow at its end.  A smaller size (an older caller) reads the missing members as zero; a larger one (a newer
+ *   caller) is accepted if the bytes this library does not know are all zero, else REMO_ERR_ARG; a size that does not reach n_fun
+ *   is REMO_ERR_ARG.
+ * What a source is: the weak form's f += I * phi(p).  In 2D a source at r > 0 is a RING that carries the total current I (the form
+ * has the weight 2 pi r already).  In 3D the half ball stands for the whole one by mirror symmetry in y = 0: a source in that plane
+ * (the axis included) gives the solution of 2 I in the full space - the caller halves, as for axis sources - and a source at y > 0
+ * stands for itself and its mirror image.
+ * Points: a batch whose points all have lateral coordinates exactly 0.0 is located and read by the kernels of the axis entries -
+ * with op = 2 its outputs carry the bits of the entry it stands for.  Otherwise all its points are located through the cell grid of
+ * remo_solve_batch_field (same tolerances, lowest element number among several that hold a point).  A point in no element gives
+ * REMO_ERR_POINT - in the half ball that includes y < 0 - and a non-finite coordinate gives REMO_ERR_POINT before any device work.
+ */
+typedef struct {
+    uint32_t size;                 /* sizeof(remo_job_t) as the caller compiled it */
+    int32_t tensor;                /* 0: sigma[n_mat]; 1: sigma[n_mat * nc] upper triangles (remo_solve_batch_tensor) */
+    int32_t n_mat; const double *sigma;
+    int32_t n_rhs; const int32_t *src_ptr; const double *src_p /*[src_ptr[n_rhs] * dim]*/; const double *src_I;
+    const int32_t *eval_ptr; const double *eval_p /*[eval_ptr[n_rhs] * dim]*/; double *u_out;
+    int32_t n_fun; const int32_t *fun_rhs, *fun_ptr; const double *fun_p /*[fun_ptr[n_fun] * dim]*/, *fun_w; double *J_out, *dJ_out;
+    int32_t n_group; const int32_t *group; double *dJg_out;       /* n_group = 0: no groups */
+    remo_warm_t *warm;                                            /* NULL: cold */
+    int32_t n_pts; const double *pts; int32_t n_frhs; const int32_t *field_rhs; double *u_f, *grad_f, *J_f; int32_t *elem_f;
+} remo_job_t;
+int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, const remo_opts_t *opts, remo_stats_t *stats);
+
+/*
  * Staged form of the same work, for callers that keep a batch resident (bench.py: inputs are in
  * HBM before the timed region).  create = validate + upload; run = numbering, pattern, assembly,
  * PCG, evaluation, all RHS; fetch = potentials to the host.
@@ -322,6 +358,9 @@ int remo_batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, c
 int remo_batch_create_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor,
                              int32_t n_rhs, const int32_t *src_ptr, const double *src_z, const double *src_I,
                              const int32_t *eval_ptr, const double *eval_z, remo_batch_t **out);
+/* The same from a job (reads tensor, sigma, the sources and the evaluation points only): the resident form of batches with points
+ * off the axis.  remo_batch_eval stays an axis entry; remo_batch_field reads anywhere. */
+int remo_batch_create_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, remo_batch_t **out);
 int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *batch, const remo_opts_t *opts, remo_stats_t *stats);
 int remo_batch_fetch(remo_ctx_t *ctx, remo_batch_t *batch, double *u_out);
 void remo_batch_destroy(remo_ctx_t *ctx, remo_batch_t *batch);
@@ -384,6 +423,10 @@ int remo_host_sens_element(int32_t dim, const double *vertex_coords, int32_t ten
  * triangle of the material's tensor (REMO_ERR_ARG if not finite and positive definite), else the scalar sigma. */
 int remo_host_field_element(int32_t dim, const double *vertex_coords, const double *sigma_tensor, double sigma, const double *x_e,
                             const double *point, double *out);
+/* The shape values of a point anywhere in an element on the host (the code k_point_shapes_at runs): phi_out[nld] at `point` [dim] of
+ * the element with sorted vertices vertex_coords - what a source there adds to the load, times I, and what a reading there weighs
+ * the element vector with.  REMO_ERR_MESH for a degenerate element. */
+int remo_host_point_shapes(int32_t dim, const double *vertex_coords, const double *point, double *phi_out);
 /* max |sum_m B_a[m][i] B_b[m][j] - M_ab[i][j]|: how well the factorised reference tensors of the patch operator
  * (remo_opts_t.op = 3) reproduce the tensors the CSR assembly contracts (both exact polynomial integrals). */
 double remo_host_factor_error(void);

@@ -57,6 +57,9 @@ int remo_debug_sens_group_timing(remo_ctx_t *ctx, double *out4);
 /* The field path of the last remo_solve_batch_field / remo_batch_field on this context, ms by HIP events: out2[0] = the location of
  * the points (cells, radix sort, offsets, both element passes; once per batch), out2[1] = the evaluation launches of all chunks. */
 int remo_debug_field_timing(remo_ctx_t *ctx, double *out2);
+/* How the last remo_batch_run on this context located the points of its right-hand sides: 0 = the kernels of the axis entries (every
+ * lateral coordinate exactly 0), 1 = the cell grid of the field sections (a batch of remo_solve_job with a point off the axis). */
+int remo_debug_point_location(remo_ctx_t *ctx);
 
 /* Process-global knobs, two kinds.  Returns 0, or -1 for a key this build does not have.
  *

@@ -48,15 +48,29 @@ class RemoStats(C.Structure):
         return d
 
 
+class RemoJob(C.Structure):
+    """remo_job_t: the description of one batch for remo_solve_job / remo_batch_create_job (points are full coordinates)."""
+    _dp, _ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    _fields_ = [("size", C.c_uint32), ("tensor", C.c_int32), ("n_mat", C.c_int32), ("sigma", _dp),
+                ("n_rhs", C.c_int32), ("src_ptr", _ip), ("src_p", _dp), ("src_I", _dp),
+                ("eval_ptr", _ip), ("eval_p", _dp), ("u_out", _dp),
+                ("n_fun", C.c_int32), ("fun_rhs", _ip), ("fun_ptr", _ip), ("fun_p", _dp), ("fun_w", _dp), ("J_out", _dp), ("dJ_out", _dp),
+                ("n_group", C.c_int32), ("group", _ip), ("dJg_out", _dp),
+                ("warm", C.c_void_p),
+                ("n_pts", C.c_int32), ("pts", _dp), ("n_frhs", C.c_int32), ("field_rhs", _ip), ("u_f", _dp), ("grad_f", _dp), ("J_f", _dp),
+                ("elem_f", _ip)]
+
+
 # include/remo3d_hip.h: the drop-in boundary + inspection hooks of the parity tests
 EXPORTS = ["remo_abi_version", "remo_opts_default", "remo_ctx_create", "remo_ctx_destroy", "remo_last_error",
            "remo_solve_batch", "remo_solve_batch_tensor", "remo_solve_batch_sens", "remo_solve_batch_sens_tensor", "remo_solve_batch_sens_groups", "remo_solve_batch_sens_groups_tensor",
            "remo_solve_batch_field", "remo_solve_batch_field_tensor", "remo_batch_field", "remo_host_field_element",
            "remo_warm_create", "remo_warm_destroy", "remo_warm_clear", "remo_warm_info", "remo_solve_batch_sens_warm", "remo_solve_batch_sens_warm_tensor", "remo_batch_create", "remo_batch_create_tensor", "remo_batch_run", "remo_batch_fetch", "remo_batch_destroy",
            "remo_batch_eval", "remo_batch_get_system", "remo_batch_get_vectors", "remo_batch_apply_coarse", "remo_batch_spmv",
-           "remo_host_element_matrix", "remo_host_element_matrix_tensor", "remo_host_sens_element", "remo_host_factor_error", "remo_host_symbolic"]
+           "remo_host_element_matrix", "remo_host_element_matrix_tensor", "remo_host_sens_element", "remo_host_factor_error", "remo_host_symbolic",
+           "remo_solve_job", "remo_batch_create_job", "remo_host_point_shapes"]
 # include/remo3d_hip_debug.h: probes and tuning knobs (tests, tools, bench.py's `box` record) - not part of the boundary
-DEBUG_EXPORTS = ["remo_debug_stream", "remo_debug_clock", "remo_debug_device", "remo_debug_cache_gather", "remo_debug_xcc", "remo_debug_tune", "remo_debug_patch_phases", "remo_debug_patch_phases_p", "remo_debug_grid_barrier", "remo_debug_sens_timing", "remo_debug_sens_group_timing", "remo_debug_field_timing"]
+DEBUG_EXPORTS = ["remo_debug_stream", "remo_debug_clock", "remo_debug_device", "remo_debug_cache_gather", "remo_debug_xcc", "remo_debug_tune", "remo_debug_patch_phases", "remo_debug_patch_phases_p", "remo_debug_grid_barrier", "remo_debug_sens_timing", "remo_debug_sens_group_timing", "remo_debug_field_timing", "remo_debug_point_location"]
 
 SENS_GROUPS_ARGTYPES = []     # argument list of remo_solve_batch_sens_groups / _tensor, filled by load()
 
@@ -117,12 +131,20 @@ def load():
     L.remo_solve_batch_field.argtypes = field_args
     L.remo_solve_batch_field_tensor.restype = C.c_int
     L.remo_solve_batch_field_tensor.argtypes = list(field_args)
+    L.remo_solve_job.restype = C.c_int
+    L.remo_solve_job.argtypes = [vp, C.POINTER(RemoMesh), C.POINTER(RemoJob), C.POINTER(RemoOpts), C.POINTER(RemoStats)]
+    L.remo_batch_create_job.restype = C.c_int
+    L.remo_batch_create_job.argtypes = [vp, C.POINTER(RemoMesh), C.POINTER(RemoJob), C.POINTER(vp)]
+    L.remo_host_point_shapes.restype = C.c_int
+    L.remo_host_point_shapes.argtypes = [C.c_int32, dp, dp, dp]
     L.remo_batch_field.restype = C.c_int
     L.remo_batch_field.argtypes = [vp, vp, C.c_int32, C.c_int32, dp, dp, dp, dp, ip]
     L.remo_host_field_element.restype = C.c_int
     L.remo_host_field_element.argtypes = [C.c_int32, dp, dp, C.c_double, dp, dp, dp]
     L.remo_debug_field_timing.restype = C.c_int
     L.remo_debug_field_timing.argtypes = [vp, dp]
+    L.remo_debug_point_location.restype = C.c_int
+    L.remo_debug_point_location.argtypes = [vp]
     L.remo_debug_sens_group_timing.restype = C.c_int
     L.remo_debug_sens_group_timing.argtypes = [vp, dp]
     L.remo_host_sens_element.restype = C.c_int

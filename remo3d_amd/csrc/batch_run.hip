@@ -48,47 +48,66 @@ int checked_opts(remo_ctx *ctx, const remo_opts_t *opts_in, remo_opts_t &o) {
 
 // ---- points of all RHS, chunk by chunk: [sources..., evals...] --------------------------------------------------------------
 struct Points {
-    std::vector<double> z, I;
+    int dim = 0;
+    std::vector<double> P, I;                           // P: dim coordinates per point
+    std::vector<double> z;                              // on_axis: the last coordinate of every point, what launch_locate reads
     std::vector<int32_t> rhs, chunk_begin, eval_slot;   // eval_slot: u_out index or -1
-    std::vector<std::pair<int32_t, int32_t>> fun_reads; // remo_solve_batch_sens: (point, index into fun_z) of the points the functionals read
+    std::vector<std::pair<int32_t, int32_t>> fun_reads; // remo_solve_batch_sens: (point, index into fun_p) of the points the functionals read
     int forward_chunks = 0;                             // chunks [0, forward_chunks) are the batch's right-hand sides, the rest adjoint columns
     std::vector<int32_t> found_init;                    // INT_MAX per point: what launch_locate starts from
-    int n() const { return int(z.size()); }
+    bool on_axis = true;                                // every lateral coordinate is exactly 0: k_locate / k_point_shapes, else field_locate
+    FieldGrid grid{};                                   // !on_axis: the cell grid of the points and what their location needs
+    size_t sort_bytes = 0, locate_bytes = 0;
+    int n() const { return int(I.size()); }
 };
 
 Points gather_points(const remo_batch *b) {
     Points p;
+    const int dim = p.dim = b->dim;
+    auto add = [&](const std::vector<double> &from, int q, double I, int rhs, int slot) {
+        p.P.insert(p.P.end(), from.begin() + size_t(q) * dim, from.begin() + size_t(q + 1) * dim);
+        p.I.push_back(I); p.rhs.push_back(rhs); p.eval_slot.push_back(slot);
+    };
     for (int c0 = 0; c0 < b->n_rhs; c0 += REMO_MAX_RHS) {
-        p.chunk_begin.push_back(int32_t(p.z.size()));
+        p.chunk_begin.push_back(int32_t(p.n()));
         const int c1 = std::min(b->n_rhs, c0 + REMO_MAX_RHS);
         for (int r = c0; r < c1; ++r)
-            for (int q = b->src_ptr[r]; q < b->src_ptr[r + 1]; ++q) {
-                p.z.push_back(b->src_z[q]); p.I.push_back(b->src_I[q]); p.rhs.push_back(r - c0); p.eval_slot.push_back(-1);
-            }
+            for (int q = b->src_ptr[r]; q < b->src_ptr[r + 1]; ++q) add(b->src_p, q, b->src_I[q], r - c0, -1);
         for (int r = c0; r < c1; ++r)
-            for (int q = b->eval_ptr[r]; q < b->eval_ptr[r + 1]; ++q) {
-                p.z.push_back(b->eval_z[q]); p.I.push_back(0.0); p.rhs.push_back(r - c0); p.eval_slot.push_back(q);
-            }
-        if (const remo_sens_request *sn = b->sens)   // J_j = sum_i w_i u(z_i): the functionals' points are read like evaluation points
+            for (int q = b->eval_ptr[r]; q < b->eval_ptr[r + 1]; ++q) add(b->eval_p, q, 0.0, r - c0, q);
+        if (const remo_sens_request *sn = b->sens)   // J_j = sum_i w_i u(p_i): the functionals' points are read like evaluation points
             for (int j = 0; j < sn->n_fun; ++j)
                 if (sn->fun_rhs[j] >= c0 && sn->fun_rhs[j] < c1)
                     for (int q = sn->fun_ptr[j]; q < sn->fun_ptr[j + 1]; ++q) {
-                        p.fun_reads.emplace_back(int32_t(p.z.size()), q);
-                        p.z.push_back(sn->fun_z[q]); p.I.push_back(0.0); p.rhs.push_back(sn->fun_rhs[j] - c0); p.eval_slot.push_back(-1);
+                        p.fun_reads.emplace_back(int32_t(p.n()), q);
+                        add(b->fun_p, q, 0.0, sn->fun_rhs[j] - c0, -1);
                     }
     }
     p.forward_chunks = int(p.chunk_begin.size());
-    if (const remo_sens_request *sn = b->sens)   // adjoint right-hand sides g_j = sum_i w_i phi(z_i): the same points as sources of strength w_i
+    if (const remo_sens_request *sn = b->sens)   // adjoint right-hand sides g_j = sum_i w_i phi(p_i): the same points as sources of strength w_i
         for (int a0 = 0; a0 < sn->n_fun; a0 += REMO_MAX_RHS) {
-            p.chunk_begin.push_back(int32_t(p.z.size()));
+            p.chunk_begin.push_back(int32_t(p.n()));
             for (int j = a0; j < std::min(sn->n_fun, a0 + REMO_MAX_RHS); ++j)
-                for (int q = sn->fun_ptr[j]; q < sn->fun_ptr[j + 1]; ++q) {
-                    p.z.push_back(sn->fun_z[q]); p.I.push_back(sn->fun_w[q]); p.rhs.push_back(j - a0); p.eval_slot.push_back(-1);
-                }
+                for (int q = sn->fun_ptr[j]; q < sn->fun_ptr[j + 1]; ++q) add(b->fun_p, q, sn->fun_w[q], j - a0, -1);
         }
-    p.chunk_begin.push_back(int32_t(p.z.size()));
-    p.found_init.assign(p.z.size(), INT_MAX);
+    p.chunk_begin.push_back(int32_t(p.n()));
+    p.found_init.assign(size_t(p.n()), INT_MAX);
+    for (int q = 0; q < p.n(); ++q)
+        for (int k = 0; k + 1 < dim; ++k)
+            if (p.P[size_t(q) * dim + k] != 0.0) p.on_axis = false;
+    if (p.on_axis) {
+        p.z.resize(size_t(p.n()));
+        for (int q = 0; q < p.n(); ++q) p.z[size_t(q)] = p.P[size_t(q) * dim + dim - 1];
+    }
     return p;
+}
+
+// host part of the location of points off the axis (field.hip): the cell grid over their box and the bytes of its buffers
+void plan_point_location(const remo_batch *b, Points &p) {
+    if (p.on_axis || p.n() == 0) return;
+    p.grid = field_grid(p.dim, p.n(), p.P.data());
+    p.sort_bytes = field_sort_bytes(p.n(), p.grid.ncell);
+    p.locate_bytes = field_locate_bytes(p.n(), b->nt, p.grid.ncell, p.sort_bytes);
 }
 
 // ---- what the batch will build, and the arena it needs ------------------------------------------------------------------------
@@ -98,6 +117,7 @@ struct Plan {
     bool want_patch = false, want_amg = false;
     int64_t vertex_block_above = -1;    // build_symbolic_gpu: element count above which only the P1 block gets a pattern
     size_t field_bytes = 0;             // remo_solve_batch_field: everything field_take takes (Field::bytes)
+    size_t point_locate_bytes = 0;      // points off the axis: their coordinates beyond z and the buffers of field_locate (take_points)
     size_t arena_bytes = 0;
 };
 
@@ -117,6 +137,7 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
         need += patch_arena_bytes(nt, ndof_max, p.kmax) + (size_t(nt) * 21 + 64) * kmax * 8;
     need += size_t(kMaxPartialBlocks) * 8 * 8 * 3;                   // part_pq, part_rz (rz0, d_bound and the flags ride on the slack below)
     need += size_t(npts) * (N + 8) * 8;                              // d_pz, d_pI, d_prhs, d_found, d_phi, d_fint, d_out
+    need += p.point_locate_bytes;                                    // off the axis: d_pz holds dim coordinates; the location's buffers
     need += p.field_bytes;                                           // field sections: d_pts, d_found, d_elem, d_u, d_grad, d_J and the location's buffers
     need += (1 << 20);                                               // alignment of every take + the small buffers
     if (p.x_ev_only) {   // slots + values instead of x
@@ -149,10 +170,11 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
     return need;
 }
 
-Plan plan_batch(const remo_batch *b, const remo_opts_t &o, int npts, size_t field_bytes) {
+Plan plan_batch(const remo_batch *b, const remo_opts_t &o, const Points &pts, size_t field_bytes) {
     Plan p;
-    const int dim = b->dim;
+    const int dim = b->dim, npts = pts.n();
     p.field_bytes = field_bytes;
+    p.point_locate_bytes = pts.on_axis ? 0 : align_up(size_t(npts + 1) * dim * 8) + align_up(pts.locate_bytes);
     p.kmax = std::min<int>(std::max(b->n_rhs, b->sens ? b->sens->n_fun : 0), REMO_MAX_RHS);   // the adjoint columns run through the same buffers
     // one-shot fp64 solve: no x, only the values the evaluation points read (PcgBuffersT::x_ev); the debug forms of the update
     // (key 25 = 0 writes x there) and the mixed mode's refinement (x64 += x32) need the whole block
@@ -306,17 +328,20 @@ struct DevicePoints {
     double *d_phi = nullptr, *d_fint = nullptr, *d_out = nullptr;
     int64_t *d_ev_at = nullptr;   // x_ev_only: slots and values of the solution the points read
     double *d_x_ev = nullptr;
+    FieldLocate loc{};            // points off the axis: d_pz holds dim coordinates per point, and the buffers of field_locate
 };
 
-DevicePoints take_points(const Run &r, const Plan &plan, int npts) {
+DevicePoints take_points(const Run &r, const Plan &plan, const Points &pts) {
     remo_ctx *ctx = r.ctx;
+    const int npts = pts.n();
     DevicePoints p;
     p.npts = npts;
-    p.d_pz = ctx->take<double>(npts + 1); p.d_pI = ctx->take<double>(npts + 1);
+    p.d_pz = ctx->take<double>(pts.on_axis ? size_t(npts + 1) : size_t(npts + 1) * r.dim); p.d_pI = ctx->take<double>(npts + 1);
     p.d_prhs = ctx->take<int32_t>(npts + 1); p.d_found = ctx->take<int32_t>(npts + 1);
     p.d_phi = ctx->take<double>(size_t(npts + 1) * r.N); p.d_fint = ctx->take<double>(npts + 1); p.d_out = ctx->take<double>(npts + 1);
     p.d_ev_at = plan.x_ev_only ? ctx->take<int64_t>(size_t(npts + 1) * r.N) : nullptr;
     p.d_x_ev = plan.x_ev_only ? ctx->take<double>(size_t(npts + 1) * r.N) : nullptr;
+    if (!pts.on_axis && npts > 0) p.loc = field_locate_carve(ctx->take<char>(pts.locate_bytes), npts, r.b->nt, pts.grid.ncell, pts.sort_bytes);
     return p;
 }
 
@@ -324,18 +349,26 @@ void upload_points(const Run &r, const Points &pts, const DevicePoints &dp) {
     const int npts = dp.npts;
     HIP_TRY(hipMemsetAsync(r.ctx->d_err, 0, sizeof(int32_t), r.s));
     if (npts > 0) {
-        HIP_TRY(hipMemcpyAsync(dp.d_pz, pts.z.data(), sizeof(double) * npts, hipMemcpyHostToDevice, r.s));
+        if (pts.on_axis) HIP_TRY(hipMemcpyAsync(dp.d_pz, pts.z.data(), sizeof(double) * npts, hipMemcpyHostToDevice, r.s));
+        else HIP_TRY(hipMemcpyAsync(dp.d_pz, pts.P.data(), sizeof(double) * size_t(npts) * r.dim, hipMemcpyHostToDevice, r.s));
         HIP_TRY(hipMemcpyAsync(dp.d_pI, pts.I.data(), sizeof(double) * npts, hipMemcpyHostToDevice, r.s));
         HIP_TRY(hipMemcpyAsync(dp.d_prhs, pts.rhs.data(), sizeof(int32_t) * npts, hipMemcpyHostToDevice, r.s));
         HIP_TRY(hipMemcpyAsync(dp.d_found, pts.found_init.data(), sizeof(int32_t) * npts, hipMemcpyHostToDevice, r.s));
     }
 }
 
-// point location + shapes (all points at once)
-void locate_points(const Run &r, const DevicePoints &dp) {
+// point location + shapes (all points at once).  Points on the axis: the element pass over the axis' elements; a batch with a
+// point off it: all its points through the cell grid of the field sections (same tie rule, same tolerances).
+void locate_points(const Run &r, const Points &pts, const DevicePoints &dp) {
     const remo_batch *b = r.b;
     const DeviceSymbolic &sy = b->sym;
+    r.ctx->point_location = pts.on_axis ? 0 : 1;
     if (dp.npts <= 0) return;
+    if (!pts.on_axis) {
+        field_locate(r.dim, b->nt, b->d_coords, sy.conn, dp.npts, dp.d_pz, pts.grid, dp.loc, dp.d_found, r.s);
+        launch_point_shapes_at(r.dim, dp.npts, dp.d_pz, dp.d_found, b->d_coords, sy.conn, dp.d_phi, r.ctx->d_err, r.s);
+        return;
+    }
     for (int q0 = 0; q0 < dp.npts; q0 += kMaxPoints)
         launch_locate(r.dim, b->nt, b->d_coords, sy.conn, std::min(kMaxPoints, dp.npts - q0), dp.d_pz + q0, dp.d_found + q0, r.s);
     launch_point_shapes(r.dim, dp.npts, dp.d_pz, dp.d_found, b->d_coords, sy.conn, dp.d_phi, r.ctx->d_err, r.s);
@@ -913,12 +946,13 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         hipStream_t s = r.s;
 
         // ---- host side: points, plan, arena -----------------------------------------------------------------------
-        const Points points = gather_points(b);
+        Points points = gather_points(b);
         const int npts = points.n();
-        for (double z : points.z)
-            if (!std::isfinite(z)) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
+        for (double c : points.P)
+            if (!std::isfinite(c)) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
+        plan_point_location(b, points);
         Field fld = field_plan(b);
-        const Plan plan = plan_batch(b, o, npts, fld.bytes(b->dim));
+        const Plan plan = plan_batch(b, o, points, fld.bytes(b->dim));
         ctx->reserve(plan.arena_bytes);
 
         // ---- numbering, then every buffer of the solve (arena order), then the device work up to the one sync --------
@@ -926,7 +960,7 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         System sys = take_system(r, plan);
         Solve sv;
         take_pcg_buffers(r, plan, sys, sv);
-        const DevicePoints dp = take_points(r, plan, npts);
+        const DevicePoints dp = take_points(r, plan, points);
         field_take(r, fld);
         prepare_progress(r, sv.buf);
         HIP_TRY(hipEventRecord(ctx->ev[0], s));
@@ -934,7 +968,7 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         HIP_TRY(hipEventRecord(ctx->ev[1], s));
         assemble_system(r, sys);
         HIP_TRY(hipEventRecord(ctx->ev[2], s));
-        locate_points(r, dp);
+        locate_points(r, points, dp);
         field_locate_points(r, fld);
         HIP_TRY(hipEventRecord(ctx->ev[3], s));
         VertexBlock vb;

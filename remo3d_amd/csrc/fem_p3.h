@@ -200,6 +200,15 @@ template <int DIM> REMO_HD bool barycentrics(const double *X, const double *P, d
     return true;
 }
 
+// Shape values phi[NLD] at point P (DIM coords) of the element with sorted vertices X: what a point source or a reading anywhere in
+// the element needs (k_point_shapes_at, remo_host_point_shapes).  Returns false if degenerate (phi untouched).
+template <int DIM> REMO_HD bool point_shapes(const double *X, const double *P, double *phi) {
+    double l[DIM + 1];
+    if (!barycentrics<DIM>(X, P, l)) return false;
+    shape<DIM>(l, phi);
+    return true;
+}
+
 // host: exact reference tensors (ref_tables.cpp)
 const double *ref_tables(int dim);  // [NTERM][NLD][NLD], exact integrals
 const double *ref_tables2_rule4();   // 2D tensors by the 6-point degree-4 rule instead (remo_opts_t.quadrature = 1)

@@ -203,6 +203,9 @@ void launch_locate(int dim, int64_t nt, const double *coords, const int32_t *con
                    int32_t *found, hipStream_t s);
 void launch_point_shapes(int dim, int npts, const double *pz, const int32_t *found, const double *coords,
                          const int32_t *conn, double *phi, int32_t *errflag, hipStream_t s);
+// shape values at points anywhere in the mesh: pp[npts * dim] full coordinates, found[] from field_locate (field.h)
+void launch_point_shapes_at(int dim, int npts, const double *pp, const int32_t *found, const double *coords,
+                            const int32_t *conn, double *phi, int32_t *errflag, hipStream_t s);
 // f[n*k] += I * phi at sources (with the condensed-bubble fold in 2D); bubble loads kept in fint[npts]
 void launch_build_rhs(int dim, bool condense, int npts, const int32_t *pt_rhs, const double *pt_I,
                       const int32_t *found, const double *phi, const int32_t *eldof, const double *C,

@@ -1057,6 +1057,45 @@ void launch_point_shapes(int dim, int npts, const double *pz, const int32_t *fou
         hipLaunchKernelGGL(k_point_shapes<3>, dim3(grid), dim3(64), 0, s, npts, pz, found, coords, conn, phi, errflag);
 }
 
+// The same for points anywhere in the mesh (remo_solve_job): P[q] holds DIM coordinates, found[q] the element field_locate gave it.
+template <int DIM>
+__global__ void __launch_bounds__(64) k_point_shapes_at(int npts, const double *__restrict__ pp, const int32_t *__restrict__ found,
+                                                        const double *__restrict__ coords, const int32_t *__restrict__ conn,
+                                                        double *__restrict__ phi, int32_t *errflag) {
+    constexpr int NB = DIM + 1, N = P3<DIM>::NLD;
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= npts) return;
+    const int32_t t = found[q];
+    double ph[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) ph[i] = 0.0;
+    if (t == INT_MAX) {
+        atomicOr(errflag, 2);
+    } else {
+        double X[NB * DIM], P[DIM];
+#pragma unroll
+        for (int a = 0; a < NB; ++a) {
+            const int64_t v = conn[int64_t(t) * NB + a];
+#pragma unroll
+            for (int k = 0; k < DIM; ++k) X[a * DIM + k] = coords[v * DIM + k];
+        }
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) P[k] = pp[int64_t(q) * DIM + k];
+        point_shapes<DIM>(X, P, ph);
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) phi[int64_t(q) * N + i] = ph[i];
+}
+
+void launch_point_shapes_at(int dim, int npts, const double *pp, const int32_t *found, const double *coords, const int32_t *conn,
+                            double *phi, int32_t *errflag, hipStream_t s) {
+    const int grid = (npts + 63) / 64;
+    if (dim == 2)
+        hipLaunchKernelGGL(k_point_shapes_at<2>, dim3(grid), dim3(64), 0, s, npts, pp, found, coords, conn, phi, errflag);
+    else
+        hipLaunchKernelGGL(k_point_shapes_at<3>, dim3(grid), dim3(64), 0, s, npts, pp, found, coords, conn, phi, errflag);
+}
+
 // One thread per source: f[dof][rhs] += I phi (a handful of points: atomics are irrelevant here).
 template <int DIM, bool CONDENSE>
 __global__ void k_build_rhs(int npts, const int32_t *__restrict__ pt_rhs, const double *__restrict__ pt_I,

@@ -3,7 +3,9 @@
 // the CPU hooks remo_host.cpp.
 #include <limits.h>
 
+#include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <type_traits>
 
@@ -96,10 +98,19 @@ void remo_ctx_destroy(remo_ctx_t *ctx) {
 const char *remo_last_error(remo_ctx_t *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
 
+// n points as the batch keeps them, dim coordinates each: from full coordinates (full) or from axis positions z, (0, .., z)
+static void store_points(std::vector<double> &to, const double *from, int n, int dim, bool full) {
+    if (n <= 0) { to.clear(); return; }
+    if (full) { to.assign(from, from + size_t(n) * dim); return; }
+    to.assign(size_t(n) * dim, 0.0);
+    for (int q = 0; q < n; ++q) to[size_t(q) * dim + dim - 1] = from[q];
+}
+
 // tensor: sigma holds n_mat upper triangles (remo_solve_batch_tensor) instead of n_mat scalars
+// full: src_z / eval_z hold dim coordinates per point (remo_solve_job) instead of axis positions
 static int batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
                         const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
-                        const double *eval_z, remo_batch_t **out, bool pooled, bool tensor = false) {
+                        const double *eval_z, remo_batch_t **out, bool pooled, bool tensor = false, bool full = false) {
     if (!ctx) return REMO_ERR_ARG;
     if (!mesh || !sigma || !out || n_mat <= 0 || n_rhs <= 0 || !src_ptr || !eval_ptr)
         return fail(ctx, REMO_ERR_ARG, "null or empty argument");
@@ -116,6 +127,12 @@ static int batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat,
     const int dim = mesh->dim, nb = dim + 1;
     for (int64_t i = 0; i < mesh->n_nodes * dim; ++i)
         if (!std::isfinite(mesh->coords[i])) return fail(ctx, REMO_ERR_MESH, "non-finite coordinate");
+    if (full) {   // the job entries: before any device work
+        for (int64_t i = 0; i < int64_t(src_ptr[n_rhs]) * dim; ++i)
+            if (!std::isfinite(src_z[i])) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
+        for (int64_t i = 0; i < int64_t(eval_ptr[n_rhs]) * dim; ++i)
+            if (!std::isfinite(eval_z[i])) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
+    }
     const int ncomp = tensor ? ((dim == 2) ? 3 : 6) : 1;
     if (tensor) {
         for (int i = 0; i < n_mat; ++i)
@@ -134,9 +151,9 @@ static int batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat,
         b->n_rhs = n_rhs;
         b->src_ptr.assign(src_ptr, src_ptr + n_rhs + 1);
         b->eval_ptr.assign(eval_ptr, eval_ptr + n_rhs + 1);
-        b->src_z.assign(src_z, src_z + src_ptr[n_rhs]);
-        b->src_I.assign(src_I, src_I + src_ptr[n_rhs]);
-        b->eval_z.assign(eval_z, eval_z + eval_ptr[n_rhs]);
+        store_points(b->src_p, src_z, src_ptr[n_rhs], dim, full);
+        if (src_ptr[n_rhs] > 0) b->src_I.assign(src_I, src_I + src_ptr[n_rhs]);
+        store_points(b->eval_p, eval_z, eval_ptr[n_rhs], dim, full);
         hipStream_t s = ctx->stream;
         b->pooled = pooled;
         size_t pool_at = 0;
@@ -208,12 +225,12 @@ int remo_batch_fetch(remo_ctx_t *ctx, remo_batch_t *b, double *u_out) {
 
 static int solve_batch(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
                        const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
-                       const double *eval_z, double *u_out, const remo_opts_t *opts, remo_stats_t *stats, bool tensor) {
+                       const double *eval_z, double *u_out, const remo_opts_t *opts, remo_stats_t *stats, bool tensor, bool full = false) {
     if (!ctx) return REMO_ERR_ARG;
     if (u_out && eval_ptr && n_rhs > 0)
         for (int i = 0; i < eval_ptr[n_rhs]; ++i) u_out[i] = std::nan("");
     remo_batch_t *b = nullptr;
-    int rc = batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, &b, true, tensor);     // inputs into the context's pool: no hipMalloc / hipFree per batch
+    int rc = batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, &b, true, tensor, full);     // inputs into the context's pool: no hipMalloc / hipFree per batch
     if (rc != REMO_OK) return rc;
     b->eval_only = true;
     rc = remo_batch_run(ctx, b, opts, stats);
@@ -241,7 +258,7 @@ static int solve_batch_sens(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_
                             const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
                             const double *fun_z, const double *fun_w, double *J_out, double *dJ_out, const remo_opts_t *opts,
                             remo_stats_t *stats, bool tensor, bool groups = false, int32_t n_group = 0, const int32_t *group = nullptr,
-                            double *dJg_out = nullptr, remo_warm *warm = nullptr) {
+                            double *dJg_out = nullptr, remo_warm *warm = nullptr, bool full = false) {
     if (!ctx) return REMO_ERR_ARG;
     // whatever goes wrong below, the object does not keep solutions of an earlier call (remo_batch_run labels it again on success)
     struct WarmGuard {
@@ -279,11 +296,15 @@ static int solve_batch_sens(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_
         if (fun_ptr[n_fun] > 0 && (!fun_z || !fun_w)) return fail(ctx, REMO_ERR_ARG, "functional arrays missing");
         for (int q = 0; q < fun_ptr[n_fun]; ++q)
             if (!std::isfinite(fun_w[q])) return fail(ctx, REMO_ERR_ARG, "non-finite functional weight");
+        if (full && mesh && (mesh->dim == 2 || mesh->dim == 3))
+            for (int64_t i = 0; i < int64_t(fun_ptr[n_fun]) * mesh->dim; ++i)
+                if (!std::isfinite(fun_z[i])) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
     }
     remo_batch_t *b = nullptr;
-    int rc = batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, &b, true, tensor);
+    int rc = batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, &b, true, tensor, full);
     if (rc != REMO_OK) return rc;
-    const remo_sens_request rq{n_fun, fun_rhs, fun_ptr, fun_z, fun_w, J_out, dJ_out, groups ? n_group : 0, groups ? group : nullptr, groups ? dJg_out : nullptr};
+    const remo_sens_request rq{n_fun, fun_rhs, fun_ptr, fun_w, J_out, dJ_out, groups ? n_group : 0, groups ? group : nullptr, groups ? dJg_out : nullptr};
+    store_points(b->fun_p, fun_z, n_fun > 0 ? fun_ptr[n_fun] : 0, b->dim, full);
     b->sens = &rq;
     b->warm = warm;
     b->eval_only = true;
@@ -354,7 +375,8 @@ int remo_solve_batch_sens_groups_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh
 static int solve_batch_field(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
                              const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
                              const double *eval_z, double *u_out, int32_t n_pts, const double *pts, int32_t n_frhs, const int32_t *field_rhs,
-                             double *u_f, double *grad_f, double *J_f, int32_t *elem_f, const remo_opts_t *opts, remo_stats_t *stats, bool tensor) {
+                             double *u_f, double *grad_f, double *J_f, int32_t *elem_f, const remo_opts_t *opts, remo_stats_t *stats, bool tensor,
+                             bool full = false) {
     if (!ctx) return REMO_ERR_ARG;
     const int dim = (mesh && mesh->dim == 2) ? 2 : 3;
     auto nan_fill = [&]() {
@@ -377,7 +399,7 @@ static int solve_batch_field(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n
         for (int64_t i = 0; i < int64_t(n_pts) * mesh->dim; ++i)
             if (!std::isfinite(pts[i])) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
     remo_batch_t *b = nullptr;
-    int rc = batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, &b, true, tensor);
+    int rc = batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, &b, true, tensor, full);
     if (rc != REMO_OK) return rc;
     const remo_field_request rq{n_pts, pts, n_frhs, field_rhs, u_f, grad_f, J_f, elem_f};
     b->field = &rq;
@@ -404,6 +426,68 @@ int remo_solve_batch_field_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int3
                                   remo_stats_t *stats) {
     return solve_batch_field(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_pts, pts, n_frhs, field_rhs, u_f,
                              grad_f, J_f, elem_f, opts, stats, true);
+}
+
+// remo_solve_job / remo_batch_create_job: the job as this library knows it - the caller's leading `size` bytes, the rest zero.
+static int read_job(remo_ctx_t *ctx, const remo_job_t *job, remo_job_t &j) {
+    if (!ctx) return REMO_ERR_ARG;
+    if (!job) return fail(ctx, REMO_ERR_ARG, "null job");
+    const size_t size = job->size;
+    if (size < offsetof(remo_job_t, n_fun)) return fail(ctx, REMO_ERR_ARG, "remo_job_t.size is smaller than the part every job has (through u_out)");
+    std::memset(&j, 0, sizeof j);
+    std::memcpy(&j, job, std::min(size, sizeof j));
+    const unsigned char *raw = reinterpret_cast<const unsigned char *>(job);
+    for (size_t i = sizeof j; i < size; ++i)   // a newer caller: what this library does not know must not be asked for
+        if (raw[i]) return fail(ctx, REMO_ERR_ARG, "remo_job_t.size is larger than this library's struct and the tail is not zero");
+    if (j.tensor != 0 && j.tensor != 1) return fail(ctx, REMO_ERR_ARG, "remo_job_t.tensor must be 0 or 1");
+    return REMO_OK;
+}
+
+// every output the job names: NaN, elem_f -1 (sizes from the job's own counts; arrays that cannot be sized are left alone)
+static void job_nan_fill(const remo_mesh_t *mesh, const remo_job_t &j) {
+    const int dim = (mesh && mesh->dim == 2) ? 2 : 3;
+    const size_t ncomp = j.tensor ? ((dim == 2) ? 3 : 6) : 1;
+    auto fill = [](double *a, size_t n) { for (size_t i = 0; a && i < n; ++i) a[i] = std::nan(""); };
+    if (j.eval_ptr && j.n_rhs > 0 && j.eval_ptr[j.n_rhs] > 0) fill(j.u_out, size_t(j.eval_ptr[j.n_rhs]));
+    if (j.n_fun > 0) {
+        fill(j.J_out, size_t(j.n_fun));
+        if (j.n_mat > 0) fill(j.dJ_out, size_t(j.n_fun) * size_t(j.n_mat) * ncomp);
+        if (j.n_group > 0) fill(j.dJg_out, size_t(j.n_fun) * size_t(j.n_group) * ncomp);
+    }
+    if (j.n_pts > 0) {
+        const size_t nv = (j.n_frhs > 0) ? size_t(j.n_pts) * size_t(j.n_frhs) : 0;
+        fill(j.u_f, nv); fill(j.grad_f, nv * dim); fill(j.J_f, nv * dim);
+        for (int32_t i = 0; j.elem_f && i < j.n_pts; ++i) j.elem_f[i] = -1;
+    }
+}
+
+int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, const remo_opts_t *opts, remo_stats_t *stats) {
+    remo_job_t j;
+    int rc = read_job(ctx, job, j);
+    const bool fun = rc == REMO_OK && j.n_fun != 0, field = rc == REMO_OK && (j.n_pts != 0 || j.n_frhs != 0);
+    if (rc == REMO_OK && fun && field) rc = fail(ctx, REMO_ERR_ARG, "field points together with functionals: two calls");
+    if (rc == REMO_OK && !fun && (j.n_group != 0 || j.warm)) rc = fail(ctx, REMO_ERR_ARG, "groups or a warm object without functionals");
+    if (rc != REMO_OK) {
+        if (ctx && job && job->size >= offsetof(remo_job_t, n_fun)) {   // a job that could be read: its outputs as the entries leave them on an error
+            job_nan_fill(mesh, j);
+            if (j.warm) remo_warm_clear(j.warm);
+        }
+        return rc;
+    }
+    if (field)
+        return solve_batch_field(ctx, mesh, j.n_mat, j.sigma, j.n_rhs, j.src_ptr, j.src_p, j.src_I, j.eval_ptr, j.eval_p, j.u_out, j.n_pts, j.pts, j.n_frhs,
+                                 j.field_rhs, j.u_f, j.grad_f, j.J_f, j.elem_f, opts, stats, j.tensor != 0, true);
+    if (fun)
+        return solve_batch_sens(ctx, mesh, j.n_mat, j.sigma, j.n_rhs, j.src_ptr, j.src_p, j.src_I, j.eval_ptr, j.eval_p, j.u_out, j.n_fun, j.fun_rhs,
+                                j.fun_ptr, j.fun_p, j.fun_w, j.J_out, j.dJ_out, opts, stats, j.tensor != 0, j.n_group != 0, j.n_group, j.group, j.dJg_out,
+                                j.warm, true);
+    return solve_batch(ctx, mesh, j.n_mat, j.sigma, j.n_rhs, j.src_ptr, j.src_p, j.src_I, j.eval_ptr, j.eval_p, j.u_out, opts, stats, j.tensor != 0, true);
+}
+
+int remo_batch_create_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, remo_batch_t **out) {
+    remo_job_t j;
+    if (int rc = read_job(ctx, job, j)) return rc;
+    return batch_create(ctx, mesh, j.n_mat, j.sigma, j.n_rhs, j.src_ptr, j.src_p, j.src_I, j.eval_ptr, j.eval_p, out, false, j.tensor != 0, true);
 }
 
 int remo_batch_field(remo_ctx_t *ctx, remo_batch_t *b, int32_t rhs, int32_t n_pts, const double *pts, double *u, double *grad, double *J,

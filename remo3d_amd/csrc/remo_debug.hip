@@ -428,4 +428,6 @@ int remo_debug_field_timing(remo_ctx_t *ctx, double *out2) {
     return REMO_OK;
 }
 
+int remo_debug_point_location(remo_ctx_t *ctx) { return ctx ? ctx->point_location : REMO_ERR_ARG; }
+
 }  // extern "C"

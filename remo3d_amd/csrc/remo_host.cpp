@@ -81,6 +81,12 @@ int remo_host_field_element(int32_t dim, const double *X, const double *sigma_te
     return ok ? REMO_OK : REMO_ERR_MESH;
 }
 
+int remo_host_point_shapes(int32_t dim, const double *X, const double *point, double *phi_out) {
+    if ((dim != 2 && dim != 3) || !X || !point || !phi_out) return REMO_ERR_ARG;
+    const bool ok = (dim == 2) ? point_shapes<2>(X, point, phi_out) : point_shapes<3>(X, point, phi_out);
+    return ok ? REMO_OK : REMO_ERR_MESH;
+}
+
 double remo_host_factor_error(void) { return ref_factors3_error(); }
 
 int remo_host_symbolic(const remo_mesh_t *mesh, int32_t condense, int64_t *sizes, int32_t *rowptr, int32_t *col, int32_t *freeid) {

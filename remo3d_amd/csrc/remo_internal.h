@@ -93,6 +93,7 @@ struct remo_ctx {
     double sens_group_ms[4] = {};            // last remo_solve_batch_sens_groups: group order; with time_kernels also the material pass, the per-element pass and the group sums, each over all functionals (remo_debug_sens_group_timing)
     double field_ms[2] = {};                 // last remo_solve_batch_field / remo_batch_field: HIP-event time of the location of the points and of the evaluation launches (remo_debug_field_timing)
     hipEvent_t fev[4] = {};                  // their events, created by the first use
+    int point_location = 0;                  // last remo_batch_run: 0 = axis kernels, 1 = cell grid (remo_debug_point_location)
     remo::PcgProgress *progress = nullptr;  // mapped, coherent host memory
     remo::PcgProgress *progress_dev = nullptr;
     int progress_len = 0;
@@ -130,12 +131,12 @@ struct remo_ctx {
     }
 };
 
-// What remo_solve_batch_sens adds to a batch: linear functionals J_j = sum_i w[i] u_rhs[j](z[i]) and where their values and
-// derivatives go (host pointers of the caller, valid for the duration of the call only).
+// What remo_solve_batch_sens adds to a batch: linear functionals J_j = sum_i w[i] u_rhs[j](p[i]) and where their values and
+// derivatives go (host pointers of the caller, valid for the duration of the call only).  The points are the batch's fun_p.
 struct remo_sens_request {
     int n_fun = 0;
     const int32_t *fun_rhs = nullptr, *fun_ptr = nullptr;
-    const double *fun_z = nullptr, *fun_w = nullptr;
+    const double *fun_w = nullptr;
     double *J_out = nullptr, *dJ_out = nullptr;
     // remo_solve_batch_sens_groups: the caller's group of every element (host array, checked by the entry) and where the sums go
     int32_t n_group = 0;
@@ -164,7 +165,8 @@ struct remo_batch {
     // points: per chunk [sources..., evals...]
     int n_rhs = 0;
     std::vector<int32_t> src_ptr, eval_ptr;
-    std::vector<double> src_z, src_I, eval_z;
+    std::vector<double> src_p, src_I, eval_p;   // points: dim coordinates each; the axis entries store (0, .., z)
+    std::vector<double> fun_p;                  // the points of `sens`'s functionals, likewise
     // resident device inputs (everything the path reads is in HBM before remo_batch_run)
     double *d_coords = nullptr, *d_sigma = nullptr;
     int32_t *d_mat = nullptr, *d_conn = nullptr, *d_bconn = nullptr;

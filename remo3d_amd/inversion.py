@@ -176,14 +176,14 @@ def posterior(jacobian, weights, L=None, beta=0.0, beta_ref=0.0):
 # ---- what a sweep hands the next ----------------------------------------------------------------------------------------------
 def sweep_signature(plan) -> tuple:
     """Everything the batches' meshes and the sizes of their systems depend on: depths, batch size (through the batches), domain
-    radius and dip; the tools; the mesh settings; the geometric columns of both tables (TOP, BOTTOM, RDFZ; depth and caliper).
-    Resistivities are not in it."""
+    radius, dip and the tool's eccentricity; the tools; the mesh settings; the geometric columns of both tables (TOP, BOTTOM, RDFZ;
+    depth and caliper).  Resistivities are not in it."""
     model = plan.model
     def raw(a):
         return np.ascontiguousarray(np.asarray(a, dtype=float)).tobytes()
     tools = tuple((name, raw(t)) for name, t in model.tools.items())
     batches = tuple(raw(b.electrodes) for b in plan.batches)
-    return (raw(plan.depths), raw(plan.simulation_depths), batches, float(plan.domain_radius), float(model.dip_deg), tools,
+    return (raw(plan.depths), raw(plan.simulation_depths), batches, float(plan.domain_radius), float(model.dip_deg), float(getattr(plan, "eccentricity", 0.0)), tools,
             plan.mesh_scale, bool(plan.netgen_path), None if plan.default_provider else id(plan.provider),
             raw(model.formation_model[:, :3]), raw(model.borehole_model[:, :2]))
 

@@ -53,16 +53,24 @@ class Mesh:
         return int(self.conn.shape[0])
 
 
+def source_points(sources) -> list:
+    """(r, z) of every refinement centre: a number is a position z on the axis, a pair (r, z) a point at distance r from it (an
+    electrode of an eccentred tool; in the generating half plane of a revolved mesh, a ring)."""
+    return [(0.0, float(s)) if np.ndim(s) == 0 else (abs(float(s[0])), float(s[1])) for s in sources]
+
+
 def size_field(pts: np.ndarray, dim: int, sources_z: Sequence[float], scale: float = 1.0,
                h_axis: float = 0.1, h_src: float = 0.01) -> np.ndarray:
-    """Reference background mesh size at points (gmsh_functions.py:487-500 / 630-643)."""
+    """Reference background mesh size at points (gmsh_functions.py:487-500 / 630-643).  sources_z: axis positions, or (r, z)
+    points off the axis (source_points): the size grows with the distance from the point's own radius."""
     if dim == 2:
         rho = np.abs(pts[:, 0]); z = pts[:, 1]
     else:
         rho = np.hypot(pts[:, 0], pts[:, 1]); z = pts[:, 2]
     h = rho + h_axis
-    for zs in sources_z:
-        h = np.minimum(h, 0.5 * (rho * rho + (z - zs) ** 2) + h_src)
+    for rs, zs in source_points(sources_z):
+        d = rho - rs
+        h = np.minimum(h, 0.5 * (d * d + (z - zs) ** 2) + h_src)
     return scale * h
 
 
@@ -109,7 +117,7 @@ def _refine_tree(dim: int, R: float, sources_z, scale, h_axis, h_src, max_level:
         roots = np.array([[0, -1], [0, 0]], dtype=np.int64)
     else:
         roots = np.array([[ix, 0, iz] for ix in (-1, 0) for iz in (-1, 0)], dtype=np.int64)
-    src = np.asarray(list(sources_z), dtype=np.float64)
+    src = source_points(sources_z)
     leaves_o, leaves_l = [], []
     cells = roots
     for level in range(max_level + 1):
@@ -122,16 +130,19 @@ def _refine_tree(dim: int, R: float, sources_z, scale, h_axis, h_src, max_level:
         # 1.5: a body-centred cell of side s has edges s and 0.87 s and sides come in powers of two
         if dim == 2:
             rho_min = np.maximum(lo[:, 0], 0.0)
+            rho_max = hi[:, 0]
             zl, zh = lo[:, 1], hi[:, 1]
         else:
             dx = np.maximum(np.maximum(lo[:, 0], -hi[:, 0]), 0.0)
             dy = np.maximum(lo[:, 1], 0.0)
             rho_min = np.hypot(dx, dy)
+            rho_max = np.hypot(np.maximum(np.abs(lo[:, 0]), np.abs(hi[:, 0])), hi[:, 1])
             zl, zh = lo[:, 2], hi[:, 2]
         hmin = rho_min + h_axis
-        for zs in src:
+        for rs, zs in src:
             dz = np.maximum(np.maximum(zl - zs, zs - zh), 0.0)
-            hmin = np.minimum(hmin, 0.5 * (rho_min ** 2 + dz ** 2) + h_src)
+            dr = np.maximum(np.maximum(rho_min - rs, rs - rho_max), 0.0)     # rs = 0: rho_min
+            hmin = np.minimum(hmin, 0.5 * (dr ** 2 + dz ** 2) + h_src)
         hmin = np.minimum(scale * hmin, h_max)
         if layer_cap is not None:
             hmin = np.minimum(hmin, layer_cap.interval_min(zl, zh))
@@ -222,7 +233,8 @@ def make_mesh(dim: int, R: float = 50.0, sources_z: Sequence[float] = (0.0,), sc
               improve_passes: int = 6, interfaces: Sequence[np.ndarray] = (), layer_cap: Optional["LayerCap"] = None) -> Mesh:
     """Graded Delaunay mesh of the reference's half disc (dim=2) or half ball (dim=3).
 
-    sources_z : axis positions of current electrodes (refinement centres, snapped to vertices)
+    sources_z : axis positions of current electrodes (refinement centres, snapped to vertices); an entry may also be a pair
+                (r, z): a refinement centre at distance r from the axis (source_points; not snapped)
     scale     : global multiplier on the size field (scale < 1 -> finer mesh)
     material_fn(centroids[m, dim]) -> int array of material numbers (0-based); default all 0
     snap_z    : further axis positions to snap onto vertices (e.g. measuring electrodes)
@@ -269,14 +281,14 @@ def make_mesh(dim: int, R: float = 50.0, sources_z: Sequence[float] = (0.0,), sc
     n_iface = 0
     if dim == 2 and len(interfaces):
         ip, isp, isv = [], [], []          # points, local spacing, 1 for polyline vertices / junctions
-        src_list = [float(v) for v in sources_z]
+        src_list = source_points(sources_z)
         import math
 
         def h_at(r_, z_):                    # scalar copy of size_field (these loops are hot: pure Python floats)
             rho = abs(r_)
             hq = rho + h_axis
-            for zs in src_list:
-                hq = min(hq, 0.5 * (rho * rho + (z_ - zs) ** 2) + h_src)
+            for rs, zs in src_list:
+                hq = min(hq, 0.5 * ((rho - rs) * (rho - rs) + (z_ - zs) ** 2) + h_src)
             hq = min(scale * hq, h_max)
             if layer_cap is not None:
                 hq = min(hq, layer_cap.at(z_))
@@ -361,7 +373,8 @@ def make_mesh(dim: int, R: float = 50.0, sources_z: Sequence[float] = (0.0,), sc
     # snap electrodes onto the nearest axis vertex
     ax_idx = np.nonzero(on_axis & (~proj))[0]
     zc = dim - 1
-    for zs in list(sources_z) + list(snap_z):
+    on_axis_z = [zs for rs, zs in source_points(sources_z) if rs == 0.0] + list(snap_z)
+    for zs in on_axis_z:
         if abs(zs) >= R or ax_idx.size == 0:
             continue
         k = ax_idx[np.argmin(np.abs(pts[ax_idx, zc] - zs))]
@@ -397,7 +410,7 @@ def make_mesh(dim: int, R: float = 50.0, sources_z: Sequence[float] = (0.0,), sc
     # and they cost the Jacobi-PCG ~1.5x in steps.  Perturb the movable vertices of poor elements by a
     # fraction of their shortest edge and re-triangulate, a few passes (seeded, deterministic).
     pinned = on_sph | on_axis
-    for zs in list(sources_z) + list(snap_z):
+    for zs in on_axis_z:
         if ax_idx.size:
             pinned[ax_idx[np.argmin(np.abs(pts[ax_idx, zc] - zs))]] = True
     for _ in range(improve_passes if dim == 3 else 0):
@@ -440,7 +453,7 @@ def make_mesh(dim: int, R: float = 50.0, sources_z: Sequence[float] = (0.0,), sc
     cent = pts[conn].mean(1)
     mat = np.zeros(len(conn), dtype=np.int32) if material_fn is None else np.asarray(material_fn(cent), dtype=np.int32)
     exact = (np.pi * R * R / 2) if dim == 2 else (2.0 / 3.0 * np.pi * R ** 3)
-    meta = dict(R=R, scale=scale, seed=seed, sources_z=[float(s) for s in sources_z],
+    meta = dict(R=R, scale=scale, seed=seed, sources_z=[zs for _, zs in source_points(sources_z)],
                 volume=float(vol.sum()), volume_exact=float(exact), min_quality=float(qual.min()),
                 max_valence=int(valence), n_interface_points=int(n_iface), node_h=node_h, node_iface=node_iface)
     return Mesh(dim, np.ascontiguousarray(pts), np.ascontiguousarray(conn.astype(np.int32)),
@@ -677,7 +690,8 @@ def _revolve_triangulation(p2: np.ndarray, tri: np.ndarray, m: int, kappa: float
 
 def make_mesh_3d_conforming(R: float, local_formation_geometry: np.ndarray, local_borehole_geometry: np.ndarray, dip_rad: float,
                             sources_z: Sequence[float] = (0.0,), snap_z: Sequence[float] = (), scale: float = 1.0, seed: int = 0,
-                            layer_cap: Optional["LayerCap"] = None, sectors: int = 6, exact_radius: float = 0.5) -> Mesh:
+                            layer_cap: Optional["LayerCap"] = None, sectors: int = 6, exact_radius: float = 0.5,
+                            source_x: float = 0.0) -> Mesh:
     """Half-ball tetrahedral mesh whose faces follow the material interfaces of a dipping model, the
     geometry the reference builds with OpenCASCADE (gmsh_functions.py:543-628): borehole = body of
     revolution of the wall polyline, layer boundaries = planes z + x tan(dip) = const through the
@@ -695,6 +709,10 @@ def make_mesh_3d_conforming(R: float, local_formation_geometry: np.ndarray, loca
       circle's: every volume of revolution (mud column, flushed zones) is preserved exactly;
     * a caliper that varies with depth is revolved as it is seen on the axis' own z' (exact for a
       cylindrical hole, first order in radius * tan(dip) otherwise);
+    * source_x != 0: the electrodes sit at (source_x, 0, z) - an eccentred tool.  In the sheared coordinates that is radius
+      |source_x| and height z + source_x tan(dip): the refinement centres of the generating 2D mesh move there (rings of the revolved
+      mesh); no vertex is snapped onto them, and the number of sectors grows (up to 32) until a sector is no wider at the electrodes
+      than the generating mesh is fine there.  source_x = 0 gives today's arrays;
     * the sheared ball is inscribed in the physical sphere |x| = R and its outer part (beyond
       `exact_radius` of the way to the boundary) is stretched radially onto the sphere, so the Dirichlet
       boundary is the reference's; within that fraction the dipping geometry is exact.
@@ -703,12 +721,23 @@ def make_mesh_3d_conforming(R: float, local_formation_geometry: np.ndarray, loca
     fg = np.asarray(local_formation_geometry, dtype=np.float64)
     bg = np.asarray(local_borehole_geometry, dtype=np.float64)
     m = int(sectors)
+    if source_x != 0.0:
+        # the sectors set the element size AROUND the axis: |x| * pi / m at distance |x|.  At a displaced electrode that has to come
+        # down to the size the generating mesh has there (0.8 * scale * h_src: with the diagonals of the cut prisms the longest
+        # edge then stays near the 1.3 h of an axis element), or the electrode sits in slabs several times as wide as they are
+        # high; at most 32 sectors
+        chord = 0.8 * scale * 0.01 / (2.0 * abs(float(source_x)))
+        if chord < 1.0:
+            m = int(min(max(m, np.ceil(np.pi / (2.0 * np.arcsin(chord)))), 32))
     kappa = float(np.sqrt(np.pi / (m * np.sin(np.pi / m))))      # equal-area regular 2m-gon
     # shear S: (x, z') -> (x, z' - a x); its singular values bound the radius of the sheared ball
     smax = float(np.sqrt(1.0 + 0.5 * a * a + a * np.sqrt(1.0 + 0.25 * a * a)))
     Rs = R / (smax * kappa)                                       # inscribed: the stretch below only ever pushes outwards
     polys = layer_interfaces_2d(fg, bg, Rs)
     inside_src = [z for z in list(sources_z) + list(snap_z) if abs(z) < Rs]
+    if source_x != 0.0:
+        inside_src = [(abs(float(source_x)), z + a * float(source_x)) for z in list(sources_z) + list(snap_z)]
+        inside_src = [c for c in inside_src if np.hypot(*c) < Rs]
     fn2 = layered_material_fn(2, fg, bg)
     m2 = make_mesh(2, Rs, sources_z=inside_src, scale=scale, seed=seed, interfaces=polys, layer_cap=layer_cap, material_fn=fn2,
                    h_max=0.2 * R)
@@ -762,7 +791,7 @@ def make_mesh_3d_conforming(R: float, local_formation_geometry: np.ndarray, loca
     meta = dict(R=R, scale=scale, seed=seed, sources_z=[float(s) for s in sources_z], volume=float(vol.sum()),
                 volume_exact=float(2.0 / 3.0 * np.pi * R ** 3), min_quality=float(qual.min()), max_valence=valence,
                 n_interface_points=int(m2.meta["n_interface_points"]), dip_rad=float(dip_rad), sectors=m, kappa=kappa,
-                sheared_radius=Rs, exact_radius=float(t1 * Rs / smax), n_triangles_2d=int(m2.n_elems))
+                sheared_radius=Rs, exact_radius=float(t1 * Rs / smax), n_triangles_2d=int(m2.n_elems), source_x=float(source_x))
     return Mesh(3, np.ascontiguousarray(pts), np.ascontiguousarray(conn.astype(np.int32)), np.ascontiguousarray(mat.astype(np.int32)),
                 np.ascontiguousarray(bf.astype(np.int32)), np.ascontiguousarray(bdir.astype(np.uint8)), meta)
 

@@ -118,7 +118,8 @@ def default_mesh_provider(scale: Optional[float] = None, seed: int = 0, mesh_3d:
             fg = np.asarray(local_formation_geometry, dtype=float)
             cap = meshgen.LayerCap(np.concatenate([fg[:1, 0], fg[:, 1]]))
             return meshgen.make_mesh_3d_conforming(domain_radius, local_formation_geometry, local_borehole_geometry, dip_rad,
-                                                   sources_z=list(cur), snap_z=list(pot), scale=scale, seed=seed, layer_cap=cap, sectors=sectors)
+                                                   sources_z=list(cur), snap_z=list(pot), scale=scale, seed=seed, layer_cap=cap, sectors=sectors,
+                                                   source_x=float(getattr(batch, "lateral", 0.0)))     # an eccentred tool: refined where it is
         key = lattice_mesh_key(dim, domain_radius, batch, scale, seed)
         base = cache.get(key)
         if base is None:
@@ -144,8 +145,8 @@ def _mesh_worker_init(provider_kwargs):
 
 
 def _mesh_worker_run(job):
-    dim, domain_radius, electrodes, fg, bh, dip_rad = job
-    return _WORKER_PROVIDER(dim, domain_radius, types.SimpleNamespace(electrodes=electrodes), fg, bh, dip_rad)
+    dim, domain_radius, electrodes, fg, bh, dip_rad, lateral = job
+    return _WORKER_PROVIDER(dim, domain_radius, types.SimpleNamespace(electrodes=electrodes, lateral=lateral), fg, bh, dip_rad)
 
 
 # -- the stages of Model.simulate_logs, in the order a sweep goes through them ---------------------------
@@ -153,8 +154,17 @@ class _Plan:
     """Stage 1, before any batch is drawn: the arguments checked, the batches, the solver options."""
 
     def __init__(self, model, measurement_depths, domain_radius, batch_size, mesh_generator, mesh_provider, mesh_scale, solver_kw,
-                 solver_options, verbose):
+                 solver_options, verbose, eccentricity=0.0):
         extra = dict(solver_options or {})
+        # the tool's displacement from the borehole axis, along x of the mesh frame: checked before any batch is drawn
+        if not np.isfinite(eccentricity):
+            raise ValueError("eccentricity has to be a finite number of metres")
+        self.eccentricity = float(eccentricity)
+        if self.eccentricity != 0.0:
+            if abs(self.eccentricity) >= float(np.min(model.borehole_model[:, 1])):
+                raise ValueError("eccentricity has to be smaller than the smallest borehole radius: the tool is in the mud")
+            if mesh_generator == "netgen":
+                raise ValueError("An eccentred tool is a 3D model: the only mesh generator supported in 3D models is gmsh")
         self.model, self.domain_radius, self.mesh_scale = model, domain_radius, mesh_scale
         self.depths = np.asarray(measurement_depths, dtype=float)
         alert = False
@@ -168,20 +178,24 @@ class _Plan:
                   "Consider increase of the domain size")
         if mesh_generator not in ("auto", "gmsh", "netgen"):
             raise ValueError("mesh_generator has to be 'auto', 'gmsh' or 'netgen'")
-        is3d = not np.isclose(model.dip_deg, 0)
+        dipping = not np.isclose(model.dip_deg, 0)
+        is3d = dipping or self.eccentricity != 0.0      # an eccentred tool breaks the axial symmetry also between flat beds
         if is3d and mesh_generator == "netgen":
             raise ValueError("The only mesh generator supported in 3D models is gmsh")
         if solver_kw["preconditioner"] not in ("local", "multigrid"):
             raise ValueError("preconditioner has to be 'local' or 'multigrid'")
         if model.ctx is None:
             raise RuntimeError("initialize_workers() has to be called before simulate_logs()")
-        if model.dip_deg != 0:
+        if model.dip_deg != 0 or self.eccentricity != 0.0:
             model.borehole_model = model._add_points_to_borehole()
-        self.dim, self.window_dip = (3, model.dip_rad) if is3d else (2, 0.0)
+        self.dim, self.window_dip = (3, model.dip_rad if dipping else 0.0) if is3d else (2, 0.0)
+        self.mesh_dip = self.window_dip                 # what the mesher is given: exactly 0 for flat beds
         self.netgen_path = (not is3d) and mesh_generator in ("auto", "netgen")
         self.default_provider = mesh_provider is None     # its 3D meshes are the conforming revolved ones; only it runs in the mesh pool
         self.provider = mesh_provider or default_mesh_provider(scale=mesh_scale)
         self.simulation_depths, self.batches = model._prepare_simulation_depths_and_tasks(self.depths, batch_size)
+        for b in self.batches:
+            b.lateral = self.eccentricity
         self.borehole_geometry = np.ascontiguousarray(model.borehole_model[:, :2])
         self.mud = np.interp(self.simulation_depths, model.borehole_model[:, 0], model.borehole_model[:, 2])
         if verbose and sweep.rank() == 0:
@@ -307,7 +321,7 @@ class _MeshAhead:
                 if self.pool is not None and not (self.cache is not None and self.cache.has_mesh(bi)):
                     try:
                         fg, bh, _ = self.windowing.window(bi)
-                        self.pending[bi] = self.pool.submit(_mesh_worker_run, (p.dim, p.domain_radius, p.batches[bi].electrodes, fg, bh, p.model.dip_rad))
+                        self.pending[bi] = self.pool.submit(_mesh_worker_run, (p.dim, p.domain_radius, p.batches[bi].electrodes, fg, bh, p.mesh_dip, p.eccentricity))
                     except Exception:
                         pass      # reported when the batch's turn comes
                 self.ahead.append(bi)
@@ -329,7 +343,7 @@ class _MeshAhead:
                 mesh = self.pending.pop(bi).result()
             except Exception:     # a worker process died: mesh this batch here
                 mesh = None
-        return mesh if mesh is not None else p.provider(p.dim, p.domain_radius, p.batches[bi], fg, bh, p.model.dip_rad)
+        return mesh if mesh is not None else p.provider(p.dim, p.domain_radius, p.batches[bi], fg, bh, p.mesh_dip)
 
     def shutdown(self):
         if self.pool is not None:     # whatever happened in the sweep, the mesh processes do not outlive it
@@ -466,6 +480,8 @@ class _FieldSections(_Output):
         half = 0.5 if self.plan.dim == 3 else 1.0
         for j, k in enumerate(job.field_rhs):
             z, I = job.sources[k]
+            z = np.asarray(z, dtype=float)
+            z = z[:, -1] if z.ndim == 2 else z      # an eccentred tool: points (e, 0, z); x is the plan's eccentricity for all
             if len(z) > self.MAX_SOURCES:
                 raise ValueError("a right-hand side with more than {} point sources".format(self.MAX_SOURCES))
             src = np.zeros(1 + 2 * self.MAX_SOURCES)
@@ -496,6 +512,7 @@ class _FieldSections(_Output):
                 out.append((rec[1:1 + n].copy(), rec[1 + self.MAX_SOURCES:1 + self.MAX_SOURCES + n].copy()))
             return out
         model.field_sources = _per_tool(model, sources)
+        model.field_source_x = _per_tool(model, lambda i: [np.full(len(zs), self.plan.eccentricity) for zs, _ in sources(i)])
         model.field_grid = {k: np.asarray(v, dtype=float) for k, v in self.grid.items()}
         model.field_depth_index = self.kept.copy()
 
@@ -519,12 +536,12 @@ class _BatchRunner:
             fg, bh, sigma = self.windowing.window(bi)
             job = types.SimpleNamespace(bi=bi, sigma=sigma, mesh=self.meshes.mesh(bi, fg, bh), groups=None, functionals=None,
                                         field_rhs=None, field_points=None)
-            sources, evals, job.readers = tasks.batch_rhs(batch, p.model.tools)
+            sources, evals, job.readers = tasks.batch_rhs(batch, p.model.tools, p.eccentricity)
             job.sources = sources
             t1 = time.time()
             opts = p.batch_opts(job.mesh)
             if any(o.adjoint for o in self.outputs):
-                job.functionals, job.fun_readers = tasks.batch_functionals(batch, p.model.tools)
+                job.functionals, job.fun_readers = tasks.batch_functionals(batch, p.model.tools, p.eccentricity)
             for o in self.outputs:
                 o.prepare(job)
             c = self.free_ctx.get()
@@ -604,6 +621,8 @@ class Model:
         self.sensitivity_grid = None   # the grid of the last maps
         self.field_sections = None     # simulate_logs(field_grid=...): per tool dict(u [n_kept, n_z, n_h] in V, J [n_kept, n_z, n_h, dim] in A/m2)
         self.field_sources = None      # ... per tool and kept record the energised point sources (absolute z, I)
+        self.field_source_x = None     # ... and their x in the mesh frame (the eccentricity of the sweep; 0 for a centred tool)
+        self.eccentricity = None       # the displacement of the tool from the borehole axis in the last sweep, metres along x
         self.field_grid = None         # the grid of the last sections
         self.field_depth_index = None  # ... and the indices into measurement_depths they were kept for
         self.inversion = None          # invert_logs: what the last inversion found (inversion.invert_model)
@@ -786,8 +805,16 @@ class Model:
                       maxsteps: int = 1000, verbose: bool = True, mesh_workers: Optional[int] = None, precision: str = "fp64",
                       schedule: str = "static", solver_options: Optional[dict] = None, sensitivities: bool = False,
                       sensitivity_grid: Optional[dict] = None, reuse=None, field_grid: Optional[dict] = None,
-                      field_depths=None):
-        """solver_options: further keywords of solver.make_opts for every batch (op, coarse, quadrature, assemble, ...).
+                      field_depths=None, eccentricity: float = 0.0):
+        """eccentricity: signed displacement in metres of the WHOLE tool from the borehole axis, along x of the mesh frame - the dip
+        plane y = 0.  The bedding planes are z + x tan(dip) = const with z growing downwards (meshgen.layered_material_fn), so a bed
+        boundary lies shallower at +x: +x is UP-dip, a negative value moves the tool down-dip; with dip 0 the direction is immaterial.
+        A non-zero value selects the 3D model also between flat beds (dim 3, dip exactly 0), sends every batch through
+        remo_solve_job with its electrodes at (eccentricity, 0, z), and refines the batch meshes around them; it has to be smaller
+        than the smallest borehole radius (the tool is in the mud) and cannot be combined with mesh_generator="netgen".  A
+        displacement OUT of the dip plane would break the mirror symmetry in y = 0 that the half-ball model rests on: it is not
+        offered.  0.0 (default): the centred tool, exactly as without the keyword.  self.eccentricity records the value.
+        solver_options: further keywords of solver.make_opts for every batch (op, coarse, quadrature, assemble, ...).
         sensitivities: also fill self.sensitivities[tool] = dRa/dR in ohm m per ohm m, [n_depths, n_layers, n_cols] with the
         columns of the formation table from column 2 on (RDFZ - a radius, always NaN -, RTFZ, RTUZ, and RVUZ when present; 0 where
         the batch's window does not hold the entry, NaN where the table has NaN or the batch failed), and self.mud_sensitivity[tool]
@@ -821,7 +848,8 @@ class Model:
             raise ValueError("field_depths needs a field_grid")
         plan = _Plan(self, measurement_depths, domain_radius, batch_size, mesh_generator, mesh_provider, mesh_scale,
                      dict(preconditioner=preconditioner, condense=condense, rtol=rtol, maxsteps=maxsteps, precision=precision),
-                     solver_options, verbose)
+                     solver_options, verbose, eccentricity)
+        self.eccentricity = plan.eccentricity
         windowing = _Windowing(plan)
         outputs = [_Logs(plan)]     # the ONE place where the keywords of the further outputs are looked at
         if sensitivities:
@@ -848,7 +876,7 @@ class Model:
         for o in outputs:            # the same pattern for every slab: every rank has zeros outside its own records
             o.combine()
         self.sensitivities = self.mud_sensitivity = self.sensitivity_maps = self.sensitivity_map_rest = self.sensitivity_grid = None
-        self.field_sections = self.field_sources = self.field_grid = self.field_depth_index = None
+        self.field_sections = self.field_sources = self.field_source_x = self.field_grid = self.field_depth_index = None
         for o in outputs:
             o.publish(self)
         self.timing = dict(total_s=time.time() - start, mesh_s=acc["mesh"], solve_s=acc["solve"], points=acc["points"], batches=len(plan.batches),

@@ -229,8 +229,10 @@ def plot_field_section(model, tool, depth_index, path=None):
     if np.any(np.isfinite(Jh) & np.isfinite(Jz)):
         ax.streamplot(hs, zs, np.ma.masked_invalid(Jh), np.ma.masked_invalid(Jz), color="w", linewidth=0.7, density=1.2, arrowsize=0.7)
     src_z, src_I = model.field_sources[tool][k]
-    for zq, Iq in zip(np.atleast_1d(src_z), np.atleast_1d(src_I)):
-        ax.plot([0.0], [zq], marker="o" if Iq > 0 else "s", color="r" if Iq > 0 else "b", ms=6, mec="k", zorder=5)
+    src_x = getattr(model, "field_source_x", None)      # an eccentred tool: the electrodes at x = e of the dip plane
+    src_x = np.zeros(np.size(src_z)) if src_x is None else np.atleast_1d(src_x[tool][k])
+    for zq, Iq, xq in zip(np.atleast_1d(src_z), np.atleast_1d(src_I), src_x):
+        ax.plot([xq if lateral == "x" else abs(xq)], [zq], marker="o" if Iq > 0 else "s", color="r" if Iq > 0 else "b", ms=6, mec="k", zorder=5)
     ax.set_xlim(h[0], h[-1])
     ax.set_ylim(z[-1], z[0])
     ax.set_xlabel("{} [m]".format(lateral))

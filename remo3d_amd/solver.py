@@ -63,21 +63,47 @@ def make_opts(preconditioner="multigrid", condense=True, maxsteps=1000, rtol=1e-
     return o
 
 
-def _ragged(mismatch, *columns):
+def axis_points(dim, z):
+    """Axis positions z [m] as points [m, dim] of the mesh's frame: (0, z) / (0, 0, z)."""
+    z = np.atleast_1d(np.asarray(z, dtype=np.float64)).ravel()
+    out = np.zeros((z.size, int(dim)))
+    out[:, -1] = z
+    return out
+
+
+def _off_axis(*position_lists):
+    """True when any position item is an [m, dim] array of points instead of a 1-D array of axis z."""
+    return any(np.ndim(a) == 2 for col in position_lists for a in col)
+
+
+def _as_points(a, dim):
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim < 2:
+        return axis_points(dim, a)
+    if a.ndim != 2 or a.shape[1] != dim:
+        raise ValueError("positions must be 1-D axis z or [m, {}] points, not {}".format(dim, a.shape))
+    return a
+
+
+def _ragged(mismatch, *columns, dim=0):
     """columns: lists of 1-D sequences, item k of every list equally long -> [item pointer int32 [n + 1], the float64 concatenation
-    of every list]: the CSR-like form in which the library takes sources, evaluation points and functionals."""
-    cols = [[np.atleast_1d(np.asarray(a, dtype=np.float64)) for a in col] for col in columns]
-    if any(a.shape != b.shape for col in cols[1:] for a, b in zip(cols[0], col)):
+    of every list]: the CSR-like form in which the library takes sources, evaluation points and functionals.
+    dim > 0: the items of the FIRST list are positions, each 1-D axis z or [m, dim] points, and come back as points (row-major)."""
+    cols = [[np.atleast_1d(np.asarray(a, dtype=np.float64)) for a in col] for col in columns[1 if dim else 0:]]
+    if dim:
+        cols.insert(0, [_as_points(a, dim) for a in columns[0]])
+    if any(a.shape[0] != b.shape[0] or b.ndim != 1 for col in cols[1:] for a, b in zip(cols[0], col)):
         raise ValueError(mismatch)
     item_ptr = np.zeros(len(cols[0]) + 1, dtype=np.int32)
-    item_ptr[1:] = np.cumsum([a.size for a in cols[0]])
-    return [item_ptr] + [np.ascontiguousarray(np.concatenate(col) if col else np.zeros(0), dtype=np.float64) for col in cols]
+    item_ptr[1:] = np.cumsum([a.shape[0] for a in cols[0]])
+    return [item_ptr] + [np.ascontiguousarray(np.concatenate(col).ravel() if col else np.zeros(0), dtype=np.float64) for col in cols]
 
 
-def _rhs_arrays(sources, evals):
-    """sources: list (per RHS) of (z array, I array); evals: list (per RHS) of z arrays."""
-    src_ptr, sz, sI = _ragged("source positions and strengths differ in length", [z for (z, I) in sources], [I for (z, I) in sources])
-    eval_ptr, ez = _ragged(None, list(evals))
+def _rhs_arrays(sources, evals, dim=0):
+    """sources: list (per RHS) of (positions, I array); evals: list (per RHS) of positions.  dim = 0: positions are 1-D axis z;
+    dim > 0: positions are axis z or [m, dim] points and come back as points."""
+    src_ptr, sz, sI = _ragged("source positions and strengths differ in length", [z for (z, I) in sources], [I for (z, I) in sources], dim=dim)
+    eval_ptr, ez = _ragged(None, list(evals), dim=dim)
     return src_ptr, sz, sI, eval_ptr, ez
 
 
@@ -98,18 +124,25 @@ def sigma_table(sigma, dim=None):
     return np.ascontiguousarray(sigma[:, iu[0], iu[1]]), True
 
 
-def _functional_arrays(functionals):
-    """functionals: list of (rhs, z array, w array) -> (fun_rhs, fun_ptr, fun_z, fun_w) of remo_solve_batch_sens."""
-    fun_ptr, fz, fw = _ragged("functional points and weights differ in length", [z for (_, z, w) in functionals], [w for (_, z, w) in functionals])
+def _functional_arrays(functionals, dim=0):
+    """functionals: list of (rhs, positions, w array) -> (fun_rhs, fun_ptr, fun_z | fun_p, fun_w) of remo_solve_batch_sens / remo_job_t."""
+    fun_ptr, fz, fw = _ragged("functional points and weights differ in length", [z for (_, z, w) in functionals], [w for (_, z, w) in functionals],
+                              dim=dim)
     return np.ascontiguousarray([f[0] for f in functionals], dtype=np.int32), fun_ptr, fz, fw
 
 
-def _batch_args(handle, mesh, sigma, sources, evals):
+def _batch_args(handle, mesh, sigma, sources, evals, job=False):
     """The arguments every batch entry begins with (remo_solve_batch*, remo_batch_create*): handle, mesh, conductivity table, sources
-    and evaluation points.  Returns (args, sigma table, tensor?, eval_ptr, keep); keep holds what the pointers in args look at."""
+    and evaluation points.  Returns (args, sigma table, tensor?, eval_ptr, keep); keep holds what the pointers in args look at.
+    job: the same as the leading members of a remo_job_t (positions as points) - args is then [handle, mesh, job]."""
     sigma, tensor = sigma_table(sigma, int(mesh.dim))
-    src_ptr, sz, sI, eval_ptr, ez = _rhs_arrays(sources, evals)
+    src_ptr, sz, sI, eval_ptr, ez = _rhs_arrays(sources, evals, int(mesh.dim) if job else 0)
     ms, keep = _lib.mesh_struct(mesh)
+    if job:
+        j = _lib.RemoJob(size=C.sizeof(_lib.RemoJob), tensor=int(tensor), n_mat=len(sigma), sigma=ptr(sigma, C.c_double), n_rhs=len(sources),
+                         src_ptr=ptr(src_ptr, C.c_int32), src_p=ptr(sz, C.c_double), src_I=ptr(sI, C.c_double),
+                         eval_ptr=ptr(eval_ptr, C.c_int32), eval_p=ptr(ez, C.c_double))
+        return [handle, C.byref(ms), j], sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez)
     args = [handle, C.byref(ms), len(sigma), ptr(sigma, C.c_double), len(sources), ptr(src_ptr, C.c_int32), ptr(sz, C.c_double),
             ptr(sI, C.c_double), ptr(eval_ptr, C.c_int32), ptr(ez, C.c_double)]
     return args, sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez)
@@ -213,11 +246,15 @@ class Context:
                   points=None, field_rhs=None):
         """The one marshalling path of the one-shot entries remo_solve_batch<kind>[_tensor], kind "", "_sens", "_sens_warm", "_sens_groups"
         or "_field": the common arguments, then the functionals and the groups - or the field points - with their outputs where the kind
-        has them.  Returns (potentials, [J, dJ, [dJg] | field dict,] stats, rc)."""
-        args, sigma, tensor, eval_ptr, keep = _batch_args(self._h, mesh, sigma, sources, evals)
+        has them.  Returns (potentials, [J, dJ, [dJg] | field dict,] stats, rc).
+        Positions (of sources, evaluation points, functionals) are 1-D arrays of axis z or [m, dim] arrays of points; with one item
+        of the second kind the same arrays go into a remo_job_t instead (remo_solve_job), every item as points."""
+        job = _off_axis([z for (z, _) in sources], evals, [z for (_, z, _) in functionals] if functionals else [])
+        args, sigma, tensor, eval_ptr, keep = _batch_args(self._h, mesh, sigma, sources, evals, job)
         d, nc = int(mesh.dim), (sigma.shape[1] if tensor else 1)
         out = np.full(int(eval_ptr[-1]), np.nan)
         args.append(ptr(out, C.c_double))
+        n_head = len(args)
         J, grads, field = [], [], []
         if kind == "_field":
             points = _field_points(points, d)
@@ -229,7 +266,7 @@ class Context:
                      ptr(field[0]["J"], C.c_double), ptr(field[0]["elem"], C.c_int32)]
         elif kind:
             n_fun = len(functionals)
-            fun_rhs, fun_ptr, fz, fw = _functional_arrays(functionals)
+            fun_rhs, fun_ptr, fz, fw = _functional_arrays(functionals, d if job else 0)
             args += [n_fun, ptr(fun_rhs, C.c_int32), ptr(fun_ptr, C.c_int32), ptr(fz, C.c_double), ptr(fw, C.c_double)]
             J, grads = [np.full(n_fun, np.nan)], [np.full((n_fun, len(sigma), nc), np.nan)]
             if kind == "_sens_groups":
@@ -244,7 +281,18 @@ class Context:
                 args.append(warm._h)
         st = RemoStats()
         o = opts if opts is not None else make_opts()
-        rc = getattr(self._L, "remo_solve_batch" + kind + ("_tensor" if tensor else ""))(*args, C.byref(o), C.byref(st))
+        if job:   # the arguments behind the head, by the names remo_job_t gives them
+            names = {"": [], "_field": ["n_pts", "pts", "n_frhs", "field_rhs", "u_f", "grad_f", "J_f", "elem_f"],
+                     "_sens": ["n_fun", "fun_rhs", "fun_ptr", "fun_p", "fun_w", "J_out", "dJ_out"],
+                     "_sens_warm": ["n_fun", "fun_rhs", "fun_ptr", "fun_p", "fun_w", "J_out", "dJ_out", "warm"],
+                     "_sens_groups": ["n_fun", "fun_rhs", "fun_ptr", "fun_p", "fun_w", "n_group", "group", "J_out", "dJ_out", "dJg_out"]}[kind]
+            j = args[2]
+            j.u_out = args[n_head - 1]
+            for name, value in zip(names, args[n_head:]):
+                setattr(j, name, value)
+            rc = self._L.remo_solve_job(args[0], args[1], C.byref(j), C.byref(o), C.byref(st))
+        else:
+            rc = getattr(self._L, "remo_solve_batch" + kind + ("_tensor" if tensor else ""))(*args, C.byref(o), C.byref(st))
         if rc < 0 and raise_on_error:
             raise RemoError(rc, self.last_error())
         potentials = [out[eval_ptr[k]:eval_ptr[k + 1]] for k in range(len(evals))]
@@ -253,7 +301,11 @@ class Context:
     def solve_batch(self, mesh, sigma, sources, evals, opts: Optional[RemoOpts] = None, raise_on_error=True):
         """One-shot remo_solve_batch.  Returns (list of per-RHS potential arrays, stats dict, rc).
         sigma: [n_mat] conductivities, or [n_mat, dim, dim] symmetric positive definite tensors in the mesh's frame
-        (remo_solve_batch_tensor)."""
+        (remo_solve_batch_tensor).
+        sources: per right-hand side (positions, I); evals: per right-hand side positions.  Positions - here and in the functionals
+        of the methods below - are a 1-D array of axis z or an [m, dim] array of points of the mesh's frame ((r, z) / (x, y, z)); with
+        one item of the second kind the whole call goes through remo_solve_job, 1-D items padded with zeros (axis_points).  A source
+        at r > 0 of a 2D mesh is a ring of total current I; in 3D a source at y > 0 stands for itself and its mirror image."""
         return self._one_shot("", mesh, sigma, sources, evals, opts, raise_on_error)
 
     def solve_batch_sens(self, mesh, sigma, sources, evals, functionals, opts: Optional[RemoOpts] = None, raise_on_error=True,
@@ -293,6 +345,11 @@ class Context:
         self._L.remo_debug_field_timing(self._h, ptr(out, C.c_double))
         return float(out[0]), float(out[1])
 
+    def point_location(self) -> int:
+        """How the last batch that ran on this context located the points of its right-hand sides (remo_debug_point_location): 0 = the
+        kernels of the axis entries, 1 = the cell grid of the field sections (a batch with a point off the axis)."""
+        return int(self._L.remo_debug_point_location(self._h))
+
     def sens_group_timing(self):
         """ms of the group path of the last solve_batch_sens_groups on this context (remo_debug_sens_group_timing): (group order,
         material pass, per-element pass, group sums); the last three are measured only with make_opts(time_kernels=True)."""
@@ -312,14 +369,19 @@ class Context:
 
 class Batch:
     """Resident batch (remo_batch_create / run / fetch).  sigma: [n_mat] conductivities, or [n_mat, dim, dim] symmetric positive
-    definite tensors (remo_batch_create_tensor), as for Context.solve_batch."""
+    definite tensors (remo_batch_create_tensor), as for Context.solve_batch.  Positions given as [m, dim] points: remo_batch_create_job
+    (eval stays an axis entry; field reads anywhere)."""
 
     def __init__(self, ctx: Context, mesh, sigma, sources, evals):
         self.ctx = ctx
         self._L = ctx._L
-        args, _, tensor, self._eval_ptr, keep = _batch_args(ctx._h, mesh, sigma, sources, evals)
+        job = _off_axis([z for (z, _) in sources], evals)   # positions given as points: remo_batch_create_job
+        args, _, tensor, self._eval_ptr, keep = _batch_args(ctx._h, mesh, sigma, sources, evals, job)
         h = C.c_void_p()
-        rc = (self._L.remo_batch_create_tensor if tensor else self._L.remo_batch_create)(*args, C.byref(h))
+        if job:
+            rc = self._L.remo_batch_create_job(args[0], args[1], C.byref(args[2]), C.byref(h))
+        else:
+            rc = (self._L.remo_batch_create_tensor if tensor else self._L.remo_batch_create)(*args, C.byref(h))
         if rc != 0:
             raise RemoError(rc, ctx.last_error())
         self._h = h
@@ -484,6 +546,19 @@ def host_field_element(dim: int, vertex_coords: np.ndarray, sigma, x_e, point) -
     if rc != 0:
         raise RemoError(rc, "remo_host_field_element")
     return out
+
+
+def host_point_shapes(dim: int, vertex_coords: np.ndarray, point) -> np.ndarray:
+    """Shape values [nld] at `point` of the element with sorted vertices vertex_coords (remo_host_point_shapes: the code the kernel
+    of off-axis sources and readings runs)."""
+    L = _lib.load()
+    X = np.ascontiguousarray(vertex_coords, dtype=np.float64)
+    P = np.ascontiguousarray(point, dtype=np.float64)
+    phi = np.zeros(10 if dim == 2 else 20)
+    rc = L.remo_host_point_shapes(dim, ptr(X, C.c_double), ptr(P, C.c_double), ptr(phi, C.c_double))
+    if rc != 0:
+        raise RemoError(rc, "remo_host_point_shapes")
+    return phi
 
 
 def host_symbolic(mesh, condense=True):

@@ -36,6 +36,7 @@ class Batch:
     combined_depth: float
     electrodes: np.ndarray            # [2, m] union over the batch (what the mesher refines around)
     solves: List[Solve] = field(default_factory=list)
+    lateral: float = 0.0              # x of every electrode in the mesh's frame (an eccentred tool; the mesher refines there)
 
 
 def _merge(potential, current):
@@ -113,16 +114,26 @@ def to_reference_layout(batches: Sequence[Batch]):
     return out
 
 
-def batch_rhs(batch: Batch, tools: Dict[str, np.ndarray]):
+def _positions(z, lateral):
+    """Axis positions z [m] as the solver takes them: 1-D as they are, or - the tool displaced by `lateral` along x - the points
+    (lateral, 0, z) [m, 3] of the 3D frame."""
+    z = np.asarray(z, dtype=float)
+    if lateral == 0.0:
+        return z
+    return np.stack([np.full(z.shape, float(lateral)), np.zeros(z.shape), z], axis=1)
+
+
+def batch_rhs(batch: Batch, tools: Dict[str, np.ndarray], lateral: float = 0.0):
     """Sources / evaluation points of a batch in the form remo_solve_batch takes, plus the map
     back to records: returns (sources, evals, readers) with readers[k] = list of
-    (depth_index, tool_index, K, slice into evals[k]) following worker.py:113-131."""
+    (depth_index, tool_index, K, slice into evals[k]) following worker.py:113-131.
+    lateral != 0: every position is an [m, 3] array of points (lateral, 0, z) instead of a 1-D array of z (remo_solve_job)."""
     names = list(tools.keys())
     sources, evals, readers = [], [], []
     for s in batch.solves:
         z = s.electrodes[0, :]
         I = s.electrodes[1, :]
-        sources.append((z[I != 0].copy(), I[I != 0].copy()))
+        sources.append((_positions(z[I != 0].copy(), lateral), I[I != 0].copy()))
         pts, rd = [], []
         for r in s.records:
             t = tools[names[r.tool_index]]
@@ -130,16 +141,17 @@ def batch_rhs(batch: Batch, tools: Dict[str, np.ndarray]):
             meas = geo[t[1, :3] == 0]
             rd.append((r.depth_index, r.tool_index, float(t[0, 3]), len(pts), len(meas)))
             pts += list(meas)
-        evals.append(np.asarray(pts, dtype=float))
+        evals.append(_positions(np.asarray(pts, dtype=float), lateral))
         readers.append(rd)
     return sources, evals, readers
 
 
-def batch_functionals(batch: Batch, tools: Dict[str, np.ndarray]):
+def batch_functionals(batch: Batch, tools: Dict[str, np.ndarray], lateral: float = 0.0):
     """The linear functional behind every record of a batch (worker.py:113-131), in the form remo_solve_batch_sens takes:
     returns (functionals, readers) with functionals[j] = (rhs, z array, w array) - J = u_N - u_M (two measuring electrodes, in the
     order of the tool table) or u_M (one) of right-hand side `rhs` - and readers[j] = (depth_index, tool_index, K), so that
-    Ra = |K J| (/ 2 in 3D), the value apparent_resistivity gives.  Records with another electrode count get no functional."""
+    Ra = |K J| (/ 2 in 3D), the value apparent_resistivity gives.  Records with another electrode count get no functional.
+    lateral != 0: the points are (lateral, 0, z) [m, 3], as in batch_rhs."""
     names = list(tools.keys())
     functionals, readers = [], []
     for k, s in enumerate(batch.solves):
@@ -153,7 +165,7 @@ def batch_functionals(batch: Batch, tools: Dict[str, np.ndarray]):
                 w = np.array([1.0])
             else:
                 continue
-            functionals.append((k, np.asarray(meas, dtype=float), w))
+            functionals.append((k, _positions(np.asarray(meas, dtype=float), lateral), w))
             readers.append((r.depth_index, r.tool_index, float(t[0, 3])))
     return functionals, readers
 

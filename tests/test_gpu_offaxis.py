@@ -1,0 +1,417 @@
+"""Sources and readings off the borehole axis on the GPU: remo_solve_job / remo_batch_create_job through solver.Context and
+solver.Batch, and the `eccentricity` keyword of Model.
+
+Reference: the uncondensed oracle with loads and readings at arbitrary points (tests/_offaxis.py, proved on the CPU in
+tests/test_offaxis_cpu.py).  Bounds are the project's own: potentials 1e-8 of max |u_ref| at rtol 1e-12, closed
+forms 5e-3, material derivatives 4.12e-8 in the measure of _sensitivity.rel_to_scale, group sums 1e-6.
+"""
+import numpy as np
+import pytest
+
+import _offaxis as O
+import _sensitivity as S
+from conftest import SIGMA3
+
+pytestmark = pytest.mark.gpu
+
+_CACHE = {}
+
+
+def _opts(**kw):
+    from remo3d_amd import solver
+    kw.setdefault("rtol", 1e-12)
+    kw.setdefault("maxsteps", 20000)
+    return solver.make_opts(**kw)
+
+
+def _mesh(dim, mesh2d, mesh3d):
+    return mesh2d if dim == 2 else mesh3d
+
+
+def _axis_batch(dim):
+    from remo3d_amd.solver import axis_points as ap
+    src = [(ap(dim, z), I) for (z, I) in S.SOURCES]
+    ev = [ap(dim, z) for z in S.EVALS]
+    fun = [(r, ap(dim, z), w) for (r, z, w) in S.FUNCTIONALS]
+    return src, ev, fun
+
+
+# ---- 1. an all-axis job is the old entry ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dim", [2, 3])
+def test_all_axis_job_has_the_bits_of_the_axis_entries(dim, mesh2d, mesh3d, gpu_ctx):
+    """The same batch as 1-D axis positions (legacy symbols) and through solver.axis_points (remo_solve_job), op = 2: potentials, J,
+    dJ, dJg, the field outputs and pcg_steps are equal bit for bit for the plain, sens, sens-groups and field kinds - an all-axis
+    batch is located by k_locate (Context.point_location() == 0)."""
+    mesh = _mesh(dim, mesh2d, mesh3d)
+    src, ev, fun = _axis_batch(dim)
+    o = _opts(op="csr")
+    rho = np.abs(mesh.coords[mesh.conn].mean(axis=1)[:, 0])
+    groups = np.where(rho < 0.1, 0, np.where(rho < 2.0, 1, -1)).astype(np.int32)
+    P = np.concatenate([np.asarray(src[1][0]), np.array([[0.3] + [0.0] * (dim - 2) + [0.2]]), np.full((1, dim), 90.0)])
+    calls = {
+        "plain": lambda s, e, f: gpu_ctx.solve_batch(mesh, SIGMA3, s, e, o),
+        "sens": lambda s, e, f: gpu_ctx.solve_batch_sens(mesh, SIGMA3, s, e, f, o),
+        "groups": lambda s, e, f: gpu_ctx.solve_batch_sens_groups(mesh, SIGMA3, s, e, f, groups, 2, o),
+        "field": lambda s, e, f: gpu_ctx.solve_batch_field(mesh, SIGMA3, s, e, P, [2, 0], o),
+    }
+    for name, call in calls.items():
+        old = call(S.SOURCES, S.EVALS, S.FUNCTIONALS)
+        new = call(src, ev, fun)
+        assert gpu_ctx.point_location() == 0, name
+        assert old[-1] == 0 and new[-1] == 0
+        assert old[-2]["pcg_steps"] == new[-2]["pcg_steps"], name
+        for a, b in zip(old[:-2], new[:-2]):
+            if isinstance(a, dict):
+                assert all(np.array_equal(a[k], b[k], equal_nan=True) for k in a), name
+            elif isinstance(a, list):
+                assert all(np.array_equal(x, y) for x, y in zip(a, b)), name
+            else:
+                assert np.array_equal(a, b), name
+
+
+# ---- 2. off-axis against the reference ----------------------------------------------------------------------------------------------
+def _offaxis_case(mesh):
+    """Nine right-hand sides (two chunks): sources at an off-axis mesh vertex, an edge midpoint, interior points of elements (the 2D
+    bubble load), in 3D one in the plane y = 0 with x < 0 and one with y > 0, one right-hand side with two sources +1 / -1, one
+    axis-only right-hand side given as 1-D z.  Readings on and off the axis; the first reading of right-hand side 1 is the source of
+    right-hand side 0."""
+    dim = int(mesh.dim)
+    coords, conn = np.asarray(mesh.coords), np.asarray(mesh.conn)
+    rho = np.abs(coords[:, 0]) if dim == 2 else np.hypot(coords[:, 0], coords[:, 1])
+    near = np.flatnonzero((rho > 0.02) & (rho < 0.3) & (np.abs(coords[:, -1]) < 0.5))
+    assert near.size > 3
+    V = coords[near[near.size // 2]]
+    c = coords[conn].mean(axis=1)
+    crho = np.abs(c[:, 0]) if dim == 2 else np.hypot(c[:, 0], c[:, 1])
+    e = np.flatnonzero((crho > 0.03) & (crho < 0.25) & (np.abs(c[:, -1]) < 0.4))
+    X = coords[conn[e[e.size // 3]]]
+    M = 0.5 * (X[0] + X[1])
+    w = np.array([0.4, 0.3, 0.2, 0.1][:dim + 1]); w /= w.sum()
+    Pin = w @ coords[conn[e[2 * e.size // 3]]]
+
+    def p(x, y, z):
+        return [x, z] if dim == 2 else [x, y, z]
+    src = [(np.array([V]), [1.0]), (np.array([M]), [1.0]), (np.array([Pin]), [1.0]),
+           (np.array([p(-0.07 if dim == 3 else 0.07, 0.0, 0.05)]), [1.0]), (np.array([p(0.03, 0.06, -0.04)]), [0.5]),
+           (np.array([p(0.05, 0.0, 0.1), p(0.05, 0.0, -0.1)]), [1.0, -1.0]), ([0.0], [1.0]),
+           (np.array([p(0.3, 0.0, 1.5)]), [2.0]), (np.array([p(0.02, 0.0, 0.3)]), [1.0])]
+    ev = [np.array([p(0.0, 0.0, 0.4 + 0.1 * k), p(0.06, 0.0, 0.5 + 0.1 * k), p(0.5, 0.2, -1.0), p(0.0, 0.0, 6.4)]) for k in range(9)]
+    ev[1] = np.concatenate([np.array([V]), ev[1]])
+    ev[6] = [0.4, 6.4, -2.0]
+    return src, ev
+
+
+def _offaxis_reference(dim, tensor, mesh):
+    key = ("ref2", dim, tensor)
+    if key not in _CACHE:
+        sigma = S.general_tensors(dim) if tensor else np.array(SIGMA3)
+        src, ev = _offaxis_case(mesh)
+        ref = O.OffAxisOracle(mesh, sigma)
+        _, pot = ref.solve_batch([(O.as_points(dim, P), I) for P, I in src], [O.as_points(dim, P) for P in ev])
+        _CACHE[key] = (sigma, src, ev, pot)
+    return _CACHE[key]
+
+
+CASES = {
+    "2d_condensed": dict(dim=2, tensor=False, opts=dict(condense=True, op="csr")),
+    "2d_uncondensed": dict(dim=2, tensor=False, opts=dict(condense=False, op="csr")),
+    "2d_tensor": dict(dim=2, tensor=True, opts=dict(op="csr")),
+    "3d_csr_local": dict(dim=3, tensor=False, opts=dict(op="csr", preconditioner="local")),
+    "3d_tensor_patch_multigrid": dict(dim=3, tensor=True, opts=dict(op="patch", preconditioner="multigrid")),
+}
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_offaxis_against_the_reference(name, mesh2d, mesh3d, gpu_ctx):
+    """Potentials of the nine right-hand sides against the uncondensed oracle's: within 1e-8 of max |u_ref|."""
+    case = CASES[name]
+    mesh = _mesh(case["dim"], mesh2d, mesh3d)
+    sigma, src, ev, ref = _offaxis_reference(case["dim"], case["tensor"], mesh)
+    pots, st, rc = gpu_ctx.solve_batch(mesh, sigma, src, ev, _opts(**case["opts"]))
+    assert rc == 0 and gpu_ctx.point_location() == 1
+    got, want = np.concatenate(pots), np.concatenate(ref)
+    err = float(np.max(np.abs(got - want)) / np.max(np.abs(want)))
+    print("OFFAXIS {:28s} max |u - u_ref| / max |u_ref| = {:.3e}  ms_eval = {:.3f}  pcg_steps = {}".format(name, err, st["ms_eval"], st["pcg_steps"]))
+    assert not np.any(np.isnan(got))
+    assert err <= 1e-8
+
+
+def test_location_cost_of_the_3d_case(mesh3d, gpu_ctx):
+    """ms_eval of the 3D case with its points moved onto the axis (k_locate) beside the off-axis batch (field_locate): printed for
+    DESIGN 3.6; both runs must succeed."""
+    from remo3d_amd.solver import axis_points
+    sigma, src, ev, _ = _offaxis_reference(3, False, mesh3d)
+    on = ([(axis_points(3, O.as_points(3, P)[:, 2]), I) for P, I in src], [axis_points(3, O.as_points(3, P)[:, 2]) for P in ev])
+    o = _opts(op="csr", preconditioner="local")
+    ms = {}
+    for label, (s, e), where in (("axis", on, 0), ("off", (src, ev), 1)):
+        gpu_ctx.solve_batch(mesh3d, sigma, s, e, o)
+        _, st, rc = gpu_ctx.solve_batch(mesh3d, sigma, s, e, o)
+        assert rc == 0 and gpu_ctx.point_location() == where
+        ms[label] = st["ms_eval"]
+    print("OFFAXIS ms_eval 3D, {} points: all-axis {:.3f} ms, off-axis {:.3f} ms".format(sum(len(O.as_points(3, P)) for P in ev) + 10, ms["axis"], ms["off"]))
+
+
+# ---- 3. closed form -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dim", [2, 3])
+def test_offaxis_sources_in_a_homogeneous_ball(dim, mesh2d, mesh3d, gpu_ctx):
+    """Homogeneous sigma: twice Kelvin's image solution (3D) and its ring average (2D) for the sources and points of the CPU proof of
+    the reference: within 5e-3."""
+    mesh = _mesh(dim, mesh2d, mesh3d)
+    pts = np.array(O.KELVIN_POINTS[dim])
+    src = [(np.array([s]), [1.0]) for s in O.KELVIN_SOURCES[dim]]
+    pots, _, rc = gpu_ctx.solve_batch(mesh, [0.5, 0.5, 0.5], src, [pts] * len(src), _opts())
+    assert rc == 0
+    for s, got in zip(O.KELVIN_SOURCES[dim], pots):
+        exact = np.array([O.closed_form(dim, s, p, 0.5) for p in pts])
+        err = float(np.max(np.abs(got - exact) / np.abs(exact)))
+        print("OFFAXIS closed form {}D source {}: {:.3e}".format(dim, s, err))
+        assert err <= 5e-3
+
+
+# ---- 4. reciprocity -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dim,op", [(2, "csr"), (3, "csr"), (3, "patch")])
+def test_reciprocity_between_two_offaxis_points(dim, op, mesh2d, mesh3d, gpu_ctx):
+    """u_A(B) = u_B(A) for unit currents at two off-axis points in different materials: within 1e-8 relative."""
+    mesh = _mesh(dim, mesh2d, mesh3d)
+    A = np.array([[0.05, 0.2]]) if dim == 2 else np.array([[0.05, 0.0, 0.2]])
+    B = np.array([[0.5, 1.5]]) if dim == 2 else np.array([[0.4, 0.3, 1.5]])
+    pots, _, rc = gpu_ctx.solve_batch(mesh, SIGMA3, [(A, [1.0]), (B, [1.0])], [B, A], _opts(op=op))
+    assert rc == 0
+    a, b = float(pots[0][0]), float(pots[1][0])
+    print("OFFAXIS reciprocity {}D {}: {:.3e}".format(dim, op, abs(a - b) / abs(a)))
+    assert abs(a - b) <= 1e-8 * abs(a)
+
+
+# ---- 5. sensitivities ---------------------------------------------------------------------------------------------------------------
+def _sens_case(dim):
+    def p(x, y, z):
+        return [x, z] if dim == 2 else [x, y, z]
+    src = [(np.array([p(0.04, 0.0, 0.0)]), [1.0]), (np.array([p(0.04, 0.0, 0.1)]), [1.0]), (np.array([p(0.04, 0.0, -0.1), p(0.04, 0.0, 0.1)]), [1.0, -1.0])]
+    ev = [np.array([p(0.04, 0.0, 0.4)]), np.array([p(0.04, 0.0, 2.1)]), np.array([p(0.0, 0.0, 0.5)])]
+    fun = [(0, np.array([p(0.04, 0.0, 0.4), p(0.04, 0.0, 6.4)]), [-1.0, 1.0]), (0, np.array([p(0.04, 0.0, 0.4)]), [1.0]),
+           (1, np.array([p(0.04, 0.0, 2.1), p(0.04, 0.0, 2.6)]), [-1.0, 1.0]), (2, np.array([p(0.3, 0.1, 3.0)]), [1.0])]
+    return src, ev, fun
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_offaxis_sensitivities_groups_and_warm_start(dim, mesh2d, mesh3d, gpu_ctx):
+    """Functionals u(p_N) - u(p_M) at off-axis points: dJ against the adjoint identity of tests/_offaxis.py within 4.12e-8
+    (rel_to_scale), the sums of one grouping against the identity with the groups' matrices within 1e-6 of the same scale, and a
+    warm second call at sigma x 1.01 within the same bounds.  (A uniform factor c on sigma divides u and lambda by c and leaves every
+    A_k as it is: J / c and dJ / c^2 are the reference of the second call.)"""
+    from remo3d_amd import solver
+    mesh = _mesh(dim, mesh2d, mesh3d)
+    src, ev, fun = _sens_case(dim)
+    c = mesh.coords[mesh.conn].mean(axis=1)
+    rho = np.abs(c[:, 0]) if dim == 2 else np.hypot(c[:, 0], c[:, 1])
+    groups = (np.where(rho < 0.1, 0, np.where(rho < 1.0, 1, 2)) + 3 * (c[:, -1] > 0.3)).astype(np.int32)
+    groups[rho > 20.0] = -1
+    sigma = np.array(SIGMA3)
+    J_ref, dJ_ref, dJg_ref = O.offaxis_adjoint(mesh, sigma, src, fun, per_element=groups)
+    scale = np.max(np.abs(sigma[None] * dJ_ref), axis=1)
+    o = _opts()
+    pots, J, dJ, dJg, st, rc = gpu_ctx.solve_batch_sens_groups(mesh, sigma, src, ev, fun, groups, 6, o)
+    assert rc == 0 and gpu_ctx.point_location() == 1
+    e_mat = S.rel_to_scale(dJ, dJ_ref, sigma)
+    e_grp = float(np.max(np.abs(dJg - dJg_ref) / scale[:, None]))
+    print("OFFAXIS sens {}D: dJ {:.3e}  groups {:.3e}  J {:.3e}".format(dim, e_mat, e_grp, float(np.max(np.abs(J - J_ref) / np.abs(J_ref)))))
+    assert np.max(np.abs(J - J_ref)) <= 1e-8 * np.max(np.abs(J_ref))
+    assert e_mat <= 4.12e-8
+    assert e_grp <= 1e-6
+    with solver.WarmState(0) as warm:
+        _, J0, dJ0, _, rc0 = gpu_ctx.solve_batch_sens(mesh, sigma, src, ev, fun, o, warm=warm)
+        assert rc0 == 0 and warm.info()["used_last"] == 0
+        _, J1, dJ1, _, rc1 = gpu_ctx.solve_batch_sens(mesh, 1.01 * sigma, src, ev, fun, o, warm=warm)
+        assert rc1 == 0 and warm.info()["used_last"] == 1
+    assert S.rel_to_scale(dJ0, dJ_ref, sigma) <= 4.12e-8
+    e_warm = S.rel_to_scale(dJ1, dJ_ref / 1.01 ** 2, 1.01 * sigma)
+    print("OFFAXIS sens {}D warm: dJ {:.3e}".format(dim, e_warm))
+    assert e_warm <= 4.12e-8
+    assert np.max(np.abs(J1 - J_ref / 1.01)) <= 1e-8 * np.max(np.abs(J_ref))
+
+
+# ---- 6. field and resident form -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dim", [2, 3])
+def test_field_and_resident_form_with_offaxis_sources(dim, mesh2d, mesh3d, gpu_ctx):
+    """solve_batch_field with off-axis sources reads u_out's values at the off-axis evaluation points (1e-12 relative); a Batch made
+    by remo_batch_create_job has the bits of the one-shot job and Batch.field those of the one-shot field (op = 2)."""
+    from remo3d_amd import solver
+    mesh = _mesh(dim, mesh2d, mesh3d)
+    src, ev, _ = _sens_case(dim)
+    o = _opts(op="csr")
+    P = np.concatenate(ev)
+    pots, field, st, rc = gpu_ctx.solve_batch_field(mesh, SIGMA3, src, ev, P, None, o)
+    assert rc == 0 and gpu_ctx.point_location() == 1
+    at = np.cumsum([0] + [len(e) for e in ev])
+    for k in range(len(src)):
+        got, want = field["u"][k, at[k]:at[k + 1]], pots[k]
+        assert np.max(np.abs(got - want)) <= 1e-12 * np.max(np.abs(want))
+    one, _, rc = gpu_ctx.solve_batch(mesh, SIGMA3, src, ev, o)
+    assert rc == 0 and all(np.array_equal(a, b) for a, b in zip(one, pots))
+    b = solver.Batch(gpu_ctx, mesh, SIGMA3, src, ev)
+    try:
+        assert b.run(o) == 0 and gpu_ctx.point_location() == 1
+        assert all(np.array_equal(x, y) for x, y in zip(b.fetch(), one))
+        for k in range(len(src)):
+            f = b.field(k, P)
+            assert np.array_equal(f["u"], field["u"][k]) and np.array_equal(f["grad"], field["grad"][k])
+            assert np.array_equal(f["J"], field["J"][k]) and np.array_equal(f["elem"], field["elem"])
+    finally:
+        b.close()
+
+
+# ---- 7. errors ----------------------------------------------------------------------------------------------------------------------
+def _job(gpu_ctx, mesh, src, ev, o, fun=None, points=None):
+    """One raw remo_solve_job with functionals AND field points where given (no Context method asks for that): (rc, outputs)."""
+    import ctypes as C
+    from remo3d_amd import _lib, solver
+    from remo3d_amd._lib import ptr
+    d = int(mesh.dim)
+    args, sigma, _, eval_ptr, keep = solver._batch_args(gpu_ctx._h, mesh, SIGMA3, src, ev, True)
+    j = args[2]
+    out = dict(u=np.zeros(int(eval_ptr[-1])))
+    j.u_out = ptr(out["u"], C.c_double)
+    if fun is not None:
+        fun_rhs, fun_ptr, fp, fw = solver._functional_arrays(fun, d)
+        out.update(J=np.zeros(len(fun)), dJ=np.zeros((len(fun), len(sigma))))
+        j.n_fun, j.fun_rhs, j.fun_ptr, j.fun_p, j.fun_w = len(fun), ptr(fun_rhs, C.c_int32), ptr(fun_ptr, C.c_int32), ptr(fp, C.c_double), ptr(fw, C.c_double)
+        j.J_out, j.dJ_out = ptr(out["J"], C.c_double), ptr(out["dJ"], C.c_double)
+    if points is not None:
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        frhs = np.arange(len(src), dtype=np.int32)
+        out.update(u_f=np.zeros((len(src), len(points))), grad_f=np.zeros((len(src), len(points), d)), J_f=np.zeros((len(src), len(points), d)),
+                   elem_f=np.zeros(len(points), dtype=np.int32))
+        j.n_pts, j.pts, j.n_frhs, j.field_rhs = len(points), ptr(points, C.c_double), len(src), ptr(frhs, C.c_int32)
+        j.u_f, j.grad_f, j.J_f, j.elem_f = ptr(out["u_f"], C.c_double), ptr(out["grad_f"], C.c_double), ptr(out["J_f"], C.c_double), ptr(out["elem_f"], C.c_int32)
+    st = _lib.RemoStats()
+    rc = gpu_ctx._L.remo_solve_job(args[0], args[1], C.byref(j), C.byref(o), C.byref(st))
+    return rc, out
+
+
+def _all_nan(out):
+    return all(np.all(v == -1) if k == "elem_f" else np.all(np.isnan(v)) for k, v in out.items())
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_error_paths(dim, mesh2d, mesh3d, gpu_ctx):
+    """A source in no element (3D: y < 0; beyond the domain radius), a non-finite coordinate: REMO_ERR_POINT; field points together
+    with functionals, precision = 1 with functionals: REMO_ERR_ARG.  Every output NaN (elem_f -1), and the context solves a good
+    batch afterwards."""
+    mesh = _mesh(dim, mesh2d, mesh3d)
+    src, ev, fun = _sens_case(dim)
+    o = _opts(op="csr")
+    good, _, rc = gpu_ctx.solve_batch(mesh, SIGMA3, src, ev, o)
+    assert rc == 0
+
+    def moved(P):
+        return [(np.array([P]), [1.0])] + src[1:]
+    bad_points = [[60.0] + [0.0] * (dim - 1), [0.05] + [0.0] * (dim - 2) + [np.nan], [np.inf] + [0.0] * (dim - 1)]
+    if dim == 3:
+        bad_points.append([0.05, -0.1, 0.0])
+    for P in bad_points:
+        rc, out = _job(gpu_ctx, mesh, moved(P), ev, o, fun=fun)
+        assert rc == -4 and _all_nan(out), P
+        rc, out = _job(gpu_ctx, mesh, moved(P), ev, o, points=np.concatenate(ev))
+        assert rc == -4 and _all_nan(out), P
+        pots, _, rc = gpu_ctx.solve_batch(mesh, SIGMA3, moved(P), ev, o, raise_on_error=False)
+        assert rc == -4 and all(np.all(np.isnan(p)) for p in pots)
+    rc, out = _job(gpu_ctx, mesh, src, ev[:2] + [np.array([[np.nan] * dim])], o)
+    assert rc == -4 and _all_nan(out)
+    rc, out = _job(gpu_ctx, mesh, src, ev, o, fun=fun, points=np.concatenate(ev))
+    assert rc == -1 and _all_nan(out)
+    rc, out = _job(gpu_ctx, mesh, src, ev, _opts(op="csr", precision="mixed"), fun=fun)
+    assert rc == -1 and _all_nan(out)
+    rc, out = _job(gpu_ctx, mesh, src, ev, _opts(op="csr", precision="mixed"), points=np.concatenate(ev))
+    assert rc == -1 and _all_nan(out)
+    again, _, rc = gpu_ctx.solve_batch(mesh, SIGMA3, src, ev, o)
+    assert rc == 0 and all(np.array_equal(a, b) for a, b in zip(again, good))
+
+
+# ---- 8. / 9. Model -----------------------------------------------------------------------------------------------------------------
+_TOOLS = ["A0.4M6.0N", "A2.0M0.5N"]
+_RT = 10.0
+# The ratios were first asserted at the closed-form bound 5e-3.  Measured on the MI355X: at most 1.80e-4 from 1 at dip 30 (e = 0.05
+# against 0) and 1.5e-6 at dip 0 (+0.05 against -0.05) - more than ten times below it, so the tests assert ten times the largest.
+RATIO_BOUND = 1.8e-3
+
+
+def _homogeneous_bm3(dip_deg, eccentricity, **kw):
+    """BM3's geometry with one resistivity everywhere, mud included (the configuration of
+    test_model_section_of_a_homogeneous_3d_model_is_a_point_source): domain radius 12 m, mesh scale 2.5, three depths, both tools."""
+    import os
+    from remo3d_amd.model import Model
+    key = ("model", dip_deg, eccentricity, tuple(sorted(kw)))
+    if key not in _CACHE:
+        bm3 = os.path.join(os.path.dirname(__file__), "golden", "examples", "Benchmark models", "Benchmark model 3")
+        f = np.loadtxt(os.path.join(bm3, "Formation_BM3_%02d.txt" % dip_deg), skiprows=2)
+        f[:, 3:5] = np.where(np.isnan(f[:, 3:5]), np.nan, _RT)
+        b = np.loadtxt(os.path.join(bm3, "Borehole_BM3.txt"), skiprows=2)
+        b[:, 1] *= 1e-3
+        b[:, 2] = _RT
+        m = Model.compute_synthetic_logs(_TOOLS, np.array([6.0, 6.5, 7.0]), f, b, borehole_geometry_type="diameter", dip=dip_deg, domain_radius=12.0,
+                                         verbose=False, mesh_scale=2.5, gpu_workers=1, solver_options=dict(rtol=1e-10, maxsteps=20000),
+                                         eccentricity=eccentricity, **kw)
+        assert m.timing["failed_batches"] == 0, m.timing["first_error"]
+        _CACHE[key] = (m, f, b)
+    return _CACHE[key]
+
+
+def _log_ratios(a, b, label):
+    worst = 0.0
+    for name in _TOOLS:
+        ra, rb = a.logs[name][:, 1], b.logs[name][:, 1]
+        assert not np.any(np.isnan(ra)) and not np.any(np.isnan(rb))
+        print("OFFAXIS model {} {}: Ra {} / {} ratios {}".format(label, name, ra, rb, ra / rb))
+        worst = max(worst, float(np.max(np.abs(ra / rb - 1.0))))
+    return worst
+
+
+def test_model_eccentred_tool_in_a_homogeneous_dipping_model():
+    """Rm = Rt everywhere: the logs of a tool displaced by 0.05 m equal those of the centred tool up to discretisation (the grounded
+    sphere is common to both runs to O(e / R)): ratios within RATIO_BOUND of 1 at dip 30; model.eccentricity records the value."""
+    ecc, _, _ = _homogeneous_bm3(30, 0.05)
+    cen, _, _ = _homogeneous_bm3(30, 0.0)
+    assert ecc.eccentricity == 0.05 and cen.eccentricity == 0.0
+    assert _log_ratios(ecc, cen, "dip 30, e = 0.05 against 0") <= RATIO_BOUND
+
+
+def test_model_eccentred_tool_between_flat_beds_runs_in_3d():
+    """Dip 0: +0.05 against -0.05 (the direction is immaterial between flat beds; both runs take the 3D path): within RATIO_BOUND."""
+    plus, _, _ = _homogeneous_bm3(0, 0.05)
+    minus, _, _ = _homogeneous_bm3(0, -0.05)
+    assert _log_ratios(plus, minus, "dip 0, e = +0.05 against -0.05") <= RATIO_BOUND
+    assert abs(float(plus.logs[_TOOLS[0]][0, 1]) / _RT - 1.0) < 0.05      # a homogeneous medium reads its own resistivity (3D path, halved)
+
+
+def test_model_sum_rule_of_an_eccentred_tool():
+    """sensitivities=True on the eccentred dip-30 run: sum over layers of R dRa/dR plus Rm dRa/dRm equals Ra to 1e-5, the
+    Model-level bound of DESIGN 3.3 (Ra is homogeneous of degree 1 in the resistivities)."""
+    m, f, b = _homogeneous_bm3(30, 0.05, sensitivities=True)
+    worst = 0.0
+    for name in _TOOLS:
+        s = m.sensitivities[name]
+        total = np.nansum(s * f[None, :, 2:2 + s.shape[2]], axis=(1, 2)) + m.mud_sensitivity[name] * _RT
+        ra = m.logs[name][:, 1]
+        assert not np.any(np.isnan(ra))
+        worst = max(worst, float(np.max(np.abs(total / ra - 1.0))))
+    print("OFFAXIS model sum rule, eccentred dip 30: {:.3e}".format(worst))
+    assert worst <= 1e-5
+
+
+def test_model_zero_eccentricity_is_the_centred_run(examples_dir):
+    """Example_01 (2D): eccentricity=0.0 gives the logs of a run without the keyword, bit for bit."""
+    import os
+    from remo3d_amd.model import Model
+    ex = os.path.join(examples_dir, "Example_01", "Input")
+    f = np.loadtxt(os.path.join(ex, "Formation.txt"), skiprows=2)
+    b = np.loadtxt(os.path.join(ex, "Borehole.txt"), skiprows=2)
+    b[:, 1] *= 1e-3
+    depths = np.array([8.3, 12.45])
+    kw = dict(borehole_geometry_type="diameter", domain_radius=50.0, verbose=False, mesh_scale=1.0, gpu_workers=1,
+              solver_options=dict(op="csr"))
+    a = Model.compute_synthetic_logs(_TOOLS, depths, f, b, **kw)
+    z = Model.compute_synthetic_logs(_TOOLS, depths, f, b, eccentricity=0.0, **kw)
+    assert a.timing["failed_batches"] == 0 and z.timing["failed_batches"] == 0
+    for name in _TOOLS:
+        assert not np.any(np.isnan(a.logs[name])) and np.array_equal(a.logs[name], z.logs[name])
