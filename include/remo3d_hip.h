@@ -331,6 +331,33 @@ int remo_solve_batch_field_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int3
  * with op = 2 its outputs carry the bits of the entry it stands for.  Otherwise all its points are located through the cell grid of
  * remo_solve_batch_field (same tolerances, lowest element number among several that hold a point).  A point in no element gives
  * REMO_ERR_POINT - in the half ball that includes y < 0 - and a non-finite coordinate gives REMO_ERR_POINT before any device work.
+ *
+ * secondary = 1: the SECONDARY-POTENTIAL formulation (added within ABI 7: four members BEHIND the job - remo_job_secondary_t below, a
+ * job with size = sizeof(remo_job_secondary_t) - which a caller's smaller size leaves zero).  u = u_p + u_s with u_p the closed-form potential of the right-hand side's sources in a
+ * homogeneous medium sigma0 inside a grounded sphere of radius sec_radius centred at the origin of the batch frame,
+ *     u_p = I / (4 pi sigma0) G(x; a),   G(x; a) = 1 / |x - a| - (R / |a|) / |x - a*|,   a* = R^2 a / |a|^2
+ * (|a| <= 1e-9 R: the image term is -1 / R; R = 0: no image term; 3D half ball: G(x; a) + G(x; a mirrored in y = 0), which gives a
+ * source in the plane the 2 I of the convention above), and u_s the finite-element solution of
+ *     a_Sigma(u_s, v) = - int (Sigma - sigma0 I) grad(u_p) . grad(v),   u_s = 0 on the Dirichlet boundary:
+ * same operator, preconditioner and PCG, another load vector.  The integrand vanishes where Sigma = sigma0 I, so with sigma0 the
+ * conductivity around the sources the elements never resolve a 1 / r singularity.  Per element with Sigma_e != sigma0 I
+ *     f_e[i] = - sum_q w_q |T| (2 pi r_q in 2D) grad(phi_i)(x_q)^T (Sigma_e - sigma0 I) grad(u_p)(x_q)
+ * by the collapsed (conical) Gauss-Legendre product rule with n = sec_quad points per direction on [0, 1] (0: the default, 7):
+ *     2D  l_1 = u, l_2 = v (1 - u), weight 2 (1 - u) w_u w_v;   3D  l_1 = u, l_2 = v (1 - u), l_3 = w (1 - u)(1 - v), weight
+ *     6 (1 - u)^2 (1 - v) w_u w_v w_w;   l_0 = 1 - the others, barycentrics of the element's vertices sorted by number.
+ * The element vectors are added into f row by row in ascending element order (no floating-point atomics): with op = 2 two calls
+ * give the same bits.  In 2D with condense = 1 every contributing element has a bubble load; it is folded into the nine outer
+ * rows (f_j -= K_j9 f_9 / K_99) and used again when the bubble of an evaluation point's element is recovered.
+ * u_out = u_s + u_p at every evaluation point.  A homogeneous model (Sigma = sigma0 I everywhere) has f = 0: u_s = 0, 0
+ * iterations, REMO_OK.  sec_sigma0[n_rhs] is the background of every right-hand side; NULL, or an entry 0.0, stands for the
+ * (scalar) conductivity of the element that holds the right-hand side's first source of non-zero strength.
+ * Errors: an evaluation point on a source of its right-hand side, and a source in or on (k_locate's tolerance) an element with
+ * Sigma_e != sigma0 I - a source on a conductivity contrast - give REMO_ERR_POINT.  Refused with REMO_ERR_ARG before any device
+ * work: secondary together with functionals, groups, a warm object or field points; precision = 1; in 2D a source at r != 0.0 (a
+ * ring); a sec_sigma0 entry that is negative or not finite; sec_quad outside [0, 16]; a negative sec_radius; and, where sigma0 is
+ * left to the library, a source in an anisotropic material or sources of one right-hand side in materials of different
+ * conductivity.  remo_batch_create_job reads the four members too (remo_batch_get_vectors then shows this f and u_s);
+ * remo_batch_eval and remo_batch_field read u_h alone and refuse such a batch.
  */
 typedef struct {
     uint32_t size;                 /* sizeof(remo_job_t) as the caller compiled it */
@@ -343,6 +370,18 @@ typedef struct {
     remo_warm_t *warm;                                            /* NULL: cold */
     int32_t n_pts; const double *pts; int32_t n_frhs; const int32_t *field_rhs; double *u_f, *grad_f, *J_f; int32_t *elem_f;
 } remo_job_t;
+/* The job grown at its end by the four members of the secondary-potential formulation (see above): the same bytes as a remo_job_t
+ * with the members appended - job is 232 bytes, a multiple of every member's alignment, so nothing is padded - under a name of its
+ * own, so that sizeof(remo_job_t) stays what callers compiled against it know.  Set job.size = sizeof(remo_job_secondary_t) and hand
+ * &x.job to remo_solve_job / remo_batch_create_job. */
+typedef struct {
+    remo_job_t job;
+    int32_t secondary;          /* 0: as before, bit for bit.  1: secondary-potential formulation */
+    int32_t sec_quad;           /* points per direction of the element rule, 0 = default */
+    double  sec_radius;         /* R of the grounded sphere of the primary field, 0 = none */
+    const double *sec_sigma0;   /* [n_rhs] background conductivity per right-hand side; NULL or 0.0 = the (scalar) conductivity
+                                   of the element that holds the right-hand side's first source */
+} remo_job_secondary_t;
 int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, const remo_opts_t *opts, remo_stats_t *stats);
 
 /*
@@ -427,6 +466,13 @@ int remo_host_field_element(int32_t dim, const double *vertex_coords, const doub
  * the element with sorted vertices vertex_coords - what a source there adds to the load, times I, and what a reading there weighs
  * the element vector with.  REMO_ERR_MESH for a degenerate element. */
 int remo_host_point_shapes(int32_t dim, const double *vertex_coords, const double *point, double *phi_out);
+/* One element's load vector of the secondary formulation on the host (the code the kernel runs): f_out[nld] for a unit current at
+ * src [dim] in the background sigma0 inside a grounded sphere of radius `radius` (0: none), n_quad points per direction (0: the
+ * default); sigma_tensor != NULL: the upper triangle of the element's tensor, else the scalar sigma.  The raw element vector: no
+ * bubble fold.  Sigma_e = sigma0 I gives exact zeros.  REMO_ERR_MESH for a degenerate element. */
+int remo_host_secondary_element(int32_t dim, const double *vertex_coords, const double *sigma_tensor, double sigma,
+                                double sigma0, double radius, const double *src /*[dim]*/, int32_t n_quad,
+                                double *f_out /*[nld]*/);
 /* max |sum_m B_a[m][i] B_b[m][j] - M_ab[i][j]|: how well the factorised reference tensors of the patch operator
  * (remo_opts_t.op = 3) reproduce the tensors the CSR assembly contracts (both exact polynomial integrals). */
 double remo_host_factor_error(void);

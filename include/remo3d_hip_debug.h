@@ -60,6 +60,9 @@ int remo_debug_field_timing(remo_ctx_t *ctx, double *out2);
 /* How the last remo_batch_run on this context located the points of its right-hand sides: 0 = the kernels of the axis entries (every
  * lateral coordinate exactly 0), 1 = the cell grid of the field sections (a batch of remo_solve_job with a point off the axis). */
 int remo_debug_point_location(remo_ctx_t *ctx);
+/* The load-vector launches (element vectors + row sums, all chunks) of the last remo_batch_run of a batch with remo_job_secondary_t.secondary
+ * on this context, ms by HIP events; 0 when the last run was none. */
+int remo_debug_secondary_timing(remo_ctx_t *ctx, double *ms);
 
 /* Process-global knobs, two kinds.  Returns 0, or -1 for a key this build does not have.
  *

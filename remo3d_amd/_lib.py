@@ -61,6 +61,13 @@ class RemoJob(C.Structure):
                 ("elem_f", _ip)]
 
 
+class RemoJobSecondary(C.Structure):
+    """remo_job_secondary_t: a remo_job_t with the four members of the secondary-potential formulation behind it (the job's members
+    are repeated here flat: the same bytes as the header's nested form, and they can be set by name like a RemoJob's)."""
+    _fields_ = RemoJob._fields_ + [("secondary", C.c_int32), ("sec_quad", C.c_int32), ("sec_radius", C.c_double),
+                                   ("sec_sigma0", C.POINTER(C.c_double))]
+
+
 # include/remo3d_hip.h: the drop-in boundary + inspection hooks of the parity tests
 EXPORTS = ["remo_abi_version", "remo_opts_default", "remo_ctx_create", "remo_ctx_destroy", "remo_last_error",
            "remo_solve_batch", "remo_solve_batch_tensor", "remo_solve_batch_sens", "remo_solve_batch_sens_tensor", "remo_solve_batch_sens_groups", "remo_solve_batch_sens_groups_tensor",
@@ -68,9 +75,9 @@ EXPORTS = ["remo_abi_version", "remo_opts_default", "remo_ctx_create", "remo_ctx
            "remo_warm_create", "remo_warm_destroy", "remo_warm_clear", "remo_warm_info", "remo_solve_batch_sens_warm", "remo_solve_batch_sens_warm_tensor", "remo_batch_create", "remo_batch_create_tensor", "remo_batch_run", "remo_batch_fetch", "remo_batch_destroy",
            "remo_batch_eval", "remo_batch_get_system", "remo_batch_get_vectors", "remo_batch_apply_coarse", "remo_batch_spmv",
            "remo_host_element_matrix", "remo_host_element_matrix_tensor", "remo_host_sens_element", "remo_host_factor_error", "remo_host_symbolic",
-           "remo_solve_job", "remo_batch_create_job", "remo_host_point_shapes"]
+           "remo_solve_job", "remo_batch_create_job", "remo_host_point_shapes", "remo_host_secondary_element"]
 # include/remo3d_hip_debug.h: probes and tuning knobs (tests, tools, bench.py's `box` record) - not part of the boundary
-DEBUG_EXPORTS = ["remo_debug_stream", "remo_debug_clock", "remo_debug_device", "remo_debug_cache_gather", "remo_debug_xcc", "remo_debug_tune", "remo_debug_patch_phases", "remo_debug_patch_phases_p", "remo_debug_grid_barrier", "remo_debug_sens_timing", "remo_debug_sens_group_timing", "remo_debug_field_timing", "remo_debug_point_location"]
+DEBUG_EXPORTS = ["remo_debug_stream", "remo_debug_clock", "remo_debug_device", "remo_debug_cache_gather", "remo_debug_xcc", "remo_debug_tune", "remo_debug_patch_phases", "remo_debug_patch_phases_p", "remo_debug_grid_barrier", "remo_debug_sens_timing", "remo_debug_sens_group_timing", "remo_debug_field_timing", "remo_debug_point_location", "remo_debug_secondary_timing"]
 
 SENS_GROUPS_ARGTYPES = []     # argument list of remo_solve_batch_sens_groups / _tensor, filled by load()
 
@@ -132,9 +139,9 @@ def load():
     L.remo_solve_batch_field_tensor.restype = C.c_int
     L.remo_solve_batch_field_tensor.argtypes = list(field_args)
     L.remo_solve_job.restype = C.c_int
-    L.remo_solve_job.argtypes = [vp, C.POINTER(RemoMesh), C.POINTER(RemoJob), C.POINTER(RemoOpts), C.POINTER(RemoStats)]
+    L.remo_solve_job.argtypes = [vp, C.POINTER(RemoMesh), vp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]     # the job: RemoJob or RemoJobSecondary
     L.remo_batch_create_job.restype = C.c_int
-    L.remo_batch_create_job.argtypes = [vp, C.POINTER(RemoMesh), C.POINTER(RemoJob), C.POINTER(vp)]
+    L.remo_batch_create_job.argtypes = [vp, C.POINTER(RemoMesh), vp, C.POINTER(vp)]
     L.remo_host_point_shapes.restype = C.c_int
     L.remo_host_point_shapes.argtypes = [C.c_int32, dp, dp, dp]
     L.remo_batch_field.restype = C.c_int
@@ -145,6 +152,10 @@ def load():
     L.remo_debug_field_timing.argtypes = [vp, dp]
     L.remo_debug_point_location.restype = C.c_int
     L.remo_debug_point_location.argtypes = [vp]
+    L.remo_host_secondary_element.restype = C.c_int
+    L.remo_host_secondary_element.argtypes = [C.c_int32, dp, dp, C.c_double, C.c_double, C.c_double, dp, C.c_int32, dp]
+    L.remo_debug_secondary_timing.restype = C.c_int
+    L.remo_debug_secondary_timing.argtypes = [vp, dp]
     L.remo_debug_sens_group_timing.restype = C.c_int
     L.remo_debug_sens_group_timing.argtypes = [vp, dp]
     L.remo_host_sens_element.restype = C.c_int

@@ -18,6 +18,7 @@
 #include "sens.h"
 #include "field.h"
 #include "warm.h"
+#include "secondary.h"
 
 using namespace remo;
 
@@ -118,6 +119,7 @@ struct Plan {
     int64_t vertex_block_above = -1;    // build_symbolic_gpu: element count above which only the P1 block gets a pattern
     size_t field_bytes = 0;             // remo_solve_batch_field: everything field_take takes (Field::bytes)
     size_t point_locate_bytes = 0;      // points off the axis: their coordinates beyond z and the buffers of field_locate (take_points)
+    size_t secondary_bytes = 0;         // remo_job_secondary_t.secondary: everything take_secondary takes (Secondary::bytes)
     size_t arena_bytes = 0;
 };
 
@@ -138,6 +140,7 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
     need += size_t(kMaxPartialBlocks) * 8 * 8 * 3;                   // part_pq, part_rz (rz0, d_bound and the flags ride on the slack below)
     need += size_t(npts) * (N + 8) * 8;                              // d_pz, d_pI, d_prhs, d_found, d_phi, d_fint, d_out
     need += p.point_locate_bytes;                                    // off the axis: d_pz holds dim coordinates; the location's buffers
+    need += p.secondary_bytes;                                       // secondary formulation: d_rule, d_src, d_ptr, d_fe, d_fbub
     need += p.field_bytes;                                           // field sections: d_pts, d_found, d_elem, d_u, d_grad, d_J and the location's buffers
     need += (1 << 20);                                               // alignment of every take + the small buffers
     if (p.x_ev_only) {   // slots + values instead of x
@@ -170,10 +173,11 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
     return need;
 }
 
-Plan plan_batch(const remo_batch *b, const remo_opts_t &o, const Points &pts, size_t field_bytes) {
+Plan plan_batch(const remo_batch *b, const remo_opts_t &o, const Points &pts, size_t field_bytes, size_t secondary_bytes) {
     Plan p;
     const int dim = b->dim, npts = pts.n();
     p.field_bytes = field_bytes;
+    p.secondary_bytes = secondary_bytes;
     p.point_locate_bytes = pts.on_axis ? 0 : align_up(size_t(npts + 1) * dim * 8) + align_up(pts.locate_bytes);
     p.kmax = std::min<int>(std::max(b->n_rhs, b->sens ? b->sens->n_fun : 0), REMO_MAX_RHS);   // the adjoint columns run through the same buffers
     // one-shot fp64 solve: no x, only the values the evaluation points read (PcgBuffersT::x_ev); the debug forms of the update
@@ -329,6 +333,7 @@ struct DevicePoints {
     int64_t *d_ev_at = nullptr;   // x_ev_only: slots and values of the solution the points read
     double *d_x_ev = nullptr;
     FieldLocate loc{};            // points off the axis: d_pz holds dim coordinates per point, and the buffers of field_locate
+    bool full = false;            // d_pz holds dim coordinates per point (points off the axis), else z alone
 };
 
 DevicePoints take_points(const Run &r, const Plan &plan, const Points &pts) {
@@ -336,6 +341,7 @@ DevicePoints take_points(const Run &r, const Plan &plan, const Points &pts) {
     const int npts = pts.n();
     DevicePoints p;
     p.npts = npts;
+    p.full = !pts.on_axis;
     p.d_pz = ctx->take<double>(pts.on_axis ? size_t(npts + 1) : size_t(npts + 1) * r.dim); p.d_pI = ctx->take<double>(npts + 1);
     p.d_prhs = ctx->take<int32_t>(npts + 1); p.d_found = ctx->take<int32_t>(npts + 1);
     p.d_phi = ctx->take<double>(size_t(npts + 1) * r.N); p.d_fint = ctx->take<double>(npts + 1); p.d_out = ctx->take<double>(npts + 1);
@@ -372,6 +378,88 @@ void locate_points(const Run &r, const Points &pts, const DevicePoints &dp) {
     for (int q0 = 0; q0 < dp.npts; q0 += kMaxPoints)
         launch_locate(r.dim, b->nt, b->d_coords, sy.conn, std::min(kMaxPoints, dp.npts - q0), dp.d_pz + q0, dp.d_found + q0, r.s);
     launch_point_shapes(r.dim, dp.npts, dp.d_pz, dp.d_found, b->d_coords, sy.conn, dp.d_phi, r.ctx->d_err, r.s);
+}
+
+// ---- secondary-potential formulation: the load vector is an element integral instead of point values (secondary.hip) ----------------
+struct Secondary {
+    bool on = false;
+    int nq = 0, chunks = 0;
+    double R = 0.0;
+    SecSources host;              // the sources of every chunk, column by column, with I / (4 pi sigma0) and sigma0
+    std::vector<double> rule;     // element rule [nq][dim + 2]
+    double *d_rule = nullptr, *d_src = nullptr, *d_fe = nullptr, *d_fbub = nullptr;
+    int32_t *d_ptr = nullptr;
+    size_t fe_count(const remo_batch *b, int kmax) const { return size_t(b->nt) * (b->dim == 2 ? 10 : 20) * size_t(kmax); }
+    size_t bytes(const remo_batch *b, int kmax) const {   // of take_secondary, every take rounded up
+        if (!on) return 0;
+        return align_up(rule.size() * 8) + align_up(host.src.size() * 8 + 8) + align_up(host.ptr.size() * 4) + align_up(fe_count(b, kmax) * 8) +
+               align_up(size_t(b->nt) * size_t(kmax) * 8);
+    }
+};
+
+// host part: the rule and the source records.  An evaluation point on a source of its own right-hand side has no primary potential.
+int plan_secondary(remo_ctx *ctx, const remo_batch *b, Secondary &sec) {
+    if (!b->secondary) return REMO_OK;
+    const int dim = b->dim;
+    const double pi4 = 12.566370614359172953850573533118;
+    sec.on = true;
+    sec.R = b->sec_radius;
+    const int n = b->sec_quad > 0 ? b->sec_quad : kSecQuadDefault;
+    sec.rule = sec_rule(dim, n);
+    sec.nq = int(sec.rule.size() / size_t(dim + 2));
+    for (int c0 = 0; c0 < b->n_rhs; c0 += REMO_MAX_RHS, ++sec.chunks)
+        for (int c = 0; c <= REMO_MAX_RHS; ++c) {
+            sec.host.ptr.push_back(int32_t(sec.host.n()));
+            const int r = c0 + c;
+            if (c == REMO_MAX_RHS || r >= b->n_rhs) continue;
+            for (int q = b->src_ptr[r]; q < b->src_ptr[r + 1]; ++q) {
+                if (b->src_I[q] == 0.0) continue;   // zero strengths are skipped, as in k_build_rhs
+                const double *a = &b->src_p[size_t(q) * dim];
+                for (int e = b->eval_ptr[r]; e < b->eval_ptr[r + 1]; ++e) {
+                    double d2 = 0.0, a2 = 0.0;
+                    for (int k = 0; k < dim; ++k) { const double d = b->eval_p[size_t(e) * dim + k] - a[k]; d2 += d * d; a2 += a[k] * a[k]; }
+                    if (std::sqrt(d2) <= 1e-9 * (1.0 + std::sqrt(a2)))
+                        return fail(ctx, REMO_ERR_POINT, "secondary formulation: an evaluation point lies on a source of its right-hand side");
+                }
+                const double rec[kSecSrc] = {a[0], a[1], dim == 3 ? a[2] : 0.0, b->src_I[q] / (pi4 * b->sec_sigma0[size_t(r)]), b->sec_sigma0[size_t(r)]};
+                sec.host.src.insert(sec.host.src.end(), rec, rec + kSecSrc);
+            }
+        }
+    return REMO_OK;
+}
+
+void take_secondary(const Run &r, const Plan &plan, Secondary &sec) {
+    if (!sec.on) return;
+    remo_ctx *ctx = r.ctx;
+    sec.d_rule = ctx->take<double>(sec.rule.size());
+    sec.d_src = ctx->take<double>(sec.host.src.size() + 1);
+    sec.d_ptr = ctx->take<int32_t>(sec.host.ptr.size());
+    sec.d_fe = ctx->take<double>(sec.fe_count(r.b, plan.kmax));
+    sec.d_fbub = ctx->take<double>(size_t(r.b->nt) * size_t(plan.kmax));
+}
+
+void upload_secondary(const Run &r, const Secondary &sec) {
+    if (!sec.on) return;
+    HIP_TRY(hipMemcpyAsync(sec.d_rule, sec.rule.data(), sizeof(double) * sec.rule.size(), hipMemcpyHostToDevice, r.s));
+    if (!sec.host.src.empty()) HIP_TRY(hipMemcpyAsync(sec.d_src, sec.host.src.data(), sizeof(double) * sec.host.src.size(), hipMemcpyHostToDevice, r.s));
+    HIP_TRY(hipMemcpyAsync(sec.d_ptr, sec.host.ptr.data(), sizeof(int32_t) * sec.host.ptr.size(), hipMemcpyHostToDevice, r.s));
+}
+
+// a source in or on an element whose conductivity differs from its sigma0 makes the integrand singular: bit 4 of the error flag,
+// read back with the batch's one synchronisation
+void check_secondary_sources(const Run &r, const Secondary &sec) {
+    if (!sec.on) return;
+    const remo_batch *b = r.b;
+    launch_sec_check(r.dim, b->nt, b->d_coords, b->sym.conn, b->d_mat, b->sym.eperm, b->d_sigma, b->sigma_comp, b->n_mat, sec.host.n(), sec.d_src, r.ctx->d_err, r.s);
+}
+
+// the load vectors of one chunk (d_f is the chunk's): element vectors, then the rows' sums in ascending element order
+void build_secondary_rhs(const Run &r, const System &sys, const Secondary &sec, int chunk, int k) {
+    const remo_batch *b = r.b;
+    const DeviceSymbolic &sy = b->sym;
+    launch_sec_elements(r.dim, sy.condense, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, b->d_sigma, b->sigma_comp, b->n_mat, sys.d_C, sys.d_M, sec.d_rule,
+                        sec.nq, sec.d_src, sec.d_ptr + size_t(chunk) * (REMO_MAX_RHS + 1), k, sec.R, sec.d_fe, sec.d_fbub, r.s);
+    launch_sec_gather(r.dim, sys.n, k, sy.adjptr, sy.adj, sec.d_fe, sys.d_f, r.s);
 }
 
 // ---- field sections: points anywhere in the mesh, located once per batch; every chunk's solutions are read there while they exist ----
@@ -716,7 +804,7 @@ struct RunTotals {
 
 // x_prev != nullptr: the chunk's columns of the previous call (remo_warm_t) - the solve starts from them (run_pcg_warm)
 int solve_chunk(const Run &r, const Plan &plan, const System &sys, const DevicePoints &dp, Solve &sv, MixedBuffers *mx, int k, int q0, int nq,
-                std::vector<double> &h_out, RunTotals &tot, double *x_prev = nullptr) {
+                std::vector<double> &h_out, RunTotals &tot, double *x_prev = nullptr, const Secondary *sec = nullptr, int chunk = 0) {
     remo_ctx *ctx = r.ctx;
     remo_batch *b = r.b;
     remo_stats_t *st = r.st;
@@ -726,7 +814,10 @@ int solve_chunk(const Run &r, const Plan &plan, const System &sys, const DeviceP
     PcgBuffers &buf = sv.buf;
     HIP_TRY(hipEventRecord(ctx->ev[4], s));
     HIP_TRY(hipMemsetAsync(sys.d_f, 0, sizeof(double) * sys.n * k, s));
-    if (nq > 0)
+    if (sec) {   // secondary formulation: no point values in f, no bubble loads of single sources
+        if (nq > 0) HIP_TRY(hipMemsetAsync(dp.d_fint + q0, 0, sizeof(double) * nq, s));
+        build_secondary_rhs(r, sys, *sec, chunk, k);
+    } else if (nq > 0)
         launch_build_rhs(dim, sy.condense, nq, dp.d_prhs + q0, dp.d_pI + q0, dp.d_found + q0, dp.d_phi + size_t(q0) * N, sy.eldof, sys.d_C, sys.d_M, k,
                          sys.d_f, dp.d_fint + q0, s);
     if (plan.x_ev_only) {   // the slots of this chunk's points (k and the columns change with the chunk)
@@ -740,7 +831,10 @@ int solve_chunk(const Run &r, const Plan &plan, const System &sys, const DeviceP
     HIP_TRY(hipEventRecord(ctx->ev[6], s));
     if (nq > 0)
         launch_eval(dim, sy.condense, nq, dp.d_prhs + q0, dp.d_pI + q0, dp.d_found + q0, dp.d_phi + size_t(q0) * N, sy.eldof, sys.d_C, sys.d_M, k, buf.x,
-                    dp.d_fint + q0, dp.d_out + q0, s, buf.x_ev);
+                    dp.d_fint + q0, dp.d_out + q0, s, buf.x_ev, (sec && sy.condense) ? sec->d_fbub : nullptr);
+    if (sec && nq > 0)   // u = u_s + u_p at the evaluation points
+        launch_sec_add_primary(dim, nq, dp.d_prhs + q0, dp.d_pI + q0, dp.d_pz + size_t(q0) * (dp.full ? dim : 1), !dp.full,
+                               sec->d_src, sec->d_ptr + size_t(chunk) * (REMO_MAX_RHS + 1), sec->R, dp.d_out + q0, s);
     HIP_TRY(hipEventRecord(ctx->ev[7], s));
     if (nq > 0) HIP_TRY(hipMemcpyAsync(h_out.data() + q0, dp.d_out + q0, sizeof(double) * nq, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -749,6 +843,7 @@ int solve_chunk(const Run &r, const Plan &plan, const System &sys, const DeviceP
     (void)hipEventElapsedTime(&e2, ctx->ev[5], ctx->ev[6]);
     (void)hipEventElapsedTime(&e3, ctx->ev[6], ctx->ev[7]);
     tot.ms_eval += e1 + e3;
+    if (sec) ctx->sec_ms += e1;
     tot.ms_solve += e2;
     if (!cr.finite) return fail(ctx, REMO_ERR_NUMERIC, "non-finite residual in PCG");
     b->k_last = k;
@@ -933,6 +1028,11 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         if (o.precision == 1) return fail(ctx, REMO_ERR_ARG, "sensitivities are computed in fp64: remo_opts_t.precision = 1 (mixed) is not supported by remo_solve_batch_sens");
         if (int64_t(b->n_mat) * b->sigma_comp > kSensMaxAcc) return fail(ctx, REMO_ERR_ARG, "too many materials for the sensitivity contraction");
     }
+    if (b->secondary) {
+        if (o.precision == 1) return fail(ctx, REMO_ERR_ARG, "the secondary formulation is fp64: remo_opts_t.precision = 1 (mixed) is not supported with remo_job_secondary_t.secondary");
+        if (b->sens || b->field || b->warm) return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.secondary does not combine with functionals, groups, a warm object or field points");
+        ctx->sec_ms = 0.0;
+    }
     if (b->field && o.precision == 1)
         return fail(ctx, REMO_ERR_ARG, "field sections are formed from the fp64 solution: remo_opts_t.precision = 1 (mixed) is not supported by remo_solve_batch_field");
     b->has_system = false;
@@ -952,7 +1052,10 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
             if (!std::isfinite(c)) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
         plan_point_location(b, points);
         Field fld = field_plan(b);
-        const Plan plan = plan_batch(b, o, points, fld.bytes(b->dim));
+        Secondary sec;
+        if (int rc = plan_secondary(ctx, b, sec)) return rc;
+        const int kmax_plan = std::min<int>(std::max(b->n_rhs, b->sens ? b->sens->n_fun : 0), REMO_MAX_RHS);
+        const Plan plan = plan_batch(b, o, points, fld.bytes(b->dim), sec.bytes(b, kmax_plan));
         ctx->reserve(plan.arena_bytes);
 
         // ---- numbering, then every buffer of the solve (arena order), then the device work up to the one sync --------
@@ -961,14 +1064,17 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         Solve sv;
         take_pcg_buffers(r, plan, sys, sv);
         const DevicePoints dp = take_points(r, plan, points);
+        take_secondary(r, plan, sec);
         field_take(r, fld);
         prepare_progress(r, sv.buf);
         HIP_TRY(hipEventRecord(ctx->ev[0], s));
         upload_points(r, points, dp);
+        upload_secondary(r, sec);
         HIP_TRY(hipEventRecord(ctx->ev[1], s));
         assemble_system(r, sys);
         HIP_TRY(hipEventRecord(ctx->ev[2], s));
         locate_points(r, points, dp);
+        check_secondary_sources(r, sec);
         field_locate_points(r, fld);
         HIP_TRY(hipEventRecord(ctx->ev[3], s));
         VertexBlock vb;
@@ -979,6 +1085,7 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         if (int rc = vertex_block_accept(r, plan, sys, sv, vb)) return rc;
         if (vb.h_err & 1) return fail(ctx, REMO_ERR_MESH, "degenerate element or material index out of range");
         if (vb.h_err & 2) return fail(ctx, REMO_ERR_POINT, "source or evaluation point outside the mesh");
+        if (vb.h_err & 4) return fail(ctx, REMO_ERR_POINT, "secondary formulation: a source lies in or on an element whose conductivity differs from sigma0 (the integrand is singular there)");
         bool patch_op = false;
         if (int rc = choose_operator(r, plan, sys, sv, vb, patch_op)) return rc;
         const Sens sens = b->sens ? sens_take(r, sys) : Sens{};
@@ -1011,7 +1118,7 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
             const int q0 = points.chunk_begin[chunk], nq = points.chunk_begin[chunk + 1] - q0;
             if (b->sens) b->d_x = sv.buf.x = sens.block(sys.n, b->n_rhs, false, chunk);   // the solution is formed where it stays
             if (int rc = solve_chunk(r, plan, sys, dp, sv, mixed ? &mx : nullptr, k, q0, nq, h_out, tot,
-                                     warm_hit ? prev.block(sys.n, b->n_rhs, false, chunk) : nullptr)) return rc;
+                                     warm_hit ? prev.block(sys.n, b->n_rhs, false, chunk) : nullptr, sec.on ? &sec : nullptr, chunk)) return rc;
             if (b->field) field_eval_chunk(r, sys, dp, sv.buf.x, fld, c0, k, q0, nq);   // while the chunk's solutions are there
         }
         if (b->field) field_fetch(r, fld);

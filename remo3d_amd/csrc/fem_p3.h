@@ -70,6 +70,32 @@ template <int DIM> REMO_HD void shape(const double *l, double *phi) {
     }
 }
 
+// derivatives of the shape functions at barycentrics l[DIM+1], contracted with t[DIM+1]: g[i] = sum_a (d phi_i / d l_a) t[a], the
+// l_a taken as independent (polynomials of degree 2).  With t[a] = grad(l_a) . v this is grad(phi_i) . v; a unit vector t gives
+// the derivatives themselves.
+template <int DIM> REMO_HD void grad_shape(const double *l, const double *t, double *g) {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i <= DIM; ++i) g[k++] = t[i];
+#pragma unroll
+    for (int e = 0; e < P3<DIM>::NEDGE; ++e) {
+        const int a = edge_a(DIM, e), b = edge_b(DIM, e);
+        const double la = l[a], lb = l[b];
+        g[k++] = lb * t[a] + la * t[b];
+        g[k++] = lb * (lb - 2.0 * la) * t[a] + la * (2.0 * lb - la) * t[b];
+    }
+    if (DIM == 2) {
+        g[k++] = l[1] * l[2] * t[0] + l[0] * l[2] * t[1] + l[0] * l[1] * t[2];
+    } else {
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+            int a, b, c;
+            face_abc(f, a, b, c);
+            g[k++] = l[b] * l[c] * t[a] + l[a] * l[c] * t[b] + l[a] * l[b] * t[c];
+        }
+    }
+}
+
 // Gradients of l_1..l_DIM (rows of the inverse Jacobian) and the measure |T|.
 // X = coordinates of the (sorted) vertices, [NB][DIM].  Returns |T|; 0 for a degenerate element.
 template <int DIM> REMO_HD double bary_gradients(const double *X, double g[DIM][DIM]) {

@@ -213,7 +213,8 @@ void launch_build_rhs(int dim, bool condense, int npts, const int32_t *pt_rhs, c
 // x_ev != nullptr: the values of x that point q reads are x_ev[q * N + i] (PcgBuffersT::x_ev, laid out by launch_eval_slots)
 void launch_eval(int dim, bool condense, int npts, const int32_t *pt_rhs, const double *pt_I, const int32_t *found,
                  const double *phi, const int32_t *eldof, const double *C, const double *M, int k,
-                 const double *x, const double *fint, double *out, hipStream_t s, const double *x_ev = nullptr);
+                 const double *x, const double *fint, double *out, hipStream_t s, const double *x_ev = nullptr,
+                 const double *fbub = nullptr);   // fbub[element][k]: bubble loads of the secondary formulation (2D condensed), nullptr: none
 // at[q * N + i] = row * k + pt_rhs[q] of local dof i of point q's element (N = 20 in 3D, 10 in 2D), -1 where k_eval reads no x
 void launch_eval_slots(int dim, bool condense, int npts, const int32_t *pt_rhs, const int32_t *found, const int32_t *eldof, int k,
                        int64_t *at, hipStream_t s);

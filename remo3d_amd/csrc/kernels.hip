@@ -1147,7 +1147,8 @@ template <int DIM, bool CONDENSE>
 __global__ void k_eval(int npts, const int32_t *__restrict__ pt_rhs, const double *__restrict__ pt_I,
                        const int32_t *__restrict__ found, const double *__restrict__ phi, const int32_t *__restrict__ eldof,
                        const double *__restrict__ C, const double *__restrict__ M, int k, const double *__restrict__ x,
-                       const double *__restrict__ fint, double *__restrict__ out, const double *__restrict__ x_ev) {
+                       const double *__restrict__ fint, double *__restrict__ out, const double *__restrict__ x_ev,
+                       const double *__restrict__ fbub) {
     constexpr int N = P3<DIM>::NLD, NT = P3<DIM>::NTERM, NK = CONDENSE ? 9 : N;
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= npts) return;
@@ -1168,6 +1169,7 @@ __global__ void k_eval(int npts, const int32_t *__restrict__ pt_rhs, const doubl
             double acc = 0.0;
             for (int w = 0; w < npts; ++w)
                 if (pt_I[w] != 0.0 && found[w] == t && pt_rhs[w] == c) acc += fint[w];
+            if (fbub) acc += fbub[int64_t(t) * k + c];   // secondary formulation: the element's distributed bubble load (secondary.hip)
             for (int j = 0; j < 9; ++j) {
                 const int32_t row = ed[j];
                 if (row >= 0) acc -= kentry<DIM>(ce, M, 9, j) * xval(j, row);
@@ -1180,14 +1182,14 @@ __global__ void k_eval(int npts, const int32_t *__restrict__ pt_rhs, const doubl
 
 void launch_eval(int dim, bool condense, int npts, const int32_t *pt_rhs, const double *pt_I, const int32_t *found, const double *phi,
                  const int32_t *eldof, const double *C, const double *M, int k, const double *x, const double *fint, double *out,
-                 hipStream_t s, const double *x_ev) {
+                 hipStream_t s, const double *x_ev, const double *fbub) {
     const int grid = (npts + 63) / 64;
     if (dim == 3)
-        hipLaunchKernelGGL((k_eval<3, false>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, x, fint, out, x_ev);
+        hipLaunchKernelGGL((k_eval<3, false>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, x, fint, out, x_ev, fbub);
     else if (condense)
-        hipLaunchKernelGGL((k_eval<2, true>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, x, fint, out, x_ev);
+        hipLaunchKernelGGL((k_eval<2, true>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, x, fint, out, x_ev, fbub);
     else
-        hipLaunchKernelGGL((k_eval<2, false>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, x, fint, out, x_ev);
+        hipLaunchKernelGGL((k_eval<2, false>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, x, fint, out, x_ev, fbub);
 }
 
 // The entries of x that k_eval reads, one slot per (point, local dof): the slot of a row that several points read is repeated, and

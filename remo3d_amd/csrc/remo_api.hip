@@ -13,6 +13,7 @@
 #include "fem_p3.h"
 #include "field.h"
 #include "warm.h"
+#include "secondary.h"
 
 using namespace remo;
 
@@ -108,11 +109,12 @@ static void store_points(std::vector<double> &to, const double *from, int n, int
 
 // tensor: sigma holds n_mat upper triangles (remo_solve_batch_tensor) instead of n_mat scalars
 // full: src_z / eval_z hold dim coordinates per point (remo_solve_job) instead of axis positions
-static int batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
-                        const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
-                        const double *eval_z, remo_batch_t **out, bool pooled, bool tensor = false, bool full = false) {
+// the host checks of batch_create: everything that is refused before any device work
+static int check_batch_args(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
+                            const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                            const double *eval_z, bool tensor, bool full) {
     if (!ctx) return REMO_ERR_ARG;
-    if (!mesh || !sigma || !out || n_mat <= 0 || n_rhs <= 0 || !src_ptr || !eval_ptr)
+    if (!mesh || !sigma || n_mat <= 0 || n_rhs <= 0 || !src_ptr || !eval_ptr)
         return fail(ctx, REMO_ERR_ARG, "null or empty argument");
     if (mesh->dim != 2 && mesh->dim != 3) return fail(ctx, REMO_ERR_ARG, "dim must be 2 or 3");
     if (mesh->n_nodes <= 0 || mesh->n_elems <= 0 || !mesh->coords || !mesh->conn || !mesh->mat)
@@ -124,7 +126,7 @@ static int batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat,
     for (int k = 0; k < n_rhs; ++k)
         if (src_ptr[k + 1] < src_ptr[k] || eval_ptr[k + 1] < eval_ptr[k]) return fail(ctx, REMO_ERR_ARG, "src_ptr / eval_ptr not monotone");
     if ((src_ptr[n_rhs] > 0 && (!src_z || !src_I)) || (eval_ptr[n_rhs] > 0 && !eval_z)) return fail(ctx, REMO_ERR_ARG, "point arrays missing");
-    const int dim = mesh->dim, nb = dim + 1;
+    const int dim = mesh->dim;
     for (int64_t i = 0; i < mesh->n_nodes * dim; ++i)
         if (!std::isfinite(mesh->coords[i])) return fail(ctx, REMO_ERR_MESH, "non-finite coordinate");
     if (full) {   // the job entries: before any device work
@@ -142,6 +144,17 @@ static int batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat,
         for (int i = 0; i < n_mat; ++i)
             if (!(sigma[i] > 0.0) || !std::isfinite(sigma[i])) return fail(ctx, REMO_ERR_ARG, "sigma must be positive and finite");
     }
+    return REMO_OK;
+}
+
+static int batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
+                        const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                        const double *eval_z, remo_batch_t **out, bool pooled, bool tensor = false, bool full = false) {
+    if (!ctx) return REMO_ERR_ARG;
+    if (!out) return fail(ctx, REMO_ERR_ARG, "null or empty argument");
+    if (int rc = check_batch_args(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, tensor, full)) return rc;
+    const int dim = mesh->dim, nb = dim + 1;
+    const int ncomp = tensor ? ((dim == 2) ? 3 : 6) : 1;
     remo_batch *b = nullptr;
     try {
         HIP_TRY(hipSetDevice(ctx->device));
@@ -429,15 +442,17 @@ int remo_solve_batch_field_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int3
 }
 
 // remo_solve_job / remo_batch_create_job: the job as this library knows it - the caller's leading `size` bytes, the rest zero.
-static int read_job(remo_ctx_t *ctx, const remo_job_t *job, remo_job_t &j) {
+static int read_job(remo_ctx_t *ctx, const remo_job_t *job, remo_job_t &j, remo_job_secondary_t &x) {
     if (!ctx) return REMO_ERR_ARG;
     if (!job) return fail(ctx, REMO_ERR_ARG, "null job");
     const size_t size = job->size;
     if (size < offsetof(remo_job_t, n_fun)) return fail(ctx, REMO_ERR_ARG, "remo_job_t.size is smaller than the part every job has (through u_out)");
     std::memset(&j, 0, sizeof j);
-    std::memcpy(&j, job, std::min(size, sizeof j));
+    std::memset(&x, 0, sizeof x);
+    std::memcpy(&x, job, std::min(size, sizeof x));   // remo_job_secondary_t begins with a remo_job_t: one layout, two lengths
+    j = x.job;
     const unsigned char *raw = reinterpret_cast<const unsigned char *>(job);
-    for (size_t i = sizeof j; i < size; ++i)   // a newer caller: what this library does not know must not be asked for
+    for (size_t i = sizeof x; i < size; ++i)   // a newer caller: what this library does not know must not be asked for
         if (raw[i]) return fail(ctx, REMO_ERR_ARG, "remo_job_t.size is larger than this library's struct and the tail is not zero");
     if (j.tensor != 0 && j.tensor != 1) return fail(ctx, REMO_ERR_ARG, "remo_job_t.tensor must be 0 or 1");
     return REMO_OK;
@@ -461,17 +476,124 @@ static void job_nan_fill(const remo_mesh_t *mesh, const remo_job_t &j) {
     }
 }
 
+// ---- remo_job_secondary_t.secondary: what the entries check and resolve on the host, before any device work --------------------------------
+// sigma0[n_rhs]: the job's values, or - where it gives none - the scalar conductivity of the element that holds the right-hand
+// side's first source (lowest element number among several; all sources of the right-hand side must see that conductivity).
+static int resolve_secondary(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t &j, const remo_job_secondary_t &x, const remo_opts_t *opts,
+                             std::vector<double> &sigma0) {
+    if (j.n_fun != 0 || j.n_group != 0 || j.warm || j.n_pts != 0 || j.n_frhs != 0)
+        return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.secondary does not combine with functionals, groups, a warm object or field points");
+    if (opts && opts->precision == 1)
+        return fail(ctx, REMO_ERR_ARG, "the secondary formulation is fp64: remo_opts_t.precision = 1 (mixed) is not supported with remo_job_secondary_t.secondary");
+    if (x.sec_quad < 0 || x.sec_quad > kSecQuadMax) return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.sec_quad must be in [0, 16]");
+    if (!(x.sec_radius >= 0.0) || !std::isfinite(x.sec_radius)) return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.sec_radius must be finite and not negative");
+    if (int rc = check_batch_args(ctx, mesh, j.n_mat, j.sigma, j.n_rhs, j.src_ptr, j.src_p, j.src_I, j.eval_ptr, j.eval_p, j.tensor != 0, true)) return rc;
+    const int dim = mesh->dim, nb = dim + 1, ncomp = j.tensor ? ((dim == 2) ? 3 : 6) : 1;
+    const int ns = j.src_ptr[j.n_rhs];
+    if (dim == 2)
+        for (int q = 0; q < ns; ++q)
+            if (j.src_p[size_t(q) * 2] != 0.0) return fail(ctx, REMO_ERR_ARG, "secondary formulation in 2D: sources on the axis only (r == 0.0), no ring sources");
+    sigma0.assign(size_t(j.n_rhs), 0.0);
+    std::vector<int> pending;   // sources (I != 0) of the right-hand sides without a sigma0
+    for (int r = 0; r < j.n_rhs; ++r) {
+        const double s0 = x.sec_sigma0 ? x.sec_sigma0[r] : 0.0;
+        if (s0 != 0.0) {
+            if (!(s0 > 0.0) || !std::isfinite(s0)) return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.sec_sigma0 must be positive and finite (0.0: the conductivity at the source)");
+            sigma0[size_t(r)] = s0;
+            continue;
+        }
+        for (int q = j.src_ptr[r]; q < j.src_ptr[r + 1]; ++q)
+            if (j.src_I[q] != 0.0) pending.push_back(q);
+    }
+    if (pending.empty()) {
+        for (double &v : sigma0) if (v == 0.0) v = 1.0;   // a right-hand side without sources: u_p = 0 whatever sigma0
+        return REMO_OK;
+    }
+    std::vector<int64_t> elem(pending.size(), -1);
+    for (int64_t t = 0; t < mesh->n_elems; ++t) {   // the tolerances of k_locate
+        double X[12], lo[3], hi[3];
+        bool good = true;
+        for (int a = 0; a < nb && good; ++a) {
+            const int64_t v = mesh->conn[t * nb + a];
+            if (v < 0 || v >= mesh->n_nodes) { good = false; break; }
+            for (int k = 0; k < dim; ++k) {
+                const double c = mesh->coords[v * dim + k];
+                X[a * dim + k] = c;
+                lo[k] = a ? std::min(lo[k], c) : c; hi[k] = a ? std::max(hi[k], c) : c;
+            }
+        }
+        if (!good) continue;   // (the numbering reports the bad index)
+        for (size_t i = 0; i < pending.size(); ++i) {
+            if (elem[i] >= 0) continue;
+            const double *P = j.src_p + size_t(pending[i]) * dim;
+            bool in = true;
+            for (int k = 0; k < dim; ++k) {
+                const double ext = 1e-9 * (1.0 + hi[k] - lo[k]);
+                if (P[k] < lo[k] - ext || P[k] > hi[k] + ext) in = false;
+            }
+            if (!in) continue;
+            double l[4];
+            if (!(dim == 2 ? barycentrics<2>(X, P, l) : barycentrics<3>(X, P, l))) continue;
+            for (int a = 0; a < nb; ++a)
+                if (l[a] < -1e-10) in = false;
+            if (in) elem[i] = t;
+        }
+    }
+    for (size_t i = 0; i < pending.size(); ++i) {
+        if (elem[i] < 0) return fail(ctx, REMO_ERR_POINT, "source outside the mesh");
+        const int m = mesh->mat[elem[i]];
+        if (m < 0 || m >= j.n_mat) return fail(ctx, REMO_ERR_MESH, "material index out of range");
+        const double *S = j.sigma + size_t(m) * ncomp;
+        if (j.tensor) {
+            bool iso = S[0] == S[dim == 2 ? 2 : 3] && S[0] == S[ncomp - 1];
+            for (int c = 0; c < ncomp; ++c)
+                if (c != 0 && c != (dim == 2 ? 2 : 3) && c != ncomp - 1 && S[c] != 0.0) iso = false;
+            if (!iso) return fail(ctx, REMO_ERR_ARG, "secondary formulation: the material at a source is anisotropic - give remo_job_secondary_t.sec_sigma0");
+        }
+        int r = 0;
+        while (pending[i] >= j.src_ptr[r + 1]) ++r;
+        if (sigma0[size_t(r)] == 0.0) sigma0[size_t(r)] = S[0];
+        else if (sigma0[size_t(r)] != S[0])
+            return fail(ctx, REMO_ERR_ARG, "secondary formulation: the sources of one right-hand side lie in materials of different conductivity - give remo_job_secondary_t.sec_sigma0");
+    }
+    for (double &v : sigma0) if (v == 0.0) v = 1.0;
+    return REMO_OK;
+}
+
+static void attach_secondary(remo_batch *b, const remo_job_secondary_t &x, std::vector<double> &sigma0) {
+    b->secondary = true;
+    b->sec_quad = x.sec_quad;
+    b->sec_radius = x.sec_radius;
+    b->sec_sigma0.swap(sigma0);
+}
+
 int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, const remo_opts_t *opts, remo_stats_t *stats) {
     remo_job_t j;
-    int rc = read_job(ctx, job, j);
+    remo_job_secondary_t x;
+    int rc = read_job(ctx, job, j, x);
     const bool fun = rc == REMO_OK && j.n_fun != 0, field = rc == REMO_OK && (j.n_pts != 0 || j.n_frhs != 0);
     if (rc == REMO_OK && fun && field) rc = fail(ctx, REMO_ERR_ARG, "field points together with functionals: two calls");
     if (rc == REMO_OK && !fun && (j.n_group != 0 || j.warm)) rc = fail(ctx, REMO_ERR_ARG, "groups or a warm object without functionals");
+    if (rc == REMO_OK && x.secondary != 0 && x.secondary != 1) rc = fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.secondary must be 0 or 1");
+    std::vector<double> sigma0;
+    if (rc == REMO_OK && x.secondary) rc = resolve_secondary(ctx, mesh, j, x, opts, sigma0);
     if (rc != REMO_OK) {
         if (ctx && job && job->size >= offsetof(remo_job_t, n_fun)) {   // a job that could be read: its outputs as the entries leave them on an error
             job_nan_fill(mesh, j);
             if (j.warm) remo_warm_clear(j.warm);
         }
+        return rc;
+    }
+    if (x.secondary) {   // remo_solve_batch with the load vector and the read-out of the secondary formulation (batch_run.hip)
+        job_nan_fill(mesh, j);
+        remo_batch_t *b = nullptr;
+        rc = batch_create(ctx, mesh, j.n_mat, j.sigma, j.n_rhs, j.src_ptr, j.src_p, j.src_I, j.eval_ptr, j.eval_p, &b, true, j.tensor != 0, true);
+        if (rc != REMO_OK) return rc;
+        attach_secondary(b, x, sigma0);
+        b->eval_only = true;
+        rc = remo_batch_run(ctx, b, opts, stats);
+        if (rc >= 0 && j.u_out) remo_batch_fetch(ctx, b, j.u_out);
+        remo_batch_destroy(ctx, b);
         return rc;
     }
     if (field)
@@ -486,8 +608,15 @@ int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *j
 
 int remo_batch_create_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, remo_batch_t **out) {
     remo_job_t j;
-    if (int rc = read_job(ctx, job, j)) return rc;
-    return batch_create(ctx, mesh, j.n_mat, j.sigma, j.n_rhs, j.src_ptr, j.src_p, j.src_I, j.eval_ptr, j.eval_p, out, false, j.tensor != 0, true);
+    remo_job_secondary_t x;
+    if (int rc = read_job(ctx, job, j, x)) return rc;
+    if (x.secondary != 0 && x.secondary != 1) return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.secondary must be 0 or 1");
+    std::vector<double> sigma0;
+    if (x.secondary)   // (the batch entries read the sources and the evaluation points only: the other parts of the job must be empty here too)
+        if (int rc = resolve_secondary(ctx, mesh, j, x, nullptr, sigma0)) return rc;
+    const int rc = batch_create(ctx, mesh, j.n_mat, j.sigma, j.n_rhs, j.src_ptr, j.src_p, j.src_I, j.eval_ptr, j.eval_p, out, false, j.tensor != 0, true);
+    if (rc == REMO_OK && x.secondary) attach_secondary(*out, x, sigma0);
+    return rc;
 }
 
 int remo_batch_field(remo_ctx_t *ctx, remo_batch_t *b, int32_t rhs, int32_t n_pts, const double *pts, double *u, double *grad, double *J,
@@ -503,6 +632,7 @@ int remo_batch_field(remo_ctx_t *ctx, remo_batch_t *b, int32_t rhs, int32_t n_pt
             if (J) J[size_t(i) * dim + d] = std::nan("");
         }
     }
+    if (b->secondary) return fail(ctx, REMO_ERR_ARG, "remo_batch_field reads u_h alone: not available on a batch of the secondary formulation");
     if (!b->has_system || b->run_id != ctx->run_id || b->k_last <= 0 || b->n_rhs > REMO_MAX_RHS || !b->d_x)
         return fail(ctx, REMO_ERR_ARG, "no resident solution for this batch (another batch ran on the context since)");
     if (rhs < 0 || rhs >= b->k_last) return fail(ctx, REMO_ERR_ARG, "rhs index out of range");
@@ -554,6 +684,7 @@ int remo_batch_eval(remo_ctx_t *ctx, remo_batch_t *b, int32_t rhs, int32_t npts,
     if (!ctx) return REMO_ERR_ARG;
     if (!b || !z || !u_out || npts <= 0) return fail(ctx, REMO_ERR_ARG, "bad argument");
     for (int i = 0; i < npts; ++i) u_out[i] = std::nan("");
+    if (b->secondary) return fail(ctx, REMO_ERR_ARG, "remo_batch_eval reads u_h alone: not available on a batch of the secondary formulation");
     if (!b->has_system || b->run_id != ctx->run_id || b->k_last <= 0 || b->n_rhs > REMO_MAX_RHS)
         return fail(ctx, REMO_ERR_ARG, "no resident solution for this batch (another batch ran on the context since)");
     if (rhs < 0 || rhs >= b->k_last) return fail(ctx, REMO_ERR_ARG, "rhs index out of range");

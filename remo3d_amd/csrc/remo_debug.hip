@@ -429,5 +429,10 @@ int remo_debug_field_timing(remo_ctx_t *ctx, double *out2) {
 }
 
 int remo_debug_point_location(remo_ctx_t *ctx) { return ctx ? ctx->point_location : REMO_ERR_ARG; }
+int remo_debug_secondary_timing(remo_ctx_t *ctx, double *ms) {
+    if (!ctx || !ms) return REMO_ERR_ARG;
+    *ms = ctx->sec_ms;
+    return REMO_OK;
+}
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include "symbolic.h"
 #include "sens.h"
 #include "field.h"
+#include "secondary.h"
 
 namespace remo {
 
@@ -26,6 +27,23 @@ bool tensor_ok(int dim, const double *S) {
 }  // namespace remo
 
 using namespace remo;
+
+// remo_host_secondary_element: the quadrature loop of k_sec_elements, point after point
+template <int DIM>
+static int secondary_element(const double *X, const double *sigma_tensor, double sigma, double sigma0, double radius, const double *src, int n, double *f) {
+    constexpr int N = P3<DIM>::NLD, NS = SigmaTensor<DIM>::N;
+    double g[DIM][DIM], D[NS], acc[N];
+    const double vol = bary_gradients<DIM>(X, g);
+    if (!(vol > 0.0)) return REMO_ERR_MESH;
+    for (int i = 0; i < N; ++i) acc[i] = 0.0;
+    if (sec_contrast<DIM>(sigma_tensor ? sigma_tensor : &sigma, sigma_tensor != nullptr, sigma0, D)) {
+        const double rec[kSecSrc] = {src[0], src[1], DIM == 3 ? src[DIM - 1] : 0.0, 1.0 / (12.566370614359172953850573533118 * sigma0), sigma0};
+        const std::vector<double> rule = sec_rule(DIM, n);
+        for (size_t p = 0; p < rule.size(); p += DIM + 2) sec_point<DIM>(X, g, vol, D, &rule[p], rec, 1, radius, acc);
+    }
+    for (int i = 0; i < N; ++i) f[i] = acc[i];
+    return REMO_OK;
+}
 
 extern "C" {
 
@@ -85,6 +103,16 @@ int remo_host_point_shapes(int32_t dim, const double *X, const double *point, do
     if ((dim != 2 && dim != 3) || !X || !point || !phi_out) return REMO_ERR_ARG;
     const bool ok = (dim == 2) ? point_shapes<2>(X, point, phi_out) : point_shapes<3>(X, point, phi_out);
     return ok ? REMO_OK : REMO_ERR_MESH;
+}
+
+int remo_host_secondary_element(int32_t dim, const double *X, const double *sigma_tensor, double sigma, double sigma0, double radius,
+                                const double *src, int32_t n_quad, double *f_out) {
+    if ((dim != 2 && dim != 3) || !X || !src || !f_out || n_quad < 0 || n_quad > kSecQuadMax) return REMO_ERR_ARG;
+    if (!(sigma0 > 0.0) || !std::isfinite(sigma0) || !(radius >= 0.0)) return REMO_ERR_ARG;
+    if (sigma_tensor && !tensor_ok(dim, sigma_tensor)) return REMO_ERR_ARG;
+    const int n = n_quad > 0 ? n_quad : kSecQuadDefault;
+    return dim == 2 ? secondary_element<2>(X, sigma_tensor, sigma, sigma0, radius, src, n, f_out)
+                    : secondary_element<3>(X, sigma_tensor, sigma, sigma0, radius, src, n, f_out);
 }
 
 double remo_host_factor_error(void) { return ref_factors3_error(); }

@@ -93,6 +93,7 @@ struct remo_ctx {
     double sens_group_ms[4] = {};            // last remo_solve_batch_sens_groups: group order; with time_kernels also the material pass, the per-element pass and the group sums, each over all functionals (remo_debug_sens_group_timing)
     double field_ms[2] = {};                 // last remo_solve_batch_field / remo_batch_field: HIP-event time of the location of the points and of the evaluation launches (remo_debug_field_timing)
     hipEvent_t fev[4] = {};                  // their events, created by the first use
+    double sec_ms = 0.0;                     // last remo_batch_run with remo_job_secondary_t.secondary: HIP-event time of the load-vector launches, all chunks (remo_debug_secondary_timing)
     int point_location = 0;                  // last remo_batch_run: 0 = axis kernels, 1 = cell grid (remo_debug_point_location)
     remo::PcgProgress *progress = nullptr;  // mapped, coherent host memory
     remo::PcgProgress *progress_dev = nullptr;
@@ -175,6 +176,12 @@ struct remo_batch {
     const remo_sens_request *sens = nullptr;   // remo_solve_batch_sens: adjoint solves + contraction after the forward solves (batch_run.hip)
     remo_warm *warm = nullptr;                 // remo_solve_batch_sens_warm: where the solutions of the previous call are, and where these go (warm.h)
     const remo_field_request *field = nullptr; // remo_solve_batch_field: the solution at arbitrary points, chunk by chunk (batch_run.hip, field.hip)
+    // remo_job_secondary_t.secondary: the secondary-potential formulation (secondary.h) - element rule, sphere of the primary field and the
+    // background conductivity of every right-hand side as the entry resolved it
+    bool secondary = false;
+    int sec_quad = 0;
+    double sec_radius = 0.0;
+    std::vector<double> sec_sigma0;
     bool eval_only = false;  // remo_solve_batch: nothing reads the solution after the run but the evaluation points (PcgBuffersT::x_ev)
     // last system (pointers into the context arena; valid until the next run on the context)
     bool has_system = false;

@@ -1,0 +1,263 @@
+// secondary.hip — load vector of the secondary-potential formulation (secondary.h) on gfx950, and the primary field at the
+// evaluation points.  fp64 vector code.
+//
+// k_sec_elements: one wave per element.  The lanes share the element's quadrature points; every lane keeps the NLD partial sums of
+// one column at a time in registers (all arrays are indexed by unrolled loops: nothing in scratch), a transposing wave reduction
+// (wave_util.h) leaves each sum on one lane, which stores it.  k_sec_gather then adds, per row, the entries of the row's elements in
+// ascending element order.  Both orders are fixed: two runs give the same bits.
+#include <limits.h>
+
+#include <cmath>
+
+#include "secondary.h"
+#include "wave_util.h"
+#include "../../include/remo3d_hip.h"
+
+namespace remo {
+
+// ---- the element rule ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+// Gauss-Legendre nodes and weights on [0, 1] (Newton on P_n from the Chebyshev guess)
+void gauss01(int n, std::vector<double> &x, std::vector<double> &w) {
+    x.assign(size_t(n), 0.0); w.assign(size_t(n), 0.0);
+    const double pi = 3.14159265358979323846;
+    for (int i = 0; i < n; ++i) {
+        double z = std::cos(pi * (i + 0.75) / (n + 0.5)), dp = 1.0;
+        for (int it = 0; it < 100; ++it) {
+            double p0 = 1.0, p1 = z;
+            for (int m = 2; m <= n; ++m) {
+                const double p2 = ((2.0 * m - 1.0) * z * p1 - (m - 1.0) * p0) / m;
+                p0 = p1; p1 = p2;
+            }
+            dp = n * (z * p1 - p0) / (z * z - 1.0);
+            const double dz = p1 / dp;
+            z -= dz;
+            if (std::fabs(dz) < 1e-16) break;
+        }
+        {   // derivative at the converged node
+            double p0 = 1.0, p1 = z;
+            for (int m = 2; m <= n; ++m) {
+                const double p2 = ((2.0 * m - 1.0) * z * p1 - (m - 1.0) * p0) / m;
+                p0 = p1; p1 = p2;
+            }
+            dp = n * (z * p1 - p0) / (z * z - 1.0);
+        }
+        x[size_t(n - 1 - i)] = 0.5 * (z + 1.0);                       // ascending
+        w[size_t(n - 1 - i)] = 1.0 / ((1.0 - z * z) * dp * dp);       // (2 / ((1 - z^2) P_n'^2)) / 2
+    }
+}
+
+}  // namespace
+
+std::vector<double> sec_rule(int dim, int n) {
+    std::vector<double> x, w, rule;
+    gauss01(n, x, w);
+    for (int iu = 0; iu < n; ++iu)
+        for (int iv = 0; iv < n; ++iv) {
+            const double u = x[size_t(iu)], v = x[size_t(iv)];
+            if (dim == 2) {
+                const double l1 = u, l2 = v * (1.0 - u);
+                rule.insert(rule.end(), {1.0 - l1 - l2, l1, l2, 2.0 * (1.0 - u) * w[size_t(iu)] * w[size_t(iv)]});
+                continue;
+            }
+            for (int iw = 0; iw < n; ++iw) {
+                const double t = x[size_t(iw)];
+                const double l1 = u, l2 = v * (1.0 - u), l3 = t * (1.0 - u) * (1.0 - v);
+                rule.insert(rule.end(), {1.0 - l1 - l2 - l3, l1, l2, l3,
+                                         6.0 * (1.0 - u) * (1.0 - u) * (1.0 - v) * w[size_t(iu)] * w[size_t(iv)] * w[size_t(iw)]});
+            }
+        }
+    return rule;
+}
+
+// ---- kernels ------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+template <int DIM>
+__device__ __forceinline__ void load_vertices(const double *__restrict__ coords, const int32_t *__restrict__ conn, int64_t t, double *X) {
+    constexpr int NB = DIM + 1;
+#pragma unroll
+    for (int a = 0; a < NB; ++a) {
+        const int64_t v = conn[t * NB + a];
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) X[a * DIM + k] = coords[v * DIM + k];
+    }
+}
+
+// one thread per element: does it hold a source (k_locate's box slack and barycentric tolerance) while its conductivity differs
+// from the sigma0 of that source's right-hand side?
+template <int DIM>
+__global__ void __launch_bounds__(256) k_sec_check(int64_t nt, const double *__restrict__ coords, const int32_t *__restrict__ conn,
+                                                   const int32_t *__restrict__ mat, const int32_t *__restrict__ eperm,
+                                                   const double *__restrict__ sigma, int ncomp, int nmat, int ns,
+                                                   const double *__restrict__ src, int32_t *errflag) {
+    constexpr int NB = DIM + 1, NS = SigmaTensor<DIM>::N;
+    const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (t >= nt) return;
+    double X[NB * DIM], lo[DIM], hi[DIM];
+    load_vertices<DIM>(coords, conn, t, X);
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) {
+        lo[k] = X[k]; hi[k] = X[k];
+#pragma unroll
+        for (int a = 1; a < NB; ++a) { lo[k] = fmin(lo[k], X[a * DIM + k]); hi[k] = fmax(hi[k], X[a * DIM + k]); }
+    }
+    const int m = mat[eperm ? int64_t(eperm[t]) : t];
+    if (m < 0 || m >= nmat) return;   // (k_metric_terms reports it)
+    double S[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) S[i] = (i < ncomp) ? sigma[int64_t(m) * ncomp + i] : 0.0;
+    for (int q = 0; q < ns; ++q) {
+        const double *a = src + int64_t(q) * kSecSrc;
+        bool in = true;
+        double P[DIM];
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) {
+            P[k] = a[k];
+            const double ext = 1e-9 * (1.0 + hi[k] - lo[k]);
+            if (P[k] < lo[k] - ext || P[k] > hi[k] + ext) in = false;
+        }
+        if (!in) continue;
+        double l[NB], D[NS];
+        if (!barycentrics<DIM>(X, P, l)) continue;
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+            if (l[b] < -1e-10) in = false;
+        if (in && sec_contrast<DIM>(S, ncomp > 1, a[4], D)) atomicOr(errflag, 4);
+    }
+}
+
+template <int DIM, bool CONDENSE>
+__global__ void __launch_bounds__(64) k_sec_elements(int64_t nt, const double *__restrict__ coords, const int32_t *__restrict__ conn,
+                                                     const int32_t *__restrict__ mat, const int32_t *__restrict__ eperm,
+                                                     const double *__restrict__ sigma, int ncomp, int nmat, const double *__restrict__ C,
+                                                     const double *__restrict__ M, const double *__restrict__ rule, int nq,
+                                                     const double *__restrict__ src, const int32_t *__restrict__ ptr, int k, double R,
+                                                     double *__restrict__ fe, double *__restrict__ fbub) {
+    constexpr int NB = DIM + 1, N = P3<DIM>::NLD, NT = P3<DIM>::NTERM, NS = SigmaTensor<DIM>::N, NK = CONDENSE ? 9 : N;
+    const int64_t t = blockIdx.x;
+    const int lane = threadIdx.x;
+    if (t >= nt) return;
+    double X[NB * DIM], g[DIM][DIM], S[NS];
+    load_vertices<DIM>(coords, conn, t, X);
+    const double vol = bary_gradients<DIM>(X, g);
+    const int m = mat[eperm ? int64_t(eperm[t]) : t];
+    const bool ok = vol > 0.0 && m >= 0 && m < nmat;   // (a degenerate element or a bad material is k_metric_terms' error)
+#pragma unroll
+    for (int i = 0; i < NS; ++i) S[i] = (ok && i < ncomp) ? sigma[int64_t(m) * ncomp + i] : 0.0;
+    double fold[9];   // 2D condensed: K_j9 / K_99, what the bubble load takes from the outer rows
+    if (CONDENSE) {
+        const double *ce = C + t * NT;
+        const double kbb = kentry<DIM>(ce, M, 9, 9);
+#pragma unroll
+        for (int j = 0; j < 9; ++j) fold[j] = ok ? kentry<DIM>(ce, M, 9, j) / kbb : 0.0;
+    }
+    int idx[N], own[N];
+    towner_init<N, 64>(idx, own, lane);
+    for (int c = 0; c < k; ++c) {
+        const int s0 = ptr[c], ns = ptr[c + 1] - s0;
+        double D[NS], acc[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) acc[i] = 0.0;
+        const bool contributes = ok && ns > 0 && sec_contrast<DIM>(S, ncomp > 1, src[int64_t(s0) * kSecSrc + 4], D);   // wave-uniform
+        if (contributes) {
+            for (int p = lane; p < nq; p += 64) {
+                double lw[NB + 1];
+#pragma unroll
+                for (int i = 0; i <= NB; ++i) lw[i] = rule[int64_t(p) * (NB + 1) + i];
+                sec_point<DIM>(X, g, vol, D, lw, src + int64_t(s0) * kSecSrc, ns, R, acc);
+            }
+            if (CONDENSE) {   // f_j -= K_j9 f_9 / K_99, lane by lane (the fold is linear)
+#pragma unroll
+                for (int j = 0; j < 9; ++j) acc[j] -= fold[j] * acc[9];
+            }
+            TReduce<N, 64>::run(acc, lane);
+        }
+        // after the reduction lane `lane` holds the sum of entry idx[0] in acc[0] (one sum per lane: N <= 64)
+        if (own[0]) {
+            if (idx[0] < NK) fe[(t * N + idx[0]) * k + c] = acc[0];
+            else if (CONDENSE) fbub[t * k + c] = acc[0];
+        }
+    }
+}
+
+template <int N>
+__global__ void __launch_bounds__(256) k_sec_gather(int64_t n, int k, const int32_t *__restrict__ adjptr, const uint32_t *__restrict__ adj,
+                                                    const double *__restrict__ fe, double *__restrict__ f) {
+    const int64_t at = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (at >= n * k) return;
+    const int64_t row = at / k;
+    const int c = int(at - row * k);
+    double s = 0.0;
+    for (int32_t a = adjptr[row]; a < adjptr[row + 1]; ++a) {
+        const uint32_t code = adj[a];
+        s += fe[(int64_t(code >> 5) * N + int64_t(code & 31u)) * k + c];
+    }
+    f[at] = s;
+}
+
+template <int DIM>
+__global__ void __launch_bounds__(64) k_sec_add_primary(int npts, const int32_t *__restrict__ pt_rhs, const double *__restrict__ pt_I,
+                                                        const double *__restrict__ pp, int on_axis, const double *__restrict__ src,
+                                                        const int32_t *__restrict__ ptr, double R, double *__restrict__ out) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= npts || pt_I[q] != 0.0) return;   // sources read nothing
+    double x[DIM], du[DIM];
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) { x[k] = on_axis ? 0.0 : pp[int64_t(q) * DIM + k]; du[k] = 0.0; }
+    if (on_axis) x[DIM - 1] = pp[q];
+    const int c = pt_rhs[q];
+    double up = 0.0;
+    for (int s = ptr[c]; s < ptr[c + 1]; ++s) {
+        double u = 0.0;
+        sec_primary<DIM>(x, src + int64_t(s) * kSecSrc, R, u, du);
+        up += src[int64_t(s) * kSecSrc + 3] * u;
+    }
+    out[q] += up;
+}
+
+}  // namespace
+
+void launch_sec_check(int dim, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat, const int32_t *eperm, const double *sigma,
+                      int ncomp, int nmat, int ns, const double *src, int32_t *errflag, hipStream_t s) {
+    if (ns <= 0) return;
+    const int grid = int((nt + 255) / 256);
+    if (dim == 2)
+        hipLaunchKernelGGL(k_sec_check<2>, dim3(grid), dim3(256), 0, s, nt, coords, conn, mat, eperm, sigma, ncomp, nmat, ns, src, errflag);
+    else
+        hipLaunchKernelGGL(k_sec_check<3>, dim3(grid), dim3(256), 0, s, nt, coords, conn, mat, eperm, sigma, ncomp, nmat, ns, src, errflag);
+}
+
+void launch_sec_elements(int dim, bool condense, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat, const int32_t *eperm,
+                         const double *sigma, int ncomp, int nmat, const double *C, const double *M, const double *rule, int nq, const double *src,
+                         const int32_t *ptr, int k, double R, double *fe, double *fbub, hipStream_t s) {
+    const dim3 grid{unsigned(nt)}, block{64};
+    if (dim == 3)
+        hipLaunchKernelGGL((k_sec_elements<3, false>), grid, block, 0, s, nt, coords, conn, mat, eperm, sigma, ncomp, nmat, C, M, rule, nq, src, ptr, k, R, fe, fbub);
+    else if (condense)
+        hipLaunchKernelGGL((k_sec_elements<2, true>), grid, block, 0, s, nt, coords, conn, mat, eperm, sigma, ncomp, nmat, C, M, rule, nq, src, ptr, k, R, fe, fbub);
+    else
+        hipLaunchKernelGGL((k_sec_elements<2, false>), grid, block, 0, s, nt, coords, conn, mat, eperm, sigma, ncomp, nmat, C, M, rule, nq, src, ptr, k, R, fe, fbub);
+}
+
+void launch_sec_gather(int dim, int64_t n, int k, const int32_t *adjptr, const uint32_t *adj, const double *fe, double *f, hipStream_t s) {
+    const int64_t grid = (n * k + 255) / 256;
+    if (grid <= 0) return;
+    if (dim == 3)
+        hipLaunchKernelGGL(k_sec_gather<20>, dim3(unsigned(grid)), dim3(256), 0, s, n, k, adjptr, adj, fe, f);
+    else
+        hipLaunchKernelGGL(k_sec_gather<10>, dim3(unsigned(grid)), dim3(256), 0, s, n, k, adjptr, adj, fe, f);
+}
+
+void launch_sec_add_primary(int dim, int npts, const int32_t *pt_rhs, const double *pt_I, const double *pp, bool on_axis, const double *src,
+                            const int32_t *ptr, double R, double *out, hipStream_t s) {
+    if (npts <= 0) return;
+    const int grid = (npts + 63) / 64;
+    if (dim == 2)
+        hipLaunchKernelGGL(k_sec_add_primary<2>, dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, pp, on_axis ? 1 : 0, src, ptr, R, out);
+    else
+        hipLaunchKernelGGL(k_sec_add_primary<3>, dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, pp, on_axis ? 1 : 0, src, ptr, R, out);
+}
+
+}  // namespace remo

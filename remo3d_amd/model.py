@@ -209,6 +209,7 @@ class _Plan:
         self.tuned_coarse = self.base_kw["preconditioner"] == "multigrid" and not any(k in extra for k in ("coarse", "coarse_degree", "coarse_ratio"))
         self.contexts = [model.ctx] + list(getattr(model, "extra_ctx", []))
         self.share_len = len(list(sweep.my_share(len(self.batches))))
+        self.secondary = None      # simulate_logs(formulation="secondary"): the keyword every batch's solve is given
 
     def batch_opts(self, mesh):
         if self.tuned_coarse and getattr(mesh, "dim", 0) == 3:
@@ -560,6 +561,8 @@ class _BatchRunner:
                         job.outs, job.J, job.dJ, st, rc = c.solve_batch_sens(job.mesh, job.sigma, sources, evals, job.functionals, opts)
                 elif job.field_rhs is not None:
                     job.outs, job.field, st, rc = c.solve_batch_field(job.mesh, job.sigma, sources, evals, job.field_points, job.field_rhs, opts)
+                elif p.secondary is not None:
+                    job.outs, st, rc = c.solve_batch(job.mesh, job.sigma, sources, evals, opts, secondary=p.secondary)
                 else:
                     job.outs, st, rc = c.solve_batch(job.mesh, job.sigma, sources, evals, opts)
             finally:
@@ -622,6 +625,7 @@ class Model:
         self.field_sections = None     # simulate_logs(field_grid=...): per tool dict(u [n_kept, n_z, n_h] in V, J [n_kept, n_z, n_h, dim] in A/m2)
         self.field_sources = None      # ... per tool and kept record the energised point sources (absolute z, I)
         self.field_source_x = None     # ... and their x in the mesh frame (the eccentricity of the sweep; 0 for a centred tool)
+        self.formulation = None        # "primary" or "secondary": how the last sweep treated the point sources (simulate_logs)
         self.eccentricity = None       # the displacement of the tool from the borehole axis in the last sweep, metres along x
         self.field_grid = None         # the grid of the last sections
         self.field_depth_index = None  # ... and the indices into measurement_depths they were kept for
@@ -805,8 +809,14 @@ class Model:
                       maxsteps: int = 1000, verbose: bool = True, mesh_workers: Optional[int] = None, precision: str = "fp64",
                       schedule: str = "static", solver_options: Optional[dict] = None, sensitivities: bool = False,
                       sensitivity_grid: Optional[dict] = None, reuse=None, field_grid: Optional[dict] = None,
-                      field_depths=None, eccentricity: float = 0.0):
-        """eccentricity: signed displacement in metres of the WHOLE tool from the borehole axis, along x of the mesh frame - the dip
+                      field_depths=None, eccentricity: float = 0.0, formulation: str = "primary"):
+        """formulation: "primary" (default) - every point source goes into the load vector, as without the keyword - or "secondary":
+        every batch is solved for the smooth remainder u_s of u = u_p + u_s, u_p the closed-form potential of the batch's sources in
+        homogeneous mud inside a grounded sphere of radius domain_radius (remo_job_secondary_t.secondary; sigma0 is left to the library: the
+        conductivity at the source), so the elements around the electrodes no longer resolve a 1 / r singularity.  Works with
+        eccentricity, with anisotropic tables and with any mesh_scale; not (yet) with sensitivities, sensitivity_grid, field_grid,
+        reuse, precision="mixed" or invert_logs: a ValueError before any batch is drawn.  self.formulation records the choice.
+        eccentricity: signed displacement in metres of the WHOLE tool from the borehole axis, along x of the mesh frame - the dip
         plane y = 0.  The bedding planes are z + x tan(dip) = const with z growing downwards (meshgen.layered_material_fn), so a bed
         boundary lies shallower at +x: +x is UP-dip, a negative value moves the tool down-dip; with dip 0 the direction is immaterial.
         A non-zero value selects the 3D model also between flat beds (dim 3, dip exactly 0), sends every batch through
@@ -838,6 +848,14 @@ class Model:
         after the first sweep, and with sensitivities=True every batch's solves start from its solutions of the previous sweep
         (solver.WarmState); self.timing then also reports mesh_hits and warm_hits.  None (default): nothing is kept."""
         start = time.time()
+        if formulation not in ("primary", "secondary"):
+            raise ValueError("formulation has to be 'primary' or 'secondary'")
+        if formulation == "secondary":
+            if sensitivities or sensitivity_grid is not None or field_grid is not None or reuse is not None:
+                raise ValueError("formulation='secondary' cannot be combined with sensitivities, sensitivity_grid, field_grid or an inversion's "
+                                 "sweeps (reuse, invert_logs): the adjoint and field entries read the finite-element potential alone")
+            if precision != "fp64" or (solver_options or {}).get("precision", "fp64") != "fp64":
+                raise ValueError("formulation='secondary' is fp64: precision has to be 'fp64'")
         if field_grid is not None:
             if sensitivities or sensitivity_grid is not None or reuse is not None:
                 raise ValueError("field_grid cannot be combined with sensitivities, sensitivity_grid or an inversion's sweeps: "
@@ -849,7 +867,9 @@ class Model:
         plan = _Plan(self, measurement_depths, domain_radius, batch_size, mesh_generator, mesh_provider, mesh_scale,
                      dict(preconditioner=preconditioner, condense=condense, rtol=rtol, maxsteps=maxsteps, precision=precision),
                      solver_options, verbose, eccentricity)
+        plan.secondary = dict(radius=float(domain_radius)) if formulation == "secondary" else None
         self.eccentricity = plan.eccentricity
+        self.formulation = formulation
         windowing = _Windowing(plan)
         outputs = [_Logs(plan)]     # the ONE place where the keywords of the further outputs are looked at
         if sensitivities:

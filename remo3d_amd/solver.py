@@ -131,18 +131,42 @@ def _functional_arrays(functionals, dim=0):
     return np.ascontiguousarray([f[0] for f in functionals], dtype=np.int32), fun_ptr, fz, fw
 
 
-def _batch_args(handle, mesh, sigma, sources, evals, job=False):
+def _secondary_members(secondary, n_rhs):
+    """secondary=dict(radius=R, sigma0=None, quad=0) -> (sec_quad, sec_radius, sec_sigma0 array or None, valid?).  sigma0: None (the
+    conductivity at each right-hand side's source), one value for all right-hand sides or one per right-hand side.  The library
+    reads an entry 0.0 as "not given", so an EXPLICIT value that is not positive and finite is not handed over: valid is False and
+    the caller answers with the library's REMO_ERR_ARG itself."""
+    unknown = set(secondary) - {"radius", "sigma0", "quad"}
+    if unknown:
+        raise ValueError("secondary: unknown keys {}".format(sorted(unknown)))
+    s0 = secondary.get("sigma0")
+    if s0 is not None:
+        s0 = np.ascontiguousarray(np.broadcast_to(np.asarray(s0, dtype=np.float64), (n_rhs,)))
+    valid = s0 is None or bool(np.all(np.isfinite(s0) & (s0 > 0.0)))
+    return int(secondary.get("quad") or 0), float(secondary.get("radius") or 0.0), s0, valid
+
+
+def _batch_args(handle, mesh, sigma, sources, evals, job=False, secondary=None):
     """The arguments every batch entry begins with (remo_solve_batch*, remo_batch_create*): handle, mesh, conductivity table, sources
     and evaluation points.  Returns (args, sigma table, tensor?, eval_ptr, keep); keep holds what the pointers in args look at.
-    job: the same as the leading members of a remo_job_t (positions as points) - args is then [handle, mesh, job]."""
+    job: the same as the leading members of a remo_job_t (positions as points) - args is then [handle, mesh, job].
+    secondary: dict(radius, sigma0, quad) - the job with the members of the secondary-potential formulation set (job is implied)."""
+    job = job or secondary is not None
     sigma, tensor = sigma_table(sigma, int(mesh.dim))
     src_ptr, sz, sI, eval_ptr, ez = _rhs_arrays(sources, evals, int(mesh.dim) if job else 0)
     ms, keep = _lib.mesh_struct(mesh)
     if job:
-        j = _lib.RemoJob(size=C.sizeof(_lib.RemoJob), tensor=int(tensor), n_mat=len(sigma), sigma=ptr(sigma, C.c_double), n_rhs=len(sources),
+        Job = _lib.RemoJob if secondary is None else _lib.RemoJobSecondary
+        j = Job(size=C.sizeof(Job), tensor=int(tensor), n_mat=len(sigma), sigma=ptr(sigma, C.c_double), n_rhs=len(sources),
                          src_ptr=ptr(src_ptr, C.c_int32), src_p=ptr(sz, C.c_double), src_I=ptr(sI, C.c_double),
                          eval_ptr=ptr(eval_ptr, C.c_int32), eval_p=ptr(ez, C.c_double))
-        return [handle, C.byref(ms), j], sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez)
+        s0 = None
+        if secondary is not None:
+            j.sec_quad, j.sec_radius, s0, _ = _secondary_members(secondary, len(sources))
+            j.secondary = 1
+            if s0 is not None:
+                j.sec_sigma0 = ptr(s0, C.c_double)
+        return [handle, C.byref(ms), j], sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez, s0)
     args = [handle, C.byref(ms), len(sigma), ptr(sigma, C.c_double), len(sources), ptr(src_ptr, C.c_int32), ptr(sz, C.c_double),
             ptr(sI, C.c_double), ptr(eval_ptr, C.c_int32), ptr(ez, C.c_double)]
     return args, sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez)
@@ -243,14 +267,14 @@ class Context:
         return (self._L.remo_last_error(self._h) or b"").decode()
 
     def _one_shot(self, kind, mesh, sigma, sources, evals, opts, raise_on_error, functionals=None, groups=None, n_group=None, warm=None,
-                  points=None, field_rhs=None):
+                  points=None, field_rhs=None, secondary=None):
         """The one marshalling path of the one-shot entries remo_solve_batch<kind>[_tensor], kind "", "_sens", "_sens_warm", "_sens_groups"
         or "_field": the common arguments, then the functionals and the groups - or the field points - with their outputs where the kind
         has them.  Returns (potentials, [J, dJ, [dJg] | field dict,] stats, rc).
         Positions (of sources, evaluation points, functionals) are 1-D arrays of axis z or [m, dim] arrays of points; with one item
         of the second kind the same arrays go into a remo_job_t instead (remo_solve_job), every item as points."""
-        job = _off_axis([z for (z, _) in sources], evals, [z for (_, z, _) in functionals] if functionals else [])
-        args, sigma, tensor, eval_ptr, keep = _batch_args(self._h, mesh, sigma, sources, evals, job)
+        job = secondary is not None or _off_axis([z for (z, _) in sources], evals, [z for (_, z, _) in functionals] if functionals else [])
+        args, sigma, tensor, eval_ptr, keep = _batch_args(self._h, mesh, sigma, sources, evals, job, secondary)
         d, nc = int(mesh.dim), (sigma.shape[1] if tensor else 1)
         out = np.full(int(eval_ptr[-1]), np.nan)
         args.append(ptr(out, C.c_double))
@@ -290,7 +314,12 @@ class Context:
             j.u_out = args[n_head - 1]
             for name, value in zip(names, args[n_head:]):
                 setattr(j, name, value)
-            rc = self._L.remo_solve_job(args[0], args[1], C.byref(j), C.byref(o), C.byref(st))
+            if secondary is not None and not _secondary_members(secondary, len(sources))[3]:
+                rc, msg = REMO_ERR_ARG, "secondary: sigma0 must be positive and finite (None: the conductivity at the source)"
+                if raise_on_error:
+                    raise RemoError(rc, msg)
+            else:
+                rc = self._L.remo_solve_job(args[0], args[1], C.byref(j), C.byref(o), C.byref(st))
         else:
             rc = getattr(self._L, "remo_solve_batch" + kind + ("_tensor" if tensor else ""))(*args, C.byref(o), C.byref(st))
         if rc < 0 and raise_on_error:
@@ -298,15 +327,19 @@ class Context:
         potentials = [out[eval_ptr[k]:eval_ptr[k + 1]] for k in range(len(evals))]
         return (potentials, *J, *[_symmetric_gradient(g, d, tensor) for g in grads], *field, st.as_dict(), rc)
 
-    def solve_batch(self, mesh, sigma, sources, evals, opts: Optional[RemoOpts] = None, raise_on_error=True):
+    def solve_batch(self, mesh, sigma, sources, evals, opts: Optional[RemoOpts] = None, raise_on_error=True, secondary=None):
         """One-shot remo_solve_batch.  Returns (list of per-RHS potential arrays, stats dict, rc).
         sigma: [n_mat] conductivities, or [n_mat, dim, dim] symmetric positive definite tensors in the mesh's frame
         (remo_solve_batch_tensor).
         sources: per right-hand side (positions, I); evals: per right-hand side positions.  Positions - here and in the functionals
         of the methods below - are a 1-D array of axis z or an [m, dim] array of points of the mesh's frame ((r, z) / (x, y, z)); with
         one item of the second kind the whole call goes through remo_solve_job, 1-D items padded with zeros (axis_points).  A source
-        at r > 0 of a 2D mesh is a ring of total current I; in 3D a source at y > 0 stands for itself and its mirror image."""
-        return self._one_shot("", mesh, sigma, sources, evals, opts, raise_on_error)
+        at r > 0 of a 2D mesh is a ring of total current I; in 3D a source at y > 0 stands for itself and its mirror image.
+        secondary=dict(radius=R, sigma0=None, quad=0): the secondary-potential formulation (remo_job_secondary_t.secondary) - the potentials are
+        u_p + u_s with u_p the closed-form field of the sources in a homogeneous sigma0 inside a grounded sphere of radius R (0: no
+        image term) and u_s the finite-element solution for the smooth remainder.  sigma0: None (the conductivity at each
+        right-hand side's source), one value, or one per right-hand side; quad: points per direction of the element rule (0: default)."""
+        return self._one_shot("", mesh, sigma, sources, evals, opts, raise_on_error, secondary=secondary)
 
     def solve_batch_sens(self, mesh, sigma, sources, evals, functionals, opts: Optional[RemoOpts] = None, raise_on_error=True,
                          warm: Optional[WarmState] = None):
@@ -345,6 +378,12 @@ class Context:
         self._L.remo_debug_field_timing(self._h, ptr(out, C.c_double))
         return float(out[0]), float(out[1])
 
+    def secondary_timing(self) -> float:
+        """ms of the load-vector launches of the last batch with `secondary` on this context (remo_debug_secondary_timing)."""
+        ms = C.c_double(0.0)
+        self._L.remo_debug_secondary_timing(self._h, C.byref(ms))
+        return float(ms.value)
+
     def point_location(self) -> int:
         """How the last batch that ran on this context located the points of its right-hand sides (remo_debug_point_location): 0 = the
         kernels of the axis entries, 1 = the cell grid of the field sections (a batch with a point off the axis)."""
@@ -363,20 +402,24 @@ class Context:
         self._L.remo_debug_sens_timing(self._h, ptr(out, C.c_double))
         return float(out[0]), float(out[1])
 
-    def batch(self, mesh, sigma, sources, evals) -> "Batch":
-        return Batch(self, mesh, sigma, sources, evals)
+    def batch(self, mesh, sigma, sources, evals, secondary=None) -> "Batch":
+        return Batch(self, mesh, sigma, sources, evals, secondary)
 
 
 class Batch:
     """Resident batch (remo_batch_create / run / fetch).  sigma: [n_mat] conductivities, or [n_mat, dim, dim] symmetric positive
     definite tensors (remo_batch_create_tensor), as for Context.solve_batch.  Positions given as [m, dim] points: remo_batch_create_job
-    (eval stays an axis entry; field reads anywhere)."""
+    (eval stays an axis entry; field reads anywhere).  secondary=dict(radius, sigma0, quad): the secondary-potential formulation, as
+    for Context.solve_batch - fetch() then returns u_p + u_s, vectors() the smooth part u_s and its load vector; eval() and field() read
+    u_h alone and refuse such a batch."""
 
-    def __init__(self, ctx: Context, mesh, sigma, sources, evals):
+    def __init__(self, ctx: Context, mesh, sigma, sources, evals, secondary=None):
         self.ctx = ctx
         self._L = ctx._L
-        job = _off_axis([z for (z, _) in sources], evals)   # positions given as points: remo_batch_create_job
-        args, _, tensor, self._eval_ptr, keep = _batch_args(ctx._h, mesh, sigma, sources, evals, job)
+        job = secondary is not None or _off_axis([z for (z, _) in sources], evals)   # positions given as points: remo_batch_create_job
+        if secondary is not None and not _secondary_members(secondary, len(sources))[3]:
+            raise RemoError(REMO_ERR_ARG, "secondary: sigma0 must be positive and finite (None: the conductivity at the source)")
+        args, _, tensor, self._eval_ptr, keep = _batch_args(ctx._h, mesh, sigma, sources, evals, job, secondary)
         h = C.c_void_p()
         if job:
             rc = self._L.remo_batch_create_job(args[0], args[1], C.byref(args[2]), C.byref(h))
