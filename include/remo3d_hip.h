@@ -75,7 +75,7 @@ typedef struct {
                                others number / assemble theirs beside it (software pipelining across batches); 0: no lock      */
     int32_t op;             /* how the CG applies A (CGSolver's a.mat, ngsolve_functions.py:50-51):
                                3 = patch operator (3D; a 2D batch runs on the CSR product whatever this says): matrix-free - the element
-                                   list is cut into patches of 256 / k tetrahedra, a workgroup stages the x rows of its patch in LDS, applies
+                                   list is cut into patches of 256 / k tetrahedra (twice that in fp64 solves with k >= 3), a workgroup stages the x rows of its patch in LDS, applies
                                    every K_e through the factorised reference tensors and writes each row once (rows shared by patches
                                    through a compact slab); same operator to rounding; results reproducible to rounding, not bit for bit
                                    (LDS atomics) - the one kernel of the path for which that holds;
@@ -137,7 +137,8 @@ typedef struct {
     int32_t coarse_used; /* vertex-block solver of the run: 0 = none ("local"), 1 = Chebyshev polynomial, 2 = multigrid cycle */
     int32_t assembled;   /* 1 = the whole matrix, 2 = only the Jacobi diagonal and the P1 (vertex) block (remo_opts_t.assemble):
                             then remo_batch_get_system hands out dinv / freeid only and nnz reads 0                  */
-    int32_t reserved_;
+    int32_t patch_rounds; /* patch operator: elements a lane of its kernel took, 1 or 2 (remo_debug_tune key 40); 0 with the CSR product.
+                            (In the place of a reserved field: the layout is the one of ABI 7.) */
 } remo_stats_t;
 
 typedef struct remo_ctx remo_ctx_t;

@@ -87,6 +87,10 @@ int remo_debug_secondary_timing(remo_ctx_t *ctx, double *ms);
  *          pass (k_pcg_update_tile, fp64 storage);
  *   39  0 = one-shot fp64 solves (remo_solve_batch[_tensor]) carry the whole solution block instead of only the values the
  *       evaluation points read (default 1; bit-identical potentials on the CSR product).  Resident batches always keep the whole x.
+ *   40  1 = the patch operator takes one element per lane: patches of 256 / k elements (k = right-hand sides of the batch);
+ *       2 (default) = two elements per lane, one after the other, in fp64 solves with k >= 3: patches of 2 * (256 / k) elements
+ *       (k_patch_apply ROUNDS = 2).  A batch whose largest such patch does not fit the tables or LDS gets the tables of 1.
+ *       Read when a batch's tables are built (every run).
  *
  * (b) ONLY IN A LIBRARY BUILT WITH -DREMO_PROBES (`make -C remo3d_amd/csrc probes` -> libremo3d_hip_probes.so, loaded by the tools
  * through REMO_LIB=...): rejected experiments and ablations, some of which give WRONG RESULTS ON PURPOSE.  The product ignores them:

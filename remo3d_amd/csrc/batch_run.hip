@@ -575,6 +575,8 @@ struct VertexBlock {
     int32_t *vb_rowptr = nullptr, *vb_col = nullptr;
     double *vb_val = nullptr;
     PatchTables ptab{};
+    int32_t *d_pflag = nullptr;         // device side of h_patch
+    size_t patch_mark = 0;              // arena mark in front of the patch tables (patch_tables_one_round)
     bool amg32_ready = false;
     VertexBlock() = default;
     VertexBlock(const VertexBlock &) = delete;
@@ -622,12 +624,27 @@ void vertex_block_enqueue(const Run &r, const Plan &plan, const System &sys, con
     }
     // patch operator (patch.hip): its tables are built beside the assembly; their overflow flag and largest patch come
     // back with the other small read-backs
+    // Two elements per lane (remo_debug_tune key 40) in fp64 storage; the mixed mode's fp32 kernel takes one, and it runs on these tables.
     if (plan.want_patch) {
-        int32_t *d_pflag = ctx->take<int32_t>(4);
-        build_patch_tables(ctx->ar, s, sy, sys.d_C, plan.kmax, vb.ptab, d_pflag);
-        HIP_TRY(hipMemcpyAsync(vb.h_patch, d_pflag, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        vb.d_pflag = ctx->take<int32_t>(4);
+        vb.patch_mark = ctx->ar.lo_mark();      // nothing else is taken before the synchronisation: patch_tables_one_round may build them again here
+        build_patch_tables(ctx->ar, s, sy, sys.d_C, plan.kmax, r.o.precision == 0 ? patch_rounds_wanted() : 1, vb.ptab, vb.d_pflag);
+        HIP_TRY(hipMemcpyAsync(vb.h_patch, vb.d_pflag, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(hipMemcpyAsync(&vb.h_err, ctx->d_err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+}
+
+// Right after the synchronisation, before anything else is taken from the arena: a batch whose largest patch of two rounds holds
+// more rows than the tables or the kernel's LDS do (vb.h_patch: the flag and the row count the build left on the device) gets
+// tables of one round in the same place - the patch operator stays, and the batch waits once more.
+void patch_tables_one_round(const Run &r, const Plan &plan, const System &sys, VertexBlock &vb) {
+    if (!plan.want_patch || vb.ptab.rounds == 1) return;
+    if (vb.h_patch[0] == 0 && patch_lds_bytes(vb.h_patch[1], plan.kmax) <= kPatchLdsLimit) return;
+    remo_ctx *ctx = r.ctx;
+    ctx->ar.lo_release(vb.patch_mark);
+    build_patch_tables(ctx->ar, r.s, r.b->sym, sys.d_C, plan.kmax, 1, vb.ptab, vb.d_pflag);
+    HIP_TRY(hipMemcpyAsync(vb.h_patch, vb.d_pflag, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, r.s));
+    HIP_TRY(hipStreamSynchronize(r.s));
 }
 
 // After the synchronisation: which images the solve uses (buf), and the ones that are built from the accepted ones.
@@ -714,6 +731,7 @@ int choose_operator(const Run &r, const Plan &plan, const System &sys, const Sol
     if (r.o.op == 3 && r.dim == 3 && !patch_ok) return fail(ctx, REMO_ERR_ARG, "patch operator: a patch of the element list touches more distinct rows than its tables hold (or the mesh is too large)");
     patch_op = patch_ok;
     r.st->op_used = patch_op ? 3 : 0;
+    r.st->patch_rounds = patch_op ? ptab.rounds : 0;
     r.st->assembled = sys.lite ? 2 : 1;
     if (patch_op) {
         ptab.nslot_cap = h_patch[2] > 0 ? h_patch[2] : 1;     // the slab holds the slots in use
@@ -1080,6 +1098,7 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         VertexBlock vb;
         vertex_block_enqueue(r, plan, sys, sv, vb);
         HIP_TRY(hipStreamSynchronize(s));
+        patch_tables_one_round(r, plan, sys, vb);
 
         // ---- what came back: preconditioner images, mesh / point errors, operator -------------------------------------
         if (int rc = vertex_block_accept(r, plan, sys, sv, vb)) return rc;

@@ -82,7 +82,7 @@ constexpr int kDoneSlot = 4 * 8;   // rz0[kDoneSlot] (as int): step + 1 of the u
 // Patch operator (3D, remo_opts_t.op = 3; patch.hip): the element list cut into runs of E elements, one workgroup each
 struct PatchTables {
     int64_t nt = 0, n = 0, npatch = 0;
-    int E = 0;                         // elements per patch = kPatchBlock / right-hand sides of the batch (one lane per element and column)
+    int E = 0;                         // elements per patch = rounds * (kPatchBlock / right-hand sides of the batch) (one lane per element and column, `rounds` elements per lane)
     int rows_cap = 0;                  // rows of prow / pout per patch
     // block, all_slab, stagger: CONSTANTS (build_patch_tables sets 256 / 1 / 0) that no code reads, kept where they are because the
     // struct is a by-value argument of every patch kernel: dropping them shifts every argument load (a follow-up)
@@ -101,6 +101,7 @@ struct PatchTables {
     const double *C = nullptr;         // [nt][6] metric terms (launch_metric_terms)
     int64_t nslot_cap = 0;             // upper bound of bptr[n]: rows of the slab
     int stagger = 0;                   // (layout only, see block)
+    int rounds = 1;                    // elements a lane of k_patch_apply takes, one after the other: E = rounds * (256 / right-hand sides) (in the struct's tail padding)
 };
 template <class T> struct PatchOpT {
     PatchTables t;
@@ -116,7 +117,7 @@ constexpr int kPatchPasses = REMO_PATCH_PASSES;   // staging passes a lane's reg
 constexpr int kPatchBlock = 256;                  // threads per workgroup of k_patch_apply; the tables are laid out for it
 // dynamic LDS of k_patch_apply: staged k-wide rows (later the fp64 accumulators; + the zero row and one of slack); a workgroup may
 // ask for 64 KB less the kernel's static 128 k bytes.  (No row tables in LDS - the row numbers go straight into registers - so five
-// workgroups of a 700-row batch share a CU's 160 KB.)
+// workgroups of a 700-row batch share a CU's 160 KB; patches of two rounds have up to ~1000 rows at size L: 40 KB, three workgroups.)
 inline size_t patch_lds_bytes(int lds_rows, int k) { return size_t(lds_rows + 2) * size_t(k) * 8; }
 constexpr size_t kPatchLdsLimit = 63 * 1024;
 

@@ -630,7 +630,7 @@ template <class T, int K> static void spmm_dispatch(const CsrViewT<T> &A, const 
 }
 
 template <class T> bool patch_applies(const CsrViewT<T> &A, int k) {
-    return A.patch && k * A.patch->t.E <= kPatchBlock && patch_lds_bytes(A.patch->lds_rows, k) <= kPatchLdsLimit;
+    return A.patch && k * (A.patch->t.E / A.patch->t.rounds) <= kPatchBlock && patch_lds_bytes(A.patch->lds_rows, k) <= kPatchLdsLimit;
 }
 template bool patch_applies<double>(const CsrViewT<double> &, int);
 template bool patch_applies<float>(const CsrViewT<float> &, int);

@@ -3,8 +3,12 @@
 // CSR product of the assembled matrix to rounding.
 //
 // The element list (sorted by smallest vertices, symbolic_gpu.hip: neighbours in the list are neighbours in the mesh) is cut into
-// PATCHES of E consecutive tetrahedra, one 256-thread workgroup each.  A patch touches ~7.5 distinct matrix rows per element
-// instead of 20 (E = 85), and 45 % of them belong to no other patch.  Per patch (k_patch_apply):
+// PATCHES of E consecutive tetrahedra, one 256-thread workgroup each: E = 256 / k for k right-hand sides, or twice that where a
+// lane takes two elements (fp64 solves with k >= 3: ROUNDS = 2 below).  Counted on a batch of the headline sweep (370 568
+// tetrahedra, 1 703 039 rows; tools/count_patch_rows.py, profiles/patch_two_rounds_ab.txt), distinct matrix rows per element
+// instead of 20, and the share of a patch's rows that belong to no other patch:
+//     E = 51: 8.45, 24 %     E = 85: 7.75, 30 %     E = 102: 7.53, 32 %
+// (the largest patch has 559 / 859 / 994 rows).  Per patch (k_patch_apply):
 //   1. every lane asks for the numbers of the rows it stages straight into REGISTERS (no row table in LDS, no barrier before the x
 //      rows can be requested) and stages the x rows of the patch's distinct dofs in LDS - every row read once per patch;
 //   2. lane (element, right-hand side) reads its 20 rows from LDS, runs the factorised reference tensors
@@ -14,7 +18,8 @@
 //      row of the patch, also the rows no other patch touches (slot pboff[p] + m for local row m; blocks padded to 16 rows).
 // y itself is written by whoever sums a row's slots in ascending patch order: the PCG's update launch (pcg_kernels.hip), or
 // k_patch_reduce below (products outside the PCG, and remo_debug_tune key 22 = 0).
-// HBM / L2 traffic per application: ~1.6 x-rows and ~2.5 y-rows of k values per matrix row plus 88 bytes per element, against
+// HBM / L2 traffic per application: every patch reads its x rows once and writes them once to the slab, 1.84 (E = 51) or 1.64
+// (E = 102) rows of k values per matrix row each way, plus 88 bytes per element, against
 // 12 bytes per STORED ENTRY of the CSR product (48 entries per row).  The LDS accumulation uses ds_add_f64: the order of the adds
 // inside a patch is not fixed, so results are reproducible to rounding (1e-16 relative per row), not bit for bit - the one kernel
 // of the path for which that holds.
@@ -28,6 +33,7 @@
 #include "kernels.h"
 #include "kutil.h"
 #include "patch.h"
+#include <stdexcept>
 #include <type_traits>
 #include "symbolic_gpu.h"
 #include "wave_util.h"
@@ -182,7 +188,15 @@ template <class T> __device__ __forceinline__ void lds_add(T *p, T v) {
 #ifndef REMO_LEAN_WAVES
 #define REMO_LEAN_WAVES 5
 #endif
-template <class T, int K, int MODE = 0, bool LEAN = false>
+// ROUNDS = 2 (fp64 storage, PatchTables::rounds): a patch holds 2 * (256 / K) elements and every lane takes TWO of them, one after
+// the other, in its one column - element A from the first half of the patch's list, element B from the second (the spread of the
+// lanes over runs applies inside each half).  The fixed cost of a patch (tables, staging round trip, clearing, rows out, barriers)
+// is paid half as often and a patch of twice the elements has fewer rows per element (7.5 against 8.4 at size L: fewer slab rows
+// written here and gathered by the update launch).  Order of phase 2: x of A -> y of A in registers and x of B read while the staged
+// image is whole, THEN the image becomes the accumulators, y of A goes out, B is computed and goes out.  The lanes hold up to
+// kPatchPasses2 staging passes (a patch of 2 * 51 elements has ~770 rows, 15 passes of 51; the largest ~1000).
+constexpr int kPatchPasses2 = 20;
+template <class T, int K, int MODE = 0, bool LEAN = false, int ROUNDS = 1>
 __global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_patch_apply(PatchTables tb, int rows, const T *__restrict__ x, T *__restrict__ y, T *__restrict__ Yb,
                                                      double *__restrict__ ppart, const double *__restrict__ scal, int step, long long *__restrict__ stamps,
                                                      double *__restrict__ pbins) {
@@ -195,7 +209,8 @@ __global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_p
 #define REMO_STAMP(k) if constexpr (MODE == 4) { if (threadIdx.x == 0) stamps[(int64_t(blockIdx.x) << 3) + (k)] = __builtin_readcyclecounter(); }
     REMO_STAMP(0)
     constexpr int NL = K;
-    constexpr int U = kPatchPasses;                      // loads in flight per lane: one trip over up to U * (256 / K) rows
+    static_assert(ROUNDS == 1 || (ROUNDS == 2 && MODE == 0 && !LEAN), "two rounds: the plain order of the product only");
+    constexpr int U = ROUNDS == 2 ? kPatchPasses2 : kPatchPasses;   // loads in flight per lane: one trip over up to U * (256 / K) rows
     constexpr int BLK = kPatchBlock;
     constexpr int EK = BLK / K;                          // rows per pass of the staging / output phases
     constexpr uint32_t S = sizeof(T);
@@ -235,10 +250,14 @@ __global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_p
     // (R runs: lane group el takes element el / R of run el % R; run r has ceil((E - r) / R) elements and starts behind the runs before it:
     //  r * floor(E / R) + min(r, E % R))
     const int R = tb.spread > 1 ? tb.spread : 1;
-    const int run = el % R, base = tb.E / R, extra = tb.E % R;
+    const int EL = ROUNDS == 2 ? (tb.E >> 1) : tb.E;      // elements per round: one per lane group
+    const int run = el % R, base = EL / R, extra = EL % R;
     const int elp = R > 1 ? (run * base + (run < extra ? run : extra) + el / R) : el;
     const int64_t e = p * tb.E + elp;
-    const bool active = el < tb.E && e < tb.nt;
+    const bool active = el < EL && e < tb.nt;
+    // two rounds: the lane's second element sits EL places further down the patch's list (a short last patch may have none)
+    const int64_t eB = e + EL;
+    const bool activeB = ROUNDS == 2 && el < EL && eB < tb.nt;
     uint32_t li[10];
     double cm[6];
 #pragma unroll
@@ -253,6 +272,16 @@ __global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_p
     const rsrc_t rli = make_rsrc(tb.lidx, uint64_t(tb.nt) * 40), rcm = make_rsrc(tb.C, uint64_t(tb.nt) * 48);
     buf_load<uint32_t, 10>(rli, active ? uint32_t(e) * 40u : kOutOfRange, li);   // 40-byte records: 8-byte aligned
     if constexpr (!(LEAN && MODE != 2)) buf_load<double, 6>(rcm, active ? uint32_t(e) * 48u : kOutOfRange, cm);   // metric terms (1,1) (1,2) (1,3) (2,2) (2,3) (3,3)
+    uint32_t liB[ROUNDS == 2 ? 10 : 1];
+    double cmB[ROUNDS == 2 ? 6 : 1];
+    if constexpr (ROUNDS == 2) {
+#pragma unroll
+        for (int q = 0; q < 10; ++q) liB[q] = 0u;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) cmB[q] = 0.0;
+        buf_load<uint32_t, 10>(rli, activeB ? uint32_t(eB) * 40u : kOutOfRange, liB);
+        buf_load<double, 6>(rcm, activeB ? uint32_t(eB) * 48u : kOutOfRange, cmB);
+    }
     const int rows_own = __builtin_amdgcn_readfirstlane(rows_own_v);
     if (__builtin_amdgcn_readfirstlane(done_word) != 0 && __builtin_amdgcn_readfirstlane(done_word) <= step) return;   // (solve_done; uniform)
     const int rows_p = (tb.trim && rows_own < rows) ? rows_own : rows;
@@ -267,18 +296,32 @@ __global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_p
     // 24-bit multiplies: rows and slots are below 2^24 (checked by the caller).  Row `rows` is the zero row constrained dofs read.
     const rsrc_t rx = make_rsrc(x, uint64_t(tb.n) * K * S);
     const uint32_t slack = uint32_t((rows + 1) * K + c0);
-#define REMO_PASSES(fn)                                                                                                   \
-    switch (npass) {                                                                                                      \
+#define REMO_PASSES_UP_TO_12(fn)                                                                                          \
         case 1: fn(std::integral_constant<int, 1>{}, 0); break;   case 2: fn(std::integral_constant<int, 2>{}, 0); break;   \
         case 3: fn(std::integral_constant<int, 3>{}, 0); break;   case 4: fn(std::integral_constant<int, 4>{}, 0); break;   \
         case 5: fn(std::integral_constant<int, 5>{}, 0); break;   case 6: fn(std::integral_constant<int, 6>{}, 0); break;   \
         case 7: fn(std::integral_constant<int, 7>{}, 0); break;   case 8: fn(std::integral_constant<int, 8>{}, 0); break;   \
         case 9: fn(std::integral_constant<int, 9>{}, 0); break;   case 10: fn(std::integral_constant<int, 10>{}, 0); break; \
-        case 11: fn(std::integral_constant<int, 11>{}, 0); break; case 12: fn(std::integral_constant<int, 12>{}, 0); break; \
-        default:                                                                                                          \
-            for (int m0 = 0; m0 < rows_p; m0 += U * EK) fn(std::integral_constant<int, U>{}, m0);                         \
+        case 11: fn(std::integral_constant<int, 11>{}, 0); break; case 12: fn(std::integral_constant<int, 12>{}, 0); break;
+#define REMO_PASSES(fn)                                                                                                   \
+    if constexpr (ROUNDS == 2) {                                                                                          \
+        switch (npass) {                                                                                                  \
+            REMO_PASSES_UP_TO_12(fn)                                                                                      \
+            case 13: fn(std::integral_constant<int, 13>{}, 0); break; case 14: fn(std::integral_constant<int, 14>{}, 0); break; \
+            case 15: fn(std::integral_constant<int, 15>{}, 0); break; case 16: fn(std::integral_constant<int, 16>{}, 0); break; \
+            case 17: fn(std::integral_constant<int, 17>{}, 0); break; case 18: fn(std::integral_constant<int, 18>{}, 0); break; \
+            case 19: fn(std::integral_constant<int, 19>{}, 0); break; case 20: fn(std::integral_constant<int, 20>{}, 0); break; \
+            default:                                                                                                      \
+                for (int m0 = 0; m0 < rows_p; m0 += U * EK) fn(std::integral_constant<int, U>{}, m0);                     \
+        }                                                                                                                 \
+    } else {                                                                                                              \
+        switch (npass) {                                                                                                  \
+            REMO_PASSES_UP_TO_12(fn)                                                                                      \
+            default:                                                                                                      \
+                for (int m0 = 0; m0 < rows_p; m0 += U * EK) fn(std::integral_constant<int, U>{}, m0);                     \
+        }                                                                                                                 \
     }
-    static_assert(U == 12, "REMO_PASSES lists the cases 1 .. U");
+    static_assert(kPatchPasses == 12 && kPatchPasses2 == 20, "REMO_PASSES lists the cases 1 .. U");
     // the row numbers come from registers (a patch with more than U passes of rows - the largest few of a batch - asks for the
     // numbers of its later chunks when it gets there)
     auto stage = [&](auto np_c, int m0) {
@@ -363,6 +406,64 @@ __global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_p
 #undef REMO_PATCH_EMIT
 #undef REMO_BAR_ON
 #undef REMO_BAR_OFF
+        }
+    } else if constexpr (ROUNDS == 2) {
+        typedef const T __attribute__((address_space(4))) *ctab_t;
+        ctab_t tgrad = (ctab_t)ElemTables<T>::grad(), tdiv = (ctab_t)ElemTables<T>::div();
+        if constexpr (sizeof(T) == 8) { asm volatile("" : "+s"(tgrad)); asm volatile("" : "+s"(tdiv)); }
+        // y = B^T c~ B x of one element in this lane's column; returns g . h
+        auto element = [&](const T (&xe)[20], const double (&ce)[6], T (&ye)[20]) -> double {
+            const T c11 = T(ce[0]), c12 = T(ce[1]), c13 = T(ce[2]), c22 = T(ce[3]), c23 = T(ce[4]), c33 = T(ce[5]);
+            T g[30];
+            REMO_ELEM_GRAD(T, xe, g, tgrad)
+            T dd = T(0);
+#pragma unroll
+            for (int m = 0; m < 10; ++m) {     // h = c~ g, in place; g . h on the way
+                const T g1 = g[m], g2 = g[10 + m], g3 = g[20 + m];
+                const T h1 = c11 * g1 + c12 * g2 + c13 * g3, h2 = c12 * g1 + c22 * g2 + c23 * g3, h3 = c13 * g1 + c23 * g2 + c33 * g3;
+                dd += g1 * h1 + g2 * h2 + g3 * h3;
+                g[m] = h1; g[10 + m] = h2; g[20 + m] = h3;
+            }
+            REMO_ELEM_DIV(T, g, ye, tdiv)
+            return double(dd);
+        };
+        // the local rows of an element are read a second time for its accumulation (an L1 / L2 hit), as in the one-round order
+        auto emit = [&](int64_t ee, const T (&ye)[20]) {
+            uint32_t lq[10];
+            const uint32_t *pl2 = reinterpret_cast<const uint32_t *>(tb.lidx + ee * 20);
+#pragma unroll
+            for (int q = 0; q < 10; ++q) lq[q] = __builtin_nontemporal_load(pl2 + q);
+#pragma unroll
+            for (int i = 0; i < 20; ++i) lds_add(ya + ((lq[i >> 1] >> (16 * (i & 1))) & 0xFFFFu) * K + c0, double(ye[i]));
+        };
+        // element A: its x values and its whole result; element B: its x values - all while the staged image is whole
+        T yA[20], xB[20];
+        double dA = 0.0;
+        if (active) {
+            T xA[20];
+#pragma unroll
+            for (int i = 0; i < 20; ++i) xA[i] = xs[REMO_PATCH_L(i) * K + c0];
+            dA = element(xA, cm, yA);
+            // (pin the result HERE: it is used behind the barriers, and the compiler would sink the arithmetic there)
+#pragma unroll
+            for (int i = 0; i < 20; ++i) asm volatile("" : "+v"(yA[i]));
+        }
+        if (activeB) {
+#pragma unroll
+            for (int i = 0; i < 20; ++i) xB[i] = xs[((liB[i >> 1] >> (16 * (i & 1))) & 0xFFFFu) * K + c0];
+        }
+        __syncthreads();        // every lane holds what it wants of the image: the staging area becomes the accumulators
+        REMO_STAMP(3)
+        for (int j = 2 * tid; j < rows_p * K; j += 2 * BLK) { ya[j] = 0.0; ya[j + 1] = 0.0; }
+        if (tid < K) ya[rows * K + tid] = 0.0;
+        __syncthreads();
+        REMO_STAMP(4)
+        if (active) emit(e, yA);
+        d0 = dA;
+        if (activeB) {
+            T yB[20];
+            d0 += element(xB, cmB, yB);
+            emit(eB, yB);
         }
     } else {
     T xv[20];
@@ -460,6 +561,7 @@ __global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_p
     REMO_STAMP(7)
 #undef REMO_STAMP
 #undef REMO_PASSES
+#undef REMO_PASSES_UP_TO_12
 }
 
 // y = for every row the sum of its slab slots (one per patch that touches it) in ascending patch order.  DOT: the patches' <x, A x> are folded
@@ -545,23 +647,41 @@ void set_patch_spread(int v) { g_patch_spread = v; }
 #include "patch_persist.inc"     // keys 34 and 35: k_patch_apply_p / k_patch_apply_r and launch_patch_persistent
 #endif
 
-// one lane per (element, right-hand side); at most 204 elements (the table builder sorts 20 slots per element in 32 KB of LDS)
-int patch_elements_per_group(int kmax) { const int e = kPatchBlock / (kmax > 0 ? kmax : 1); return e < 204 ? e : 204; }   // 204 x 20 slots sort in 4096 LDS keys
+// remo_debug_tune key 40: 2 (default) = two elements per lane where the patch then fits the tables (patch_rounds), 1 = one
+int g_patch_rounds = 2;
+void set_patch_rounds(int v) { g_patch_rounds = v == 1 ? 1 : 2; }
+int patch_rounds_wanted() { return g_patch_rounds; }
+
+// one lane per (element, right-hand side) and round; at most 204 elements (the table builder sorts 20 slots per element in 32 KB of LDS)
+constexpr int kPatchMaxElements = 204;   // 204 x 20 slots sort in 4096 LDS keys (and fit the 13-bit slot field of a key)
+// rounds of a patch: two where 2 * (256 / kmax) elements fit the table builder (kmax >= 3)
+int patch_rounds(int kmax, int wanted) { return (wanted >= 2 && 2 * (kPatchBlock / (kmax > 0 ? kmax : 1)) <= kPatchMaxElements) ? 2 : 1; }
+int patch_elements_per_group(int kmax, int rounds) {
+    const int e = rounds * (kPatchBlock / (kmax > 0 ? kmax : 1));
+    return e < kPatchMaxElements ? e : kPatchMaxElements;
+}
 
 size_t patch_arena_bytes(int64_t nt, int64_t n_max, int kmax) {
-    const int E = patch_elements_per_group(kmax);
-    const int64_t npatch = (nt + E - 1) / E;
-    const int64_t cap = int64_t(E) * 20;
-    return size_t(nt) * 40 + size_t(npatch) * (16 + 12 * size_t(cap)) + size_t(n_max + 2) * 8 + size_t(n_max + 1) * 16 + size_t(npatch) * 8 * 8 + (1 << 20);
+    size_t most = 0;
+    for (int rounds = 1; rounds <= 2; ++rounds) {      // whichever the batch gets (a batch that falls back to one round reuses the room)
+        const int E = patch_elements_per_group(kmax, patch_rounds(kmax, rounds));
+        const int64_t npatch = (nt + E - 1) / E;
+        const int64_t cap = int64_t(E) * 20;
+        const size_t b = size_t(nt) * 40 + size_t(npatch) * (16 + 12 * size_t(cap)) + size_t(n_max + 2) * 8 + size_t(n_max + 1) * 16 + size_t(npatch) * 8 * 8 + (1 << 20);
+        most = b > most ? b : most;
+    }
+    return most;
 }
 
 // Everything is enqueued on s; flag_and_max (device, two ints) must be read by the caller after its next synchronisation:
-// [0] != 0 -> a patch has more distinct rows than the tables hold (the caller falls back to another operator), [1] = the
-// largest row count (sizes the kernel's LDS).
-void build_patch_tables(Arena &ar, hipStream_t s, const DeviceSymbolic &sy, const double *C, int kmax, PatchTables &out, int32_t *flag_and_max) {
+// [0] != 0 -> a patch has more distinct rows than the tables hold (the caller builds tables of one round instead of two, or, with
+// one round, falls back to another operator), [1] = the largest row count (sizes the kernel's LDS).
+void build_patch_tables(Arena &ar, hipStream_t s, const DeviceSymbolic &sy, const double *C, int kmax, int rounds, PatchTables &out, int32_t *flag_and_max) {
     out = PatchTables{};
     const int64_t nt = sy.nt, n = sy.nfree;
-    const int E = patch_elements_per_group(kmax);
+    rounds = patch_rounds(kmax, rounds);
+    const int E = patch_elements_per_group(kmax, rounds);
+    out.rounds = rounds;
     // rows a patch may hold: what fits the LDS budget of one workgroup (48 KB of k-wide fp64 rows), at most every dof distinct
     int rows_cap = int((48 * 1024) / (size_t(kmax) * 8)) - 2;
     if (rows_cap > E * 20) rows_cap = E * 20;
@@ -618,8 +738,8 @@ template <class T, int K> static void patch_dispatch(const CsrViewT<T> &A, const
     bool launched = false;
 #ifdef REMO_PROBES      // persistent forms, ablations (wrong results on purpose), the phase probe, the other arithmetic order: tools/ builds only (make probes)
     launched = launch_patch_persistent<T, K>(P, g_patch_mode, g_patch_stamps, x, y, pp, scal, step, bins, s);
-    if constexpr (K == 5) {     // ablations and the phase probe (tools/probe_patch.py)
-        if (!launched && g_patch_mode >= 1 && g_patch_mode <= 3 + (g_patch_stamps ? 1 : 0)) {
+    if constexpr (K == 5) {     // ablations and the phase probe (tools/probe_patch.py); one-round tables only
+        if (!launched && tb.rounds == 1 && g_patch_mode >= 1 && g_patch_mode <= 3 + (g_patch_stamps ? 1 : 0)) {
             launched = true;
             if (g_patch_mode == 1) launch(k_patch_apply<T, 5, 1>);
             else if (g_patch_mode == 2) launch(k_patch_apply<T, 5, 2>);
@@ -627,14 +747,21 @@ template <class T, int K> static void patch_dispatch(const CsrViewT<T> &A, const
             else launch(k_patch_apply<T, 5, 4>);
         }
     }
-    if (!launched && ((g_patch_lean == 1) != (sizeof(T) == 4)) && g_patch_lean >= 0) {     // the other order than the product's
+    if (!launched && tb.rounds == 1 && ((g_patch_lean == 1) != (sizeof(T) == 4)) && g_patch_lean >= 0) {     // the other order than the product's
         if (sizeof(T) == 4) launch(k_patch_apply<T, K, 0>); else launch(k_patch_apply<T, K, 0, true>);
         launched = true;
     }
 #endif
-    if (!launched) {     // the product: plain order in fp64 (124 registers, four waves per SIMD), register-lean order in fp32 storage (seven)
-        if constexpr (sizeof(T) == 4) launch(k_patch_apply<T, K, 0, true>);
-        else launch(k_patch_apply<T, K, 0>);
+    // the product: plain order in fp64 (124 registers, four waves per SIMD; two rounds: 146 registers, three waves - a size-L batch's
+    // 40 KB of LDS allow three workgroups per CU anyway), register-lean order in fp32 storage (seven)
+    if (!launched) {
+        if constexpr (sizeof(T) == 4) {
+            if (tb.rounds != 1) throw std::logic_error("patch operator: tables of two rounds in fp32 storage (they are built for fp64 solves only)");
+            launch(k_patch_apply<T, K, 0, true>);
+        } else {
+            if (tb.rounds == 2) launch(k_patch_apply<T, K, 0, false, 2>);
+            else launch(k_patch_apply<T, K, 0>);
+        }
     }
     if (bins) return;     // the patches have added their sums into the update launch's rows themselves
     if (part && defer) {

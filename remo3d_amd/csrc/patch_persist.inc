@@ -592,6 +592,7 @@ static bool launch_patch_persistent(const PatchOpT<T> &P, int mode, long long *s
     const PatchTables &tb = P.t;
     const int64_t per = (tb.npatch + 7) / 8;
     if (mode != 0 && mode != 4) return false;
+    if (tb.rounds != 1) return false;      // the persistent forms take one element per lane
     if (g_patch_persist == 2 && P.lds_rows <= kPatchPasses * (256 / K) && P.lds_rows <= 1024) {
         // persistent form with the prefetch through registers: three workgroups per CU by its registers (LDS would allow four or five)
         const size_t bytes = patch_lds_bytes_r(P.lds_rows, K, tb.E);

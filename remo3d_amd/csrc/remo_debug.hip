@@ -277,6 +277,7 @@ struct PatchProbe {
 // the argument errors both probes answer with (REMO_OK: go on)
 int patch_probe_check(remo_ctx *ctx, remo_batch *b) {
     if (!b->has_system || b->run_id != ctx->run_id || !b->A.patch) return fail(ctx, REMO_ERR_ARG, "the last run on this batch did not use the patch operator");
+    if (b->patch64.t.rounds != 1) return fail(ctx, REMO_ERR_ARG, "the batch's patch tables hold two elements per lane: set remo_debug_tune key 40 to 1 and run the batch again");
     if (PatchProbe::k * b->patch64.t.E > kPatchBlock) return fail(ctx, REMO_ERR_ARG, "the batch's patch tables are laid out for fewer than 5 columns");
     return REMO_OK;
 }
@@ -384,6 +385,7 @@ int remo_debug_tune(int32_t key, int32_t value) {
         case 39: g_tune.x_ev = value; return 0;              // one-shot solves: only the values of x the evaluation points read / the whole x
         case 22: g_tune.defer_q = value; return 0;           // shared rows summed by k_patch_reduce / by the update launch
         case 24: g_tune.ell = value; return 0;               // fixed-width image of the vertex block
+        case 40: set_patch_rounds(value); return 0;          // patch operator: two elements per lane where the patch fits its tables / one
         default: break;
     }
 #ifdef REMO_PROBES

@@ -31,6 +31,8 @@ struct Arena {
     }
     size_t hi_mark() const { return hi_off; }
     void hi_release(size_t mark) { hi_off = mark; }
+    size_t lo_mark() const { return lo_off; }
+    void lo_release(size_t mark) { lo_off = mark; }
     void reset() { lo_off = hi_off = 0; }
 };
 
