@@ -153,6 +153,7 @@ void remo_ctx_destroy(remo_ctx_t *ctx);
 /* Text of the last error on this context (or of the failed remo_ctx_create when ctx == NULL). */
 const char *remo_last_error(remo_ctx_t *ctx);
 
+/* The entries with an argument list, from here to remo_solve_job: each is remo_solve_job with axis positions z and the parts its name says. */
 /*
  * Whole batch in one call: the inner hot loop of worker.py:104-131.
  * RHS k has point sources src_z[src_ptr[k] .. src_ptr[k+1]) on the borehole axis with strengths

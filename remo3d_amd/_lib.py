@@ -79,7 +79,22 @@ EXPORTS = ["remo_abi_version", "remo_opts_default", "remo_ctx_create", "remo_ctx
 # include/remo3d_hip_debug.h: probes and tuning knobs (tests, tools, bench.py's `box` record) - not part of the boundary
 DEBUG_EXPORTS = ["remo_debug_stream", "remo_debug_clock", "remo_debug_device", "remo_debug_cache_gather", "remo_debug_xcc", "remo_debug_tune", "remo_debug_patch_phases", "remo_debug_patch_phases_p", "remo_debug_grid_barrier", "remo_debug_sens_timing", "remo_debug_sens_group_timing", "remo_debug_field_timing", "remo_debug_point_location", "remo_debug_secondary_timing"]
 
-SENS_GROUPS_ARGTYPES = []     # argument list of remo_solve_batch_sens_groups / _tensor, filled by load()
+# The argument lists of the entries that take one (remo_solve_batch<kind>[_tensor], remo_batch_create[_tensor]) as members of
+# RemoJob: ctx and mesh, JOB_HEAD, then the kind's members - for the solves followed by opts and stats.  load() derives the
+# argtypes from this table and legacy_args() reads a call's arguments off a job, so a kind is spelled once.
+JOB_HEAD = ["n_mat", "sigma", "n_rhs", "src_ptr", "src_p", "src_I", "eval_ptr", "eval_p"]
+_SENS = ["u_out", "n_fun", "fun_rhs", "fun_ptr", "fun_p", "fun_w"]
+LEGACY_MEMBERS = {"": ["u_out"],
+                  "_sens": _SENS + ["J_out", "dJ_out"],
+                  "_sens_warm": _SENS + ["J_out", "dJ_out", "warm"],
+                  "_sens_groups": _SENS + ["n_group", "group", "J_out", "dJ_out", "dJg_out"],
+                  "_field": ["u_out", "n_pts", "pts", "n_frhs", "field_rhs", "u_f", "grad_f", "J_f", "elem_f"]}
+
+
+def legacy_args(job, kind=None):
+    """The arguments behind (ctx, mesh) of remo_solve_batch<kind>[_tensor] - kind None: of remo_batch_create[_tensor] - read off a job."""
+    return [getattr(job, name) for name in JOB_HEAD + (LEGACY_MEMBERS[kind] if kind is not None else [])]
+
 
 _lib = None
 
@@ -102,22 +117,12 @@ def load():
     L.remo_ctx_destroy.argtypes = [vp]
     L.remo_last_error.restype = C.c_char_p
     L.remo_last_error.argtypes = [vp]
-    batch_args = [vp, C.POINTER(RemoMesh), C.c_int32, dp, C.c_int32, ip, dp, dp, ip, dp]
-    L.remo_solve_batch.restype = C.c_int
-    L.remo_solve_batch.argtypes = batch_args + [dp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]
-    L.remo_solve_batch_tensor.restype = C.c_int
-    L.remo_solve_batch_tensor.argtypes = batch_args + [dp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]
-    sens_args = [dp, C.c_int32, ip, ip, dp, dp, dp, dp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]
-    L.remo_solve_batch_sens.restype = C.c_int
-    L.remo_solve_batch_sens.argtypes = batch_args + sens_args
-    L.remo_solve_batch_sens_tensor.restype = C.c_int
-    L.remo_solve_batch_sens_tensor.argtypes = batch_args + sens_args
-    # ... J_out, dJ_out, warm, opts, stats
-    warm_args = batch_args + [dp, C.c_int32, ip, ip, dp, dp, dp, dp, vp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]
-    L.remo_solve_batch_sens_warm.restype = C.c_int
-    L.remo_solve_batch_sens_warm.argtypes = warm_args
-    L.remo_solve_batch_sens_warm_tensor.restype = C.c_int
-    L.remo_solve_batch_sens_warm_tensor.argtypes = list(warm_args)
+    member = dict(RemoJob._fields_)
+    batch_args = [vp, C.POINTER(RemoMesh)] + [member[name] for name in JOB_HEAD]
+    for kind, names in LEGACY_MEMBERS.items():
+        for entry in (getattr(L, "remo_solve_batch" + kind), getattr(L, "remo_solve_batch" + kind + "_tensor")):
+            entry.restype = C.c_int
+            entry.argtypes = batch_args + [member[name] for name in names] + [C.POINTER(RemoOpts), C.POINTER(RemoStats)]
     L.remo_warm_create.restype = vp
     L.remo_warm_create.argtypes = [C.c_int]
     L.remo_warm_destroy.restype = None
@@ -126,18 +131,6 @@ def load():
     L.remo_warm_clear.argtypes = [vp]
     L.remo_warm_info.restype = C.c_int
     L.remo_warm_info.argtypes = [vp, i64p, ip, i64p, ip]
-    # ... fun_z, fun_w, n_group, group, J_out, dJ_out, dJg_out, opts, stats
-    SENS_GROUPS_ARGTYPES[:] = batch_args + [dp, C.c_int32, ip, ip, dp, dp, C.c_int32, ip, dp, dp, dp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]
-    L.remo_solve_batch_sens_groups.restype = C.c_int
-    L.remo_solve_batch_sens_groups.argtypes = list(SENS_GROUPS_ARGTYPES)
-    L.remo_solve_batch_sens_groups_tensor.restype = C.c_int
-    L.remo_solve_batch_sens_groups_tensor.argtypes = list(SENS_GROUPS_ARGTYPES)
-    # ... u_out, n_pts, pts, n_frhs, field_rhs, u_f, grad_f, J_f, elem_f, opts, stats
-    field_args = batch_args + [dp, C.c_int32, dp, C.c_int32, ip, dp, dp, dp, ip, C.POINTER(RemoOpts), C.POINTER(RemoStats)]
-    L.remo_solve_batch_field.restype = C.c_int
-    L.remo_solve_batch_field.argtypes = field_args
-    L.remo_solve_batch_field_tensor.restype = C.c_int
-    L.remo_solve_batch_field_tensor.argtypes = list(field_args)
     L.remo_solve_job.restype = C.c_int
     L.remo_solve_job.argtypes = [vp, C.POINTER(RemoMesh), vp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]     # the job: RemoJob or RemoJobSecondary
     L.remo_batch_create_job.restype = C.c_int

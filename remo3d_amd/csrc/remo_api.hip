@@ -21,6 +21,52 @@ namespace remo {
 thread_local std::string g_create_error;
 }
 
+// n points as the batch keeps them, dim coordinates each: from full coordinates (full) or from axis positions z, (0, .., z)
+static void store_points(std::vector<double> &to, const double *from, int n, int dim, bool full) {
+    if (n <= 0) { to.clear(); return; }
+    if (full) { to.assign(from, from + size_t(n) * dim); return; }
+    to.assign(size_t(n) * dim, 0.0);
+    for (int q = 0; q < n; ++q) to[size_t(q) * dim + dim - 1] = from[q];
+}
+
+// the host checks of batch_create (remo_internal.h).  j.tensor: sigma holds n_mat upper triangles instead of n_mat scalars
+int remo::check_batch_args(remo_ctx *ctx, const remo_mesh_t *mesh, const remo_job_t &j, bool full) {
+    if (!ctx) return REMO_ERR_ARG;
+    const bool tensor = j.tensor != 0;
+    if (!mesh || !j.sigma || j.n_mat <= 0 || j.n_rhs <= 0 || !j.src_ptr || !j.eval_ptr)
+        return fail(ctx, REMO_ERR_ARG, "null or empty argument");
+    if (mesh->dim != 2 && mesh->dim != 3) return fail(ctx, REMO_ERR_ARG, "dim must be 2 or 3");
+    if (mesh->n_nodes <= 0 || mesh->n_elems <= 0 || !mesh->coords || !mesh->conn || !mesh->mat)
+        return fail(ctx, REMO_ERR_ARG, "empty mesh");
+    if (mesh->n_bfacets < 0 || (mesh->n_bfacets > 0 && (!mesh->bconn || !mesh->bdirichlet)))
+        return fail(ctx, REMO_ERR_ARG, "boundary arrays missing");
+    if (mesh->n_nodes >= (int64_t(1) << 31) || mesh->n_elems >= (int64_t(1) << 27)) return fail(ctx, REMO_ERR_ARG, "mesh too large");
+    if (j.src_ptr[0] != 0 || j.eval_ptr[0] != 0) return fail(ctx, REMO_ERR_ARG, "src_ptr / eval_ptr must start at 0");
+    for (int k = 0; k < j.n_rhs; ++k)
+        if (j.src_ptr[k + 1] < j.src_ptr[k] || j.eval_ptr[k + 1] < j.eval_ptr[k]) return fail(ctx, REMO_ERR_ARG, "src_ptr / eval_ptr not monotone");
+    if ((j.src_ptr[j.n_rhs] > 0 && (!j.src_p || !j.src_I)) || (j.eval_ptr[j.n_rhs] > 0 && !j.eval_p)) return fail(ctx, REMO_ERR_ARG, "point arrays missing");
+    const int dim = mesh->dim;
+    for (int64_t i = 0; i < mesh->n_nodes * dim; ++i)
+        if (!std::isfinite(mesh->coords[i])) return fail(ctx, REMO_ERR_MESH, "non-finite coordinate");
+    if (full) {   // the job entries: before any device work
+        for (int64_t i = 0; i < int64_t(j.src_ptr[j.n_rhs]) * dim; ++i)
+            if (!std::isfinite(j.src_p[i])) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
+        for (int64_t i = 0; i < int64_t(j.eval_ptr[j.n_rhs]) * dim; ++i)
+            if (!std::isfinite(j.eval_p[i])) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
+    }
+    const int ncomp = tensor ? ((dim == 2) ? 3 : 6) : 1;
+    if (tensor) {
+        for (int i = 0; i < j.n_mat; ++i)
+            if (!tensor_ok(dim, j.sigma + size_t(i) * ncomp))
+                return fail(ctx, REMO_ERR_ARG, "sigma_tensor of material " + std::to_string(i) + " is not finite and positive definite");
+    } else {
+        for (int i = 0; i < j.n_mat; ++i)
+            if (!(j.sigma[i] > 0.0) || !std::isfinite(j.sigma[i])) return fail(ctx, REMO_ERR_ARG, "sigma must be positive and finite");
+    }
+    return REMO_OK;
+}
+
+
 extern "C" {
 
 
@@ -98,81 +144,32 @@ void remo_ctx_destroy(remo_ctx_t *ctx) {
 
 const char *remo_last_error(remo_ctx_t *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
-
-// n points as the batch keeps them, dim coordinates each: from full coordinates (full) or from axis positions z, (0, .., z)
-static void store_points(std::vector<double> &to, const double *from, int n, int dim, bool full) {
-    if (n <= 0) { to.clear(); return; }
-    if (full) { to.assign(from, from + size_t(n) * dim); return; }
-    to.assign(size_t(n) * dim, 0.0);
-    for (int q = 0; q < n; ++q) to[size_t(q) * dim + dim - 1] = from[q];
-}
-
-// tensor: sigma holds n_mat upper triangles (remo_solve_batch_tensor) instead of n_mat scalars
-// full: src_z / eval_z hold dim coordinates per point (remo_solve_job) instead of axis positions
-// the host checks of batch_create: everything that is refused before any device work
-static int check_batch_args(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
-                            const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
-                            const double *eval_z, bool tensor, bool full) {
-    if (!ctx) return REMO_ERR_ARG;
-    if (!mesh || !sigma || n_mat <= 0 || n_rhs <= 0 || !src_ptr || !eval_ptr)
-        return fail(ctx, REMO_ERR_ARG, "null or empty argument");
-    if (mesh->dim != 2 && mesh->dim != 3) return fail(ctx, REMO_ERR_ARG, "dim must be 2 or 3");
-    if (mesh->n_nodes <= 0 || mesh->n_elems <= 0 || !mesh->coords || !mesh->conn || !mesh->mat)
-        return fail(ctx, REMO_ERR_ARG, "empty mesh");
-    if (mesh->n_bfacets < 0 || (mesh->n_bfacets > 0 && (!mesh->bconn || !mesh->bdirichlet)))
-        return fail(ctx, REMO_ERR_ARG, "boundary arrays missing");
-    if (mesh->n_nodes >= (int64_t(1) << 31) || mesh->n_elems >= (int64_t(1) << 27)) return fail(ctx, REMO_ERR_ARG, "mesh too large");
-    if (src_ptr[0] != 0 || eval_ptr[0] != 0) return fail(ctx, REMO_ERR_ARG, "src_ptr / eval_ptr must start at 0");
-    for (int k = 0; k < n_rhs; ++k)
-        if (src_ptr[k + 1] < src_ptr[k] || eval_ptr[k + 1] < eval_ptr[k]) return fail(ctx, REMO_ERR_ARG, "src_ptr / eval_ptr not monotone");
-    if ((src_ptr[n_rhs] > 0 && (!src_z || !src_I)) || (eval_ptr[n_rhs] > 0 && !eval_z)) return fail(ctx, REMO_ERR_ARG, "point arrays missing");
-    const int dim = mesh->dim;
-    for (int64_t i = 0; i < mesh->n_nodes * dim; ++i)
-        if (!std::isfinite(mesh->coords[i])) return fail(ctx, REMO_ERR_MESH, "non-finite coordinate");
-    if (full) {   // the job entries: before any device work
-        for (int64_t i = 0; i < int64_t(src_ptr[n_rhs]) * dim; ++i)
-            if (!std::isfinite(src_z[i])) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
-        for (int64_t i = 0; i < int64_t(eval_ptr[n_rhs]) * dim; ++i)
-            if (!std::isfinite(eval_z[i])) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
-    }
-    const int ncomp = tensor ? ((dim == 2) ? 3 : 6) : 1;
-    if (tensor) {
-        for (int i = 0; i < n_mat; ++i)
-            if (!tensor_ok(dim, sigma + size_t(i) * ncomp))
-                return fail(ctx, REMO_ERR_ARG, "sigma_tensor of material " + std::to_string(i) + " is not finite and positive definite");
-    } else {
-        for (int i = 0; i < n_mat; ++i)
-            if (!(sigma[i] > 0.0) || !std::isfinite(sigma[i])) return fail(ctx, REMO_ERR_ARG, "sigma must be positive and finite");
-    }
-    return REMO_OK;
-}
-
-static int batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
-                        const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
-                        const double *eval_z, remo_batch_t **out, bool pooled, bool tensor = false, bool full = false) {
+// The head of a job - conductivities, sources, evaluation points - checked and uploaded.  full: src_p / eval_p are full coordinates
+// (the job entries), else axis positions z (every other entry, through axis_job).  pooled: the inputs go into the context's pool.
+static int batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t &j, bool full, remo_batch_t **out, bool pooled) {
     if (!ctx) return REMO_ERR_ARG;
     if (!out) return fail(ctx, REMO_ERR_ARG, "null or empty argument");
-    if (int rc = check_batch_args(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, tensor, full)) return rc;
+    if (int rc = check_batch_args(ctx, mesh, j, full)) return rc;
     const int dim = mesh->dim, nb = dim + 1;
-    const int ncomp = tensor ? ((dim == 2) ? 3 : 6) : 1;
+    const int ncomp = j.tensor ? ((dim == 2) ? 3 : 6) : 1;
     remo_batch *b = nullptr;
     try {
         HIP_TRY(hipSetDevice(ctx->device));
         b = new remo_batch();
-        b->dim = dim; b->nv = mesh->n_nodes; b->nt = mesh->n_elems; b->nbf = mesh->n_bfacets; b->n_mat = n_mat;
+        b->dim = dim; b->nv = mesh->n_nodes; b->nt = mesh->n_elems; b->nbf = mesh->n_bfacets; b->n_mat = j.n_mat;
         b->sigma_comp = ncomp;
-        b->n_rhs = n_rhs;
-        b->src_ptr.assign(src_ptr, src_ptr + n_rhs + 1);
-        b->eval_ptr.assign(eval_ptr, eval_ptr + n_rhs + 1);
-        store_points(b->src_p, src_z, src_ptr[n_rhs], dim, full);
-        if (src_ptr[n_rhs] > 0) b->src_I.assign(src_I, src_I + src_ptr[n_rhs]);
-        store_points(b->eval_p, eval_z, eval_ptr[n_rhs], dim, full);
+        b->n_rhs = j.n_rhs;
+        b->src_ptr.assign(j.src_ptr, j.src_ptr + j.n_rhs + 1);
+        b->eval_ptr.assign(j.eval_ptr, j.eval_ptr + j.n_rhs + 1);
+        store_points(b->src_p, j.src_p, j.src_ptr[j.n_rhs], dim, full);
+        if (j.src_ptr[j.n_rhs] > 0) b->src_I.assign(j.src_I, j.src_I + j.src_ptr[j.n_rhs]);
+        store_points(b->eval_p, j.eval_p, j.eval_ptr[j.n_rhs], dim, full);
         hipStream_t s = ctx->stream;
         b->pooled = pooled;
         size_t pool_at = 0;
         if (pooled) {     // one grow-only device buffer per context holds the inputs of the batch in hand
             const size_t need = align_up(sizeof(double) * size_t(b->nv) * dim) + align_up(sizeof(int32_t) * size_t(b->nt) * nb) + align_up(sizeof(int32_t) * size_t(b->nt)) +
-                                align_up(sizeof(double) * size_t(n_mat) * ncomp) + align_up(sizeof(int32_t) * size_t(b->nbf) * dim + 4) + align_up(size_t(b->nbf) + 4) + 4096;
+                                align_up(sizeof(double) * size_t(j.n_mat) * ncomp) + align_up(sizeof(int32_t) * size_t(b->nbf) * dim + 4) + align_up(size_t(b->nbf) + 4) + 4096;
             if (need > ctx->in_cap) {
                 HIP_TRY(hipStreamSynchronize(s));
                 if (ctx->in_pool) HIP_TRY(hipFree(ctx->in_pool));
@@ -195,11 +192,11 @@ static int batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat,
         up(&b->d_coords, mesh->coords, size_t(b->nv) * dim);
         up(&b->d_conn, mesh->conn, size_t(b->nt) * nb);
         up(&b->d_mat, mesh->mat, size_t(b->nt));
-        up(&b->d_sigma, sigma, size_t(n_mat) * ncomp);
+        up(&b->d_sigma, j.sigma, size_t(j.n_mat) * ncomp);
         up(&b->d_bconn, mesh->bconn, size_t(b->nbf) * dim);
         up(&b->d_bdir, mesh->bdirichlet, size_t(b->nbf));
         HIP_TRY(hipStreamSynchronize(s));
-        b->u_out.assign(size_t(eval_ptr[n_rhs]), std::nan(""));
+        b->u_out.assign(size_t(j.eval_ptr[j.n_rhs]), std::nan(""));
         *out = b;
         return REMO_OK;
     } catch (const std::exception &ex) {
@@ -208,16 +205,31 @@ static int batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat,
     }
 }
 
+// The head of an argument-list entry as a job (scalar conductivities; the _tensor entries set j.tensor): src_p / eval_p hold its axis
+// positions z, so the job goes on with full = false.  The entries add the members of their parts by name.
+static remo_job_t axis_job(int32_t n_mat, const double *sigma, int32_t n_rhs, const int32_t *src_ptr, const double *src_z, const double *src_I,
+                           const int32_t *eval_ptr, const double *eval_z, double *u_out) {
+    remo_job_t j;
+    std::memset(&j, 0, sizeof j);
+    j.size = sizeof j;
+    j.n_mat = n_mat; j.sigma = sigma;
+    j.n_rhs = n_rhs; j.src_ptr = src_ptr; j.src_p = src_z; j.src_I = src_I;
+    j.eval_ptr = eval_ptr; j.eval_p = eval_z; j.u_out = u_out;
+    return j;
+}
+
 int remo_batch_create(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
                       const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
                       const double *eval_z, remo_batch_t **out) {
-    return batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, out, false);
+    return batch_create(ctx, mesh, axis_job(n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, nullptr), false, out, false);
 }
 
 int remo_batch_create_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor, int32_t n_rhs,
                              const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
                              const double *eval_z, remo_batch_t **out) {
-    return batch_create(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, out, false, true);
+    remo_job_t j = axis_job(n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, nullptr);
+    j.tensor = 1;
+    return batch_create(ctx, mesh, j, false, out, false);
 }
 
 void remo_batch_destroy(remo_ctx_t *ctx, remo_batch_t *b) {
@@ -236,97 +248,130 @@ int remo_batch_fetch(remo_ctx_t *ctx, remo_batch_t *b, double *u_out) {
     return REMO_OK;
 }
 
-static int solve_batch(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
-                       const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
-                       const double *eval_z, double *u_out, const remo_opts_t *opts, remo_stats_t *stats, bool tensor, bool full = false) {
-    if (!ctx) return REMO_ERR_ARG;
-    if (u_out && eval_ptr && n_rhs > 0)
-        for (int i = 0; i < eval_ptr[n_rhs]; ++i) u_out[i] = std::nan("");
-    remo_batch_t *b = nullptr;
-    int rc = batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, &b, true, tensor, full);     // inputs into the context's pool: no hipMalloc / hipFree per batch
-    if (rc != REMO_OK) return rc;
-    b->eval_only = true;
-    rc = remo_batch_run(ctx, b, opts, stats);
-    if (rc >= 0 && u_out) remo_batch_fetch(ctx, b, u_out);
-    remo_batch_destroy(ctx, b);
-    return rc;
+// every output the job names: NaN, elem_f -1 (sizes from the job's own counts; arrays that cannot be sized are left alone)
+static void job_nan_fill(const remo_mesh_t *mesh, const remo_job_t &j) {
+    const int dim = (mesh && mesh->dim == 2) ? 2 : 3;
+    const size_t ncomp = (j.tensor && mesh) ? ((dim == 2) ? 3 : 6) : 1;   // (no mesh: the call is refused, and nothing sizes a triangle)
+    auto fill = [](double *a, size_t n) { for (size_t i = 0; a && i < n; ++i) a[i] = std::nan(""); };
+    if (j.eval_ptr && j.n_rhs > 0 && j.eval_ptr[j.n_rhs] > 0) fill(j.u_out, size_t(j.eval_ptr[j.n_rhs]));
+    if (j.n_fun > 0) {
+        fill(j.J_out, size_t(j.n_fun));
+        if (j.n_mat > 0) fill(j.dJ_out, size_t(j.n_fun) * size_t(j.n_mat) * ncomp);
+        if (j.n_group > 0) fill(j.dJg_out, size_t(j.n_fun) * size_t(j.n_group) * ncomp);
+    }
+    if (j.n_pts > 0) {
+        const size_t nv = (j.n_frhs > 0) ? size_t(j.n_pts) * size_t(j.n_frhs) : 0;
+        fill(j.u_f, nv); fill(j.grad_f, nv * dim); fill(j.J_f, nv * dim);
+        for (int32_t i = 0; j.elem_f && i < j.n_pts; ++i) j.elem_f[i] = -1;
+    }
 }
 
-int remo_solve_batch(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
-                     const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
-                     const double *eval_z, double *u_out, const remo_opts_t *opts, remo_stats_t *stats) {
-    return solve_batch(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, opts, stats, false);
+// The parts of a one-shot call that its ENTRY names (not its counts: remo_solve_batch_sens with n_fun = 0 is a sens call).  A warm
+// object and the secondary formulation need no flag: j.warm, and the `sec` of solve_one.
+enum : unsigned { kFun = 1, kGroups = 2, kField = 4 };
+
+// the functionals of a job (and its groups), on the host arrays, before any device work
+static int check_functionals(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t &j, unsigned parts, bool full) {
+    if (parts & kGroups) {
+        if (j.n_group < 1 || !j.group) return fail(ctx, REMO_ERR_ARG, "n_group must be at least 1 and group must be given");
+        if (!mesh || mesh->n_elems <= 0) return fail(ctx, REMO_ERR_ARG, "empty mesh");
+        if (j.n_fun > 0 && !j.dJg_out) return fail(ctx, REMO_ERR_ARG, "dJg_out missing");
+        for (int64_t e = 0; e < mesh->n_elems; ++e)
+            if (j.group[e] < -1 || j.group[e] >= j.n_group) return fail(ctx, REMO_ERR_ARG, "group id of element " + std::to_string(e) + " outside [-1, n_group)");
+    }
+    if (j.n_fun < 0 || (j.n_fun > 0 && (!j.fun_rhs || !j.fun_ptr || !j.J_out || !j.dJ_out))) return fail(ctx, REMO_ERR_ARG, "functional arrays missing");
+    if (j.n_fun <= 0) return REMO_OK;
+    if (j.fun_ptr[0] != 0) return fail(ctx, REMO_ERR_ARG, "fun_ptr must start at 0");
+    for (int f = 0; f < j.n_fun; ++f) {
+        if (j.fun_ptr[f + 1] < j.fun_ptr[f]) return fail(ctx, REMO_ERR_ARG, "fun_ptr not monotone");
+        if (j.fun_rhs[f] < 0 || j.fun_rhs[f] >= j.n_rhs) return fail(ctx, REMO_ERR_ARG, "fun_rhs names no right-hand side of the batch");
+    }
+    const int nq = j.fun_ptr[j.n_fun];
+    if (nq > 0 && (!j.fun_p || !j.fun_w)) return fail(ctx, REMO_ERR_ARG, "functional arrays missing");
+    for (int q = 0; q < nq; ++q)
+        if (!std::isfinite(j.fun_w[q])) return fail(ctx, REMO_ERR_ARG, "non-finite functional weight");
+    if (full && mesh && (mesh->dim == 2 || mesh->dim == 3))
+        for (int64_t i = 0; i < int64_t(nq) * mesh->dim; ++i)
+            if (!std::isfinite(j.fun_p[i])) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
+    return REMO_OK;
 }
 
-int remo_solve_batch_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor, int32_t n_rhs,
-                            const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
-                            const double *eval_z, double *u_out, const remo_opts_t *opts, remo_stats_t *stats) {
-    return solve_batch(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, opts, stats, true);
+// the field points of a job, likewise
+static int check_field(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t &j, const remo_opts_t *opts) {
+    if (j.n_pts < 0 || j.n_frhs < 0 || (j.n_pts > 0 && !j.pts) || (j.n_frhs > 0 && !j.field_rhs)) return fail(ctx, REMO_ERR_ARG, "field points or field_rhs missing");
+    if (j.n_pts >= (1 << 28)) return fail(ctx, REMO_ERR_ARG, "too many field points");
+    for (int f = 0; f < j.n_frhs; ++f)
+        if (j.field_rhs[f] < 0 || j.field_rhs[f] >= j.n_rhs) return fail(ctx, REMO_ERR_ARG, "field_rhs names no right-hand side of the batch");
+    if (opts && opts->precision == 1)
+        return fail(ctx, REMO_ERR_ARG, "field sections are formed from the fp64 solution: remo_opts_t.precision = 1 (mixed) is not supported by remo_solve_batch_field");
+    if (mesh && (mesh->dim == 2 || mesh->dim == 3))
+        for (int64_t i = 0; i < int64_t(j.n_pts) * mesh->dim; ++i)
+            if (!std::isfinite(j.pts[i])) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
+    return REMO_OK;
 }
 
-// remo_solve_batch_sens / _tensor: the same one-shot batch with the functionals attached (batch_run.hip solves the adjoint columns
-// after the forward ones and contracts them, sens.hip)
-static int solve_batch_sens(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
-                            const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
-                            const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
-                            const double *fun_z, const double *fun_w, double *J_out, double *dJ_out, const remo_opts_t *opts,
-                            remo_stats_t *stats, bool tensor, bool groups = false, int32_t n_group = 0, const int32_t *group = nullptr,
-                            double *dJg_out = nullptr, remo_warm *warm = nullptr, bool full = false) {
+// Every one-shot call: outputs NaN, the checks of the named parts (theirs first, the batch's own in batch_create), the batch with its
+// inputs in the context's pool (no hipMalloc / hipFree per batch), the parts attached - batch_run.hip solves the adjoint columns of
+// the functionals after the forward ones and contracts them (sens.hip), locates the field points once and reads every chunk's solutions
+// there (field.hip), builds the load vector of the secondary formulation (secondary.hip) - run, fetch, destroy.
+// full: src_p / eval_p / fun_p are full coordinates (remo_solve_job), else axis positions z (the remo_solve_batch* entries).
+static int solve_one(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t &j, const remo_job_secondary_t *sec, unsigned parts, bool full,
+                     const remo_opts_t *opts, remo_stats_t *stats) {
     if (!ctx) return REMO_ERR_ARG;
     // whatever goes wrong below, the object does not keep solutions of an earlier call (remo_batch_run labels it again on success)
     struct WarmGuard {
         remo_warm *w;
         int rc = REMO_ERR_ARG;
         ~WarmGuard() { if (w && rc < 0) remo_warm_clear(w); }
-    } guard{warm};
-    if (warm) warm->used_last = 0;
-    if (warm && warm->device != ctx->device) return fail(ctx, REMO_ERR_ARG, "the warm object belongs to another device than the context");
-    const int ncomp = (tensor && mesh) ? ((mesh->dim == 2) ? 3 : 6) : 1;
-    auto nan_fill = [&]() {
-        if (u_out && eval_ptr && n_rhs > 0)
-            for (int i = 0; i < eval_ptr[n_rhs]; ++i) u_out[i] = std::nan("");
-        for (int j = 0; j < n_fun && J_out; ++j) J_out[j] = std::nan("");
-        if (dJ_out && n_fun > 0 && n_mat > 0)
-            for (size_t i = 0; i < size_t(n_fun) * size_t(n_mat) * ncomp; ++i) dJ_out[i] = std::nan("");
-        if (dJg_out && n_fun > 0 && n_group > 0)
-            for (size_t i = 0; i < size_t(n_fun) * size_t(n_group) * ncomp; ++i) dJg_out[i] = std::nan("");
-    };
-    nan_fill();
-    if (groups) {   // on the host array, before any device work
-        if (n_group < 1 || !group) return fail(ctx, REMO_ERR_ARG, "n_group must be at least 1 and group must be given");
-        if (!mesh || mesh->n_elems <= 0) return fail(ctx, REMO_ERR_ARG, "empty mesh");
-        if (n_fun > 0 && !dJg_out) return fail(ctx, REMO_ERR_ARG, "dJg_out missing");
-        for (int64_t e = 0; e < mesh->n_elems; ++e)
-            if (group[e] < -1 || group[e] >= n_group) return fail(ctx, REMO_ERR_ARG, "group id of element " + std::to_string(e) + " outside [-1, n_group)");
-    }
-    if (n_fun < 0 || (n_fun > 0 && (!fun_rhs || !fun_ptr || !J_out || !dJ_out))) return fail(ctx, REMO_ERR_ARG, "functional arrays missing");
-    if (n_fun > 0) {
-        if (fun_ptr[0] != 0) return fail(ctx, REMO_ERR_ARG, "fun_ptr must start at 0");
-        for (int j = 0; j < n_fun; ++j) {
-            if (fun_ptr[j + 1] < fun_ptr[j]) return fail(ctx, REMO_ERR_ARG, "fun_ptr not monotone");
-            if (fun_rhs[j] < 0 || fun_rhs[j] >= n_rhs) return fail(ctx, REMO_ERR_ARG, "fun_rhs names no right-hand side of the batch");
-        }
-        if (fun_ptr[n_fun] > 0 && (!fun_z || !fun_w)) return fail(ctx, REMO_ERR_ARG, "functional arrays missing");
-        for (int q = 0; q < fun_ptr[n_fun]; ++q)
-            if (!std::isfinite(fun_w[q])) return fail(ctx, REMO_ERR_ARG, "non-finite functional weight");
-        if (full && mesh && (mesh->dim == 2 || mesh->dim == 3))
-            for (int64_t i = 0; i < int64_t(fun_ptr[n_fun]) * mesh->dim; ++i)
-                if (!std::isfinite(fun_z[i])) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
-    }
+    } guard{j.warm};
+    if (j.warm) j.warm->used_last = 0;
+    if (j.warm && !sec && j.warm->device != ctx->device) return fail(ctx, REMO_ERR_ARG, "the warm object belongs to another device than the context");
+    job_nan_fill(mesh, j);
+    std::vector<double> sigma0;
+    int rc = sec ? resolve_secondary(ctx, mesh, j, *sec, opts, sigma0) : REMO_OK;   // (refuses every other part, a warm object included)
+    if (rc == REMO_OK && (parts & kFun)) rc = check_functionals(ctx, mesh, j, parts, full);
+    if (rc == REMO_OK && (parts & kField)) rc = check_field(ctx, mesh, j, opts);
     remo_batch_t *b = nullptr;
-    int rc = batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, &b, true, tensor, full);
+    if (rc == REMO_OK) rc = batch_create(ctx, mesh, j, full, &b, true);
     if (rc != REMO_OK) return rc;
-    const remo_sens_request rq{n_fun, fun_rhs, fun_ptr, fun_w, J_out, dJ_out, groups ? n_group : 0, groups ? group : nullptr, groups ? dJg_out : nullptr};
-    store_points(b->fun_p, fun_z, n_fun > 0 ? fun_ptr[n_fun] : 0, b->dim, full);
-    b->sens = &rq;
-    b->warm = warm;
+    const bool groups = parts & kGroups;
+    const remo_sens_request sens{j.n_fun, j.fun_rhs, j.fun_ptr, j.fun_w, j.J_out, j.dJ_out, groups ? j.n_group : 0, groups ? j.group : nullptr, groups ? j.dJg_out : nullptr};
+    const remo_field_request field{j.n_pts, j.pts, j.n_frhs, j.field_rhs, j.u_f, j.grad_f, j.J_f, j.elem_f};
+    if (parts & kFun) {
+        store_points(b->fun_p, j.fun_p, j.n_fun > 0 ? j.fun_ptr[j.n_fun] : 0, b->dim, full);
+        b->sens = &sens;
+        b->warm = j.warm;
+    }
+    if (parts & kField) b->field = &field;
+    if (sec) attach_secondary(b, *sec, sigma0);
     b->eval_only = true;
     rc = remo_batch_run(ctx, b, opts, stats);
-    if (rc >= 0 && u_out) remo_batch_fetch(ctx, b, u_out);
-    if (rc < 0) nan_fill();
+    if (rc >= 0 && j.u_out) remo_batch_fetch(ctx, b, j.u_out);
+    if (rc < 0) job_nan_fill(mesh, j);
     remo_batch_destroy(ctx, b);
     guard.rc = rc;
     return rc;
+}
+
+// ---- the entries with an argument list: each is remo_solve_job with axis positions z and the parts its name says ------------------------
+int remo_solve_batch(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
+                     const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                     const double *eval_z, double *u_out, const remo_opts_t *opts, remo_stats_t *stats) {
+    return solve_one(ctx, mesh, axis_job(n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out), nullptr, 0, false, opts, stats);
+}
+
+int remo_solve_batch_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor, int32_t n_rhs,
+                            const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
+                            const double *eval_z, double *u_out, const remo_opts_t *opts, remo_stats_t *stats) {
+    remo_job_t j = axis_job(n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out);
+    j.tensor = 1;
+    return solve_one(ctx, mesh, j, nullptr, 0, false, opts, stats);
+}
+
+static void set_functionals(remo_job_t &j, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr, const double *fun_z, const double *fun_w,
+                            double *J_out, double *dJ_out) {
+    j.n_fun = n_fun; j.fun_rhs = fun_rhs; j.fun_ptr = fun_ptr; j.fun_p = fun_z; j.fun_w = fun_w;
+    j.J_out = J_out; j.dJ_out = dJ_out;
 }
 
 int remo_solve_batch_sens(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
@@ -334,8 +379,9 @@ int remo_solve_batch_sens(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_ma
                           const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
                           const double *fun_z, const double *fun_w, double *J_out, double *dJ_out, const remo_opts_t *opts,
                           remo_stats_t *stats) {
-    return solve_batch_sens(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_fun, fun_rhs, fun_ptr, fun_z, fun_w,
-                            J_out, dJ_out, opts, stats, false);
+    remo_job_t j = axis_job(n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out);
+    set_functionals(j, n_fun, fun_rhs, fun_ptr, fun_z, fun_w, J_out, dJ_out);
+    return solve_one(ctx, mesh, j, nullptr, kFun, false, opts, stats);
 }
 
 int remo_solve_batch_sens_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor, int32_t n_rhs,
@@ -343,8 +389,10 @@ int remo_solve_batch_sens_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32
                                  const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
                                  const double *fun_z, const double *fun_w, double *J_out, double *dJ_out, const remo_opts_t *opts,
                                  remo_stats_t *stats) {
-    return solve_batch_sens(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_fun, fun_rhs, fun_ptr, fun_z,
-                            fun_w, J_out, dJ_out, opts, stats, true);
+    remo_job_t j = axis_job(n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out);
+    j.tensor = 1;
+    set_functionals(j, n_fun, fun_rhs, fun_ptr, fun_z, fun_w, J_out, dJ_out);
+    return solve_one(ctx, mesh, j, nullptr, kFun, false, opts, stats);
 }
 
 int remo_solve_batch_sens_warm(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
@@ -352,8 +400,10 @@ int remo_solve_batch_sens_warm(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t
                                const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
                                const double *fun_z, const double *fun_w, double *J_out, double *dJ_out, remo_warm_t *warm,
                                const remo_opts_t *opts, remo_stats_t *stats) {
-    return solve_batch_sens(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_fun, fun_rhs, fun_ptr, fun_z, fun_w,
-                            J_out, dJ_out, opts, stats, false, false, 0, nullptr, nullptr, warm);
+    remo_job_t j = axis_job(n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out);
+    set_functionals(j, n_fun, fun_rhs, fun_ptr, fun_z, fun_w, J_out, dJ_out);
+    j.warm = warm;
+    return solve_one(ctx, mesh, j, nullptr, kFun, false, opts, stats);
 }
 
 int remo_solve_batch_sens_warm_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor, int32_t n_rhs,
@@ -361,8 +411,11 @@ int remo_solve_batch_sens_warm_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, 
                                       const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
                                       const double *fun_z, const double *fun_w, double *J_out, double *dJ_out, remo_warm_t *warm,
                                       const remo_opts_t *opts, remo_stats_t *stats) {
-    return solve_batch_sens(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_fun, fun_rhs, fun_ptr, fun_z,
-                            fun_w, J_out, dJ_out, opts, stats, true, false, 0, nullptr, nullptr, warm);
+    remo_job_t j = axis_job(n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out);
+    j.tensor = 1;
+    set_functionals(j, n_fun, fun_rhs, fun_ptr, fun_z, fun_w, J_out, dJ_out);
+    j.warm = warm;
+    return solve_one(ctx, mesh, j, nullptr, kFun, false, opts, stats);
 }
 
 int remo_solve_batch_sens_groups(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
@@ -370,8 +423,10 @@ int remo_solve_batch_sens_groups(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32
                                  const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
                                  const double *fun_z, const double *fun_w, int32_t n_group, const int32_t *group, double *J_out, double *dJ_out,
                                  double *dJg_out, const remo_opts_t *opts, remo_stats_t *stats) {
-    return solve_batch_sens(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_fun, fun_rhs, fun_ptr, fun_z, fun_w,
-                            J_out, dJ_out, opts, stats, false, true, n_group, group, dJg_out);
+    remo_job_t j = axis_job(n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out);
+    set_functionals(j, n_fun, fun_rhs, fun_ptr, fun_z, fun_w, J_out, dJ_out);
+    j.n_group = n_group; j.group = group; j.dJg_out = dJg_out;
+    return solve_one(ctx, mesh, j, nullptr, kFun | kGroups, false, opts, stats);
 }
 
 int remo_solve_batch_sens_groups_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor, int32_t n_rhs,
@@ -379,57 +434,21 @@ int remo_solve_batch_sens_groups_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh
                                         const double *eval_z, double *u_out, int32_t n_fun, const int32_t *fun_rhs, const int32_t *fun_ptr,
                                         const double *fun_z, const double *fun_w, int32_t n_group, const int32_t *group, double *J_out,
                                         double *dJ_out, double *dJg_out, const remo_opts_t *opts, remo_stats_t *stats) {
-    return solve_batch_sens(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_fun, fun_rhs, fun_ptr, fun_z,
-                            fun_w, J_out, dJ_out, opts, stats, true, true, n_group, group, dJg_out);
-}
-
-// remo_solve_batch_field / _tensor: the same one-shot batch with the points attached (batch_run.hip locates them once and reads every
-// chunk's solutions there, field.hip)
-static int solve_batch_field(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
-                             const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
-                             const double *eval_z, double *u_out, int32_t n_pts, const double *pts, int32_t n_frhs, const int32_t *field_rhs,
-                             double *u_f, double *grad_f, double *J_f, int32_t *elem_f, const remo_opts_t *opts, remo_stats_t *stats, bool tensor,
-                             bool full = false) {
-    if (!ctx) return REMO_ERR_ARG;
-    const int dim = (mesh && mesh->dim == 2) ? 2 : 3;
-    auto nan_fill = [&]() {
-        if (u_out && eval_ptr && n_rhs > 0)
-            for (int i = 0; i < eval_ptr[n_rhs]; ++i) u_out[i] = std::nan("");
-        const size_t nv = (n_pts > 0 && n_frhs > 0) ? size_t(n_pts) * size_t(n_frhs) : 0;
-        for (size_t i = 0; i < nv && u_f; ++i) u_f[i] = std::nan("");
-        for (size_t i = 0; i < nv * dim && grad_f; ++i) grad_f[i] = std::nan("");
-        for (size_t i = 0; i < nv * dim && J_f; ++i) J_f[i] = std::nan("");
-        for (int32_t i = 0; i < n_pts && elem_f; ++i) elem_f[i] = -1;
-    };
-    nan_fill();
-    if (n_pts < 0 || n_frhs < 0 || (n_pts > 0 && !pts) || (n_frhs > 0 && !field_rhs)) return fail(ctx, REMO_ERR_ARG, "field points or field_rhs missing");
-    if (n_pts >= (1 << 28)) return fail(ctx, REMO_ERR_ARG, "too many field points");
-    for (int j = 0; j < n_frhs; ++j)
-        if (field_rhs[j] < 0 || field_rhs[j] >= n_rhs) return fail(ctx, REMO_ERR_ARG, "field_rhs names no right-hand side of the batch");
-    if (opts && opts->precision == 1)
-        return fail(ctx, REMO_ERR_ARG, "field sections are formed from the fp64 solution: remo_opts_t.precision = 1 (mixed) is not supported by remo_solve_batch_field");
-    if (mesh && (mesh->dim == 2 || mesh->dim == 3))
-        for (int64_t i = 0; i < int64_t(n_pts) * mesh->dim; ++i)
-            if (!std::isfinite(pts[i])) return fail(ctx, REMO_ERR_POINT, "non-finite point coordinate");
-    remo_batch_t *b = nullptr;
-    int rc = batch_create(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, &b, true, tensor, full);
-    if (rc != REMO_OK) return rc;
-    const remo_field_request rq{n_pts, pts, n_frhs, field_rhs, u_f, grad_f, J_f, elem_f};
-    b->field = &rq;
-    b->eval_only = true;
-    rc = remo_batch_run(ctx, b, opts, stats);
-    if (rc >= 0 && u_out) remo_batch_fetch(ctx, b, u_out);
-    if (rc < 0) nan_fill();
-    remo_batch_destroy(ctx, b);
-    return rc;
+    remo_job_t j = axis_job(n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out);
+    j.tensor = 1;
+    set_functionals(j, n_fun, fun_rhs, fun_ptr, fun_z, fun_w, J_out, dJ_out);
+    j.n_group = n_group; j.group = group; j.dJg_out = dJg_out;
+    return solve_one(ctx, mesh, j, nullptr, kFun | kGroups, false, opts, stats);
 }
 
 int remo_solve_batch_field(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma, int32_t n_rhs,
                            const int32_t *src_ptr, const double *src_z, const double *src_I, const int32_t *eval_ptr,
                            const double *eval_z, double *u_out, int32_t n_pts, const double *pts, int32_t n_frhs, const int32_t *field_rhs,
                            double *u_f, double *grad_f, double *J_f, int32_t *elem_f, const remo_opts_t *opts, remo_stats_t *stats) {
-    return solve_batch_field(ctx, mesh, n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_pts, pts, n_frhs, field_rhs, u_f, grad_f,
-                             J_f, elem_f, opts, stats, false);
+    remo_job_t j = axis_job(n_mat, sigma, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out);
+    j.n_pts = n_pts; j.pts = pts; j.n_frhs = n_frhs; j.field_rhs = field_rhs;
+    j.u_f = u_f; j.grad_f = grad_f; j.J_f = J_f; j.elem_f = elem_f;
+    return solve_one(ctx, mesh, j, nullptr, kField, false, opts, stats);
 }
 
 int remo_solve_batch_field_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int32_t n_mat, const double *sigma_tensor, int32_t n_rhs,
@@ -437,8 +456,11 @@ int remo_solve_batch_field_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int3
                                   const double *eval_z, double *u_out, int32_t n_pts, const double *pts, int32_t n_frhs,
                                   const int32_t *field_rhs, double *u_f, double *grad_f, double *J_f, int32_t *elem_f, const remo_opts_t *opts,
                                   remo_stats_t *stats) {
-    return solve_batch_field(ctx, mesh, n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out, n_pts, pts, n_frhs, field_rhs, u_f,
-                             grad_f, J_f, elem_f, opts, stats, true);
+    remo_job_t j = axis_job(n_mat, sigma_tensor, n_rhs, src_ptr, src_z, src_I, eval_ptr, eval_z, u_out);
+    j.tensor = 1;
+    j.n_pts = n_pts; j.pts = pts; j.n_frhs = n_frhs; j.field_rhs = field_rhs;
+    j.u_f = u_f; j.grad_f = grad_f; j.J_f = J_f; j.elem_f = elem_f;
+    return solve_one(ctx, mesh, j, nullptr, kField, false, opts, stats);
 }
 
 // remo_solve_job / remo_batch_create_job: the job as this library knows it - the caller's leading `size` bytes, the rest zero.
@@ -458,115 +480,6 @@ static int read_job(remo_ctx_t *ctx, const remo_job_t *job, remo_job_t &j, remo_
     return REMO_OK;
 }
 
-// every output the job names: NaN, elem_f -1 (sizes from the job's own counts; arrays that cannot be sized are left alone)
-static void job_nan_fill(const remo_mesh_t *mesh, const remo_job_t &j) {
-    const int dim = (mesh && mesh->dim == 2) ? 2 : 3;
-    const size_t ncomp = j.tensor ? ((dim == 2) ? 3 : 6) : 1;
-    auto fill = [](double *a, size_t n) { for (size_t i = 0; a && i < n; ++i) a[i] = std::nan(""); };
-    if (j.eval_ptr && j.n_rhs > 0 && j.eval_ptr[j.n_rhs] > 0) fill(j.u_out, size_t(j.eval_ptr[j.n_rhs]));
-    if (j.n_fun > 0) {
-        fill(j.J_out, size_t(j.n_fun));
-        if (j.n_mat > 0) fill(j.dJ_out, size_t(j.n_fun) * size_t(j.n_mat) * ncomp);
-        if (j.n_group > 0) fill(j.dJg_out, size_t(j.n_fun) * size_t(j.n_group) * ncomp);
-    }
-    if (j.n_pts > 0) {
-        const size_t nv = (j.n_frhs > 0) ? size_t(j.n_pts) * size_t(j.n_frhs) : 0;
-        fill(j.u_f, nv); fill(j.grad_f, nv * dim); fill(j.J_f, nv * dim);
-        for (int32_t i = 0; j.elem_f && i < j.n_pts; ++i) j.elem_f[i] = -1;
-    }
-}
-
-// ---- remo_job_secondary_t.secondary: what the entries check and resolve on the host, before any device work --------------------------------
-// sigma0[n_rhs]: the job's values, or - where it gives none - the scalar conductivity of the element that holds the right-hand
-// side's first source (lowest element number among several; all sources of the right-hand side must see that conductivity).
-static int resolve_secondary(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t &j, const remo_job_secondary_t &x, const remo_opts_t *opts,
-                             std::vector<double> &sigma0) {
-    if (j.n_fun != 0 || j.n_group != 0 || j.warm || j.n_pts != 0 || j.n_frhs != 0)
-        return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.secondary does not combine with functionals, groups, a warm object or field points");
-    if (opts && opts->precision == 1)
-        return fail(ctx, REMO_ERR_ARG, "the secondary formulation is fp64: remo_opts_t.precision = 1 (mixed) is not supported with remo_job_secondary_t.secondary");
-    if (x.sec_quad < 0 || x.sec_quad > kSecQuadMax) return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.sec_quad must be in [0, 16]");
-    if (!(x.sec_radius >= 0.0) || !std::isfinite(x.sec_radius)) return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.sec_radius must be finite and not negative");
-    if (int rc = check_batch_args(ctx, mesh, j.n_mat, j.sigma, j.n_rhs, j.src_ptr, j.src_p, j.src_I, j.eval_ptr, j.eval_p, j.tensor != 0, true)) return rc;
-    const int dim = mesh->dim, nb = dim + 1, ncomp = j.tensor ? ((dim == 2) ? 3 : 6) : 1;
-    const int ns = j.src_ptr[j.n_rhs];
-    if (dim == 2)
-        for (int q = 0; q < ns; ++q)
-            if (j.src_p[size_t(q) * 2] != 0.0) return fail(ctx, REMO_ERR_ARG, "secondary formulation in 2D: sources on the axis only (r == 0.0), no ring sources");
-    sigma0.assign(size_t(j.n_rhs), 0.0);
-    std::vector<int> pending;   // sources (I != 0) of the right-hand sides without a sigma0
-    for (int r = 0; r < j.n_rhs; ++r) {
-        const double s0 = x.sec_sigma0 ? x.sec_sigma0[r] : 0.0;
-        if (s0 != 0.0) {
-            if (!(s0 > 0.0) || !std::isfinite(s0)) return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.sec_sigma0 must be positive and finite (0.0: the conductivity at the source)");
-            sigma0[size_t(r)] = s0;
-            continue;
-        }
-        for (int q = j.src_ptr[r]; q < j.src_ptr[r + 1]; ++q)
-            if (j.src_I[q] != 0.0) pending.push_back(q);
-    }
-    if (pending.empty()) {
-        for (double &v : sigma0) if (v == 0.0) v = 1.0;   // a right-hand side without sources: u_p = 0 whatever sigma0
-        return REMO_OK;
-    }
-    std::vector<int64_t> elem(pending.size(), -1);
-    for (int64_t t = 0; t < mesh->n_elems; ++t) {   // the tolerances of k_locate
-        double X[12], lo[3], hi[3];
-        bool good = true;
-        for (int a = 0; a < nb && good; ++a) {
-            const int64_t v = mesh->conn[t * nb + a];
-            if (v < 0 || v >= mesh->n_nodes) { good = false; break; }
-            for (int k = 0; k < dim; ++k) {
-                const double c = mesh->coords[v * dim + k];
-                X[a * dim + k] = c;
-                lo[k] = a ? std::min(lo[k], c) : c; hi[k] = a ? std::max(hi[k], c) : c;
-            }
-        }
-        if (!good) continue;   // (the numbering reports the bad index)
-        for (size_t i = 0; i < pending.size(); ++i) {
-            if (elem[i] >= 0) continue;
-            const double *P = j.src_p + size_t(pending[i]) * dim;
-            bool in = true;
-            for (int k = 0; k < dim; ++k) {
-                const double ext = 1e-9 * (1.0 + hi[k] - lo[k]);
-                if (P[k] < lo[k] - ext || P[k] > hi[k] + ext) in = false;
-            }
-            if (!in) continue;
-            double l[4];
-            if (!(dim == 2 ? barycentrics<2>(X, P, l) : barycentrics<3>(X, P, l))) continue;
-            for (int a = 0; a < nb; ++a)
-                if (l[a] < -1e-10) in = false;
-            if (in) elem[i] = t;
-        }
-    }
-    for (size_t i = 0; i < pending.size(); ++i) {
-        if (elem[i] < 0) return fail(ctx, REMO_ERR_POINT, "source outside the mesh");
-        const int m = mesh->mat[elem[i]];
-        if (m < 0 || m >= j.n_mat) return fail(ctx, REMO_ERR_MESH, "material index out of range");
-        const double *S = j.sigma + size_t(m) * ncomp;
-        if (j.tensor) {
-            bool iso = S[0] == S[dim == 2 ? 2 : 3] && S[0] == S[ncomp - 1];
-            for (int c = 0; c < ncomp; ++c)
-                if (c != 0 && c != (dim == 2 ? 2 : 3) && c != ncomp - 1 && S[c] != 0.0) iso = false;
-            if (!iso) return fail(ctx, REMO_ERR_ARG, "secondary formulation: the material at a source is anisotropic - give remo_job_secondary_t.sec_sigma0");
-        }
-        int r = 0;
-        while (pending[i] >= j.src_ptr[r + 1]) ++r;
-        if (sigma0[size_t(r)] == 0.0) sigma0[size_t(r)] = S[0];
-        else if (sigma0[size_t(r)] != S[0])
-            return fail(ctx, REMO_ERR_ARG, "secondary formulation: the sources of one right-hand side lie in materials of different conductivity - give remo_job_secondary_t.sec_sigma0");
-    }
-    for (double &v : sigma0) if (v == 0.0) v = 1.0;
-    return REMO_OK;
-}
-
-static void attach_secondary(remo_batch *b, const remo_job_secondary_t &x, std::vector<double> &sigma0) {
-    b->secondary = true;
-    b->sec_quad = x.sec_quad;
-    b->sec_radius = x.sec_radius;
-    b->sec_sigma0.swap(sigma0);
-}
-
 int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, const remo_opts_t *opts, remo_stats_t *stats) {
     remo_job_t j;
     remo_job_secondary_t x;
@@ -575,8 +488,6 @@ int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *j
     if (rc == REMO_OK && fun && field) rc = fail(ctx, REMO_ERR_ARG, "field points together with functionals: two calls");
     if (rc == REMO_OK && !fun && (j.n_group != 0 || j.warm)) rc = fail(ctx, REMO_ERR_ARG, "groups or a warm object without functionals");
     if (rc == REMO_OK && x.secondary != 0 && x.secondary != 1) rc = fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.secondary must be 0 or 1");
-    std::vector<double> sigma0;
-    if (rc == REMO_OK && x.secondary) rc = resolve_secondary(ctx, mesh, j, x, opts, sigma0);
     if (rc != REMO_OK) {
         if (ctx && job && job->size >= offsetof(remo_job_t, n_fun)) {   // a job that could be read: its outputs as the entries leave them on an error
             job_nan_fill(mesh, j);
@@ -584,26 +495,8 @@ int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *j
         }
         return rc;
     }
-    if (x.secondary) {   // remo_solve_batch with the load vector and the read-out of the secondary formulation (batch_run.hip)
-        job_nan_fill(mesh, j);
-        remo_batch_t *b = nullptr;
-        rc = batch_create(ctx, mesh, j.n_mat, j.sigma, j.n_rhs, j.src_ptr, j.src_p, j.src_I, j.eval_ptr, j.eval_p, &b, true, j.tensor != 0, true);
-        if (rc != REMO_OK) return rc;
-        attach_secondary(b, x, sigma0);
-        b->eval_only = true;
-        rc = remo_batch_run(ctx, b, opts, stats);
-        if (rc >= 0 && j.u_out) remo_batch_fetch(ctx, b, j.u_out);
-        remo_batch_destroy(ctx, b);
-        return rc;
-    }
-    if (field)
-        return solve_batch_field(ctx, mesh, j.n_mat, j.sigma, j.n_rhs, j.src_ptr, j.src_p, j.src_I, j.eval_ptr, j.eval_p, j.u_out, j.n_pts, j.pts, j.n_frhs,
-                                 j.field_rhs, j.u_f, j.grad_f, j.J_f, j.elem_f, opts, stats, j.tensor != 0, true);
-    if (fun)
-        return solve_batch_sens(ctx, mesh, j.n_mat, j.sigma, j.n_rhs, j.src_ptr, j.src_p, j.src_I, j.eval_ptr, j.eval_p, j.u_out, j.n_fun, j.fun_rhs,
-                                j.fun_ptr, j.fun_p, j.fun_w, j.J_out, j.dJ_out, opts, stats, j.tensor != 0, j.n_group != 0, j.n_group, j.group, j.dJg_out,
-                                j.warm, true);
-    return solve_batch(ctx, mesh, j.n_mat, j.sigma, j.n_rhs, j.src_ptr, j.src_p, j.src_I, j.eval_ptr, j.eval_p, j.u_out, opts, stats, j.tensor != 0, true);
+    const unsigned parts = (fun ? kFun : 0) | (j.n_group != 0 ? kGroups : 0) | (field ? kField : 0);
+    return solve_one(ctx, mesh, j, x.secondary ? &x : nullptr, parts, true, opts, stats);
 }
 
 int remo_batch_create_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, remo_batch_t **out) {
@@ -614,7 +507,7 @@ int remo_batch_create_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_j
     std::vector<double> sigma0;
     if (x.secondary)   // (the batch entries read the sources and the evaluation points only: the other parts of the job must be empty here too)
         if (int rc = resolve_secondary(ctx, mesh, j, x, nullptr, sigma0)) return rc;
-    const int rc = batch_create(ctx, mesh, j.n_mat, j.sigma, j.n_rhs, j.src_ptr, j.src_p, j.src_I, j.eval_ptr, j.eval_p, out, false, j.tensor != 0, true);
+    const int rc = batch_create(ctx, mesh, j, true, out, false);
     if (rc == REMO_OK && x.secondary) attach_secondary(*out, x, sigma0);
     return rc;
 }

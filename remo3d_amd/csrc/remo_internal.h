@@ -211,4 +211,9 @@ inline int fail(remo_ctx *ctx, int code, const std::string &msg) {
     return code;
 }
 
+// The host checks of a batch's mesh, conductivities, sources and evaluation points: everything that is refused before any device
+// work (remo_api.hip).  full: src_p / eval_p hold dim coordinates per point (the job entries) and are checked for finiteness here;
+// else they hold axis positions z, and a bad one is found when the points are located.
+int check_batch_args(remo_ctx *ctx, const remo_mesh_t *mesh, const remo_job_t &j, bool full);
+
 }  // namespace remo

@@ -19,6 +19,7 @@
 
 #include <vector>
 
+#include "../../include/remo3d_hip.h"
 #include "fem_p3.h"
 
 namespace remo {
@@ -150,5 +151,13 @@ void launch_sec_gather(int dim, int64_t n, int k, const int32_t *adjptr, const u
 // out[q] += u_p(point q) for the points that are no sources; pp: z per point (on_axis) or dim coordinates
 void launch_sec_add_primary(int dim, int npts, const int32_t *pt_rhs, const double *pt_I, const double *pp, bool on_axis, const double *src,
                             const int32_t *ptr, double R, double *out, hipStream_t s);
+
+// ---- host: the job entries (remo_api.hip), before any device work ------------------------------------------------------------------
+// Checks the members of x and the batch's own arguments (check_batch_args, points as full coordinates) and resolves sigma0[n_rhs]:
+// the job's values, or the scalar conductivity of the element that holds the right-hand side's first source.  opts may be NULL.
+int resolve_secondary(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t &j, const remo_job_secondary_t &x, const remo_opts_t *opts,
+                      std::vector<double> &sigma0);
+// marks the batch for the formulation and hands it sigma0 (swapped out of the argument)
+void attach_secondary(remo_batch_t *b, const remo_job_secondary_t &x, std::vector<double> &sigma0);
 
 }  // namespace remo

@@ -5,13 +5,15 @@
 // one column at a time in registers (all arrays are indexed by unrolled loops: nothing in scratch), a transposing wave reduction
 // (wave_util.h) leaves each sum on one lane, which stores it.  k_sec_gather then adds, per row, the entries of the row's elements in
 // ascending element order.  Both orders are fixed: two runs give the same bits.
+// At the end of the file, the host side: what a job entry checks and resolves before any device work.
 #include <limits.h>
 
+#include <algorithm>
 #include <cmath>
 
 #include "secondary.h"
 #include "wave_util.h"
-#include "../../include/remo3d_hip.h"
+#include "remo_internal.h"
 
 namespace remo {
 
@@ -258,6 +260,97 @@ void launch_sec_add_primary(int dim, int npts, const int32_t *pt_rhs, const doub
         hipLaunchKernelGGL(k_sec_add_primary<2>, dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, pp, on_axis ? 1 : 0, src, ptr, R, out);
     else
         hipLaunchKernelGGL(k_sec_add_primary<3>, dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, pp, on_axis ? 1 : 0, src, ptr, R, out);
+}
+
+// ---- host: what the job entries check and resolve for remo_job_secondary_t.secondary, before any device work ------------------------------
+// sigma0[n_rhs]: the job's values, or - where it gives none - the scalar conductivity of the element that holds the right-hand
+// side's first source (lowest element number among several; all sources of the right-hand side must see that conductivity).
+int resolve_secondary(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t &j, const remo_job_secondary_t &x, const remo_opts_t *opts,
+                      std::vector<double> &sigma0) {
+    if (j.n_fun != 0 || j.n_group != 0 || j.warm || j.n_pts != 0 || j.n_frhs != 0)
+        return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.secondary does not combine with functionals, groups, a warm object or field points");
+    if (opts && opts->precision == 1)
+        return fail(ctx, REMO_ERR_ARG, "the secondary formulation is fp64: remo_opts_t.precision = 1 (mixed) is not supported with remo_job_secondary_t.secondary");
+    if (x.sec_quad < 0 || x.sec_quad > kSecQuadMax) return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.sec_quad must be in [0, 16]");
+    if (!(x.sec_radius >= 0.0) || !std::isfinite(x.sec_radius)) return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.sec_radius must be finite and not negative");
+    if (int rc = check_batch_args(ctx, mesh, j, true)) return rc;
+    const int dim = mesh->dim, nb = dim + 1, ncomp = j.tensor ? ((dim == 2) ? 3 : 6) : 1;
+    const int ns = j.src_ptr[j.n_rhs];
+    if (dim == 2)
+        for (int q = 0; q < ns; ++q)
+            if (j.src_p[size_t(q) * 2] != 0.0) return fail(ctx, REMO_ERR_ARG, "secondary formulation in 2D: sources on the axis only (r == 0.0), no ring sources");
+    sigma0.assign(size_t(j.n_rhs), 0.0);
+    std::vector<int> pending;   // sources (I != 0) of the right-hand sides without a sigma0
+    for (int r = 0; r < j.n_rhs; ++r) {
+        const double s0 = x.sec_sigma0 ? x.sec_sigma0[r] : 0.0;
+        if (s0 != 0.0) {
+            if (!(s0 > 0.0) || !std::isfinite(s0)) return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.sec_sigma0 must be positive and finite (0.0: the conductivity at the source)");
+            sigma0[size_t(r)] = s0;
+            continue;
+        }
+        for (int q = j.src_ptr[r]; q < j.src_ptr[r + 1]; ++q)
+            if (j.src_I[q] != 0.0) pending.push_back(q);
+    }
+    if (pending.empty()) {
+        for (double &v : sigma0) if (v == 0.0) v = 1.0;   // a right-hand side without sources: u_p = 0 whatever sigma0
+        return REMO_OK;
+    }
+    std::vector<int64_t> elem(pending.size(), -1);
+    for (int64_t t = 0; t < mesh->n_elems; ++t) {   // the tolerances of k_locate
+        double X[12], lo[3], hi[3];
+        bool good = true;
+        for (int a = 0; a < nb && good; ++a) {
+            const int64_t v = mesh->conn[t * nb + a];
+            if (v < 0 || v >= mesh->n_nodes) { good = false; break; }
+            for (int k = 0; k < dim; ++k) {
+                const double c = mesh->coords[v * dim + k];
+                X[a * dim + k] = c;
+                lo[k] = a ? std::min(lo[k], c) : c; hi[k] = a ? std::max(hi[k], c) : c;
+            }
+        }
+        if (!good) continue;   // (the numbering reports the bad index)
+        for (size_t i = 0; i < pending.size(); ++i) {
+            if (elem[i] >= 0) continue;
+            const double *P = j.src_p + size_t(pending[i]) * dim;
+            bool in = true;
+            for (int k = 0; k < dim; ++k) {
+                const double ext = 1e-9 * (1.0 + hi[k] - lo[k]);
+                if (P[k] < lo[k] - ext || P[k] > hi[k] + ext) in = false;
+            }
+            if (!in) continue;
+            double l[4];
+            if (!(dim == 2 ? barycentrics<2>(X, P, l) : barycentrics<3>(X, P, l))) continue;
+            for (int a = 0; a < nb; ++a)
+                if (l[a] < -1e-10) in = false;
+            if (in) elem[i] = t;
+        }
+    }
+    for (size_t i = 0; i < pending.size(); ++i) {
+        if (elem[i] < 0) return fail(ctx, REMO_ERR_POINT, "source outside the mesh");
+        const int m = mesh->mat[elem[i]];
+        if (m < 0 || m >= j.n_mat) return fail(ctx, REMO_ERR_MESH, "material index out of range");
+        const double *S = j.sigma + size_t(m) * ncomp;
+        if (j.tensor) {
+            bool iso = S[0] == S[dim == 2 ? 2 : 3] && S[0] == S[ncomp - 1];
+            for (int c = 0; c < ncomp; ++c)
+                if (c != 0 && c != (dim == 2 ? 2 : 3) && c != ncomp - 1 && S[c] != 0.0) iso = false;
+            if (!iso) return fail(ctx, REMO_ERR_ARG, "secondary formulation: the material at a source is anisotropic - give remo_job_secondary_t.sec_sigma0");
+        }
+        int r = 0;
+        while (pending[i] >= j.src_ptr[r + 1]) ++r;
+        if (sigma0[size_t(r)] == 0.0) sigma0[size_t(r)] = S[0];
+        else if (sigma0[size_t(r)] != S[0])
+            return fail(ctx, REMO_ERR_ARG, "secondary formulation: the sources of one right-hand side lie in materials of different conductivity - give remo_job_secondary_t.sec_sigma0");
+    }
+    for (double &v : sigma0) if (v == 0.0) v = 1.0;
+    return REMO_OK;
+}
+
+void attach_secondary(remo_batch *b, const remo_job_secondary_t &x, std::vector<double> &sigma0) {
+    b->secondary = true;
+    b->sec_quad = x.sec_quad;
+    b->sec_radius = x.sec_radius;
+    b->sec_sigma0.swap(sigma0);
 }
 
 }  // namespace remo

@@ -147,29 +147,27 @@ def _secondary_members(secondary, n_rhs):
 
 
 def _batch_args(handle, mesh, sigma, sources, evals, job=False, secondary=None):
-    """The arguments every batch entry begins with (remo_solve_batch*, remo_batch_create*): handle, mesh, conductivity table, sources
-    and evaluation points.  Returns (args, sigma table, tensor?, eval_ptr, keep); keep holds what the pointers in args look at.
-    job: the same as the leading members of a remo_job_t (positions as points) - args is then [handle, mesh, job].
+    """What every batch entry begins with (remo_solve_batch*, remo_solve_job, remo_batch_create*): [handle, mesh, job], the job a
+    remo_job_t with the conductivity table, the sources and the evaluation points set.  Returns (args, sigma table, tensor?,
+    eval_ptr, keep); keep holds what the pointers in the job look at.
+    job: positions are points, as remo_solve_job reads them; else src_p / eval_p hold axis z and the job only names the arguments of
+    an entry that takes a list (_lib.legacy_args).
     secondary: dict(radius, sigma0, quad) - the job with the members of the secondary-potential formulation set (job is implied)."""
     job = job or secondary is not None
     sigma, tensor = sigma_table(sigma, int(mesh.dim))
     src_ptr, sz, sI, eval_ptr, ez = _rhs_arrays(sources, evals, int(mesh.dim) if job else 0)
     ms, keep = _lib.mesh_struct(mesh)
-    if job:
-        Job = _lib.RemoJob if secondary is None else _lib.RemoJobSecondary
-        j = Job(size=C.sizeof(Job), tensor=int(tensor), n_mat=len(sigma), sigma=ptr(sigma, C.c_double), n_rhs=len(sources),
-                         src_ptr=ptr(src_ptr, C.c_int32), src_p=ptr(sz, C.c_double), src_I=ptr(sI, C.c_double),
-                         eval_ptr=ptr(eval_ptr, C.c_int32), eval_p=ptr(ez, C.c_double))
-        s0 = None
-        if secondary is not None:
-            j.sec_quad, j.sec_radius, s0, _ = _secondary_members(secondary, len(sources))
-            j.secondary = 1
-            if s0 is not None:
-                j.sec_sigma0 = ptr(s0, C.c_double)
-        return [handle, C.byref(ms), j], sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez, s0)
-    args = [handle, C.byref(ms), len(sigma), ptr(sigma, C.c_double), len(sources), ptr(src_ptr, C.c_int32), ptr(sz, C.c_double),
-            ptr(sI, C.c_double), ptr(eval_ptr, C.c_int32), ptr(ez, C.c_double)]
-    return args, sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez)
+    Job = _lib.RemoJob if secondary is None else _lib.RemoJobSecondary
+    j = Job(size=C.sizeof(Job), tensor=int(tensor), n_mat=len(sigma), sigma=ptr(sigma, C.c_double), n_rhs=len(sources),
+            src_ptr=ptr(src_ptr, C.c_int32), src_p=ptr(sz, C.c_double), src_I=ptr(sI, C.c_double),
+            eval_ptr=ptr(eval_ptr, C.c_int32), eval_p=ptr(ez, C.c_double))
+    s0 = None
+    if secondary is not None:
+        j.sec_quad, j.sec_radius, s0, _ = _secondary_members(secondary, len(sources))
+        j.secondary = 1
+        if s0 is not None:
+            j.sec_sigma0 = ptr(s0, C.c_double)
+    return [handle, C.byref(ms), j], sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez, s0)
 
 
 def _field_points(points, dim):
@@ -272,13 +270,13 @@ class Context:
         or "_field": the common arguments, then the functionals and the groups - or the field points - with their outputs where the kind
         has them.  Returns (potentials, [J, dJ, [dJg] | field dict,] stats, rc).
         Positions (of sources, evaluation points, functionals) are 1-D arrays of axis z or [m, dim] arrays of points; with one item
-        of the second kind the same arrays go into a remo_job_t instead (remo_solve_job), every item as points."""
+        of the second kind the job goes to remo_solve_job, every item as points; else its members, positions as axis z, are the
+        arguments of the kind's own symbol."""
         job = secondary is not None or _off_axis([z for (z, _) in sources], evals, [z for (_, z, _) in functionals] if functionals else [])
-        args, sigma, tensor, eval_ptr, keep = _batch_args(self._h, mesh, sigma, sources, evals, job, secondary)
+        (handle, ms, j), sigma, tensor, eval_ptr, keep = _batch_args(self._h, mesh, sigma, sources, evals, job, secondary)
         d, nc = int(mesh.dim), (sigma.shape[1] if tensor else 1)
         out = np.full(int(eval_ptr[-1]), np.nan)
-        args.append(ptr(out, C.c_double))
-        n_head = len(args)
+        j.u_out = ptr(out, C.c_double)
         J, grads, field = [], [], []
         if kind == "_field":
             points = _field_points(points, d)
@@ -286,42 +284,35 @@ class Context:
             n_pts, n_f = points.shape[0], field_rhs.size
             field = [dict(u=np.full((n_f, n_pts), np.nan), grad=np.full((n_f, n_pts, d), np.nan), J=np.full((n_f, n_pts, d), np.nan),
                           elem=np.full(n_pts, -1, dtype=np.int32))]
-            args += [n_pts, ptr(points, C.c_double), n_f, ptr(field_rhs, C.c_int32), ptr(field[0]["u"], C.c_double), ptr(field[0]["grad"], C.c_double),
-                     ptr(field[0]["J"], C.c_double), ptr(field[0]["elem"], C.c_int32)]
+            j.n_pts, j.pts, j.n_frhs, j.field_rhs = n_pts, ptr(points, C.c_double), n_f, ptr(field_rhs, C.c_int32)
+            j.u_f, j.grad_f, j.J_f = (ptr(field[0][name], C.c_double) for name in ("u", "grad", "J"))
+            j.elem_f = ptr(field[0]["elem"], C.c_int32)
         elif kind:
             n_fun = len(functionals)
             fun_rhs, fun_ptr, fz, fw = _functional_arrays(functionals, d if job else 0)
-            args += [n_fun, ptr(fun_rhs, C.c_int32), ptr(fun_ptr, C.c_int32), ptr(fz, C.c_double), ptr(fw, C.c_double)]
+            j.n_fun, j.fun_rhs, j.fun_ptr, j.fun_p, j.fun_w = n_fun, ptr(fun_rhs, C.c_int32), ptr(fun_ptr, C.c_int32), ptr(fz, C.c_double), ptr(fw, C.c_double)
             J, grads = [np.full(n_fun, np.nan)], [np.full((n_fun, len(sigma), nc), np.nan)]
+            j.J_out, j.dJ_out = ptr(J[0], C.c_double), ptr(grads[0], C.c_double)
             if kind == "_sens_groups":
                 groups = np.ascontiguousarray(groups, dtype=np.int32).ravel()
                 if groups.size != keep[1][1].shape[0]:
                     raise ValueError("groups must hold one id per element")
                 n_group = int(groups.max(initial=-1)) + 1 if n_group is None else int(n_group)
-                args += [n_group, ptr(groups, C.c_int32)]
                 grads.append(np.full((n_fun, max(n_group, 0), nc), np.nan))
-            args += [ptr(a, C.c_double) for a in J + grads]
+                j.n_group, j.group, j.dJg_out = n_group, ptr(groups, C.c_int32), ptr(grads[1], C.c_double)
             if kind == "_sens_warm":
-                args.append(warm._h)
+                j.warm = warm._h
         st = RemoStats()
         o = opts if opts is not None else make_opts()
-        if job:   # the arguments behind the head, by the names remo_job_t gives them
-            names = {"": [], "_field": ["n_pts", "pts", "n_frhs", "field_rhs", "u_f", "grad_f", "J_f", "elem_f"],
-                     "_sens": ["n_fun", "fun_rhs", "fun_ptr", "fun_p", "fun_w", "J_out", "dJ_out"],
-                     "_sens_warm": ["n_fun", "fun_rhs", "fun_ptr", "fun_p", "fun_w", "J_out", "dJ_out", "warm"],
-                     "_sens_groups": ["n_fun", "fun_rhs", "fun_ptr", "fun_p", "fun_w", "n_group", "group", "J_out", "dJ_out", "dJg_out"]}[kind]
-            j = args[2]
-            j.u_out = args[n_head - 1]
-            for name, value in zip(names, args[n_head:]):
-                setattr(j, name, value)
-            if secondary is not None and not _secondary_members(secondary, len(sources))[3]:
-                rc, msg = REMO_ERR_ARG, "secondary: sigma0 must be positive and finite (None: the conductivity at the source)"
-                if raise_on_error:
-                    raise RemoError(rc, msg)
-            else:
-                rc = self._L.remo_solve_job(args[0], args[1], C.byref(j), C.byref(o), C.byref(st))
+        if not job:
+            entry = getattr(self._L, "remo_solve_batch" + kind + ("_tensor" if tensor else ""))
+            rc = entry(handle, ms, *_lib.legacy_args(j, kind), C.byref(o), C.byref(st))
+        elif secondary is not None and not _secondary_members(secondary, len(sources))[3]:
+            rc, msg = REMO_ERR_ARG, "secondary: sigma0 must be positive and finite (None: the conductivity at the source)"
+            if raise_on_error:
+                raise RemoError(rc, msg)
         else:
-            rc = getattr(self._L, "remo_solve_batch" + kind + ("_tensor" if tensor else ""))(*args, C.byref(o), C.byref(st))
+            rc = self._L.remo_solve_job(handle, ms, C.byref(j), C.byref(o), C.byref(st))
         if rc < 0 and raise_on_error:
             raise RemoError(rc, self.last_error())
         potentials = [out[eval_ptr[k]:eval_ptr[k + 1]] for k in range(len(evals))]
@@ -419,12 +410,12 @@ class Batch:
         job = secondary is not None or _off_axis([z for (z, _) in sources], evals)   # positions given as points: remo_batch_create_job
         if secondary is not None and not _secondary_members(secondary, len(sources))[3]:
             raise RemoError(REMO_ERR_ARG, "secondary: sigma0 must be positive and finite (None: the conductivity at the source)")
-        args, _, tensor, self._eval_ptr, keep = _batch_args(ctx._h, mesh, sigma, sources, evals, job, secondary)
+        (handle, ms, j), _, tensor, self._eval_ptr, keep = _batch_args(ctx._h, mesh, sigma, sources, evals, job, secondary)
         h = C.c_void_p()
         if job:
-            rc = self._L.remo_batch_create_job(args[0], args[1], C.byref(args[2]), C.byref(h))
+            rc = self._L.remo_batch_create_job(handle, ms, C.byref(j), C.byref(h))
         else:
-            rc = (self._L.remo_batch_create_tensor if tensor else self._L.remo_batch_create)(*args, C.byref(h))
+            rc = (self._L.remo_batch_create_tensor if tensor else self._L.remo_batch_create)(handle, ms, *_lib.legacy_args(j), C.byref(h))
         if rc != 0:
             raise RemoError(rc, ctx.last_error())
         self._h = h

@@ -40,23 +40,20 @@ def _axis_batch(dim):
 @pytest.mark.parametrize("dim", [2, 3])
 def test_all_axis_job_has_the_bits_of_the_axis_entries(dim, mesh2d, mesh3d, gpu_ctx):
     """The same batch as 1-D axis positions (legacy symbols) and through solver.axis_points (remo_solve_job), op = 2: potentials, J,
-    dJ, dJg, the field outputs and pcg_steps are equal bit for bit for the plain, sens, sens-groups and field kinds - an all-axis
-    batch is located by k_locate (Context.point_location() == 0)."""
+    dJ, dJg, the field outputs and pcg_steps are equal bit for bit for the plain, sens, sens-groups and field kinds, with scalar
+    conductivities and with tensors (all twelve symbols of the argument-list entries with the warm kind below) - an all-axis batch is
+    located by k_locate (Context.point_location() == 0).
+    warm: two consecutive calls per route, each route with its own WarmState - potentials, J, dJ and pcg_steps of both calls and
+    WarmState.info() after each are equal."""
+    from remo3d_amd import solver
     mesh = _mesh(dim, mesh2d, mesh3d)
     src, ev, fun = _axis_batch(dim)
     o = _opts(op="csr")
     rho = np.abs(mesh.coords[mesh.conn].mean(axis=1)[:, 0])
     groups = np.where(rho < 0.1, 0, np.where(rho < 2.0, 1, -1)).astype(np.int32)
     P = np.concatenate([np.asarray(src[1][0]), np.array([[0.3] + [0.0] * (dim - 2) + [0.2]]), np.full((1, dim), 90.0)])
-    calls = {
-        "plain": lambda s, e, f: gpu_ctx.solve_batch(mesh, SIGMA3, s, e, o),
-        "sens": lambda s, e, f: gpu_ctx.solve_batch_sens(mesh, SIGMA3, s, e, f, o),
-        "groups": lambda s, e, f: gpu_ctx.solve_batch_sens_groups(mesh, SIGMA3, s, e, f, groups, 2, o),
-        "field": lambda s, e, f: gpu_ctx.solve_batch_field(mesh, SIGMA3, s, e, P, [2, 0], o),
-    }
-    for name, call in calls.items():
-        old = call(S.SOURCES, S.EVALS, S.FUNCTIONALS)
-        new = call(src, ev, fun)
+
+    def same(old, new, name):
         assert gpu_ctx.point_location() == 0, name
         assert old[-1] == 0 and new[-1] == 0
         assert old[-2]["pcg_steps"] == new[-2]["pcg_steps"], name
@@ -67,6 +64,22 @@ def test_all_axis_job_has_the_bits_of_the_axis_entries(dim, mesh2d, mesh3d, gpu_
                 assert all(np.array_equal(x, y) for x, y in zip(a, b)), name
             else:
                 assert np.array_equal(a, b), name
+
+    for label, sigma in (("scalar", SIGMA3), ("tensor", S.general_tensors(dim))):
+        calls = {
+            "plain": lambda s, e, f: gpu_ctx.solve_batch(mesh, sigma, s, e, o),
+            "sens": lambda s, e, f: gpu_ctx.solve_batch_sens(mesh, sigma, s, e, f, o),
+            "groups": lambda s, e, f: gpu_ctx.solve_batch_sens_groups(mesh, sigma, s, e, f, groups, 2, o),
+            "field": lambda s, e, f: gpu_ctx.solve_batch_field(mesh, sigma, s, e, P, [2, 0], o),
+        }
+        for name, call in calls.items():
+            same(call(S.SOURCES, S.EVALS, S.FUNCTIONALS), call(src, ev, fun), (label, name))
+        with solver.WarmState(0) as w_old, solver.WarmState(0) as w_new:
+            for k, factor in enumerate((1.0, 1.01)):   # the second call starts from the first one's solutions
+                old = gpu_ctx.solve_batch_sens(mesh, factor * np.asarray(sigma), S.SOURCES, S.EVALS, S.FUNCTIONALS, o, warm=w_old)
+                new = gpu_ctx.solve_batch_sens(mesh, factor * np.asarray(sigma), src, ev, fun, o, warm=w_new)
+                same(old, new, (label, "warm", k))
+                assert w_old.info() == w_new.info() and w_old.info()["used_last"] == k, (label, k)
 
 
 # ---- 2. off-axis against the reference ----------------------------------------------------------------------------------------------
