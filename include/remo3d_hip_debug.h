@@ -60,6 +60,11 @@ int remo_debug_field_timing(remo_ctx_t *ctx, double *out2);
 /* How the last remo_batch_run on this context located the points of its right-hand sides: 0 = the kernels of the axis entries (every
  * lateral coordinate exactly 0), 1 = the cell grid of the field sections (a batch of remo_solve_job with a point off the axis). */
 int remo_debug_point_location(remo_ctx_t *ctx);
+/* Bytes per stored value of the PCG's search direction in the last remo_batch_run on this context: 4 or 8 (0 before the first run).
+ * 4: a one-shot fp64 solve on the patch operator that carries only the evaluated values of x (remo_debug_tune key 41), or the mixed
+ * mode (precision = 1), whose inner solver stores every vector in fp32.  8: every other fp64 solve - resident batches, the CSR
+ * product and all of 2D, the sens, warm and field entries. */
+int remo_debug_direction_bytes(remo_ctx_t *ctx);
 /* The load-vector launches (element vectors + row sums, all chunks) of the last remo_batch_run of a batch with remo_job_secondary_t.secondary
  * on this context, ms by HIP events; 0 when the last run was none. */
 int remo_debug_secondary_timing(remo_ctx_t *ctx, double *ms);
@@ -87,6 +92,10 @@ int remo_debug_secondary_timing(remo_ctx_t *ctx, double *ms);
  *          pass (k_pcg_update_tile, fp64 storage);
  *   39  0 = one-shot fp64 solves (remo_solve_batch[_tensor]) carry the whole solution block instead of only the values the
  *       evaluation points read (default 1; bit-identical potentials on the CSR product).  Resident batches always keep the whole x.
+ *   41  0 = those solves keep the search direction p in fp64 on the patch operator too (default 1: p is STORED in fp32 there and
+ *       widened by its three readers - the direction launch, the operator's staging phase, the evaluated values of the update
+ *       launch; r, q, the slab and every sum stay fp64; same potentials to the solve's tolerance, under 1 % more steps).  Keys
+ *       39 = 0, 25 = 0 and 22 = 0 imply fp64.  remo_debug_direction_bytes says which form the last run took.
  *   40  1 = the patch operator takes one element per lane: patches of 256 / k elements (k = right-hand sides of the batch);
  *       2 (default) = two elements per lane, one after the other, in fp64 solves with k >= 3: patches of 2 * (256 / k) elements
  *       (k_patch_apply ROUNDS = 2).  A batch whose largest such patch does not fit the tables or LDS gets the tables of 1.

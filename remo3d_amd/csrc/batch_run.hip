@@ -115,6 +115,7 @@ void plan_point_location(const remo_batch *b, Points &p) {
 struct Plan {
     int kmax = 0;                       // right-hand sides per chunk
     bool x_ev_only = false;             // no x, only the values the evaluation points read (PcgBuffersT::x_ev)
+    bool p32 = false;                   // ... and, if the operator turns out to be the patch operator, the search direction in fp32 storage (PcgBuffersT::p32)
     bool want_patch = false, want_amg = false;
     int64_t vertex_block_above = -1;    // build_symbolic_gpu: element count above which only the P1 block gets a pattern
     size_t field_bytes = 0;             // remo_solve_batch_field: everything field_take takes (Field::bytes)
@@ -145,6 +146,8 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
     need += (1 << 20);                                               // alignment of every take + the small buffers
     if (p.x_ev_only) {   // slots + values instead of x
         need -= size_t(ndof_max) * 8 * kmax;                         // x, one of the five vectors above
+        // (p.p32: the direction takes half its room; the other half stays in the estimate for the fp64 vector set_launch_shape takes
+        // instead where the patch operator does not run after all)
         need += size_t(npts + 1) * N * 16;                           // d_ev_at, d_x_ev
     }
     need += size_t(nv + 64) * 200 * 20 + size_t(nv + 64) * 8;        // squared vertex block (paired Chebyshev steps): sq_col, sq_a, sq_b; sq_rowptr
@@ -186,6 +189,9 @@ Plan plan_batch(const remo_batch *b, const remo_opts_t &o, const Points &pts, si
     p.x_ev_only = b->eval_only && !b->sens && !b->field && g_tune.x_ev && g_tune.x_in_direction && o.precision == 0;
     // the patch operator is 3D only; a 2D batch always runs on the CSR product, whatever `op` says
     p.want_patch = dim == 3 && (o.op == 3 || o.op == 0);
+    // on that path and the patch operator the search direction is stored in fp32 (remo_debug_tune key 41; whole-x solves, i.e.
+    // keys 39 = 0 and 25 = 0, keep fp64): nothing but the direction launch, the operator's staging and the x_ev slots reads it
+    p.p32 = p.x_ev_only && p.want_patch && g_tune.p32 && g_tune.defer_q;
     p.want_amg = o.preconditioner != 0 && g_tune.amg != 1 &&
                  (g_tune.amg == 2 || o.coarse == 2 || o.coarse == 3 || (o.coarse == 0 && dim == 2 && o.coarse_degree <= 0));   // coarse = 0: an explicit degree asks for the polynomial
     // patch operator batches above 200 k tetrahedra (assemble = 2: any size) number only the P1 block of the matrix
@@ -294,7 +300,9 @@ void take_pcg_buffers(const Run &r, const Plan &plan, const System &sys, Solve &
     PcgBuffers &buf = sv.buf;
     buf.x = plan.x_ev_only ? nullptr : ctx->take<double>(n * kmax);
     buf.r = ctx->take<double>(n * kmax);
-    buf.p = ctx->take<double>(n * kmax); buf.q = ctx->take<double>(n * kmax);
+    if (plan.p32) buf.p32 = ctx->take<float>(n * kmax + 4);      // (set_launch_shape takes the fp64 vector instead where the patch operator does not run)
+    else buf.p = ctx->take<double>(n * kmax);
+    buf.q = ctx->take<double>(n * kmax);
     buf.dinv = sys.d_dinv;
     buf.part_pq = ctx->take<double>(kMaxPartialBlocks * 8);
     buf.part_rz = ctx->take<double>(kMaxPartialBlocks * 8 * 2);
@@ -749,7 +757,7 @@ int choose_operator(const Run &r, const Plan &plan, const System &sys, const Sol
 }
 
 // grids of the PCG's launches and the forms of its update / direction launches
-void set_launch_shape(const Run &r, const System &sys, bool patch_op, PcgBuffers &buf) {
+void set_launch_shape(const Run &r, const Plan &plan, const System &sys, bool patch_op, PcgBuffers &buf) {
     remo_batch *b = r.b;
     const int lpr = choose_lanes_per_row(sys.n, b->sym.nnz);
     buf.nb_spmv = spmv_grid(sys.n, lpr);
@@ -758,6 +766,13 @@ void set_launch_shape(const Run &r, const System &sys, bool patch_op, PcgBuffers
     buf.x_in_direction = g_tune.x_in_direction != 0;
     buf.pq_bins = buf.defer_q && g_tune.dot_bins != 0;
     if (patch_op) b->patch64.dot_bins = buf.pq_bins;
+    // the fp32 search direction needs the patch operator with its shared rows left in the slab (no update form that reads p row by
+    // row, no CSR product): anything else - op = 0 on a mesh the tables do not take, a folded Chebyshev step - gets its fp64 vector now
+    if (buf.p32 && !(patch_op && buf.defer_q && buf.x_in_direction)) {
+        buf.p32 = nullptr;
+        buf.p = r.ctx->take<double>(sys.n * plan.kmax);
+    }
+    r.ctx->direction_bytes = (buf.p32 || r.o.precision == 1) ? 4 : 8;     // (mixed mode: the inner solver's vectors are fp32, p among them)
 }
 
 // ---- mixed precision: the same solve in fp32 storage ----------------------------------------------------------------------------
@@ -1125,7 +1140,7 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         // serialize_solves: batches of other contexts may number and assemble beside this PCG, but not run theirs
         std::unique_lock<std::mutex> solve_turn(g_solve_mutex, std::defer_lock);
         if (o.serialize_solves) solve_turn.lock();
-        set_launch_shape(r, sys, patch_op, sv.buf);
+        set_launch_shape(r, plan, sys, patch_op, sv.buf);
         const bool mixed = (o.precision == 1);
         MixedBuffers mx;
         if (mixed) mx = mixed_buffers(r, plan, sys, sv, vb, patch_op);   // fp32 images of the system for the inner solver

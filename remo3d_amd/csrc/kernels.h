@@ -70,6 +70,12 @@ template <class T> struct PcgBuffersT {
     const int64_t *x_ev_at = nullptr;
     T *x_ev = nullptr;
     int x_ev_n = 0;
+    // evaluated values only, on the patch operator with defer_q (T = double): the search direction is STORED in fp32 here and p is
+    // nullptr.  p is written by the direction launch and read by it, by the operator's staging phase and by the x_ev slots of the
+    // update launch - all three widen the stored value, none keeps an unrounded copy, so q = A p, x += alpha p and r -= alpha q use
+    // one and the same p and the recurrences stay consistent; the stored direction loses conjugacy at the 6e-8 level only
+    // (remo_debug_tune key 41).  [n*k]
+    float *p32 = nullptr;
     PcgProgress *progress; // mapped host records [progress_len]: one per step, the last one is the "all columns frozen" record
     int progress_len;
     int nb_spmv, nb_vec;    // grid sizes actually used (partials valid for these many blocks)
@@ -160,6 +166,8 @@ template <class T> bool patch_applies(const CsrViewT<T> &A, int k);   // launch_
 template <class T> void launch_spmm(const CsrViewT<T> &A, int k, const T *x, T *y, double *part, const double *scal, int nblocks, hipStream_t s, int step = 0, bool defer = false);
 
 template <class T> void launch_patch_spmm(const CsrViewT<T> &A, int k, const T *x, T *y, double *part, const double *scal, int nblocks, hipStream_t s, int step, bool defer);   // patch.hip
+// the PCG's q = A p with p in fp32 storage (PcgBuffersT::p32): fp64 product, shared rows left in the slab, partials of <p, A p>; throws where the patch operator does not apply
+void launch_patch_spmm_x32(const CsrViewT<double> &A, int k, const float *x, double *part, const double *scal, int nblocks, hipStream_t s, int step);   // patch.hip
 template <class T> bool pcg_update_folds(const PcgBuffersT<T> &b);   // the update launch takes the first Chebyshev step along (and gathers q)
 void set_slab_masked(int v);         // key 29: k_pcg_update<.., MASKED = true> (1) / <.., false> (0)
 void set_flat_direction(int v);      // key 30: k_pcg_direction_flat (1) / k_pcg_direction_row (0)

@@ -196,10 +196,15 @@ template <class T> __device__ __forceinline__ void lds_add(T *p, T v) {
 // image is whole, THEN the image becomes the accumulators, y of A goes out, B is computed and goes out.  The lanes hold up to
 // kPatchPasses2 staging passes (a patch of 2 * 51 elements has ~770 rows, 15 passes of 51; the largest ~1000).
 constexpr int kPatchPasses2 = 20;
-template <class T, int K, int MODE = 0, bool LEAN = false, int ROUNDS = 1>
-__global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_patch_apply(PatchTables tb, int rows, const T *__restrict__ x, T *__restrict__ y, T *__restrict__ Yb,
+// TX = storage type of x, T = type of everything else.  TX = float with T = double (the PCG's fp32 search direction,
+// PcgBuffersT::p32): phase 1 stages 4-byte values, the staged image in LDS is fp32 and a lane widens its twenty values as it reads
+// them; the registers, <x, A x>, the accumulators and the slab are fp64 as with TX = T.
+template <class T, int K, int MODE = 0, bool LEAN = false, int ROUNDS = 1, class TX = T>
+__global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_patch_apply(PatchTables tb, int rows, const TX *__restrict__ x, T *__restrict__ y, T *__restrict__ Yb,
                                                      double *__restrict__ ppart, const double *__restrict__ scal, int step, long long *__restrict__ stamps,
                                                      double *__restrict__ pbins) {
+    static_assert(std::is_same<TX, T>::value || (std::is_same<TX, float>::value && std::is_same<T, double>::value && MODE == 0 && !LEAN),
+                  "an x narrower than the rest: fp32 into the fp64 product, plain order");
     (void)y;     // (every row leaves through the slab; the argument keeps its place in the launch)
     // the "solve is over" word is asked for HERE but looked at when the row numbers are there (it travels with them, as a vector
     // load, so that no scalar load of the prologue queues behind a word another XCD wrote: one round trip instead of two)
@@ -213,9 +218,9 @@ __global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_p
     constexpr int U = ROUNDS == 2 ? kPatchPasses2 : kPatchPasses;   // loads in flight per lane: one trip over up to U * (256 / K) rows
     constexpr int BLK = kPatchBlock;
     constexpr int EK = BLK / K;                          // rows per pass of the staging / output phases
-    constexpr uint32_t S = sizeof(T);
+    constexpr uint32_t S = sizeof(T), SX = sizeof(TX);
     extern __shared__ double lds_raw[];
-    T *xs = reinterpret_cast<T *>(lds_raw);              // [(rows + 2)][K]: x rows (T), later the accumulators of y (double); row `rows` = zeros, row rows + 1 = slack
+    TX *xs = reinterpret_cast<TX *>(lds_raw);            // [(rows + 2)][K]: x rows (TX), later the accumulators of y (double); row `rows` = zeros, row rows + 1 = slack
     __shared__ double smem[16 * K];
     const int tid = threadIdx.x;
     // workgroups b, b + 8, ... share an XCD and its L2: every XCD takes one contiguous eighth of the patches (neighbouring patches
@@ -294,7 +299,7 @@ __global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_p
     // round trip is ~2-5 k clocks here, the arithmetic of a whole patch ~4 k).  Buffer loads with the hardware range check: a lane
     // without a row hands over an offset beyond the descriptor (no request, no branch); its LDS store goes to the slack row.
     // 24-bit multiplies: rows and slots are below 2^24 (checked by the caller).  Row `rows` is the zero row constrained dofs read.
-    const rsrc_t rx = make_rsrc(x, uint64_t(tb.n) * K * S);
+    const rsrc_t rx = make_rsrc(x, uint64_t(tb.n) * K * SX);
     const uint32_t slack = uint32_t((rows + 1) * K + c0);
 #define REMO_PASSES_UP_TO_12(fn)                                                                                          \
         case 1: fn(std::integral_constant<int, 1>{}, 0); break;   case 2: fn(std::integral_constant<int, 2>{}, 0); break;   \
@@ -327,7 +332,7 @@ __global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_p
     auto stage = [&](auto np_c, int m0) {
         constexpr int NP = decltype(np_c)::value;
         int32_t r[NP];
-        T v[NP][1];
+        TX v[NP][1];
         if (m0 == 0) {
 #pragma unroll
             for (int u = 0; u < NP; ++u) r[u] = r0[u];
@@ -343,12 +348,12 @@ __global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_p
         for (int u = 0; u < NP; ++u) r[u] = (off_mask == 0 && m0 + el + EK * u < rows_own) ? r[u] : -1;
 #pragma unroll
         for (int u = 0; u < NP; ++u)
-            buf_load<T, 1>(rx, r[u] >= 0 ? __umul24(uint32_t(r[u]), K * S) + uint32_t(c0) * S : kOutOfRange, v[u]);
+            buf_load<TX, 1>(rx, r[u] >= 0 ? __umul24(uint32_t(r[u]), K * SX) + uint32_t(c0) * SX : kOutOfRange, v[u]);
 #pragma unroll
         for (int u = 0; u < NP; ++u) xs[r[u] >= 0 ? uint32_t((m0 + el + EK * u) * K + c0) : slack] = v[u][0];
     };
     REMO_PASSES(stage)
-    if (tid < 2 * K) xs[rows * K + tid] = T(0);
+    if (tid < 2 * K) xs[rows * K + tid] = TX(0);
     __syncthreads();
     REMO_STAMP(2)
     // 2. my element, my column
@@ -442,7 +447,7 @@ __global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_p
         if (active) {
             T xA[20];
 #pragma unroll
-            for (int i = 0; i < 20; ++i) xA[i] = xs[REMO_PATCH_L(i) * K + c0];
+            for (int i = 0; i < 20; ++i) xA[i] = T(xs[REMO_PATCH_L(i) * K + c0]);
             dA = element(xA, cm, yA);
             // (pin the result HERE: it is used behind the barriers, and the compiler would sink the arithmetic there)
 #pragma unroll
@@ -450,7 +455,7 @@ __global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_p
         }
         if (activeB) {
 #pragma unroll
-            for (int i = 0; i < 20; ++i) xB[i] = xs[((liB[i >> 1] >> (16 * (i & 1))) & 0xFFFFu) * K + c0];
+            for (int i = 0; i < 20; ++i) xB[i] = T(xs[((liB[i >> 1] >> (16 * (i & 1))) & 0xFFFFu) * K + c0]);
         }
         __syncthreads();        // every lane holds what it wants of the image: the staging area becomes the accumulators
         REMO_STAMP(3)
@@ -469,7 +474,7 @@ __global__ void __launch_bounds__(kPatchBlock, (LEAN ? REMO_LEAN_WAVES : 1)) k_p
     T xv[20];
     if (active) {
 #pragma unroll
-        for (int i = 0; i < 20; ++i) xv[i] = xs[REMO_PATCH_L(i) * K + c0];
+        for (int i = 0; i < 20; ++i) xv[i] = T(xs[REMO_PATCH_L(i) * K + c0]);
     }
     __syncthreads();        // every lane holds its x values: the staging area becomes the accumulators
     REMO_STAMP(3)
@@ -785,6 +790,36 @@ template <class T> void launch_patch_spmm(const CsrViewT<T> &A, int k, const T *
         default: patch_dispatch<T, 8>(A, x, y, part, scal, step, nb, s, defer); break;
     }
 }
+// The PCG's product with the search direction in fp32 storage (PcgBuffersT::p32): the shared rows stay in the slab (defer_q), the
+// patches' <p, A p> go where launch_patch_spmm puts them.  The tables' own kernel or none: a batch the patch operator does not take
+// never gets an fp32 direction (batch_run.hip set_launch_shape).
+template <int K> static void patch_dispatch_x32(const CsrViewT<double> &A, const float *x, double *part, const double *scal, int step, int nb, hipStream_t s) {
+    const PatchOpT<double> &P = *A.patch;
+    const PatchTables &tb = P.t;
+    const int64_t per = (tb.npatch + 7) / 8;
+    double *bins = P.dot_bins ? part + (step & 1) * (kPqBins * 8) : nullptr;
+    const size_t bytes = patch_lds_bytes(P.lds_rows, K);
+    if (tb.rounds == 2)
+        hipLaunchKernelGGL((k_patch_apply<double, K, 0, false, 2, float>), dim3(int(per * 8)), dim3(kPatchBlock), bytes, s, tb, P.lds_rows, x, (double *)nullptr, P.Yb, P.ppart, scal, step, (long long *)nullptr, bins);
+    else
+        hipLaunchKernelGGL((k_patch_apply<double, K, 0, false, 1, float>), dim3(int(per * 8)), dim3(kPatchBlock), bytes, s, tb, P.lds_rows, x, (double *)nullptr, P.Yb, P.ppart, scal, step, (long long *)nullptr, bins);
+    if (!bins) hipLaunchKernelGGL(k_patch_dot<K>, dim3(nb < kPatchDotBlocks ? nb : kPatchDotBlocks), dim3(256), 0, s, tb.npatch, (const double *)P.ppart, part, scal, step);
+}
+
+void launch_patch_spmm_x32(const CsrViewT<double> &A, int k, const float *x, double *part, const double *scal, int nb, hipStream_t s, int step) {
+    if (!patch_applies(A, k) || !part) throw std::logic_error("patch operator on an fp32 direction: no patch tables for this batch");
+    switch (k) {
+        case 1: patch_dispatch_x32<1>(A, x, part, scal, step, nb, s); break;
+        case 2: patch_dispatch_x32<2>(A, x, part, scal, step, nb, s); break;
+        case 3: patch_dispatch_x32<3>(A, x, part, scal, step, nb, s); break;
+        case 4: patch_dispatch_x32<4>(A, x, part, scal, step, nb, s); break;
+        case 5: patch_dispatch_x32<5>(A, x, part, scal, step, nb, s); break;
+        case 6: patch_dispatch_x32<6>(A, x, part, scal, step, nb, s); break;
+        case 7: patch_dispatch_x32<7>(A, x, part, scal, step, nb, s); break;
+        default: patch_dispatch_x32<8>(A, x, part, scal, step, nb, s); break;
+    }
+}
+
 template void launch_patch_spmm<double>(const CsrViewT<double> &, int, const double *, double *, double *, const double *, int, hipStream_t, int, bool);
 template void launch_patch_spmm<float>(const CsrViewT<float> &, int, const float *, float *, double *, const double *, int, hipStream_t, int, bool);
 

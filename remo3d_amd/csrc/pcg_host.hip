@@ -46,18 +46,28 @@ ChunkResult run_pcg_t(remo_ctx *ctx, const CsrViewT<T> &A, int k, const T *d_f, 
     volatile int32_t *done_step = &ctx->progress[ctx->progress_len - 1].step;
     int step = 0;
     bool done = false;
+    // q = A p (+ partials of <p, A p>) of the step; a search direction in fp32 storage (PcgBuffersT::p32) has the patch operator's own kernel
+    auto apply = [&]() {
+        if constexpr (std::is_same<T, double>::value) {
+            if (buf.p32) {
+                launch_patch_spmm_x32(A, k, (const float *)buf.p32, buf.part_pq, (const double *)buf.rz0, buf.nb_spmv, s, step);
+                return;
+            }
+        }
+        launch_spmm(A, k, (const T *)buf.p, buf.q, buf.part_pq, (const double *)buf.rz0, buf.nb_spmv, s, step, buf.defer_q);
+    };
     for (; step < maxit && !done;) {
         // time_kernels = k: every k-th SpMM launch is bracketed with events (a bracket costs the stream ~1.5 us)
         if (time_kernels > 0 && (step % time_kernels) == (time_kernels / 2) && ev_used + 2 <= ctx->spmv_ev.size()) {
             HIP_TRY(hipEventRecord(ctx->spmv_ev[ev_used], s));
-            launch_spmm(A, k, (const T *)buf.p, buf.q, buf.part_pq, (const double *)buf.rz0, buf.nb_spmv, s, step, buf.defer_q);
+            apply();
             HIP_TRY(hipEventRecord(ctx->spmv_ev[ev_used + 1], s));
             ev_used += 2;
         } else {
-            launch_spmm(A, k, (const T *)buf.p, buf.q, buf.part_pq, (const double *)buf.rz0, buf.nb_spmv, s, step, buf.defer_q);
+            apply();
         }
 #ifdef REMO_PROBES
-        for (int extra = 0; extra < g_tune.extra_apply; ++extra)      // (idempotent: the same q and slab again, no dot products)
+        for (int extra = 0; extra < g_tune.extra_apply && buf.p; ++extra)      // (idempotent: the same q and slab again, no dot products)
             launch_spmm(A, k, (const T *)buf.p, buf.q, (double *)nullptr, (const double *)buf.rz0, buf.nb_spmv, s, step, false);
 #endif
         bool replaced = false;

@@ -8,6 +8,9 @@
 
 #include <math.h>
 
+#include <stdexcept>
+#include <type_traits>
+
 #include "wave_util.h"
 #include "kutil.h"
 
@@ -95,9 +98,11 @@ template <class T> struct UpdHeadT {
 // fp64 solve; the outer target of the refinement in the mixed mode)
 constexpr int kFloorSlot = 5 * 8;
 
-template <class T, int K>
+// TP, here and in the launches below: the storage type of the search direction p - T, or float inside an fp64 solve
+// (PcgBuffersT::p32).  Every reader widens the stored value; nothing keeps an unrounded copy.
+template <class T, int K, class TP = T>
 __global__ void __launch_bounds__(256) k_pcg_init(int64_t n, ChebArgsT<T> ch, const T *__restrict__ f, const T *__restrict__ dinv,
-                                                  T *__restrict__ x, T *__restrict__ r, T *__restrict__ p,
+                                                  T *__restrict__ x, T *__restrict__ r, TP *__restrict__ p,
                                                   double *__restrict__ part_rz) {
     __shared__ double smem[16 * K];
     double rz[K];
@@ -112,7 +117,7 @@ __global__ void __launch_bounds__(256) k_pcg_init(int64_t n, ChebArgsT<T> ch, co
             const T zi = d * ri;
             if (x) x[i * K + c] = T(0);   // (evaluated values only: x_ev is cleared by the host)
             r[i * K + c] = ri;
-            p[i * K + c] = coarse ? T(0) : zi;
+            p[i * K + c] = TP(coarse ? T(0) : zi);
             rz[c] += coarse ? 0.0 : double(ri) * double(zi);   // the vertex block's share comes from the Chebyshev kernels
         }
     }
@@ -131,8 +136,8 @@ __global__ void __launch_bounds__(256) k_pcg_init(int64_t n, ChebArgsT<T> ch, co
 // What every form does first.  Returns false when an earlier step froze every column (the launch is a no-op); else alpha[] of the step.
 // scal = rz0[8] | pq[8] | rz of even steps[8] | rz of odd steps[8]: totals forwarded between launches
 // by workgroup 0, so every launch re-reduces only the ONE partial array that is new to it
-template <class T, int K>
-__device__ __forceinline__ bool pcg_update_head(const UpdHeadT<T> &hd, const T *__restrict__ p, double (&alpha)[K], double *smem /* [16*3*K] */) {
+template <class T, int K, class TP = T>
+__device__ __forceinline__ bool pcg_update_head(const UpdHeadT<T> &hd, const TP *__restrict__ p, double (&alpha)[K], double *smem /* [16*3*K] */) {
     double *scal = hd.rz0;
     const int step = hd.step;
     if (solve_done(scal, step)) return false;
@@ -178,7 +183,7 @@ __device__ __forceinline__ bool pcg_update_head(const UpdHeadT<T> &hd, const T *
         double a = 0.0;
 #pragma unroll
         for (int c = 0; c < K; ++c) a = (c == col) ? alpha[c] : a;
-        const T xv = hd.ev.x[j], pv = p[at];
+        const T xv = hd.ev.x[j], pv = T(p[at]);
         hd.ev.x[j] = xv + T(a) * pv;
     }
     return true;
@@ -290,6 +295,17 @@ __global__ void __launch_bounds__(256) k_pcg_update(int64_t n, UpdHeadT<T> hd, i
     pcg_update_rows<T, K, MASKED, AHEAD>(0, n, int(gridDim.x), nv, alpha, p, q, x, r, dinv, qv, part_rz_next, smem);
 }
 
+// the row form beside an fp32 search direction (evaluated values only: x and p belong to the direction launch, qv.skip_x; p is read by the x_ev slots alone)
+template <int K, bool MASKED>
+__global__ void __launch_bounds__(256) k_pcg_update_p32(int64_t n, UpdHeadT<double> hd, int64_t nv, double *__restrict__ part_rz_next,
+                                                        const float *__restrict__ p, const double *__restrict__ q, double *__restrict__ r,
+                                                        const double *__restrict__ dinv, QViewT<double> qv) {
+    __shared__ double smem[16 * 3 * K];
+    double alpha[K];
+    if (!pcg_update_head<double, K, float>(hd, p, alpha, smem)) return;
+    pcg_update_rows<double, K, MASKED, true>(0, n, int(gridDim.x), nv, alpha, (const double *)nullptr, q, (double *)nullptr, r, dinv, qv, part_rz_next, smem);
+}
+
 // x += alpha p alone: the residual replacement step of the mixed mode (r and the <Cr,r> partials come from k_mixed_replace)
 template <class T, int K>
 __global__ void __launch_bounds__(256) k_pcg_update_x(int64_t n, UpdHeadT<T> hd, const T *__restrict__ p, T *__restrict__ x) {
@@ -380,13 +396,13 @@ __global__ void __launch_bounds__(256) k_pcg_update_folded(int64_t n, UpdHeadT<T
 // holds them (ds_bpermute), and ITS column of each slab slot - the K lanes of a row read a slot's 40 bytes side by side.
 // All 6 K loads of a lane are in flight together.  Same sums, same order as the row form (rows of five or more patches, the
 // first vertex rows: their further slots are summed by the row's lane and handed over through LDS - another association).
-template <class T, int K>
+template <class T, int K, class TP = T>
 __global__ void __launch_bounds__(256) k_pcg_update_tile(int64_t n, UpdHeadT<T> hd, int64_t nv, double *__restrict__ part_rz_next,
-                                                         const T *__restrict__ p, T *__restrict__ r, const T *__restrict__ dinv, QViewT<T> qv) {
+                                                         const TP *__restrict__ p, T *__restrict__ r, const T *__restrict__ dinv, QViewT<T> qv) {
     __shared__ double smem[16 * 3 * K];
     __shared__ double ex_lds[4 * 64 * K];
     double alpha[K], acc[K];
-    if (!pcg_update_head<T, K>(hd, p, alpha, smem)) return;
+    if (!pcg_update_head<T, K, TP>(hd, p, alpha, smem)) return;
     constexpr uint32_t S = sizeof(T);
     __syncthreads();          // (the reductions' last reads of smem)
     if (threadIdx.x == 0) {
@@ -631,16 +647,21 @@ __device__ __forceinline__ bool pcg_direction_head(int step, double tol2, int nb
 // out of a 2.5 KB span, three instructions per line).  The column of a value is its index mod K: beta and alpha come from LDS
 // (an index into registers would put them into scratch memory); the Jacobi factor of its row is an 8-byte load (an L1 hit for
 // four of five).  Buffer accesses: the range check drops what lies behind the last value, dword by dword.
-template <class T, int K>
+// TP = float beside T = double: a lane still moves 16 bytes per access - FOUR consecutive values, one 16-byte access of p and two of r
+// (values e0, e0 + 1 and e0 + 2, e0 + 3: the two accesses of a wave cover the same 2 KB of whole lines); as many load sets in flight.
+template <class T, int K, class TP = T>
 __global__ void __launch_bounds__(256) k_pcg_direction_flat(int64_t n, int first, int step, double tol2, int nb_rz, ChebArgsT<T> ch,
                                                             const double *__restrict__ part_rz_new, double *__restrict__ scal,
-                                                            const T *__restrict__ r, T *__restrict__ p,
+                                                            const T *__restrict__ r, TP *__restrict__ p,
                                                             const T *__restrict__ dinv, T *__restrict__ x) {
     __shared__ double smem[16 * K];
     double beta[K], alpha[K];
     if (!pcg_direction_head<K>(step, tol2, nb_rz, part_rz_new, scal, beta, alpha, smem)) return;
-    constexpr int VEC = 16 / int(sizeof(T));
-    constexpr uint32_t S = sizeof(T);
+    constexpr bool SAME = std::is_same<TP, T>::value;
+    constexpr int VEC = 16 / int(sizeof(TP));     // values per lane and load set: 16 bytes of p
+    constexpr int RV = 16 / int(sizeof(T));       // values per 16-byte access of r
+    constexpr int NR = VEC / RV;                  // accesses of r per load set
+    constexpr uint32_t S = sizeof(T), SP = sizeof(TP);
     constexpr int UF = 4;
     __syncthreads();          // (block_sum's last reads of smem)
     if (threadIdx.x == 0) {
@@ -649,22 +670,27 @@ __global__ void __launch_bounds__(256) k_pcg_direction_flat(int64_t n, int first
     }
     __syncthreads();
     const uint32_t N = uint32_t(n) * K, NV = uint32_t(ch.nv) * K;
-    const rsrc_t rr = make_rsrc(r, uint64_t(N) * S), rz = make_rsrc(ch.z, uint64_t(NV) * S), rp = make_rsrc(p, uint64_t(N) * S),
-                 rd = make_rsrc(dinv, uint64_t(n) * S), rx = make_rsrc(x ? x : p, uint64_t(N) * S);
-    const bool with_x = x != nullptr && !first;
+    const rsrc_t rr = make_rsrc(r, uint64_t(N) * S), rz = make_rsrc(ch.z, uint64_t(NV) * S), rp = make_rsrc(p, uint64_t(N) * SP),
+                 rd = make_rsrc(dinv, uint64_t(n) * S), rx = make_rsrc((SAME && x) ? (const void *)x : (const void *)p, uint64_t(N) * S);
+    const bool with_x = SAME && x != nullptr && !first;      // (evaluated values only - the one case with TP != T - has no x)
     const uint32_t span = uint32_t(gridDim.x) * blockDim.x * VEC;
     for (uint32_t g0 = (uint32_t(blockIdx.x) * blockDim.x + threadIdx.x) * VEC; g0 < N; g0 += UF * span) {
-        T zv[UF][VEC], pv[UF][VEC], xv[UF][VEC], dv[UF][VEC];
+        T zv[UF][VEC], xv[UF][VEC], dv[UF][VEC];
+        TP pv[UF][VEC];
 #pragma unroll
         for (int u = 0; u < UF; ++u) {
             const uint32_t e0 = g0 + u * span;
-            const uint32_t off = e0 < N ? e0 * S : kOutOfRange;
-            buf_load<T, VEC>(rr, off, zv[u]);
-            {                   // vertex rows: the vertex-block solver's result (stored pre-divided by the Jacobi factor) instead of r
-                T zz[VEC];      // (no branch: the other lanes hand over an offset out of range and send no request)
-                buf_load<T, VEC>(rz, e0 < NV ? e0 * S : kOutOfRange, zz);
+            const uint32_t off = e0 < N ? e0 * SP : kOutOfRange;
 #pragma unroll
-                for (int v = 0; v < VEC; ++v) zv[u][v] = (e0 + v < NV) ? zz[v] : zv[u][v];
+            for (int j = 0; j < NR; ++j) {
+                const uint32_t ej = e0 + uint32_t(RV * j);
+                T rj[RV];
+                buf_load<T, RV>(rr, ej < N ? ej * S : kOutOfRange, rj);
+                // vertex rows: the vertex-block solver's result (stored pre-divided by the Jacobi factor) instead of r
+                T zz[RV];       // (no branch: the other lanes hand over an offset out of range and send no request)
+                buf_load<T, RV>(rz, ej < NV ? ej * S : kOutOfRange, zz);
+#pragma unroll
+                for (int v = 0; v < RV; ++v) zv[u][RV * j + v] = (ej + v < NV) ? zz[v] : rj[v];
             }
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
@@ -672,10 +698,10 @@ __global__ void __launch_bounds__(256) k_pcg_direction_flat(int64_t n, int first
                 buf_load<T, 1>(rd, e0 < N ? ((e0 + v) / uint32_t(K)) * S : kOutOfRange, one);
                 dv[u][v] = one[0];
             }
-            if (!first) buf_load<T, VEC>(rp, off, pv[u]);
+            if (!first) buf_load<TP, VEC>(rp, off, pv[u]);
             else {
 #pragma unroll
-                for (int v = 0; v < VEC; ++v) pv[u][v] = T(0);
+                for (int v = 0; v < VEC; ++v) pv[u][v] = TP(0);
             }
             if (with_x) buf_load<T, VEC>(rx, off, xv[u]);
             else {
@@ -686,31 +712,31 @@ __global__ void __launch_bounds__(256) k_pcg_direction_flat(int64_t n, int first
 #pragma unroll
         for (int u = 0; u < UF; ++u) {
             const uint32_t e0 = g0 + u * span;
-            const uint32_t off = e0 < N ? e0 * S : kOutOfRange;
-            T pn[VEC], xn[VEC];
+            const uint32_t off = e0 < N ? e0 * SP : kOutOfRange;
+            TP pn[VEC];
+            T xn[VEC];
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
                 const uint32_t c = (e0 + v) % uint32_t(K);
-                const T zi = dv[u][v] * zv[u][v];
-                pn[v] = first ? zi : zi + T(smem[c]) * pv[u][v];      // (the launchers pass first = 0; kept: it fixes which product the compiler fuses)
-                xn[v] = xv[u][v] + T(smem[K + c]) * pv[u][v];
+                const T zi = dv[u][v] * zv[u][v], po = T(pv[u][v]);
+                pn[v] = TP(first ? zi : zi + T(smem[c]) * po);      // (the launchers pass first = 0; kept: it fixes which product the compiler fuses)
+                xn[v] = xv[u][v] + T(smem[K + c]) * po;
             }
-            buf_store<T, VEC>(rp, off, pn);
+            buf_store<TP, VEC>(rp, off, pn);
             if (with_x) buf_store<T, VEC>(rx, off, xn);
         }
     }
 }
-
 // ROW form.  first: p0 = C r0 (no scalars, no old direction).
 // U rows per thread are loaded before any of them is stored: p is read and written through the same pointer, and a store
 // of one row otherwise holds back the loads of the next (one row in flight per thread: 2.7 TB/s at 5.4 M rows in fp32)
 #ifndef REMO_DIR_U
 #define REMO_DIR_U 4
 #endif
-template <class T, int K>
+template <class T, int K, class TP = T>
 __global__ void __launch_bounds__(256) k_pcg_direction_row(int64_t n, int first, int step, double tol2, int nb_rz, ChebArgsT<T> ch,
                                                            const double *__restrict__ part_rz_new, double *__restrict__ scal,
-                                                           const T *__restrict__ r, T *__restrict__ p,
+                                                           const T *__restrict__ r, TP *__restrict__ p,
                                                            const T *__restrict__ dinv, T *__restrict__ x) {
     __shared__ double smem[16 * K];
     double beta[K], alpha[K];
@@ -738,7 +764,7 @@ __global__ void __launch_bounds__(256) k_pcg_direction_row(int64_t n, int first,
                 for (int c = 0; c < K; ++c) zv[u][c] = src[i * K + c];
                 if (!first)
 #pragma unroll
-                    for (int c = 0; c < K; ++c) pv[u][c] = p[i * K + c];
+                    for (int c = 0; c < K; ++c) pv[u][c] = T(p[i * K + c]);
                 if (x && !first)
 #pragma unroll
                     for (int c = 0; c < K; ++c) xv[u][c] = x[i * K + c];
@@ -751,7 +777,7 @@ __global__ void __launch_bounds__(256) k_pcg_direction_row(int64_t n, int first,
 #pragma unroll
                 for (int c = 0; c < K; ++c) {
                     const T zi = d[u] * zv[u][c];
-                    p[i * K + c] = first ? zi : zi + T(beta[c]) * pv[u][c];
+                    p[i * K + c] = TP(first ? zi : zi + T(beta[c]) * pv[u][c]);
                     // x += alpha p of THIS step, with the old direction that is in registers anyway (PcgBuffersT::x_in_direction):
                     // the update launch then neither reads p nor touches x - one pass over p less per step
                     if (x && !first) x[i * K + c] = xv[u][c] + T(alpha[c]) * pv[u][c];
@@ -759,7 +785,6 @@ __global__ void __launch_bounds__(256) k_pcg_direction_row(int64_t n, int first,
         }
     }
 }
-
 template <int K>
 __global__ void __launch_bounds__(256) k_pcg_final(int step, int nb_rz, const double *__restrict__ part_rz, const double *__restrict__ scal,
                                                    PcgProgress *progress, int progress_len) {
@@ -1002,6 +1027,15 @@ template <class T> void launch_pcg_init(const CsrViewT<T> &A, int k, const T *f,
     const int64_t n = A.n;
     const int g = b.nb_vec;
     const ChebArgsT<T> ch = cheb_args(b);
+    if constexpr (sizeof(T) == 8) {
+        if (b.p32) {      // the search direction in fp32 storage: the same launches, TP = float
+            REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_init<double, KK, float>), dim3(g), dim3(256), 0, s, n, ch, f, b.dinv, b.x, b.r, b.p32, b.part_rz));
+            launch_cheb(A, k, 0, b, b.part_rz, s);
+            if (ch.nv > 0)
+                REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction_row<double, KK, float>), dim3(g), dim3(256), 0, s, n, 1, 0, 0.0, nb_rz(b), ch, b.part_rz, b.rz0, b.r, b.p32, b.dinv, (double *)nullptr));
+            return;
+        }
+    }
     REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_init<T, KK>), dim3(g), dim3(256), 0, s, n, ch, f, b.dinv, b.x, b.r, b.p, b.part_rz));
     launch_cheb(A, k, 0, b, b.part_rz, s);
     if (ch.nv > 0)
@@ -1050,6 +1084,16 @@ template <class T> void launch_pcg_update(const CsrViewT<T> &A, int k, int step,
     if (slab) { qv.bptr = A.patch->t.bptr; qv.bslot = A.patch->t.bslot; qv.Yb = A.patch->Yb; }
     if (masked) { qv.slab_bytes = slab_bytes; qv.row4 = A.patch->t.row4; }
     // 3. the launch
+    if constexpr (sizeof(T) == 8) {
+        if (b.p32) {      // fp32 search direction: read by the x_ev slots alone (the host grants it with defer_q, x in the direction launch and no x: set_launch_shape)
+            if (!slab || !skip_x || b.x || one_by_one) throw std::logic_error("update launch: an fp32 search direction outside the evaluated-values path of the patch operator");
+            if (tile) { REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_update_tile<double, KK, float>), dim3(g), dim3(256), 0, s, n, hd, ch.nv, nxt, b.p32, b.r, b.dinv, qv)); }
+            else if (masked) { REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_update_p32<KK, true>), dim3(g), dim3(256), 0, s, n, hd, ch.nv, nxt, b.p32, b.q, b.r, b.dinv, qv)); }
+            else { REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_update_p32<KK, false>), dim3(g), dim3(256), 0, s, n, hd, ch.nv, nxt, b.p32, b.q, b.r, b.dinv, qv)); }
+            launch_cheb(A, k, step, b, nxt, s, false);
+            return;
+        }
+    }
     if (folded) {
         FoldArgsT<T> fold;
         const double theta = 0.5 * (b.cheb_lmax + b.cheb_lmin), delta = 0.5 * (b.cheb_lmax - b.cheb_lmin);
@@ -1122,6 +1166,13 @@ template <class T> void launch_pcg_direction(const CsrViewT<T> &A, int k, int st
     const ChebArgsT<T> ch = cheb_args(b);
     T *xp = (add_x && b.x_in_direction) ? b.x : nullptr;
     const bool flat = g_flat_direction && uint64_t(n) * uint64_t(k) * sizeof(T) < 0xFFFFF000ull;
+    if constexpr (sizeof(T) == 8) {
+        if (b.p32) {      // fp32 search direction (no x: evaluated values only)
+            if (flat) { REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction_flat<double, KK, float>), dim3(g), dim3(256), 0, s, n, 0, step, tol2, nb_rz(b), ch, nw, b.rz0, b.r, b.p32, b.dinv, (double *)nullptr)); }
+            else { REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction_row<double, KK, float>), dim3(g), dim3(256), 0, s, n, 0, step, tol2, nb_rz(b), ch, nw, b.rz0, b.r, b.p32, b.dinv, (double *)nullptr)); }
+            return;
+        }
+    }
     if (flat) {
         REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction_flat<T, KK>), dim3(g), dim3(256), 0, s, n, 0, step, tol2, nb_rz(b), ch, nw, b.rz0, b.r, b.p, b.dinv, xp));
     } else {

@@ -383,6 +383,7 @@ int remo_debug_tune(int32_t key, int32_t value) {
         case 29: set_slab_masked(value); return 0;      // slab slots a row does not have: not fetched / fetched and weighted by zero
         case 25: g_tune.x_in_direction = value; return 0;    // x += alpha p in the direction / in the update launch
         case 39: g_tune.x_ev = value; return 0;              // one-shot solves: only the values of x the evaluation points read / the whole x
+        case 41: g_tune.p32 = value; return 0;               // ... on the patch operator: the search direction stored in fp32 / in fp64
         case 22: g_tune.defer_q = value; return 0;           // shared rows summed by k_patch_reduce / by the update launch
         case 24: g_tune.ell = value; return 0;               // fixed-width image of the vertex block
         case 40: set_patch_rounds(value); return 0;          // patch operator: two elements per lane where the patch fits its tables / one
@@ -431,6 +432,7 @@ int remo_debug_field_timing(remo_ctx_t *ctx, double *out2) {
 }
 
 int remo_debug_point_location(remo_ctx_t *ctx) { return ctx ? ctx->point_location : REMO_ERR_ARG; }
+int remo_debug_direction_bytes(remo_ctx_t *ctx) { return ctx ? ctx->direction_bytes : REMO_ERR_ARG; }
 int remo_debug_secondary_timing(remo_ctx_t *ctx, double *ms) {
     if (!ctx || !ms) return REMO_ERR_ARG;
     *ms = ctx->sec_ms;

@@ -54,6 +54,7 @@ struct Tune {
     int x_in_direction = 1;  // key 25: 1 = x += alpha p formed by the direction launch of the step (default), 0 = by the update launch
     int dot_bins = 1;        // key 28 (probe builds): 1 = the patches add their <p, A p> straight into the update launch's rows (default), 0 = a row per patch + k_patch_dot
     int x_ev = 1;            // key 39: 1 = one-shot fp64 solves carry only the values of x the evaluation points read (default), 0 = the whole x
+    int p32 = 1;             // key 41: 1 = those solves, on the patch operator, store the search direction in fp32 (default; PcgBuffersT::p32), 0 = in fp64
 #ifdef REMO_PROBES
     int extra_apply = 0;     // key 36 (probe builds): extra operator applications (apply + shared-row sums, results discarded) per PCG step: what a step with more applications would cost
 #endif
@@ -95,6 +96,7 @@ struct remo_ctx {
     hipEvent_t fev[4] = {};                  // their events, created by the first use
     double sec_ms = 0.0;                     // last remo_batch_run with remo_job_secondary_t.secondary: HIP-event time of the load-vector launches, all chunks (remo_debug_secondary_timing)
     int point_location = 0;                  // last remo_batch_run: 0 = axis kernels, 1 = cell grid (remo_debug_point_location)
+    int direction_bytes = 0;                 // last remo_batch_run: bytes per stored value of the PCG's search direction, 4 or 8 (remo_debug_direction_bytes)
     remo::PcgProgress *progress = nullptr;  // mapped, coherent host memory
     remo::PcgProgress *progress_dev = nullptr;
     int progress_len = 0;

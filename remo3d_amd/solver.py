@@ -380,6 +380,11 @@ class Context:
         kernels of the axis entries, 1 = the cell grid of the field sections (a batch with a point off the axis)."""
         return int(self._L.remo_debug_point_location(self._h))
 
+    def direction_bytes(self) -> int:
+        """Bytes per stored value of the PCG's search direction in the last batch that ran on this context (remo_debug_direction_bytes):
+        4 = fp32 (one-shot fp64 solves on the patch operator, remo_debug_tune key 41; the mixed mode), 8 = fp64."""
+        return int(self._L.remo_debug_direction_bytes(self._h))
+
     def sens_group_timing(self):
         """ms of the group path of the last solve_batch_sens_groups on this context (remo_debug_sens_group_timing): (group order,
         material pass, per-element pass, group sums); the last three are measured only with make_opts(time_kernels=True)."""
