@@ -384,6 +384,39 @@ typedef struct {
     const double *sec_sigma0;   /* [n_rhs] background conductivity per right-hand side; NULL or 0.0 = the (scalar) conductivity
                                    of the element that holds the right-hand side's first source */
 } remo_job_secondary_t;
+/*
+ * err = 1: goal-oriented ERROR ESTIMATES of the functionals (added within ABI 7: five members behind remo_job_secondary_t, which
+ * keeps its 256 bytes as remo_job_t keeps its 232; set job.size = sizeof(remo_job_error_t) and hand &x.sec.job to remo_solve_job).
+ * The error a caller sees in a reading is the discretisation error of the mesh; J(u) - J(u_h) = a(u - u_h, lambda - lambda_h) is
+ * bounded element by element by an indicator of u times one of the adjoint solution lambda the sensitivities solve for anyway.
+ * For a solution column v, an element e (vertices sorted) and a facet F of e (a face in 3D, an edge in 2D) with unit normal n out of
+ * e, q_e = n . Sigma_e grad v_h|_e:
+ *     interior facet, shared with e':   [q] = q_e - n . Sigma_e' grad v_h|_e',  s_F = (n.Sigma_e n + n.Sigma_e' n) / 2,  c_F = 1/2;
+ *     boundary facet, not Dirichlet:    [q] = q_e,  s_F = n.Sigma_e n,  c_F = 1   (y = 0 of the half ball, the axis in 2D);
+ *     Dirichlet facet:                  0;
+ *     eta_e(v)^2 = sum_F c_F h_F / (2 p s_F) int_F [q]^2 dS,  p = 3, h_F the longest edge of F, dS with 2 pi r in 2D,
+ * integrated exactly (three Gauss-Legendre points on an edge, the symmetric six-point rule of degree 4 on a face); in 2D with
+ * condense = 1 the cell bubbles of both elements are recovered first.  Functional j, which reads right-hand side fun_rhs[j]:
+ *     E_je = eta_e(u_fun_rhs[j]) * eta_e(lambda_j),   err_out[j] = E_j = sum_e E_je   (in the units of J_j),
+ *     errg_out[j * err_n_group + g] = sum over the elements e with err_group[e] = g of E_je   (an empty group: 0).
+ * The constant is the conventional one and is not claimed to be sharp; the delta sources are not part of the residual - near an
+ * electrode the estimate comes from the facet jumps alone.  The grouping is the estimate's own: group / dJg_out and err_group /
+ * errg_out may differ in one call.  Every element sums its own facets and all sums have a fixed order (no floating-point atomics):
+ * two calls give the same bits.  u_out, J_out, dJ_out and dJg_out are exactly what the same job returns with err = 0 (bit for bit
+ * with op = 2).  Allowed with tensors, groups, a warm object and points off the axis.
+ * Errors, REMO_ERR_ARG before any device work: err = 1 with n_fun = 0, with secondary = 1, with field points or with precision = 1;
+ * an err other than 0 or 1; err_out == NULL; err_n_group < 0; err_n_group > 0 without err_group or errg_out; a group id outside
+ * [-1, err_n_group).  On any negative return err_out and errg_out are NaN-filled like the other outputs.  remo_batch_create_job
+ * refuses err = 1: a resident batch has no functionals.
+ */
+typedef struct {
+    remo_job_secondary_t sec;
+    int32_t err;                /* 0: as before, bit for bit.  1: error estimates of the functionals */
+    int32_t err_n_group;        /* 0: no groups */
+    const int32_t *err_group;   /* [mesh->n_elems], caller's element order, -1 = in no group */
+    double *err_out;            /* [n_fun]               E_j  */
+    double *errg_out;           /* [n_fun * err_n_group] Eg_j,g; may be NULL when err_n_group = 0 */
+} remo_job_error_t;             /* 288 bytes */
 int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, const remo_opts_t *opts, remo_stats_t *stats);
 
 /*
@@ -475,6 +508,13 @@ int remo_host_point_shapes(int32_t dim, const double *vertex_coords, const doubl
 int remo_host_secondary_element(int32_t dim, const double *vertex_coords, const double *sigma_tensor, double sigma,
                                 double sigma0, double radius, const double *src /*[dim]*/, int32_t n_quad,
                                 double *f_out /*[nld]*/);
+/* The facet term of the error indicator of remo_job_error_t on the host (the code the kernel runs): *out = c_F h_F / (2 p s_F)
+ * int_F [q]^2 dS of facet `facet` of element e - 3D: 0 .. 3, the faces 012 013 023 123 of its sorted vertices; 2D: 0 .. 2, the edges
+ * 01 02 12 - from e's sorted vertex coordinates, element vector x_e [nld] and conductivity (sigma_tensor_e != NULL: the upper
+ * triangle, else sigma_e).  vertex_coords_n != NULL: an interior facet, with the same three of the neighbour; NULL: a natural
+ * boundary facet.  REMO_ERR_ARG for a tensor that is not finite and positive definite, REMO_ERR_MESH for a degenerate element. */
+int remo_host_error_facet(int32_t dim, int32_t facet, const double *vertex_coords_e, const double *sigma_tensor_e, double sigma_e, const double *x_e,
+                          const double *vertex_coords_n, const double *sigma_tensor_n, double sigma_n, const double *x_n, double *out);
 /* max |sum_m B_a[m][i] B_b[m][j] - M_ab[i][j]|: how well the factorised reference tensors of the patch operator
  * (remo_opts_t.op = 3) reproduce the tensors the CSR assembly contracts (both exact polynomial integrals). */
 double remo_host_factor_error(void);

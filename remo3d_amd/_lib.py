@@ -68,6 +68,12 @@ class RemoJobSecondary(C.Structure):
                                    ("sec_sigma0", C.POINTER(C.c_double))]
 
 
+class RemoJobError(C.Structure):
+    """remo_job_error_t: a remo_job_secondary_t with the five members of the error estimates behind it (flat, like RemoJobSecondary)."""
+    _fields_ = RemoJobSecondary._fields_ + [("err", C.c_int32), ("err_n_group", C.c_int32), ("err_group", C.POINTER(C.c_int32)),
+                                            ("err_out", C.POINTER(C.c_double)), ("errg_out", C.POINTER(C.c_double))]
+
+
 # include/remo3d_hip.h: the drop-in boundary + inspection hooks of the parity tests
 EXPORTS = ["remo_abi_version", "remo_opts_default", "remo_ctx_create", "remo_ctx_destroy", "remo_last_error",
            "remo_solve_batch", "remo_solve_batch_tensor", "remo_solve_batch_sens", "remo_solve_batch_sens_tensor", "remo_solve_batch_sens_groups", "remo_solve_batch_sens_groups_tensor",
@@ -75,7 +81,7 @@ EXPORTS = ["remo_abi_version", "remo_opts_default", "remo_ctx_create", "remo_ctx
            "remo_warm_create", "remo_warm_destroy", "remo_warm_clear", "remo_warm_info", "remo_solve_batch_sens_warm", "remo_solve_batch_sens_warm_tensor", "remo_batch_create", "remo_batch_create_tensor", "remo_batch_run", "remo_batch_fetch", "remo_batch_destroy",
            "remo_batch_eval", "remo_batch_get_system", "remo_batch_get_vectors", "remo_batch_apply_coarse", "remo_batch_spmv",
            "remo_host_element_matrix", "remo_host_element_matrix_tensor", "remo_host_sens_element", "remo_host_factor_error", "remo_host_symbolic",
-           "remo_solve_job", "remo_batch_create_job", "remo_host_point_shapes", "remo_host_secondary_element"]
+           "remo_solve_job", "remo_batch_create_job", "remo_host_point_shapes", "remo_host_secondary_element", "remo_host_error_facet"]
 # include/remo3d_hip_debug.h: probes and tuning knobs (tests, tools, bench.py's `box` record) - not part of the boundary
 DEBUG_EXPORTS = ["remo_debug_stream", "remo_debug_clock", "remo_debug_device", "remo_debug_cache_gather", "remo_debug_xcc", "remo_debug_tune", "remo_debug_patch_phases", "remo_debug_patch_phases_p", "remo_debug_grid_barrier", "remo_debug_sens_timing", "remo_debug_sens_group_timing", "remo_debug_field_timing", "remo_debug_point_location", "remo_debug_secondary_timing", "remo_debug_direction_bytes"]
 
@@ -132,7 +138,7 @@ def load():
     L.remo_warm_info.restype = C.c_int
     L.remo_warm_info.argtypes = [vp, i64p, ip, i64p, ip]
     L.remo_solve_job.restype = C.c_int
-    L.remo_solve_job.argtypes = [vp, C.POINTER(RemoMesh), vp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]     # the job: RemoJob or RemoJobSecondary
+    L.remo_solve_job.argtypes = [vp, C.POINTER(RemoMesh), vp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]     # the job: RemoJob, RemoJobSecondary or RemoJobError
     L.remo_batch_create_job.restype = C.c_int
     L.remo_batch_create_job.argtypes = [vp, C.POINTER(RemoMesh), vp, C.POINTER(vp)]
     L.remo_host_point_shapes.restype = C.c_int
@@ -149,6 +155,8 @@ def load():
     L.remo_debug_direction_bytes.argtypes = [vp]
     L.remo_host_secondary_element.restype = C.c_int
     L.remo_host_secondary_element.argtypes = [C.c_int32, dp, dp, C.c_double, C.c_double, C.c_double, dp, C.c_int32, dp]
+    L.remo_host_error_facet.restype = C.c_int
+    L.remo_host_error_facet.argtypes = [C.c_int32, C.c_int32, dp, dp, C.c_double, dp, dp, dp, C.c_double, dp, dp]
     L.remo_debug_secondary_timing.restype = C.c_int
     L.remo_debug_secondary_timing.argtypes = [vp, dp]
     L.remo_debug_sens_group_timing.restype = C.c_int

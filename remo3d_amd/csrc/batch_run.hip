@@ -19,6 +19,7 @@
 #include "field.h"
 #include "warm.h"
 #include "secondary.h"
+#include "errest.h"
 
 using namespace remo;
 
@@ -165,6 +166,16 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
             need += sens_group_sort_bytes(nt, b->sens->n_group) + 256;                                    // rocPRIM's temporary storage
             need += size_t(nt) * ncomp * 8 + size_t(sens_group_chunks(nt)) * 2 * ncomp * 8;               // ev (one functional at a time), cpart
             need += size_t(b->sens->n_fun) * ng * ncomp * 8 + 16 * 256;                                   // d_dJg (+ the alignment of these takes)
+        }
+        if (b->sens->err) {   // error estimates (err_take)
+            need += size_t(nt) * 8 * size_t(b->n_rhs + b->sens->n_fun) + 256;                             // eta2: a slab of nt per forward and adjoint column
+            need += size_t(nt) * 8 + size_t(b->sens->n_fun) * 8 * (size_t(sens_grid(nt)) + 1) + 8 * 256;  // ev; part, d_E; d_rule (+ the alignment of these takes)
+            if (b->sens->err_group) {   // the second group ordering
+                const size_t ng = size_t(b->sens->err_n_group);
+                need += size_t(nt) * 4 * 5 + (ng + 2) * 4;                                                // d_group, keys_in, ids, keys, perm; off
+                need += sens_group_sort_bytes(nt, b->sens->err_n_group) + 256;                            // rocPRIM's temporary storage
+                need += size_t(sens_group_chunks(nt)) * 2 * 8 + size_t(b->sens->n_fun) * ng * 8 + 16 * 256;   // cpart, d_Eg
+            }
         }
     }
     if (o.precision == 1) {   // fp32 copies of the matrix values and of every PCG vector (mixed_buffers)
@@ -1003,6 +1014,73 @@ void sens_contract(const Run &r, const System &sys, const DevicePoints &dp, cons
     ctx->sens_bytes = double(rq->n_fun) * (16.0 * double(sys.n) + double(b->nt) * (4.0 * r.N + 4.0 * (r.dim + 1) + 4.0 + (r.dim == 2 ? 8.0 * r.NT : 0.0)));
 }
 
+// ---- error estimates of the functionals (errest.hip) ------------------------------------------------------------------------------
+// eta2: column c of the forward solutions at eta2 + nt * c, adjoint column j at eta2 + nt * (n_rhs + j)
+struct ErrEst {
+    double *d_rule = nullptr, *eta2 = nullptr, *ev = nullptr, *part = nullptr, *d_E = nullptr;
+    int grid = 0;
+    int32_t *d_group = nullptr, *ids = nullptr, *perm = nullptr, *off = nullptr;
+    uint32_t *keys_in = nullptr, *keys = nullptr;
+    void *sort_tmp = nullptr;
+    size_t sort_bytes = 0;
+    double *cpart = nullptr, *d_Eg = nullptr;
+};
+
+ErrEst err_take(const Run &r) {
+    const remo_batch *b = r.b;
+    const remo_sens_request *rq = b->sens;
+    const size_t nt = size_t(b->nt);
+    ErrEst e;
+    e.grid = sens_grid(b->nt);
+    e.d_rule = r.ctx->take<double>(ErrRule<3>::NTAB);
+    e.eta2 = r.ctx->take<double>(nt * size_t(b->n_rhs + rq->n_fun));
+    e.ev = r.ctx->take<double>(nt);
+    e.part = r.ctx->take<double>(size_t(rq->n_fun) * e.grid + 1);
+    e.d_E = r.ctx->take<double>(size_t(rq->n_fun) + 1);
+    if (rq->err_group) {
+        const size_t ng = size_t(rq->err_n_group);
+        e.d_group = r.ctx->take<int32_t>(nt); e.keys_in = r.ctx->take<uint32_t>(nt); e.ids = r.ctx->take<int32_t>(nt);
+        e.keys = r.ctx->take<uint32_t>(nt); e.perm = r.ctx->take<int32_t>(nt);
+        e.off = r.ctx->take<int32_t>(ng + 2);
+        e.sort_bytes = sens_group_sort_bytes(b->nt, rq->err_n_group);
+        e.sort_tmp = r.ctx->take<char>(e.sort_bytes + 256);
+        e.cpart = r.ctx->take<double>(size_t(sens_group_chunks(b->nt)) * 2);
+        e.d_Eg = r.ctx->take<double>(size_t(rq->n_fun) * ng + 1);
+    }
+    HIP_TRY(hipMemcpyAsync(e.d_rule, err_rule(r.dim), sizeof(double) * (r.dim == 2 ? ErrRule<2>::NTAB : ErrRule<3>::NTAB), hipMemcpyHostToDevice, r.s));
+    return e;
+}
+
+// eta_e^2 of the k columns of a chunk (solution in x[n][k]) into the slabs from column `slab0` on, while the chunk's solutions are there
+void err_facets_chunk(const Run &r, const System &sys, const DevicePoints &dp, const double *x, const ErrEst &e, int slab0, int k, int q0, int nq) {
+    const remo_batch *b = r.b;
+    const DeviceSymbolic &sy = b->sym;
+    const FieldSources src{dp.d_prhs + q0, dp.d_pI + q0, dp.d_found + q0, dp.d_fint + q0, nq};
+    launch_error_facets(r.dim, sy.condense, b->sigma_comp > 1, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, b->d_sigma, b->n_mat, sy.eldof, sy.adjptr, sy.adj,
+                        sys.d_C, sys.d_M, e.d_rule, k, x, src, e.eta2 + size_t(b->nt) * size_t(slab0), r.s);
+}
+
+// E_j and the group sums of every functional, in the fixed orders of the sensitivity sums
+void err_combine(const Run &r, const ErrEst &e) {
+    const remo_batch *b = r.b;
+    const remo_sens_request *rq = b->sens;
+    hipStream_t s = r.s;
+    const size_t nt = size_t(b->nt), ng = size_t(rq->err_n_group);
+    const bool groups = rq->err_group != nullptr;
+    if (groups) {
+        HIP_TRY(hipMemcpyAsync(e.d_group, rq->err_group, sizeof(int32_t) * nt, hipMemcpyHostToDevice, s));
+        sens_group_order(b->nt, e.d_group, b->sym.eperm, rq->err_n_group, e.keys_in, e.ids, e.keys, e.perm, e.off, e.sort_tmp, e.sort_bytes, s);
+    }
+    for (int j = 0; j < rq->n_fun; ++j) {
+        launch_error_combine(b->nt, e.eta2 + nt * size_t(rq->fun_rhs[j]), e.eta2 + nt * size_t(b->n_rhs + j), groups ? e.ev : nullptr, e.part + size_t(j) * e.grid, s);
+        if (groups) launch_sens_group_sum(1, b->nt, rq->err_n_group, e.keys, e.perm, e.off, e.ev, e.cpart, e.d_Eg + size_t(j) * ng, s);
+    }
+    launch_sens_reduce(rq->n_fun, e.grid, 1, e.part, e.d_E, s);
+    HIP_TRY(hipMemcpyAsync(rq->err_out, e.d_E, sizeof(double) * size_t(rq->n_fun), hipMemcpyDeviceToHost, s));
+    if (groups && ng > 0) HIP_TRY(hipMemcpyAsync(rq->errg_out, e.d_Eg, sizeof(double) * size_t(rq->n_fun) * ng, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+}
+
 // ---- events -> remo_stats_t -----------------------------------------------------------------------------------------------------
 void fill_timing_stats(const Run &r, const Plan &plan, const System &sys, bool mixed, bool patch_op, const RunTotals &tot) {
     remo_ctx *ctx = r.ctx;
@@ -1123,6 +1201,8 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         bool patch_op = false;
         if (int rc = choose_operator(r, plan, sys, sv, vb, patch_op)) return rc;
         const Sens sens = b->sens ? sens_take(r, sys) : Sens{};
+        const bool want_err = b->sens && b->sens->err;
+        const ErrEst est = want_err ? err_take(r) : ErrEst{};
         // remo_solve_batch_sens_warm: the previous call's solutions, in the layout of `sens` (same block offsets in another allocation).
         // Until this run ends well the object counts as empty; a hit keeps its contents, a miss makes room for this run's.
         remo_warm *warm = b->sens ? b->warm : nullptr;
@@ -1154,6 +1234,7 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
             if (int rc = solve_chunk(r, plan, sys, dp, sv, mixed ? &mx : nullptr, k, q0, nq, h_out, tot,
                                      warm_hit ? prev.block(sys.n, b->n_rhs, false, chunk) : nullptr, sec.on ? &sec : nullptr, chunk)) return rc;
             if (b->field) field_eval_chunk(r, sys, dp, sv.buf.x, fld, c0, k, q0, nq);   // while the chunk's solutions are there
+            if (want_err) err_facets_chunk(r, sys, dp, sv.buf.x, est, c0, k, q0, nq);
         }
         if (b->field) field_fetch(r, fld);
         for (int q = 0; q < npts; ++q)
@@ -1164,6 +1245,7 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
                 const int q0 = points.chunk_begin[chunk], nq = points.chunk_begin[chunk + 1] - q0;
                 b->d_x = sv.buf.x = sens.block(sys.n, b->n_rhs, true, ca);
                 if (int rc = solve_chunk(r, plan, sys, dp, sv, nullptr, k, q0, nq, h_out, tot, warm_hit ? prev.block(sys.n, b->n_rhs, true, ca) : nullptr)) return rc;
+                if (want_err) err_facets_chunk(r, sys, dp, sv.buf.x, est, b->n_rhs + a0, k, q0, nq);
             }
             if (warm) {   // a warm chunk left its sum in the object already; a cold run's solutions are copied there whole
                 if (!warm_hit) HIP_TRY(hipMemcpyAsync(warm->d, sens.keep, sizeof(double) * (warm_doubles(sys.n, b->n_rhs, rq->n_fun) - 64), hipMemcpyDeviceToDevice, s));
@@ -1178,6 +1260,7 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
                 rq->J_out[j] += rq->fun_w[fr.second] * h_out[fr.first];
             }
             if (!h_dJ.empty()) std::memcpy(rq->dJ_out, h_dJ.data(), sizeof(double) * h_dJ.size());
+            if (want_err) err_combine(r, est);
         }
         fill_timing_stats(r, plan, sys, mixed, patch_op, tot);
         st->ms_total = now_ms() - t_start;

@@ -296,6 +296,33 @@ static int check_functionals(remo_ctx_t *ctx, const remo_mesh_t *mesh, const rem
     return REMO_OK;
 }
 
+// the error estimates of a job (remo_job_error_t), likewise: what they do not combine with, and their grouping
+static int check_error(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t &j, const remo_job_error_t &e, unsigned parts, const remo_opts_t *opts) {
+    if (e.err != 0 && e.err != 1) return fail(ctx, REMO_ERR_ARG, "remo_job_error_t.err must be 0 or 1");
+    if (e.err == 0) return REMO_OK;
+    if (j.n_fun <= 0) return fail(ctx, REMO_ERR_ARG, "remo_job_error_t.err estimates the error of functionals: n_fun must be at least 1");
+    if (e.sec.secondary) return fail(ctx, REMO_ERR_ARG, "remo_job_error_t.err does not combine with the secondary formulation");
+    if (parts & kField) return fail(ctx, REMO_ERR_ARG, "remo_job_error_t.err does not combine with field points");
+    if (opts && opts->precision == 1) return fail(ctx, REMO_ERR_ARG, "the error estimates are formed from fp64 solutions: remo_opts_t.precision = 1 (mixed) is not supported with remo_job_error_t.err");
+    if (!e.err_out) return fail(ctx, REMO_ERR_ARG, "err_out missing");
+    if (e.err_n_group < 0) return fail(ctx, REMO_ERR_ARG, "err_n_group must not be negative");
+    if (e.err_n_group > 0) {
+        if (!e.err_group || !e.errg_out) return fail(ctx, REMO_ERR_ARG, "err_n_group > 0 needs err_group and errg_out");
+        if (!mesh || mesh->n_elems <= 0) return fail(ctx, REMO_ERR_ARG, "empty mesh");
+        for (int64_t t = 0; t < mesh->n_elems; ++t)
+            if (e.err_group[t] < -1 || e.err_group[t] >= e.err_n_group) return fail(ctx, REMO_ERR_ARG, "err_group id of element " + std::to_string(t) + " outside [-1, err_n_group)");
+    }
+    return REMO_OK;
+}
+
+// err_out / errg_out as a negative return leaves them
+static void error_nan_fill(const remo_job_t &j, const remo_job_error_t &e) {
+    if (e.err == 0 || j.n_fun <= 0) return;
+    for (int32_t i = 0; e.err_out && i < j.n_fun; ++i) e.err_out[i] = std::nan("");
+    if (e.errg_out && e.err_n_group > 0)
+        for (size_t i = 0; i < size_t(j.n_fun) * size_t(e.err_n_group); ++i) e.errg_out[i] = std::nan("");
+}
+
 // the field points of a job, likewise
 static int check_field(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t &j, const remo_opts_t *opts) {
     if (j.n_pts < 0 || j.n_frhs < 0 || (j.n_pts > 0 && !j.pts) || (j.n_frhs > 0 && !j.field_rhs)) return fail(ctx, REMO_ERR_ARG, "field points or field_rhs missing");
@@ -316,7 +343,7 @@ static int check_field(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_
 // there (field.hip), builds the load vector of the secondary formulation (secondary.hip) - run, fetch, destroy.
 // full: src_p / eval_p / fun_p are full coordinates (remo_solve_job), else axis positions z (the remo_solve_batch* entries).
 static int solve_one(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t &j, const remo_job_secondary_t *sec, unsigned parts, bool full,
-                     const remo_opts_t *opts, remo_stats_t *stats) {
+                     const remo_opts_t *opts, remo_stats_t *stats, const remo_job_error_t *est = nullptr) {
     if (!ctx) return REMO_ERR_ARG;
     // whatever goes wrong below, the object does not keep solutions of an earlier call (remo_batch_run labels it again on success)
     struct WarmGuard {
@@ -327,18 +354,27 @@ static int solve_one(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t 
     if (j.warm) j.warm->used_last = 0;
     if (j.warm && !sec && j.warm->device != ctx->device) return fail(ctx, REMO_ERR_ARG, "the warm object belongs to another device than the context");
     job_nan_fill(mesh, j);
+    if (est) error_nan_fill(j, *est);
     std::vector<double> sigma0;
-    int rc = sec ? resolve_secondary(ctx, mesh, j, *sec, opts, sigma0) : REMO_OK;   // (refuses every other part, a warm object included)
+    int rc = est ? check_error(ctx, mesh, j, *est, parts, opts) : REMO_OK;
+    if (rc != REMO_OK) return rc;
+    rc = sec ? resolve_secondary(ctx, mesh, j, *sec, opts, sigma0) : REMO_OK;   // (refuses every other part, a warm object included)
     if (rc == REMO_OK && (parts & kFun)) rc = check_functionals(ctx, mesh, j, parts, full);
     if (rc == REMO_OK && (parts & kField)) rc = check_field(ctx, mesh, j, opts);
     remo_batch_t *b = nullptr;
     if (rc == REMO_OK) rc = batch_create(ctx, mesh, j, full, &b, true);
     if (rc != REMO_OK) return rc;
     const bool groups = parts & kGroups;
-    const remo_sens_request sens{j.n_fun, j.fun_rhs, j.fun_ptr, j.fun_w, j.J_out, j.dJ_out, groups ? j.n_group : 0, groups ? j.group : nullptr, groups ? j.dJg_out : nullptr};
+    remo_sens_request sens{j.n_fun, j.fun_rhs, j.fun_ptr, j.fun_w, j.J_out, j.dJ_out, groups ? j.n_group : 0, groups ? j.group : nullptr, groups ? j.dJg_out : nullptr};
     const remo_field_request field{j.n_pts, j.pts, j.n_frhs, j.field_rhs, j.u_f, j.grad_f, j.J_f, j.elem_f};
     if (parts & kFun) {
         store_points(b->fun_p, j.fun_p, j.n_fun > 0 ? j.fun_ptr[j.n_fun] : 0, b->dim, full);
+        if (est && est->err) {
+            sens.err = true;
+            sens.err_n_group = est->err_n_group;
+            sens.err_group = est->err_n_group > 0 ? est->err_group : nullptr;
+            sens.err_out = est->err_out; sens.errg_out = est->errg_out;
+        }
         b->sens = &sens;
         b->warm = j.warm;
     }
@@ -348,6 +384,7 @@ static int solve_one(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t 
     rc = remo_batch_run(ctx, b, opts, stats);
     if (rc >= 0 && j.u_out) remo_batch_fetch(ctx, b, j.u_out);
     if (rc < 0) job_nan_fill(mesh, j);
+    if (rc < 0 && est) error_nan_fill(j, *est);
     remo_batch_destroy(ctx, b);
     guard.rc = rc;
     return rc;
@@ -464,15 +501,15 @@ int remo_solve_batch_field_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int3
 }
 
 // remo_solve_job / remo_batch_create_job: the job as this library knows it - the caller's leading `size` bytes, the rest zero.
-static int read_job(remo_ctx_t *ctx, const remo_job_t *job, remo_job_t &j, remo_job_secondary_t &x) {
+static int read_job(remo_ctx_t *ctx, const remo_job_t *job, remo_job_t &j, remo_job_error_t &x) {
     if (!ctx) return REMO_ERR_ARG;
     if (!job) return fail(ctx, REMO_ERR_ARG, "null job");
     const size_t size = job->size;
     if (size < offsetof(remo_job_t, n_fun)) return fail(ctx, REMO_ERR_ARG, "remo_job_t.size is smaller than the part every job has (through u_out)");
     std::memset(&j, 0, sizeof j);
     std::memset(&x, 0, sizeof x);
-    std::memcpy(&x, job, std::min(size, sizeof x));   // remo_job_secondary_t begins with a remo_job_t: one layout, two lengths
-    j = x.job;
+    std::memcpy(&x, job, std::min(size, sizeof x));   // remo_job_error_t begins with a remo_job_secondary_t, that with a remo_job_t: one layout, three lengths
+    j = x.sec.job;
     const unsigned char *raw = reinterpret_cast<const unsigned char *>(job);
     for (size_t i = sizeof x; i < size; ++i)   // a newer caller: what this library does not know must not be asked for
         if (raw[i]) return fail(ctx, REMO_ERR_ARG, "remo_job_t.size is larger than this library's struct and the tail is not zero");
@@ -482,8 +519,9 @@ static int read_job(remo_ctx_t *ctx, const remo_job_t *job, remo_job_t &j, remo_
 
 int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, const remo_opts_t *opts, remo_stats_t *stats) {
     remo_job_t j;
-    remo_job_secondary_t x;
-    int rc = read_job(ctx, job, j, x);
+    remo_job_error_t xe;
+    int rc = read_job(ctx, job, j, xe);
+    const remo_job_secondary_t &x = xe.sec;
     const bool fun = rc == REMO_OK && j.n_fun != 0, field = rc == REMO_OK && (j.n_pts != 0 || j.n_frhs != 0);
     if (rc == REMO_OK && fun && field) rc = fail(ctx, REMO_ERR_ARG, "field points together with functionals: two calls");
     if (rc == REMO_OK && !fun && (j.n_group != 0 || j.warm)) rc = fail(ctx, REMO_ERR_ARG, "groups or a warm object without functionals");
@@ -491,18 +529,25 @@ int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *j
     if (rc != REMO_OK) {
         if (ctx && job && job->size >= offsetof(remo_job_t, n_fun)) {   // a job that could be read: its outputs as the entries leave them on an error
             job_nan_fill(mesh, j);
+            error_nan_fill(j, xe);
             if (j.warm) remo_warm_clear(j.warm);
         }
         return rc;
     }
     const unsigned parts = (fun ? kFun : 0) | (j.n_group != 0 ? kGroups : 0) | (field ? kField : 0);
-    return solve_one(ctx, mesh, j, x.secondary ? &x : nullptr, parts, true, opts, stats);
+    if (xe.err != 0 && !fun) {   // (with functionals solve_one checks the members beside the other parts)
+        job_nan_fill(mesh, j);
+        return check_error(ctx, mesh, j, xe, parts, opts);
+    }
+    return solve_one(ctx, mesh, j, x.secondary ? &x : nullptr, parts, true, opts, stats, &xe);
 }
 
 int remo_batch_create_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, remo_batch_t **out) {
     remo_job_t j;
-    remo_job_secondary_t x;
-    if (int rc = read_job(ctx, job, j, x)) return rc;
+    remo_job_error_t xe;
+    if (int rc = read_job(ctx, job, j, xe)) return rc;
+    const remo_job_secondary_t &x = xe.sec;
+    if (xe.err != 0) return fail(ctx, REMO_ERR_ARG, "remo_job_error_t.err needs functionals: a resident batch has none (remo_solve_job)");
     if (x.secondary != 0 && x.secondary != 1) return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.secondary must be 0 or 1");
     std::vector<double> sigma0;
     if (x.secondary)   // (the batch entries read the sources and the evaluation points only: the other parts of the job must be empty here too)

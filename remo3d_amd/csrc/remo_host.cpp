@@ -10,6 +10,7 @@
 #include "sens.h"
 #include "field.h"
 #include "secondary.h"
+#include "errest.h"
 
 namespace remo {
 
@@ -42,6 +43,20 @@ static int secondary_element(const double *X, const double *sigma_tensor, double
         for (size_t p = 0; p < rule.size(); p += DIM + 2) sec_point<DIM>(X, g, vol, D, &rule[p], rec, 1, radius, acc);
     }
     for (int i = 0; i < N; ++i) f[i] = acc[i];
+    return REMO_OK;
+}
+
+// remo_host_error_facet: error_facet as k_error_facets calls it
+template <int DIM, bool TENSOR>
+static int error_facet_host(int f, const double *Xe, const double *Se, const double *xe, const double *Xn, const double *Sn, const double *xn, double *out) {
+    double ge[DIM][DIM];
+    const double vol = bary_gradients<DIM>(Xe, ge);
+    if (!(vol > 0.0)) return REMO_ERR_MESH;
+    if (Xn) {
+        double gn[DIM][DIM];
+        if (!(bary_gradients<DIM>(Xn, gn) > 0.0)) return REMO_ERR_MESH;
+    }
+    *out = error_facet<DIM, TENSOR>(err_rule(DIM), f, Xe, ge, vol, xe, Se, Xn != nullptr, Xn, xn, Sn);
     return REMO_OK;
 }
 
@@ -113,6 +128,17 @@ int remo_host_secondary_element(int32_t dim, const double *X, const double *sigm
     const int n = n_quad > 0 ? n_quad : kSecQuadDefault;
     return dim == 2 ? secondary_element<2>(X, sigma_tensor, sigma, sigma0, radius, src, n, f_out)
                     : secondary_element<3>(X, sigma_tensor, sigma, sigma0, radius, src, n, f_out);
+}
+
+int remo_host_error_facet(int32_t dim, int32_t facet, const double *Xe, const double *sigma_tensor_e, double sigma_e, const double *x_e, const double *Xn,
+                          const double *sigma_tensor_n, double sigma_n, const double *x_n, double *out) {
+    if ((dim != 2 && dim != 3) || facet < 0 || facet > dim || !Xe || !x_e || !out || (Xn && !x_n)) return REMO_ERR_ARG;
+    if (Xn && (sigma_tensor_e != nullptr) != (sigma_tensor_n != nullptr)) return REMO_ERR_ARG;
+    if (sigma_tensor_e && (!tensor_ok(dim, sigma_tensor_e) || (Xn && !tensor_ok(dim, sigma_tensor_n)))) return REMO_ERR_ARG;
+    const bool tensor = sigma_tensor_e != nullptr;
+    const double *Se = tensor ? sigma_tensor_e : &sigma_e, *Sn = tensor ? sigma_tensor_n : &sigma_n;
+    if (dim == 2) return tensor ? error_facet_host<2, true>(facet, Xe, Se, x_e, Xn, Sn, x_n, out) : error_facet_host<2, false>(facet, Xe, Se, x_e, Xn, Sn, x_n, out);
+    return tensor ? error_facet_host<3, true>(facet, Xe, Se, x_e, Xn, Sn, x_n, out) : error_facet_host<3, false>(facet, Xe, Se, x_e, Xn, Sn, x_n, out);
 }
 
 double remo_host_factor_error(void) { return ref_factors3_error(); }

@@ -145,6 +145,11 @@ struct remo_sens_request {
     int32_t n_group = 0;
     const int32_t *group = nullptr;
     double *dJg_out = nullptr;
+    // remo_job_error_t.err: error estimates of the functionals (errest.h), with a grouping of their own (checked by the entry)
+    bool err = false;
+    int32_t err_n_group = 0;
+    const int32_t *err_group = nullptr;
+    double *err_out = nullptr, *errg_out = nullptr;
 };
 
 // What remo_solve_batch_field adds to a batch: points of the mesh, the right-hand sides whose solution is read there and where the

@@ -448,6 +448,42 @@ class _Maps(_Output):
         model.sensitivity_grid = {k: np.asarray(v, dtype=float) for k, v in self.grid.items()}
 
 
+class _ErrorEstimates(_Output):
+    """The estimated relative discretisation error E / |J| of every reading (remo_job_error_t: the facet jumps of the forward and the
+    adjoint solution, element by element) and, with a grid, the share of E made in every cell and in the rest pseudo-cell."""
+    adjoint = True
+
+    def __init__(self, plan, grid):
+        self.plan, self.grid = plan, grid
+        self.slabs = [plan.slab()]
+        if grid is not None:
+            self.lateral = "x" if "x" in grid else "r"
+            self.n_cells = (len(grid["z"]) - 1) * (len(grid[self.lateral]) - 1)
+            self.slabs.append(plan.slab(self.n_cells + 1))
+
+    def prepare(self, job):
+        job.error = True
+        if self.grid is not None:     # one group per cell: an element belongs to the cell of geometry.sensitivity_cells, whatever its material
+            group, _, group_cell = geometry.sensitivity_cells(job.mesh, None, self.grid, self.plan.simulation_depths[job.bi])
+            job.error = dict(n_group=self.n_cells + 1, group=np.asarray(group_cell)[group].astype(np.int32))
+
+    def store(self, job):
+        for j, (di, ti, K) in enumerate(job.fun_readers):
+            Jj, E = job.J[j], job.E[j]
+            self.slabs[0][di, ti] = E / abs(Jj) if Jj != 0 else np.nan
+            if self.grid is not None:
+                self.slabs[1][di, ti] = job.Eg[j] / E if E != 0 else np.nan
+
+    def publish(self, model):
+        model.error_estimates = _per_tool(model, lambda i: self.slabs[0][:, i])
+        if self.grid is not None:
+            n = self.n_cells
+            shape = (len(self.plan.depths), len(self.grid["z"]) - 1, len(self.grid[self.lateral]) - 1)
+            model.error_maps = _per_tool(model, lambda i: self.slabs[1][:, i, :n].reshape(shape))
+            model.error_map_rest = _per_tool(model, lambda i: self.slabs[1][:, i, n])
+            model.error_grid = {k: np.asarray(v, dtype=float) for k, v in self.grid.items()}
+
+
 class _FieldSections(_Output):
     """The potential and the current density of the right-hand side behind a record - the electrode configuration actually
     energised - on a section grid of points: physical values (3D: the half-space FE field halved, as tasks.apparent_resistivity
@@ -536,7 +572,7 @@ class _BatchRunner:
             t0 = time.time()
             fg, bh, sigma = self.windowing.window(bi)
             job = types.SimpleNamespace(bi=bi, sigma=sigma, mesh=self.meshes.mesh(bi, fg, bh), groups=None, functionals=None,
-                                        field_rhs=None, field_points=None)
+                                        field_rhs=None, field_points=None, error=None)
             sources, evals, job.readers = tasks.batch_rhs(batch, p.model.tools, p.eccentricity)
             job.sources = sources
             t1 = time.time()
@@ -545,20 +581,27 @@ class _BatchRunner:
                 job.functionals, job.fun_readers = tasks.batch_functionals(batch, p.model.tools, p.eccentricity)
             for o in self.outputs:
                 o.prepare(job)
+            est = {} if job.error is None else dict(error=job.error)     # the keyword only where an output asked for it
+
+            def adjoint(res, *names):     # (potentials, J, dJ, [dJg,] [E, [Eg],] stats, rc) of the adjoint entries into the job
+                for name, value in zip(names, res):
+                    setattr(job, name, value)
+                job.E, job.Eg = (tuple(res[len(names):-2]) + (None, None))[:2]
+                return res[-2], res[-1]
             c = self.free_ctx.get()
             try:     # the solver entry follows from what the outputs asked for
                 if job.groups is not None:
-                    job.outs, job.J, job.dJ, job.dJg, st, rc = c.solve_batch_sens_groups(job.mesh, job.sigma, sources, evals, job.functionals,
-                                                                                         job.groups, len(job.group_mat), opts)
+                    st, rc = adjoint(c.solve_batch_sens_groups(job.mesh, job.sigma, sources, evals, job.functionals, job.groups, len(job.group_mat), opts, **est),
+                                     "outs", "J", "dJ", "dJg")
                 elif job.functionals is not None:
                     warm = self.cache.warm_state(bi) if self.cache is not None else None      # the batch's solutions of the previous sweep
                     if warm is not None:
                         try:
-                            job.outs, job.J, job.dJ, st, rc = c.solve_batch_sens(job.mesh, job.sigma, sources, evals, job.functionals, opts, warm=warm)
+                            st, rc = adjoint(c.solve_batch_sens(job.mesh, job.sigma, sources, evals, job.functionals, opts, warm=warm, **est), "outs", "J", "dJ")
                         finally:
                             self.cache.after_solve(bi, warm)
                     else:
-                        job.outs, job.J, job.dJ, st, rc = c.solve_batch_sens(job.mesh, job.sigma, sources, evals, job.functionals, opts)
+                        st, rc = adjoint(c.solve_batch_sens(job.mesh, job.sigma, sources, evals, job.functionals, opts, **est), "outs", "J", "dJ")
                 elif job.field_rhs is not None:
                     job.outs, job.field, st, rc = c.solve_batch_field(job.mesh, job.sigma, sources, evals, job.field_points, job.field_rhs, opts)
                 elif p.secondary is not None:
@@ -625,6 +668,10 @@ class Model:
         self.field_sections = None     # simulate_logs(field_grid=...): per tool dict(u [n_kept, n_z, n_h] in V, J [n_kept, n_z, n_h, dim] in A/m2)
         self.field_sources = None      # ... per tool and kept record the energised point sources (absolute z, I)
         self.field_source_x = None     # ... and their x in the mesh frame (the eccentricity of the sweep; 0 for a centred tool)
+        self.error_estimates = None    # simulate_logs(error_estimate=True): per tool the estimated relative error of the apparent resistivity [n_depths]
+        self.error_maps = None         # simulate_logs(error_grid=...): per tool the share of that estimate made in every grid cell [n_depths, n_z, n_r]
+        self.error_map_rest = None     # ... and outside the grid [n_depths]; the cells and the rest sum to 1
+        self.error_grid = None         # the grid of the last error maps
         self.formulation = None        # "primary" or "secondary": how the last sweep treated the point sources (simulate_logs)
         self.eccentricity = None       # the displacement of the tool from the borehole axis in the last sweep, metres along x
         self.field_grid = None         # the grid of the last sections
@@ -809,8 +856,19 @@ class Model:
                       maxsteps: int = 1000, verbose: bool = True, mesh_workers: Optional[int] = None, precision: str = "fp64",
                       schedule: str = "static", solver_options: Optional[dict] = None, sensitivities: bool = False,
                       sensitivity_grid: Optional[dict] = None, reuse=None, field_grid: Optional[dict] = None,
-                      field_depths=None, eccentricity: float = 0.0, formulation: str = "primary"):
-        """formulation: "primary" (default) - every point source goes into the load vector, as without the keyword - or "secondary":
+                      field_depths=None, eccentricity: float = 0.0, formulation: str = "primary", error_estimate: bool = False,
+                      error_grid: Optional[dict] = None):
+        """error_estimate: also fill self.error_estimates[tool] [n_depths] with E / |J| of the record's reading, the estimated relative
+        discretisation error of the apparent resistivity on the batch mesh the sweep drew (mesh_scale): the goal-oriented estimate
+        from the facet jumps of the normal current density of the forward and the adjoint solution (remo_job_error_t; dimensionless,
+        NaN where J = 0 or the batch failed).  Implies the adjoint solves; about what the sensitivities cost.  The constant is the
+        conventional one, not a sharp one: DESIGN.md section 3.8 states how the estimate compares with the true error.
+        error_grid: dict(r=edges, z=edges[, x=edges]), cells as sensitivity_grid defines them: also fill self.error_maps[tool]
+        [n_depths, n_z, n_r] and self.error_map_rest[tool] [n_depths] with the share of the estimate made in every cell and outside the
+        grid (they sum to 1) - where a size field should be tightened -, and self.error_grid.  Implies error_estimate.  Both work with
+        sensitivities, sensitivity_grid, eccentricity, anisotropic tables and reuse; not with formulation="secondary",
+        precision="mixed" or field_grid: a ValueError before any batch is drawn.
+        formulation: "primary" (default) - every point source goes into the load vector, as without the keyword - or "secondary":
         every batch is solved for the smooth remainder u_s of u = u_p + u_s, u_p the closed-form potential of the batch's sources in
         homogeneous mud inside a grounded sphere of radius domain_radius (remo_job_secondary_t.secondary; sigma0 is left to the library: the
         conductivity at the source), so the elements around the electrodes no longer resolve a 1 / r singularity.  Works with
@@ -856,6 +914,21 @@ class Model:
                                  "sweeps (reuse, invert_logs): the adjoint and field entries read the finite-element potential alone")
             if precision != "fp64" or (solver_options or {}).get("precision", "fp64") != "fp64":
                 raise ValueError("formulation='secondary' is fp64: precision has to be 'fp64'")
+        error_estimate = bool(error_estimate) or error_grid is not None
+        if error_estimate:
+            if formulation == "secondary":
+                raise ValueError("error estimates cannot be combined with formulation='secondary': the indicator reads the finite-element potential alone")
+            if precision != "fp64" or (solver_options or {}).get("precision", "fp64") != "fp64":
+                raise ValueError("error estimates are formed from fp64 solutions: precision has to be 'fp64'")
+            if field_grid is not None:
+                raise ValueError("error estimates cannot be combined with field_grid: there are no field sections with the adjoint solver entries")
+            if error_grid is not None:     # a malformed grid fails here, before any batch is drawn
+                lateral = [k for k in ("r", "x") if k in error_grid]
+                if len(lateral) != 1 or "z" not in error_grid:
+                    raise ValueError("error_grid must hold the edges of 'z' and of one of 'r' and 'x'")
+                for e in (error_grid["z"], error_grid[lateral[0]]):
+                    if np.ndim(e) != 1 or len(e) < 2 or np.any(np.diff(np.asarray(e, dtype=float)) <= 0):
+                        raise ValueError("error_grid edges must be increasing, two at least")
         if field_grid is not None:
             if sensitivities or sensitivity_grid is not None or reuse is not None:
                 raise ValueError("field_grid cannot be combined with sensitivities, sensitivity_grid or an inversion's sweeps: "
@@ -878,6 +951,8 @@ class Model:
             outputs.append(_Maps(plan, sensitivity_grid))
         if field_grid is not None:
             outputs.append(_FieldSections(plan, field_grid, field_depths))
+        if error_estimate:
+            outputs.append(_ErrorEstimates(plan, error_grid))
         bq = sweep.BatchQueue(len(plan.batches), schedule)
         if reuse is not None:
             from . import inversion
@@ -897,6 +972,7 @@ class Model:
             o.combine()
         self.sensitivities = self.mud_sensitivity = self.sensitivity_maps = self.sensitivity_map_rest = self.sensitivity_grid = None
         self.field_sections = self.field_sources = self.field_source_x = self.field_grid = self.field_depth_index = None
+        self.error_estimates = self.error_maps = self.error_map_rest = self.error_grid = None
         for o in outputs:
             o.publish(self)
         self.timing = dict(total_s=time.time() - start, mesh_s=acc["mesh"], solve_s=acc["solve"], points=acc["points"], batches=len(plan.batches),

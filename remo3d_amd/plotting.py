@@ -172,6 +172,41 @@ def plot_sensitivity_map(model, tool, depth_index, path=None):
     return fig
 
 
+def plot_error_map(model, tool, depth_index, path=None):
+    """One picture of model.error_maps[tool][depth_index] (Model.simulate_logs(error_grid=...)): the share of the reading's error
+    estimate made in every cell as a pcolormesh on a logarithmic colour scale, depth downwards, with the bed boundaries and the
+    borehole wall drawn over it; the title carries the estimated relative error.  Returns the figure; `path`: also written there."""
+    import matplotlib
+    if not os.environ.get("MPLBACKEND") and not os.environ.get("DISPLAY"):
+        matplotlib.use("Agg", force=False)
+    import matplotlib.pyplot as plt
+    from matplotlib.colors import LogNorm
+    grid = model.error_grid
+    lateral = "x" if "x" in grid else "r"
+    m = np.asarray(model.error_maps[tool][depth_index], dtype=float)
+    top = float(np.nanmax(m)) if np.any(np.isfinite(m)) else 1.0
+    top = top if top > 0 else 1.0
+    fig, ax = plt.subplots(figsize=(5, 7))
+    mesh = ax.pcolormesh(grid[lateral], grid["z"], np.where(m > 0, m, np.nan), cmap="magma", norm=LogNorm(vmin=1e-6 * top, vmax=top), shading="flat")
+    slope = np.tan(np.deg2rad(model.dip_deg)) if lateral == "x" else 0.0
+    h = np.array([grid[lateral][0], grid[lateral][-1]])
+    for z in np.unique(np.asarray(model.formation_model, dtype=float)[:, :2]):      # bed boundaries (sheared by the dip in the x view)
+        ax.plot(h, z + slope * h, color="w", lw=0.6)
+    bh = np.asarray(model.borehole_model, dtype=float)
+    for sgn in ((1.0, -1.0) if h[0] < 0 else (1.0,)):
+        ax.plot(sgn * bh[:, 1], bh[:, 0], color="w", lw=0.9)
+    ax.set_xlim(h[0], h[1])
+    ax.set_ylim(grid["z"][-1], grid["z"][0])
+    ax.set_xlabel("{} [m]".format(lateral))
+    ax.set_ylabel("depth [m]")
+    ax.set_title("{} at {:.2f} m: share of the estimate {:.2e}".format(tool, float(model.logs[tool][depth_index, 0]),
+                                                                      float(model.error_estimates[tool][depth_index])))
+    fig.colorbar(mesh, ax=ax)
+    if path is not None:
+        fig.savefig(path, dpi=120)
+    return fig
+
+
 def _uniform_axis(c):
     c = np.asarray(c, dtype=float)
     return c.size < 3 or np.allclose(np.diff(c), (c[-1] - c[0]) / (c.size - 1), rtol=1e-6, atol=0.0)

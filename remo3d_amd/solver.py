@@ -146,18 +146,41 @@ def _secondary_members(secondary, n_rhs):
     return int(secondary.get("quad") or 0), float(secondary.get("radius") or 0.0), s0, valid
 
 
-def _batch_args(handle, mesh, sigma, sources, evals, job=False, secondary=None):
+def _error_members(error, n_elems):
+    """error=True | dict(n_group=, group=) -> (err_n_group, err_group int32 array or None) of remo_job_error_t.  group: [n_elems] ids
+    in the order of mesh.conn, -1 = in no group; n_group: default largest id + 1."""
+    if error is True:
+        return 0, None
+    if not isinstance(error, dict):
+        raise ValueError("error must be True or dict(n_group=, group=)")
+    unknown = set(error) - {"n_group", "group"}
+    if unknown:
+        raise ValueError("error: unknown keys {}".format(sorted(unknown)))
+    group = error.get("group")
+    if group is None:
+        return int(error.get("n_group") or 0), None
+    group = np.ascontiguousarray(group, dtype=np.int32).ravel()
+    if group.size != n_elems:
+        raise ValueError("error: group must hold one id per element")
+    n_group = error.get("n_group")
+    return (int(group.max(initial=-1)) + 1 if n_group is None else int(n_group)), group
+
+
+def _batch_args(handle, mesh, sigma, sources, evals, job=False, secondary=None, error=None):
     """What every batch entry begins with (remo_solve_batch*, remo_solve_job, remo_batch_create*): [handle, mesh, job], the job a
     remo_job_t with the conductivity table, the sources and the evaluation points set.  Returns (args, sigma table, tensor?,
     eval_ptr, keep); keep holds what the pointers in the job look at.
     job: positions are points, as remo_solve_job reads them; else src_p / eval_p hold axis z and the job only names the arguments of
     an entry that takes a list (_lib.legacy_args).
-    secondary: dict(radius, sigma0, quad) - the job with the members of the secondary-potential formulation set (job is implied)."""
-    job = job or secondary is not None
+    secondary: dict(radius, sigma0, quad) - the job with the members of the secondary-potential formulation set (job is implied).
+    error: True | dict(n_group, group) - the job with the members of the error estimates set (job is implied); the outputs err_out /
+    errg_out are the caller's to add."""
+    error = None if error is False else error
+    job = job or secondary is not None or error is not None
     sigma, tensor = sigma_table(sigma, int(mesh.dim))
     src_ptr, sz, sI, eval_ptr, ez = _rhs_arrays(sources, evals, int(mesh.dim) if job else 0)
     ms, keep = _lib.mesh_struct(mesh)
-    Job = _lib.RemoJob if secondary is None else _lib.RemoJobSecondary
+    Job = _lib.RemoJobError if error is not None else (_lib.RemoJob if secondary is None else _lib.RemoJobSecondary)
     j = Job(size=C.sizeof(Job), tensor=int(tensor), n_mat=len(sigma), sigma=ptr(sigma, C.c_double), n_rhs=len(sources),
             src_ptr=ptr(src_ptr, C.c_int32), src_p=ptr(sz, C.c_double), src_I=ptr(sI, C.c_double),
             eval_ptr=ptr(eval_ptr, C.c_int32), eval_p=ptr(ez, C.c_double))
@@ -167,7 +190,13 @@ def _batch_args(handle, mesh, sigma, sources, evals, job=False, secondary=None):
         j.secondary = 1
         if s0 is not None:
             j.sec_sigma0 = ptr(s0, C.c_double)
-    return [handle, C.byref(ms), j], sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez, s0)
+    eg = None
+    if error is not None:
+        j.err = 1
+        j.err_n_group, eg = _error_members(error, keep[1].shape[0])
+        if eg is not None:
+            j.err_group = ptr(eg, C.c_int32)
+    return [handle, C.byref(ms), j], sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez, s0, eg)
 
 
 def _field_points(points, dim):
@@ -265,19 +294,20 @@ class Context:
         return (self._L.remo_last_error(self._h) or b"").decode()
 
     def _one_shot(self, kind, mesh, sigma, sources, evals, opts, raise_on_error, functionals=None, groups=None, n_group=None, warm=None,
-                  points=None, field_rhs=None, secondary=None):
+                  points=None, field_rhs=None, secondary=None, error=None):
         """The one marshalling path of the one-shot entries remo_solve_batch<kind>[_tensor], kind "", "_sens", "_sens_warm", "_sens_groups"
         or "_field": the common arguments, then the functionals and the groups - or the field points - with their outputs where the kind
         has them.  Returns (potentials, [J, dJ, [dJg] | field dict,] stats, rc).
         Positions (of sources, evaluation points, functionals) are 1-D arrays of axis z or [m, dim] arrays of points; with one item
         of the second kind the job goes to remo_solve_job, every item as points; else its members, positions as axis z, are the
         arguments of the kind's own symbol."""
-        job = secondary is not None or _off_axis([z for (z, _) in sources], evals, [z for (_, z, _) in functionals] if functionals else [])
-        (handle, ms, j), sigma, tensor, eval_ptr, keep = _batch_args(self._h, mesh, sigma, sources, evals, job, secondary)
+        error = None if error is False else error
+        job = secondary is not None or error is not None or _off_axis([z for (z, _) in sources], evals, [z for (_, z, _) in functionals] if functionals else [])
+        (handle, ms, j), sigma, tensor, eval_ptr, keep = _batch_args(self._h, mesh, sigma, sources, evals, job, secondary, error)
         d, nc = int(mesh.dim), (sigma.shape[1] if tensor else 1)
         out = np.full(int(eval_ptr[-1]), np.nan)
         j.u_out = ptr(out, C.c_double)
-        J, grads, field = [], [], []
+        J, grads, field, est = [], [], [], []
         if kind == "_field":
             points = _field_points(points, d)
             field_rhs = np.ascontiguousarray(np.arange(len(sources)) if field_rhs is None else field_rhs, dtype=np.int32).ravel()
@@ -302,6 +332,12 @@ class Context:
                 j.n_group, j.group, j.dJg_out = n_group, ptr(groups, C.c_int32), ptr(grads[1], C.c_double)
             if kind == "_sens_warm":
                 j.warm = warm._h
+            if error is not None:
+                est = [np.full(n_fun, np.nan)]
+                j.err_out = ptr(est[0], C.c_double)
+                if j.err_n_group > 0:
+                    est.append(np.full((n_fun, j.err_n_group), np.nan))
+                    j.errg_out = ptr(est[1], C.c_double)
         st = RemoStats()
         o = opts if opts is not None else make_opts()
         if not job:
@@ -316,7 +352,7 @@ class Context:
         if rc < 0 and raise_on_error:
             raise RemoError(rc, self.last_error())
         potentials = [out[eval_ptr[k]:eval_ptr[k + 1]] for k in range(len(evals))]
-        return (potentials, *J, *[_symmetric_gradient(g, d, tensor) for g in grads], *field, st.as_dict(), rc)
+        return (potentials, *J, *[_symmetric_gradient(g, d, tensor) for g in grads], *est, *field, st.as_dict(), rc)
 
     def solve_batch(self, mesh, sigma, sources, evals, opts: Optional[RemoOpts] = None, raise_on_error=True, secondary=None):
         """One-shot remo_solve_batch.  Returns (list of per-RHS potential arrays, stats dict, rc).
@@ -333,26 +369,30 @@ class Context:
         return self._one_shot("", mesh, sigma, sources, evals, opts, raise_on_error, secondary=secondary)
 
     def solve_batch_sens(self, mesh, sigma, sources, evals, functionals, opts: Optional[RemoOpts] = None, raise_on_error=True,
-                         warm: Optional[WarmState] = None):
+                         warm: Optional[WarmState] = None, error=None):
         """One-shot remo_solve_batch_sens: the batch of solve_batch plus linear functionals of the potentials and their derivatives
         with respect to the materials' conductivities (adjoint solves).  functionals: list of (rhs, z array, w array),
         J = sum_i w[i] * u_rhs(z[i]).  Returns (potentials, J [n_fun], dJ, stats, rc) with dJ [n_fun, n_mat] for sigma [n_mat] and
         [n_fun, n_mat, dim, dim] for tensors: symmetric G with dJ = G : dSigma for symmetric dSigma (the library's triangle holds
         both halves of an off-diagonal pair; each half gets half of it here).
         warm: a WarmState of this device (remo_solve_batch_sens_warm): the solves start from the solutions it holds when they belong
-        to a batch of the same sizes, and it holds this call's afterwards; stats["pcg_steps"] then counts one measuring step per chunk."""
+        to a batch of the same sizes, and it holds this call's afterwards; stats["pcg_steps"] then counts one measuring step per chunk.
+        error=True | dict(n_group=, group=): goal-oriented error estimates of the functionals from the facet jumps of the forward and
+        the adjoint solutions (remo_job_error_t; the call goes through remo_solve_job).  Returns (potentials, J, dJ, E [n_fun],
+        [Eg [n_fun, n_group],] stats, rc): E_j estimates |J_j(u) - J_j(u_h)|, Eg its part made in every group of elements (group:
+        [n_elems] ids in the order of mesh.conn, -1 = in no group)."""
         if warm is not None:
-            return self._one_shot("_sens_warm", mesh, sigma, sources, evals, opts, raise_on_error, functionals, warm=warm)
-        return self._one_shot("_sens", mesh, sigma, sources, evals, opts, raise_on_error, functionals)
+            return self._one_shot("_sens_warm", mesh, sigma, sources, evals, opts, raise_on_error, functionals, warm=warm, error=error)
+        return self._one_shot("_sens", mesh, sigma, sources, evals, opts, raise_on_error, functionals, error=error)
 
     def solve_batch_sens_groups(self, mesh, sigma, sources, evals, functionals, groups, n_group=None, opts: Optional[RemoOpts] = None,
-                                raise_on_error=True):
+                                raise_on_error=True, error=None):
         """One-shot remo_solve_batch_sens_groups: solve_batch_sens plus the derivatives with respect to caller-defined groups of
         elements.  groups: [n_elems] int, the group of every element of mesh.conn (-1: in no group); n_group: the number of groups
         (default: largest id + 1).  With sigma_e = sigma_mat(e) + p_group(e), dJg[j, g] = dJ_j/dp_g.  Returns
         (potentials, J, dJ, dJg, stats, rc); dJg is [n_fun, n_group] for sigma [n_mat] and [n_fun, n_group, dim, dim] for tensors,
-        with the symmetric-G convention of dJ."""
-        return self._one_shot("_sens_groups", mesh, sigma, sources, evals, opts, raise_on_error, functionals, groups, n_group)
+        with the symmetric-G convention of dJ.  error: as for solve_batch_sens - E (and Eg) follow dJg in the result."""
+        return self._one_shot("_sens_groups", mesh, sigma, sources, evals, opts, raise_on_error, functionals, groups, n_group, error=error)
 
     def solve_batch_field(self, mesh, sigma, sources, evals, points, field_rhs=None, opts: Optional[RemoOpts] = None, raise_on_error=True):
         """One-shot remo_solve_batch_field: the batch of solve_batch plus the solution away from the axis.  points: [n_pts, dim] in the
