@@ -417,6 +417,33 @@ typedef struct {
     double *err_out;            /* [n_fun]               E_j  */
     double *errg_out;           /* [n_fun * err_n_group] Eg_j,g; may be NULL when err_n_group = 0 */
 } remo_job_error_t;             /* 288 bytes */
+/*
+ * n_pair > 0: PAIR DERIVATIVES - the derivatives of all transfer impedances of an electrode array by reciprocity (added within ABI 7:
+ * five members behind remo_job_error_t, which keeps its 288 bytes; set job.size = sizeof(remo_job_pairs_t) and hand &x.err.sec.job to
+ * remo_solve_job).  A multi-electrode tool reads linear combinations of Z_ij, the potential at electrode i per unit current at
+ * electrode j.  A is symmetric, so the adjoint of "read u at electrode i" is the forward solution of a source at electrode i:
+ *     Z_ij = e_i^T A^{-1} f_j,    dZ_ij/dsigma_m = -u_i^T (dA/dsigma_m) u_j,
+ * with u_i and u_j both right-hand sides of the batch - no adjoint solves.  For the right-hand sides a = pair_a[p], b = pair_b[p]
+ *     dP_out[(p * n_mat + m) * nc + c] = -u_a^T (dA / d component c of material m) u_b,
+ * components as in dJ_out (nc = 1, or 3 / 6 for tensor = 1, off-diagonal entries carrying both halves).  Any order, a == b and
+ * repeats are allowed, and a pair may join columns of different chunks of REMO_MAX_RHS.  Z itself is what u_out gives when the
+ * electrodes are listed as evaluation points.  In 2D with condense = 1 the cell bubbles of both columns are recovered, each with the
+ * point loads of its own chunk.  One pass over the elements serves all pairs of one or two chunks (pairs.h): the element vector of
+ * every column is gathered once and reduced to 30 (2D: 40) moments, and a pair costs an inner product of those.  Every sum has a fixed
+ * order (no floating-point atomics): with op = 2 two calls give the same bits of dP_out.  n_fun = 0 is allowed with pairs; with
+ * functionals, groups or err in the same job u_out, J_out, dJ_out, dJg_out and err_out are exactly what the job returns with
+ * n_pair = 0 (bit for bit with op = 2).  n_pair = 0: as before, bit for bit.
+ * Errors, REMO_ERR_ARG before any device work: a pair_a / pair_b outside [0, n_rhs); NULL arrays or a NULL dP_out with n_pair > 0;
+ * n_pair < 0; pair_reserved != 0; pairs together with secondary = 1, with field points, with a warm object or with precision = 1.
+ * On any negative return dP_out is NaN-filled like the other outputs.  remo_batch_create_job refuses n_pair > 0.
+ */
+typedef struct {
+    remo_job_error_t err;
+    int32_t n_pair;                   /* 0: as before, bit for bit */
+    int32_t pair_reserved;            /* must be 0 */
+    const int32_t *pair_a, *pair_b;   /* [n_pair] right-hand sides */
+    double *dP_out;                   /* [n_pair * n_mat * nc], pair-major */
+} remo_job_pairs_t;                   /* 320 bytes */
 int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, const remo_opts_t *opts, remo_stats_t *stats);
 
 /*
@@ -492,6 +519,11 @@ int remo_host_element_matrix_tensor(int32_t dim, const double *vertex_coords, co
 /* The element contraction of remo_solve_batch_sens on the host (the code the kernel runs): out[nc] = x_l^T (dK_e / d component) x_u
  * for element vectors x_l, x_u [nld]; tensor = 0: nc = 1 (d/dsigma), else nc = 3 / 6 (upper triangle, off-diagonal both halves). */
 int remo_host_sens_element(int32_t dim, const double *vertex_coords, int32_t tensor, const double *x_l, const double *x_u, double *out);
+/* The element arithmetic of remo_job_pairs_t on the host (the code the kernel runs): the moments of the k element vectors x[k * nld]
+ * once, then out[p * nc + c] = x_a^T (dK_e / d component c) x_b for a = pa[p], b = pb[p] in [0, k) from the moments alone - the value
+ * remo_host_sens_element forms from the two vectors, by another order of summation.  REMO_ERR_MESH for a degenerate element. */
+int remo_host_pair_element(int32_t dim, const double *vertex_coords, int32_t tensor, int32_t k, const double *x, int32_t n_pair,
+                           const int32_t *pa, const int32_t *pb, double *out);
 /* The per-point arithmetic of remo_solve_batch_field on the host (the code the kernel runs): out[1 + 2 * dim] = u, grad u, J at
  * `point` [dim] of the element with sorted vertices vertex_coords and element vector x_e [nld].  sigma_tensor != NULL: the upper
  * triangle of the material's tensor (REMO_ERR_ARG if not finite and positive definite), else the scalar sigma. */

@@ -68,6 +68,9 @@ int remo_debug_direction_bytes(remo_ctx_t *ctx);
 /* The load-vector launches (element vectors + row sums, all chunks) of the last remo_batch_run of a batch with remo_job_secondary_t.secondary
  * on this context, ms by HIP events; 0 when the last run was none. */
 int remo_debug_secondary_timing(remo_ctx_t *ctx, double *ms);
+/* The pair pass of the last job with remo_job_pairs_t.n_pair > 0 on this context: out2[0] = its time in ms (HIP events around the element
+ * launches of all chunk pairs and the reduction), [1] = the number of element launches. */
+int remo_debug_pairs_timing(remo_ctx_t *ctx, double *out2);
 
 /* Process-global knobs, two kinds.  Returns 0, or -1 for a key this build does not have.
  *
@@ -96,6 +99,8 @@ int remo_debug_secondary_timing(remo_ctx_t *ctx, double *ms);
  *       widened by its three readers - the direction launch, the operator's staging phase, the evaluated values of the update
  *       launch; r, q, the slab and every sum stay fp64; same potentials to the solve's tolerance, under 1 % more steps).  Keys
  *       39 = 0, 25 = 0 and 22 = 0 imply fp64.  remo_debug_direction_bytes says which form the last run took.
+ *   42  0 = the pair derivatives of remo_job_pairs_t by one launch of k_sens_contract per pair, both columns forward, instead of
+ *       the fused pass of k_pair_contract (default 1; the same values to rounding - what the fused pass is measured against).
  *   40  1 = the patch operator takes one element per lane: patches of 256 / k elements (k = right-hand sides of the batch);
  *       2 (default) = two elements per lane, one after the other, in fp64 solves with k >= 3: patches of 2 * (256 / k) elements
  *       (k_patch_apply ROUNDS = 2).  A batch whose largest such patch does not fit the tables or LDS gets the tables of 1.

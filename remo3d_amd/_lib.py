@@ -74,6 +74,12 @@ class RemoJobError(C.Structure):
                                             ("err_out", C.POINTER(C.c_double)), ("errg_out", C.POINTER(C.c_double))]
 
 
+class RemoJobPairs(C.Structure):
+    """remo_job_pairs_t: a remo_job_error_t with the five members of the pair derivatives behind it (flat, like RemoJobSecondary)."""
+    _fields_ = RemoJobError._fields_ + [("n_pair", C.c_int32), ("pair_reserved", C.c_int32), ("pair_a", C.POINTER(C.c_int32)),
+                                        ("pair_b", C.POINTER(C.c_int32)), ("dP_out", C.POINTER(C.c_double))]
+
+
 # include/remo3d_hip.h: the drop-in boundary + inspection hooks of the parity tests
 EXPORTS = ["remo_abi_version", "remo_opts_default", "remo_ctx_create", "remo_ctx_destroy", "remo_last_error",
            "remo_solve_batch", "remo_solve_batch_tensor", "remo_solve_batch_sens", "remo_solve_batch_sens_tensor", "remo_solve_batch_sens_groups", "remo_solve_batch_sens_groups_tensor",
@@ -81,9 +87,9 @@ EXPORTS = ["remo_abi_version", "remo_opts_default", "remo_ctx_create", "remo_ctx
            "remo_warm_create", "remo_warm_destroy", "remo_warm_clear", "remo_warm_info", "remo_solve_batch_sens_warm", "remo_solve_batch_sens_warm_tensor", "remo_batch_create", "remo_batch_create_tensor", "remo_batch_run", "remo_batch_fetch", "remo_batch_destroy",
            "remo_batch_eval", "remo_batch_get_system", "remo_batch_get_vectors", "remo_batch_apply_coarse", "remo_batch_spmv",
            "remo_host_element_matrix", "remo_host_element_matrix_tensor", "remo_host_sens_element", "remo_host_factor_error", "remo_host_symbolic",
-           "remo_solve_job", "remo_batch_create_job", "remo_host_point_shapes", "remo_host_secondary_element", "remo_host_error_facet"]
+           "remo_solve_job", "remo_batch_create_job", "remo_host_point_shapes", "remo_host_secondary_element", "remo_host_error_facet", "remo_host_pair_element"]
 # include/remo3d_hip_debug.h: probes and tuning knobs (tests, tools, bench.py's `box` record) - not part of the boundary
-DEBUG_EXPORTS = ["remo_debug_stream", "remo_debug_clock", "remo_debug_device", "remo_debug_cache_gather", "remo_debug_xcc", "remo_debug_tune", "remo_debug_patch_phases", "remo_debug_patch_phases_p", "remo_debug_grid_barrier", "remo_debug_sens_timing", "remo_debug_sens_group_timing", "remo_debug_field_timing", "remo_debug_point_location", "remo_debug_secondary_timing", "remo_debug_direction_bytes"]
+DEBUG_EXPORTS = ["remo_debug_stream", "remo_debug_clock", "remo_debug_device", "remo_debug_cache_gather", "remo_debug_xcc", "remo_debug_tune", "remo_debug_patch_phases", "remo_debug_patch_phases_p", "remo_debug_grid_barrier", "remo_debug_sens_timing", "remo_debug_sens_group_timing", "remo_debug_field_timing", "remo_debug_point_location", "remo_debug_secondary_timing", "remo_debug_direction_bytes", "remo_debug_pairs_timing"]
 
 # The argument lists of the entries that take one (remo_solve_batch<kind>[_tensor], remo_batch_create[_tensor]) as members of
 # RemoJob: ctx and mesh, JOB_HEAD, then the kind's members - for the solves followed by opts and stats.  load() derives the
@@ -138,7 +144,7 @@ def load():
     L.remo_warm_info.restype = C.c_int
     L.remo_warm_info.argtypes = [vp, i64p, ip, i64p, ip]
     L.remo_solve_job.restype = C.c_int
-    L.remo_solve_job.argtypes = [vp, C.POINTER(RemoMesh), vp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]     # the job: RemoJob, RemoJobSecondary or RemoJobError
+    L.remo_solve_job.argtypes = [vp, C.POINTER(RemoMesh), vp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]     # the job: RemoJob, RemoJobSecondary, RemoJobError or RemoJobPairs
     L.remo_batch_create_job.restype = C.c_int
     L.remo_batch_create_job.argtypes = [vp, C.POINTER(RemoMesh), vp, C.POINTER(vp)]
     L.remo_host_point_shapes.restype = C.c_int
@@ -161,6 +167,10 @@ def load():
     L.remo_debug_secondary_timing.argtypes = [vp, dp]
     L.remo_debug_sens_group_timing.restype = C.c_int
     L.remo_debug_sens_group_timing.argtypes = [vp, dp]
+    L.remo_host_pair_element.restype = C.c_int
+    L.remo_host_pair_element.argtypes = [C.c_int32, dp, C.c_int32, C.c_int32, dp, C.c_int32, ip, ip, dp]
+    L.remo_debug_pairs_timing.restype = C.c_int
+    L.remo_debug_pairs_timing.argtypes = [vp, dp]
     L.remo_host_sens_element.restype = C.c_int
     L.remo_host_sens_element.argtypes = [C.c_int32, dp, C.c_int32, dp, dp, dp]
     L.remo_debug_sens_timing.restype = C.c_int

@@ -16,6 +16,7 @@
 #include "pcg_host.h"
 #include "patch.h"
 #include "sens.h"
+#include "pairs.h"
 #include "field.h"
 #include "warm.h"
 #include "secondary.h"
@@ -178,6 +179,8 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
             }
         }
     }
+    if (b->pairs)   // pair derivatives (pairs_take): slots; part, d_dP (+ the alignment of these takes)
+        need += size_t(b->pairs->n_pair) * 8 + size_t(b->pairs->n_pair) * size_t(b->n_mat) * size_t(b->sigma_comp) * 8 * (size_t(pair_grid(nt)) + 1) + 4 * 256;
     if (o.precision == 1) {   // fp32 copies of the matrix values and of every PCG vector (mixed_buffers)
         need += size_t(nv + 64) * 200 * 8;                           // fp32 sq_a, sq_b
         need += size_t(nnz_max) * 4;                                 // v32
@@ -941,6 +944,16 @@ Sens sens_take(const Run &r, const System &sys) {
     return sn;
 }
 
+// the tables sens_element / pair_moments read: 2D the reference tensors of the run, 3D their factors, uploaded by the first use
+const double *sens_tables(const Run &r, const System &sys) {
+    remo_ctx *ctx = r.ctx;
+    if (r.dim == 3 && !ctx->d_B3) {
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->d_B3), sizeof(double) * 600));
+        HIP_TRY(hipMemcpyAsync(ctx->d_B3, ref_factors3(), sizeof(double) * 600, hipMemcpyHostToDevice, r.s));
+    }
+    return (r.dim == 3) ? ctx->d_B3 : sys.d_M;
+}
+
 // dJ_j/d(component of material m) = -lambda_j^T A_m u_rhs(j): one pass over the elements per functional, then the workgroups' sums
 // With groups: the elements are ordered by group once, then per functional the material pass as before (dJ_out has the bits of
 // remo_solve_batch_sens), the per-element pass into the one ev buffer, and the sums of its segments.
@@ -950,11 +963,7 @@ void sens_contract(const Run &r, const System &sys, const DevicePoints &dp, cons
     const remo_sens_request *rq = b->sens;
     const DeviceSymbolic &sy = b->sym;
     hipStream_t s = r.s;
-    if (r.dim == 3 && !ctx->d_B3) {
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->d_B3), sizeof(double) * 600));
-        HIP_TRY(hipMemcpyAsync(ctx->d_B3, ref_factors3(), sizeof(double) * 600, hipMemcpyHostToDevice, s));
-    }
-    const double *tab = (r.dim == 3) ? ctx->d_B3 : sys.d_M;
+    const double *tab = sens_tables(r, sys);
     const bool groups = rq->group != nullptr && rq->n_fun > 0;
     const bool split_times = groups && r.o.time_kernels != 0;   // one synchronisation per functional: measuring runs only
     const size_t ngc = size_t(rq->n_group) * size_t(b->sigma_comp);
@@ -1012,6 +1021,106 @@ void sens_contract(const Run &r, const System &sys, const DevicePoints &dp, cons
     ctx->sens_ms = ms;
     // per functional: the x rows of both columns once (8 n each), and per element its dof numbers, vertices, material and (2D) metric terms
     ctx->sens_bytes = double(rq->n_fun) * (16.0 * double(sys.n) + double(b->nt) * (4.0 * r.N + 4.0 * (r.dim + 1) + 4.0 + (r.dim == 2 ? 8.0 * r.NT : 0.0)));
+}
+
+// ---- pair derivatives (pairs.hip): dP_p = -u_a^T (dA/dsigma) u_b for pairs of forward columns ------------------------------------------
+struct Pairs {
+    int32_t *d_slots = nullptr;   // two staged-column slots per pair, in the order the launches take the pairs
+    double *part = nullptr, *d_dP = nullptr;
+    int grid = 0, nmc = 0;
+};
+
+Pairs pairs_take(const Run &r) {
+    const remo_batch *b = r.b;
+    const size_t np = size_t(b->pairs->n_pair);
+    Pairs pr;
+    pr.grid = pair_grid(b->nt);
+    pr.nmc = b->n_mat * b->sigma_comp;
+    pr.d_slots = r.ctx->take<int32_t>(2 * np);
+    pr.part = r.ctx->take<double>(np * pr.grid * pr.nmc + 1);
+    pr.d_dP = r.ctx->take<double>(np * pr.nmc + 1);
+    return pr;
+}
+
+// The pairs that join chunk ca with chunk cb go together: both blocks are staged once per element.  A launch keeps at most
+// kPairSliceAcc accumulators (always one pair), so a chunk pair with many pairs or materials takes several.  The launches take the
+// pairs in an order of their own; dP_out gets them back in the caller's.
+void pairs_contract(const Run &r, const System &sys, const DevicePoints &dp, const Points &pts, const Sens &sn, const Pairs &pr) {
+    remo_ctx *ctx = r.ctx;
+    const remo_batch *b = r.b;
+    const remo_pairs_request *rq = b->pairs;
+    const DeviceSymbolic &sy = b->sym;
+    hipStream_t s = r.s;
+    const double *tab = sens_tables(r, sys);
+    const int np = rq->n_pair, nchunk = pts.forward_chunks, per_launch = std::max(1, kPairSliceAcc / std::max(1, pr.nmc));
+    struct Launch { PairColumns pc; int first, count; };
+    std::vector<Launch> launches;
+    std::vector<int32_t> order, slots;   // order[i]: the caller's index of the pair at position i
+    for (int ca = 0; ca < nchunk; ++ca)
+        for (int cb = ca; cb < nchunk; ++cb) {
+            std::vector<int32_t> mine;
+            for (int p = 0; p < np; ++p) {
+                const int a = rq->pair_a[p] / REMO_MAX_RHS, c = rq->pair_b[p] / REMO_MAX_RHS;
+                if (std::min(a, c) == ca && std::max(a, c) == cb) mine.push_back(p);
+            }
+            for (size_t i0 = 0; i0 < mine.size(); i0 += size_t(per_launch)) {
+                Launch L{};
+                L.first = int(order.size());
+                L.count = int(std::min(mine.size() - i0, size_t(per_launch)));
+                const int chunks[2] = {ca, cb};
+                for (int i = 0; i < 2; ++i) {
+                    L.pc.x[i] = sn.block(sys.n, b->n_rhs, false, chunks[i]);
+                    L.pc.k[i] = std::min(b->n_rhs - chunks[i] * REMO_MAX_RHS, REMO_MAX_RHS);
+                    L.pc.q0[i] = pts.chunk_begin[chunks[i]];
+                    L.pc.nq[i] = pts.chunk_begin[chunks[i] + 1] - L.pc.q0[i];
+                }
+                int slot_of[kPairMaxCols];
+                std::fill(slot_of, slot_of + kPairMaxCols, -1);
+                for (int i = 0; i < L.count; ++i) {
+                    const int p = mine[i0 + size_t(i)];
+                    order.push_back(p);
+                    for (const int rhs : {rq->pair_a[p], rq->pair_b[p]}) {
+                        const int key = ((rhs / REMO_MAX_RHS == ca) ? 0 : 8) + rhs % REMO_MAX_RHS;   // block and column (ca == cb: block 0)
+                        if (slot_of[key] < 0) { slot_of[key] = L.pc.ncol; L.pc.col[L.pc.ncol++] = int8_t(key); }
+                        slots.push_back(slot_of[key]);
+                    }
+                }
+                launches.push_back(L);
+            }
+        }
+    HIP_TRY(hipEventRecord(ctx->ev[4], s));
+    const bool fused = g_tune.pairs_fused != 0;
+    const int grid = fused ? pr.grid : sens_grid(b->nt);   // (sens_grid <= pair_grid: part holds either)
+    size_t n_launch = launches.size();
+    if (fused) {
+        HIP_TRY(hipMemcpyAsync(pr.d_slots, slots.data(), sizeof(int32_t) * slots.size(), hipMemcpyHostToDevice, s));
+        for (const Launch &L : launches)
+            launch_pair_contract(r.dim, sy.condense, b->sigma_comp > 1, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, sy.eldof, sys.d_C, sys.d_M, tab, L.pc,
+                                 L.count, pr.d_slots + 2 * size_t(L.first), dp.d_prhs, dp.d_pI, dp.d_found, dp.d_fint, b->n_mat, grid,
+                                 pr.part + size_t(L.first) * grid * pr.nmc, s);
+    } else {   // remo_debug_tune key 42 = 0: every pair as a functional whose adjoint column is the forward column a
+        n_launch = size_t(np);
+        for (int i = 0; i < np; ++i) {
+            const int a = rq->pair_a[order[size_t(i)]], c = rq->pair_b[order[size_t(i)]], ca = a / REMO_MAX_RHS, cc = c / REMO_MAX_RHS;
+            SensColumns col;
+            col.xu = sn.block(sys.n, b->n_rhs, false, cc); col.ku = std::min(b->n_rhs - cc * REMO_MAX_RHS, REMO_MAX_RHS); col.cu = c % REMO_MAX_RHS;
+            col.xl = sn.block(sys.n, b->n_rhs, false, ca); col.kl = std::min(b->n_rhs - ca * REMO_MAX_RHS, REMO_MAX_RHS); col.cl = a % REMO_MAX_RHS;
+            col.qu0 = pts.chunk_begin[cc]; col.nqu = pts.chunk_begin[cc + 1] - col.qu0;
+            col.ql0 = pts.chunk_begin[ca]; col.nql = pts.chunk_begin[ca + 1] - col.ql0;
+            launch_sens_contract(r.dim, sy.condense, b->sigma_comp > 1, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, sy.eldof, sys.d_C, sys.d_M, tab, col,
+                                 dp.d_prhs, dp.d_pI, dp.d_found, dp.d_fint, b->n_mat, pr.part + size_t(i) * grid * pr.nmc, s);
+        }
+    }
+    launch_sens_reduce(np, grid, pr.nmc, pr.part, pr.d_dP, s);
+    HIP_TRY(hipEventRecord(ctx->ev[5], s));
+    std::vector<double> h(size_t(np) * pr.nmc);
+    HIP_TRY(hipMemcpyAsync(h.data(), pr.d_dP, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < np; ++i) std::memcpy(rq->dP_out + size_t(order[size_t(i)]) * pr.nmc, h.data() + size_t(i) * pr.nmc, sizeof(double) * pr.nmc);
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]);
+    ctx->pair_ms[0] = ms;
+    ctx->pair_ms[1] = double(n_launch);
 }
 
 // ---- error estimates of the functionals (errest.hip) ------------------------------------------------------------------------------
@@ -1203,6 +1312,7 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         const Sens sens = b->sens ? sens_take(r, sys) : Sens{};
         const bool want_err = b->sens && b->sens->err;
         const ErrEst est = want_err ? err_take(r) : ErrEst{};
+        const Pairs prs = b->pairs ? pairs_take(r) : Pairs{};
         // remo_solve_batch_sens_warm: the previous call's solutions, in the layout of `sens` (same block offsets in another allocation).
         // Until this run ends well the object counts as empty; a hit keeps its contents, a miss makes room for this run's.
         remo_warm *warm = b->sens ? b->warm : nullptr;
@@ -1261,6 +1371,7 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
             }
             if (!h_dJ.empty()) std::memcpy(rq->dJ_out, h_dJ.data(), sizeof(double) * h_dJ.size());
             if (want_err) err_combine(r, est);
+            if (b->pairs && b->pairs->n_pair > 0) pairs_contract(r, sys, dp, points, sens, prs);
         }
         fill_timing_stats(r, plan, sys, mixed, patch_op, tot);
         st->ms_total = now_ms() - t_start;

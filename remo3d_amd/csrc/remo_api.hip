@@ -323,6 +323,29 @@ static void error_nan_fill(const remo_job_t &j, const remo_job_error_t &e) {
         for (size_t i = 0; i < size_t(j.n_fun) * size_t(e.err_n_group); ++i) e.errg_out[i] = std::nan("");
 }
 
+// the pairs of a job (remo_job_pairs_t), likewise: what they do not combine with, and their indices
+static int check_pairs(remo_ctx_t *ctx, const remo_job_t &j, const remo_job_pairs_t &x, unsigned parts, const remo_opts_t *opts) {
+    if (x.n_pair < 0) return fail(ctx, REMO_ERR_ARG, "n_pair must not be negative");
+    if (x.pair_reserved != 0) return fail(ctx, REMO_ERR_ARG, "remo_job_pairs_t.pair_reserved must be 0");
+    if (x.n_pair == 0) return REMO_OK;
+    if (!x.pair_a || !x.pair_b || !x.dP_out) return fail(ctx, REMO_ERR_ARG, "n_pair > 0 needs pair_a, pair_b and dP_out");
+    if (x.err.sec.secondary) return fail(ctx, REMO_ERR_ARG, "pairs do not combine with the secondary formulation");
+    if (parts & kField) return fail(ctx, REMO_ERR_ARG, "pairs do not combine with field points");
+    if (j.warm) return fail(ctx, REMO_ERR_ARG, "pairs do not combine with a warm object");
+    if (opts && opts->precision == 1) return fail(ctx, REMO_ERR_ARG, "the pair derivatives are formed from fp64 solutions: remo_opts_t.precision = 1 (mixed) is not supported with n_pair > 0");
+    for (int32_t p = 0; p < x.n_pair; ++p)
+        if (x.pair_a[p] < 0 || x.pair_a[p] >= j.n_rhs || x.pair_b[p] < 0 || x.pair_b[p] >= j.n_rhs)
+            return fail(ctx, REMO_ERR_ARG, "pair " + std::to_string(p) + " names no right-hand side of the batch");
+    return REMO_OK;
+}
+
+// dP_out as a negative return leaves it
+static void pairs_nan_fill(const remo_mesh_t *mesh, const remo_job_t &j, const remo_job_pairs_t &x) {
+    if (x.n_pair <= 0 || !x.dP_out || j.n_mat <= 0) return;
+    const size_t ncomp = (j.tensor && mesh) ? ((mesh->dim == 2) ? 3 : 6) : 1;
+    for (size_t i = 0; i < size_t(x.n_pair) * size_t(j.n_mat) * ncomp; ++i) x.dP_out[i] = std::nan("");
+}
+
 // the field points of a job, likewise
 static int check_field(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t &j, const remo_opts_t *opts) {
     if (j.n_pts < 0 || j.n_frhs < 0 || (j.n_pts > 0 && !j.pts) || (j.n_frhs > 0 && !j.field_rhs)) return fail(ctx, REMO_ERR_ARG, "field points or field_rhs missing");
@@ -343,7 +366,7 @@ static int check_field(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_
 // there (field.hip), builds the load vector of the secondary formulation (secondary.hip) - run, fetch, destroy.
 // full: src_p / eval_p / fun_p are full coordinates (remo_solve_job), else axis positions z (the remo_solve_batch* entries).
 static int solve_one(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t &j, const remo_job_secondary_t *sec, unsigned parts, bool full,
-                     const remo_opts_t *opts, remo_stats_t *stats, const remo_job_error_t *est = nullptr) {
+                     const remo_opts_t *opts, remo_stats_t *stats, const remo_job_error_t *est = nullptr, const remo_job_pairs_t *prs = nullptr) {
     if (!ctx) return REMO_ERR_ARG;
     // whatever goes wrong below, the object does not keep solutions of an earlier call (remo_batch_run labels it again on success)
     struct WarmGuard {
@@ -355,8 +378,10 @@ static int solve_one(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t 
     if (j.warm && !sec && j.warm->device != ctx->device) return fail(ctx, REMO_ERR_ARG, "the warm object belongs to another device than the context");
     job_nan_fill(mesh, j);
     if (est) error_nan_fill(j, *est);
+    if (prs) pairs_nan_fill(mesh, j, *prs);
     std::vector<double> sigma0;
     int rc = est ? check_error(ctx, mesh, j, *est, parts, opts) : REMO_OK;
+    if (rc == REMO_OK && prs) rc = check_pairs(ctx, j, *prs, parts, opts);
     if (rc != REMO_OK) return rc;
     rc = sec ? resolve_secondary(ctx, mesh, j, *sec, opts, sigma0) : REMO_OK;   // (refuses every other part, a warm object included)
     if (rc == REMO_OK && (parts & kFun)) rc = check_functionals(ctx, mesh, j, parts, full);
@@ -378,6 +403,8 @@ static int solve_one(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t 
         b->sens = &sens;
         b->warm = j.warm;
     }
+    const remo_pairs_request pairs{prs ? prs->n_pair : 0, prs ? prs->pair_a : nullptr, prs ? prs->pair_b : nullptr, prs ? prs->dP_out : nullptr};
+    if (pairs.n_pair > 0) b->pairs = &pairs;   // (the entry has made a job with pairs a kFun job: the forward solutions stay for the pass)
     if (parts & kField) b->field = &field;
     if (sec) attach_secondary(b, *sec, sigma0);
     b->eval_only = true;
@@ -385,6 +412,7 @@ static int solve_one(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t 
     if (rc >= 0 && j.u_out) remo_batch_fetch(ctx, b, j.u_out);
     if (rc < 0) job_nan_fill(mesh, j);
     if (rc < 0 && est) error_nan_fill(j, *est);
+    if (rc < 0 && prs) pairs_nan_fill(mesh, j, *prs);
     remo_batch_destroy(ctx, b);
     guard.rc = rc;
     return rc;
@@ -501,15 +529,15 @@ int remo_solve_batch_field_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int3
 }
 
 // remo_solve_job / remo_batch_create_job: the job as this library knows it - the caller's leading `size` bytes, the rest zero.
-static int read_job(remo_ctx_t *ctx, const remo_job_t *job, remo_job_t &j, remo_job_error_t &x) {
+static int read_job(remo_ctx_t *ctx, const remo_job_t *job, remo_job_t &j, remo_job_pairs_t &x) {
     if (!ctx) return REMO_ERR_ARG;
     if (!job) return fail(ctx, REMO_ERR_ARG, "null job");
     const size_t size = job->size;
     if (size < offsetof(remo_job_t, n_fun)) return fail(ctx, REMO_ERR_ARG, "remo_job_t.size is smaller than the part every job has (through u_out)");
     std::memset(&j, 0, sizeof j);
     std::memset(&x, 0, sizeof x);
-    std::memcpy(&x, job, std::min(size, sizeof x));   // remo_job_error_t begins with a remo_job_secondary_t, that with a remo_job_t: one layout, three lengths
-    j = x.sec.job;
+    std::memcpy(&x, job, std::min(size, sizeof x));   // remo_job_pairs_t begins with a remo_job_error_t, that with a remo_job_secondary_t, that with a remo_job_t: one layout, four lengths
+    j = x.err.sec.job;
     const unsigned char *raw = reinterpret_cast<const unsigned char *>(job);
     for (size_t i = sizeof x; i < size; ++i)   // a newer caller: what this library does not know must not be asked for
         if (raw[i]) return fail(ctx, REMO_ERR_ARG, "remo_job_t.size is larger than this library's struct and the tail is not zero");
@@ -519,10 +547,12 @@ static int read_job(remo_ctx_t *ctx, const remo_job_t *job, remo_job_t &j, remo_
 
 int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, const remo_opts_t *opts, remo_stats_t *stats) {
     remo_job_t j;
-    remo_job_error_t xe;
-    int rc = read_job(ctx, job, j, xe);
+    remo_job_pairs_t xp;
+    int rc = read_job(ctx, job, j, xp);
+    const remo_job_error_t &xe = xp.err;
     const remo_job_secondary_t &x = xe.sec;
-    const bool fun = rc == REMO_OK && j.n_fun != 0, field = rc == REMO_OK && (j.n_pts != 0 || j.n_frhs != 0);
+    const bool pairs = rc == REMO_OK && xp.n_pair > 0;   // (a job with pairs is a job with functionals, n_fun = 0 included: its solutions stay)
+    const bool fun = rc == REMO_OK && (j.n_fun != 0 || pairs), field = rc == REMO_OK && (j.n_pts != 0 || j.n_frhs != 0);
     if (rc == REMO_OK && fun && field) rc = fail(ctx, REMO_ERR_ARG, "field points together with functionals: two calls");
     if (rc == REMO_OK && !fun && (j.n_group != 0 || j.warm)) rc = fail(ctx, REMO_ERR_ARG, "groups or a warm object without functionals");
     if (rc == REMO_OK && x.secondary != 0 && x.secondary != 1) rc = fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.secondary must be 0 or 1");
@@ -530,6 +560,7 @@ int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *j
         if (ctx && job && job->size >= offsetof(remo_job_t, n_fun)) {   // a job that could be read: its outputs as the entries leave them on an error
             job_nan_fill(mesh, j);
             error_nan_fill(j, xe);
+            pairs_nan_fill(mesh, j, xp);
             if (j.warm) remo_warm_clear(j.warm);
         }
         return rc;
@@ -539,14 +570,16 @@ int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *j
         job_nan_fill(mesh, j);
         return check_error(ctx, mesh, j, xe, parts, opts);
     }
-    return solve_one(ctx, mesh, j, x.secondary ? &x : nullptr, parts, true, opts, stats, &xe);
+    return solve_one(ctx, mesh, j, x.secondary ? &x : nullptr, parts, true, opts, stats, &xe, &xp);
 }
 
 int remo_batch_create_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, remo_batch_t **out) {
     remo_job_t j;
-    remo_job_error_t xe;
-    if (int rc = read_job(ctx, job, j, xe)) return rc;
+    remo_job_pairs_t xp;
+    if (int rc = read_job(ctx, job, j, xp)) return rc;
+    const remo_job_error_t &xe = xp.err;
     const remo_job_secondary_t &x = xe.sec;
+    if (xp.n_pair > 0) return fail(ctx, REMO_ERR_ARG, "remo_job_pairs_t.n_pair needs the solutions of a one-shot job: a resident batch keeps none (remo_solve_job)");
     if (xe.err != 0) return fail(ctx, REMO_ERR_ARG, "remo_job_error_t.err needs functionals: a resident batch has none (remo_solve_job)");
     if (x.secondary != 0 && x.secondary != 1) return fail(ctx, REMO_ERR_ARG, "remo_job_secondary_t.secondary must be 0 or 1");
     std::vector<double> sigma0;

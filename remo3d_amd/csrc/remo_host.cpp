@@ -8,6 +8,7 @@
 #include "fem_p3.h"
 #include "symbolic.h"
 #include "sens.h"
+#include "pairs.h"
 #include "field.h"
 #include "secondary.h"
 #include "errest.h"
@@ -60,6 +61,23 @@ static int error_facet_host(int f, const double *Xe, const double *Se, const dou
     return REMO_OK;
 }
 
+// remo_host_pair_element: pair_moments of every column once, then pair_value per pair, as k_pair_contract stages them
+template <int DIM>
+static int pair_element_host(const double *X, const double *tab, bool tensor, int k, const double *x, int n_pair, const int32_t *pa, const int32_t *pb, double *out) {
+    constexpr int N = P3<DIM>::NLD, NM = PairMom<DIM>::N, NS = SigmaTensor<DIM>::N;
+    double g[DIM][DIM];
+    const double vol = bary_gradients<DIM>(X, g);
+    if (!(vol > 0.0)) return REMO_ERR_MESH;
+    std::vector<double> mom(size_t(k) * NM);
+    for (int c = 0; c < k; ++c) pair_moments<DIM>(X, g, tab, x + size_t(c) * N, &mom[size_t(c) * NM]);
+    for (int p = 0; p < n_pair; ++p) {
+        const double *ma = &mom[size_t(pa[p]) * NM], *mb = &mom[size_t(pb[p]) * NM];
+        if (tensor) pair_value<DIM, true>(vol, g, ma, mb, out + size_t(p) * NS);
+        else pair_value<DIM, false>(vol, g, ma, mb, out + p);
+    }
+    return REMO_OK;
+}
+
 extern "C" {
 
 int remo_host_element_matrix(int32_t dim, const double *X, double sigma, double *K_out) {
@@ -103,6 +121,15 @@ int remo_host_sens_element(int32_t dim, const double *X, int32_t tensor, const d
     if (dim == 2) ok = tensor ? sens_element<2, true>(X, ref_tables(2), xl, xu, out) : sens_element<2, false>(X, ref_tables(2), xl, xu, out);
     else ok = tensor ? sens_element<3, true>(X, ref_factors3(), xl, xu, out) : sens_element<3, false>(X, ref_factors3(), xl, xu, out);
     return ok ? REMO_OK : REMO_ERR_MESH;
+}
+
+int remo_host_pair_element(int32_t dim, const double *X, int32_t tensor, int32_t k, const double *x, int32_t n_pair, const int32_t *pa, const int32_t *pb,
+                           double *out) {
+    if ((dim != 2 && dim != 3) || !X || !x || k < 1 || n_pair < 0 || (n_pair > 0 && (!pa || !pb || !out))) return REMO_ERR_ARG;
+    for (int p = 0; p < n_pair; ++p)
+        if (pa[p] < 0 || pa[p] >= k || pb[p] < 0 || pb[p] >= k) return REMO_ERR_ARG;
+    return (dim == 2) ? pair_element_host<2>(X, ref_tables(2), tensor != 0, k, x, n_pair, pa, pb, out)
+                      : pair_element_host<3>(X, ref_factors3(), tensor != 0, k, x, n_pair, pa, pb, out);
 }
 
 int remo_host_field_element(int32_t dim, const double *X, const double *sigma_tensor, double sigma, const double *x_e, const double *point, double *out) {

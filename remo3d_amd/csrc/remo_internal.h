@@ -55,6 +55,7 @@ struct Tune {
     int dot_bins = 1;        // key 28 (probe builds): 1 = the patches add their <p, A p> straight into the update launch's rows (default), 0 = a row per patch + k_patch_dot
     int x_ev = 1;            // key 39: 1 = one-shot fp64 solves carry only the values of x the evaluation points read (default), 0 = the whole x
     int p32 = 1;             // key 41: 1 = those solves, on the patch operator, store the search direction in fp32 (default; PcgBuffersT::p32), 0 = in fp64
+    int pairs_fused = 1;     // key 42: 1 = the pairs of remo_job_pairs_t in one fused element pass per chunk pair (default; k_pair_contract), 0 = one launch of k_sens_contract per pair
 #ifdef REMO_PROBES
     int extra_apply = 0;     // key 36 (probe builds): extra operator applications (apply + shared-row sums, results discarded) per PCG step: what a step with more applications would cost
 #endif
@@ -92,6 +93,7 @@ struct remo_ctx {
     double *d_B3 = nullptr;                  // factors of the 3D tensors (ref_factors3) for the sensitivity contraction, uploaded by its first use
     double sens_ms = 0.0, sens_bytes = 0.0;  // last remo_solve_batch_sens: HIP-event time and algorithmic bytes of the contraction launches (remo_debug_sens_timing)
     double sens_group_ms[4] = {};            // last remo_solve_batch_sens_groups: group order; with time_kernels also the material pass, the per-element pass and the group sums, each over all functionals (remo_debug_sens_group_timing)
+    double pair_ms[2] = {};                  // last job with pairs: HIP-event time of the pair pass (element launches + reduction) and its launch count (remo_debug_pairs_timing)
     double field_ms[2] = {};                 // last remo_solve_batch_field / remo_batch_field: HIP-event time of the location of the points and of the evaluation launches (remo_debug_field_timing)
     hipEvent_t fev[4] = {};                  // their events, created by the first use
     double sec_ms = 0.0;                     // last remo_batch_run with remo_job_secondary_t.secondary: HIP-event time of the load-vector launches, all chunks (remo_debug_secondary_timing)
@@ -163,6 +165,15 @@ struct remo_field_request {
     int32_t *elem = nullptr;
 };
 
+// What remo_job_pairs_t adds to a batch: pairs of right-hand sides (a, b) and where -u_a^T (dA/dsigma) u_b goes (host pointers of the
+// caller, checked by the entry, valid for the duration of the call only).  A batch with pairs has a `sens` request too (n_fun may be
+// 0): the forward solutions stay in the arena for the pass (pairs.h).
+struct remo_pairs_request {
+    int n_pair = 0;
+    const int32_t *pair_a = nullptr, *pair_b = nullptr;
+    double *dP_out = nullptr;
+};
+
 struct remo_warm;   // warm.h
 
 struct remo_batch {
@@ -181,6 +192,7 @@ struct remo_batch {
     uint8_t *d_bdir = nullptr;
     bool pooled = false;     // the six arrays live in the context's input pool (remo_solve_batch): not freed with the batch
     const remo_sens_request *sens = nullptr;   // remo_solve_batch_sens: adjoint solves + contraction after the forward solves (batch_run.hip)
+    const remo_pairs_request *pairs = nullptr; // remo_job_pairs_t: derivatives of u_a(x_b) for pairs of forward columns, one element pass (batch_run.hip, pairs.hip)
     remo_warm *warm = nullptr;                 // remo_solve_batch_sens_warm: where the solutions of the previous call are, and where these go (warm.h)
     const remo_field_request *field = nullptr; // remo_solve_batch_field: the solution at arbitrary points, chunk by chunk (batch_run.hip, field.hip)
     // remo_job_secondary_t.secondary: the secondary-potential formulation (secondary.h) - element rule, sphere of the primary field and the

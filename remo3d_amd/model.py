@@ -29,7 +29,7 @@ from typing import Callable, Dict, Optional
 
 import numpy as np
 
-from . import geometry, meshgen, solver, sweep, tasks, tools as tools_mod
+from . import arrays, geometry, meshgen, solver, sweep, tasks, tools as tools_mod
 
 CONVERSION = {"M": 1.0, "DM": 0.1, "CM": 0.01, "MM": 0.001, "IN": 0.0254, "FT": 0.3048}
 
@@ -168,8 +168,7 @@ class _Plan:
         self.model, self.domain_radius, self.mesh_scale = model, domain_radius, mesh_scale
         self.depths = np.asarray(measurement_depths, dtype=float)
         alert = False
-        for t in model.tools.values():
-            far = np.max(np.abs(t[0, :3]))
+        for far in self._reaches():
             if far > domain_radius:
                 raise ValueError("Some electrodes are locate outside the simulation domain. Domain size have to be increased")
             alert |= far > 0.75 * domain_radius
@@ -193,7 +192,7 @@ class _Plan:
         self.netgen_path = (not is3d) and mesh_generator in ("auto", "netgen")
         self.default_provider = mesh_provider is None     # its 3D meshes are the conforming revolved ones; only it runs in the mesh pool
         self.provider = mesh_provider or default_mesh_provider(scale=mesh_scale)
-        self.simulation_depths, self.batches = model._prepare_simulation_depths_and_tasks(self.depths, batch_size)
+        self.simulation_depths, self.batches = self._draw_batches(batch_size)
         for b in self.batches:
             b.lateral = self.eccentricity
         self.borehole_geometry = np.ascontiguousarray(model.borehole_model[:, :2])
@@ -210,6 +209,13 @@ class _Plan:
         self.contexts = [model.ctx] + list(getattr(model, "extra_ctx", []))
         self.share_len = len(list(sweep.my_share(len(self.batches))))
         self.secondary = None      # simulate_logs(formulation="secondary"): the keyword every batch's solve is given
+
+    def _reaches(self):
+        """How far from a batch's centre the electrodes of every tool lie."""
+        return [float(np.max(np.abs(t[0, :3]))) for t in self.model.tools.values()]
+
+    def _draw_batches(self, batch_size):
+        return self.model._prepare_simulation_depths_and_tasks(self.depths, batch_size)
 
     def batch_opts(self, mesh):
         if self.tuned_coarse and getattr(mesh, "dim", 0) == 3:
@@ -646,6 +652,141 @@ class _BatchRunner:
             self._drive()
 
 
+# -- the stages of Model.simulate_array_logs: a plan, outputs and a batch of their own; windowing, meshes and threads are the tools' ----
+class _ArrayPlan(_Plan):
+    """Stage 1 for an electrode array (arrays.ElectrodeArray): batches of consecutive depths; slabs per (depth, mode)."""
+
+    def __init__(self, model, array, sensitivities, *args):
+        self.array, self.sensitivities = array, bool(sensitivities)
+        super().__init__(model, *args)
+
+    def _reaches(self):
+        a = self.array
+        return [float(np.max(np.abs(a.offsets - np.mean(a.offsets[a.current_electrodes]))))]
+
+    def _draw_batches(self, batch_size):
+        return arrays.build_batches(self.array, self.depths, batch_size)
+
+    def slab(self, *tail):
+        return np.zeros((len(self.depths), len(self.array.modes)) + tail)
+
+
+class _ArrayOutput(_Output):
+    def fail(self, rows):
+        for slab in self.slabs:
+            for di, _ in rows:
+                slab[di] = np.nan
+
+
+class _ArrayLogs(_ArrayOutput):
+    """Ra and the currents of every mode, and the impedances they were formed from (physical values; NaN where not measured)."""
+
+    def __init__(self, plan):
+        m = len(plan.array.names)
+        self.plan, self.slabs = plan, [plan.slab(), plan.slab(m), np.zeros((len(plan.depths), m, m))]
+
+    def store(self, job):
+        for di, Z in zip(job.depth_index, job.Z):
+            self.slabs[2][di] = Z
+            for k, mode in enumerate(self.plan.array.modes):
+                self.slabs[0][di, k], self.slabs[1][di, k], _ = self.plan.array.apparent_resistivity(mode, Z)
+
+    def publish(self, model):
+        modes = list(self.plan.array.modes)
+        model.array = self.plan.array
+        model.array_logs = {mode: np.vstack([self.plan.depths, self.slabs[0][:, k]]).T for k, mode in enumerate(modes)}
+        model.array_currents = {mode: self.slabs[1][:, k] for k, mode in enumerate(modes)}
+        model.array_impedances = self.slabs[2]
+
+
+class _ArraySensitivities(_ArrayOutput):
+    """dRa/dR of every table entry and dRa/dRm per mode: dy = sum_ij w_hat_i I_j dZ_ij (arrays.focus) with dZ_ij the pair derivative of
+    the right-hand sides of electrodes i and j, Ra = |K y / I0|; the table entries through geometry.resistivity_sensitivity as for the tools."""
+
+    def __init__(self, plan, windowing):
+        fm = plan.model.formation_model
+        self.plan, self.windowing = plan, windowing
+        self.slabs = [plan.slab(fm.shape[0], fm.shape[1] - 2), plan.slab()]
+        dip = plan.model.dip_rad
+        self.ti_normal = np.array([np.sin(dip), 0.0, np.cos(dip)]) if plan.dim == 3 else np.array([0.0, 1.0])   # geometry.ti_conductivity
+
+    def prepare(self, job):
+        job.entries, job.sigma = self.windowing.entries(job.bi, job.sigma)
+
+    def store(self, job):
+        p = self.plan
+        for di, Z, dZ in zip(job.depth_index, job.Z, job.dZ):
+            for k, mode in enumerate(p.array.modes):
+                mm = p.array.matrices(mode)
+                I, _, y, w_hat = arrays.focus(Z, mm)
+                G = sum(w_hat[i] * I[j] * d for (i, j), d in dZ.items() if w_hat[i] != 0.0 and I[j] != 0.0)
+                scale = np.sign(mm.K * y / mm.I0) * mm.K / mm.I0
+                self.slabs[0][di, k], dmud = geometry.resistivity_sensitivity(G, job.entries, p.model.formation_model, scale, self.ti_normal)
+                self.slabs[1][di, k] = dmud * (-1.0 / p.mud[job.bi] ** 2)
+
+    def publish(self, model):
+        modes = list(self.plan.array.modes)
+        model.array_sensitivities = {mode: self.slabs[0][:, k] for k, mode in enumerate(modes)}
+        model.array_mud_sensitivity = {mode: self.slabs[1][:, k] for k, mode in enumerate(modes)}
+
+
+class _ArrayRunner(_BatchRunner):
+    """Stage 5 for an array: per depth of the batch one right-hand side of unit current per electrode that some mode makes carry
+    current - with sensitivities also per read / null electrode: by reciprocity their solutions are the adjoint ones - each read at all
+    other electrodes of its depth; the pairs (read / null electrode, current electrode) give dZ (Context.solve_batch_pairs)."""
+
+    def run_batch(self, bi):
+        p, acc = self.plan, self.acc
+        batch, arr = p.batches[bi], p.array
+        try:
+            t0 = time.time()
+            fg, bh, sigma = self.windowing.window(bi)
+            job = types.SimpleNamespace(bi=bi, sigma=sigma, mesh=self.meshes.mesh(bi, fg, bh), depth_index=[s.records[0].depth_index for s in batch.solves])
+            m = len(arr.names)
+            cur, pot = np.flatnonzero(arr.current_electrodes), np.flatnonzero(arr.potential_electrodes)
+            active = sorted(set(cur) | (set(pot) if p.sensitivities else set()))
+            sources, evals, rhs_of = [], [], {}
+            for s, solve in enumerate(batch.solves):
+                z = solve.electrodes[0]
+                for i in active:
+                    rhs_of[(s, i)] = len(sources)
+                    sources.append((np.array([z[i]]), np.array([1.0])))
+                    evals.append(np.array([z[k] for k in range(m) if k != i]))
+            t1 = time.time()
+            opts = p.batch_opts(job.mesh)
+            for o in self.outputs:
+                o.prepare(job)
+            pairs = [(rhs_of[(s, i)], rhs_of[(s, j)]) for s in range(len(batch.solves)) for i in pot for j in cur] if p.sensitivities else []
+            c = self.free_ctx.get()
+            try:      # an array reads potentials, not differences: against infinity, not against the grounded surface of the batch mesh
+                outs, dP, st, rc = c.solve_batch_pairs(job.mesh, job.sigma, sources, evals, pairs, opts, far_field=float(p.domain_radius))
+            finally:
+                self.free_ctx.put(c)
+            t2 = time.time()
+            half = 0.5 if p.dim == 3 else 1.0      # the half ball with its sources in the symmetry plane: the potentials of 2 I
+            job.Z, job.dZ = [], []
+            for s in range(len(batch.solves)):
+                Z = np.full((m, m), np.nan)
+                for i in active:
+                    Z[[k for k in range(m) if k != i], i] = half * np.asarray(outs[rhs_of[(s, i)]])
+                job.Z.append(Z)
+                job.dZ.append({(i, j): half * dP[pairs.index((rhs_of[(s, i)], rhs_of[(s, j)]))] for i in pot for j in cur} if pairs else {})
+            for o in self.outputs:
+                o.store(job)
+            with self.lock:
+                acc["mesh"] += t1 - t0; acc["solve"] += t2 - t1; acc["points"] += len(batch.solves) * len(arr.modes)
+                acc["not_converged"] += int(rc == solver.REMO_NOT_CONVERGED); acc["pcg_steps"] += int(st.get("pcg_steps", 0))
+        except Exception as ex:
+            for o in self.outputs:      # any failure in a batch -> NaN for its depths
+                o.fail([(r.depth_index, r.tool_index) for s in batch.solves for r in s.records])
+            with self.lock:
+                acc["failed_batches"] += 1
+                if acc["first_error"] is None:
+                    acc["first_error"] = "batch {}: {}: {}".format(bi, type(ex).__name__, ex)
+                if isinstance(ex, (TypeError, AttributeError, NameError)) and acc["programming_error"] is None:
+                    acc["programming_error"] = ex
+
+
 class Model:
     conversion_table = CONVERSION
 
@@ -677,6 +818,12 @@ class Model:
         self.field_grid = None         # the grid of the last sections
         self.field_depth_index = None  # ... and the indices into measurement_depths they were kept for
         self.inversion = None          # invert_logs: what the last inversion found (inversion.invert_model)
+        self.array = None              # simulate_array_logs: the arrays.ElectrodeArray of the last array sweep
+        self.array_logs = None         # ... per mode [n_depths, 2] (depth, Ra)
+        self.array_currents = None     # ... per mode the electrode currents [n_depths, m]
+        self.array_impedances = None   # ... the transfer impedances [n_depths, m, m] in V / A, NaN where not measured
+        self.array_sensitivities = None    # simulate_array_logs(sensitivities=True): per mode dRa/dR [n_depths, n_layers, n_cols]
+        self.array_mud_sensitivity = None  # ... and dRa/dRm [n_depths]
         self.timing = {}
 
     # -- complete procedure (remo3d.py:65-174) ---------------------------------------------------
@@ -959,6 +1106,16 @@ class Model:
             reuse.begin(inversion.sweep_signature(plan))
         meshes = _MeshAhead(plan, windowing, bq, schedule, mesh_workers, reuse)
         runner = _BatchRunner(plan, windowing, meshes, outputs, reuse)
+
+        def reset():
+            self.sensitivities = self.mud_sensitivity = self.sensitivity_maps = self.sensitivity_map_rest = self.sensitivity_grid = None
+            self.field_sections = self.field_sources = self.field_source_x = self.field_grid = self.field_depth_index = None
+            self.error_estimates = self.error_maps = self.error_map_rest = self.error_grid = None
+        self._drive_and_report(plan, bq, meshes, runner, outputs, reset, schedule, start, verbose, reuse)
+
+    def _drive_and_report(self, plan, bq, meshes, runner, outputs, reset, schedule, start, verbose, reuse=None):
+        """The end of every sweep: the host threads, then - collectives, in this order on every rank - the slabs combined and
+        published (reset() clears what an earlier sweep of the same kind published) and self.timing."""
         t_busy = time.time()
         try:
             runner.drive()
@@ -970,9 +1127,7 @@ class Model:
         bq.check_complete()          # every batch was taken exactly once over the ranks
         for o in outputs:            # the same pattern for every slab: every rank has zeros outside its own records
             o.combine()
-        self.sensitivities = self.mud_sensitivity = self.sensitivity_maps = self.sensitivity_map_rest = self.sensitivity_grid = None
-        self.field_sections = self.field_sources = self.field_source_x = self.field_grid = self.field_depth_index = None
-        self.error_estimates = self.error_maps = self.error_map_rest = self.error_grid = None
+        reset()
         for o in outputs:
             o.publish(self)
         self.timing = dict(total_s=time.time() - start, mesh_s=acc["mesh"], solve_s=acc["solve"], points=acc["points"], batches=len(plan.batches),
@@ -989,6 +1144,40 @@ class Model:
             print("rank {}: PCG stopped at maxsteps in {} batches".format(sweep.rank(), acc["not_converged"]))
         if verbose and sweep.rank() == 0:
             print("\nProcessed in: ", datetime.timedelta(seconds=self.timing["total_s"]))
+
+    # -- electrode arrays and focused logs (no counterpart in the reference) -------------------------
+    def simulate_array_logs(self, array, measurement_depths, domain_radius=50, batch_size=1, preconditioner="multigrid", condense=True,
+                            mesh_provider: Optional[Callable] = None, mesh_scale: Optional[float] = None, rtol: float = 1e-8,
+                            maxsteps: int = 1000, verbose: bool = True, solver_options: Optional[dict] = None, sensitivities: bool = False):
+        """The logs of a multi-electrode array (arrays.ElectrodeArray; arrays.laterolog7() is the seven-electrode laterolog) in the
+        model of simulate_logs: 2D for dip 0, 3D otherwise; windowing, meshes, contexts, the NaN of a failed batch and self.timing as
+        there.  A batch holds batch_size consecutive depths; per depth every electrode that some mode makes carry current is one
+        right-hand side of unit current, read at all other electrodes: the transfer impedances, from which every mode's bucking
+        currents and reading follow (arrays.focus).  Fills self.array, self.array_logs[mode] [n_depths, 2] (depth, Ra),
+        self.array_currents[mode] [n_depths, m] and self.array_impedances [n_depths, m, m] (V / A, physical values against infinity -
+        solver.far_field_reference adds what the grounded surface of the batch mesh at domain_radius takes -, NaN where not measured).  sensitivities: also self.array_sensitivities[mode] [n_depths, n_layers, n_cols] and
+        self.array_mud_sensitivity[mode] [n_depths], with the meaning, units and NaN / 0 conventions of self.sensitivities and
+        self.mud_sensitivity - by reciprocity, from the pair derivatives of the forward solutions (the read / null electrodes become
+        right-hand sides too; no adjoint solves).  fp64 only.  Nothing simulate_logs publishes is touched, and the other way round."""
+        start = time.time()
+        if not isinstance(array, arrays.ElectrodeArray):
+            raise ValueError("array has to be an arrays.ElectrodeArray")
+        if (solver_options or {}).get("precision", "fp64") != "fp64":
+            raise ValueError("array logs are formed from fp64 solutions: precision has to be 'fp64'")
+        plan = _ArrayPlan(self, array, sensitivities, measurement_depths, domain_radius, batch_size, "auto", mesh_provider, mesh_scale,
+                          dict(preconditioner=preconditioner, condense=condense, rtol=rtol, maxsteps=maxsteps, precision="fp64"),
+                          solver_options, verbose)
+        windowing = _Windowing(plan)
+        outputs = [_ArrayLogs(plan)]
+        if sensitivities:
+            outputs.append(_ArraySensitivities(plan, windowing))
+        bq = sweep.BatchQueue(len(plan.batches), "static")
+        meshes = _MeshAhead(plan, windowing, bq, "static", None)
+        runner = _ArrayRunner(plan, windowing, meshes, outputs)
+
+        def reset():
+            self.array_sensitivities = self.array_mud_sensitivity = None
+        self._drive_and_report(plan, bq, meshes, runner, outputs, reset, "static", start, verbose)
 
     # -- inversion (no counterpart in the reference) -----------------------------------------------
     def invert_logs(self, observed, measurement_depths, free="RTUZ", **kw):

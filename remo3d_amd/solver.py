@@ -166,7 +166,13 @@ def _error_members(error, n_elems):
     return (int(group.max(initial=-1)) + 1 if n_group is None else int(n_group)), group
 
 
-def _batch_args(handle, mesh, sigma, sources, evals, job=False, secondary=None, error=None):
+def _pair_arrays(pairs):
+    """pairs: list of (a, b) right-hand sides -> (pair_a, pair_b) int32 arrays of remo_job_pairs_t."""
+    pairs = np.asarray(list(pairs), dtype=np.int64).reshape(-1, 2)
+    return np.ascontiguousarray(pairs[:, 0], dtype=np.int32), np.ascontiguousarray(pairs[:, 1], dtype=np.int32)
+
+
+def _batch_args(handle, mesh, sigma, sources, evals, job=False, secondary=None, error=None, pairs=None):
     """What every batch entry begins with (remo_solve_batch*, remo_solve_job, remo_batch_create*): [handle, mesh, job], the job a
     remo_job_t with the conductivity table, the sources and the evaluation points set.  Returns (args, sigma table, tensor?,
     eval_ptr, keep); keep holds what the pointers in the job look at.
@@ -174,13 +180,17 @@ def _batch_args(handle, mesh, sigma, sources, evals, job=False, secondary=None, 
     an entry that takes a list (_lib.legacy_args).
     secondary: dict(radius, sigma0, quad) - the job with the members of the secondary-potential formulation set (job is implied).
     error: True | dict(n_group, group) - the job with the members of the error estimates set (job is implied); the outputs err_out /
-    errg_out are the caller's to add."""
+    errg_out are the caller's to add.
+    pairs: list of (a, b) - a remo_job_pairs_t with the pairs set (job is implied); dP_out is the caller's to add.  Without the
+    keyword the job types and sizes are what they are without it."""
     error = None if error is False else error
-    job = job or secondary is not None or error is not None
+    job = job or secondary is not None or error is not None or pairs is not None
     sigma, tensor = sigma_table(sigma, int(mesh.dim))
     src_ptr, sz, sI, eval_ptr, ez = _rhs_arrays(sources, evals, int(mesh.dim) if job else 0)
     ms, keep = _lib.mesh_struct(mesh)
     Job = _lib.RemoJobError if error is not None else (_lib.RemoJob if secondary is None else _lib.RemoJobSecondary)
+    if pairs is not None:
+        Job = _lib.RemoJobPairs
     j = Job(size=C.sizeof(Job), tensor=int(tensor), n_mat=len(sigma), sigma=ptr(sigma, C.c_double), n_rhs=len(sources),
             src_ptr=ptr(src_ptr, C.c_int32), src_p=ptr(sz, C.c_double), src_I=ptr(sI, C.c_double),
             eval_ptr=ptr(eval_ptr, C.c_int32), eval_p=ptr(ez, C.c_double))
@@ -196,7 +206,11 @@ def _batch_args(handle, mesh, sigma, sources, evals, job=False, secondary=None, 
         j.err_n_group, eg = _error_members(error, keep[1].shape[0])
         if eg is not None:
             j.err_group = ptr(eg, C.c_int32)
-    return [handle, C.byref(ms), j], sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez, s0, eg)
+    pab = None
+    if pairs is not None:
+        pab = _pair_arrays(pairs)
+        j.n_pair, j.pair_a, j.pair_b = pab[0].size, ptr(pab[0], C.c_int32), ptr(pab[1], C.c_int32)
+    return [handle, C.byref(ms), j], sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez, s0, eg, pab)
 
 
 def _field_points(points, dim):
@@ -220,6 +234,50 @@ def _symmetric_gradient(dJ, d, tensor):
     G[:, :, iu[0], iu[1]] = dJ * half
     G[:, :, iu[1], iu[0]] = dJ * half
     return G
+
+
+def far_field_reference(mesh, sigma, radius):
+    """(c, dc): what the grounded surface of the mesh takes from the potential of a unit current, and its derivative.
+    The mesh is the ball (2D: its meridian half disc; 3D: the half ball y >= 0) of `radius` around the origin with u = 0 on the
+    surface; the medium goes on beyond it, and a potential meant against infinity lies higher by the current times the resistance
+    of the exterior.  With the exterior seen as radial current tubes that continue the conductivity at the surface, its conductance
+    is radius * integral of n . Sigma n over the solid angle, so c = 1 / (4 pi radius sigma_ext) with sigma_ext the mean of the radial
+    conductivity n . Sigma n over the Dirichlet facets, weighted by their solid angle.  Exact for a homogeneous ball up to
+    O(|a| |x| / radius^2) for a source at a and a reading at x; a constant for all readings, so differences of potentials do not see
+    it.  dc: [n_mat] for sigma [n_mat], the symmetric [n_mat, dim, dim] with d c = dc : dSigma for tensors (the convention of dJ)."""
+    d = int(mesh.dim)
+    sigma = np.asarray(sigma, dtype=np.float64)
+    coords, conn, mat = np.asarray(mesh.coords, dtype=np.float64), np.asarray(mesh.conn), np.asarray(mesh.mat)
+    bc = np.asarray(mesh.bconn).reshape(-1, d)[np.asarray(mesh.bdirichlet).astype(bool)]
+    if bc.shape[0] == 0 or not radius > 0.0:
+        raise ValueError("far_field needs a positive radius and a mesh with a Dirichlet surface")
+    on = np.zeros(coords.shape[0], dtype=bool)
+    on[bc.ravel()] = True
+    owner = {}      # facet (sorted vertices) -> the element behind it
+    for t in np.flatnonzero(on[conn].sum(axis=1) >= d):
+        v = conn[t]
+        for skip in range(d + 1):
+            f = np.delete(v, skip)
+            if on[f].all():
+                owner[tuple(sorted(int(i) for i in f))] = int(t)
+    m = mat[[owner[tuple(sorted(int(i) for i in f))] for f in bc]]
+    X = coords[bc]                                   # [nb, d, d]
+    xc = X.mean(axis=1)
+    n = xc / np.linalg.norm(xc, axis=1)[:, None]
+    if d == 2:      # a segment of the meridian, revolved
+        w = np.linalg.norm(X[:, 1] - X[:, 0], axis=1) * 2.0 * np.pi * np.abs(xc[:, 0])
+    else:
+        w = 0.5 * np.linalg.norm(np.cross(X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]), axis=1)
+    w = w / w.sum()
+    if sigma.ndim == 3:
+        G = np.zeros_like(sigma)
+        np.add.at(G, m, w[:, None, None] * n[:, :, None] * n[:, None, :])     # d sigma_ext / d Sigma_m
+        s_ext = float(np.sum(G * sigma))
+    else:
+        G = np.bincount(m, weights=w, minlength=sigma.shape[0]).astype(np.float64)
+        s_ext = float(G @ sigma)
+    c = 1.0 / (4.0 * np.pi * float(radius) * s_ext)
+    return c, -c / s_ext * G
 
 
 class WarmState:
@@ -294,16 +352,16 @@ class Context:
         return (self._L.remo_last_error(self._h) or b"").decode()
 
     def _one_shot(self, kind, mesh, sigma, sources, evals, opts, raise_on_error, functionals=None, groups=None, n_group=None, warm=None,
-                  points=None, field_rhs=None, secondary=None, error=None):
+                  points=None, field_rhs=None, secondary=None, error=None, pairs=None):
         """The one marshalling path of the one-shot entries remo_solve_batch<kind>[_tensor], kind "", "_sens", "_sens_warm", "_sens_groups"
         or "_field": the common arguments, then the functionals and the groups - or the field points - with their outputs where the kind
         has them.  Returns (potentials, [J, dJ, [dJg] | field dict,] stats, rc).
         Positions (of sources, evaluation points, functionals) are 1-D arrays of axis z or [m, dim] arrays of points; with one item
         of the second kind the job goes to remo_solve_job, every item as points; else its members, positions as axis z, are the
-        arguments of the kind's own symbol."""
+        arguments of the kind's own symbol.  pairs: list of (a, b) (remo_job_pairs_t, always remo_solve_job); dP follows the gradients."""
         error = None if error is False else error
-        job = secondary is not None or error is not None or _off_axis([z for (z, _) in sources], evals, [z for (_, z, _) in functionals] if functionals else [])
-        (handle, ms, j), sigma, tensor, eval_ptr, keep = _batch_args(self._h, mesh, sigma, sources, evals, job, secondary, error)
+        job = secondary is not None or error is not None or pairs is not None or _off_axis([z for (z, _) in sources], evals, [z for (_, z, _) in functionals] if functionals else [])
+        (handle, ms, j), sigma, tensor, eval_ptr, keep = _batch_args(self._h, mesh, sigma, sources, evals, job, secondary, error, pairs)
         d, nc = int(mesh.dim), (sigma.shape[1] if tensor else 1)
         out = np.full(int(eval_ptr[-1]), np.nan)
         j.u_out = ptr(out, C.c_double)
@@ -338,6 +396,9 @@ class Context:
                 if j.err_n_group > 0:
                     est.append(np.full((n_fun, j.err_n_group), np.nan))
                     j.errg_out = ptr(est[1], C.c_double)
+        if pairs is not None:
+            grads.append(np.full((int(j.n_pair), len(sigma), nc), np.nan))
+            j.dP_out = ptr(grads[-1], C.c_double)
         st = RemoStats()
         o = opts if opts is not None else make_opts()
         if not job:
@@ -393,6 +454,40 @@ class Context:
         (potentials, J, dJ, dJg, stats, rc); dJg is [n_fun, n_group] for sigma [n_mat] and [n_fun, n_group, dim, dim] for tensors,
         with the symmetric-G convention of dJ.  error: as for solve_batch_sens - E (and Eg) follow dJg in the result."""
         return self._one_shot("_sens_groups", mesh, sigma, sources, evals, opts, raise_on_error, functionals, groups, n_group, error=error)
+
+    def solve_batch_pairs(self, mesh, sigma, sources, evals, pairs, opts: Optional[RemoOpts] = None, raise_on_error=True, functionals=None,
+                          far_field=None):
+        """One-shot remo_solve_job with pairs (remo_job_pairs_t): the batch of solve_batch plus, for every pair (a, b) of right-hand
+        sides, dP = -u_a^T (dA/dsigma) u_b - by reciprocity the derivative of u_b read where the unit source of a sits (and the other
+        way round), with no adjoint solve: all transfer impedances of an electrode array and their derivatives from one solve per
+        electrode.  Returns (potentials, dP, stats, rc), or with functionals (as for solve_batch_sens)
+        (potentials, J, dJ, dP, stats, rc).  dP is [n_pair, n_mat] for sigma [n_mat] and the symmetric [n_pair, n_mat, dim, dim] for
+        tensors, with the convention of dJ.  Pairs may repeat, have a == b, and join any two right-hand sides of the batch.
+        far_field=R: the mesh is a ball of radius R around the origin whose surface is grounded, and the potentials are wanted
+        against infinity, as an array that reads potentials rather than differences needs them: every potential is raised by the
+        right-hand side's total current times far_field_reference's constant (twice that in the 3D half ball, whose potentials are
+        those of twice the current), and dP by the constant's derivative times both currents.  Not with functionals."""
+        if far_field is not None and functionals:
+            raise ValueError("far_field is not offered together with functionals")
+        out = self._one_shot("_sens", mesh, sigma, sources, evals, opts, raise_on_error, list(functionals) if functionals else [], pairs=list(pairs))
+        if functionals:
+            return out
+        potentials, dP, st, rc = (out[0],) + out[3:]
+        if far_field is not None and rc >= 0:
+            c, dc = far_field_reference(mesh, sigma, float(far_field))
+            k = 2.0 if int(mesh.dim) == 3 else 1.0
+            total = [float(np.sum(I)) for (_, I) in sources]
+            potentials = [u + k * total[r] * c for r, u in enumerate(potentials)]
+            if len(dP):
+                pa, pb = _pair_arrays(pairs)
+                dP = dP + (k * np.array(total)[pa] * np.array(total)[pb]).reshape((-1,) + (1,) * dc.ndim) * dc[None]
+        return potentials, dP, st, rc
+
+    def pairs_timing(self):
+        """(ms, element launches) of the pair pass of the last solve_batch_pairs on this context (remo_debug_pairs_timing)."""
+        out = np.zeros(2)
+        self._L.remo_debug_pairs_timing(self._h, ptr(out, C.c_double))
+        return float(out[0]), int(out[1])
 
     def solve_batch_field(self, mesh, sigma, sources, evals, points, field_rhs=None, opts: Optional[RemoOpts] = None, raise_on_error=True):
         """One-shot remo_solve_batch_field: the batch of solve_batch plus the solution away from the axis.  points: [n_pts, dim] in the
@@ -624,6 +719,21 @@ def host_field_element(dim: int, vertex_coords: np.ndarray, sigma, x_e, point) -
         rc = L.remo_host_field_element(dim, ptr(X, C.c_double), ptr(S, C.c_double), 0.0, ptr(xe, C.c_double), ptr(P, C.c_double), ptr(out, C.c_double))
     if rc != 0:
         raise RemoError(rc, "remo_host_field_element")
+    return out
+
+
+def host_pair_element(dim: int, vertex_coords: np.ndarray, x, pairs, tensor=False) -> np.ndarray:
+    """x_a^T (dK_e / d component) x_b of one element for the pairs (a, b) of the element vectors x [k, nld], from the moments of the
+    columns (remo_host_pair_element: the code the pair kernel runs).  Returns [n_pair, nc], nc = 1 or (tensor) 3 / 6."""
+    L = _lib.load()
+    X = np.ascontiguousarray(vertex_coords, dtype=np.float64)
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 10 if dim == 2 else 20)
+    pa, pb = _pair_arrays(pairs)
+    out = np.zeros((pa.size, (3 if dim == 2 else 6) if tensor else 1))
+    rc = L.remo_host_pair_element(dim, ptr(X, C.c_double), int(bool(tensor)), x.shape[0], ptr(x, C.c_double), pa.size, ptr(pa, C.c_int32),
+                                  ptr(pb, C.c_int32), ptr(out, C.c_double))
+    if rc != 0:
+        raise RemoError(rc, "remo_host_pair_element")
     return out
 
 
