@@ -444,6 +444,31 @@ typedef struct {
     const int32_t *pair_a, *pair_b;   /* [n_pair] right-hand sides */
     double *dP_out;                   /* [n_pair * n_mat * nc], pair-major */
 } remo_job_pairs_t;                   /* 320 bytes */
+/*
+ * pair_n_group > 0: PAIR DERIVATIVES PER GROUP OF ELEMENTS - the sensitivity maps of an electrode array (added within ABI 7: four
+ * members behind remo_job_pairs_t, which keeps its 320 bytes; set job.size = sizeof(remo_job_pair_groups_t) and hand
+ * &x.pairs.err.sec.job to remo_solve_job).  With u_a,e the element vector of right-hand side a = pair_a[p] on element e,
+ *     dPg_out[(p * pair_n_group + g) * nc + c] = -sum over the elements e with pair_group[e] = g of u_a,e^T (dK_e / d component c) u_b,e,
+ * components as in dP_out: with sigma_e = sigma_mat(e) + s_group(e) the derivative of the pair's transfer impedance with respect to
+ * s_g.  A group may mix materials, an empty group gets +0, an element with pair_group[e] = -1 is in no group; pair_n_group is
+ * bounded by memory only, and pair_group[e] = e gives the value of every element.  The grouping is the pairs' own, as err_group is
+ * the estimate's own: group / dJg_out may differ from it in the same job.  The element pass of the pairs runs a second time in a
+ * form that writes the value of every (pair, element); the elements are ordered by group once per job and every group's segment is
+ * added as remo_solve_batch_sens_groups adds it, for all pairs of a slice in one launch.  Every sum has a fixed order that depends
+ * only on the mesh, the grouping and the job (no floating-point atomics): with op = 2 two calls give the same bits of dPg_out.
+ * u_out, J_out, dJ_out, dJg_out, err_out and dP_out are exactly what the same job returns with pair_n_group = 0 (bit for bit with
+ * op = 2).  pair_n_group = 0: as before, bit for bit.
+ * Errors, REMO_ERR_ARG before any device work: pair_n_group < 0; pair_group_reserved != 0; pair_n_group > 0 with n_pair = 0, without
+ * pair_group or without dPg_out; a group id outside [-1, pair_n_group); and what pairs do not combine with.  On any negative return
+ * dPg_out is NaN-filled like the other outputs.  remo_batch_create_job refuses pair_n_group > 0.
+ */
+typedef struct {
+    remo_job_pairs_t pairs;
+    int32_t pair_n_group;             /* 0: as before, bit for bit */
+    int32_t pair_group_reserved;      /* must be 0 */
+    const int32_t *pair_group;        /* [mesh->n_elems], caller's element order, -1 = in no group */
+    double *dPg_out;                  /* [n_pair * pair_n_group * nc], pair-major */
+} remo_job_pair_groups_t;             /* 344 bytes */
 int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, const remo_opts_t *opts, remo_stats_t *stats);
 
 /*

@@ -71,6 +71,11 @@ int remo_debug_secondary_timing(remo_ctx_t *ctx, double *ms);
 /* The pair pass of the last job with remo_job_pairs_t.n_pair > 0 on this context: out2[0] = its time in ms (HIP events around the element
  * launches of all chunk pairs and the reduction), [1] = the number of element launches. */
 int remo_debug_pairs_timing(remo_ctx_t *ctx, double *out2);
+/* The group path of the last job with remo_job_pair_groups_t.pair_n_group > 0 on this context, ms by HIP events: out4[0] = the ordering
+ * of the elements by group (upload, keys, sort, offsets), [1] = the per-element launches of all slices, [2] = their group sums - the
+ * two are told apart only with remo_opts_t.time_kernels (one synchronisation per slice), else [1] holds both and [2] = 0 -,
+ * [3] = the number of slices (one per-element launch and one batched group sum each).  Zeros when the last job had no pair groups. */
+int remo_debug_pair_groups_timing(remo_ctx_t *ctx, double *out4);
 
 /* Process-global knobs, two kinds.  Returns 0, or -1 for a key this build does not have.
  *
@@ -101,6 +106,9 @@ int remo_debug_pairs_timing(remo_ctx_t *ctx, double *out2);
  *       39 = 0, 25 = 0 and 22 = 0 imply fp64.  remo_debug_direction_bytes says which form the last run took.
  *   42  0 = the pair derivatives of remo_job_pairs_t by one launch of k_sens_contract per pair, both columns forward, instead of
  *       the fused pass of k_pair_contract (default 1; the same values to rounding - what the fused pass is measured against).
+ *   43  bytes of element values ev[pairs][elements][nc] one per-element launch of remo_job_pair_groups_t may write (0 = default,
+ *       128 MB; always one pair at least): a (chunk, chunk) set of pairs with more takes several slices.  The order of the additions
+ *       of a (pair, group) does not depend on the slice: the same bits at any setting.
  *   40  1 = the patch operator takes one element per lane: patches of 256 / k elements (k = right-hand sides of the batch);
  *       2 (default) = two elements per lane, one after the other, in fp64 solves with k >= 3: patches of 2 * (256 / k) elements
  *       (k_patch_apply ROUNDS = 2).  A batch whose largest such patch does not fit the tables or LDS gets the tables of 1.

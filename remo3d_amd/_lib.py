@@ -80,6 +80,13 @@ class RemoJobPairs(C.Structure):
                                         ("pair_b", C.POINTER(C.c_int32)), ("dP_out", C.POINTER(C.c_double))]
 
 
+class RemoJobPairGroups(C.Structure):
+    """remo_job_pair_groups_t: a remo_job_pairs_t with the four members of the pair derivatives per group of elements behind it (flat,
+    like RemoJobSecondary)."""
+    _fields_ = RemoJobPairs._fields_ + [("pair_n_group", C.c_int32), ("pair_group_reserved", C.c_int32), ("pair_group", C.POINTER(C.c_int32)),
+                                        ("dPg_out", C.POINTER(C.c_double))]
+
+
 # include/remo3d_hip.h: the drop-in boundary + inspection hooks of the parity tests
 EXPORTS = ["remo_abi_version", "remo_opts_default", "remo_ctx_create", "remo_ctx_destroy", "remo_last_error",
            "remo_solve_batch", "remo_solve_batch_tensor", "remo_solve_batch_sens", "remo_solve_batch_sens_tensor", "remo_solve_batch_sens_groups", "remo_solve_batch_sens_groups_tensor",
@@ -89,7 +96,7 @@ EXPORTS = ["remo_abi_version", "remo_opts_default", "remo_ctx_create", "remo_ctx
            "remo_host_element_matrix", "remo_host_element_matrix_tensor", "remo_host_sens_element", "remo_host_factor_error", "remo_host_symbolic",
            "remo_solve_job", "remo_batch_create_job", "remo_host_point_shapes", "remo_host_secondary_element", "remo_host_error_facet", "remo_host_pair_element"]
 # include/remo3d_hip_debug.h: probes and tuning knobs (tests, tools, bench.py's `box` record) - not part of the boundary
-DEBUG_EXPORTS = ["remo_debug_stream", "remo_debug_clock", "remo_debug_device", "remo_debug_cache_gather", "remo_debug_xcc", "remo_debug_tune", "remo_debug_patch_phases", "remo_debug_patch_phases_p", "remo_debug_grid_barrier", "remo_debug_sens_timing", "remo_debug_sens_group_timing", "remo_debug_field_timing", "remo_debug_point_location", "remo_debug_secondary_timing", "remo_debug_direction_bytes", "remo_debug_pairs_timing"]
+DEBUG_EXPORTS = ["remo_debug_stream", "remo_debug_clock", "remo_debug_device", "remo_debug_cache_gather", "remo_debug_xcc", "remo_debug_tune", "remo_debug_patch_phases", "remo_debug_patch_phases_p", "remo_debug_grid_barrier", "remo_debug_sens_timing", "remo_debug_sens_group_timing", "remo_debug_field_timing", "remo_debug_point_location", "remo_debug_secondary_timing", "remo_debug_direction_bytes", "remo_debug_pairs_timing", "remo_debug_pair_groups_timing"]
 
 # The argument lists of the entries that take one (remo_solve_batch<kind>[_tensor], remo_batch_create[_tensor]) as members of
 # RemoJob: ctx and mesh, JOB_HEAD, then the kind's members - for the solves followed by opts and stats.  load() derives the
@@ -144,7 +151,7 @@ def load():
     L.remo_warm_info.restype = C.c_int
     L.remo_warm_info.argtypes = [vp, i64p, ip, i64p, ip]
     L.remo_solve_job.restype = C.c_int
-    L.remo_solve_job.argtypes = [vp, C.POINTER(RemoMesh), vp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]     # the job: RemoJob, RemoJobSecondary, RemoJobError or RemoJobPairs
+    L.remo_solve_job.argtypes = [vp, C.POINTER(RemoMesh), vp, C.POINTER(RemoOpts), C.POINTER(RemoStats)]     # the job: RemoJob, RemoJobSecondary, RemoJobError, RemoJobPairs or RemoJobPairGroups
     L.remo_batch_create_job.restype = C.c_int
     L.remo_batch_create_job.argtypes = [vp, C.POINTER(RemoMesh), vp, C.POINTER(vp)]
     L.remo_host_point_shapes.restype = C.c_int
@@ -171,6 +178,8 @@ def load():
     L.remo_host_pair_element.argtypes = [C.c_int32, dp, C.c_int32, C.c_int32, dp, C.c_int32, ip, ip, dp]
     L.remo_debug_pairs_timing.restype = C.c_int
     L.remo_debug_pairs_timing.argtypes = [vp, dp]
+    L.remo_debug_pair_groups_timing.restype = C.c_int
+    L.remo_debug_pair_groups_timing.argtypes = [vp, dp]
     L.remo_host_sens_element.restype = C.c_int
     L.remo_host_sens_element.argtypes = [C.c_int32, dp, C.c_int32, dp, dp, dp]
     L.remo_debug_sens_timing.restype = C.c_int

@@ -126,6 +126,13 @@ struct Plan {
     size_t arena_bytes = 0;
 };
 
+// pairs one per-element launch takes: what the budget of element values holds (remo_debug_tune key 43), one at least
+int pair_ev_pairs(int64_t nt, int ncomp, int n_pair) {
+    const size_t budget = g_tune.pair_ev_bytes > 0 ? size_t(g_tune.pair_ev_bytes) : kPairEvBytes;
+    const size_t per_pair = size_t(std::max<int64_t>(nt, 1)) * size_t(ncomp) * 8;
+    return int(std::max<size_t>(1, std::min<size_t>({budget / per_pair, size_t(std::max(n_pair, 1)), size_t(kPairEvMaxPairs)})));
+}
+
 // Upper bounds of everything the stages take, in the order they take it.  (Generous in places - e.g. the squared, compact and
 // fixed-width images are never all built for one batch - and meant to stay as it is: reserve() only ever grows the arena.)
 size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, int npts) {
@@ -181,6 +188,15 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
     }
     if (b->pairs)   // pair derivatives (pairs_take): slots; part, d_dP (+ the alignment of these takes)
         need += size_t(b->pairs->n_pair) * 8 + size_t(b->pairs->n_pair) * size_t(b->n_mat) * size_t(b->sigma_comp) * 8 * (size_t(pair_grid(nt)) + 1) + 4 * 256;
+    if (b->pairs && b->pairs->n_group > 0) {   // ... per group of elements: the ordering of their own, one slice's element values, every pair's sums
+        const size_t ng = size_t(b->pairs->n_group), ncomp = size_t(b->sigma_comp), npair = size_t(b->pairs->n_pair);
+        const size_t slice = size_t(pair_ev_pairs(nt, b->sigma_comp, b->pairs->n_pair));
+        need += npair * 8;                                                                            // gslots
+        need += size_t(nt) * 4 * 5 + (ng + 2) * 4;                                                    // d_group, keys_in, ids, keys, perm; off
+        need += sens_group_sort_bytes(nt, b->pairs->n_group) + 256;                                   // rocPRIM's temporary storage
+        need += slice * (size_t(nt) * ncomp * 8 + size_t(sens_group_chunks(nt)) * 2 * ncomp * 8);     // ev, cpart of a slice
+        need += npair * ng * ncomp * 8 + 16 * 256;                                                    // d_dPg (+ the alignment of these takes)
+    }
     if (o.precision == 1) {   // fp32 copies of the matrix values and of every PCG vector (mixed_buffers)
         need += size_t(nv + 64) * 200 * 8;                           // fp32 sq_a, sq_b
         need += size_t(nnz_max) * 4;                                 // v32
@@ -1028,6 +1044,15 @@ struct Pairs {
     int32_t *d_slots = nullptr;   // two staged-column slots per pair, in the order the launches take the pairs
     double *part = nullptr, *d_dP = nullptr;
     int grid = 0, nmc = 0;
+    // remo_job_pair_groups_t: the slots of the per-element launches, the group ordering (buffers of its own, as ErrEst has), the
+    // element values and chunk sums of one slice of `slice` pairs, and every pair's sums
+    int32_t *d_gslots = nullptr;
+    int32_t *d_group = nullptr, *ids = nullptr, *perm = nullptr, *off = nullptr;
+    uint32_t *keys_in = nullptr, *keys = nullptr;
+    void *sort_tmp = nullptr;
+    size_t sort_bytes = 0;
+    int slice = 0;
+    double *ev = nullptr, *cpart = nullptr, *d_dPg = nullptr;
 };
 
 Pairs pairs_take(const Run &r) {
@@ -1039,12 +1064,27 @@ Pairs pairs_take(const Run &r) {
     pr.d_slots = r.ctx->take<int32_t>(2 * np);
     pr.part = r.ctx->take<double>(np * pr.grid * pr.nmc + 1);
     pr.d_dP = r.ctx->take<double>(np * pr.nmc + 1);
+    if (b->pairs->n_group > 0) {
+        const size_t nt = size_t(b->nt), ng = size_t(b->pairs->n_group), ncomp = size_t(b->sigma_comp);
+        pr.slice = pair_ev_pairs(b->nt, b->sigma_comp, b->pairs->n_pair);
+        pr.d_gslots = r.ctx->take<int32_t>(2 * np);
+        pr.d_group = r.ctx->take<int32_t>(nt); pr.keys_in = r.ctx->take<uint32_t>(nt); pr.ids = r.ctx->take<int32_t>(nt);
+        pr.keys = r.ctx->take<uint32_t>(nt); pr.perm = r.ctx->take<int32_t>(nt);
+        pr.off = r.ctx->take<int32_t>(ng + 2);
+        pr.sort_bytes = sens_group_sort_bytes(b->nt, b->pairs->n_group);
+        pr.sort_tmp = r.ctx->take<char>(pr.sort_bytes + 256);
+        pr.ev = r.ctx->take<double>(size_t(pr.slice) * nt * ncomp);
+        pr.cpart = r.ctx->take<double>(size_t(pr.slice) * size_t(sens_group_chunks(b->nt)) * 2 * ncomp);
+        pr.d_dPg = r.ctx->take<double>(np * ng * ncomp + 1);
+    }
     return pr;
 }
 
 // The pairs that join chunk ca with chunk cb go together: both blocks are staged once per element.  A launch keeps at most
 // kPairSliceAcc accumulators (always one pair), so a chunk pair with many pairs or materials takes several.  The launches take the
 // pairs in an order of their own; dP_out gets them back in the caller's.
+// With groups (remo_job_pair_groups_t) the same partition is walked once more, sliced by the bytes of element values a launch may
+// write: per slice one per-element launch and one batched group sum; dPg_out gets its rows back in the caller's order too.
 void pairs_contract(const Run &r, const System &sys, const DevicePoints &dp, const Points &pts, const Sens &sn, const Pairs &pr) {
     remo_ctx *ctx = r.ctx;
     const remo_batch *b = r.b;
@@ -1052,42 +1092,47 @@ void pairs_contract(const Run &r, const System &sys, const DevicePoints &dp, con
     const DeviceSymbolic &sy = b->sym;
     hipStream_t s = r.s;
     const double *tab = sens_tables(r, sys);
-    const int np = rq->n_pair, nchunk = pts.forward_chunks, per_launch = std::max(1, kPairSliceAcc / std::max(1, pr.nmc));
+    const int np = rq->n_pair, nchunk = pts.forward_chunks;
     struct Launch { PairColumns pc; int first, count; };
-    std::vector<Launch> launches;
-    std::vector<int32_t> order, slots;   // order[i]: the caller's index of the pair at position i
-    for (int ca = 0; ca < nchunk; ++ca)
-        for (int cb = ca; cb < nchunk; ++cb) {
-            std::vector<int32_t> mine;
-            for (int p = 0; p < np; ++p) {
-                const int a = rq->pair_a[p] / REMO_MAX_RHS, c = rq->pair_b[p] / REMO_MAX_RHS;
-                if (std::min(a, c) == ca && std::max(a, c) == cb) mine.push_back(p);
-            }
-            for (size_t i0 = 0; i0 < mine.size(); i0 += size_t(per_launch)) {
-                Launch L{};
-                L.first = int(order.size());
-                L.count = int(std::min(mine.size() - i0, size_t(per_launch)));
-                const int chunks[2] = {ca, cb};
-                for (int i = 0; i < 2; ++i) {
-                    L.pc.x[i] = sn.block(sys.n, b->n_rhs, false, chunks[i]);
-                    L.pc.k[i] = std::min(b->n_rhs - chunks[i] * REMO_MAX_RHS, REMO_MAX_RHS);
-                    L.pc.q0[i] = pts.chunk_begin[chunks[i]];
-                    L.pc.nq[i] = pts.chunk_begin[chunks[i] + 1] - L.pc.q0[i];
+    // the launches of the (chunk, chunk) partition with at most per_launch pairs each; order[i]: the caller's index of the pair at
+    // position i (the same for every per_launch: a set's pairs stay in the caller's order)
+    auto partition = [&](int per_launch, std::vector<Launch> &launches, std::vector<int32_t> &order, std::vector<int32_t> &slots) {
+        for (int ca = 0; ca < nchunk; ++ca)
+            for (int cb = ca; cb < nchunk; ++cb) {
+                std::vector<int32_t> mine;
+                for (int p = 0; p < np; ++p) {
+                    const int a = rq->pair_a[p] / REMO_MAX_RHS, c = rq->pair_b[p] / REMO_MAX_RHS;
+                    if (std::min(a, c) == ca && std::max(a, c) == cb) mine.push_back(p);
                 }
-                int slot_of[kPairMaxCols];
-                std::fill(slot_of, slot_of + kPairMaxCols, -1);
-                for (int i = 0; i < L.count; ++i) {
-                    const int p = mine[i0 + size_t(i)];
-                    order.push_back(p);
-                    for (const int rhs : {rq->pair_a[p], rq->pair_b[p]}) {
-                        const int key = ((rhs / REMO_MAX_RHS == ca) ? 0 : 8) + rhs % REMO_MAX_RHS;   // block and column (ca == cb: block 0)
-                        if (slot_of[key] < 0) { slot_of[key] = L.pc.ncol; L.pc.col[L.pc.ncol++] = int8_t(key); }
-                        slots.push_back(slot_of[key]);
+                for (size_t i0 = 0; i0 < mine.size(); i0 += size_t(per_launch)) {
+                    Launch L{};
+                    L.first = int(order.size());
+                    L.count = int(std::min(mine.size() - i0, size_t(per_launch)));
+                    const int chunks[2] = {ca, cb};
+                    for (int i = 0; i < 2; ++i) {
+                        L.pc.x[i] = sn.block(sys.n, b->n_rhs, false, chunks[i]);
+                        L.pc.k[i] = std::min(b->n_rhs - chunks[i] * REMO_MAX_RHS, REMO_MAX_RHS);
+                        L.pc.q0[i] = pts.chunk_begin[chunks[i]];
+                        L.pc.nq[i] = pts.chunk_begin[chunks[i] + 1] - L.pc.q0[i];
                     }
+                    int slot_of[kPairMaxCols];
+                    std::fill(slot_of, slot_of + kPairMaxCols, -1);
+                    for (int i = 0; i < L.count; ++i) {
+                        const int p = mine[i0 + size_t(i)];
+                        order.push_back(p);
+                        for (const int rhs : {rq->pair_a[p], rq->pair_b[p]}) {
+                            const int key = ((rhs / REMO_MAX_RHS == ca) ? 0 : 8) + rhs % REMO_MAX_RHS;   // block and column (ca == cb: block 0)
+                            if (slot_of[key] < 0) { slot_of[key] = L.pc.ncol; L.pc.col[L.pc.ncol++] = int8_t(key); }
+                            slots.push_back(slot_of[key]);
+                        }
+                    }
+                    launches.push_back(L);
                 }
-                launches.push_back(L);
             }
-        }
+    };
+    std::vector<Launch> launches;
+    std::vector<int32_t> order, slots;
+    partition(std::max(1, kPairSliceAcc / std::max(1, pr.nmc)), launches, order, slots);
     HIP_TRY(hipEventRecord(ctx->ev[4], s));
     const bool fused = g_tune.pairs_fused != 0;
     const int grid = fused ? pr.grid : sens_grid(b->nt);   // (sens_grid <= pair_grid: part holds either)
@@ -1121,6 +1166,55 @@ void pairs_contract(const Run &r, const System &sys, const DevicePoints &dp, con
     (void)hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]);
     ctx->pair_ms[0] = ms;
     ctx->pair_ms[1] = double(n_launch);
+    for (double &m : ctx->pair_group_ms) m = 0.0;
+    if (rq->n_group <= 0) return;
+    // ---- per group of elements (remo_job_pair_groups_t): the material launches above stay what they are (dP_out keeps its bits); the
+    // moments are formed once more by per-element launches, sliced by the bytes of ev, each followed by one batched group sum
+    const size_t ngc = size_t(rq->n_group) * size_t(b->sigma_comp), evs = size_t(b->nt) * size_t(b->sigma_comp);
+    HIP_TRY(hipEventRecord(ctx->ev[6], s));
+    HIP_TRY(hipMemcpyAsync(pr.d_group, rq->group, sizeof(int32_t) * size_t(b->nt), hipMemcpyHostToDevice, s));
+    sens_group_order(b->nt, pr.d_group, sy.eperm, rq->n_group, pr.keys_in, pr.ids, pr.keys, pr.perm, pr.off, pr.sort_tmp, pr.sort_bytes, s);
+    HIP_TRY(hipEventRecord(ctx->ev[7], s));
+    std::vector<Launch> slices;
+    std::vector<int32_t> gorder, gslots;
+    partition(pr.slice, slices, gorder, gslots);
+    HIP_TRY(hipMemcpyAsync(pr.d_gslots, gslots.data(), sizeof(int32_t) * gslots.size(), hipMemcpyHostToDevice, s));
+    const bool split_times = r.o.time_kernels != 0;   // one synchronisation per slice: measuring runs only
+    hipEvent_t tev[3] = {};
+    if (split_times)
+        for (hipEvent_t &e : tev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(ctx->ev[4], s));
+    for (const Launch &L : slices) {
+        if (split_times) HIP_TRY(hipEventRecord(tev[0], s));
+        launch_pair_contract(r.dim, sy.condense, b->sigma_comp > 1, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, sy.eldof, sys.d_C, sys.d_M, tab, L.pc,
+                             L.count, pr.d_gslots + 2 * size_t(L.first), dp.d_prhs, dp.d_pI, dp.d_found, dp.d_fint, b->n_mat, pr.grid, pr.ev, s, true);
+        if (split_times) HIP_TRY(hipEventRecord(tev[1], s));
+        launch_sens_group_sum_batch(b->sigma_comp, b->nt, rq->n_group, pr.keys, pr.perm, pr.off, pr.ev, pr.cpart, pr.d_dPg + size_t(L.first) * ngc, L.count,
+                                    int64_t(evs), int64_t(ngc), s);
+        if (split_times) {
+            HIP_TRY(hipEventRecord(tev[2], s));
+            HIP_TRY(hipEventSynchronize(tev[2]));
+            for (int k = 0; k < 2; ++k) {
+                float e = 0;
+                (void)hipEventElapsedTime(&e, tev[k], tev[k + 1]);
+                ctx->pair_group_ms[1 + k] += e;
+            }
+        }
+    }
+    for (hipEvent_t e : tev)
+        if (e) (void)hipEventDestroy(e);
+    HIP_TRY(hipEventRecord(ctx->ev[5], s));
+    std::vector<double> hg(size_t(np) * ngc);
+    HIP_TRY(hipMemcpyAsync(hg.data(), pr.d_dPg, sizeof(double) * hg.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < np; ++i) std::memcpy(rq->dPg_out + size_t(gorder[size_t(i)]) * ngc, hg.data() + size_t(i) * ngc, sizeof(double) * ngc);
+    (void)hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]);
+    ctx->pair_group_ms[0] = ms;
+    if (!split_times) {
+        (void)hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]);
+        ctx->pair_group_ms[1] = ms;
+    }
+    ctx->pair_group_ms[3] = double(slices.size());
 }
 
 // ---- error estimates of the functionals (errest.hip) ------------------------------------------------------------------------------

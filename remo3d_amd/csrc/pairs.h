@@ -133,6 +133,10 @@ int pair_grid(int64_t nt);            // workgroups of every launch of a job (on
 void launch_pair_contract(int dim, bool condense, bool tensor, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat,
                           const int32_t *eperm, const int32_t *eldof, const double *C, const double *M, const double *tab, const PairColumns &pc,
                           int np, const int32_t *slots, const int32_t *pt_rhs, const double *pt_I, const int32_t *found, const double *fint, int nmat,
-                          int grid, double *part, hipStream_t s);
+                          int grid, double *part, hipStream_t s, bool per_elem = false);
+// per_elem: part = ev[np][nt][nc], the value of every (pair, device element) instead - every entry written, a dead element 0; no
+// material sums, no bound on np (the caller slices by the bytes of ev: kPairEvBytes)
+constexpr size_t kPairEvBytes = size_t(128) << 20;   // ev of one per-element launch (remo_debug_tune key 43); always one pair at least
+constexpr int kPairEvMaxPairs = 65535;                // pairs of one launch: the second grid dimension of the group sums
 
 }  // namespace remo

@@ -12,6 +12,11 @@
 //      accumulator - the scheme of k_sens_contract, no floating-point atomics.
 // The workgroups' accumulators go to part[pair][workgroup][material * component]; k_sens_reduce (sens.hip) adds them in index
 // order.  Every sum depends only on the mesh, the job and the grid.
+//
+// k_pair_contract<.., PER_ELEM = true> (remo_job_pair_groups_t): phases 0 and 1 as above; phase 2 writes the value of every (pair,
+// element) to ev[q][t][NC] - q the pair's position in the launch, t the device element - instead of scanning by material: lane =
+// (pair, element) with the element fastest, so a tile's values of one pair are one contiguous segment.  Every t < nt is written, a
+// dead element writes 0.  No accumulators, no span of materials, no value buffer in LDS; sens.hip's group sums read ev.
 #include <limits.h>
 
 #include "kernels.h"
@@ -40,7 +45,7 @@ __host__ __device__ inline int pair_elem_stride(int dim, int ncol) { return (nco
 
 // colbits: 4 bits per slot - bit 3 the block, bits 0 .. 2 the column in it (PairColumns::col, packed: a run-time index into a
 // kernel argument would send the array through scratch)
-template <int DIM, bool CONDENSE, bool TENSOR>
+template <int DIM, bool CONDENSE, bool TENSOR, bool PER_ELEM>
 __global__ void __launch_bounds__(kPairBlock) k_pair_contract(int64_t nt, const double *__restrict__ coords, const int32_t *__restrict__ conn,
                                                               const int32_t *__restrict__ mat, const int32_t *__restrict__ eperm,
                                                               const int32_t *__restrict__ eldof, const double *__restrict__ C,
@@ -54,20 +59,20 @@ __global__ void __launch_bounds__(kPairBlock) k_pair_contract(int64_t nt, const 
     constexpr int NTAB = (DIM == 2) ? 9 * N * N : 3 * 10 * N, CS = pair_col_stride<DIM>();
     constexpr int NGEO = 1 + DIM * DIM + (DIM == 2 ? 3 : 0);   // |T|, grad(l_a)[p], 2D: r_k
     __shared__ double s_tab[NTAB];
-    __shared__ double s_val[kPairBlock * NC];
+    __shared__ double s_val[PER_ELEM ? 1 : kPairBlock * NC];
     __shared__ double s_geo[kPairTileMax * NGEO];
     __shared__ int32_t s_mat[kPairTileMax];
     __shared__ int32_t s_range[2];
-    extern __shared__ double s_dyn[];   // moments [te][es], then the accumulators [np][nmat * NC]
-    const int tid = threadIdx.x, nmc = nmat * NC, es = pair_elem_stride(DIM, ncol);
+    extern __shared__ double s_dyn[];   // moments [te][es], then (!PER_ELEM) the accumulators [np][nmat * NC]
+    const int tid = threadIdx.x, nmc = PER_ELEM ? 0 : nmat * NC, es = pair_elem_stride(DIM, ncol);
     double *s_mom = s_dyn, *s_acc = s_dyn + te * es;
     for (int i = tid; i < NTAB; i += kPairBlock) s_tab[i] = tab[i];
     for (int i = tid; i < np * nmc; i += kPairBlock) s_acc[i] = 0.0;
     const int64_t ntiles = (nt + te - 1) / te;
     const int ppr = kPairBlock / te;   // pairs per round
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        if (tid == 0) { s_range[0] = INT_MAX; s_range[1] = -1; }
-        __syncthreads();   // (first tile: the tables; later tiles: the scan of the tile before)
+        if (!PER_ELEM && tid == 0) { s_range[0] = INT_MAX; s_range[1] = -1; }
+        __syncthreads();   // (first tile: the tables; later tiles: the scan / the pair values of the tile before)
         // ---- 0: the elements of the tile ------------------------------------------------------------------------------------
         if (tid < te) {
             const int64_t t = tile * te + tid;
@@ -96,7 +101,7 @@ __global__ void __launch_bounds__(kPairBlock) k_pair_contract(int64_t nt, const 
                 }
             }
             s_mat[tid] = m;
-            if (m >= 0) { atomicMin(&s_range[0], m); atomicMax(&s_range[1], m); }   // integer LDS atomics: the span of materials of the tile
+            if (!PER_ELEM && m >= 0) { atomicMin(&s_range[0], m); atomicMax(&s_range[1], m); }   // integer LDS atomics: the span of materials of the tile
         }
         __syncthreads();
         // ---- 1: moments of every (element, column) ------------------------------------------------------------------------------
@@ -131,6 +136,29 @@ __global__ void __launch_bounds__(kPairBlock) k_pair_contract(int64_t nt, const 
         }
         __syncthreads();
         // ---- 2: the pairs, a round at a time; sums per material in element order ----------------------------------------------------
+        if constexpr (PER_ELEM) {   // ... or every value to ev[q][t][NC] (part = ev): nothing in LDS is written, so no barrier between rounds
+            const int e = tid % te, pl = tid / te;
+            const int64_t t = tile * te + e;
+            if (pl < ppr && t < nt) {
+                const double *geo = s_geo + e * NGEO;
+                double g[DIM][DIM];
+#pragma unroll
+                for (int a = 0; a < DIM; ++a)
+#pragma unroll
+                    for (int q = 0; q < DIM; ++q) g[a][q] = geo[1 + a * DIM + q];
+                const bool live = s_mat[e] >= 0;
+                for (int p = pl; p < np; p += ppr) {
+                    double out[NC];
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) out[c] = 0.0;
+                    if (live) pair_value<DIM, TENSOR>(geo[0], g, s_mom + e * es + slots[2 * p] * CS, s_mom + e * es + slots[2 * p + 1] * CS, out);
+                    double *dst = part + (int64_t(p) * nt + t) * NC;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) dst[c] = out[c];
+                }
+            }
+            continue;
+        }
         const int m0 = s_range[0], span = s_range[1] - m0 + 1;   // (span <= 0: no live element in the tile)
         for (int p0 = 0; p0 < np; p0 += ppr) {
             const int e = tid % te, pl = tid / te, p = p0 + pl;
@@ -160,10 +188,12 @@ __global__ void __launch_bounds__(kPairBlock) k_pair_contract(int64_t nt, const 
             __syncthreads();
         }
     }
-    __syncthreads();
-    for (int i = tid; i < np * nmc; i += kPairBlock) {
-        const int p = i / nmc, mc = i - p * nmc;
-        part[(int64_t(p) * gridDim.x + blockIdx.x) * nmc + mc] = s_acc[i];
+    if constexpr (!PER_ELEM) {
+        __syncthreads();
+        for (int i = tid; i < np * nmc; i += kPairBlock) {
+            const int p = i / nmc, mc = i - p * nmc;
+            part[(int64_t(p) * gridDim.x + blockIdx.x) * nmc + mc] = s_acc[i];
+        }
     }
 }
 
@@ -184,23 +214,27 @@ int pair_grid(int64_t nt) {
 void launch_pair_contract(int dim, bool condense, bool tensor, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat,
                           const int32_t *eperm, const int32_t *eldof, const double *C, const double *M, const double *tab, const PairColumns &pc,
                           int np, const int32_t *slots, const int32_t *pt_rhs, const double *pt_I, const int32_t *found, const double *fint, int nmat,
-                          int grid, double *part, hipStream_t s) {
+                          int grid, double *part, hipStream_t s, bool per_elem) {
     const int nc = tensor ? (dim == 2 ? 3 : 6) : 1;
-    const size_t acc = sizeof(double) * size_t(np) * size_t(nmat) * nc;
+    const size_t acc = per_elem ? 0 : sizeof(double) * size_t(np) * size_t(nmat) * nc;
     const int te = pair_tile(dim, pc.ncol, acc);
     const size_t lds = sizeof(double) * size_t(te) * size_t(pair_elem_stride(dim, pc.ncol)) + acc;
     unsigned long long colbits = 0;
     for (int i = 0; i < pc.ncol; ++i) colbits |= (unsigned long long)(pc.col[i] & 15) << (4 * i);
-#define REMO_PAIR_LAUNCH(D, CO, TE) \
+#define REMO_PAIR_LAUNCH_(D, CO, TE, PE) \
     do { \
         static bool sized = false;   /* static + dynamic LDS pass 64 KB: the kernel is allowed them once */ \
         if (!sized) { \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pair_contract<D, CO, TE>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pair_contract<D, CO, TE, PE>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); \
             sized = true; \
         } \
-        hipLaunchKernelGGL((k_pair_contract<D, CO, TE>), dim3(grid), dim3(kPairBlock), lds, s, nt, coords, conn, mat, eperm, eldof, C, M, tab, pc.x[0], \
+        hipLaunchKernelGGL((k_pair_contract<D, CO, TE, PE>), dim3(grid), dim3(kPairBlock), lds, s, nt, coords, conn, mat, eperm, eldof, C, M, tab, pc.x[0], \
                            pc.x[1], pc.k[0], pc.k[1], pc.q0[0], pc.nq[0], pc.q0[1], pc.nq[1], pc.ncol, colbits, te, np, slots, pt_rhs, pt_I, found, fint, \
                            nmat, part); \
+    } while (0)
+#define REMO_PAIR_LAUNCH(D, CO, TE) \
+    do { \
+        if (per_elem) REMO_PAIR_LAUNCH_(D, CO, TE, true); else REMO_PAIR_LAUNCH_(D, CO, TE, false); \
     } while (0)
     if (dim == 3) {
         if (tensor) REMO_PAIR_LAUNCH(3, false, true); else REMO_PAIR_LAUNCH(3, false, false);
@@ -210,6 +244,7 @@ void launch_pair_contract(int dim, bool condense, bool tensor, int64_t nt, const
         if (tensor) REMO_PAIR_LAUNCH(2, false, true); else REMO_PAIR_LAUNCH(2, false, false);
     }
 #undef REMO_PAIR_LAUNCH
+#undef REMO_PAIR_LAUNCH_
 }
 
 }  // namespace remo

@@ -324,9 +324,21 @@ static void error_nan_fill(const remo_job_t &j, const remo_job_error_t &e) {
 }
 
 // the pairs of a job (remo_job_pairs_t), likewise: what they do not combine with, and their indices
-static int check_pairs(remo_ctx_t *ctx, const remo_job_t &j, const remo_job_pairs_t &x, unsigned parts, const remo_opts_t *opts) {
+static int check_pairs(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t &j, const remo_job_pair_groups_t &xg, unsigned parts,
+                       const remo_opts_t *opts) {
+    const remo_job_pairs_t &x = xg.pairs;
     if (x.n_pair < 0) return fail(ctx, REMO_ERR_ARG, "n_pair must not be negative");
     if (x.pair_reserved != 0) return fail(ctx, REMO_ERR_ARG, "remo_job_pairs_t.pair_reserved must be 0");
+    if (xg.pair_n_group < 0) return fail(ctx, REMO_ERR_ARG, "pair_n_group must not be negative");
+    if (xg.pair_group_reserved != 0) return fail(ctx, REMO_ERR_ARG, "remo_job_pair_groups_t.pair_group_reserved must be 0");
+    if (xg.pair_n_group > 0) {
+        if (x.n_pair == 0) return fail(ctx, REMO_ERR_ARG, "pair_n_group > 0 needs pairs: n_pair must be at least 1");
+        if (!xg.pair_group || !xg.dPg_out) return fail(ctx, REMO_ERR_ARG, "pair_n_group > 0 needs pair_group and dPg_out");
+        if (!mesh || mesh->n_elems <= 0) return fail(ctx, REMO_ERR_ARG, "empty mesh");
+        for (int64_t t = 0; t < mesh->n_elems; ++t)
+            if (xg.pair_group[t] < -1 || xg.pair_group[t] >= xg.pair_n_group)
+                return fail(ctx, REMO_ERR_ARG, "pair_group id of element " + std::to_string(t) + " outside [-1, pair_n_group)");
+    }
     if (x.n_pair == 0) return REMO_OK;
     if (!x.pair_a || !x.pair_b || !x.dP_out) return fail(ctx, REMO_ERR_ARG, "n_pair > 0 needs pair_a, pair_b and dP_out");
     if (x.err.sec.secondary) return fail(ctx, REMO_ERR_ARG, "pairs do not combine with the secondary formulation");
@@ -339,11 +351,15 @@ static int check_pairs(remo_ctx_t *ctx, const remo_job_t &j, const remo_job_pair
     return REMO_OK;
 }
 
-// dP_out as a negative return leaves it
-static void pairs_nan_fill(const remo_mesh_t *mesh, const remo_job_t &j, const remo_job_pairs_t &x) {
-    if (x.n_pair <= 0 || !x.dP_out || j.n_mat <= 0) return;
+// dP_out and dPg_out as a negative return leaves them
+static void pairs_nan_fill(const remo_mesh_t *mesh, const remo_job_t &j, const remo_job_pair_groups_t &xg) {
+    const remo_job_pairs_t &x = xg.pairs;
+    if (x.n_pair <= 0) return;
     const size_t ncomp = (j.tensor && mesh) ? ((mesh->dim == 2) ? 3 : 6) : 1;
-    for (size_t i = 0; i < size_t(x.n_pair) * size_t(j.n_mat) * ncomp; ++i) x.dP_out[i] = std::nan("");
+    if (x.dP_out && j.n_mat > 0)
+        for (size_t i = 0; i < size_t(x.n_pair) * size_t(j.n_mat) * ncomp; ++i) x.dP_out[i] = std::nan("");
+    if (xg.dPg_out && xg.pair_n_group > 0)
+        for (size_t i = 0; i < size_t(x.n_pair) * size_t(xg.pair_n_group) * ncomp; ++i) xg.dPg_out[i] = std::nan("");
 }
 
 // the field points of a job, likewise
@@ -366,7 +382,7 @@ static int check_field(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_
 // there (field.hip), builds the load vector of the secondary formulation (secondary.hip) - run, fetch, destroy.
 // full: src_p / eval_p / fun_p are full coordinates (remo_solve_job), else axis positions z (the remo_solve_batch* entries).
 static int solve_one(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t &j, const remo_job_secondary_t *sec, unsigned parts, bool full,
-                     const remo_opts_t *opts, remo_stats_t *stats, const remo_job_error_t *est = nullptr, const remo_job_pairs_t *prs = nullptr) {
+                     const remo_opts_t *opts, remo_stats_t *stats, const remo_job_error_t *est = nullptr, const remo_job_pair_groups_t *prs = nullptr) {
     if (!ctx) return REMO_ERR_ARG;
     // whatever goes wrong below, the object does not keep solutions of an earlier call (remo_batch_run labels it again on success)
     struct WarmGuard {
@@ -381,7 +397,7 @@ static int solve_one(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t 
     if (prs) pairs_nan_fill(mesh, j, *prs);
     std::vector<double> sigma0;
     int rc = est ? check_error(ctx, mesh, j, *est, parts, opts) : REMO_OK;
-    if (rc == REMO_OK && prs) rc = check_pairs(ctx, j, *prs, parts, opts);
+    if (rc == REMO_OK && prs) rc = check_pairs(ctx, mesh, j, *prs, parts, opts);
     if (rc != REMO_OK) return rc;
     rc = sec ? resolve_secondary(ctx, mesh, j, *sec, opts, sigma0) : REMO_OK;   // (refuses every other part, a warm object included)
     if (rc == REMO_OK && (parts & kFun)) rc = check_functionals(ctx, mesh, j, parts, full);
@@ -403,7 +419,11 @@ static int solve_one(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t 
         b->sens = &sens;
         b->warm = j.warm;
     }
-    const remo_pairs_request pairs{prs ? prs->n_pair : 0, prs ? prs->pair_a : nullptr, prs ? prs->pair_b : nullptr, prs ? prs->dP_out : nullptr};
+    remo_pairs_request pairs;
+    if (prs) {
+        pairs.n_pair = prs->pairs.n_pair; pairs.pair_a = prs->pairs.pair_a; pairs.pair_b = prs->pairs.pair_b; pairs.dP_out = prs->pairs.dP_out;
+        if (prs->pair_n_group > 0) { pairs.n_group = prs->pair_n_group; pairs.group = prs->pair_group; pairs.dPg_out = prs->dPg_out; }
+    }
     if (pairs.n_pair > 0) b->pairs = &pairs;   // (the entry has made a job with pairs a kFun job: the forward solutions stay for the pass)
     if (parts & kField) b->field = &field;
     if (sec) attach_secondary(b, *sec, sigma0);
@@ -529,15 +549,15 @@ int remo_solve_batch_field_tensor(remo_ctx_t *ctx, const remo_mesh_t *mesh, int3
 }
 
 // remo_solve_job / remo_batch_create_job: the job as this library knows it - the caller's leading `size` bytes, the rest zero.
-static int read_job(remo_ctx_t *ctx, const remo_job_t *job, remo_job_t &j, remo_job_pairs_t &x) {
+static int read_job(remo_ctx_t *ctx, const remo_job_t *job, remo_job_t &j, remo_job_pair_groups_t &x) {
     if (!ctx) return REMO_ERR_ARG;
     if (!job) return fail(ctx, REMO_ERR_ARG, "null job");
     const size_t size = job->size;
     if (size < offsetof(remo_job_t, n_fun)) return fail(ctx, REMO_ERR_ARG, "remo_job_t.size is smaller than the part every job has (through u_out)");
     std::memset(&j, 0, sizeof j);
     std::memset(&x, 0, sizeof x);
-    std::memcpy(&x, job, std::min(size, sizeof x));   // remo_job_pairs_t begins with a remo_job_error_t, that with a remo_job_secondary_t, that with a remo_job_t: one layout, four lengths
-    j = x.err.sec.job;
+    std::memcpy(&x, job, std::min(size, sizeof x));   // remo_job_pair_groups_t begins with a remo_job_pairs_t, that with a remo_job_error_t, that with a remo_job_secondary_t, that with a remo_job_t: one layout, five lengths
+    j = x.pairs.err.sec.job;
     const unsigned char *raw = reinterpret_cast<const unsigned char *>(job);
     for (size_t i = sizeof x; i < size; ++i)   // a newer caller: what this library does not know must not be asked for
         if (raw[i]) return fail(ctx, REMO_ERR_ARG, "remo_job_t.size is larger than this library's struct and the tail is not zero");
@@ -547,8 +567,9 @@ static int read_job(remo_ctx_t *ctx, const remo_job_t *job, remo_job_t &j, remo_
 
 int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, const remo_opts_t *opts, remo_stats_t *stats) {
     remo_job_t j;
-    remo_job_pairs_t xp;
-    int rc = read_job(ctx, job, j, xp);
+    remo_job_pair_groups_t xg;
+    int rc = read_job(ctx, job, j, xg);
+    const remo_job_pairs_t &xp = xg.pairs;
     const remo_job_error_t &xe = xp.err;
     const remo_job_secondary_t &x = xe.sec;
     const bool pairs = rc == REMO_OK && xp.n_pair > 0;   // (a job with pairs is a job with functionals, n_fun = 0 included: its solutions stay)
@@ -560,7 +581,7 @@ int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *j
         if (ctx && job && job->size >= offsetof(remo_job_t, n_fun)) {   // a job that could be read: its outputs as the entries leave them on an error
             job_nan_fill(mesh, j);
             error_nan_fill(j, xe);
-            pairs_nan_fill(mesh, j, xp);
+            pairs_nan_fill(mesh, j, xg);
             if (j.warm) remo_warm_clear(j.warm);
         }
         return rc;
@@ -570,14 +591,16 @@ int remo_solve_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *j
         job_nan_fill(mesh, j);
         return check_error(ctx, mesh, j, xe, parts, opts);
     }
-    return solve_one(ctx, mesh, j, x.secondary ? &x : nullptr, parts, true, opts, stats, &xe, &xp);
+    return solve_one(ctx, mesh, j, x.secondary ? &x : nullptr, parts, true, opts, stats, &xe, &xg);
 }
 
 int remo_batch_create_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_job_t *job, remo_batch_t **out) {
     remo_job_t j;
-    remo_job_pairs_t xp;
-    if (int rc = read_job(ctx, job, j, xp)) return rc;
+    remo_job_pair_groups_t xg;
+    if (int rc = read_job(ctx, job, j, xg)) return rc;
+    const remo_job_pairs_t &xp = xg.pairs;
     const remo_job_error_t &xe = xp.err;
+    if (xg.pair_n_group > 0) return fail(ctx, REMO_ERR_ARG, "remo_job_pair_groups_t.pair_n_group needs the solutions of a one-shot job: a resident batch keeps none (remo_solve_job)");
     const remo_job_secondary_t &x = xe.sec;
     if (xp.n_pair > 0) return fail(ctx, REMO_ERR_ARG, "remo_job_pairs_t.n_pair needs the solutions of a one-shot job: a resident batch keeps none (remo_solve_job)");
     if (xe.err != 0) return fail(ctx, REMO_ERR_ARG, "remo_job_error_t.err needs functionals: a resident batch has none (remo_solve_job)");

@@ -385,6 +385,7 @@ int remo_debug_tune(int32_t key, int32_t value) {
         case 39: g_tune.x_ev = value; return 0;              // one-shot solves: only the values of x the evaluation points read / the whole x
         case 41: g_tune.p32 = value; return 0;               // ... on the patch operator: the search direction stored in fp32 / in fp64
         case 42: g_tune.pairs_fused = value; return 0;       // pair derivatives: one fused element pass / one k_sens_contract launch per pair
+        case 43: g_tune.pair_ev_bytes = value; return 0;     // pair derivatives per group: bytes of element values per launch (slices)
         case 22: g_tune.defer_q = value; return 0;           // shared rows summed by k_patch_reduce / by the update launch
         case 24: g_tune.ell = value; return 0;               // fixed-width image of the vertex block
         case 40: set_patch_rounds(value); return 0;          // patch operator: two elements per lane where the patch fits its tables / one
@@ -436,6 +437,12 @@ int remo_debug_pairs_timing(remo_ctx_t *ctx, double *out2) {
     if (!ctx || !out2) return REMO_ERR_ARG;
     out2[0] = ctx->pair_ms[0];
     out2[1] = ctx->pair_ms[1];
+    return REMO_OK;
+}
+
+int remo_debug_pair_groups_timing(remo_ctx_t *ctx, double *out4) {
+    if (!ctx || !out4) return REMO_ERR_ARG;
+    for (int i = 0; i < 4; ++i) out4[i] = ctx->pair_group_ms[i];
     return REMO_OK;
 }
 

@@ -55,6 +55,7 @@ struct Tune {
     int dot_bins = 1;        // key 28 (probe builds): 1 = the patches add their <p, A p> straight into the update launch's rows (default), 0 = a row per patch + k_patch_dot
     int x_ev = 1;            // key 39: 1 = one-shot fp64 solves carry only the values of x the evaluation points read (default), 0 = the whole x
     int p32 = 1;             // key 41: 1 = those solves, on the patch operator, store the search direction in fp32 (default; PcgBuffersT::p32), 0 = in fp64
+    int pair_ev_bytes = 0;   // key 43: bytes of element values one per-element launch of remo_job_pair_groups_t writes (0 = kPairEvBytes; always one pair at least)
     int pairs_fused = 1;     // key 42: 1 = the pairs of remo_job_pairs_t in one fused element pass per chunk pair (default; k_pair_contract), 0 = one launch of k_sens_contract per pair
 #ifdef REMO_PROBES
     int extra_apply = 0;     // key 36 (probe builds): extra operator applications (apply + shared-row sums, results discarded) per PCG step: what a step with more applications would cost
@@ -94,6 +95,7 @@ struct remo_ctx {
     double sens_ms = 0.0, sens_bytes = 0.0;  // last remo_solve_batch_sens: HIP-event time and algorithmic bytes of the contraction launches (remo_debug_sens_timing)
     double sens_group_ms[4] = {};            // last remo_solve_batch_sens_groups: group order; with time_kernels also the material pass, the per-element pass and the group sums, each over all functionals (remo_debug_sens_group_timing)
     double pair_ms[2] = {};                  // last job with pairs: HIP-event time of the pair pass (element launches + reduction) and its launch count (remo_debug_pairs_timing)
+    double pair_group_ms[4] = {};            // last job with pair_n_group > 0: HIP-event time of the group order; of the per-element launches and of the group sums (apart only with time_kernels, else both in [1]); the number of slices (remo_debug_pair_groups_timing)
     double field_ms[2] = {};                 // last remo_solve_batch_field / remo_batch_field: HIP-event time of the location of the points and of the evaluation launches (remo_debug_field_timing)
     hipEvent_t fev[4] = {};                  // their events, created by the first use
     double sec_ms = 0.0;                     // last remo_batch_run with remo_job_secondary_t.secondary: HIP-event time of the load-vector launches, all chunks (remo_debug_secondary_timing)
@@ -172,6 +174,10 @@ struct remo_pairs_request {
     int n_pair = 0;
     const int32_t *pair_a = nullptr, *pair_b = nullptr;
     double *dP_out = nullptr;
+    // remo_job_pair_groups_t: the caller's group of every element (host array, checked by the entry) and where the sums per (pair, group) go
+    int32_t n_group = 0;
+    const int32_t *group = nullptr;
+    double *dPg_out = nullptr;
 };
 
 struct remo_warm;   // warm.h

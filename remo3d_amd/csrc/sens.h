@@ -124,5 +124,9 @@ void sens_group_order(int64_t nt, const int32_t *group, const int32_t *eperm, in
 // dJg[n_group][nc] = -(sum of ev over the group's segment), fixed order, every entry written (an empty group: 0)
 void launch_sens_group_sum(int nc, int64_t nt, int32_t n_group, const uint32_t *keys, const int32_t *perm, const int32_t *off, const double *ev,
                            double *cpart, double *dJg, hipStream_t s);
+// The same for nq functionals in one launch of either kernel (the pairs of a slice, pairs.h): the values of functional q at
+// ev + q * ev_stride, its sums to dJg + q * out_stride, cpart[nq][chunks][2][nc].  Per (q, group) the additions are those above.
+void launch_sens_group_sum_batch(int nc, int64_t nt, int32_t n_group, const uint32_t *keys, const int32_t *perm, const int32_t *off, const double *ev,
+                                 double *cpart, double *dJg, int nq, int64_t ev_stride, int64_t out_stride, hipStream_t s);
 
 }  // namespace remo

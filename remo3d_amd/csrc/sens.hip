@@ -157,11 +157,16 @@ __global__ void __launch_bounds__(256) k_sens_group_offsets(int64_t nt, int32_t 
 // One workgroup per chunk of kSensChunk sorted positions.  A segment longer than a chunk that meets this chunk holds the chunk's
 // first position (slot 0) or its last one (slot 1) - a third one would have to lie inside the chunk.  cpart[chunk][slot][NC]: the
 // sum of that segment's entries inside the chunk (0 where the slot has no long segment), every entry written.
+// blockIdx.y = q: one of several functionals (the pairs of a slice, pairs.h) on the same sorted list - ev and cpart of q lie
+// q * ev_stride and q * cpart_stride doubles on; the additions of every q are those of a launch of its own.
 template <int NC>
 __global__ void __launch_bounds__(256) k_sens_group_long(int64_t nt, int32_t n_group, const uint32_t *__restrict__ keys, const int32_t *__restrict__ perm,
-                                                         const int32_t *__restrict__ off, const double *__restrict__ ev, double *__restrict__ cpart) {
+                                                         const int32_t *__restrict__ off, const double *__restrict__ ev, double *__restrict__ cpart,
+                                                         int64_t ev_stride, int64_t cpart_stride) {
     __shared__ double s_w[4 * NC];
     const int tid = threadIdx.x;
+    ev += int64_t(blockIdx.y) * ev_stride;
+    cpart += int64_t(blockIdx.y) * cpart_stride;
     const int64_t p0 = int64_t(blockIdx.x) * kSensChunk, p1 = (p0 + kSensChunk < nt) ? p0 + kSensChunk : nt;
     const uint32_t gA = keys[p0], gB = keys[p1 - 1];
 #pragma unroll
@@ -198,10 +203,14 @@ __global__ void __launch_bounds__(256) k_sens_group_long(int64_t nt, int32_t n_g
 
 // W lanes per group: dJg[g][c] = -(sum of the group's segment).  Short segments: lane l adds the entries l, l + W, ... of the
 // segment; long ones: the chunk sums of k_sens_group_long in the same way.  Then the butterfly over the W lanes.
+// blockIdx.y = q as in k_sens_group_long; the sums of q go to dJg + q * out_stride.
 template <int NC, int W>
 __global__ void __launch_bounds__(256) k_sens_group_sum(int32_t n_group, const uint32_t *__restrict__ keys, const int32_t *__restrict__ perm,
                                                         const int32_t *__restrict__ off, const double *__restrict__ ev, const double *__restrict__ cpart,
-                                                        double *__restrict__ dJg) {
+                                                        double *__restrict__ dJg, int64_t ev_stride, int64_t cpart_stride, int64_t out_stride) {
+    ev += int64_t(blockIdx.y) * ev_stride;
+    cpart += int64_t(blockIdx.y) * cpart_stride;
+    dJg += int64_t(blockIdx.y) * out_stride;
     const int64_t gid = (int64_t(blockIdx.x) * 256 + threadIdx.x) / W;
     const int sub = threadIdx.x % W;
     const bool live = gid < n_group;   // (lanes behind the last group stay for the exchanges)
@@ -305,23 +314,31 @@ void sens_group_order(int64_t nt, const int32_t *group, const int32_t *eperm, in
     hipLaunchKernelGGL(k_sens_group_offsets, dim3(unsigned((int64_t(n_group) + 1 + 255) / 256)), dim3(256), 0, s, nt, n_group, keys, off);
 }
 
-void launch_sens_group_sum(int nc, int64_t nt, int32_t n_group, const uint32_t *keys, const int32_t *perm, const int32_t *off, const double *ev,
-                           double *cpart, double *dJg, hipStream_t s) {
+void launch_sens_group_sum_batch(int nc, int64_t nt, int32_t n_group, const uint32_t *keys, const int32_t *perm, const int32_t *off, const double *ev,
+                                 double *cpart, double *dJg, int nq, int64_t ev_stride, int64_t out_stride, hipStream_t s) {
     // lanes per group by the mean segment length (a property of the grouping: the order of the additions stays fixed)
     const int64_t mean = nt / (n_group > 0 ? n_group : 1);
     const int w = mean <= 8 ? 4 : (mean <= 128 ? 16 : 64);
     const unsigned nchunk = unsigned(sens_group_chunks(nt)), grid = unsigned((int64_t(n_group) * w + 255) / 256);
+    const int64_t cs = int64_t(nchunk) * 2 * nc;
+    if (nq <= 0 || nt <= 0) return;
 #define REMO_GROUP_LAUNCH(NC) \
     do { \
-        hipLaunchKernelGGL((k_sens_group_long<NC>), dim3(nchunk), dim3(256), 0, s, nt, n_group, keys, perm, off, ev, cpart); \
-        if (w == 4) hipLaunchKernelGGL((k_sens_group_sum<NC, 4>), dim3(grid), dim3(256), 0, s, n_group, keys, perm, off, ev, cpart, dJg); \
-        else if (w == 16) hipLaunchKernelGGL((k_sens_group_sum<NC, 16>), dim3(grid), dim3(256), 0, s, n_group, keys, perm, off, ev, cpart, dJg); \
-        else hipLaunchKernelGGL((k_sens_group_sum<NC, 64>), dim3(grid), dim3(256), 0, s, n_group, keys, perm, off, ev, cpart, dJg); \
+        hipLaunchKernelGGL((k_sens_group_long<NC>), dim3(nchunk, nq), dim3(256), 0, s, nt, n_group, keys, perm, off, ev, cpart, ev_stride, cs); \
+        if (grid == 0) break; \
+        if (w == 4) hipLaunchKernelGGL((k_sens_group_sum<NC, 4>), dim3(grid, nq), dim3(256), 0, s, n_group, keys, perm, off, ev, cpart, dJg, ev_stride, cs, out_stride); \
+        else if (w == 16) hipLaunchKernelGGL((k_sens_group_sum<NC, 16>), dim3(grid, nq), dim3(256), 0, s, n_group, keys, perm, off, ev, cpart, dJg, ev_stride, cs, out_stride); \
+        else hipLaunchKernelGGL((k_sens_group_sum<NC, 64>), dim3(grid, nq), dim3(256), 0, s, n_group, keys, perm, off, ev, cpart, dJg, ev_stride, cs, out_stride); \
     } while (0)
     if (nc == 1) REMO_GROUP_LAUNCH(1);
     else if (nc == 3) REMO_GROUP_LAUNCH(3);
     else REMO_GROUP_LAUNCH(6);
 #undef REMO_GROUP_LAUNCH
+}
+
+void launch_sens_group_sum(int nc, int64_t nt, int32_t n_group, const uint32_t *keys, const int32_t *perm, const int32_t *off, const double *ev,
+                           double *cpart, double *dJg, hipStream_t s) {
+    launch_sens_group_sum_batch(nc, nt, n_group, keys, perm, off, ev, cpart, dJg, 1, 0, 0, s);
 }
 
 }  // namespace remo

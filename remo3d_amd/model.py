@@ -730,10 +730,58 @@ class _ArraySensitivities(_ArrayOutput):
         model.array_mud_sensitivity = {mode: self.slabs[1][:, k] for k, mode in enumerate(modes)}
 
 
+class _ArrayMaps(_ArrayOutput):
+    """d ln Ra / d ln R per mode of every cell of the grid and of the rest pseudo-cell, as _Maps forms them for the tools: per group of
+    elements Gg = sum_ij w_hat_i I_j dZg_ij (arrays.focus; dZg the pair derivatives per group), the cell value
+    -(scale / Ra) * sum over the groups of the cell of sigma_g * Gg (tensors: sigma : Gg) with scale = sign(K y / I0) K / I0."""
+
+    @staticmethod
+    def lateral_axis(grid):
+        """'r' or 'x' of a well-formed grid (geometry.sensitivity_cells' rules; Model.simulate_array_logs asks before any batch is drawn)."""
+        lateral = [k for k in ("r", "x") if k in grid] if isinstance(grid, dict) else []
+        if len(lateral) != 1 or "z" not in grid:
+            raise ValueError("sensitivity_grid must hold the edges of 'z' and of one of 'r' and 'x'")
+        for e in (grid["z"], grid[lateral[0]]):
+            if np.ndim(e) != 1 or len(e) < 2 or np.any(np.diff(np.asarray(e, dtype=float)) <= 0):
+                raise ValueError("sensitivity_grid edges must be increasing, two at least")
+        return lateral[0]
+
+    def __init__(self, plan, grid):
+        self.plan, self.grid, self.lateral = plan, grid, self.lateral_axis(grid)
+        if self.lateral == "x" and plan.dim != 3:
+            raise ValueError("the 'x' axis exists in 3D only")
+        self.n_cells = (len(grid["z"]) - 1) * (len(grid[self.lateral]) - 1)
+        self.slabs = [plan.slab(self.n_cells + 1)]
+
+    def prepare(self, job):
+        job.groups, job.group_mat, job.group_cell = geometry.sensitivity_cells(job.mesh, None, self.grid, self.plan.simulation_depths[job.bi])
+
+    def store(self, job):
+        p = self.plan
+        sig = np.asarray(job.sigma, dtype=float)[job.group_mat]
+        for di, Z, dZg in zip(job.depth_index, job.Z, job.dZg):
+            for k, mode in enumerate(p.array.modes):
+                mm = p.array.matrices(mode)
+                I, _, y, w_hat = arrays.focus(Z, mm)
+                Gg = sum(w_hat[i] * I[j] * d for (i, j), d in dZg.items() if w_hat[i] != 0.0 and I[j] != 0.0)
+                Ra = abs(mm.K * y / mm.I0)
+                scale = np.sign(mm.K * y / mm.I0) * mm.K / mm.I0
+                w = sig * Gg if sig.ndim == 1 else np.sum(sig * Gg, axis=(1, 2))
+                self.slabs[0][di, k] = -(scale / Ra) * np.bincount(job.group_cell, weights=w, minlength=self.n_cells + 1)
+
+    def publish(self, model):
+        n, modes = self.n_cells, list(self.plan.array.modes)
+        shape = (len(self.plan.depths), len(self.grid["z"]) - 1, len(self.grid[self.lateral]) - 1)
+        model.array_sensitivity_maps = {mode: self.slabs[0][:, k, :n].reshape(shape) for k, mode in enumerate(modes)}
+        model.array_sensitivity_map_rest = {mode: self.slabs[0][:, k, n] for k, mode in enumerate(modes)}
+        model.sensitivity_grid = {k: np.asarray(v, dtype=float) for k, v in self.grid.items()}
+
+
 class _ArrayRunner(_BatchRunner):
     """Stage 5 for an array: per depth of the batch one right-hand side of unit current per electrode that some mode makes carry
     current - with sensitivities also per read / null electrode: by reciprocity their solutions are the adjoint ones - each read at all
-    other electrodes of its depth; the pairs (read / null electrode, current electrode) give dZ (Context.solve_batch_pairs)."""
+    other electrodes of its depth; the pairs (read / null electrode, current electrode) give dZ (Context.solve_batch_pairs), and with
+    the groups an output asked for (_ArrayMaps) also dZg per group of elements."""
 
     def run_batch(self, bi):
         p, acc = self.plan, self.acc
@@ -741,7 +789,8 @@ class _ArrayRunner(_BatchRunner):
         try:
             t0 = time.time()
             fg, bh, sigma = self.windowing.window(bi)
-            job = types.SimpleNamespace(bi=bi, sigma=sigma, mesh=self.meshes.mesh(bi, fg, bh), depth_index=[s.records[0].depth_index for s in batch.solves])
+            job = types.SimpleNamespace(bi=bi, sigma=sigma, mesh=self.meshes.mesh(bi, fg, bh), depth_index=[s.records[0].depth_index for s in batch.solves],
+                                        groups=None)
             m = len(arr.names)
             cur, pot = np.flatnonzero(arr.current_electrodes), np.flatnonzero(arr.potential_electrodes)
             active = sorted(set(cur) | (set(pot) if p.sensitivities else set()))
@@ -759,18 +808,24 @@ class _ArrayRunner(_BatchRunner):
             pairs = [(rhs_of[(s, i)], rhs_of[(s, j)]) for s in range(len(batch.solves)) for i in pot for j in cur] if p.sensitivities else []
             c = self.free_ctx.get()
             try:      # an array reads potentials, not differences: against infinity, not against the grounded surface of the batch mesh
-                outs, dP, st, rc = c.solve_batch_pairs(job.mesh, job.sigma, sources, evals, pairs, opts, far_field=float(p.domain_radius))
+                if job.groups is not None:
+                    outs, dP, dPg, st, rc = c.solve_batch_pairs(job.mesh, job.sigma, sources, evals, pairs, opts, far_field=float(p.domain_radius),
+                                                                groups=job.groups, n_group=len(job.group_mat))
+                else:
+                    outs, dP, st, rc = c.solve_batch_pairs(job.mesh, job.sigma, sources, evals, pairs, opts, far_field=float(p.domain_radius))
             finally:
                 self.free_ctx.put(c)
             t2 = time.time()
             half = 0.5 if p.dim == 3 else 1.0      # the half ball with its sources in the symmetry plane: the potentials of 2 I
-            job.Z, job.dZ = [], []
+            job.Z, job.dZ, job.dZg = [], [], []
             for s in range(len(batch.solves)):
                 Z = np.full((m, m), np.nan)
                 for i in active:
                     Z[[k for k in range(m) if k != i], i] = half * np.asarray(outs[rhs_of[(s, i)]])
                 job.Z.append(Z)
                 job.dZ.append({(i, j): half * dP[pairs.index((rhs_of[(s, i)], rhs_of[(s, j)]))] for i in pot for j in cur} if pairs else {})
+                if job.groups is not None:
+                    job.dZg.append({(i, j): half * dPg[pairs.index((rhs_of[(s, i)], rhs_of[(s, j)]))] for i in pot for j in cur})
             for o in self.outputs:
                 o.store(job)
             with self.lock:
@@ -824,6 +879,8 @@ class Model:
         self.array_impedances = None   # ... the transfer impedances [n_depths, m, m] in V / A, NaN where not measured
         self.array_sensitivities = None    # simulate_array_logs(sensitivities=True): per mode dRa/dR [n_depths, n_layers, n_cols]
         self.array_mud_sensitivity = None  # ... and dRa/dRm [n_depths]
+        self.array_sensitivity_maps = None      # simulate_array_logs(sensitivity_grid=...): per mode d ln Ra / d ln R of every grid cell [n_depths, n_z, n_r]
+        self.array_sensitivity_map_rest = None  # ... and of everything outside the grid [n_depths]; the grid is self.sensitivity_grid
         self.timing = {}
 
     # -- complete procedure (remo3d.py:65-174) ---------------------------------------------------
@@ -1148,7 +1205,8 @@ class Model:
     # -- electrode arrays and focused logs (no counterpart in the reference) -------------------------
     def simulate_array_logs(self, array, measurement_depths, domain_radius=50, batch_size=1, preconditioner="multigrid", condense=True,
                             mesh_provider: Optional[Callable] = None, mesh_scale: Optional[float] = None, rtol: float = 1e-8,
-                            maxsteps: int = 1000, verbose: bool = True, solver_options: Optional[dict] = None, sensitivities: bool = False):
+                            maxsteps: int = 1000, verbose: bool = True, solver_options: Optional[dict] = None, sensitivities: bool = False,
+                            sensitivity_grid: Optional[dict] = None):
         """The logs of a multi-electrode array (arrays.ElectrodeArray; arrays.laterolog7() is the seven-electrode laterolog) in the
         model of simulate_logs: 2D for dip 0, 3D otherwise; windowing, meshes, contexts, the NaN of a failed batch and self.timing as
         there.  A batch holds batch_size consecutive depths; per depth every electrode that some mode makes carry current is one
@@ -1158,25 +1216,36 @@ class Model:
         solver.far_field_reference adds what the grounded surface of the batch mesh at domain_radius takes -, NaN where not measured).  sensitivities: also self.array_sensitivities[mode] [n_depths, n_layers, n_cols] and
         self.array_mud_sensitivity[mode] [n_depths], with the meaning, units and NaN / 0 conventions of self.sensitivities and
         self.mud_sensitivity - by reciprocity, from the pair derivatives of the forward solutions (the read / null electrodes become
-        right-hand sides too; no adjoint solves).  fp64 only.  Nothing simulate_logs publishes is touched, and the other way round."""
+        right-hand sides too; no adjoint solves).  sensitivity_grid: dict(r=edges, z=edges), in 3D also x=edges instead of r, with the
+        meaning of simulate_logs' keyword: also self.array_sensitivity_maps[mode] [n_depths, n_z, n_r], d ln Ra / d ln R of every cell -
+        what the focused reading sees where -, self.array_sensitivity_map_rest[mode] [n_depths] for everything outside the grid (cells
+        and rest sum to 1) and self.sensitivity_grid; from the pair derivatives per group of elements (remo_job_pair_groups_t), with the
+        right-hand sides sensitivities=True adds, with or without that flag.  fp64 only.  Beyond self.sensitivity_grid nothing
+        simulate_logs publishes is touched, and the other way round."""
         start = time.time()
         if not isinstance(array, arrays.ElectrodeArray):
             raise ValueError("array has to be an arrays.ElectrodeArray")
         if (solver_options or {}).get("precision", "fp64") != "fp64":
             raise ValueError("array logs are formed from fp64 solutions: precision has to be 'fp64'")
-        plan = _ArrayPlan(self, array, sensitivities, measurement_depths, domain_radius, batch_size, "auto", mesh_provider, mesh_scale,
+        if sensitivity_grid is not None:
+            _ArrayMaps.lateral_axis(sensitivity_grid)
+        plan = _ArrayPlan(self, array, sensitivities or sensitivity_grid is not None, measurement_depths, domain_radius, batch_size, "auto", mesh_provider, mesh_scale,
                           dict(preconditioner=preconditioner, condense=condense, rtol=rtol, maxsteps=maxsteps, precision="fp64"),
                           solver_options, verbose)
         windowing = _Windowing(plan)
         outputs = [_ArrayLogs(plan)]
         if sensitivities:
             outputs.append(_ArraySensitivities(plan, windowing))
+        if sensitivity_grid is not None:
+            outputs.append(_ArrayMaps(plan, sensitivity_grid))
         bq = sweep.BatchQueue(len(plan.batches), "static")
         meshes = _MeshAhead(plan, windowing, bq, "static", None)
         runner = _ArrayRunner(plan, windowing, meshes, outputs)
 
         def reset():
-            self.array_sensitivities = self.array_mud_sensitivity = None
+            self.array_sensitivities = self.array_mud_sensitivity = self.array_sensitivity_maps = self.array_sensitivity_map_rest = None
+            if sensitivity_grid is not None:
+                self.sensitivity_grid = None
         self._drive_and_report(plan, bq, meshes, runner, outputs, reset, "static", start, verbose)
 
     # -- inversion (no counterpart in the reference) -----------------------------------------------

@@ -142,6 +142,16 @@ def plot_sensitivity_map(model, tool, depth_index, path=None):
     """One picture of model.sensitivity_maps[tool][depth_index] (Model.simulate_logs(sensitivity_grid=...)): d ln Ra / d ln R per
     cell as a pcolormesh on a symmetric-log colour scale, depth downwards, with the bed boundaries and the borehole wall drawn
     over it.  Returns the figure; `path`: also written there."""
+    return _draw_sensitivity_map(model, model.sensitivity_maps[tool][depth_index], tool, float(model.logs[tool][depth_index, 0]), path)
+
+
+def plot_array_sensitivity_map(model, mode, depth_index, path=None):
+    """The same picture of model.array_sensitivity_maps[mode][depth_index] (Model.simulate_array_logs(sensitivity_grid=...)): what the
+    mode of the array - a focused laterolog, say - sees where."""
+    return _draw_sensitivity_map(model, model.array_sensitivity_maps[mode][depth_index], mode, float(model.array_logs[mode][depth_index, 0]), path)
+
+
+def _draw_sensitivity_map(model, cells, name, depth, path):
     import matplotlib
     if not os.environ.get("MPLBACKEND") and not os.environ.get("DISPLAY"):
         matplotlib.use("Agg", force=False)
@@ -149,7 +159,7 @@ def plot_sensitivity_map(model, tool, depth_index, path=None):
     from matplotlib.colors import SymLogNorm
     grid = model.sensitivity_grid
     lateral = "x" if "x" in grid else "r"
-    m = np.asarray(model.sensitivity_maps[tool][depth_index], dtype=float)
+    m = np.asarray(cells, dtype=float)
     top = float(np.nanmax(np.abs(m))) if np.any(np.isfinite(m)) else 1.0
     top = top if top > 0 else 1.0
     fig, ax = plt.subplots(figsize=(5, 7))
@@ -165,7 +175,7 @@ def plot_sensitivity_map(model, tool, depth_index, path=None):
     ax.set_ylim(grid["z"][-1], grid["z"][0])
     ax.set_xlabel("{} [m]".format(lateral))
     ax.set_ylabel("depth [m]")
-    ax.set_title("{} at {:.2f} m: d ln Ra / d ln R".format(tool, float(model.logs[tool][depth_index, 0])))
+    ax.set_title("{} at {:.2f} m: d ln Ra / d ln R".format(name, depth))
     fig.colorbar(mesh, ax=ax)
     if path is not None:
         fig.savefig(path, dpi=120)

@@ -172,7 +172,17 @@ def _pair_arrays(pairs):
     return np.ascontiguousarray(pairs[:, 0], dtype=np.int32), np.ascontiguousarray(pairs[:, 1], dtype=np.int32)
 
 
-def _batch_args(handle, mesh, sigma, sources, evals, job=False, secondary=None, error=None, pairs=None):
+def _pair_group_arrays(pair_groups, n_elems):
+    """pair_groups: (group, n_group) -> (group int32 [n_elems], n_group) of remo_job_pair_groups_t.  group: ids in the order of
+    mesh.conn, -1 = in no group; n_group None: largest id + 1."""
+    group, n_group = pair_groups
+    group = np.ascontiguousarray(group, dtype=np.int32).ravel()
+    if group.size != n_elems:
+        raise ValueError("groups must hold one id per element")
+    return group, (int(group.max(initial=-1)) + 1 if n_group is None else int(n_group))
+
+
+def _batch_args(handle, mesh, sigma, sources, evals, job=False, secondary=None, error=None, pairs=None, pair_groups=None):
     """What every batch entry begins with (remo_solve_batch*, remo_solve_job, remo_batch_create*): [handle, mesh, job], the job a
     remo_job_t with the conductivity table, the sources and the evaluation points set.  Returns (args, sigma table, tensor?,
     eval_ptr, keep); keep holds what the pointers in the job look at.
@@ -182,7 +192,11 @@ def _batch_args(handle, mesh, sigma, sources, evals, job=False, secondary=None, 
     error: True | dict(n_group, group) - the job with the members of the error estimates set (job is implied); the outputs err_out /
     errg_out are the caller's to add.
     pairs: list of (a, b) - a remo_job_pairs_t with the pairs set (job is implied); dP_out is the caller's to add.  Without the
-    keyword the job types and sizes are what they are without it."""
+    keyword the job types and sizes are what they are without it.
+    pair_groups: (group, n_group) - a remo_job_pair_groups_t with the pairs' grouping set (needs pairs); dPg_out is the caller's to
+    add.  Without the keyword the job types and sizes are what they are without it."""
+    if pair_groups is not None and pairs is None:
+        raise ValueError("pair_groups needs pairs")
     error = None if error is False else error
     job = job or secondary is not None or error is not None or pairs is not None
     sigma, tensor = sigma_table(sigma, int(mesh.dim))
@@ -190,7 +204,7 @@ def _batch_args(handle, mesh, sigma, sources, evals, job=False, secondary=None, 
     ms, keep = _lib.mesh_struct(mesh)
     Job = _lib.RemoJobError if error is not None else (_lib.RemoJob if secondary is None else _lib.RemoJobSecondary)
     if pairs is not None:
-        Job = _lib.RemoJobPairs
+        Job = _lib.RemoJobPairs if pair_groups is None else _lib.RemoJobPairGroups
     j = Job(size=C.sizeof(Job), tensor=int(tensor), n_mat=len(sigma), sigma=ptr(sigma, C.c_double), n_rhs=len(sources),
             src_ptr=ptr(src_ptr, C.c_int32), src_p=ptr(sz, C.c_double), src_I=ptr(sI, C.c_double),
             eval_ptr=ptr(eval_ptr, C.c_int32), eval_p=ptr(ez, C.c_double))
@@ -210,7 +224,11 @@ def _batch_args(handle, mesh, sigma, sources, evals, job=False, secondary=None, 
     if pairs is not None:
         pab = _pair_arrays(pairs)
         j.n_pair, j.pair_a, j.pair_b = pab[0].size, ptr(pab[0], C.c_int32), ptr(pab[1], C.c_int32)
-    return [handle, C.byref(ms), j], sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez, s0, eg, pab)
+    pg = None
+    if pair_groups is not None:
+        pg, j.pair_n_group = _pair_group_arrays(pair_groups, keep[1].shape[0])
+        j.pair_group = ptr(pg, C.c_int32)
+    return [handle, C.byref(ms), j], sigma, tensor, eval_ptr, (ms, keep, src_ptr, sz, sI, ez, s0, eg, pab, pg)
 
 
 def _field_points(points, dim):
@@ -236,7 +254,7 @@ def _symmetric_gradient(dJ, d, tensor):
     return G
 
 
-def far_field_reference(mesh, sigma, radius):
+def far_field_reference(mesh, sigma, radius, groups=None, n_group=None):
     """(c, dc): what the grounded surface of the mesh takes from the potential of a unit current, and its derivative.
     The mesh is the ball (2D: its meridian half disc; 3D: the half ball y >= 0) of `radius` around the origin with u = 0 on the
     surface; the medium goes on beyond it, and a potential meant against infinity lies higher by the current times the resistance
@@ -244,7 +262,11 @@ def far_field_reference(mesh, sigma, radius):
     is radius * integral of n . Sigma n over the solid angle, so c = 1 / (4 pi radius sigma_ext) with sigma_ext the mean of the radial
     conductivity n . Sigma n over the Dirichlet facets, weighted by their solid angle.  Exact for a homogeneous ball up to
     O(|a| |x| / radius^2) for a source at a and a reading at x; a constant for all readings, so differences of potentials do not see
-    it.  dc: [n_mat] for sigma [n_mat], the symmetric [n_mat, dim, dim] with d c = dc : dSigma for tensors (the convention of dJ)."""
+    it.  dc: [n_mat] for sigma [n_mat], the symmetric [n_mat, dim, dim] with d c = dc : dSigma for tensors (the convention of dJ).
+    groups ([n_elems] ids in the order of mesh.conn, -1 = in no group; n_group: default largest id + 1): returns (c, dc, dcg) with dcg
+    [n_group] or [n_group, dim, dim], the same terms added by the group of the element behind each Dirichlet facet instead of by its
+    material - the derivative of c with respect to a conductivity added to the elements of a group; the facets of an element in no
+    group are dropped."""
     d = int(mesh.dim)
     sigma = np.asarray(sigma, dtype=np.float64)
     coords, conn, mat = np.asarray(mesh.coords, dtype=np.float64), np.asarray(mesh.conn), np.asarray(mesh.mat)
@@ -260,7 +282,8 @@ def far_field_reference(mesh, sigma, radius):
             f = np.delete(v, skip)
             if on[f].all():
                 owner[tuple(sorted(int(i) for i in f))] = int(t)
-    m = mat[[owner[tuple(sorted(int(i) for i in f))] for f in bc]]
+    behind = np.array([owner[tuple(sorted(int(i) for i in f))] for f in bc], dtype=np.int64)
+    m = mat[behind]
     X = coords[bc]                                   # [nb, d, d]
     xc = X.mean(axis=1)
     n = xc / np.linalg.norm(xc, axis=1)[:, None]
@@ -277,7 +300,20 @@ def far_field_reference(mesh, sigma, radius):
         G = np.bincount(m, weights=w, minlength=sigma.shape[0]).astype(np.float64)
         s_ext = float(G @ sigma)
     c = 1.0 / (4.0 * np.pi * float(radius) * s_ext)
-    return c, -c / s_ext * G
+    if groups is None:
+        return c, -c / s_ext * G
+    groups = np.ascontiguousarray(groups, dtype=np.int64).ravel()
+    if groups.size != conn.shape[0]:
+        raise ValueError("groups must hold one id per element")
+    n_group = int(groups.max(initial=-1)) + 1 if n_group is None else int(n_group)
+    g = groups[behind]
+    kept = g >= 0
+    if sigma.ndim == 3:
+        Gg = np.zeros((n_group, d, d))
+        np.add.at(Gg, g[kept], (w[:, None, None] * n[:, :, None] * n[:, None, :])[kept])
+    else:
+        Gg = np.bincount(g[kept], weights=w[kept], minlength=n_group).astype(np.float64)
+    return c, -c / s_ext * G, -c / s_ext * Gg
 
 
 class WarmState:
@@ -352,16 +388,17 @@ class Context:
         return (self._L.remo_last_error(self._h) or b"").decode()
 
     def _one_shot(self, kind, mesh, sigma, sources, evals, opts, raise_on_error, functionals=None, groups=None, n_group=None, warm=None,
-                  points=None, field_rhs=None, secondary=None, error=None, pairs=None):
+                  points=None, field_rhs=None, secondary=None, error=None, pairs=None, pair_groups=None):
         """The one marshalling path of the one-shot entries remo_solve_batch<kind>[_tensor], kind "", "_sens", "_sens_warm", "_sens_groups"
         or "_field": the common arguments, then the functionals and the groups - or the field points - with their outputs where the kind
         has them.  Returns (potentials, [J, dJ, [dJg] | field dict,] stats, rc).
         Positions (of sources, evaluation points, functionals) are 1-D arrays of axis z or [m, dim] arrays of points; with one item
         of the second kind the job goes to remo_solve_job, every item as points; else its members, positions as axis z, are the
-        arguments of the kind's own symbol.  pairs: list of (a, b) (remo_job_pairs_t, always remo_solve_job); dP follows the gradients."""
+        arguments of the kind's own symbol.  pairs: list of (a, b) (remo_job_pairs_t, always remo_solve_job); dP follows the gradients.
+        pair_groups: (group, n_group) of the pairs (remo_job_pair_groups_t); dPg follows dP."""
         error = None if error is False else error
         job = secondary is not None or error is not None or pairs is not None or _off_axis([z for (z, _) in sources], evals, [z for (_, z, _) in functionals] if functionals else [])
-        (handle, ms, j), sigma, tensor, eval_ptr, keep = _batch_args(self._h, mesh, sigma, sources, evals, job, secondary, error, pairs)
+        (handle, ms, j), sigma, tensor, eval_ptr, keep = _batch_args(self._h, mesh, sigma, sources, evals, job, secondary, error, pairs, pair_groups)
         d, nc = int(mesh.dim), (sigma.shape[1] if tensor else 1)
         out = np.full(int(eval_ptr[-1]), np.nan)
         j.u_out = ptr(out, C.c_double)
@@ -399,6 +436,9 @@ class Context:
         if pairs is not None:
             grads.append(np.full((int(j.n_pair), len(sigma), nc), np.nan))
             j.dP_out = ptr(grads[-1], C.c_double)
+        if pair_groups is not None:
+            grads.append(np.full((int(j.n_pair), max(int(j.pair_n_group), 0), nc), np.nan))
+            j.dPg_out = ptr(grads[-1], C.c_double)
         st = RemoStats()
         o = opts if opts is not None else make_opts()
         if not job:
@@ -456,7 +496,7 @@ class Context:
         return self._one_shot("_sens_groups", mesh, sigma, sources, evals, opts, raise_on_error, functionals, groups, n_group, error=error)
 
     def solve_batch_pairs(self, mesh, sigma, sources, evals, pairs, opts: Optional[RemoOpts] = None, raise_on_error=True, functionals=None,
-                          far_field=None):
+                          far_field=None, groups=None, n_group=None):
         """One-shot remo_solve_job with pairs (remo_job_pairs_t): the batch of solve_batch plus, for every pair (a, b) of right-hand
         sides, dP = -u_a^T (dA/dsigma) u_b - by reciprocity the derivative of u_b read where the unit source of a sits (and the other
         way round), with no adjoint solve: all transfer impedances of an electrode array and their derivatives from one solve per
@@ -466,21 +506,42 @@ class Context:
         far_field=R: the mesh is a ball of radius R around the origin whose surface is grounded, and the potentials are wanted
         against infinity, as an array that reads potentials rather than differences needs them: every potential is raised by the
         right-hand side's total current times far_field_reference's constant (twice that in the 3D half ball, whose potentials are
-        those of twice the current), and dP by the constant's derivative times both currents.  Not with functionals."""
+        those of twice the current), and dP by the constant's derivative times both currents.  Not with functionals.
+        groups ([n_elems] int, the group of every element of mesh.conn, -1: in no group; n_group: default largest id + 1): also
+        dPg[p, g] = -sum over the elements e of group g of u_a,e^T (dK_e/dsigma) u_b,e (remo_job_pair_groups_t) - with sigma_e =
+        sigma_mat(e) + s_group(e), dPg = dP/ds_g: the sensitivity maps of an array.  Returns (potentials, dP, dPg, stats, rc), with
+        functionals (potentials, J, dJ, dP, dPg, stats, rc); dPg is [n_pair, n_group], for tensors [n_pair, n_group, dim, dim].  With
+        far_field, dPg gets the constant's derivative per group (far_field_reference(groups=...)) as dP gets it per material."""
         if far_field is not None and functionals:
             raise ValueError("far_field is not offered together with functionals")
-        out = self._one_shot("_sens", mesh, sigma, sources, evals, opts, raise_on_error, list(functionals) if functionals else [], pairs=list(pairs))
+        pairs = list(pairs)
+        pg = None
+        if groups is not None:
+            groups = np.ascontiguousarray(groups, dtype=np.int32).ravel()
+            if groups.size != np.asarray(mesh.conn).shape[0]:
+                raise ValueError("groups must hold one id per element")
+            n_group = int(groups.max(initial=-1)) + 1 if n_group is None else int(n_group)
+            pg = (groups, n_group)
+        out = self._one_shot("_sens", mesh, sigma, sources, evals, opts, raise_on_error, list(functionals) if functionals else [], pairs=pairs,
+                             pair_groups=pg)
         if functionals:
             return out
-        potentials, dP, st, rc = (out[0],) + out[3:]
+        potentials, dP, st, rc = out[0], out[3], out[-2], out[-1]
+        dPg = out[4] if pg is not None else None
         if far_field is not None and rc >= 0:
-            c, dc = far_field_reference(mesh, sigma, float(far_field))
+            ref = far_field_reference(mesh, sigma, float(far_field), *(pg or ()))
+            c, dc = ref[0], ref[1]
             k = 2.0 if int(mesh.dim) == 3 else 1.0
             total = [float(np.sum(I)) for (_, I) in sources]
             potentials = [u + k * total[r] * c for r, u in enumerate(potentials)]
             if len(dP):
                 pa, pb = _pair_arrays(pairs)
-                dP = dP + (k * np.array(total)[pa] * np.array(total)[pb]).reshape((-1,) + (1,) * dc.ndim) * dc[None]
+                kII = (k * np.array(total)[pa] * np.array(total)[pb]).reshape((-1,) + (1,) * dc.ndim)
+                dP = dP + kII * dc[None]
+                if pg is not None:
+                    dPg = dPg + kII * ref[2][None]
+        if pg is not None:
+            return potentials, dP, dPg, st, rc
         return potentials, dP, st, rc
 
     def pairs_timing(self):
@@ -488,6 +549,14 @@ class Context:
         out = np.zeros(2)
         self._L.remo_debug_pairs_timing(self._h, ptr(out, C.c_double))
         return float(out[0]), int(out[1])
+
+    def pair_groups_timing(self):
+        """(ms of the ordering by group, ms of the per-element launches, ms of the group sums, slices) of the group path of the last
+        solve_batch_pairs(groups=...) on this context (remo_debug_pair_groups_timing); the two middle ones are told apart only with
+        make_opts(time_kernels=True), else the first of them holds both."""
+        out = np.zeros(4)
+        self._L.remo_debug_pair_groups_timing(self._h, ptr(out, C.c_double))
+        return float(out[0]), float(out[1]), float(out[2]), int(out[3])
 
     def solve_batch_field(self, mesh, sigma, sources, evals, points, field_rhs=None, opts: Optional[RemoOpts] = None, raise_on_error=True):
         """One-shot remo_solve_batch_field: the batch of solve_batch plus the solution away from the axis.  points: [n_pts, dim] in the

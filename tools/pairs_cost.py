@@ -8,6 +8,13 @@ Writes profiles/pairs_cost.json and prints it.
 
     python tools/pairs_cost.py [--size L] [--batch 20] [--reps 3]
 
+--groups: what the pair derivatives per group of elements (remo_job_pair_groups_t) cost on the same batch instead - the seven
+electrodes, the 12 pairs (monitor, current electrode) Model.simulate_array_logs asks for, and two groupings: the (material, cell)
+groups of an 8192-cell grid (geometry.sensitivity_cells, 128 z x 64 r) and group = arange(n_elems), the per-element map.  Per
+grouping the ordering by group, the per-element launches and the group sums (HIP events of remo_debug_pair_groups_timing, from
+calls with time_kernels) and the whole call (host clock around the call, calls without time_kernels) against the same call
+without groups, alternating.  Writes profiles/pair_groups_cost.json.
+
 The GPU work runs in a child process under its own time limit."""
 import argparse
 import json
@@ -67,20 +74,66 @@ def measure(size, bi, reps):
     print(json.dumps(out), flush=True)
 
 
+def measure_groups(size, bi, reps):
+    import time
+    import numpy as np
+    import bench
+    from remo3d_amd import arrays, geometry, solver
+    w = bench._build_some((100, bench.SIZES[size], "lattice", [bi]))[0]
+    mesh, sigma = w["mesh"], w["sigma"]
+    arr = arrays.laterolog7()
+    z0 = float(np.atleast_1d(np.asarray(w["sources"][0][0], dtype=float))[0])
+    z = z0 + arr.offsets
+    m = len(z)
+    src = [([z[i]], [1.0]) for i in range(m)]
+    ev = [[z[k] for k in range(m) if k != i] for i in range(m)]
+    pairs = [(i, j) for i in np.flatnonzero(arr.potential_electrodes) for j in np.flatnonzero(arr.current_electrodes)]
+    n = int(mesh.conn.shape[0])
+    grid = dict(z=np.linspace(z0 - 16.0, z0 + 16.0, 129), r=np.concatenate([[0.0], np.geomspace(0.05, 50.0, 64)]))
+    cells, gmat, _ = geometry.sensitivity_cells(mesh, None, grid)
+    groupings = {"grid_8192_cells": (cells, len(gmat)), "per_element": (np.arange(n, dtype=np.int32), n)}
+    o, ot = solver.make_opts(), solver.make_opts(time_kernels=True)
+    out = dict(size=size, batch=bi, elements=n, n_rhs=m, n_pair=len(pairs), n_mat=int(np.asarray(sigma).shape[0]), reps=reps)
+    with solver.Context(0) as ctx:
+        ctx.solve_batch_pairs(mesh, sigma, src, ev, pairs, o)      # warm-up: arena, code objects
+        for name, (group, n_group) in groupings.items():
+            ctx.solve_batch_pairs(mesh, sigma, src, ev, pairs, o, groups=group, n_group=n_group)      # ... of the group path, at this size
+            plain, grouped, parts, pass_ms = [], [], [], []
+            for _ in range(reps):
+                t0 = time.perf_counter(); r0 = ctx.solve_batch_pairs(mesh, sigma, src, ev, pairs, o); plain.append(time.perf_counter() - t0)
+                pass_ms.append(ctx.pairs_timing()[0])
+                t0 = time.perf_counter(); r = ctx.solve_batch_pairs(mesh, sigma, src, ev, pairs, o, groups=group, n_group=n_group); grouped.append(time.perf_counter() - t0)
+                assert r0[-1] == 0 and r[-1] == 0 and np.all(np.isfinite(r[2]))
+                both = ctx.pair_groups_timing()
+                rt = ctx.solve_batch_pairs(mesh, sigma, src, ev, pairs, ot, groups=group, n_group=n_group)
+                assert rt[-1] == 0
+                parts.append(ctx.pair_groups_timing() + (both[1],))
+            best = min(parts, key=lambda p: p[0] + p[1] + p[2])
+            out[name] = dict(n_group=int(n_group), order_ms=best[0], per_element_launches_ms=best[1], group_sums_ms=best[2], slices=best[3],
+                             launches_and_sums_unsplit_ms=min(p[4] for p in parts), material_pass_ms=min(pass_ms),
+                             call_ms=1e3 * min(grouped), call_without_groups_ms=1e3 * min(plain), call_ratio=min(grouped) / min(plain),
+                             call_ms_all=[1e3 * t for t in grouped], call_without_groups_ms_all=[1e3 * t for t in plain],
+                             dPg_bytes=int(r[2].nbytes), pcg_steps=int(r[3]["pcg_steps"]))
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", default="L")
     ap.add_argument("--batch", type=int, default=20)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--child", action="store_true")
+    ap.add_argument("--groups", action="store_true", help="the cost of the pair derivatives per group of elements instead")
     ap.add_argument("--limit", type=int, default=420, help="seconds for the measurement")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pairs_cost.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/pairs_cost.json, with --groups profiles/pair_groups_cost.json")
     a = ap.parse_args()
     if a.child:
-        measure(a.size, a.batch, a.reps)
+        (measure_groups if a.groups else measure)(a.size, a.batch, a.reps)
         return 0
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "pair_groups_cost.json" if a.groups else "pairs_cost.json")
     p = subprocess.run(["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--size", a.size, "--batch", str(a.batch),
-                        "--reps", str(a.reps), "--child"], stdout=subprocess.PIPE, text=True)
+                        "--reps", str(a.reps), "--child"] + (["--groups"] if a.groups else []), stdout=subprocess.PIPE, text=True)
     if p.returncode != 0:
         print("measurement: exit status %d" % p.returncode, file=sys.stderr)
         return p.returncode
