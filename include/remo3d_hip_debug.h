@@ -65,6 +65,25 @@ int remo_debug_point_location(remo_ctx_t *ctx);
  * mode (precision = 1), whose inner solver stores every vector in fp32.  8: every other fp64 solve - resident batches, the CSR
  * product and all of 2D, the sens, warm and field entries. */
 int remo_debug_direction_bytes(remo_ctx_t *ctx);
+/* ONE direction launch of an fp64 solve with the search direction in fp32 storage, on the caller's own data and in both forms: the
+ * flat form (k_pcg_direction_flat<double, k, float>) and the row form (k_pcg_direction_row<double, k, float>), each from the same
+ * inputs, `grid` workgroups of 256 threads.  r [n][k], p [n][k] (float), z [nv][k] (the vertex rows' preconditioned residual, stored
+ * divided by the Jacobi factor; nv = 0: none), dinv [n]; part_even / part_odd [nb_rz][k]: the partial sums of <Cr, r> left by the
+ * update launch of an even / odd step + 1 - the launch of `step` reads the set of (step + 1) & 1; scal48: the scalar block, 48 doubles:
+ * <Cr0, r0> [8] | <p, A p> [8] | <Cr, r> of even steps [8] | of odd steps [8] | the done word (an int in the first of 8) | the floors [8].
+ * Out: p after the launch and the scalar block after it (the new <Cr, r> forwarded in it), per form.  No solve is involved, so the two
+ * forms are comparable bit for bit. */
+int remo_debug_direction_forms(remo_ctx_t *ctx, int64_t n, int64_t nv, int32_t k, int32_t grid, int32_t step, double tol2, const double *r,
+                               const float *p, const double *z, const double *dinv, const double *part_even, const double *part_odd,
+                               int32_t nb_rz, const double *scal48, float *p_flat, float *p_row, double *scal_flat, double *scal_row);
+/* Where a workgroup of the PCG's two vector launches spends its time before its first stored value (-DREMO_PROBES builds only):
+ * on = 1 makes wave 0 of every workgroup of k_pcg_direction_flat and k_pcg_update_tile leave three clocks (on entry | scalars in
+ * LDS | at the end) from now on; on = 0 stops that and reports the LAST launch of each kind that was not a no-op:
+ * out8[0..3] = direction launch: mean ticks of the head, of the whole workgroup, mean of head / whole per workgroup, workgroups;
+ * out8[4..7] = the same for the update launch.  Run a batch between the two calls.  ONE context of ONE device at a time: the stamp
+ * buffer is process-wide and the kernels' pointer to it is set on the calling context's device; switch the probe off (on = 0) before
+ * that context is destroyed. */
+int remo_debug_vector_heads(remo_ctx_t *ctx, int32_t on, double *out8);
 /* The load-vector launches (element vectors + row sums, all chunks) of the last remo_batch_run of a batch with remo_job_secondary_t.secondary
  * on this context, ms by HIP events; 0 when the last run was none. */
 int remo_debug_secondary_timing(remo_ctx_t *ctx, double *ms);

@@ -178,6 +178,10 @@ template <class T> void launch_pcg_init(const CsrViewT<T> &A, int k, const T *f,
 template <class T> void launch_pcg_update(const CsrViewT<T> &A, int k, int step, double tol2, const PcgBuffersT<T> &b, hipStream_t s);  // + C r (Chebyshev steps)
 template <class T> void launch_pcg_direction(const CsrViewT<T> &A, int k, int step, double tol2, const PcgBuffersT<T> &b, hipStream_t s, bool add_x = true);
 template <class T> void launch_pcg_final(int k, int step, const PcgBuffersT<T> &b, hipStream_t s);
+// one direction launch (fp64 storage, direction in fp32) on the caller's own vectors and scalars, flat or row form (remo_debug_direction_forms)
+void launch_direction_form(bool flat, int grid, int64_t n, int64_t nv, int k, int step, double tol2, int nb_rz, const double *part_rz_new,
+                           double *scal, const double *r, float *p, const double *dinv, double *z, hipStream_t s);
+void set_vector_stamps(long long *stamps);   // probe builds: where k_pcg_direction_flat / k_pcg_update_tile leave their clocks (remo_debug_vector_heads)
 void launch_vblock_bound(int64_t nv, const CsrView &A, const double *dinv, unsigned long long *out_bits, hipStream_t s);
 // B = A_vv D^-1 A_vv (and A_vv itself) on the pattern of B, rows sorted; cnt / rowptr [nv + 1], col / a / b [capacity];
 // *flag (device int, pre-zeroed) is raised when a row has more than kSquareSlots distinct columns or the capacity

@@ -22,6 +22,22 @@ constexpr bool kProbes = true;     // the build of tools/: rejected variants and
 constexpr bool kProbes = false;
 #endif
 
+// Probe builds: where a workgroup of k_pcg_direction_flat / k_pcg_update_tile spends its time - three clocks of its wave 0 (on entry |
+// scalars in LDS | at the end), four words per workgroup, written together at the end (a launch that finds the solve over leaves none)
+// where remo_debug_vector_heads points the launches (set_vector_stamps): direction launch in rows [0, kMaxPartialBlocks), update launch behind
+#ifdef REMO_PROBES
+__device__ long long *g_vec_stamps = nullptr;
+#define REMO_VEC_CLOCK(var) const long long var = (long long)__builtin_readcyclecounter();
+#define REMO_VEC_STAMPS(which, t0, t1)                                                                \
+    if (g_vec_stamps && threadIdx.x == 0) {                                                           \
+        long long *w_ = g_vec_stamps + (int64_t(which) * kMaxPartialBlocks + int64_t(blockIdx.x)) * 4; \
+        w_[0] = t0; w_[1] = t1; w_[2] = (long long)__builtin_readcyclecounter();                      \
+    }
+#else
+#define REMO_VEC_CLOCK(var)
+#define REMO_VEC_STAMPS(which, t0, t1)
+#endif
+
 // Progress records live in mapped, coherent host memory: the stores bypass the caches (sc0 sc1).  A system-scope RELEASE
 // store would also write back the whole L2 of the XCD (buffer_wbl2) on every PCG step; the record only needs its data to
 // land before its step number, so the data stores are relaxed, the wave waits for their acknowledgement, then stores the
@@ -136,8 +152,33 @@ __global__ void __launch_bounds__(256) k_pcg_init(int64_t n, ChebArgsT<T> ch, co
 // What every form does first.  Returns false when an earlier step froze every column (the launch is a no-op); else alpha[] of the step.
 // scal = rz0[8] | pq[8] | rz of even steps[8] | rz of odd steps[8]: totals forwarded between launches
 // by workgroup 0, so every launch re-reduces only the ONE partial array that is new to it
-template <class T, int K, class TP = T>
-__device__ __forceinline__ bool pcg_update_head(const UpdHeadT<T> &hd, const TP *__restrict__ p, double (&alpha)[K], double *smem /* [16*3*K] */) {
+// block_sum (kutil.h) for a workgroup of exactly 256 threads: the same tree, the same bits - but the number of waves is not read from the
+// dispatch packet: that load would be the YOUNGEST of the wave, and waiting for it waits for every vector load requested before it
+template <int K> __device__ __forceinline__ void block_sum_256(double (&v)[K], double *smem /* [4*K] */) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < K; ++c) v[c] = wave_sum(v[c]);
+    __syncthreads();
+    if (lane == 0)
+#pragma unroll
+        for (int c = 0; c < K; ++c) smem[wave * K + c] = v[c];
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) s += smem[w * K + c];
+        v[c] = s;
+    }
+}
+#ifndef REMO_UPD_EARLY
+#define REMO_UPD_EARLY 1      /* 0: k_pcg_update_tile beside an fp32 direction reduces its scalars before its first load (the form before) */
+#endif
+// PRE: the rows threadIdx.x + 256 i of part_pq are in pre[] already (requested before the caller's first vector loads, so that the wait
+// for them does not wait for those); a row beyond nb_spmv read as zero.  Same order of additions as reduce_partials: the same bits.
+template <class T, int K, class TP = T, bool PRE = false, int NPRE = 1>
+__device__ __forceinline__ bool pcg_update_head(const UpdHeadT<T> &hd, const TP *__restrict__ p, double (&alpha)[K], double *smem /* [16*3*K] */,
+                                                const double (*pre)[K] = nullptr) {
     double *scal = hd.rz0;
     const int step = hd.step;
     if (solve_done(scal, step)) return false;
@@ -145,7 +186,17 @@ __device__ __forceinline__ bool pcg_update_head(const UpdHeadT<T> &hd, const TP 
     if (step == 0) {
         reduce_partials3<K>(hd.part_pq, hd.nb_spmv, hd.part_rz_cur, hd.nb_rz, nullptr, 0, pq, rz, unused, smem);
     } else {
-        reduce_partials<K>(hd.part_pq, hd.nb_spmv, pq, smem);
+        if constexpr (PRE) {
+#pragma unroll
+            for (int c = 0; c < K; ++c) pq[c] = 0.0;
+#pragma unroll
+            for (int i = 0; i < NPRE; ++i)
+#pragma unroll
+                for (int c = 0; c < K; ++c) pq[c] += pre[i][c];
+            block_sum_256<K>(pq, smem);
+        } else {
+            reduce_partials<K>(hd.part_pq, hd.nb_spmv, pq, smem);
+        }
 #pragma unroll
         for (int c = 0; c < K; ++c) rz[c] = scal[16 + 8 * (step & 1) + c];
     }
@@ -396,12 +447,145 @@ __global__ void __launch_bounds__(256) k_pcg_update_folded(int64_t n, UpdHeadT<T
 // holds them (ds_bpermute), and ITS column of each slab slot - the K lanes of a row read a slot's 40 bytes side by side.
 // All 6 K loads of a lane are in flight together.  Same sums, same order as the row form (rows of five or more patches, the
 // first vertex rows: their further slots are summed by the row's lane and handed over through LDS - another association).
+// The tile form beside an fp32 direction (the one-shot solves; REMO_UPD_EARLY): the same tiles, sums and order as k_pcg_update_tile
+// below, but the partial sums of <p, A p> and then the FIRST tile's slots, r, Jacobi factors and slab values are requested before
+// the scalars are reduced, and the head runs while they are in flight - no load depends on alpha.
+template <int K>
+__device__ __forceinline__ void pcg_update_tile_early(int64_t n, const UpdHeadT<double> &hd, int64_t nv, double *__restrict__ part_rz_next,
+                                                      const float *__restrict__ p, double *__restrict__ r, const double *__restrict__ dinv,
+                                                      const QViewT<double> &qv, double *smem /* [16*3*K] */, double *ex_lds /* [4*64*K] */) {
+    using T = double;
+    double alpha[K], acc[K];
+    REMO_VEC_CLOCK(t_in)
+    constexpr uint32_t S = sizeof(T);
+    constexpr int NPRE = kMaxPartialBlocks / 256;
+    double pre[NPRE][K];
+    if (solve_done(hd.rz0, hd.step)) return;       // (a finished solve leaves before any request)
+    {
+        const rsrc_t rq = make_rsrc(hd.part_pq, uint64_t(hd.nb_spmv) * (K * 8));
+#pragma unroll
+        for (int i = 0; i < NPRE; ++i) buf_load<double, K>(rq, (uint32_t(threadIdx.x) + 256u * i) * uint32_t(K * 8), pre[i]);
+        __builtin_amdgcn_sched_barrier(0);      // the OLDEST loads of the wave: the head's wait for them leaves the tile's loads in flight
+    }
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t N = uint32_t(n) * K, NV = uint32_t(nv) * K;
+    const rsrc_t rr = make_rsrc(r, uint64_t(N) * S), rd = make_rsrc(dinv, uint64_t(n) * S), rs = make_rsrc(qv.Yb, qv.slab_bytes),
+                 r4 = make_rsrc(qv.row4, uint64_t(n) * 16);
+    uint32_t rowof[K], colof[K];      // pass t: this lane's value is (row rowof[t] of the tile, column colof[t]) - the same for every tile
+    T al[K];
+    double accv[K];
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+        const uint32_t v = 64u * t + lane;
+        rowof[t] = v / uint32_t(K); colof[t] = v - rowof[t] * uint32_t(K);
+        accv[t] = 0.0;
+    }
+    double *exw = ex_lds + wave * (64 * K);
+    const uint32_t nwaves = uint32_t(gridDim.x) * 4u;
+    // (the slots of the NEXT tile are requested before this tile's values: one memory round trip per tile on a wave's critical path, not two)
+    int32_t w4n[4];
+    {
+        const uint32_t row0 = (uint32_t(blockIdx.x) * 4u + wave) * 64u + lane;
+        buf_load<int32_t, 4>(r4, row0 < uint32_t(n) ? row0 * 16u : kOutOfRange, w4n);
+    }
+    int32_t w4[4];
+    T rv[K], dv[K], part[K][4];
+    // the slots of the tile at R0 (requested one tile ahead), the request for the next tile's, and this tile's r, Jacobi factors and slab values
+    auto request = [&](uint32_t R0) {
+        const uint32_t myrow = R0 + lane;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w4[j] = myrow < uint32_t(n) ? w4n[j] : -1;
+        {
+            const uint32_t nrow = myrow + nwaves * 64u;
+            buf_load<int32_t, 4>(r4, nrow < uint32_t(n) ? nrow * 16u : kOutOfRange, w4n);
+        }
+        const uint32_t e0 = R0 * uint32_t(K);
+#pragma unroll
+        for (int t = 0; t < K; ++t) {
+            const uint32_t e = e0 + 64u * t + lane;
+            T one[1];
+            buf_load<T, 1>(rr, e < N ? e * S : kOutOfRange, one);
+            rv[t] = one[0];
+            buf_load<T, 1>(rd, e < N ? (R0 + rowof[t]) * S : kOutOfRange, one);
+            dv[t] = one[0];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int32_t sj = __builtin_amdgcn_ds_bpermute(int(rowof[t] << 2), w4[j]);
+                buf_load<T, 1>(rs, sj >= 0 ? (uint32_t(sj) * uint32_t(K) + colof[t]) * S : kOutOfRange, one);
+                part[t][j] = one[0];
+            }
+        }
+    };
+    request((uint32_t(blockIdx.x) * 4u + wave) * 64u);      // (a wave with no tile asks for nothing: every offset is out of range)
+    bool requested = true;
+    if (!pcg_update_head<T, K, float, true, NPRE>(hd, p, alpha, smem, pre)) return;
+    __syncthreads();          // (the reductions' last reads of smem)
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < K; ++c) smem[c] = alpha[c];
+    }
+    __syncthreads();
+    REMO_VEC_CLOCK(t_head)
+#pragma unroll
+    for (int t = 0; t < K; ++t) al[t] = T(smem[colof[t]]);
+    for (uint32_t R0 = (uint32_t(blockIdx.x) * 4u + wave) * 64u; R0 < uint32_t(n); R0 += nwaves * 64u) {
+        const uint32_t myrow = R0 + lane;
+        const uint32_t e0 = R0 * uint32_t(K);
+        if (!requested) request(R0);
+        requested = false;
+        const bool more = w4[3] == -2;
+        const bool any_more = __builtin_amdgcn_ballot_w64(more) != 0;
+        if (any_more) {       // (wave-uniform) rows of five or more patches in this tile: their lanes sum the slots from the fourth on
+#pragma unroll
+            for (int c = 0; c < K; ++c) exw[lane * K + c] = 0.0;
+            if (more) {
+                const int32_t c0 = qv.bptr[myrow], c1 = qv.bptr[myrow + 1];
+                for (int32_t sl = c0 + 3; sl < c1; ++sl) {
+                    const int64_t a2 = qv.bslot[sl];
+#pragma unroll
+                    for (int c = 0; c < K; ++c) exw[lane * K + c] += double(qv.Yb[a2 * K + c]);
+                }
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's LDS writes are done before its lanes read each other's
+        }
+#pragma unroll
+        for (int t = 0; t < K; ++t) {
+            const uint32_t e = e0 + 64u * t + lane;
+            T qi = part[t][0];
+#pragma unroll
+            for (int j = 1; j < 4; ++j) qi += part[t][j];
+            if (any_more) qi += T(exw[64 * t + lane]);
+            const T ri = rv[t] - al[t] * qi;
+            T one[1] = {ri};
+            buf_store<T, 1>(rr, e < N ? e * S : kOutOfRange, one);
+            accv[t] += (e < NV || e >= N) ? 0.0 : double(ri) * double(ri) * double(dv[t]);
+        }
+        if (any_more) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads done before the next tile's zeros
+    }
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        double tsum = 0.0;
+#pragma unroll
+        for (int t = 0; t < K; ++t) tsum += (colof[t] == uint32_t(c)) ? accv[t] : 0.0;
+        acc[c] = tsum;
+    }
+    __syncthreads();
+    const double mine = block_sum_column<K>(acc, smem);
+    if (threadIdx.x < K) part_rz_next[blockIdx.x * K + threadIdx.x] = mine;
+    REMO_VEC_STAMPS(1, t_in, t_head)
+}
+
 template <class T, int K, class TP = T>
 __global__ void __launch_bounds__(256) k_pcg_update_tile(int64_t n, UpdHeadT<T> hd, int64_t nv, double *__restrict__ part_rz_next,
                                                          const TP *__restrict__ p, T *__restrict__ r, const T *__restrict__ dinv, QViewT<T> qv) {
     __shared__ double smem[16 * 3 * K];
     __shared__ double ex_lds[4 * 64 * K];
+    if constexpr (!std::is_same<TP, T>::value && REMO_UPD_EARLY) {
+        pcg_update_tile_early<K>(n, hd, nv, part_rz_next, p, r, dinv, qv, smem, ex_lds);
+        return;
+    }
     double alpha[K], acc[K];
+    REMO_VEC_CLOCK(t_in)
     if (!pcg_update_head<T, K, TP>(hd, p, alpha, smem)) return;
     constexpr uint32_t S = sizeof(T);
     __syncthreads();          // (the reductions' last reads of smem)
@@ -410,6 +594,7 @@ __global__ void __launch_bounds__(256) k_pcg_update_tile(int64_t n, UpdHeadT<T> 
         for (int c = 0; c < K; ++c) smem[c] = alpha[c];
     }
     __syncthreads();
+    REMO_VEC_CLOCK(t_head)
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t N = uint32_t(n) * K, NV = uint32_t(nv) * K;
     const rsrc_t rr = make_rsrc(r, uint64_t(N) * S), rd = make_rsrc(dinv, uint64_t(n) * S), rs = make_rsrc(qv.Yb, qv.slab_bytes),
@@ -496,6 +681,7 @@ __global__ void __launch_bounds__(256) k_pcg_update_tile(int64_t n, UpdHeadT<T> 
     __syncthreads();
     const double mine = block_sum_column<K>(acc, smem);
     if (threadIdx.x < K) part_rz_next[blockIdx.x * K + threadIdx.x] = mine;
+    REMO_VEC_STAMPS(1, t_in, t_head)
 }
 
 // One Chebyshev step on the vertex block, 8 lanes per row:
@@ -649,12 +835,116 @@ __device__ __forceinline__ bool pcg_direction_head(int step, double tol2, int nb
 // four of five).  Buffer accesses: the range check drops what lies behind the last value, dword by dword.
 // TP = float beside T = double: a lane still moves 16 bytes per access - FOUR consecutive values, one 16-byte access of p and two of r
 // (values e0, e0 + 1 and e0 + 2, e0 + 3: the two accesses of a wave cover the same 2 KB of whole lines); as many load sets in flight.
+// TP = float beside T = double, REMO_DIR_P32_MAP = 1 (0: the map above, four consecutive values per lane - a measuring aid only, for a
+// library built beside this one; no product build and no test takes it):
+// a lane takes TWO consecutive values per access - 16 bytes of r, 8 of p - so that every wave instruction on r covers 1 KB of
+// consecutive bytes (on p: 512) and no line is asked for twice; a load set is kDirJ such instructions, values
+// base + 128 j + 2 lane, + 1.  The Jacobi factors of the two values' rows (the same row, or two neighbours) come as ONE 16-byte load
+// and are chosen in registers; the z load is skipped, wave by wave, once the wave is past the vertex rows.  The first load sets are
+// requested BEFORE the scalars are reduced - the partial sums first, so that the wait for them does not wait for the vectors - and
+// the head runs while they are in flight: no load depends on beta.  Same operands, same expression: the same bits of p.
+#ifndef REMO_DIR_P32_MAP
+#define REMO_DIR_P32_MAP 1
+#endif
+constexpr int kDirUF = 4, kDirJ = 2;     // load sets in flight per lane, wave instructions on r per set: 16 values per lane, as in the map above
+template <int K>
+__device__ __forceinline__ void pcg_direction_flat_p32(int64_t n, int first, int step, double tol2, int nb_rz, const ChebArgsT<double> &ch,
+                                                       const double *__restrict__ part_rz_new, double *__restrict__ scal,
+                                                       const double *__restrict__ r, float *__restrict__ p, const double *__restrict__ dinv,
+                                                       double *smem /* [16*K] */) {
+    REMO_VEC_CLOCK(t_in)
+    if (solve_done(scal, step)) return;
+    constexpr int UF = kDirUF, NJ = kDirJ;
+    constexpr uint32_t WV = 128;          // values per wave instruction
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t N = uint32_t(n) * K, NV = uint32_t(ch.nv) * K;
+    const rsrc_t rr = make_rsrc(r, uint64_t(N) * 8), rz = make_rsrc(ch.z, uint64_t(NV) * 8), rp = make_rsrc(p, uint64_t(N) * 4),
+                 rd = make_rsrc(dinv, uint64_t(n) * 8), rq = make_rsrc(part_rz_new, uint64_t(nb_rz) * (K * 8));
+    // the partial sums of the update launch: rows threadIdx.x + 256 i, the order of reduce_partials (a row beyond nb_rz reads as zero)
+    constexpr int NP = kMaxPartialBlocks / 256;
+    double part[NP][K];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) buf_load<double, K>(rq, (uint32_t(threadIdx.x) + 256u * i) * uint32_t(K * 8), part[i]);
+    const uint32_t span = uint32_t(gridDim.x) * 4u * (NJ * WV);     // values of one load set of the whole grid
+    uint32_t g0 = (uint32_t(blockIdx.x) * 4u + wave) * (NJ * WV) + 2u * lane;
+    double rv[UF][NJ][2], zz[UF][NJ][2], dd[UF][NJ][2];
+    float pv[UF][NJ][2];
+    auto request = [&](uint32_t g) {
+#pragma unroll
+        for (int u = 0; u < UF; ++u)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const uint32_t e = g + u * span + j * WV;
+                buf_load<double, 2>(rr, e < N ? e * 8u : kOutOfRange, rv[u][j]);
+                buf_load<float, 2>(rp, e < N ? e * 4u : kOutOfRange, pv[u][j]);
+                buf_load<double, 2>(rd, e < N ? (e / uint32_t(K)) * 8u : kOutOfRange, dd[u][j]);
+                // vertex rows: the vertex-block solver's result (stored pre-divided by the Jacobi factor) instead of r
+                zz[u][j][0] = 0.0; zz[u][j][1] = 0.0;
+                if (uint32_t(__builtin_amdgcn_readfirstlane(int(e))) < NV) buf_load<double, 2>(rz, e < NV ? e * 8u : kOutOfRange, zz[u][j]);
+            }
+    };
+    request(g0);
+    double rzn[K], beta[K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) rzn[c] = 0.0;
+#pragma unroll
+    for (int i = 0; i < NP; ++i)
+#pragma unroll
+        for (int c = 0; c < K; ++c) rzn[c] += part[i][c];
+    block_sum_256<K>(rzn, smem);
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        const double pq = scal[8 + c], rzo = scal[16 + 8 * (step & 1) + c];   // forwarded by the update launch
+        const bool live = (rzo > tol2 * scal[c]) && (rzo > scal[kFloorSlot + c]) && (pq > 0.0);
+        beta[c] = live ? rzn[c] / rzo : 0.0;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+#pragma unroll
+        for (int c = 0; c < K; ++c) scal[16 + 8 * ((step + 1) & 1) + c] = rzn[c];   // read by the next update launch
+    __syncthreads();          // (block_sum's last reads of smem)
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < K; ++c) smem[c] = first ? 0.0 : beta[c];      // first (no launcher passes it): p = C r, the old direction counts for nothing
+    }
+    __syncthreads();
+    REMO_VEC_CLOCK(t_head)
+    while (g0 < N) {
+#pragma unroll
+        for (int u = 0; u < UF; ++u)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const uint32_t e = g0 + u * span + j * WV;
+                const uint32_t c0 = e % uint32_t(K);
+                float pn[2];
+#pragma unroll
+                for (int v = 0; v < 2; ++v) {
+                    const bool next_row = c0 + v >= uint32_t(K);
+                    const uint32_t c = next_row ? 0u : c0 + v;
+                    const double d = next_row ? dd[u][j][1] : dd[u][j][0];
+                    const double zi = d * ((e + v < NV) ? zz[u][j][v] : rv[u][j][v]), po = first ? 0.0 : double(pv[u][j][v]);
+                    // one rounded product and one fused multiply-add, spelled out: what the compiler makes of `first ? zi : zi + beta * po`
+                    // in the other forms (it fuses beta * po), without the branch on `first` around every read of beta
+                    pn[v] = float(__builtin_fma(smem[c], po, zi));
+                }
+                buf_store<float, 2>(rp, e < N ? e * 4u : kOutOfRange, pn);
+            }
+        g0 += UF * span;
+        if (g0 < N) request(g0);
+    }
+    REMO_VEC_STAMPS(0, t_in, t_head)
+}
+
 template <class T, int K, class TP = T>
 __global__ void __launch_bounds__(256) k_pcg_direction_flat(int64_t n, int first, int step, double tol2, int nb_rz, ChebArgsT<T> ch,
                                                             const double *__restrict__ part_rz_new, double *__restrict__ scal,
                                                             const T *__restrict__ r, TP *__restrict__ p,
                                                             const T *__restrict__ dinv, T *__restrict__ x) {
     __shared__ double smem[16 * K];
+    REMO_VEC_CLOCK(t_in)
+    if constexpr (!std::is_same<TP, T>::value && REMO_DIR_P32_MAP == 1) {
+        pcg_direction_flat_p32<K>(n, first, step, tol2, nb_rz, ch, part_rz_new, scal, r, p, dinv, smem);
+        return;
+    }
     double beta[K], alpha[K];
     if (!pcg_direction_head<K>(step, tol2, nb_rz, part_rz_new, scal, beta, alpha, smem)) return;
     constexpr bool SAME = std::is_same<TP, T>::value;
@@ -669,6 +959,7 @@ __global__ void __launch_bounds__(256) k_pcg_direction_flat(int64_t n, int first
         for (int c = 0; c < K; ++c) { smem[c] = beta[c]; smem[K + c] = alpha[c]; }
     }
     __syncthreads();
+    REMO_VEC_CLOCK(t_head)
     const uint32_t N = uint32_t(n) * K, NV = uint32_t(ch.nv) * K;
     const rsrc_t rr = make_rsrc(r, uint64_t(N) * S), rz = make_rsrc(ch.z, uint64_t(NV) * S), rp = make_rsrc(p, uint64_t(N) * SP),
                  rd = make_rsrc(dinv, uint64_t(n) * S), rx = make_rsrc((SAME && x) ? (const void *)x : (const void *)p, uint64_t(N) * S);
@@ -726,6 +1017,7 @@ __global__ void __launch_bounds__(256) k_pcg_direction_flat(int64_t n, int first
             if (with_x) buf_store<T, VEC>(rx, off, xn);
         }
     }
+    REMO_VEC_STAMPS(0, t_in, t_head)
 }
 // ROW form.  first: p0 = C r0 (no scalars, no old direction).
 // U rows per thread are loaded before any of them is stored: p is read and written through the same pointer, and a store
@@ -777,6 +1069,8 @@ __global__ void __launch_bounds__(256) k_pcg_direction_row(int64_t n, int first,
 #pragma unroll
                 for (int c = 0; c < K; ++c) {
                     const T zi = d[u] * zv[u][c];
+                    // (the compiler contracts beta * p into one fma on the rounded zi; pcg_direction_flat_p32 spells the same two operations
+                    // out, and tests/test_gpu_vector_launches.py holds the two forms to the same bits)
                     p[i * K + c] = TP(first ? zi : zi + T(beta[c]) * pv[u][c]);
                     // x += alpha p of THIS step, with the old direction that is in registers anyway (PcgBuffersT::x_in_direction):
                     // the update launch then neither reads p nor touches x - one pass over p less per step
@@ -1178,6 +1472,26 @@ template <class T> void launch_pcg_direction(const CsrViewT<T> &A, int k, int st
     } else {
         REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction_row<T, KK>), dim3(g), dim3(256), 0, s, n, 0, step, tol2, nb_rz(b), ch, nw, b.rz0, b.r, b.p, b.dinv, xp));
     }
+}
+
+// One direction launch on the caller's own vectors and scalars, fp64 storage with the direction in fp32 (remo_debug_direction_forms):
+// flat != 0: k_pcg_direction_flat<double, k, float>, else k_pcg_direction_row<double, k, float>; `grid` workgroups.
+void launch_direction_form(bool flat, int grid, int64_t n, int64_t nv, int k, int step, double tol2, int nb_rz, const double *part_rz_new,
+                           double *scal, const double *r, float *p, const double *dinv, double *z, hipStream_t s) {
+    ChebArgsT<double> ch;
+    ch.nv = nv; ch.inv_theta = 0.0; ch.z = z; ch.res = nullptr; ch.d0 = nullptr;
+    if (uint64_t(n) * uint64_t(k) * 8 >= 0xFFFFF000ull || nb_rz > kMaxPartialBlocks || grid < 1) throw std::invalid_argument("launch_direction_form: sizes");
+    if (flat) { REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction_flat<double, KK, float>), dim3(grid), dim3(256), 0, s, n, 0, step, tol2, nb_rz, ch, part_rz_new, scal, r, p, dinv, (double *)nullptr)); }
+    else { REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction_row<double, KK, float>), dim3(grid), dim3(256), 0, s, n, 0, step, tol2, nb_rz, ch, part_rz_new, scal, r, p, dinv, (double *)nullptr)); }
+}
+
+// probe builds: where the vector launches leave their clocks (nullptr: nowhere) - four words per workgroup, REMO_VEC_STAMPS
+void set_vector_stamps(long long *stamps) {
+#ifdef REMO_PROBES
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_vec_stamps), &stamps, sizeof stamps) != hipSuccess) throw std::runtime_error("set_vector_stamps: hipMemcpyToSymbol failed");
+#else
+    (void)stamps;
+#endif
 }
 
 template <class T> void launch_pcg_final(int k, int step, const PcgBuffersT<T> &b, hipStream_t s) {

@@ -366,6 +366,91 @@ int remo_debug_patch_phases_p(remo_ctx_t *ctx, remo_batch_t *b, int32_t fp32, do
 #endif
 }
 
+int remo_debug_direction_forms(remo_ctx_t *ctx, int64_t n, int64_t nv, int32_t k, int32_t grid, int32_t step, double tol2, const double *r,
+                               const float *p, const double *z, const double *dinv, const double *part_even, const double *part_odd,
+                               int32_t nb_rz, const double *scal48, float *p_flat, float *p_row, double *scal_flat, double *scal_row) {
+    if (!ctx || n < 1 || nv < 0 || nv > n || k < 1 || k > 8 || grid < 1 || grid > kMaxPartialBlocks || step < 0 || nb_rz < 0 || nb_rz > kMaxPartialBlocks ||
+        !r || !p || !dinv || (nv > 0 && !z) || !part_even || !part_odd || !scal48 || !p_flat || !p_row || !scal_flat || !scal_row)
+        return REMO_ERR_ARG;
+    if (uint64_t(n) * uint64_t(k) * 8 >= 0xFFFFF000ull) return fail(ctx, REMO_ERR_ARG, "remo_debug_direction_forms: n k sizeof(double) must stay below 4 GB (the flat form's range)");
+    try {
+        HIP_TRY(hipSetDevice(ctx->device));
+        const size_t N = size_t(n) * k, NV = size_t(nv) * k, NP = size_t(nb_rz > 0 ? nb_rz : 1) * k;
+        DeviceTemp tmp;
+        double *dr = tmp.alloc<double>(N), *dz = tmp.alloc<double>(NV + 2), *dd = tmp.alloc<double>(n), *dpart = tmp.alloc<double>(2 * NP),
+               *dscal = tmp.alloc<double>(48);
+        float *dp = tmp.alloc<float>(N);
+        HIP_TRY(hipMemcpy(dr, r, sizeof(double) * N, hipMemcpyHostToDevice));
+        if (NV) HIP_TRY(hipMemcpy(dz, z, sizeof(double) * NV, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dd, dinv, sizeof(double) * n, hipMemcpyHostToDevice));
+        if (nb_rz > 0) {
+            HIP_TRY(hipMemcpy(dpart, part_even, sizeof(double) * NP, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(dpart + NP, part_odd, sizeof(double) * NP, hipMemcpyHostToDevice));
+        }
+        for (int form = 1; form >= 0; --form) {      // the flat form, then the row form, each from the caller's p and scalars
+            HIP_TRY(hipMemcpy(dp, p, sizeof(float) * N, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(dscal, scal48, sizeof(double) * 48, hipMemcpyHostToDevice));
+            launch_direction_form(form != 0, grid, n, nv, k, step, tol2, nb_rz, dpart + ((step + 1) & 1) * NP, dscal, dr, dp, dd, dz, ctx->stream);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            HIP_TRY(hipMemcpy(form ? p_flat : p_row, dp, sizeof(float) * N, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(form ? scal_flat : scal_row, dscal, sizeof(double) * 48, hipMemcpyDeviceToHost));
+        }
+        return REMO_OK;
+    } catch (const std::exception &ex) {
+        return fail(ctx, REMO_ERR_DEVICE, ex.what());
+    }
+}
+
+#ifdef REMO_PROBES
+namespace {
+// remo_debug_vector_heads: the stamp rows of both launches while the probe is on.  One buffer for the process, on the device of the context
+// that switched the probe on (the kernels' g_vec_stamps is that device's symbol): a probe for one context at a time, as the header says.
+long long *g_vec_stamp_buf = nullptr;
+}
+#endif
+
+int remo_debug_vector_heads(remo_ctx_t *ctx, int32_t on, double *out8) {
+    if (!ctx || (!on && !out8)) return REMO_ERR_ARG;
+#ifndef REMO_PROBES
+    return fail(ctx, REMO_ERR_ARG, "remo_debug_vector_heads: the library was built without -DREMO_PROBES (make -C remo3d_amd/csrc probes)");
+#else
+    const size_t words = size_t(2) * kMaxPartialBlocks * 4;
+    try {
+        HIP_TRY(hipSetDevice(ctx->device));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (on) {
+            if (!g_vec_stamp_buf) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g_vec_stamp_buf), sizeof(long long) * words));
+            HIP_TRY(hipMemset(g_vec_stamp_buf, 0, sizeof(long long) * words));
+            set_vector_stamps(g_vec_stamp_buf);
+            return REMO_OK;
+        }
+        set_vector_stamps(nullptr);
+        for (int i = 0; i < 8; ++i) out8[i] = 0.0;
+        if (!g_vec_stamp_buf) return REMO_OK;
+        std::vector<long long> h(words);
+        HIP_TRY(hipMemcpy(h.data(), g_vec_stamp_buf, sizeof(long long) * words, hipMemcpyDeviceToHost));
+        HIP_TRY(hipFree(g_vec_stamp_buf));
+        g_vec_stamp_buf = nullptr;
+        for (int which = 0; which < 2; ++which) {
+            double head = 0, whole = 0, share = 0, cnt = 0;
+            for (int w = 0; w < kMaxPartialBlocks; ++w) {
+                const long long *s4 = h.data() + (size_t(which) * kMaxPartialBlocks + w) * 4;
+                if (s4[0] == 0 || s4[2] <= s4[0]) continue;
+                head += double(s4[1] - s4[0]); whole += double(s4[2] - s4[0]);
+                share += double(s4[1] - s4[0]) / double(s4[2] - s4[0]);
+                cnt += 1;
+            }
+            const double c = cnt > 0 ? cnt : 1;
+            out8[4 * which] = head / c; out8[4 * which + 1] = whole / c; out8[4 * which + 2] = share / c; out8[4 * which + 3] = cnt;
+        }
+        return REMO_OK;
+    } catch (const std::exception &ex) {
+        return fail(ctx, REMO_ERR_DEVICE, ex.what());
+    }
+#endif
+}
+
 int remo_debug_tune(int32_t key, int32_t value) {
     // Keys that force ONE OF THE PRODUCT'S OWN PATHS - a choice the library makes by size or dimension, forced so that a small test
     // mesh reaches the code a large batch runs; every setting gives the same operator / preconditioner to rounding: always there.
