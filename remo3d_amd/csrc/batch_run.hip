@@ -6,6 +6,8 @@
 // The context's arena is a bump allocator: the addresses of a batch follow from the ORDER of the ctx->take calls (and of
 // build_patch_tables / amg_setup / amg_to_float, which take from it too).  The stages below keep one order; arena_estimate names
 // the buffers term by term so that the two can be compared by eye.
+// The element passes (metric terms, loads, evaluation, sensitivities, pairs, field, error estimates, secondary loads) are launched with
+// ONE view of the batch's mesh and system, System::em (ElemMesh, elem_access.h; elem_mesh of remo_internal.h fills it in take_system).
 #include <limits.h>
 
 #include <algorithm>
@@ -252,6 +254,7 @@ struct System {
     double *d_C = nullptr, *d_val = nullptr, *d_dinv = nullptr, *d_f = nullptr;
     const double *d_M = nullptr;              // reference tensors (remo_opts_t.quadrature)
     int64_t pair_begin = 0, pair_end = 0;     // edge-dof rows: consecutive pairs with identical patterns, values interleaved
+    ElemMesh em;                              // mesh and system as the element kernels read them (elem_mesh): take_system fills it with the rest
     CsrView view(const DeviceSymbolic &sy) const { return CsrView{n, sy.nnz, sy.rowptr, sy.col, d_val}; }
 };
 
@@ -264,6 +267,8 @@ System take_system(const Run &r, const Plan &plan) {
     sys.d_val = r.ctx->take<double>(sy.nnz + 2);   // + 16 bytes: the SpMM reads single rows' values as 16-byte pairs (CsrViewT)
     sys.d_dinv = r.ctx->take<double>(sys.n);
     sys.d_f = r.ctx->take<double>(sys.n * plan.kmax);
+    sys.d_M = (r.dim == 2) ? (r.o.quadrature == 1 ? r.ctx->d_M2q : r.ctx->d_M2) : r.ctx->d_M3;
+    sys.em = elem_mesh(r.b, sys.d_C, sys.d_M);   // once per run: no stage sees a System without its view
     return sys;
 }
 
@@ -271,12 +276,11 @@ void assemble_system(const Run &r, System &sys) {
     remo_batch *b = r.b;
     const DeviceSymbolic &sy = b->sym;
     const int dim = r.dim;
-    sys.d_M = (dim == 2) ? (r.o.quadrature == 1 ? r.ctx->d_M2q : r.ctx->d_M2) : r.ctx->d_M3;
     b->d_M_last = sys.d_M;
-    if (b->sigma_comp > 1)
-        launch_metric_terms_tensor(dim, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, b->d_sigma, b->n_mat, sys.d_C, r.ctx->d_err, r.s);
+    if (sys.em.tensor())
+        launch_metric_terms_tensor(sys.em, r.ctx->d_err, r.s);
     else
-        launch_metric_terms(dim, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, b->d_sigma, b->n_mat, sys.d_C, r.ctx->d_err, r.s);
+        launch_metric_terms(sys.em, r.ctx->d_err, r.s);
     if (sys.lite) {   // values of the P1 block (the generic row walk over the vertex rows: their columns are vertex dofs, other local dofs
                       // of an element fall behind the row's last column and are dropped) + the Jacobi factors of every other row
         launch_assemble(dim, sy.condense, sy.nvfree, 0, 0, sy.rowptr, sy.col, sy.adjptr, sy.adj, sy.eldof, sys.d_C, sys.d_M, sys.d_val, sys.d_dinv, r.s);
@@ -485,18 +489,15 @@ void upload_secondary(const Run &r, const Secondary &sec) {
 
 // a source in or on an element whose conductivity differs from its sigma0 makes the integrand singular: bit 4 of the error flag,
 // read back with the batch's one synchronisation
-void check_secondary_sources(const Run &r, const Secondary &sec) {
+void check_secondary_sources(const Run &r, const System &sys, const Secondary &sec) {
     if (!sec.on) return;
-    const remo_batch *b = r.b;
-    launch_sec_check(r.dim, b->nt, b->d_coords, b->sym.conn, b->d_mat, b->sym.eperm, b->d_sigma, b->sigma_comp, b->n_mat, sec.host.n(), sec.d_src, r.ctx->d_err, r.s);
+    launch_sec_check(sys.em, sec.host.n(), sec.d_src, r.ctx->d_err, r.s);
 }
 
 // the load vectors of one chunk (d_f is the chunk's): element vectors, then the rows' sums in ascending element order
 void build_secondary_rhs(const Run &r, const System &sys, const Secondary &sec, int chunk, int k) {
-    const remo_batch *b = r.b;
-    const DeviceSymbolic &sy = b->sym;
-    launch_sec_elements(r.dim, sy.condense, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, b->d_sigma, b->sigma_comp, b->n_mat, sys.d_C, sys.d_M, sec.d_rule,
-                        sec.nq, sec.d_src, sec.d_ptr + size_t(chunk) * (REMO_MAX_RHS + 1), k, sec.R, sec.d_fe, sec.d_fbub, r.s);
+    const DeviceSymbolic &sy = r.b->sym;
+    launch_sec_elements(sys.em, sec.d_rule, sec.nq, sec.d_src, sec.d_ptr + size_t(chunk) * (REMO_MAX_RHS + 1), k, sec.R, sec.d_fe, sec.d_fbub, r.s);
     launch_sec_gather(r.dim, sys.n, k, sy.adjptr, sy.adj, sec.d_fe, sys.d_f, r.s);
 }
 
@@ -555,16 +556,14 @@ void field_locate_points(const Run &r, Field &f) {
 void field_eval_chunk(const Run &r, const System &sys, const DevicePoints &dp, const double *x, Field &f, int c0, int k, int q0, int nq) {
     if (f.n <= 0 || f.n_frhs <= 0) return;
     const remo_batch *b = r.b;
-    const DeviceSymbolic &sy = b->sym;
-    const FieldSources src{dp.d_prhs + q0, dp.d_pI + q0, dp.d_found + q0, dp.d_fint + q0, nq};
+    const PointLoads src{dp.d_prhs + q0, dp.d_pI + q0, dp.d_found + q0, dp.d_fint + q0, nq};
     FieldCols cols;
     bool any = false;
     auto flush = [&]() {
         if (cols.n == 0) return;
         if (!any) HIP_TRY(hipEventRecord(r.ctx->fev[2], r.s));
         any = true;
-        launch_field_eval(r.dim, sy.condense, b->sigma_comp > 1, f.n, f.d_pts, f.d_found, b->d_coords, sy.conn, b->d_mat, sy.eperm, b->d_sigma, b->n_mat,
-                          sy.eldof, sys.d_C, sys.d_M, k, x, cols, src, f.d_u, f.d_grad, f.d_J, r.s);
+        launch_field_eval(sys.em, f.n, f.d_pts, f.d_found, k, x, cols, src, f.d_u, f.d_grad, f.d_J, r.s);
         cols.n = 0;
     };
     for (int j = 0; j < f.n_frhs; ++j) {
@@ -881,10 +880,9 @@ int solve_chunk(const Run &r, const Plan &plan, const System &sys, const DeviceP
         if (nq > 0) HIP_TRY(hipMemsetAsync(dp.d_fint + q0, 0, sizeof(double) * nq, s));
         build_secondary_rhs(r, sys, *sec, chunk, k);
     } else if (nq > 0)
-        launch_build_rhs(dim, sy.condense, nq, dp.d_prhs + q0, dp.d_pI + q0, dp.d_found + q0, dp.d_phi + size_t(q0) * N, sy.eldof, sys.d_C, sys.d_M, k,
-                         sys.d_f, dp.d_fint + q0, s);
+        launch_build_rhs(sys.em, nq, dp.d_prhs + q0, dp.d_pI + q0, dp.d_found + q0, dp.d_phi + size_t(q0) * N, k, sys.d_f, dp.d_fint + q0, s);
     if (plan.x_ev_only) {   // the slots of this chunk's points (k and the columns change with the chunk)
-        launch_eval_slots(dim, sy.condense, nq, dp.d_prhs + q0, dp.d_found + q0, sy.eldof, k, dp.d_ev_at, s);
+        launch_eval_slots(sys.em, nq, dp.d_prhs + q0, dp.d_found + q0, k, dp.d_ev_at, s);
         if (nq > 0) HIP_TRY(hipMemsetAsync(dp.d_x_ev, 0, sizeof(double) * size_t(nq) * N, s));
         buf.x_ev_at = dp.d_ev_at; buf.x_ev = dp.d_x_ev; buf.x_ev_n = nq * N;
     }
@@ -893,8 +891,8 @@ int solve_chunk(const Run &r, const Plan &plan, const System &sys, const DeviceP
                         : (x_prev ? run_pcg_warm(ctx, b->A, k, sys.d_f, buf, x_prev, r.o, st, tot.ev_used) : run_pcg(ctx, b->A, k, sys.d_f, buf, r.o, st, tot.ev_used));
     HIP_TRY(hipEventRecord(ctx->ev[6], s));
     if (nq > 0)
-        launch_eval(dim, sy.condense, nq, dp.d_prhs + q0, dp.d_pI + q0, dp.d_found + q0, dp.d_phi + size_t(q0) * N, sy.eldof, sys.d_C, sys.d_M, k, buf.x,
-                    dp.d_fint + q0, dp.d_out + q0, s, buf.x_ev, (sec && sy.condense) ? sec->d_fbub : nullptr);
+        launch_eval(sys.em, nq, dp.d_prhs + q0, dp.d_pI + q0, dp.d_found + q0, dp.d_phi + size_t(q0) * N, k, buf.x, dp.d_fint + q0, dp.d_out + q0, s, buf.x_ev,
+                    (sec && sy.condense) ? sec->d_fbub : nullptr);
     if (sec && nq > 0)   // u = u_s + u_p at the evaluation points
         launch_sec_add_primary(dim, nq, dp.d_prhs + q0, dp.d_pI + q0, dp.d_pz + size_t(q0) * (dp.full ? dim : 1), !dp.full,
                                sec->d_src, sec->d_ptr + size_t(chunk) * (REMO_MAX_RHS + 1), sec->R, dp.d_out + q0, s);
@@ -980,6 +978,7 @@ void sens_contract(const Run &r, const System &sys, const DevicePoints &dp, cons
     const DeviceSymbolic &sy = b->sym;
     hipStream_t s = r.s;
     const double *tab = sens_tables(r, sys);
+    const PointLoads pl{dp.d_prhs, dp.d_pI, dp.d_found, dp.d_fint, 0};   // the whole batch's points: the columns name their own ranges
     const bool groups = rq->group != nullptr && rq->n_fun > 0;
     const bool split_times = groups && r.o.time_kernels != 0;   // one synchronisation per functional: measuring runs only
     const size_t ngc = size_t(rq->n_group) * size_t(b->sigma_comp);
@@ -1006,12 +1005,10 @@ void sens_contract(const Run &r, const System &sys, const DevicePoints &dp, cons
         col.xl = sn.block(sys.n, b->n_rhs, true, ca); col.kl = std::min(rq->n_fun - ca * REMO_MAX_RHS, REMO_MAX_RHS); col.cl = j % REMO_MAX_RHS;
         col.qu0 = pts.chunk_begin[cf]; col.nqu = pts.chunk_begin[cf + 1] - col.qu0;
         col.ql0 = pts.chunk_begin[fa]; col.nql = pts.chunk_begin[fa + 1] - col.ql0;
-        launch_sens_contract(r.dim, sy.condense, b->sigma_comp > 1, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, sy.eldof, sys.d_C, sys.d_M, tab, col,
-                             dp.d_prhs, dp.d_pI, dp.d_found, dp.d_fint, b->n_mat, sn.part + size_t(j) * sn.grid * sn.nmc, s);
+        launch_sens_contract(sys.em, tab, col, pl, sn.part + size_t(j) * sn.grid * sn.nmc, s);
         if (!groups) continue;
         if (split_times) HIP_TRY(hipEventRecord(tev[1], s));
-        launch_sens_contract(r.dim, sy.condense, b->sigma_comp > 1, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, sy.eldof, sys.d_C, sys.d_M, tab, col,
-                             dp.d_prhs, dp.d_pI, dp.d_found, dp.d_fint, b->n_mat, sn.ev, s, true);
+        launch_sens_contract(sys.em, tab, col, pl, sn.ev, s, true);
         if (split_times) HIP_TRY(hipEventRecord(tev[2], s));
         launch_sens_group_sum(b->sigma_comp, b->nt, rq->n_group, sn.keys, sn.perm, sn.off, sn.ev, sn.cpart, sn.d_dJg + size_t(j) * ngc, s);
         if (split_times) {
@@ -1092,6 +1089,7 @@ void pairs_contract(const Run &r, const System &sys, const DevicePoints &dp, con
     const DeviceSymbolic &sy = b->sym;
     hipStream_t s = r.s;
     const double *tab = sens_tables(r, sys);
+    const PointLoads pl{dp.d_prhs, dp.d_pI, dp.d_found, dp.d_fint, 0};   // the whole batch's points: the columns name their own ranges
     const int np = rq->n_pair, nchunk = pts.forward_chunks;
     struct Launch { PairColumns pc; int first, count; };
     // the launches of the (chunk, chunk) partition with at most per_launch pairs each; order[i]: the caller's index of the pair at
@@ -1140,9 +1138,7 @@ void pairs_contract(const Run &r, const System &sys, const DevicePoints &dp, con
     if (fused) {
         HIP_TRY(hipMemcpyAsync(pr.d_slots, slots.data(), sizeof(int32_t) * slots.size(), hipMemcpyHostToDevice, s));
         for (const Launch &L : launches)
-            launch_pair_contract(r.dim, sy.condense, b->sigma_comp > 1, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, sy.eldof, sys.d_C, sys.d_M, tab, L.pc,
-                                 L.count, pr.d_slots + 2 * size_t(L.first), dp.d_prhs, dp.d_pI, dp.d_found, dp.d_fint, b->n_mat, grid,
-                                 pr.part + size_t(L.first) * grid * pr.nmc, s);
+            launch_pair_contract(sys.em, tab, L.pc, L.count, pr.d_slots + 2 * size_t(L.first), pl, grid, pr.part + size_t(L.first) * grid * pr.nmc, s);
     } else {   // remo_debug_tune key 42 = 0: every pair as a functional whose adjoint column is the forward column a
         n_launch = size_t(np);
         for (int i = 0; i < np; ++i) {
@@ -1152,8 +1148,7 @@ void pairs_contract(const Run &r, const System &sys, const DevicePoints &dp, con
             col.xl = sn.block(sys.n, b->n_rhs, false, ca); col.kl = std::min(b->n_rhs - ca * REMO_MAX_RHS, REMO_MAX_RHS); col.cl = a % REMO_MAX_RHS;
             col.qu0 = pts.chunk_begin[cc]; col.nqu = pts.chunk_begin[cc + 1] - col.qu0;
             col.ql0 = pts.chunk_begin[ca]; col.nql = pts.chunk_begin[ca + 1] - col.ql0;
-            launch_sens_contract(r.dim, sy.condense, b->sigma_comp > 1, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, sy.eldof, sys.d_C, sys.d_M, tab, col,
-                                 dp.d_prhs, dp.d_pI, dp.d_found, dp.d_fint, b->n_mat, pr.part + size_t(i) * grid * pr.nmc, s);
+            launch_sens_contract(sys.em, tab, col, pl, pr.part + size_t(i) * grid * pr.nmc, s);
         }
     }
     launch_sens_reduce(np, grid, pr.nmc, pr.part, pr.d_dP, s);
@@ -1186,8 +1181,7 @@ void pairs_contract(const Run &r, const System &sys, const DevicePoints &dp, con
     HIP_TRY(hipEventRecord(ctx->ev[4], s));
     for (const Launch &L : slices) {
         if (split_times) HIP_TRY(hipEventRecord(tev[0], s));
-        launch_pair_contract(r.dim, sy.condense, b->sigma_comp > 1, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, sy.eldof, sys.d_C, sys.d_M, tab, L.pc,
-                             L.count, pr.d_gslots + 2 * size_t(L.first), dp.d_prhs, dp.d_pI, dp.d_found, dp.d_fint, b->n_mat, pr.grid, pr.ev, s, true);
+        launch_pair_contract(sys.em, tab, L.pc, L.count, pr.d_gslots + 2 * size_t(L.first), pl, pr.grid, pr.ev, s, true);
         if (split_times) HIP_TRY(hipEventRecord(tev[1], s));
         launch_sens_group_sum_batch(b->sigma_comp, b->nt, rq->n_group, pr.keys, pr.perm, pr.off, pr.ev, pr.cpart, pr.d_dPg + size_t(L.first) * ngc, L.count,
                                     int64_t(evs), int64_t(ngc), s);
@@ -1256,11 +1250,8 @@ ErrEst err_take(const Run &r) {
 
 // eta_e^2 of the k columns of a chunk (solution in x[n][k]) into the slabs from column `slab0` on, while the chunk's solutions are there
 void err_facets_chunk(const Run &r, const System &sys, const DevicePoints &dp, const double *x, const ErrEst &e, int slab0, int k, int q0, int nq) {
-    const remo_batch *b = r.b;
-    const DeviceSymbolic &sy = b->sym;
-    const FieldSources src{dp.d_prhs + q0, dp.d_pI + q0, dp.d_found + q0, dp.d_fint + q0, nq};
-    launch_error_facets(r.dim, sy.condense, b->sigma_comp > 1, b->nt, b->d_coords, sy.conn, b->d_mat, sy.eperm, b->d_sigma, b->n_mat, sy.eldof, sy.adjptr, sy.adj,
-                        sys.d_C, sys.d_M, e.d_rule, k, x, src, e.eta2 + size_t(b->nt) * size_t(slab0), r.s);
+    const PointLoads src{dp.d_prhs + q0, dp.d_pI + q0, dp.d_found + q0, dp.d_fint + q0, nq};
+    launch_error_facets(sys.em, e.d_rule, k, x, src, e.eta2 + size_t(r.b->nt) * size_t(slab0), r.s);
 }
 
 // E_j and the group sums of every functional, in the fixed orders of the sensitivity sums
@@ -1388,7 +1379,7 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         assemble_system(r, sys);
         HIP_TRY(hipEventRecord(ctx->ev[2], s));
         locate_points(r, points, dp);
-        check_secondary_sources(r, sec);
+        check_secondary_sources(r, sys, sec);
         field_locate_points(r, fld);
         HIP_TRY(hipEventRecord(ctx->ev[3], s));
         VertexBlock vb;

@@ -109,10 +109,7 @@ REMO_HD double error_facet(const double *rule, int f, const double *Xe, const do
 // neighbour across a facet comes from the adjacency list of the facet's dof row (eldof: local dofs 16 .. 19 in 3D, the first dof of
 // each edge in 2D; row -1: a Dirichlet facet).  src: the chunk's axis points (2D, condensed: the bubble loads, as k_field_eval reads
 // them).  rule: device copy of err_rule(dim).
-void launch_error_facets(int dim, bool condense, bool tensor, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat,
-                         const int32_t *eperm, const double *sigma, int n_mat, const int32_t *eldof, const int32_t *adjptr, const uint32_t *adj,
-                         const double *C, const double *M, const double *rule, int k, const double *x, const FieldSources &src, double *eta2,
-                         hipStream_t s);
+void launch_error_facets(const ElemMesh &em, const double *rule, int k, const double *x, const PointLoads &src, double *eta2, hipStream_t s);
 // ev[t] = -sqrt(eu[t] * el[t]) (ev may be nullptr) and part[workgroup] = the workgroup's sum of them, sens_grid(nt) workgroups in a
 // fixed order: launch_sens_reduce / launch_sens_group_sum, which negate, then give E_j and the group sums.
 void launch_error_combine(int64_t nt, const double *eu, const double *el, double *ev, double *part, hipStream_t s);

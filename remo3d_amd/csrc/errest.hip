@@ -12,6 +12,8 @@
 //
 // k_error_combine: E_je = sqrt(eta_e^2(u) eta_e^2(lambda)) per functional, with the sign k_sens_reduce / k_sens_group_sum take off
 // again, and the workgroups' sums in a fixed order.
+// err_load puts together elem_access.h's reads of an element (vertices, conductivity, a column's element vector, the condensed bubble).
+#include "elem_access.h"
 #include "errest.h"
 #include "sens.h"
 #include "wave_util.h"
@@ -33,40 +35,19 @@ const double kRule3[ErrRule<3>::NTAB] = {
     0.09157621350977074346, 0.81684757298045851308, 0.09157621350977074346, 0.10995174365532186764,
     0.09157621350977074346, 0.09157621350977074346, 0.81684757298045851308, 0.10995174365532186764};
 
-// vertices, conductivity and column `col` of the element vector of device element t (2D condensed: the bubble recovered as k_eval
-// does it); false: the material is out of range (k_metric_terms has flagged it: the batch fails)
+// vertices, conductivity and column `col` of the element vector of device element t; false: the material is out of range
 template <int DIM, bool CONDENSE, bool TENSOR>
 __device__ __forceinline__ bool err_load(int32_t t, const double *__restrict__ coords, const int32_t *__restrict__ conn, const int32_t *__restrict__ mat,
                                          const int32_t *__restrict__ eperm, const double *__restrict__ sigma, int n_mat, const int32_t *__restrict__ eldof,
                                          const double *__restrict__ C, const double *__restrict__ M, int k, const double *__restrict__ x, int col,
-                                         const FieldSources &src, double *X, double *S, double *xe) {
-    constexpr int NB = DIM + 1, N = P3<DIM>::NLD, NT = P3<DIM>::NTERM, NK = (DIM == 2 && CONDENSE) ? 9 : N;
-    constexpr int NS = TENSOR ? SigmaTensor<DIM>::N : 1;
-    const int32_t m = mat[eperm ? int64_t(eperm[t]) : int64_t(t)];
-    if (m < 0 || m >= n_mat) return false;
-#pragma unroll
-    for (int a = 0; a < NB; ++a) {
-        const int64_t v = conn[int64_t(t) * NB + a];
-#pragma unroll
-        for (int d = 0; d < DIM; ++d) X[a * DIM + d] = coords[v * DIM + d];
-    }
-#pragma unroll
-    for (int i = 0; i < NS; ++i) S[i] = sigma[int64_t(m) * NS + i];
-    const int32_t *ed = eldof + int64_t(t) * N;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const int32_t row = (i < NK) ? ed[i] : -1;
-        xe[i] = (row >= 0) ? x[int64_t(row) * k + col] : 0.0;
-    }
-    if constexpr (DIM == 2 && CONDENSE) {   // x_9 = (f_9 - sum_j K_9j x_j) / K_99
-        const double *ce = C + int64_t(t) * NT;
-        double acc = 0.0;
-        for (int w = 0; w < src.nq; ++w)
-            if (src.pt_I[w] != 0.0 && src.found[w] == t && src.pt_rhs[w] == col) acc += src.fint[w];
-#pragma unroll
-        for (int j = 0; j < 9; ++j) acc -= kentry<2>(ce, M, 9, j) * xe[j];
-        xe[9] = acc / kentry<2>(ce, M, 9, 9);
-    }
+                                         const PointLoads &src, double *X, double *S, double (&xe)[P3<DIM>::NLD]) {
+    constexpr int N = P3<DIM>::NLD, NT = P3<DIM>::NTERM, NK = (DIM == 2 && CONDENSE) ? 9 : N;
+    const int32_t m = elem_material(mat, eperm, t, n_mat);
+    if (m < 0) return false;
+    load_vertices<DIM>(coords, conn, t, X);
+    load_sigma<DIM, TENSOR>(sigma, m, S);
+    gather_column<N, NK>(eldof + int64_t(t) * N, x, k, col, xe);
+    if constexpr (DIM == 2 && CONDENSE) recover_bubble(t, C + int64_t(t) * NT, M, col, 0, src.nq, src.pt_rhs, src.pt_I, src.found, src.fint, xe);
     return true;
 }
 
@@ -78,7 +59,7 @@ __global__ void __launch_bounds__(256) k_error_facets(int64_t nt, const double *
                                                       const int32_t *__restrict__ mat, const int32_t *__restrict__ eperm, const double *__restrict__ sigma,
                                                       int n_mat, const int32_t *__restrict__ eldof, const int32_t *__restrict__ adjptr,
                                                       const uint32_t *__restrict__ adj, const double *__restrict__ C, const double *__restrict__ M,
-                                                      const double *__restrict__ rule, int k, const double *__restrict__ x, FieldSources src, int kp_log2,
+                                                      const double *__restrict__ rule, int k, const double *__restrict__ x, PointLoads src, int kp_log2,
                                                       double *__restrict__ eta2) {
     constexpr int NB = DIM + 1, N = P3<DIM>::NLD, NS = TENSOR ? SigmaTensor<DIM>::N : 1, NTAB = ErrRule<DIM>::NTAB;
     constexpr int FD0 = (DIM == 3) ? 16 : 3, FDS = (DIM == 3) ? 1 : 2;   // local dof of facet f: FD0 + FDS * f
@@ -144,26 +125,16 @@ __global__ void __launch_bounds__(256) k_error_combine(int64_t nt, const double 
 
 const double *err_rule(int dim) { return dim == 2 ? kRule2 : kRule3; }
 
-void launch_error_facets(int dim, bool condense, bool tensor, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat,
-                         const int32_t *eperm, const double *sigma, int n_mat, const int32_t *eldof, const int32_t *adjptr, const uint32_t *adj,
-                         const double *C, const double *M, const double *rule, int k, const double *x, const FieldSources &src, double *eta2,
-                         hipStream_t s) {
-    if (nt <= 0 || k <= 0) return;
+void launch_error_facets(const ElemMesh &em, const double *rule, int k, const double *x, const PointLoads &src, double *eta2, hipStream_t s) {
+    if (em.nt <= 0 || k <= 0) return;
     int kp_log2 = 0;
     while ((1 << kp_log2) < k) ++kp_log2;
     const int ppb = 256 >> kp_log2;
-    const unsigned grid = unsigned((nt + ppb - 1) / ppb);
-#define REMO_ERR_LAUNCH(D, CO, TE) \
-    hipLaunchKernelGGL((k_error_facets<D, CO, TE>), dim3(grid), dim3(256), 0, s, nt, coords, conn, mat, eperm, sigma, n_mat, eldof, adjptr, adj, C, M, rule, k, x, \
-                       src, kp_log2, eta2)
-    if (dim == 3) {
-        if (tensor) REMO_ERR_LAUNCH(3, false, true); else REMO_ERR_LAUNCH(3, false, false);
-    } else if (condense) {
-        if (tensor) REMO_ERR_LAUNCH(2, true, true); else REMO_ERR_LAUNCH(2, true, false);
-    } else {
-        if (tensor) REMO_ERR_LAUNCH(2, false, true); else REMO_ERR_LAUNCH(2, false, false);
-    }
-#undef REMO_ERR_LAUNCH
+    const unsigned grid = unsigned((em.nt + ppb - 1) / ppb);
+    for_elem_kind(em.dim, em.condense, em.tensor(), [&](auto d, auto co, auto te) {
+        hipLaunchKernelGGL((k_error_facets<decltype(d)::value, decltype(co)::value, decltype(te)::value>), dim3(grid), dim3(256), 0, s, em.nt, em.coords, em.conn,
+                           em.mat, em.eperm, em.sigma, em.n_mat, em.eldof, em.adjptr, em.adj, em.C, em.M, rule, k, x, src, kp_log2, eta2);
+    });
 }
 
 void launch_error_combine(int64_t nt, const double *eu, const double *el, double *ev, double *part, hipStream_t s) {

@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "../../include/remo3d_hip.h"
+#include "elem_access.h"
 #include "fem_p3.h"
 
 namespace remo {
@@ -147,19 +148,10 @@ struct FieldCols {
     int n = 0;
     int col[REMO_MAX_RHS] = {}, slot[REMO_MAX_RHS] = {};
 };
-// The axis points of the block's right-hand sides (2D, condensed: the bubble loads of sources inside an element, as k_eval reads them)
-struct FieldSources {
-    const int32_t *pt_rhs = nullptr;
-    const double *pt_I = nullptr;
-    const int32_t *found = nullptr;
-    const double *fint = nullptr;
-    int nq = 0;
-};
 // u[slot][n_pts], grad[slot][n_pts][dim], J[slot][n_pts][dim] of the columns of `cols` (any of the three may be nullptr); NaN
-// where found[q] == INT_MAX.  sigma: [n_mat] scalars, or (tensor) [n_mat][3 | 6] upper triangles; mat is indexed through eperm.
-void launch_field_eval(int dim, bool condense, bool tensor, int64_t n_pts, const double *pts, const int32_t *found, const double *coords,
-                       const int32_t *conn, const int32_t *mat, const int32_t *eperm, const double *sigma, int n_mat, const int32_t *eldof,
-                       const double *C, const double *M, int k, const double *x, const FieldCols &cols, const FieldSources &src, double *u,
-                       double *grad, double *J, hipStream_t s);
+// where found[q] == INT_MAX.  em.sigma: [n_mat] scalars, or (tensor) [n_mat][3 | 6] upper triangles; src: the axis points of the
+// block's right-hand sides (elem_access.h).
+void launch_field_eval(const ElemMesh &em, int64_t n_pts, const double *pts, const int32_t *found, int k, const double *x, const FieldCols &cols,
+                       const PointLoads &src, double *u, double *grad, double *J, hipStream_t s);
 
 }  // namespace remo

@@ -16,7 +16,8 @@
 // fastest: the kp lanes of a point read the kp neighbouring values of a row of x[n][k] in one instruction - one 8 k byte piece of a
 // row per request instead of one 8-byte value per lane and row.  Every lane holds one column's element vector in registers
 // (compile-time indices only) and calls field_point, the code remo_host_field_element runs.  The results go through LDS so that
-// the stores run along the points: plain vector stores, consecutive lanes on consecutive addresses.
+// the stores run along the points: plain vector stores, consecutive lanes on consecutive addresses.  Its reads of the element are
+// elem_access.h's; field_elem_setup keeps a vertex loop of its own, which folds the element's box in.
 #include <limits.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -24,6 +25,7 @@
 #include <cmath>
 #include <stdexcept>
 
+#include "elem_access.h"
 #include "field.h"
 
 namespace remo {
@@ -194,7 +196,7 @@ __global__ void __launch_bounds__(256) k_field_eval(int64_t n_pts, const double 
                                                     const double *__restrict__ coords, const int32_t *__restrict__ conn, const int32_t *__restrict__ mat,
                                                     const int32_t *__restrict__ eperm, const double *__restrict__ sigma, int n_mat,
                                                     const int32_t *__restrict__ eldof, const double *__restrict__ C, const double *__restrict__ M, int k,
-                                                    const double *__restrict__ x, FieldCols cols, FieldSources src, int kp_log2, double *__restrict__ u,
+                                                    const double *__restrict__ x, FieldCols cols, PointLoads src, int kp_log2, double *__restrict__ u,
                                                     double *__restrict__ grad, double *__restrict__ J) {
     constexpr int NB = DIM + 1, N = P3<DIM>::NLD, NT = P3<DIM>::NTERM, NK = (DIM == 2 && CONDENSE) ? 9 : N, NO = FieldOut<DIM>::N;
     constexpr int NS = TENSOR ? SigmaTensor<DIM>::N : 1;
@@ -208,34 +210,15 @@ __global__ void __launch_bounds__(256) k_field_eval(int64_t n_pts, const double 
     for (int i = 0; i < NO; ++i) out[i] = nan("");
     const int32_t t = (p < n_pts && col >= 0) ? found[p] : INT_MAX;
     if (t != INT_MAX) {
-        int32_t m = mat[eperm ? int64_t(eperm[t]) : int64_t(t)];
-        if (m >= 0 && m < n_mat) {   // (otherwise k_metric_terms has flagged it: the batch fails)
+        const int32_t m = elem_material(mat, eperm, t, n_mat);
+        if (m >= 0) {   // (otherwise k_metric_terms has flagged it: the batch fails)
             double X[NB * DIM], P[DIM], S[NS], xe[N];
-#pragma unroll
-            for (int a = 0; a < NB; ++a) {
-                const int64_t v = conn[int64_t(t) * NB + a];
-#pragma unroll
-                for (int d = 0; d < DIM; ++d) X[a * DIM + d] = coords[v * DIM + d];
-            }
+            load_vertices<DIM>(coords, conn, t, X);
 #pragma unroll
             for (int d = 0; d < DIM; ++d) P[d] = pts[p * DIM + d];
-#pragma unroll
-            for (int i = 0; i < NS; ++i) S[i] = sigma[int64_t(m) * NS + i];
-            const int32_t *ed = eldof + int64_t(t) * N;
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                const int32_t row = (i < NK) ? ed[i] : -1;
-                xe[i] = (row >= 0) ? x[int64_t(row) * k + col] : 0.0;
-            }
-            if constexpr (DIM == 2 && CONDENSE) {   // the cell bubble as k_eval recovers it: x_9 = (f_9 - sum_j K_9j x_j) / K_99
-                const double *ce = C + int64_t(t) * NT;
-                double acc = 0.0;
-                for (int w = 0; w < src.nq; ++w)
-                    if (src.pt_I[w] != 0.0 && src.found[w] == t && src.pt_rhs[w] == col) acc += src.fint[w];
-#pragma unroll
-                for (int j = 0; j < 9; ++j) acc -= kentry<2>(ce, M, 9, j) * xe[j];
-                xe[9] = acc / kentry<2>(ce, M, 9, 9);
-            }
+            load_sigma<DIM, TENSOR>(sigma, m, S);
+            gather_column<N, NK>(eldof + int64_t(t) * N, x, k, col, xe);
+            if constexpr (DIM == 2 && CONDENSE) recover_bubble(t, C + int64_t(t) * NT, M, col, 0, src.nq, src.pt_rhs, src.pt_I, src.found, src.fint, xe);
             double res[NO];
             if (field_point<DIM, TENSOR>(X, P, xe, S, res)) {
 #pragma unroll
@@ -363,26 +346,17 @@ void launch_field_elem(int64_t n_pts, const int32_t *found, const int32_t *eperm
     hipLaunchKernelGGL(k_field_elem, dim3(unsigned((n_pts + 255) / 256)), dim3(256), 0, s, n_pts, found, eperm, elem);
 }
 
-void launch_field_eval(int dim, bool condense, bool tensor, int64_t n_pts, const double *pts, const int32_t *found, const double *coords,
-                       const int32_t *conn, const int32_t *mat, const int32_t *eperm, const double *sigma, int n_mat, const int32_t *eldof,
-                       const double *C, const double *M, int k, const double *x, const FieldCols &cols, const FieldSources &src, double *u,
-                       double *grad, double *J, hipStream_t s) {
+void launch_field_eval(const ElemMesh &em, int64_t n_pts, const double *pts, const int32_t *found, int k, const double *x, const FieldCols &cols,
+                       const PointLoads &src, double *u, double *grad, double *J, hipStream_t s) {
     if (n_pts <= 0 || cols.n <= 0) return;
     int kp_log2 = 0;
     while ((1 << kp_log2) < cols.n) ++kp_log2;
     const int ppb = 256 >> kp_log2;
     const unsigned grid = unsigned((n_pts + ppb - 1) / ppb);
-#define REMO_FIELD_LAUNCH(D, CO, TE) \
-    hipLaunchKernelGGL((k_field_eval<D, CO, TE>), dim3(grid), dim3(256), 0, s, n_pts, pts, found, coords, conn, mat, eperm, sigma, n_mat, eldof, C, M, k, x, \
-                       cols, src, kp_log2, u, grad, J)
-    if (dim == 3) {
-        if (tensor) REMO_FIELD_LAUNCH(3, false, true); else REMO_FIELD_LAUNCH(3, false, false);
-    } else if (condense) {
-        if (tensor) REMO_FIELD_LAUNCH(2, true, true); else REMO_FIELD_LAUNCH(2, true, false);
-    } else {
-        if (tensor) REMO_FIELD_LAUNCH(2, false, true); else REMO_FIELD_LAUNCH(2, false, false);
-    }
-#undef REMO_FIELD_LAUNCH
+    for_elem_kind(em.dim, em.condense, em.tensor(), [&](auto d, auto co, auto te) {
+        hipLaunchKernelGGL((k_field_eval<decltype(d)::value, decltype(co)::value, decltype(te)::value>), dim3(grid), dim3(256), 0, s, n_pts, pts, found, em.coords,
+                           em.conn, em.mat, em.eperm, em.sigma, em.n_mat, em.eldof, em.C, em.M, k, x, cols, src, kp_log2, u, grad, J);
+    });
 }
 
 }  // namespace remo

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "elem_access.h"
+
 namespace remo {
 
 constexpr int kMaxPartialBlocks = 1024;   // grid cap of every kernel that leaves per-block partial sums
@@ -142,11 +144,11 @@ template <class T> struct CsrViewT {
 };
 using CsrView = CsrViewT<double>;
 
-void launch_metric_terms(int dim, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat, const int32_t *eperm /* or null */,
-                         const double *sigma, int nmat, double *C, int32_t *errflag, hipStream_t s);
-// anisotropic materials: sigma_tensor[nmat][3 (2D: rr, rz, zz) or 6 (3D: xx, xy, xz, yy, yz, zz)] (fem_p3.h metric_terms_tensor)
-void launch_metric_terms_tensor(int dim, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat, const int32_t *eperm /* or null */,
-                                const double *sigma_tensor, int nmat, double *C, int32_t *errflag, hipStream_t s);
+// WRITES em.C[nt][NTERM] (the view's pointer is const for its readers; the caller owns the buffer) from em.sigma[n_mat] scalars
+// (em.eperm may be null); a bad material or a degenerate element raises bit 1 of *errflag
+void launch_metric_terms(const ElemMesh &em, int32_t *errflag, hipStream_t s);
+// anisotropic materials: em.sigma[n_mat][3 (2D: rr, rz, zz) or 6 (3D: xx, xy, xz, yy, yz, zz)] (fem_p3.h metric_terms_tensor)
+void launch_metric_terms_tensor(const ElemMesh &em, int32_t *errflag, hipStream_t s);
 // rows [pair_begin, pair_end) (the two dofs of every free edge) get their values interleaved: entry e of the first row
 // at rowptr[row] + 2e, of the second at rowptr[row] + 2e + 1 (CsrViewT below); all other rows plain CSR
 void launch_diag_rows(int dim, int64_t row0, int64_t nfree, const int32_t *adjptr, const uint32_t *adj, const double *C, const double *M, double *dinv, hipStream_t s);
@@ -220,16 +222,13 @@ void launch_point_shapes(int dim, int npts, const double *pz, const int32_t *fou
 void launch_point_shapes_at(int dim, int npts, const double *pp, const int32_t *found, const double *coords,
                             const int32_t *conn, double *phi, int32_t *errflag, hipStream_t s);
 // f[n*k] += I * phi at sources (with the condensed-bubble fold in 2D); bubble loads kept in fint[npts]
-void launch_build_rhs(int dim, bool condense, int npts, const int32_t *pt_rhs, const double *pt_I,
-                      const int32_t *found, const double *phi, const int32_t *eldof, const double *C,
-                      const double *M, int k, double *f, double *fint, hipStream_t s);
+void launch_build_rhs(const ElemMesh &em, int npts, const int32_t *pt_rhs, const double *pt_I, const int32_t *found, const double *phi, int k, double *f,
+                      double *fint, hipStream_t s);
 // x_ev != nullptr: the values of x that point q reads are x_ev[q * N + i] (PcgBuffersT::x_ev, laid out by launch_eval_slots)
-void launch_eval(int dim, bool condense, int npts, const int32_t *pt_rhs, const double *pt_I, const int32_t *found,
-                 const double *phi, const int32_t *eldof, const double *C, const double *M, int k,
-                 const double *x, const double *fint, double *out, hipStream_t s, const double *x_ev = nullptr,
+void launch_eval(const ElemMesh &em, int npts, const int32_t *pt_rhs, const double *pt_I, const int32_t *found, const double *phi, int k, const double *x,
+                 const double *fint, double *out, hipStream_t s, const double *x_ev = nullptr,
                  const double *fbub = nullptr);   // fbub[element][k]: bubble loads of the secondary formulation (2D condensed), nullptr: none
 // at[q * N + i] = row * k + pt_rhs[q] of local dof i of point q's element (N = 20 in 3D, 10 in 2D), -1 where k_eval reads no x
-void launch_eval_slots(int dim, bool condense, int npts, const int32_t *pt_rhs, const int32_t *found, const int32_t *eldof, int k,
-                       int64_t *at, hipStream_t s);
+void launch_eval_slots(const ElemMesh &em, int npts, const int32_t *pt_rhs, const int32_t *found, int k, int64_t *at, hipStream_t s);
 
 }  // namespace remo

@@ -5,11 +5,13 @@
 // The vector kernels of the PCG step and the Chebyshev steps are pcg_kernels.hip, the patch operator patch.hip.
 // All of it is HBM/L2-bound sparse work: no MFMA (a sparse row is not a dense contraction); the levers are
 // coalesced CSR streams, DPP (not LDS) cross-lane reductions, XCD-aware row placement and LDS-staged reference
-// tensors.  Reference lines each kernel replaces are cited at the kernel.
+// tensors.  Reference lines each kernel replaces are cited at the kernel.  Element reads shared with the element passes of the
+// other files (sens, pairs, errest, field, secondary) are elem_access.h's; the launchers that need the mesh take its ElemMesh view.
 #include "kernels.h"
 
 #include <limits.h>
 
+#include "elem_access.h"
 #include "fem_p3.h"
 #include "wave_util.h"
 #include "kutil.h"
@@ -38,13 +40,8 @@ __global__ void __launch_bounds__(256) k_metric_terms(int64_t nt, const double *
     const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (t >= nt) return;
     double X[NB * DIM];
-#pragma unroll
-    for (int a = 0; a < NB; ++a) {
-        const int64_t v = conn[t * NB + a];
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) X[a * DIM + k] = coords[v * DIM + k];
-    }
-    const int m = mat[eperm ? int64_t(eperm[t]) : t];   // materials stay in the caller's element order (symbolic_gpu.hip)
+    load_vertices<DIM>(coords, conn, t, X);
+    const int m = mat[caller_element(eperm, t)];   // the raw index: this is the kernel that reports a bad one (the others read elem_material)
     double c[NT];
     bool ok = (m >= 0 && m < nmat);
     if (ok) ok = metric_terms<DIM>(X, sigma[m], c);
@@ -57,13 +54,13 @@ __global__ void __launch_bounds__(256) k_metric_terms(int64_t nt, const double *
     for (int i = 0; i < NT; ++i) C[t * NT + i] = c[i];
 }
 
-void launch_metric_terms(int dim, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat, const int32_t *eperm,
-                         const double *sigma, int nmat, double *C, int32_t *errflag, hipStream_t s) {
-    const int grid = int((nt + 255) / 256);
-    if (dim == 2)
-        hipLaunchKernelGGL(k_metric_terms<2>, dim3(grid), dim3(256), 0, s, nt, coords, conn, mat, eperm, sigma, nmat, C, errflag);
+void launch_metric_terms(const ElemMesh &em, int32_t *errflag, hipStream_t s) {
+    const int grid = int((em.nt + 255) / 256);
+    double *C = const_cast<double *>(em.C);   // the one launch that writes what every other element pass reads through the view
+    if (em.dim == 2)
+        hipLaunchKernelGGL(k_metric_terms<2>, dim3(grid), dim3(256), 0, s, em.nt, em.coords, em.conn, em.mat, em.eperm, em.sigma, em.n_mat, C, errflag);
     else
-        hipLaunchKernelGGL(k_metric_terms<3>, dim3(grid), dim3(256), 0, s, nt, coords, conn, mat, eperm, sigma, nmat, C, errflag);
+        hipLaunchKernelGGL(k_metric_terms<3>, dim3(grid), dim3(256), 0, s, em.nt, em.coords, em.conn, em.mat, em.eperm, em.sigma, em.n_mat, C, errflag);
 }
 
 // the same for anisotropic materials: sigma_tensor[nmat][SigmaTensor<DIM>::N] (upper triangles, remo_solve_batch_tensor)
@@ -76,17 +73,12 @@ __global__ void __launch_bounds__(256) k_metric_terms_tensor(int64_t nt, const d
     const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (t >= nt) return;
     double X[NB * DIM];
-#pragma unroll
-    for (int a = 0; a < NB; ++a) {
-        const int64_t v = conn[t * NB + a];
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) X[a * DIM + k] = coords[v * DIM + k];
-    }
-    const int m = mat[eperm ? int64_t(eperm[t]) : t];
+    load_vertices<DIM>(coords, conn, t, X);
+    const int m = mat[caller_element(eperm, t)];
     double c[NT];
     bool ok = (m >= 0 && m < nmat);
     if (ok) {
-        double S[NS];
+        double S[NS];   // (read in place, not through load_sigma: with it the 3D kernel is allocated 72 registers for 76 and is another kernel)
 #pragma unroll
         for (int i = 0; i < NS; ++i) S[i] = sigma_tensor[int64_t(m) * NS + i];
         ok = metric_terms_tensor<DIM>(X, S, c);
@@ -100,13 +92,13 @@ __global__ void __launch_bounds__(256) k_metric_terms_tensor(int64_t nt, const d
     for (int i = 0; i < NT; ++i) C[t * NT + i] = c[i];
 }
 
-void launch_metric_terms_tensor(int dim, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat, const int32_t *eperm,
-                                const double *sigma_tensor, int nmat, double *C, int32_t *errflag, hipStream_t s) {
-    const int grid = int((nt + 255) / 256);
-    if (dim == 2)
-        hipLaunchKernelGGL(k_metric_terms_tensor<2>, dim3(grid), dim3(256), 0, s, nt, coords, conn, mat, eperm, sigma_tensor, nmat, C, errflag);
+void launch_metric_terms_tensor(const ElemMesh &em, int32_t *errflag, hipStream_t s) {
+    const int grid = int((em.nt + 255) / 256);
+    double *C = const_cast<double *>(em.C);
+    if (em.dim == 2)
+        hipLaunchKernelGGL(k_metric_terms_tensor<2>, dim3(grid), dim3(256), 0, s, em.nt, em.coords, em.conn, em.mat, em.eperm, em.sigma, em.n_mat, C, errflag);
     else
-        hipLaunchKernelGGL(k_metric_terms_tensor<3>, dim3(grid), dim3(256), 0, s, nt, coords, conn, mat, eperm, sigma_tensor, nmat, C, errflag);
+        hipLaunchKernelGGL(k_metric_terms_tensor<3>, dim3(grid), dim3(256), 0, s, em.nt, em.coords, em.conn, em.mat, em.eperm, em.sigma, em.n_mat, C, errflag);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1037,10 +1029,7 @@ __global__ void k_point_shapes(int npts, const double *__restrict__ pz, const in
         return;
     }
     double X[NB * DIM], P[DIM], l[NB], ph[N];
-    for (int a = 0; a < NB; ++a) {
-        const int64_t v = conn[int64_t(t) * NB + a];
-        for (int k = 0; k < DIM; ++k) X[a * DIM + k] = coords[v * DIM + k];
-    }
+    load_vertices<DIM>(coords, conn, t, X);
     for (int k = 0; k < DIM; ++k) P[k] = 0.0;
     P[DIM - 1] = pz[q];
     barycentrics<DIM>(X, P, l);
@@ -1073,12 +1062,7 @@ __global__ void __launch_bounds__(64) k_point_shapes_at(int npts, const double *
         atomicOr(errflag, 2);
     } else {
         double X[NB * DIM], P[DIM];
-#pragma unroll
-        for (int a = 0; a < NB; ++a) {
-            const int64_t v = conn[int64_t(t) * NB + a];
-#pragma unroll
-            for (int k = 0; k < DIM; ++k) X[a * DIM + k] = coords[v * DIM + k];
-        }
+        load_vertices<DIM>(coords, conn, t, X);
 #pragma unroll
         for (int k = 0; k < DIM; ++k) P[k] = pp[int64_t(q) * DIM + k];
         point_shapes<DIM>(X, P, ph);
@@ -1114,7 +1098,7 @@ __global__ void k_build_rhs(int npts, const int32_t *__restrict__ pt_rhs, const 
         const int32_t row = ed[i];
         if (row >= 0) atomicAdd(&f[int64_t(row) * k + c], I * phi[q * N + i]);
     }
-    if (CONDENSE) {  // fold the bubble load: f_b -= K_bi K_ii^-1 f_i
+    if (CONDENSE) {  // fold the bubble load: f_b -= K_bi K_ii^-1 f_i (recover_bubble, elem_access.h, takes it back out of fint)
         const double fi = I * phi[q * N + 9];
         fint[q] = fi;
         if (fi != 0.0) {
@@ -1128,21 +1112,19 @@ __global__ void k_build_rhs(int npts, const int32_t *__restrict__ pt_rhs, const 
     }
 }
 
-void launch_build_rhs(int dim, bool condense, int npts, const int32_t *pt_rhs, const double *pt_I, const int32_t *found,
-                      const double *phi, const int32_t *eldof, const double *C, const double *M, int k, double *f, double *fint,
-                      hipStream_t s) {
+void launch_build_rhs(const ElemMesh &em, int npts, const int32_t *pt_rhs, const double *pt_I, const int32_t *found, const double *phi, int k, double *f,
+                      double *fint, hipStream_t s) {
     const int grid = (npts + 63) / 64;
-    if (dim == 3)
-        hipLaunchKernelGGL((k_build_rhs<3, false>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, f, fint);
-    else if (condense)
-        hipLaunchKernelGGL((k_build_rhs<2, true>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, f, fint);
-    else
-        hipLaunchKernelGGL((k_build_rhs<2, false>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, f, fint);
+    for_elem_kind(em.dim, em.condense, [&](auto d, auto co) {
+        hipLaunchKernelGGL((k_build_rhs<decltype(d)::value, decltype(co)::value>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, em.eldof, em.C, em.M, k,
+                           f, fint);
+    });
 }
 
 // One thread per point: u_h(point) = sum phi_i x[dof_i] (+ recovered bubble when condensed:
 // u_i = K_ii^-1 (f_i - K_ib u_b), ngsolve_functions.py:53-56).  Points with I != 0 are sources:
-// they get NaN-free zeros in `out` slots they do not own (out is indexed by point).
+// they get NaN-free zeros in `out` slots they do not own (out is indexed by point).  (The bubble here is weighted by phi, reads x_ev
+// and adds fbub: the plain recovery of a whole column is recover_bubble, elem_access.h.)
 template <int DIM, bool CONDENSE>
 __global__ void k_eval(int npts, const int32_t *__restrict__ pt_rhs, const double *__restrict__ pt_I,
                        const int32_t *__restrict__ found, const double *__restrict__ phi, const int32_t *__restrict__ eldof,
@@ -1180,16 +1162,13 @@ __global__ void k_eval(int npts, const int32_t *__restrict__ pt_rhs, const doubl
     out[q] = s;
 }
 
-void launch_eval(int dim, bool condense, int npts, const int32_t *pt_rhs, const double *pt_I, const int32_t *found, const double *phi,
-                 const int32_t *eldof, const double *C, const double *M, int k, const double *x, const double *fint, double *out,
-                 hipStream_t s, const double *x_ev, const double *fbub) {
+void launch_eval(const ElemMesh &em, int npts, const int32_t *pt_rhs, const double *pt_I, const int32_t *found, const double *phi, int k, const double *x,
+                 const double *fint, double *out, hipStream_t s, const double *x_ev, const double *fbub) {
     const int grid = (npts + 63) / 64;
-    if (dim == 3)
-        hipLaunchKernelGGL((k_eval<3, false>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, x, fint, out, x_ev, fbub);
-    else if (condense)
-        hipLaunchKernelGGL((k_eval<2, true>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, x, fint, out, x_ev, fbub);
-    else
-        hipLaunchKernelGGL((k_eval<2, false>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, eldof, C, M, k, x, fint, out, x_ev, fbub);
+    for_elem_kind(em.dim, em.condense, [&](auto d, auto co) {
+        hipLaunchKernelGGL((k_eval<decltype(d)::value, decltype(co)::value>), dim3(grid), dim3(64), 0, s, npts, pt_rhs, pt_I, found, phi, em.eldof, em.C, em.M, k, x,
+                           fint, out, x_ev, fbub);
+    });
 }
 
 // The entries of x that k_eval reads, one slot per (point, local dof): the slot of a row that several points read is repeated, and
@@ -1210,15 +1189,14 @@ __global__ void k_eval_slots(int npts, int nk, const int32_t *__restrict__ pt_rh
     at[j] = a;
 }
 
-void launch_eval_slots(int dim, bool condense, int npts, const int32_t *pt_rhs, const int32_t *found, const int32_t *eldof, int k,
-                       int64_t *at, hipStream_t s) {
-    const int N = (dim == 3) ? 20 : 10, nk = (dim == 2 && condense) ? 9 : N;
+void launch_eval_slots(const ElemMesh &em, int npts, const int32_t *pt_rhs, const int32_t *found, int k, int64_t *at, hipStream_t s) {
+    const int N = (em.dim == 3) ? 20 : 10, nk = (em.dim == 2 && em.condense) ? 9 : N;
     const int grid = (npts * N + 255) / 256;
     if (grid == 0) return;
-    if (dim == 3)
-        hipLaunchKernelGGL(k_eval_slots<3>, dim3(grid), dim3(256), 0, s, npts, nk, pt_rhs, found, eldof, k, at);
+    if (em.dim == 3)
+        hipLaunchKernelGGL(k_eval_slots<3>, dim3(grid), dim3(256), 0, s, npts, nk, pt_rhs, found, em.eldof, k, at);
     else
-        hipLaunchKernelGGL(k_eval_slots<2>, dim3(grid), dim3(256), 0, s, npts, nk, pt_rhs, found, eldof, k, at);
+        hipLaunchKernelGGL(k_eval_slots<2>, dim3(grid), dim3(256), 0, s, npts, nk, pt_rhs, found, em.eldof, k, at);
 }
 
 }  // namespace remo

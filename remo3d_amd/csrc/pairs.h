@@ -130,10 +130,9 @@ int pair_tile(int dim, int ncol, size_t acc_bytes);
 int pair_grid(int64_t nt);            // workgroups of every launch of a job (one count, so that one k_sens_reduce sums them all)
 // part[p][grid][nmat * nc] for the np pairs slots[2 * p], slots[2 * p + 1] (device array): per-workgroup sums by material of
 // x_a^T (dK_e / d component) x_b in element order, every entry written.  np * nmat * nc <= kSensMaxAcc.
-void launch_pair_contract(int dim, bool condense, bool tensor, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat,
-                          const int32_t *eperm, const int32_t *eldof, const double *C, const double *M, const double *tab, const PairColumns &pc,
-                          int np, const int32_t *slots, const int32_t *pt_rhs, const double *pt_I, const int32_t *found, const double *fint, int nmat,
-                          int grid, double *part, hipStream_t s, bool per_elem = false);
+// pl: the point arrays of the whole batch (PairColumns::q0 / nq index them); its nq is not read
+void launch_pair_contract(const ElemMesh &em, const double *tab, const PairColumns &pc, int np, const int32_t *slots, const PointLoads &pl, int grid,
+                          double *part, hipStream_t s, bool per_elem = false);
 // per_elem: part = ev[np][nt][nc], the value of every (pair, device element) instead - every entry written, a dead element 0; no
 // material sums, no bound on np (the caller slices by the bytes of ev: kPairEvBytes)
 constexpr size_t kPairEvBytes = size_t(128) << 20;   // ev of one per-element launch (remo_debug_tune key 43); always one pair at least

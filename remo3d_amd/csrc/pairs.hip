@@ -17,26 +17,16 @@
 // element) to ev[q][t][NC] - q the pair's position in the launch, t the device element - instead of scanning by material: lane =
 // (pair, element) with the element fastest, so a tile's values of one pair are one contiguous segment.  Every t < nt is written, a
 // dead element writes 0.  No accumulators, no span of materials, no value buffer in LDS; sens.hip's group sums read ev.
+// The reads of an element (vertices, material, a column's element vector, the condensed bubble) are elem_access.h's, as in k_sens_contract.
 #include <limits.h>
 
+#include "elem_access.h"
 #include "kernels.h"
 #include "pairs.h"
 
 namespace remo {
 
 namespace {
-
-// condensed cell bubble of column c of a chunk, as k_eval recovers it (the arithmetic of k_sens_contract)
-__device__ __forceinline__ void pair_bubble(int32_t t, const double *ce, const double *M, int c, int q0, int nq, const int32_t *__restrict__ pt_rhs,
-                                            const double *__restrict__ pt_I, const int32_t *__restrict__ found, const double *__restrict__ fint,
-                                            double (&v)[10]) {
-    double acc = 0.0;
-    for (int w = q0; w < q0 + nq; ++w)
-        if (pt_I[w] != 0.0 && found[w] == t && pt_rhs[w] == c) acc += fint[w];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) acc -= kentry<2>(ce, M, 9, j) * v[j];
-    v[9] = acc / kentry<2>(ce, M, 9, 9);
-}
 
 template <int DIM> constexpr int pair_col_stride() { return PairMom<DIM>::N + 1; }                         // 31 / 41 doubles
 __host__ __device__ inline int pair_elem_stride(int dim, int ncol) { return (ncol * (dim == 3 ? 31 : 41)) | 1; }
@@ -78,15 +68,9 @@ __global__ void __launch_bounds__(kPairBlock) k_pair_contract(int64_t nt, const 
             const int64_t t = tile * te + tid;
             int32_t m = -1;
             if (t < nt) {
-                m = mat[eperm ? int64_t(eperm[t]) : t];
-                if (m < 0 || m >= nmat) m = -1;   // (k_metric_terms has flagged it: the batch fails before these sums are read)
+                m = elem_material(mat, eperm, t, nmat);
                 double X[NB * DIM], g[DIM][DIM];
-#pragma unroll
-                for (int a = 0; a < NB; ++a) {
-                    const int64_t v = conn[t * NB + a];
-#pragma unroll
-                    for (int k = 0; k < DIM; ++k) X[a * DIM + k] = coords[v * DIM + k];
-                }
+                load_vertices<DIM>(coords, conn, t, X);
                 const double vol = bary_gradients<DIM>(X, g);
                 if (!(vol > 0.0)) m = -1;
                 double *geo = s_geo + tid * NGEO;
@@ -114,12 +98,8 @@ __global__ void __launch_bounds__(kPairBlock) k_pair_contract(int64_t nt, const 
             const int k = blk ? k1 : k0;
             const int32_t *ed = eldof + t * N;
             double v[N];
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                const int32_t row = (i < NK) ? ed[i] : -1;
-                v[i] = (row >= 0) ? x[int64_t(row) * k + c] : 0.0;
-            }
-            if constexpr (DIM == 2 && CONDENSE) pair_bubble(int32_t(t), C + t * NT, M, c, blk ? q01 : q00, blk ? nq1 : nq0, pt_rhs, pt_I, found, fint, v);
+            gather_column<N, NK>(ed, x, k, c, v);
+            if constexpr (DIM == 2 && CONDENSE) recover_bubble(int32_t(t), C + t * NT, M, c, blk ? q01 : q00, blk ? nq1 : nq0, pt_rhs, pt_I, found, fint, v);
             const double *geo = s_geo + e * NGEO;
             double g[DIM][DIM], X[NB * DIM];
 #pragma unroll
@@ -211,40 +191,30 @@ int pair_grid(int64_t nt) {
     return int(ntiles < kMaxPartialBlocks ? (ntiles > 0 ? ntiles : 1) : kMaxPartialBlocks);
 }
 
-void launch_pair_contract(int dim, bool condense, bool tensor, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat,
-                          const int32_t *eperm, const int32_t *eldof, const double *C, const double *M, const double *tab, const PairColumns &pc,
-                          int np, const int32_t *slots, const int32_t *pt_rhs, const double *pt_I, const int32_t *found, const double *fint, int nmat,
-                          int grid, double *part, hipStream_t s, bool per_elem) {
-    const int nc = tensor ? (dim == 2 ? 3 : 6) : 1;
-    const size_t acc = per_elem ? 0 : sizeof(double) * size_t(np) * size_t(nmat) * nc;
+void launch_pair_contract(const ElemMesh &em, const double *tab, const PairColumns &pc, int np, const int32_t *slots, const PointLoads &pl, int grid,
+                          double *part, hipStream_t s, bool per_elem) {
+    const int dim = em.dim, nc = em.tensor() ? (dim == 2 ? 3 : 6) : 1;
+    const size_t acc = per_elem ? 0 : sizeof(double) * size_t(np) * size_t(em.n_mat) * nc;
     const int te = pair_tile(dim, pc.ncol, acc);
     const size_t lds = sizeof(double) * size_t(te) * size_t(pair_elem_stride(dim, pc.ncol)) + acc;
     unsigned long long colbits = 0;
     for (int i = 0; i < pc.ncol; ++i) colbits |= (unsigned long long)(pc.col[i] & 15) << (4 * i);
-#define REMO_PAIR_LAUNCH_(D, CO, TE, PE) \
-    do { \
-        static bool sized = false;   /* static + dynamic LDS pass 64 KB: the kernel is allowed them once */ \
-        if (!sized) { \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pair_contract<D, CO, TE, PE>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); \
-            sized = true; \
-        } \
-        hipLaunchKernelGGL((k_pair_contract<D, CO, TE, PE>), dim3(grid), dim3(kPairBlock), lds, s, nt, coords, conn, mat, eperm, eldof, C, M, tab, pc.x[0], \
-                           pc.x[1], pc.k[0], pc.k[1], pc.q0[0], pc.nq[0], pc.q0[1], pc.nq[1], pc.ncol, colbits, te, np, slots, pt_rhs, pt_I, found, fint, \
-                           nmat, part); \
-    } while (0)
-#define REMO_PAIR_LAUNCH(D, CO, TE) \
-    do { \
-        if (per_elem) REMO_PAIR_LAUNCH_(D, CO, TE, true); else REMO_PAIR_LAUNCH_(D, CO, TE, false); \
-    } while (0)
-    if (dim == 3) {
-        if (tensor) REMO_PAIR_LAUNCH(3, false, true); else REMO_PAIR_LAUNCH(3, false, false);
-    } else if (condense) {
-        if (tensor) REMO_PAIR_LAUNCH(2, true, true); else REMO_PAIR_LAUNCH(2, true, false);
-    } else {
-        if (tensor) REMO_PAIR_LAUNCH(2, false, true); else REMO_PAIR_LAUNCH(2, false, false);
-    }
-#undef REMO_PAIR_LAUNCH
-#undef REMO_PAIR_LAUNCH_
+    for_elem_kind(dim, em.condense, em.tensor(), [&](auto d, auto co, auto tens) {
+        constexpr int D = decltype(d)::value;
+        constexpr bool CO = decltype(co)::value, TE = decltype(tens)::value;
+        auto launch = [&](auto pe) {
+            constexpr bool PE = decltype(pe)::value;
+            static bool sized = false;   // static + dynamic LDS pass 64 KB: the kernel is allowed them once (one `sized` per instantiation of this body)
+            if (!sized) {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pair_contract<D, CO, TE, PE>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+                sized = true;
+            }
+            hipLaunchKernelGGL((k_pair_contract<D, CO, TE, PE>), dim3(grid), dim3(kPairBlock), lds, s, em.nt, em.coords, em.conn, em.mat, em.eperm, em.eldof, em.C, em.M, tab, pc.x[0],
+                               pc.x[1], pc.k[0], pc.k[1], pc.q0[0], pc.nq[0], pc.q0[1], pc.nq[1], pc.ncol, colbits, te, np, slots, pl.pt_rhs, pl.pt_I, pl.found,
+                               pl.fint, em.n_mat, part);
+        };
+        if (per_elem) launch(std::true_type{}); else launch(std::false_type{});
+    });
 }
 
 }  // namespace remo

@@ -1,6 +1,7 @@
 // remo_api.hip — the C ABI of include/remo3d_hip.h: context, resident batches (creation, one-shot solves, fetch) and the
 // inspection entries that read a batch's last system.  remo_batch_run itself is batch_run.hip; the probes are remo_debug.hip,
-// the CPU hooks remo_host.cpp.
+// the CPU hooks remo_host.cpp.  remo_batch_field / remo_batch_eval launch their element kernels with resident_mesh: the ElemMesh view
+// (elem_access.h) of the batch's last system, built by the same elem_mesh as the run's.
 #include <limits.h>
 
 #include <algorithm>
@@ -613,6 +614,11 @@ int remo_batch_create_job(remo_ctx_t *ctx, const remo_mesh_t *mesh, const remo_j
     return rc;
 }
 
+// the system of a batch's last run, still resident, as the element kernels read it: what remo_batch_field / remo_batch_eval evaluate on
+static ElemMesh resident_mesh(const remo_ctx_t *ctx, const remo_batch_t *b) {
+    return elem_mesh(b, b->d_C, b->d_M_last ? b->d_M_last : ((b->dim == 2) ? ctx->d_M2 : ctx->d_M3));
+}
+
 int remo_batch_field(remo_ctx_t *ctx, remo_batch_t *b, int32_t rhs, int32_t n_pts, const double *pts, double *u, double *grad, double *J,
                      int32_t *elem) {
     if (!ctx) return REMO_ERR_ARG;
@@ -653,12 +659,10 @@ int remo_batch_field(remo_ctx_t *ctx, remo_batch_t *b, int32_t rhs, int32_t n_pt
         HIP_TRY(hipEventRecord(ctx->fev[1], s));
         FieldCols cols;
         cols.n = 1; cols.col[0] = rhs; cols.slot[0] = 0;
-        const FieldSources src{b->d_prhs_last, b->d_pI_last, b->d_found_last, b->d_fint_last, b->nq_last};
-        const double *d_M = b->d_M_last ? b->d_M_last : ((dim == 2) ? ctx->d_M2 : ctx->d_M3);
+        const PointLoads src{b->d_prhs_last, b->d_pI_last, b->d_found_last, b->d_fint_last, b->nq_last};
         double *d_u = d_out, *d_grad = d_out + np, *d_J = d_grad + np * dim;
         HIP_TRY(hipEventRecord(ctx->fev[2], s));
-        launch_field_eval(dim, sy.condense, b->sigma_comp > 1, n_pts, d_pts, d_found, b->d_coords, sy.conn, b->d_mat, sy.eperm, b->d_sigma, b->n_mat, sy.eldof,
-                          b->d_C, d_M, b->k_last, b->d_x, cols, src, d_u, d_grad, d_J, s);
+        launch_field_eval(resident_mesh(ctx, b), n_pts, d_pts, d_found, b->k_last, b->d_x, cols, src, d_u, d_grad, d_J, s);
         HIP_TRY(hipEventRecord(ctx->fev[3], s));
         if (u) HIP_TRY(hipMemcpyAsync(u, d_u, sizeof(double) * np, hipMemcpyDeviceToHost, s));
         if (grad) HIP_TRY(hipMemcpyAsync(grad, d_grad, sizeof(double) * np * dim, hipMemcpyDeviceToHost, s));
@@ -701,8 +705,7 @@ int remo_batch_eval(remo_ctx_t *ctx, remo_batch_t *b, int32_t rhs, int32_t npts,
         for (int q0 = 0; q0 < npts; q0 += kMaxPoints)
             launch_locate(dim, b->nt, b->d_coords, sy.conn, std::min(kMaxPoints, npts - q0), d_z + q0, d_found + q0, s);
         launch_point_shapes(dim, npts, d_z, d_found, b->d_coords, sy.conn, d_phi, ctx->d_err, s);
-        const double *d_M = b->d_M_last ? b->d_M_last : ((dim == 2) ? ctx->d_M2 : ctx->d_M3);
-        launch_eval(dim, sy.condense, npts, d_rhs, d_I, d_found, d_phi, sy.eldof, b->d_C, d_M, b->k_last, b->d_x, d_fint, d_out, s);
+        launch_eval(resident_mesh(ctx, b), npts, d_rhs, d_I, d_found, d_phi, b->k_last, b->d_x, d_fint, d_out, s);
         int32_t h_err = 0;
         HIP_TRY(hipMemcpyAsync(u_out, d_out, sizeof(double) * npts, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(&h_err, ctx->d_err, sizeof(int32_t), hipMemcpyDeviceToHost, s));

@@ -236,6 +236,19 @@ inline int fail(remo_ctx *ctx, int code, const std::string &msg) {
     return code;
 }
 
+// A batch's mesh with metric terms C[nt][NTERM] and reference tensors M as the element kernels read it (elem_access.h): a view, valid
+// while the batch's numbering (pointers into the context's arena) is
+inline ElemMesh elem_mesh(const remo_batch *b, const double *C, const double *M) {
+    const DeviceSymbolic &sy = b->sym;
+    ElemMesh em;
+    em.dim = b->dim; em.condense = sy.condense; em.nt = b->nt;
+    em.coords = b->d_coords; em.conn = sy.conn; em.mat = b->d_mat; em.eperm = sy.eperm;
+    em.sigma = b->d_sigma; em.sigma_comp = b->sigma_comp; em.n_mat = b->n_mat;
+    em.eldof = sy.eldof; em.C = C; em.M = M;
+    em.adjptr = sy.adjptr; em.adj = sy.adj;
+    return em;
+}
+
 // The host checks of a batch's mesh, conductivities, sources and evaluation points: everything that is refused before any device
 // work (remo_api.hip).  full: src_p / eval_p hold dim coordinates per point (the job entries) and are checked for finiteness here;
 // else they hold axis positions z, and a bad one is found when the points are located.

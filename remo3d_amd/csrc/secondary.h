@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/remo3d_hip.h"
+#include "elem_access.h"
 #include "fem_p3.h"
 
 namespace remo {
@@ -139,13 +140,11 @@ struct SecSources {
 };
 
 // a contributing element (Sigma_e != sigma0 I) that holds a source within k_locate's tolerance raises bit 4 of *errflag
-void launch_sec_check(int dim, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat, const int32_t *eperm, const double *sigma,
-                      int ncomp, int nmat, int ns, const double *src, int32_t *errflag, hipStream_t s);
+void launch_sec_check(const ElemMesh &em, int ns, const double *src, int32_t *errflag, hipStream_t s);
 // element vectors fe[nt][NLD][k] of one chunk (zeros where Sigma_e = sigma0 I; 2D condensed: the bubble load folded into the nine
 // outer entries as k_build_rhs folds a point source's, and kept in fbub[nt][k]), one wave per element
-void launch_sec_elements(int dim, bool condense, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat, const int32_t *eperm,
-                         const double *sigma, int ncomp, int nmat, const double *C, const double *M, const double *rule, int nq, const double *src,
-                         const int32_t *ptr, int k, double R, double *fe, double *fbub, hipStream_t s);
+void launch_sec_elements(const ElemMesh &em, const double *rule, int nq, const double *src, const int32_t *ptr, int k, double R, double *fe, double *fbub,
+                         hipStream_t s);
 // f[row][c] = the sum of the row's element entries in ascending element order (DeviceSymbolic::adj): no atomics, a fixed order
 void launch_sec_gather(int dim, int64_t n, int k, const int32_t *adjptr, const uint32_t *adj, const double *fe, double *f, hipStream_t s);
 // out[q] += u_p(point q) for the points that are no sources; pp: z per point (on_axis) or dim coordinates

@@ -4,13 +4,15 @@
 // k_sec_elements: one wave per element.  The lanes share the element's quadrature points; every lane keeps the NLD partial sums of
 // one column at a time in registers (all arrays are indexed by unrolled loops: nothing in scratch), a transposing wave reduction
 // (wave_util.h) leaves each sum on one lane, which stores it.  k_sec_gather then adds, per row, the entries of the row's elements in
-// ascending element order.  Both orders are fixed: two runs give the same bits.
+// ascending element order.  Both orders are fixed: two runs give the same bits.  Vertices and material come through elem_access.h; the
+// conductivity is read with the run-time stride ncomp here (a scalar table is widened to a tensor), not through load_sigma.
 // At the end of the file, the host side: what a job entry checks and resolves before any device work.
 #include <limits.h>
 
 #include <algorithm>
 #include <cmath>
 
+#include "elem_access.h"
 #include "secondary.h"
 #include "wave_util.h"
 #include "remo_internal.h"
@@ -76,17 +78,6 @@ std::vector<double> sec_rule(int dim, int n) {
 // ---- kernels ------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-template <int DIM>
-__device__ __forceinline__ void load_vertices(const double *__restrict__ coords, const int32_t *__restrict__ conn, int64_t t, double *X) {
-    constexpr int NB = DIM + 1;
-#pragma unroll
-    for (int a = 0; a < NB; ++a) {
-        const int64_t v = conn[t * NB + a];
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) X[a * DIM + k] = coords[v * DIM + k];
-    }
-}
-
 // one thread per element: does it hold a source (k_locate's box slack and barycentric tolerance) while its conductivity differs
 // from the sigma0 of that source's right-hand side?
 template <int DIM>
@@ -105,8 +96,8 @@ __global__ void __launch_bounds__(256) k_sec_check(int64_t nt, const double *__r
 #pragma unroll
         for (int a = 1; a < NB; ++a) { lo[k] = fmin(lo[k], X[a * DIM + k]); hi[k] = fmax(hi[k], X[a * DIM + k]); }
     }
-    const int m = mat[eperm ? int64_t(eperm[t]) : t];
-    if (m < 0 || m >= nmat) return;   // (k_metric_terms reports it)
+    const int m = elem_material(mat, eperm, t, nmat);
+    if (m < 0) return;   // (k_metric_terms reports it)
     double S[NS];
 #pragma unroll
     for (int i = 0; i < NS; ++i) S[i] = (i < ncomp) ? sigma[int64_t(m) * ncomp + i] : 0.0;
@@ -144,11 +135,11 @@ __global__ void __launch_bounds__(64) k_sec_elements(int64_t nt, const double *_
     double X[NB * DIM], g[DIM][DIM], S[NS];
     load_vertices<DIM>(coords, conn, t, X);
     const double vol = bary_gradients<DIM>(X, g);
-    const int m = mat[eperm ? int64_t(eperm[t]) : t];
-    const bool ok = vol > 0.0 && m >= 0 && m < nmat;   // (a degenerate element or a bad material is k_metric_terms' error)
+    const int m = elem_material(mat, eperm, t, nmat);
+    const bool ok = vol > 0.0 && m >= 0;   // (a degenerate element or a bad material is k_metric_terms' error)
 #pragma unroll
     for (int i = 0; i < NS; ++i) S[i] = (ok && i < ncomp) ? sigma[int64_t(m) * ncomp + i] : 0.0;
-    double fold[9];   // 2D condensed: K_j9 / K_99, what the bubble load takes from the outer rows
+    double fold[9];   // 2D condensed: K_j9 / K_99, what the bubble load takes from the outer rows (the unweighted recovery: recover_bubble, elem_access.h)
     if (CONDENSE) {
         const double *ce = C + t * NT;
         const double kbb = kentry<DIM>(ce, M, 9, 9);
@@ -221,26 +212,21 @@ __global__ void __launch_bounds__(64) k_sec_add_primary(int npts, const int32_t 
 
 }  // namespace
 
-void launch_sec_check(int dim, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat, const int32_t *eperm, const double *sigma,
-                      int ncomp, int nmat, int ns, const double *src, int32_t *errflag, hipStream_t s) {
+void launch_sec_check(const ElemMesh &em, int ns, const double *src, int32_t *errflag, hipStream_t s) {
     if (ns <= 0) return;
-    const int grid = int((nt + 255) / 256);
-    if (dim == 2)
-        hipLaunchKernelGGL(k_sec_check<2>, dim3(grid), dim3(256), 0, s, nt, coords, conn, mat, eperm, sigma, ncomp, nmat, ns, src, errflag);
+    const int grid = int((em.nt + 255) / 256);
+    if (em.dim == 2)
+        hipLaunchKernelGGL(k_sec_check<2>, dim3(grid), dim3(256), 0, s, em.nt, em.coords, em.conn, em.mat, em.eperm, em.sigma, em.sigma_comp, em.n_mat, ns, src, errflag);
     else
-        hipLaunchKernelGGL(k_sec_check<3>, dim3(grid), dim3(256), 0, s, nt, coords, conn, mat, eperm, sigma, ncomp, nmat, ns, src, errflag);
+        hipLaunchKernelGGL(k_sec_check<3>, dim3(grid), dim3(256), 0, s, em.nt, em.coords, em.conn, em.mat, em.eperm, em.sigma, em.sigma_comp, em.n_mat, ns, src, errflag);
 }
 
-void launch_sec_elements(int dim, bool condense, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat, const int32_t *eperm,
-                         const double *sigma, int ncomp, int nmat, const double *C, const double *M, const double *rule, int nq, const double *src,
-                         const int32_t *ptr, int k, double R, double *fe, double *fbub, hipStream_t s) {
-    const dim3 grid{unsigned(nt)}, block{64};
-    if (dim == 3)
-        hipLaunchKernelGGL((k_sec_elements<3, false>), grid, block, 0, s, nt, coords, conn, mat, eperm, sigma, ncomp, nmat, C, M, rule, nq, src, ptr, k, R, fe, fbub);
-    else if (condense)
-        hipLaunchKernelGGL((k_sec_elements<2, true>), grid, block, 0, s, nt, coords, conn, mat, eperm, sigma, ncomp, nmat, C, M, rule, nq, src, ptr, k, R, fe, fbub);
-    else
-        hipLaunchKernelGGL((k_sec_elements<2, false>), grid, block, 0, s, nt, coords, conn, mat, eperm, sigma, ncomp, nmat, C, M, rule, nq, src, ptr, k, R, fe, fbub);
+void launch_sec_elements(const ElemMesh &em, const double *rule, int nq, const double *src, const int32_t *ptr, int k, double R, double *fe, double *fbub,
+                         hipStream_t s) {
+    for_elem_kind(em.dim, em.condense, [&](auto d, auto co) {
+        hipLaunchKernelGGL((k_sec_elements<decltype(d)::value, decltype(co)::value>), dim3(unsigned(em.nt)), dim3(64), 0, s, em.nt, em.coords, em.conn, em.mat,
+                           em.eperm, em.sigma, em.sigma_comp, em.n_mat, em.C, em.M, rule, nq, src, ptr, k, R, fe, fbub);
+    });
 }
 
 void launch_sec_gather(int dim, int64_t n, int k, const int32_t *adjptr, const uint32_t *adj, const double *fe, double *f, hipStream_t s) {

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "elem_access.h"
 #include "fem_p3.h"
 
 namespace remo {
@@ -106,9 +107,8 @@ constexpr int kSensBlock = 256;       // elements per tile of k_sens_contract
 constexpr int kSensMaxAcc = 4096;
 int sens_grid(int64_t nt);
 // part[grid][nmat * nc]: per-workgroup sums of lambda_e^T (dK_e/d component) u_e by material, every entry written
-void launch_sens_contract(int dim, bool condense, bool tensor, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat,
-                          const int32_t *eperm, const int32_t *eldof, const double *C, const double *M, const double *tab, const SensColumns &col,
-                          const int32_t *pt_rhs, const double *pt_I, const int32_t *found, const double *fint, int nmat, double *part, hipStream_t s,
+// pl: the point arrays of the whole batch (SensColumns indexes them); its nq is not read
+void launch_sens_contract(const ElemMesh &em, const double *tab, const SensColumns &col, const PointLoads &pl, double *part, hipStream_t s,
                           bool per_elem = false);   // per_elem: part = ev[nt][nc], the values of every device element instead (no material sums)
 // dJ[j][nmat * nc] = -(sum over the workgroups, in index order) for n_fun functionals whose partials lie one after the other
 void launch_sens_reduce(int n_fun, int grid, int nmc, const double *part, double *dJ, hipStream_t s);

@@ -14,44 +14,19 @@
 // sorted list in an order that depends only on that list - lane l of the group's lanes adds the entries congruent to l in
 // ascending order, a fixed butterfly combines the lanes; segments longer than kSensChunk are first summed per chunk of the
 // sorted list by whole workgroups.  No floating-point atomics anywhere.
+// The reads of an element (vertices, material, the two element vectors, the condensed bubble) are elem_access.h's.
 #include <limits.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <stdexcept>
 
+#include "elem_access.h"
 #include "kernels.h"
 #include "sens.h"
 #include "wave_util.h"
 
 namespace remo {
-
-namespace {
-
-// element vector of column c of x[n][k]: constrained rows read 0; NK rows are gathered (2D condensed: the bubble follows below)
-template <int N, int NK>
-__device__ __forceinline__ void gather_rows(const int32_t *__restrict__ ed, const double *__restrict__ x, int k, int c, double (&v)[N]) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const int32_t row = (i < NK) ? ed[i] : -1;
-        v[i] = (row >= 0) ? x[int64_t(row) * k + c] : 0.0;
-    }
-}
-
-// condensed cell bubble of one column, as k_eval recovers it: x_9 = (f_9 - sum_j K_9j x_j) / K_99, f_9 the bubble loads of the
-// column's points that lie in this element
-__device__ __forceinline__ void recover_bubble(int32_t t, const double *ce, const double *M, int c, int q0, int nq, const int32_t *__restrict__ pt_rhs,
-                                               const double *__restrict__ pt_I, const int32_t *__restrict__ found, const double *__restrict__ fint,
-                                               double (&v)[10]) {
-    double acc = 0.0;
-    for (int w = q0; w < q0 + nq; ++w)
-        if (pt_I[w] != 0.0 && found[w] == t && pt_rhs[w] == c) acc += fint[w];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) acc -= kentry<2>(ce, M, 9, j) * v[j];
-    v[9] = acc / kentry<2>(ce, M, 9, 9);
-}
-
-}  // namespace
 
 // PER_ELEM: the nc values of device element t go to part[t * nc + c] (part = ev) and the material scan is skipped
 template <int DIM, bool CONDENSE, bool TENSOR, bool PER_ELEM>
@@ -82,19 +57,13 @@ __global__ void __launch_bounds__(kSensBlock) k_sens_contract(int64_t nt, const 
         for (int c = 0; c < NC; ++c) out[c] = 0.0;
         int32_t m = -1;
         if (t < nt) {
-            m = mat[eperm ? int64_t(eperm[t]) : t];
-            if (m < 0 || m >= nmat) m = -1;   // (k_metric_terms has flagged it: the batch fails before these sums are read)
+            m = elem_material(mat, eperm, t, nmat);
             double X[NB * DIM];
-#pragma unroll
-            for (int a = 0; a < NB; ++a) {
-                const int64_t v = conn[t * NB + a];
-#pragma unroll
-                for (int k = 0; k < DIM; ++k) X[a * DIM + k] = coords[v * DIM + k];
-            }
+            load_vertices<DIM>(coords, conn, t, X);
             const int32_t *ed = eldof + t * N;
             double xl[N], xu[N];
-            gather_rows<N, NK>(ed, col.xu, col.ku, col.cu, xu);
-            gather_rows<N, NK>(ed, col.xl, col.kl, col.cl, xl);
+            gather_column<N, NK>(ed, col.xu, col.ku, col.cu, xu);
+            gather_column<N, NK>(ed, col.xl, col.kl, col.cl, xl);
             if constexpr (DIM == 2 && CONDENSE) {
                 const double *ce = C + t * NT;
                 recover_bubble(int32_t(t), ce, M, col.cu, col.qu0, col.nqu, pt_rhs, pt_I, found, fint, xu);
@@ -137,7 +106,7 @@ __global__ void __launch_bounds__(256) k_sens_group_keys(int64_t nt, const int32
                                                          uint32_t *__restrict__ keys, int32_t *__restrict__ ids) {
     const int64_t t = int64_t(blockIdx.x) * 256 + threadIdx.x;
     if (t >= nt) return;
-    const int32_t g = group[eperm ? int64_t(eperm[t]) : t];
+    const int32_t g = group[caller_element(eperm, t)];
     keys[t] = (g < 0 || g >= n_group) ? uint32_t(n_group) : uint32_t(g);   // (the host has checked the range)
     ids[t] = int32_t(t);
 }
@@ -257,29 +226,19 @@ int sens_grid(int64_t nt) {
     return int(ntiles < kMaxPartialBlocks ? (ntiles > 0 ? ntiles : 1) : kMaxPartialBlocks);
 }
 
-void launch_sens_contract(int dim, bool condense, bool tensor, int64_t nt, const double *coords, const int32_t *conn, const int32_t *mat,
-                          const int32_t *eperm, const int32_t *eldof, const double *C, const double *M, const double *tab, const SensColumns &col,
-                          const int32_t *pt_rhs, const double *pt_I, const int32_t *found, const double *fint, int nmat, double *part, hipStream_t s,
-                          bool per_elem) {
-    const int grid = sens_grid(nt);
-    const size_t lds = per_elem ? 0 : sizeof(double) * size_t(nmat) * (tensor ? (dim == 2 ? 3 : 6) : 1);
-#define REMO_SENS_LAUNCH(D, CO, TE) \
-    do { \
-        if (per_elem) \
-            hipLaunchKernelGGL((k_sens_contract<D, CO, TE, true>), dim3(grid), dim3(kSensBlock), lds, s, nt, coords, conn, mat, eperm, eldof, C, M, tab, col, \
-                               pt_rhs, pt_I, found, fint, nmat, part); \
-        else \
-            hipLaunchKernelGGL((k_sens_contract<D, CO, TE, false>), dim3(grid), dim3(kSensBlock), lds, s, nt, coords, conn, mat, eperm, eldof, C, M, tab, col, \
-                               pt_rhs, pt_I, found, fint, nmat, part); \
-    } while (0)
-    if (dim == 3) {
-        if (tensor) REMO_SENS_LAUNCH(3, false, true); else REMO_SENS_LAUNCH(3, false, false);
-    } else if (condense) {
-        if (tensor) REMO_SENS_LAUNCH(2, true, true); else REMO_SENS_LAUNCH(2, true, false);
-    } else {
-        if (tensor) REMO_SENS_LAUNCH(2, false, true); else REMO_SENS_LAUNCH(2, false, false);
-    }
-#undef REMO_SENS_LAUNCH
+void launch_sens_contract(const ElemMesh &em, const double *tab, const SensColumns &col, const PointLoads &pl, double *part, hipStream_t s, bool per_elem) {
+    const int grid = sens_grid(em.nt);
+    for_elem_kind(em.dim, em.condense, em.tensor(), [&](auto d, auto co, auto te) {
+        constexpr int D = decltype(d)::value;
+        constexpr bool CO = decltype(co)::value, TE = decltype(te)::value;
+        auto launch = [&](auto pe) {
+            constexpr bool PE = decltype(pe)::value;
+            const size_t lds = PE ? 0 : sizeof(double) * size_t(em.n_mat) * SensOut<D, TE>::N;
+            hipLaunchKernelGGL((k_sens_contract<D, CO, TE, PE>), dim3(grid), dim3(kSensBlock), lds, s, em.nt, em.coords, em.conn, em.mat, em.eperm, em.eldof, em.C,
+                               em.M, tab, col, pl.pt_rhs, pl.pt_I, pl.found, pl.fint, em.n_mat, part);
+        };
+        if (per_elem) launch(std::true_type{}); else launch(std::false_type{});
+    });
 }
 
 void launch_sens_reduce(int n_fun, int grid, int nmc, const double *part, double *dJ, hipStream_t s) {

@@ -61,6 +61,8 @@ __global__ void __launch_bounds__(256) k_warm_add(int64_t n, double *__restrict_
     }
 }
 
+// (not the k switch of pcg_kernels.hip / amg.hip: theirs take every k outside 1 .. 7 as 8, this one throws above REMO_MAX_RHS - the
+// warm object is sized by the caller's k - so the three stay apart)
 #define REMO_WARM_K_SWITCH(k, CALL)                          \
     switch (k) {                                             \
         case 1: { constexpr int KK = 1; CALL; } break;       \
