@@ -885,48 +885,35 @@ void amg_to_float(Arena &ar, hipStream_t s, const AmgT<double> &in, int kmax, Am
 
 template <class T, class TR> void launch_amg_cycle(const AmgT<T> &H, int k, int step, const TR *r, TR *cz, double *part, int nblocks, const double *scal, hipStream_t s) {
     const int L = H.levels;
-#define AMG_K_SWITCH(CALL)                                  \
-    switch (k) {                                            \
-        case 1: { constexpr int KK = 1; CALL; } break;      \
-        case 2: { constexpr int KK = 2; CALL; } break;      \
-        case 3: { constexpr int KK = 3; CALL; } break;      \
-        case 4: { constexpr int KK = 4; CALL; } break;      \
-        case 5: { constexpr int KK = 5; CALL; } break;      \
-        case 6: { constexpr int KK = 6; CALL; } break;      \
-        case 7: { constexpr int KK = 7; CALL; } break;      \
-        default: { constexpr int KK = 8; CALL; } break;     \
-    }
     auto rows_grid = [&](int64_t n) { return int((n + kRpb - 1) / kRpb); };
     // the levels from `lt` on go into the single-workgroup kernel (always at least the coarsest one)
     int lt = L - 1;
     while (lt > 1 && H.lev[lt - 1].n <= kTailRows && L - (lt - 1) <= kTailLevels) --lt;
-    for (int l = 0; l < lt; ++l) {   // down
-        const AmgLevelT<T> &a = H.lev[l], &b = H.lev[l + 1];
-        if (l == 0) {
-            AMG_K_SWITCH(hipLaunchKernelGGL((k_amg_pre<T, KK, TR>), dim3(rows_grid(a.n)), dim3(256), 0, s, a, r, scal, step));
-        } else {
-            AMG_K_SWITCH(hipLaunchKernelGGL((k_amg_pre<T, KK, T>), dim3(rows_grid(a.n)), dim3(256), 0, s, a, (const T *)a.r, scal, step));
+    for_k(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        for (int l = 0; l < lt; ++l) {   // down
+            const AmgLevelT<T> &a = H.lev[l], &b = H.lev[l + 1];
+            if (l == 0) hipLaunchKernelGGL((k_amg_pre<T, K, TR>), dim3(rows_grid(a.n)), dim3(256), 0, s, a, r, scal, step);
+            else hipLaunchKernelGGL((k_amg_pre<T, K, T>), dim3(rows_grid(a.n)), dim3(256), 0, s, a, (const T *)a.r, scal, step);
+            if (l + 1 < lt) hipLaunchKernelGGL((k_amg_restrict<T, K>), dim3(rows_grid(b.n)), dim3(256), 0, s, a, b.n, b.r, scal, step);
         }
-        if (l + 1 < lt) AMG_K_SWITCH(hipLaunchKernelGGL((k_amg_restrict<T, KK>), dim3(rows_grid(b.n)), dim3(256), 0, s, a, b.n, b.r, scal, step));
-    }
-    {
-        AmgTailT<T> tail;
-        tail.levels = L - lt;
-        tail.up = H.lev[lt - 1];
-        for (int l = lt; l < L; ++l) tail.lev[l - lt] = H.lev[l];
-        tail.inv = H.inv;
-        AMG_K_SWITCH(hipLaunchKernelGGL((k_amg_tail<T, KK>), dim3(1), dim3(1024), 0, s, tail, scal, step));
-    }
-    for (int l = lt - 1; l >= 0; --l) {   // up
-        const AmgLevelT<T> &a = H.lev[l], &b = H.lev[l + 1];
-        AMG_K_SWITCH(hipLaunchKernelGGL((k_amg_prolong<T, KK>), dim3(rows_grid(a.n)), dim3(256), 0, s, a, (const T *)b.z2, scal, step));
-        if (l == 0) {   // the launch that leaves the partial sums is held to `nblocks` workgroups: 128 rows each
-            AMG_K_SWITCH(hipLaunchKernelGGL((k_amg_post<T, KK, true, 1024, TR>), dim3(nblocks), dim3(1024), 0, s, a, r, cz, part, scal, step));
-        } else {
-            AMG_K_SWITCH(hipLaunchKernelGGL((k_amg_post<T, KK, false, 256, T>), dim3(rows_grid(a.n)), dim3(256), 0, s, a, (const T *)a.r, a.z2, (double *)nullptr, scal, step));
+        {
+            AmgTailT<T> tail;
+            tail.levels = L - lt;
+            tail.up = H.lev[lt - 1];
+            for (int l = lt; l < L; ++l) tail.lev[l - lt] = H.lev[l];
+            tail.inv = H.inv;
+            hipLaunchKernelGGL((k_amg_tail<T, K>), dim3(1), dim3(1024), 0, s, tail, scal, step);
         }
-    }
-#undef AMG_K_SWITCH
+        for (int l = lt - 1; l >= 0; --l) {   // up
+            const AmgLevelT<T> &a = H.lev[l], &b = H.lev[l + 1];
+            hipLaunchKernelGGL((k_amg_prolong<T, K>), dim3(rows_grid(a.n)), dim3(256), 0, s, a, (const T *)b.z2, scal, step);
+            if (l == 0)   // the launch that leaves the partial sums is held to `nblocks` workgroups: 128 rows each
+                hipLaunchKernelGGL((k_amg_post<T, K, true, 1024, TR>), dim3(nblocks), dim3(1024), 0, s, a, r, cz, part, scal, step);
+            else
+                hipLaunchKernelGGL((k_amg_post<T, K, false, 256, T>), dim3(rows_grid(a.n)), dim3(256), 0, s, a, (const T *)a.r, a.z2, (double *)nullptr, scal, step);
+        }
+    });
 }
 
 template void launch_amg_cycle<double, double>(const AmgT<double> &, int, int, const double *, double *, double *, int, const double *, hipStream_t);

@@ -665,7 +665,7 @@ void vertex_block_enqueue(const Run &r, const Plan &plan, const System &sys, con
     if (plan.want_patch) {
         vb.d_pflag = ctx->take<int32_t>(4);
         vb.patch_mark = ctx->ar.lo_mark();      // nothing else is taken before the synchronisation: patch_tables_one_round may build them again here
-        build_patch_tables(ctx->ar, s, sy, sys.d_C, plan.kmax, r.o.precision == 0 ? patch_rounds_wanted() : 1, vb.ptab, vb.d_pflag);
+        build_patch_tables(ctx->ar, s, sy, sys.d_C, plan.kmax, r.o.precision == 0 ? g_tune.patch_rounds : 1, vb.ptab, vb.d_pflag);
         HIP_TRY(hipMemcpyAsync(vb.h_patch, vb.d_pflag, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(hipMemcpyAsync(&vb.h_err, ctx->d_err, sizeof(int32_t), hipMemcpyDeviceToHost, s));

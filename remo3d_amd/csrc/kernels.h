@@ -1,15 +1,39 @@
-// kernels.h — launchers of the gfx950 kernels (kernels.hip; the PCG step's: pcg_kernels.hip).  All launches are asynchronous on
-// the given stream; no launcher allocates or synchronises.
+// kernels.h — launchers of the gfx950 kernels (kernels.hip; the PCG step's: pcg_kernels.hip) and the dispatch on the column count
+// they share (for_k).  All launches are asynchronous on the given stream; no launcher allocates or synchronises.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "elem_access.h"
+#include "tune.h"
 
 namespace remo {
 
 constexpr int kMaxPartialBlocks = 1024;   // grid cap of every kernel that leaves per-block partial sums
 constexpr int kMaxPoints = 256;          // sources + evaluation points of one RHS chunk
+
+template <int V> using int_c = std::integral_constant<int, V>;
+// fn(int_c<K>) for the column counts the solver kernels are instantiated for: K = k for k in 1 .. 7, K = 8 for every other k (a
+// launcher with a stricter contract checks k before it dispatches).  A generic lambda instantiates every kernel it names for all
+// eight K: what exists for some T or some build only stays behind `if constexpr` inside it.
+template <class F> void for_k(int k, F &&fn) {
+    switch (k) {
+        case 1: fn(int_c<1>{}); break;
+        case 2: fn(int_c<2>{}); break;
+        case 3: fn(int_c<3>{}); break;
+        case 4: fn(int_c<4>{}); break;
+        case 5: fn(int_c<5>{}); break;
+        case 6: fn(int_c<6>{}); break;
+        case 7: fn(int_c<7>{}); break;
+        default: fn(int_c<8>{}); break;
+    }
+}
+// fn(bool_constant<B>): a kernel's boolean template parameter from a run-time flag
+template <class F> void for_bool(bool b, F &&fn) {
+    if (b) fn(std::true_type{}); else fn(std::false_type{});
+}
 
 // per-iteration record the PCG kernels write straight into mapped host memory
 struct PcgProgress {
@@ -158,8 +182,6 @@ void launch_assemble(int dim, bool condense, int64_t nfree, int64_t pair_begin, 
 
 int spmv_grid(int64_t n, int lanes_per_row);
 int vec_grid(int64_t n);
-void set_fold_first(int v);                 // 1 (default): FIRST Chebyshev step inside the update launch (k_pcg_update_folded)
-void set_spmm_tuning(int key, int value);  // 0 variant, 1 lanes per row, 2 threads, 3 mapping, 4 grid (0 = default)
 int choose_lanes_per_row(int64_t n, int64_t nnz);
 // y = A x for k interleaved columns; if part != nullptr also leaves per-block partial sums of <x_c, y_c>
 // scal != nullptr: the launch belongs to PCG step `step` and returns at once when an earlier step froze every column
@@ -171,10 +193,6 @@ template <class T> void launch_patch_spmm(const CsrViewT<T> &A, int k, const T *
 // the PCG's q = A p with p in fp32 storage (PcgBuffersT::p32): fp64 product, shared rows left in the slab, partials of <p, A p>; throws where the patch operator does not apply
 void launch_patch_spmm_x32(const CsrViewT<double> &A, int k, const float *x, double *part, const double *scal, int nblocks, hipStream_t s, int step);   // patch.hip
 template <class T> bool pcg_update_folds(const PcgBuffersT<T> &b);   // the update launch takes the first Chebyshev step along (and gathers q)
-void set_slab_masked(int v);         // key 29: k_pcg_update<.., MASKED = true> (1) / <.., false> (0)
-void set_flat_direction(int v);      // key 30: k_pcg_direction_flat (1) / k_pcg_direction_row (0)
-void set_tile_update(int v);         // key 31: k_pcg_update_tile (1) / k_pcg_update (0)
-void set_slab_ahead(int v);          // 0: slab slots of a shared row one by one in the update launch (default 1: four in flight)
 
 template <class T> void launch_pcg_init(const CsrViewT<T> &A, int k, const T *f, const PcgBuffersT<T> &b, hipStream_t s);       // + C r0, p0
 template <class T> void launch_pcg_update(const CsrViewT<T> &A, int k, int step, double tol2, const PcgBuffersT<T> &b, hipStream_t s);  // + C r (Chebyshev steps)

@@ -529,39 +529,17 @@ __global__ void __launch_bounds__(512) k_spmm_pair(int64_t n, int64_t pair_begin
     }
 }
 
-// tuning knobs (remo_debug_tune): 0 = heuristic default
-struct SpmmTuning {
-    int mode = 0;     // ablation mode of the pair kernel (K = 5, 16 lanes per row only)
-    int variant = 0;  // 1 = lane per stored entry, 3 = edge row pairs (default)
-    int lpr = 0;
-    int threads = 0;
-    int mapping = -1;
-    int grid = 0;
-};
-static SpmmTuning g_spmm_tune;
-void set_spmm_tuning(int key, int value) {
-    switch (key) {
-        case 0: g_spmm_tune.variant = value; break;
-        case 1: g_spmm_tune.lpr = value; break;
-        case 2: g_spmm_tune.threads = value; break;
-        case 3: g_spmm_tune.mapping = value; break;
-        case 4: g_spmm_tune.grid = value; break;
-        case 5: g_spmm_tune.mode = value; break;
-        default: break;
-    }
-}
-
 int choose_lanes_per_row(int64_t n, int64_t nnz) {
-    if (g_spmm_tune.lpr) return g_spmm_tune.lpr;
+    if (g_tune.spmm_lpr) return g_tune.spmm_lpr;
     const double avg = double(nnz) / double(n > 0 ? n : 1);
     if (avg > 40) return 16;
     if (avg > 20) return 8;
     return 4;
 }
-static int spmm_threads() { return g_spmm_tune.threads ? g_spmm_tune.threads : 256; }
+static int spmm_threads() { return g_tune.spmm_threads ? g_tune.spmm_threads : 256; }
 
 int spmv_grid(int64_t n, int lpr) {
-    if (g_spmm_tune.grid) return g_spmm_tune.grid;
+    if (g_tune.spmm_grid) return g_tune.spmm_grid;
     const int64_t rpb = spmm_threads() / lpr;
     int64_t g = (n + rpb - 1) / rpb;
     g = (g + 7) / 8 * 8;  // whole residue classes mod 8 (one per XCD)
@@ -577,7 +555,7 @@ int spmv_grid(int64_t n, int lpr) {
 template <class T, int K> static void spmm_dispatch(const CsrViewT<T> &A, const T *x, T *y, double *part, const double *scal, int step, int nb, hipStream_t s) {
     int lpr = choose_lanes_per_row(A.n, A.nnz);
     const int threads = spmm_threads();
-    int variant = g_spmm_tune.variant ? g_spmm_tune.variant : 3;
+    int variant = g_tune.spmm_variant ? g_tune.spmm_variant : 3;
     if (variant == 3 && !(A.pair_end > A.pair_begin)) variant = 1;
     // default row schedule of the pair kernel: XCD windows (measured 69 -> 60 us at 334k rows, k = 5); once the matrix no
     // longer stays in the 256 MB of MALL between launches (3D, more than ~20 M stored entries), XCD regions (4 chunks
@@ -587,38 +565,30 @@ template <class T, int K> static void spmm_dispatch(const CsrViewT<T> &A, const 
     // chunks per XCD: about 0.4 MB of x per chunk, 4 ... 64 (bench at 5.4 M rows: 4 chunks 1257 us, 16: 1227, 64: 1216)
     int64_t nc = (A.n * int64_t(K) * int64_t(sizeof(T)) / 8 + 210000) / 420000;
     nc = nc < 4 ? 4 : (nc > 64 ? 64 : nc);
-    const int mapping = (g_spmm_tune.mapping >= 0) ? g_spmm_tune.mapping : ((lpr == 16 && A.nnz > 20000000) ? int(16 * nc) : 1);
-#define REMO_SPMM(L)                                                                                                        \
-    if (part)                                                                                                               \
-        hipLaunchKernelGGL((k_spmm<T, K, L, true>), dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, A.rowptr, A.col, A.val, x, y, part, scal, step); \
-    else                                                                                                                    \
-        hipLaunchKernelGGL((k_spmm<T, K, L, false>), dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, A.rowptr, A.col, A.val, x, y, part, scal, step)
-#define REMO_SPMM_PAIR(L)                                                                                                               \
-    if (part)                                                                                                                           \
-        hipLaunchKernelGGL((k_spmm_pair<T, K, L, true>), dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, mapping, A.rowptr, A.col, A.val, x, y, part, scal, step); \
-    else                                                                                                                                \
-        hipLaunchKernelGGL((k_spmm_pair<T, K, L, false>), dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, mapping, A.rowptr, A.col, A.val, x, y, part, scal, step)
+    const int mapping = (g_tune.spmm_mapping >= 0) ? g_tune.spmm_mapping : ((lpr == 16 && A.nnz > 20000000) ? int(16 * nc) : 1);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, A.rowptr, A.col, A.val, x, y, part, scal, step); };
+    auto launch_pair = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, mapping, A.rowptr, A.col, A.val, x, y, part, scal, step); };
     if constexpr (K == 5 && sizeof(T) == 8) {   // ablation modes of tools/probe_ablate.py
-        if (variant == 3 && lpr == 16 && g_spmm_tune.mode >= 1 && g_spmm_tune.mode <= 3 && !part) {
-            if (g_spmm_tune.mode == 1) hipLaunchKernelGGL((k_spmm_pair<T, 5, 16, false, 1>), dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, mapping, A.rowptr, A.col, A.val, x, y, part, scal, step);
-            if (g_spmm_tune.mode == 2) hipLaunchKernelGGL((k_spmm_pair<T, 5, 16, false, 2>), dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, mapping, A.rowptr, A.col, A.val, x, y, part, scal, step);
-            if (g_spmm_tune.mode == 3) hipLaunchKernelGGL((k_spmm_pair<T, 5, 16, false, 3>), dim3(nb), dim3(threads), 0, s, A.n, A.pair_begin, A.pair_end, mapping, A.rowptr, A.col, A.val, x, y, part, scal, step);
+        const int mode = g_tune.spmm_mode;
+        if (variant == 3 && lpr == 16 && mode >= 1 && mode <= 3 && !part) {
+            if (mode == 1) launch_pair(k_spmm_pair<T, 5, 16, false, 1>);
+            if (mode == 2) launch_pair(k_spmm_pair<T, 5, 16, false, 2>);
+            if (mode == 3) launch_pair(k_spmm_pair<T, 5, 16, false, 3>);
             return;
         }
     }
-    if (variant == 3) {
-        if (lpr >= 32) { REMO_SPMM_PAIR(32); }
-        else if (lpr == 16) { REMO_SPMM_PAIR(16); }
-        else if (lpr == 8) { REMO_SPMM_PAIR(8); }
-        else { REMO_SPMM_PAIR(4); }
-    } else {
-        if (lpr >= 32) { REMO_SPMM(32); }
-        else if (lpr == 16) { REMO_SPMM(16); }
-        else if (lpr == 8) { REMO_SPMM(8); }
-        else { REMO_SPMM(4); }
-    }
-#undef REMO_SPMM
-#undef REMO_SPMM_PAIR
+    // the lanes per row the kernels are instantiated for; `part`: the launch leaves partial sums of <x, y> (DOT)
+    auto for_lanes = [&](auto fn) {
+        if (lpr >= 32) fn(int_c<32>{});
+        else if (lpr == 16) fn(int_c<16>{});
+        else if (lpr == 8) fn(int_c<8>{});
+        else fn(int_c<4>{});
+    };
+    for_lanes([&](auto lc) {
+        constexpr int L = decltype(lc)::value;
+        if (variant == 3) { if (part) launch_pair(k_spmm_pair<T, K, L, true>); else launch_pair(k_spmm_pair<T, K, L, false>); }
+        else { if (part) launch(k_spmm<T, K, L, true>); else launch(k_spmm<T, K, L, false>); }
+    });
 }
 
 template <class T> bool patch_applies(const CsrViewT<T> &A, int k) {
@@ -634,16 +604,7 @@ template <class T> void launch_spmm(const CsrViewT<T> &A, int k, const T *x, T *
         launch_patch_spmm(A, k, x, y, part, scal, nb, s, step, defer);
         return;
     }
-    switch (k) {
-        case 1: spmm_dispatch<T, 1>(A, x, y, part, scal, step, nb, s); break;
-        case 2: spmm_dispatch<T, 2>(A, x, y, part, scal, step, nb, s); break;
-        case 3: spmm_dispatch<T, 3>(A, x, y, part, scal, step, nb, s); break;
-        case 4: spmm_dispatch<T, 4>(A, x, y, part, scal, step, nb, s); break;
-        case 5: spmm_dispatch<T, 5>(A, x, y, part, scal, step, nb, s); break;
-        case 6: spmm_dispatch<T, 6>(A, x, y, part, scal, step, nb, s); break;
-        case 7: spmm_dispatch<T, 7>(A, x, y, part, scal, step, nb, s); break;
-        default: spmm_dispatch<T, 8>(A, x, y, part, scal, step, nb, s); break;
-    }
+    for_k(k, [&](auto kc) { constexpr int K = decltype(kc)::value; spmm_dispatch<T, K>(A, x, y, part, scal, step, nb, s); });
 }
 template void launch_spmm<double>(const CsrViewT<double> &, int, const double *, double *, double *, const double *, int, hipStream_t, int, bool);
 template void launch_spmm<float>(const CsrViewT<float> &, int, const float *, float *, double *, const double *, int, hipStream_t, int, bool);

@@ -628,34 +628,15 @@ __global__ void __launch_bounds__(256) k_patch_dot(int64_t npatch, const double 
     if (threadIdx.x < K) part[blockIdx.x * K + threadIdx.x] = pick<K>(dot, threadIdx.x);
 }
 
-int g_patch_mode = 0;  // key 21: ablation mode of k_patch_apply (fp64, k = 5 only)
 long long *g_patch_stamps = nullptr;   // mode 4: device buffer [grid][8] of phase time stamps (remo_debug_patch_phases)
 
 }  // namespace
 
-void set_patch_mode(int mode) { g_patch_mode = mode; }
 void set_patch_stamps(long long *buf) { g_patch_stamps = buf; }
-
-// remo_debug_tune key 26: the register-lean order of the kernel's arithmetic phase (k_patch_apply LEAN): -1 = in fp32 storage only
-// (default), 0 = never, 1 = always.  fp32: 72-80 registers against 104 at first (111 against 124 us at 443 k tetrahedra); once the
-// staging / output phases had their pass count as a compile-time constant the plain order needed 67 registers by itself and was
-// level at 443 k tetrahedra (87 against 90 us) but not on the batches of the headline sweep (370 k / 320 k: 86 against 77 us, solve
-// 158.3 against 153.1 ms per four batches): lean stays the fp32 default.  fp64: 96 registers with spills, five waves: 160 against 156 us.
-int g_patch_lean = -1;
-void set_patch_lean(int v) { g_patch_lean = v; }
-int g_patch_trim = 1;
-void set_patch_trim(int v) { g_patch_trim = v; }
-int g_patch_spread = 4;
-void set_patch_spread(int v) { g_patch_spread = v; }
 
 #ifdef REMO_PROBES
 #include "patch_persist.inc"     // keys 34 and 35: k_patch_apply_p / k_patch_apply_r and launch_patch_persistent
 #endif
-
-// remo_debug_tune key 40: 2 (default) = two elements per lane where the patch then fits the tables (patch_rounds), 1 = one
-int g_patch_rounds = 2;
-void set_patch_rounds(int v) { g_patch_rounds = v == 1 ? 1 : 2; }
-int patch_rounds_wanted() { return g_patch_rounds; }
 
 // one lane per (element, right-hand side) and round; at most 204 elements (the table builder sorts 20 slots per element in 32 KB of LDS)
 constexpr int kPatchMaxElements = 204;   // 204 x 20 slots sort in 4096 LDS keys (and fit the 13-bit slot field of a key)
@@ -692,7 +673,7 @@ void build_patch_tables(Arena &ar, hipStream_t s, const DeviceSymbolic &sy, cons
     if (rows_cap > E * 20) rows_cap = E * 20;
     int npad = 256;
     while (npad < E * 20) npad <<= 1;
-    out.nt = nt; out.n = n; out.E = E; out.rows_cap = rows_cap; out.spread = g_patch_spread; out.trim = g_patch_trim;
+    out.nt = nt; out.n = n; out.E = E; out.rows_cap = rows_cap; out.spread = g_tune.patch_spread; out.trim = g_tune.patch_trim;
     // constants, kept for the layout of the kernels' by-value argument (kernels.h): threads per workgroup, every row through the slab, no stagger
     out.block = kPatchBlock; out.all_slab = 1; out.stagger = 0;
     out.npatch = (nt + E - 1) / E;
@@ -742,17 +723,23 @@ template <class T, int K> static void patch_dispatch(const CsrViewT<T> &A, const
     };
     bool launched = false;
 #ifdef REMO_PROBES      // persistent forms, ablations (wrong results on purpose), the phase probe, the other arithmetic order: tools/ builds only (make probes)
-    launched = launch_patch_persistent<T, K>(P, g_patch_mode, g_patch_stamps, x, y, pp, scal, step, bins, s);
+    const int mode = g_tune.patch_mode, lean = g_tune.patch_lean;
+    launched = launch_patch_persistent<T, K>(P, mode, g_patch_stamps, x, y, pp, scal, step, bins, s);
     if constexpr (K == 5) {     // ablations and the phase probe (tools/probe_patch.py); one-round tables only
-        if (!launched && tb.rounds == 1 && g_patch_mode >= 1 && g_patch_mode <= 3 + (g_patch_stamps ? 1 : 0)) {
+        if (!launched && tb.rounds == 1 && mode >= 1 && mode <= 3 + (g_patch_stamps ? 1 : 0)) {
             launched = true;
-            if (g_patch_mode == 1) launch(k_patch_apply<T, 5, 1>);
-            else if (g_patch_mode == 2) launch(k_patch_apply<T, 5, 2>);
-            else if (g_patch_mode == 3) launch(k_patch_apply<T, 5, 3>);
+            if (mode == 1) launch(k_patch_apply<T, 5, 1>);
+            else if (mode == 2) launch(k_patch_apply<T, 5, 2>);
+            else if (mode == 3) launch(k_patch_apply<T, 5, 3>);
             else launch(k_patch_apply<T, 5, 4>);
         }
     }
-    if (!launched && tb.rounds == 1 && ((g_patch_lean == 1) != (sizeof(T) == 4)) && g_patch_lean >= 0) {     // the other order than the product's
+    // remo_debug_tune key 26: the register-lean order of the kernel's arithmetic phase (k_patch_apply LEAN): -1 = in fp32 storage only
+    // (default), 0 = never, 1 = always.  fp32: 72-80 registers against 104 at first (111 against 124 us at 443 k tetrahedra); once the
+    // staging / output phases had their pass count as a compile-time constant the plain order needed 67 registers by itself and was
+    // level at 443 k tetrahedra (87 against 90 us) but not on the batches of the headline sweep (370 k / 320 k: 86 against 77 us, solve
+    // 158.3 against 153.1 ms per four batches): lean stays the fp32 default.  fp64: 96 registers with spills, five waves: 160 against 156 us.
+    if (!launched && tb.rounds == 1 && ((lean == 1) != (sizeof(T) == 4)) && lean >= 0) {     // the other order than the product's
         if (sizeof(T) == 4) launch(k_patch_apply<T, K, 0>); else launch(k_patch_apply<T, K, 0, true>);
         launched = true;
     }
@@ -779,16 +766,7 @@ template <class T, int K> static void patch_dispatch(const CsrViewT<T> &A, const
 }
 
 template <class T> void launch_patch_spmm(const CsrViewT<T> &A, int k, const T *x, T *y, double *part, const double *scal, int nb, hipStream_t s, int step, bool defer) {
-    switch (k) {
-        case 1: patch_dispatch<T, 1>(A, x, y, part, scal, step, nb, s, defer); break;
-        case 2: patch_dispatch<T, 2>(A, x, y, part, scal, step, nb, s, defer); break;
-        case 3: patch_dispatch<T, 3>(A, x, y, part, scal, step, nb, s, defer); break;
-        case 4: patch_dispatch<T, 4>(A, x, y, part, scal, step, nb, s, defer); break;
-        case 5: patch_dispatch<T, 5>(A, x, y, part, scal, step, nb, s, defer); break;
-        case 6: patch_dispatch<T, 6>(A, x, y, part, scal, step, nb, s, defer); break;
-        case 7: patch_dispatch<T, 7>(A, x, y, part, scal, step, nb, s, defer); break;
-        default: patch_dispatch<T, 8>(A, x, y, part, scal, step, nb, s, defer); break;
-    }
+    for_k(k, [&](auto kc) { constexpr int K = decltype(kc)::value; patch_dispatch<T, K>(A, x, y, part, scal, step, nb, s, defer); });
 }
 // The PCG's product with the search direction in fp32 storage (PcgBuffersT::p32): the shared rows stay in the slab (defer_q), the
 // patches' <p, A p> go where launch_patch_spmm puts them.  The tables' own kernel or none: a batch the patch operator does not take
@@ -808,16 +786,7 @@ template <int K> static void patch_dispatch_x32(const CsrViewT<double> &A, const
 
 void launch_patch_spmm_x32(const CsrViewT<double> &A, int k, const float *x, double *part, const double *scal, int nb, hipStream_t s, int step) {
     if (!patch_applies(A, k) || !part) throw std::logic_error("patch operator on an fp32 direction: no patch tables for this batch");
-    switch (k) {
-        case 1: patch_dispatch_x32<1>(A, x, part, scal, step, nb, s); break;
-        case 2: patch_dispatch_x32<2>(A, x, part, scal, step, nb, s); break;
-        case 3: patch_dispatch_x32<3>(A, x, part, scal, step, nb, s); break;
-        case 4: patch_dispatch_x32<4>(A, x, part, scal, step, nb, s); break;
-        case 5: patch_dispatch_x32<5>(A, x, part, scal, step, nb, s); break;
-        case 6: patch_dispatch_x32<6>(A, x, part, scal, step, nb, s); break;
-        case 7: patch_dispatch_x32<7>(A, x, part, scal, step, nb, s); break;
-        default: patch_dispatch_x32<8>(A, x, part, scal, step, nb, s); break;
-    }
+    for_k(k, [&](auto kc) { constexpr int K = decltype(kc)::value; patch_dispatch_x32<K>(A, x, part, scal, step, nb, s); });
 }
 
 template void launch_patch_spmm<double>(const CsrViewT<double> &, int, const double *, double *, double *, const double *, int, hipStream_t, int, bool);

@@ -579,13 +579,9 @@ __global__ void __launch_bounds__(256, 3) k_patch_apply_r(PatchTables tb, int R,
 // chains (7.5 k) are bound by the fp64 rate whenever the CU's two workgroups are in them together.  With two contexts on the GPU the
 // two forms give the same points/s (115.9 against 115.3).  Kept for that record and as the starting point of a version with
 // 16-byte-tiled rows; not the default.
-int g_patch_persist = 0;
-int set_patch_persist(int v) { const int was = g_patch_persist; g_patch_persist = (v == 1 || v == 2) ? v : 0; return was; }
-int g_patch_wgs_per_xcd = 0;   // key 35: workgroups per XCD of the persistent kernel (0 = as many as stay resident); tests make small meshes walk several patches per workgroup
-void set_patch_wgs_per_xcd(int v) { g_patch_wgs_per_xcd = v > 0 ? v : 0; }
-
-// Launches the persistent form key 34 asks for, if it can run this batch (mode: g_patch_mode, stamps: g_patch_stamps of patch.hip);
-// false: nothing was launched and k_patch_apply takes the application.  per = patches per XCD.
+//
+// Launches the persistent form key 34 asks for, if it can run this batch (mode: key 21, stamps: g_patch_stamps of patch.hip), on key 35's
+// workgroups per XCD where that is fewer than stay resident; false: nothing was launched and k_patch_apply takes the application.  per = patches per XCD.
 template <class T, int K>
 static bool launch_patch_persistent(const PatchOpT<T> &P, int mode, long long *stamps, const T *x, T *y, double *pp2, const double *scal, int step,
                                     double *bins, hipStream_t s) {
@@ -593,14 +589,15 @@ static bool launch_patch_persistent(const PatchOpT<T> &P, int mode, long long *s
     const int64_t per = (tb.npatch + 7) / 8;
     if (mode != 0 && mode != 4) return false;
     if (tb.rounds != 1) return false;      // the persistent forms take one element per lane
-    if (g_patch_persist == 2 && P.lds_rows <= kPatchPasses * (256 / K) && P.lds_rows <= 1024) {
+    const int form = g_tune.patch_persist, wgs_per_xcd = g_tune.patch_wgs_per_xcd;
+    if (form == 2 && P.lds_rows <= kPatchPasses * (256 / K) && P.lds_rows <= 1024) {
         // persistent form with the prefetch through registers: three workgroups per CU by its registers (LDS would allow four or five)
         const size_t bytes = patch_lds_bytes_r(P.lds_rows, K, tb.E);
         int wpc = int((160 * 1024) / (bytes + 16 * K * 8 + 1024));
         if (wpc > 3) wpc = 3;
         if (wpc >= 1 && bytes <= 64 * 1024 - 2048) {
             int64_t nwx = int64_t(32) * wpc;
-            if (g_patch_wgs_per_xcd > 0 && g_patch_wgs_per_xcd < nwx) nwx = g_patch_wgs_per_xcd;
+            if (wgs_per_xcd > 0 && wgs_per_xcd < nwx) nwx = wgs_per_xcd;
             if (nwx > per) nwx = per;
             if (nwx < 1) nwx = 1;
             if (stamps && K == 5)
@@ -610,7 +607,7 @@ static bool launch_patch_persistent(const PatchOpT<T> &P, int mode, long long *s
             return true;
         }
     }
-    if (g_patch_persist == 1) {
+    if (form == 1) {
         // persistent form: as many workgroups as stay resident (LDS: two row images + tables per workgroup), 32 CUs per XCD
         const size_t bytes = patch_lds_bytes_p(P.lds_rows, K, tb.E);
         const size_t lds_cu = 160 * 1024, per_wg = bytes + 16 * K * 8 + 1024;
@@ -623,7 +620,7 @@ static bool launch_patch_persistent(const PatchOpT<T> &P, int mode, long long *s
             if (!ok) ok = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(150 * 1024)) == hipSuccess;
             if (ok) {
                 int64_t nwx = int64_t(32) * wpc;
-                if (g_patch_wgs_per_xcd > 0 && g_patch_wgs_per_xcd < nwx) nwx = g_patch_wgs_per_xcd;
+                if (wgs_per_xcd > 0 && wgs_per_xcd < nwx) nwx = wgs_per_xcd;
                 if (nwx > per) nwx = per;
                 if (nwx < 1) nwx = 1;
                 if (stamps && K == 5) {

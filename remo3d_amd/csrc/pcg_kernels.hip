@@ -1167,16 +1167,6 @@ __global__ void __launch_bounds__(256) k_cheb_pair(int64_t nv, const int32_t *__
     }
 }
 
-static int g_fold_first = 1;   // remo_debug_tune key 9: FIRST Chebyshev step inside the update launch (0 = own launch)
-void set_fold_first(int v) { g_fold_first = v; }
-int g_slab_ahead = 1;      // remo_debug_tune key 27: 0 = the update launch walks the slab slots of a shared row one by one
-int g_slab_masked = 1;   // remo_debug_tune key 29: 0 = every row fetches four slab slots and weights the ones it does not have by zero (the form before)
-int g_flat_direction = 1;   // remo_debug_tune key 30: 1 (default) = the direction launch walks its vectors as flat arrays, 16 bytes per lane; 0 = a k-wide row per lane
-int g_tile_update = 1;      // remo_debug_tune key 31: 1 (default, fp64 storage) = the update launch takes 64 rows per wave, a value per lane and pass (k_pcg_update_tile)
-void set_tile_update(int v) { g_tile_update = v ? 1 : 0; }
-void set_flat_direction(int v) { g_flat_direction = v ? 1 : 0; }
-void set_slab_masked(int v) { g_slab_masked = v ? 1 : 0; }
-void set_slab_ahead(int v) { g_slab_ahead = v ? 1 : 0; }
 int vec_grid(int64_t n) {
     int64_t g = (n + 255) / 256;
     if (g > kMaxPartialBlocks / 2) g = kMaxPartialBlocks / 2;
@@ -1190,17 +1180,11 @@ int cheb_grid(int64_t nv) {
     if (g > kMaxPartialBlocks / 2) g = kMaxPartialBlocks / 2;
     return int(g);
 }
-#define REMO_K_SWITCH(k, CALL) \
-    switch (k) {               \
-        case 1: { constexpr int KK = 1; CALL; } break; \
-        case 2: { constexpr int KK = 2; CALL; } break; \
-        case 3: { constexpr int KK = 3; CALL; } break; \
-        case 4: { constexpr int KK = 4; CALL; } break; \
-        case 5: { constexpr int KK = 5; CALL; } break; \
-        case 6: { constexpr int KK = 6; CALL; } break; \
-        case 7: { constexpr int KK = 7; CALL; } break; \
-        default: { constexpr int KK = 8; CALL; } break; \
-    }
+
+// every launch of this file: `grid` workgroups of 256 threads, no dynamic LDS
+template <class Kernel, class... Args> static void launch256(Kernel kernel, int grid, hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, args...);
+}
 
 template <class T> static ChebArgsT<T> cheb_args(const PcgBuffersT<T> &b) {
     ChebArgsT<T> c;
@@ -1221,7 +1205,7 @@ template bool pcg_update_folds<float>(const PcgBuffersT<float> &);
 template <class T> static bool cheb_first_folds(const PcgBuffersT<T> &b) {
     // measured in the bench, fold on vs off on one box: -2.3 % solve time at 12.8 k vertices, -0.9 % at 27 k, +0.4 % at 83 k
     // (there the step is real work, not launch latency): small vertex blocks only
-    return g_fold_first && !b.amg && b.cheb_degree >= 3 && b.nv_coarse > 0 && b.nv_coarse <= 32768 && !(b.sq_rowptr && (b.cheb_degree & 1) == 0);
+    return g_tune.fold_first && !b.amg && b.cheb_degree >= 3 && b.nv_coarse > 0 && b.nv_coarse <= 32768 && !(b.sq_rowptr && (b.cheb_degree & 1) == 0);
 }
 
 template <class T> static void launch_cheb(const CsrViewT<T> &A, int k, int step, const PcgBuffersT<T> &b, double *part_slot, hipStream_t s, bool first_done = false) {
@@ -1252,19 +1236,16 @@ template <class T> static void launch_cheb(const CsrViewT<T> &A, int k, int step
             const bool first = (j == 0), last = (j + 1 == np);
             // only the LAST launch leaves partial sums, so only it is tied to the cheb_grid slots
             auto grid_for = [&](int lpr) { int64_t gg = (b.nv_coarse + 256 / lpr - 1) / (256 / lpr); if (last && gg > g_last) gg = g_last; if (gg > 4096) gg = 4096; return int(gg); };
-#define REMO_CHEB2(LPRV, F, L)                                                                                                                        \
-    REMO_K_SWITCH(k, hipLaunchKernelGGL((k_cheb_pair<T, KK, LPRV, F, L>), dim3(grid_for(LPRV)), dim3(256), 0, s, b.nv_coarse, b.sq_rowptr, b.sq_col, b.sq_a, \
-                                        b.sq_b, b.dinv, wold, wnew, b.cz, a + bb, a * bb, b.r, part, b.rz0, step))
-#define REMO_CHEB2_FL(LPRV)                                 \
-    if (first && last) { REMO_CHEB2(LPRV, true, true); }    \
-    else if (first) { REMO_CHEB2(LPRV, true, false); }      \
-    else if (last) { REMO_CHEB2(LPRV, false, true); }       \
-    else { REMO_CHEB2(LPRV, false, false); }
-            if (b.sq_lanes >= 32) { REMO_CHEB2_FL(32) }
-            else if (b.sq_lanes >= 16) { REMO_CHEB2_FL(16) }
-            else { REMO_CHEB2_FL(8) }
-#undef REMO_CHEB2_FL
-#undef REMO_CHEB2
+            auto for_lanes = [&](auto fn) {
+                if (b.sq_lanes >= 32) fn(int_c<32>{});
+                else if (b.sq_lanes >= 16) fn(int_c<16>{});
+                else fn(int_c<8>{});
+            };
+            for_k(k, [&](auto kc) { for_lanes([&](auto lc) { for_bool(first, [&](auto fc) { for_bool(last, [&](auto ec) {
+                constexpr int K = decltype(kc)::value, LPR = decltype(lc)::value;
+                launch256(k_cheb_pair<T, K, LPR, decltype(fc)::value, decltype(ec)::value>, grid_for(LPR), s, b.nv_coarse, b.sq_rowptr, b.sq_col, b.sq_a,
+                          b.sq_b, b.dinv, wold, wnew, b.cz, a + bb, a * bb, b.r, part, b.rz0, step);
+            }); }); }); });
         }
         return;
     }
@@ -1294,24 +1275,25 @@ template <class T> static void launch_cheb(const CsrViewT<T> &A, int k, int step
         // 17.9 us per launch under rocprofv3, profiles/r01_f_kernel_stats_sizeL_10depths_before_grid_fix.csv; after: 14.2 us, …_after_grid_fix.csv)
         const int64_t g_rows = (b.nv_coarse + 31) / 32;
         const int gl = last ? g : int(g_rows < 8192 ? g_rows : 8192);
-#define REMO_CHEB_E(F, L, E)                                                                                                                        \
-    if (chain32) {                                                                                                                                  \
-        REMO_K_SWITCH(k, hipLaunchKernelGGL((k_cheb_step<T, float, KK, F, L, E>), dim3(gl), dim3(256), 0, s, b.nv_coarse, E ? b.ell_tail : vrow, vcol, b.c32_val, b.c32_dinv, \
-                                            (const float *)b.c32_d[j & 1], b.c32_d[(j + 1) & 1], b.c32_z, b.c32_res, b.cz, c1, c2, inv_theta, b.r, part, b.rz0, 0, step, \
-                                            b.ell_col, b.c32_ell_val));                                                                             \
-    } else {                                                                                                                                        \
-        REMO_K_SWITCH(k, hipLaunchKernelGGL((k_cheb_step<T, T, KK, F, L, E>), dim3(gl), dim3(256), 0, s, b.nv_coarse, E ? b.ell_tail : vrow, vcol, vval, b.dinv, dold, dnew, \
-                                            b.cz, b.cres, b.cz, c1, c2, inv_theta, b.r, part, b.rz0, commit, step, b.ell_col, b.ell_val));               \
-    }
-#define REMO_CHEB(F, L)                \
-    if (ell) { REMO_CHEB_E(F, L, true) } \
-    else { REMO_CHEB_E(F, L, false) }
-        if (first && last) { if (b.cheb_degree == 1) { REMO_CHEB(true, 1); } else { REMO_CHEB(true, 2); } }
-        else if (first) { REMO_CHEB(true, 0); }
-        else if (last) { REMO_CHEB(false, 2); }
-        else { REMO_CHEB(false, 0); }
-#undef REMO_CHEB
-#undef REMO_CHEB_E
+        // k_cheb_step<.., FIRST, LAST, ELL> as the launches of a chain take it: (FIRST, LAST) = (1, 1) the only step of degree 1, (1, 2) the
+        // only launch of a higher degree, (1, 0), (0, 2) and (0, 0) - there is no (0, 1)
+        auto go = [&](auto fc, auto lc) {
+            for_k(k, [&](auto kc) { for_bool(ell, [&](auto ec) {
+                constexpr int K = decltype(kc)::value, LAST = decltype(lc)::value;
+                constexpr bool FIRST = decltype(fc)::value, ELL = decltype(ec)::value;
+                if (chain32)
+                    launch256(k_cheb_step<T, float, K, FIRST, LAST, ELL>, gl, s, b.nv_coarse, ELL ? b.ell_tail : vrow, vcol, b.c32_val, b.c32_dinv,
+                              (const float *)b.c32_d[j & 1], b.c32_d[(j + 1) & 1], b.c32_z, b.c32_res, b.cz, c1, c2, inv_theta, b.r, part, b.rz0, 0, step,
+                              b.ell_col, b.c32_ell_val);
+                else
+                    launch256(k_cheb_step<T, T, K, FIRST, LAST, ELL>, gl, s, b.nv_coarse, ELL ? b.ell_tail : vrow, vcol, vval, b.dinv, dold, dnew,
+                              b.cz, b.cres, b.cz, c1, c2, inv_theta, b.r, part, b.rz0, commit, step, b.ell_col, b.ell_val);
+            }); });
+        };
+        if (first && last) { if (b.cheb_degree == 1) go(std::true_type{}, int_c<1>{}); else go(std::true_type{}, int_c<2>{}); }
+        else if (first) go(std::true_type{}, int_c<0>{});
+        else if (last) go(std::false_type{}, int_c<2>{});
+        else go(std::false_type{}, int_c<0>{});
     }
 }
 
@@ -1321,19 +1303,17 @@ template <class T> void launch_pcg_init(const CsrViewT<T> &A, int k, const T *f,
     const int64_t n = A.n;
     const int g = b.nb_vec;
     const ChebArgsT<T> ch = cheb_args(b);
+    auto go = [&](auto *p) {      // p: the search direction in its storage type TP
+        using TP = std::remove_pointer_t<decltype(p)>;
+        for_k(k, [&](auto kc) { constexpr int K = decltype(kc)::value; launch256(k_pcg_init<T, K, TP>, g, s, n, ch, f, b.dinv, b.x, b.r, p, b.part_rz); });
+        launch_cheb(A, k, 0, b, b.part_rz, s);
+        if (ch.nv > 0)
+            for_k(k, [&](auto kc) { constexpr int K = decltype(kc)::value; launch256(k_pcg_direction_row<T, K, TP>, g, s, n, 1, 0, 0.0, nb_rz(b), ch, b.part_rz, b.rz0, b.r, p, b.dinv, (T *)nullptr); });
+    };
     if constexpr (sizeof(T) == 8) {
-        if (b.p32) {      // the search direction in fp32 storage: the same launches, TP = float
-            REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_init<double, KK, float>), dim3(g), dim3(256), 0, s, n, ch, f, b.dinv, b.x, b.r, b.p32, b.part_rz));
-            launch_cheb(A, k, 0, b, b.part_rz, s);
-            if (ch.nv > 0)
-                REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction_row<double, KK, float>), dim3(g), dim3(256), 0, s, n, 1, 0, 0.0, nb_rz(b), ch, b.part_rz, b.rz0, b.r, b.p32, b.dinv, (double *)nullptr));
-            return;
-        }
+        if (b.p32) { go(b.p32); return; }      // the search direction in fp32 storage: the same launches, TP = float
     }
-    REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_init<T, KK>), dim3(g), dim3(256), 0, s, n, ch, f, b.dinv, b.x, b.r, b.p, b.part_rz));
-    launch_cheb(A, k, 0, b, b.part_rz, s);
-    if (ch.nv > 0)
-        REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction_row<T, KK>), dim3(g), dim3(256), 0, s, n, 1, 0, 0.0, nb_rz(b), ch, b.part_rz, b.rz0, b.r, b.p, b.dinv, (T *)nullptr));
+    go(b.p);
 }
 
 template <class T> static UpdHeadT<T> update_head(const CsrViewT<T> &A, int step, double tol2, const PcgBuffersT<T> &b) {
@@ -1360,15 +1340,15 @@ template <class T> void launch_pcg_update(const CsrViewT<T> &A, int k, int step,
     const bool slab = b.defer_q && A.patch && !folded;      // the shared rows of q = A p are still in the patch operator's boundary slab
     const bool skip_x = b.x_in_direction;
     uint64_t slab_bytes = 0;
-    if (slab && g_slab_masked) {
+    if (slab && g_tune.slab_masked) {
         const uint64_t bytes = uint64_t(A.patch->t.nslot_cap) * uint64_t(k) * sizeof(T);
         slab_bytes = bytes < kBufferLimit ? bytes : 0;
     }
     const bool masked = slab_bytes != 0;
     // (fp32 storage: 256 bytes per wave and access - the row form is ahead there, 74.7 against 76.3 ms)
-    const bool tile = g_tile_update && sizeof(T) == 8 && masked && A.patch->t.row4 && skip_x && uint64_t(n) * uint64_t(k) * sizeof(T) < kBufferLimit &&
+    const bool tile = g_tune.tile_update && sizeof(T) == 8 && masked && A.patch->t.row4 && skip_x && uint64_t(n) * uint64_t(k) * sizeof(T) < kBufferLimit &&
                       uint64_t(n) * 16 < kBufferLimit;
-    const bool one_by_one = kProbes && slab && !g_slab_ahead;      // key 27 = 0: no product build reaches it
+    const bool one_by_one = kProbes && slab && !g_tune.slab_ahead;      // key 27 = 0: no product build reaches it
     // 2. its arguments
     UpdHeadT<T> hd = update_head(A, step, tol2, b);
     hd.ev = EvSlotsT<T>{b.x_ev_at, b.x_ev, b.x_ev_n};
@@ -1378,36 +1358,37 @@ template <class T> void launch_pcg_update(const CsrViewT<T> &A, int k, int step,
     if (slab) { qv.bptr = A.patch->t.bptr; qv.bslot = A.patch->t.bslot; qv.Yb = A.patch->Yb; }
     if (masked) { qv.slab_bytes = slab_bytes; qv.row4 = A.patch->t.row4; }
     // 3. the launch
-    if constexpr (sizeof(T) == 8) {
-        if (b.p32) {      // fp32 search direction: read by the x_ev slots alone (the host grants it with defer_q, x in the direction launch and no x: set_launch_shape)
-            if (!slab || !skip_x || b.x || one_by_one) throw std::logic_error("update launch: an fp32 search direction outside the evaluated-values path of the patch operator");
-            if (tile) { REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_update_tile<double, KK, float>), dim3(g), dim3(256), 0, s, n, hd, ch.nv, nxt, b.p32, b.r, b.dinv, qv)); }
-            else if (masked) { REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_update_p32<KK, true>), dim3(g), dim3(256), 0, s, n, hd, ch.nv, nxt, b.p32, b.q, b.r, b.dinv, qv)); }
-            else { REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_update_p32<KK, false>), dim3(g), dim3(256), 0, s, n, hd, ch.nv, nxt, b.p32, b.q, b.r, b.dinv, qv)); }
-            launch_cheb(A, k, step, b, nxt, s, false);
-            return;
+    // fp32 search direction (fp64 storage): read by the x_ev slots alone (the host grants it with defer_q, x in the direction launch and no x: set_launch_shape)
+    if (sizeof(T) == 8 && b.p32 && (!slab || !skip_x || b.x || one_by_one)) throw std::logic_error("update launch: an fp32 search direction outside the evaluated-values path of the patch operator");
+    for_k(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        if constexpr (sizeof(T) == 8) {
+            if (b.p32) {
+                if (tile) launch256(k_pcg_update_tile<double, K, float>, g, s, n, hd, ch.nv, nxt, b.p32, b.r, b.dinv, qv);
+                else if (masked) launch256(k_pcg_update_p32<K, true>, g, s, n, hd, ch.nv, nxt, b.p32, b.q, b.r, b.dinv, qv);
+                else launch256(k_pcg_update_p32<K, false>, g, s, n, hd, ch.nv, nxt, b.p32, b.q, b.r, b.dinv, qv);
+                return;
+            }
         }
-    }
-    if (folded) {
-        FoldArgsT<T> fold;
-        const double theta = 0.5 * (b.cheb_lmax + b.cheb_lmin), delta = 0.5 * (b.cheb_lmax - b.cheb_lmin);
-        const double sig = theta / delta, rho = 1.0 / sig, rho_new = 1.0 / (2.0 * sig - rho);
-        fold.nb_flat = g;
-        fold.rowptr = b.vb_rowptr ? b.vb_rowptr : A.rowptr; fold.col = b.vb_rowptr ? b.vb_col : A.col; fold.val = b.vb_rowptr ? b.vb_val : A.val;
-        fold.d_new = b.cd[1]; fold.stage = b.cd[0];
-        fold.c1 = rho_new * rho; fold.c2 = 2.0 * rho_new / delta;      // the j = 0 coefficients of launch_cheb
-        const int grid = g + int((b.nv_coarse + 31) / 32);   // the vertex workgroups leave no partial sums: one row group each
-        REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_update_folded<T, KK>), dim3(grid), dim3(256), 0, s, n, hd, ch, nxt, b.p, b.q, b.x, b.r, b.dinv, fold, qv.skip_x));
-    } else if (tile) {
-        if constexpr (sizeof(T) == 8) REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_update_tile<T, KK>), dim3(g), dim3(256), 0, s, n, hd, ch.nv, nxt, b.p, b.r, b.dinv, qv));
-    } else if (one_by_one) {
-        if constexpr (kProbes) REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_update<T, KK, false, false>), dim3(g), dim3(256), 0, s, n, hd, ch.nv, nxt, b.p, b.q, b.x, b.r, b.dinv, qv));
-    } else if (masked) {
-        REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_update<T, KK, true>), dim3(g), dim3(256), 0, s, n, hd, ch.nv, nxt, b.p, b.q, b.x, b.r, b.dinv, qv));
-    } else {
-        REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_update<T, KK, false>), dim3(g), dim3(256), 0, s, n, hd, ch.nv, nxt, b.p, b.q, b.x, b.r, b.dinv, qv));
-    }
-    launch_cheb(A, k, step, b, nxt, s, folded);
+        if (folded) {
+            FoldArgsT<T> fold;
+            const double theta = 0.5 * (b.cheb_lmax + b.cheb_lmin), delta = 0.5 * (b.cheb_lmax - b.cheb_lmin);
+            const double sig = theta / delta, rho = 1.0 / sig, rho_new = 1.0 / (2.0 * sig - rho);
+            fold.nb_flat = g;
+            fold.rowptr = b.vb_rowptr ? b.vb_rowptr : A.rowptr; fold.col = b.vb_rowptr ? b.vb_col : A.col; fold.val = b.vb_rowptr ? b.vb_val : A.val;
+            fold.d_new = b.cd[1]; fold.stage = b.cd[0];
+            fold.c1 = rho_new * rho; fold.c2 = 2.0 * rho_new / delta;      // the j = 0 coefficients of launch_cheb
+            const int grid = g + int((b.nv_coarse + 31) / 32);   // the vertex workgroups leave no partial sums: one row group each
+            launch256(k_pcg_update_folded<T, K>, grid, s, n, hd, ch, nxt, b.p, b.q, b.x, b.r, b.dinv, fold, qv.skip_x);
+        } else if (tile) {
+            if constexpr (sizeof(T) == 8) launch256(k_pcg_update_tile<T, K>, g, s, n, hd, ch.nv, nxt, b.p, b.r, b.dinv, qv);
+        } else if (one_by_one) {
+            if constexpr (kProbes) launch256(k_pcg_update<T, K, false, false>, g, s, n, hd, ch.nv, nxt, b.p, b.q, b.x, b.r, b.dinv, qv);
+        } else {
+            for_bool(masked, [&](auto mc) { launch256(k_pcg_update<T, K, decltype(mc)::value>, g, s, n, hd, ch.nv, nxt, b.p, b.q, b.x, b.r, b.dinv, qv); });
+        }
+    });
+    launch_cheb(A, k, step, b, nxt, s, folded);      // (an fp32 direction never goes with the folded step: it needs the slab)
 }
 
 // Residual replacement of the mixed mode, in place of launch_pcg_update at the chosen steps:
@@ -1444,10 +1425,10 @@ void launch_pcg_replace(const CsrViewT<float> &A, const CsrViewT<double> &A64, i
     double *nxt = b.part_rz + ((step + 1) & 1) * (kMaxPartialBlocks * 8);
     const ChebArgsT<float> ch = cheb_args(b);
     const UpdHeadT<float> hd = update_head(A, step, tol2, b);
-    REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_update_x<float, KK>), dim3(g), dim3(256), 0, s, n, hd, b.p, b.x));
+    for_k(k, [&](auto kc) { constexpr int K = decltype(kc)::value; launch256(k_pcg_update_x<float, K>, g, s, n, hd, b.p, b.x); });
     launch_mixed_accumulate(n * k, x64, b.x, 1, s);
     launch_spmm(A64, k, (const double *)x64, q64, (double *)nullptr, (const double *)nullptr, b.nb_spmv, s, 0);
-    REMO_K_SWITCH(k, hipLaunchKernelGGL((k_mixed_replace<KK>), dim3(g), dim3(256), 0, s, n, ch.nv, f64, q64, b.r, b.dinv, nxt, b.rz0, step));
+    for_k(k, [&](auto kc) { constexpr int K = decltype(kc)::value; launch256(k_mixed_replace<K>, g, s, n, ch.nv, f64, q64, b.r, b.dinv, nxt, b.rz0, step); });
     launch_cheb(A, k, step, b, nxt, s);
 }
 
@@ -1459,19 +1440,19 @@ template <class T> void launch_pcg_direction(const CsrViewT<T> &A, int k, int st
     const double *nw = b.part_rz + ((step + 1) & 1) * (kMaxPartialBlocks * 8);
     const ChebArgsT<T> ch = cheb_args(b);
     T *xp = (add_x && b.x_in_direction) ? b.x : nullptr;
-    const bool flat = g_flat_direction && uint64_t(n) * uint64_t(k) * sizeof(T) < 0xFFFFF000ull;
+    const bool flat = g_tune.flat_direction && uint64_t(n) * uint64_t(k) * sizeof(T) < 0xFFFFF000ull;
+    auto go = [&](auto *p, T *x) {      // p: the search direction in its storage type TP
+        using TP = std::remove_pointer_t<decltype(p)>;
+        for_k(k, [&](auto kc) {
+            constexpr int K = decltype(kc)::value;
+            if (flat) launch256(k_pcg_direction_flat<T, K, TP>, g, s, n, 0, step, tol2, nb_rz(b), ch, nw, b.rz0, b.r, p, b.dinv, x);
+            else launch256(k_pcg_direction_row<T, K, TP>, g, s, n, 0, step, tol2, nb_rz(b), ch, nw, b.rz0, b.r, p, b.dinv, x);
+        });
+    };
     if constexpr (sizeof(T) == 8) {
-        if (b.p32) {      // fp32 search direction (no x: evaluated values only)
-            if (flat) { REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction_flat<double, KK, float>), dim3(g), dim3(256), 0, s, n, 0, step, tol2, nb_rz(b), ch, nw, b.rz0, b.r, b.p32, b.dinv, (double *)nullptr)); }
-            else { REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction_row<double, KK, float>), dim3(g), dim3(256), 0, s, n, 0, step, tol2, nb_rz(b), ch, nw, b.rz0, b.r, b.p32, b.dinv, (double *)nullptr)); }
-            return;
-        }
+        if (b.p32) { go(b.p32, nullptr); return; }      // fp32 search direction (no x: evaluated values only)
     }
-    if (flat) {
-        REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction_flat<T, KK>), dim3(g), dim3(256), 0, s, n, 0, step, tol2, nb_rz(b), ch, nw, b.rz0, b.r, b.p, b.dinv, xp));
-    } else {
-        REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction_row<T, KK>), dim3(g), dim3(256), 0, s, n, 0, step, tol2, nb_rz(b), ch, nw, b.rz0, b.r, b.p, b.dinv, xp));
-    }
+    go(b.p, xp);
 }
 
 // One direction launch on the caller's own vectors and scalars, fp64 storage with the direction in fp32 (remo_debug_direction_forms):
@@ -1481,8 +1462,11 @@ void launch_direction_form(bool flat, int grid, int64_t n, int64_t nv, int k, in
     ChebArgsT<double> ch;
     ch.nv = nv; ch.inv_theta = 0.0; ch.z = z; ch.res = nullptr; ch.d0 = nullptr;
     if (uint64_t(n) * uint64_t(k) * 8 >= 0xFFFFF000ull || nb_rz > kMaxPartialBlocks || grid < 1) throw std::invalid_argument("launch_direction_form: sizes");
-    if (flat) { REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction_flat<double, KK, float>), dim3(grid), dim3(256), 0, s, n, 0, step, tol2, nb_rz, ch, part_rz_new, scal, r, p, dinv, (double *)nullptr)); }
-    else { REMO_K_SWITCH(k, hipLaunchKernelGGL((k_pcg_direction_row<double, KK, float>), dim3(grid), dim3(256), 0, s, n, 0, step, tol2, nb_rz, ch, part_rz_new, scal, r, p, dinv, (double *)nullptr)); }
+    for_k(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        if (flat) launch256(k_pcg_direction_flat<double, K, float>, grid, s, n, 0, step, tol2, nb_rz, ch, part_rz_new, scal, r, p, dinv, (double *)nullptr);
+        else launch256(k_pcg_direction_row<double, K, float>, grid, s, n, 0, step, tol2, nb_rz, ch, part_rz_new, scal, r, p, dinv, (double *)nullptr);
+    });
 }
 
 // probe builds: where the vector launches leave their clocks (nullptr: nowhere) - four words per workgroup, REMO_VEC_STAMPS
@@ -1496,7 +1480,7 @@ void set_vector_stamps(long long *stamps) {
 
 template <class T> void launch_pcg_final(int k, int step, const PcgBuffersT<T> &b, hipStream_t s) {
     const double *cur = b.part_rz + (step & 1) * (kMaxPartialBlocks * 8);
-    REMO_K_SWITCH(k, hipLaunchKernelGGL(k_pcg_final<KK>, dim3(1), dim3(256), 0, s, step, nb_rz(b), cur, b.rz0, b.progress, b.progress_len));
+    for_k(k, [&](auto kc) { constexpr int K = decltype(kc)::value; launch256(k_pcg_final<K>, 1, s, step, nb_rz(b), cur, b.rz0, b.progress, b.progress_len); });
 }
 
 #define REMO_INSTANTIATE_PCG(T)                                                                                          \

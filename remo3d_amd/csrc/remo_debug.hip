@@ -252,9 +252,9 @@ struct PatchProbe {
         else launch_spmm(b->A, k, dx, dy, nullptr, nullptr, nb, ctx->stream);
     }
     void stamped_runs() {     // three applications that leave their phase stamps (patch mode 4)
-        set_patch_stamps(st); set_patch_mode(4);
+        set_patch_stamps(st); g_tune.patch_mode = 4;
         for (int rep = 0; rep < 3; ++rep) once();
-        set_patch_mode(0); set_patch_stamps(nullptr);
+        g_tune.patch_mode = 0; set_patch_stamps(nullptr);
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     double timed_us() {       // the whole application (apply + reduce launches), microseconds per application
@@ -292,7 +292,7 @@ int remo_debug_patch_phases(remo_ctx_t *ctx, remo_batch_t *b, int32_t fp32, doub
 #else
     if (int rc = patch_probe_check(ctx, b)) return rc;
     // (this probe is about the one-workgroup-per-patch form; remo_debug_patch_phases_p is the persistent one's: key 34 is put back on every way out)
-    struct PersistOff { int was = set_patch_persist(0); ~PersistOff() { set_patch_persist(was); } } persist_off;
+    struct PersistOff { int was = g_tune.patch_persist; PersistOff() { g_tune.patch_persist = 0; } ~PersistOff() { g_tune.patch_persist = was; } } persist_off;
     try {
         HIP_TRY(hipSetDevice(ctx->device));
         const int64_t grid = (b->patch64.t.npatch + 7) / 8 * 8;
@@ -301,10 +301,10 @@ int remo_debug_patch_phases(remo_ctx_t *ctx, remo_batch_t *b, int32_t fp32, doub
             PatchProbe pr(ctx, b, fp32 != 0, size_t(grid) * 8);
             pr.stamped_runs();
             for (int mode = 0; mode <= 3; ++mode) {     // the ablation modes 0 .. 3
-                set_patch_mode(mode);
+                g_tune.patch_mode = mode;
                 out16[10 + mode] = pr.timed_us();
             }
-            set_patch_mode(0);
+            g_tune.patch_mode = 0;
             h = pr.stamps();
         }
         for (int i = 0; i < 10; ++i) out16[i] = 0.0;
@@ -323,7 +323,7 @@ int remo_debug_patch_phases(remo_ctx_t *ctx, remo_batch_t *b, int32_t fp32, doub
         out16[9] = double(cnt);
         return REMO_OK;
     } catch (const std::exception &ex) {
-        set_patch_mode(0); set_patch_stamps(nullptr);
+        g_tune.patch_mode = 0; set_patch_stamps(nullptr);
         return fail(ctx, REMO_ERR_DEVICE, ex.what());
     }
 #endif
@@ -360,7 +360,7 @@ int remo_debug_patch_phases_p(remo_ctx_t *ctx, remo_batch_t *b, int32_t fp32, do
         out16[10] = patches; out16[11] = wgs; out16[12] = longest; out16[13] = us;
         return REMO_OK;
     } catch (const std::exception &ex) {
-        set_patch_mode(0); set_patch_stamps(nullptr);
+        g_tune.patch_mode = 0; set_patch_stamps(nullptr);
         return fail(ctx, REMO_ERR_DEVICE, ex.what());
     }
 #endif
@@ -451,51 +451,65 @@ int remo_debug_vector_heads(remo_ctx_t *ctx, int32_t on, double *out8) {
 #endif
 }
 
-int remo_debug_tune(int32_t key, int32_t value) {
+namespace {
+// the keys of remo_debug_tune: the switch a key writes (tune.h has its meaning and default) and, where a switch holds a few values only,
+// how the caller's value is stored
+struct TuneKey {
+    int key;
+    int Tune::*field;
+    int (*stored)(int) = nullptr;
+};
+const TuneKey kTuneKeys[] = {
     // Keys that force ONE OF THE PRODUCT'S OWN PATHS - a choice the library makes by size or dimension, forced so that a small test
     // mesh reaches the code a large batch runs; every setting gives the same operator / preconditioner to rounding: always there.
-    switch (key) {
-        case 3: set_spmm_tuning(3, value); return 0;    // row schedule of the CSR product
-        case 6: g_tune.square = value; return 0;             // paired Chebyshev steps
-        case 9: set_fold_first(value); return 0;        // first Chebyshev step inside the update launch
-        case 13: g_tune.compact = value; return 0;           // compact copy of the vertex block
-        case 15: g_tune.chain32 = value; return 0;           // fp32 Chebyshev chain inside fp64 solves
-        case 16: g_tune.amg = value; return 0;               // multigrid cycle on the vertex block
-        case 17: g_tune.amg32 = value; return 0;             // ... in fp32 storage
-        case 18: set_element_order(value); return 0;    // elements in the caller's order
-        case 31: set_tile_update(value); return 0;      // update launch: 64 rows per wave, a value per lane and pass / a k-wide row per lane
-        case 30: set_flat_direction(value); return 0;   // direction launch: flat arrays, 16 bytes per lane / a k-wide row per lane
-        case 29: set_slab_masked(value); return 0;      // slab slots a row does not have: not fetched / fetched and weighted by zero
-        case 25: g_tune.x_in_direction = value; return 0;    // x += alpha p in the direction / in the update launch
-        case 39: g_tune.x_ev = value; return 0;              // one-shot solves: only the values of x the evaluation points read / the whole x
-        case 41: g_tune.p32 = value; return 0;               // ... on the patch operator: the search direction stored in fp32 / in fp64
-        case 42: g_tune.pairs_fused = value; return 0;       // pair derivatives: one fused element pass / one k_sens_contract launch per pair
-        case 43: g_tune.pair_ev_bytes = value; return 0;     // pair derivatives per group: bytes of element values per launch (slices)
-        case 22: g_tune.defer_q = value; return 0;           // shared rows summed by k_patch_reduce / by the update launch
-        case 24: g_tune.ell = value; return 0;               // fixed-width image of the vertex block
-        case 40: set_patch_rounds(value); return 0;          // patch operator: two elements per lane where the patch fits its tables / one
-        default: break;
-    }
+    {3, &Tune::spmm_mapping},
+    {6, &Tune::square},
+    {9, &Tune::fold_first},
+    {13, &Tune::compact},
+    {15, &Tune::chain32},
+    {16, &Tune::amg},
+    {17, &Tune::amg32},
+    {18, &Tune::element_order},
+    {22, &Tune::defer_q},
+    {24, &Tune::ell},
+    {25, &Tune::x_in_direction},
+    {29, &Tune::slab_masked},
+    {30, &Tune::flat_direction},
+    {31, &Tune::tile_update},
+    {39, &Tune::x_ev},
+    {40, &Tune::patch_rounds, [](int v) { return v == 1 ? 1 : 2; }},      // (patch_rounds tests >= 2: anything but 1 asks for two)
+    {41, &Tune::p32},
+    {42, &Tune::pairs_fused},
+    {43, &Tune::pair_ev_bytes},
 #ifdef REMO_PROBES
     // Keys of rejected experiments and ablations (some give wrong results on purpose): tools/ builds only (make probes)
-    if (key == 7) g_tune.sq_lanes = value;
-    else if (key == 8) set_symbolic_tuning(value);
-    else if (key == 21) set_patch_mode(value);
-    else if (key == 26) set_patch_lean(value);
-    else if (key == 27) set_slab_ahead(value);
-    else if (key == 28) g_tune.dot_bins = value;
-    else if (key == 32) set_patch_spread(value);
-    else if (key == 33) set_patch_trim(value);
-    else if (key == 34) set_patch_persist(value);
-    else if (key == 35) set_patch_wgs_per_xcd(value);
-    else if (key == 36) g_tune.extra_apply = value;
-    else if (key == 0 || key == 1 || key == 2 || key == 4 || key == 5) set_spmm_tuning(key, value);
-    else return -1;     // no such key
-    return 0;
-#else
-    (void)value;
-    return -1;      // not in this build
+    {0, &Tune::spmm_variant},
+    {1, &Tune::spmm_lpr},
+    {2, &Tune::spmm_threads},
+    {4, &Tune::spmm_grid},
+    {5, &Tune::spmm_mode},
+    {7, &Tune::sq_lanes},
+    {8, &Tune::row_pattern},
+    {21, &Tune::patch_mode},
+    {26, &Tune::patch_lean},
+    {27, &Tune::slab_ahead},
+    {28, &Tune::dot_bins},
+    {32, &Tune::patch_spread},
+    {33, &Tune::patch_trim},
+    {34, &Tune::patch_persist, [](int v) { return (v == 1 || v == 2) ? v : 0; }},
+    {35, &Tune::patch_wgs_per_xcd, [](int v) { return v > 0 ? v : 0; }},
+    {36, &Tune::extra_apply},
 #endif
+};
+}  // namespace
+
+int remo_debug_tune(int32_t key, int32_t value) {
+    for (const TuneKey &t : kTuneKeys)
+        if (t.key == key) {
+            g_tune.*t.field = t.stored ? t.stored(value) : value;
+            return 0;
+        }
+    return -1;      // no such key, or not in this build
 }
 
 int remo_debug_sens_timing(remo_ctx_t *ctx, double *out2) {

@@ -1,5 +1,5 @@
-// remo_internal.h — what the translation units behind the C ABI share: the context and batch objects, error plumbing, the
-// process-wide tuning state of remo_debug_tune, and a holder for temporary device memory.  Not installed, not a public header.
+// remo_internal.h — what the translation units behind the C ABI share: the context and batch objects, error plumbing and a holder
+// for temporary device memory (the process-wide tuning state of remo_debug_tune: tune.h, through kernels.h).  Not installed, not a public header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,29 +39,6 @@ extern thread_local std::string g_create_error;
 
 // Symmetric positive definite (leading principal minors > 0) and finite: the upper triangle of one material's tensor (remo_host.cpp)
 bool tensor_ok(int dim, const double *S);
-
-// Process-wide switches of remo_debug_tune, their only writer (remo_debug.hip); a batch reads them when it is planned and run.
-// The keys that live beside the kernels they steer (the set_* of kernels.h / symbolic_gpu.h) are listed in remo_debug_tune.
-struct Tune {
-    int square = 1;          // key 6: 0 = one launch per Chebyshev step, 1 = paired steps in 2D (default), 2 = paired steps always
-    int sq_lanes = 0;        // key 7 (probe builds): lanes per row of the paired kernel (0 = by row length)
-    int compact = 1;         // key 13: 1 = Chebyshev launches read a compact copy of the vertex block above 16 k vertex rows (default), 2 = at any size, 0 = the leading entries of A's rows in place
-    int chain32 = 1;         // key 15: 1 = fp32 Chebyshev chain inside fp64 solves above 32 k vertex rows (default), 2 = at any size, 0 = chain in fp64
-    int amg = 0;             // key 16: 0 = remo_opts_t.coarse decides, 1 = never the multigrid cycle, 2 = always (any dimension)
-    int amg32 = 1;           // key 17: 1 = fp64 solves run the multigrid cycle in fp32 storage (default), 0 = in fp64
-    int defer_q = 1;         // key 22: 1 = the PCG's update launch sums the patch operator's shared rows itself (default), 0 = k_patch_reduce does
-    int ell = 1;             // key 24: 1 = the Chebyshev launches of 3D read the fixed-width image of the vertex block (default), 0 = its CSR form
-    int x_in_direction = 1;  // key 25: 1 = x += alpha p formed by the direction launch of the step (default), 0 = by the update launch
-    int dot_bins = 1;        // key 28 (probe builds): 1 = the patches add their <p, A p> straight into the update launch's rows (default), 0 = a row per patch + k_patch_dot
-    int x_ev = 1;            // key 39: 1 = one-shot fp64 solves carry only the values of x the evaluation points read (default), 0 = the whole x
-    int p32 = 1;             // key 41: 1 = those solves, on the patch operator, store the search direction in fp32 (default; PcgBuffersT::p32), 0 = in fp64
-    int pair_ev_bytes = 0;   // key 43: bytes of element values one per-element launch of remo_job_pair_groups_t writes (0 = kPairEvBytes; always one pair at least)
-    int pairs_fused = 1;     // key 42: 1 = the pairs of remo_job_pairs_t in one fused element pass per chunk pair (default; k_pair_contract), 0 = one launch of k_sens_contract per pair
-#ifdef REMO_PROBES
-    int extra_apply = 0;     // key 36 (probe builds): extra operator applications (apply + shared-row sums, results discarded) per PCG step: what a step with more applications would cost
-#endif
-};
-extern Tune g_tune;
 
 // Temporary device memory of one entry point, freed when the holder leaves scope (normal and error path alike).  hipFree
 // synchronises the device: the holder's scope ends where the call has drained its stream.

@@ -60,8 +60,4 @@ int build_symbolic_gpu(Arena &ar, hipStream_t s, int dim, int64_t nv, int64_t nt
                        const int32_t *d_bconn, const uint8_t *d_bdir, bool condense, int32_t *d_err, DeviceSymbolic &out,
                        std::string &err, int64_t vertex_block_above = -1);   // >= 0: 3D meshes with more elements get the pattern of the P1 block only
 
-// probe hook: 0 = build the CSR pattern by the global sort instead of row by row
-void set_symbolic_tuning(int row_pattern);
-void set_element_order(int on);   // probe hook: 0 = keep the caller's element order
-
 }  // namespace remo

@@ -20,6 +20,7 @@
 #include <rocprim/device/device_select.hpp>
 
 #include "fem_p3.h"
+#include "tune.h"
 
 namespace remo {
 
@@ -347,8 +348,6 @@ __global__ void __launch_bounds__(256) k_low32(int64_t n, int cbits, const uint6
     if (i < n) col[i] = int32_t(uint32_t(keys[i] & ((uint64_t(1) << cbits) - 1)));
 }
 
-int g_row_pattern = 1;   // 0: always build the pattern by sorting (A/B probe, set_symbolic_tuning)
-int g_element_order = 1; // 0: keep the caller's element order (A/B probe, set_element_order)
 inline int grid_for(int64_t n) { return int((n + 255) / 256); }
 inline int bits_for(uint64_t v) {  // bits needed to represent values 0..v
     int b = 1;
@@ -395,7 +394,7 @@ int build_symbolic_gpu(Arena &ar, hipStream_t s, int dim, int64_t nv, int64_t nt
     int32_t *d_cnt = ar.lo<int32_t>(8);           // [0]=nfree
     size_t *d_ucount = ar.lo<size_t>(4);          // unique counts
     HIP_OK(hipMemsetAsync(d_err, 0, sizeof(int32_t), s));
-    if (g_element_order) {
+    if (g_tune.element_order) {
         out.eperm = ar.lo<int32_t>(nt);
         const size_t mark = ar.hi_mark();
         int32_t *conn_tmp = ar.hi<int32_t>(nt * nb), *ids = ar.hi<int32_t>(nt);
@@ -514,7 +513,7 @@ int build_symbolic_gpu(Arena &ar, hipStream_t s, int dim, int64_t nv, int64_t nt
     out.vertex_block_only = dim == 3 && vertex_block_above >= 0 && nt > vertex_block_above && out.nvfree > 0 && nfree < (int64_t(1) << 23);   // (the patch operator addresses rows and slab slots with 24 bits)
     const int64_t prow_n = out.vertex_block_only ? out.nvfree : nfree;
     const int pcand = out.vertex_block_only ? nb : nld;
-    if (g_row_pattern || out.vertex_block_only) {
+    if (g_tune.row_pattern || out.vertex_block_only) {
         int32_t *cnt = ar.hi<int32_t>(prow_n + 1);
         HIP_OK(hipMemsetAsync(cnt + prow_n, 0, sizeof(int32_t), s));
         const int gp = int((prow_n + 3) / 4);
@@ -582,8 +581,5 @@ int build_symbolic_gpu(Arena &ar, hipStream_t s, int dim, int64_t nv, int64_t nt
     out.nadj = 0;  // adjptr[nfree] on the device holds it
     return REMO_OK;
 }
-
-void set_symbolic_tuning(int row_pattern) { g_row_pattern = row_pattern; }
-void set_element_order(int on) { g_element_order = on; }
 
 }  // namespace remo

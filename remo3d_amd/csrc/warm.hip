@@ -61,29 +61,27 @@ __global__ void __launch_bounds__(256) k_warm_add(int64_t n, double *__restrict_
     }
 }
 
-// (not the k switch of pcg_kernels.hip / amg.hip: theirs take every k outside 1 .. 7 as 8, this one throws above REMO_MAX_RHS - the
-// warm object is sized by the caller's k - so the three stay apart)
-#define REMO_WARM_K_SWITCH(k, CALL)                          \
-    switch (k) {                                             \
-        case 1: { constexpr int KK = 1; CALL; } break;       \
-        case 2: { constexpr int KK = 2; CALL; } break;       \
-        case 3: { constexpr int KK = 3; CALL; } break;       \
-        case 4: { constexpr int KK = 4; CALL; } break;       \
-        case 5: { constexpr int KK = 5; CALL; } break;       \
-        case 6: { constexpr int KK = 6; CALL; } break;       \
-        case 7: { constexpr int KK = 7; CALL; } break;       \
-        case 8: { constexpr int KK = 8; CALL; } break;       \
-        default: throw std::runtime_error("warm start: more columns than REMO_MAX_RHS"); \
-    }
+// (the warm object is sized by the caller's k: a k outside 1 .. REMO_MAX_RHS is an error here, not a launch with K = 8)
+static void warm_check_k(int k) {
+    if (k < 1 || k > REMO_MAX_RHS) throw std::runtime_error("warm start: more columns than REMO_MAX_RHS");
+}
 
 void launch_warm_residual(int64_t n, int k, double *f, const double *q, hipStream_t s) {
     if (n <= 0) return;
-    REMO_WARM_K_SWITCH(k, hipLaunchKernelGGL(k_warm_residual<KK>, dim3(stream_grid(n * k / WarmVec<KK>::V)), dim3(256), 0, s, n, f, q));
+    warm_check_k(k);
+    for_k(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        hipLaunchKernelGGL(k_warm_residual<K>, dim3(stream_grid(n * k / WarmVec<K>::V)), dim3(256), 0, s, n, f, q);
+    });
 }
 
 void launch_warm_add(int64_t n, int k, double *x, double *x_prev, hipStream_t s) {
     if (n <= 0) return;
-    REMO_WARM_K_SWITCH(k, hipLaunchKernelGGL(k_warm_add<KK>, dim3(stream_grid(n * k / WarmVec<KK>::V)), dim3(256), 0, s, n, x, x_prev));
+    warm_check_k(k);
+    for_k(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        hipLaunchKernelGGL(k_warm_add<K>, dim3(stream_grid(n * k / WarmVec<K>::V)), dim3(256), 0, s, n, x, x_prev);
+    });
 }
 
 }  // namespace remo
