@@ -30,17 +30,12 @@
 #include <vector>
 
 #include "amg.h"
-#include "kernels.h"
+#include "remo_internal.h"
 #include "wave_util.h"
+#include "kutil.h"
 
 namespace remo {
 namespace {
-
-#define HIP_OK(expr)                                                                                       \
-    do {                                                                                                   \
-        hipError_t e__ = (expr);                                                                           \
-        if (e__ != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(e__)); \
-    } while (0)
 
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -51,14 +46,6 @@ __device__ __forceinline__ bool amg_done(const double *scal, int step) {
     if (!scal) return false;
     const int d = reinterpret_cast<const int *>(scal + kDoneSlot)[0];
     return d != 0 && d <= step;
-}
-
-__device__ __forceinline__ int32_t lower_bound_i32(const int32_t *__restrict__ a, int32_t lo, int32_t hi, int32_t key) {
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (a[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // ---- leading block -> compact CSR ---------------------------------------------------------------------------------------
@@ -617,9 +604,9 @@ int grid_rows(int64_t n, int per_block) { return int((n + per_block - 1) / per_b
 // the temporary storage comes from the scratch end of the arena and is released by the caller's mark
 void scan_counts(Arena &ar, hipStream_t s, int64_t n, const int32_t *cnt, int32_t *out) {
     size_t tb = 0;
-    HIP_OK(rocprim::exclusive_scan(nullptr, tb, cnt, out, int32_t(0), size_t(n + 1), rocprim::plus<int32_t>(), s));
+    HIP_TRY(rocprim::exclusive_scan(nullptr, tb, cnt, out, int32_t(0), size_t(n + 1), rocprim::plus<int32_t>(), s));
     void *tmp = ar.hi<char>(tb + 256);
-    HIP_OK(rocprim::exclusive_scan(tmp, tb, cnt, out, int32_t(0), size_t(n + 1), rocprim::plus<int32_t>(), s));
+    HIP_TRY(rocprim::exclusive_scan(tmp, tb, cnt, out, int32_t(0), size_t(n + 1), rocprim::plus<int32_t>(), s));
 }
 
 // one product C = X Y into arena memory: count, scan, (sync: size), fill.  Returns nnz(C); -1 when a row overflowed.
@@ -667,8 +654,8 @@ int amg_build(Arena &ar, hipStream_t s, int hs, int64_t nv, const int32_t *rowpt
     H = AmgT<double>{};
     int32_t *d_flag = ar.lo<int32_t>(kFlagSlots);
     unsigned long long *d_bound = ar.lo<unsigned long long>(kAmgMaxLevels + 1);
-    HIP_OK(hipMemsetAsync(d_flag, 0, sizeof(int32_t) * kFlagSlots, s));
-    HIP_OK(hipMemsetAsync(d_bound, 0, sizeof(unsigned long long) * (kAmgMaxLevels + 1), s));
+    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int32_t) * kFlagSlots, s));
+    HIP_TRY(hipMemsetAsync(d_bound, 0, sizeof(unsigned long long) * (kAmgMaxLevels + 1), s));
     int32_t h_flags[kFlagSlots] = {};
     int32_t h_nnz_a[kAmgMaxLevels] = {}, h_nnz_p[kAmgMaxLevels] = {};
     const int32_t *d_nnz_p[kAmgMaxLevels] = {};   // where the exact entry counts of the prolongators live on the device
@@ -708,8 +695,8 @@ int amg_build(Arena &ar, hipStream_t s, int hs, int64_t nv, const int32_t *rowpt
                            (int32_t *)nullptr, (double *)nullptr);
         scan_counts(ar, s, nv, cnt, A.rowptr);
         int32_t h = 0;
-        HIP_OK(hipMemcpyAsync(&h, A.rowptr + nv, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpyAsync(&h, A.rowptr + nv, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
         ar.hi_release(mark);
         if (h <= 0 || h == INT_MAX) { why = "empty vertex block"; return -1; }
         A.nnz = h;
@@ -758,11 +745,11 @@ int amg_build(Arena &ar, hipStream_t s, int hs, int64_t nv, const int32_t *rowpt
         // ---- the level's ONE wait: number of aggregates, spectrum bound, everything flagged so far, exact size of this level's matrix
         int32_t h_nc = 0;
         unsigned long long h_bound = 0;
-        HIP_OK(hipMemcpyAsync(&h_nc, id + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipMemcpyAsync(&h_bound, d_bound + L, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipMemcpyAsync(h_flags, d_flag, sizeof(int32_t) * kFlagSlots, hipMemcpyDeviceToHost, s));
-        if (L > 0) HIP_OK(hipMemcpyAsync(&h_nnz_a[L], A.rowptr + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpyAsync(&h_nc, id + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&h_bound, d_bound + L, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h_flags, d_flag, sizeof(int32_t) * kFlagSlots, hipMemcpyDeviceToHost, s));
+        if (L > 0) HIP_TRY(hipMemcpyAsync(&h_nnz_a[L], A.rowptr + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
         const int verdict = check(L);
         if (verdict != 0) return verdict;
         double lmax;
@@ -792,8 +779,8 @@ int amg_build(Arena &ar, hipStream_t s, int hs, int64_t nv, const int32_t *rowpt
         R.rowptr = ar.lo<int32_t>(size_t(nc) + 2); R.col = ar.lo<int32_t>(size_t(nnz_a) + 2); R.val = ar.lo<double>(size_t(nnz_a) + 2);
         {
             int32_t *tcnt = ar.hi<int32_t>(size_t(nc) + 2), *cursor = ar.hi<int32_t>(size_t(nc) + 2);
-            HIP_OK(hipMemsetAsync(tcnt, 0, sizeof(int32_t) * (size_t(nc) + 2), s));
-            HIP_OK(hipMemsetAsync(cursor, 0, sizeof(int32_t) * (size_t(nc) + 2), s));
+            HIP_TRY(hipMemsetAsync(tcnt, 0, sizeof(int32_t) * (size_t(nc) + 2), s));
+            HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(int32_t) * (size_t(nc) + 2), s));
             hipLaunchKernelGGL(k_tr_count, dim3(g), dim3(256), 0, s, n, P.rowptr, P.col, tcnt);
             scan_counts(ar, s, nc, tcnt, R.rowptr);
             hipLaunchKernelGGL(k_tr_fill, dim3(g), dim3(256), 0, s, n, P.rowptr, P.col, P.val, R.rowptr, cursor, R.col, R.val);
@@ -811,10 +798,10 @@ int amg_build(Arena &ar, hipStream_t s, int hs, int64_t nv, const int32_t *rowpt
         ++L;
     }
     // ---- the last wait: flags of the last level's products and of the dense inverse, exact sizes for the fp32 image ----
-    HIP_OK(hipMemcpyAsync(h_flags, d_flag, sizeof(int32_t) * kFlagSlots, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(&h_nnz_a[L], A.rowptr + A.n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    for (int l = 0; l < L; ++l) HIP_OK(hipMemcpyAsync(&h_nnz_p[l], d_nnz_p[l], sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(h_flags, d_flag, sizeof(int32_t) * kFlagSlots, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h_nnz_a[L], A.rowptr + A.n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    for (int l = 0; l < L; ++l) HIP_TRY(hipMemcpyAsync(&h_nnz_p[l], d_nnz_p[l], sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     const int verdict = check(L);
     if (verdict != 0) return verdict;
     H.lev[L].nnz = h_nnz_a[L];

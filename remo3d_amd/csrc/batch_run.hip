@@ -29,7 +29,6 @@ using namespace remo;
 namespace {
 
 std::mutex g_solve_mutex;   // remo_opts_t.serialize_solves
-constexpr int64_t kCompactPerRow = 48;   // capacity of the compact copy per vertex (3D P1 rows hold ~15 entries; a copy that does not fit is not used)
 
 // the handles every stage reads
 struct Run {
@@ -135,8 +134,8 @@ int pair_ev_pairs(int64_t nt, int ncomp, int n_pair) {
     return int(std::max<size_t>(1, std::min<size_t>({budget / per_pair, size_t(std::max(n_pair, 1)), size_t(kPairEvMaxPairs)})));
 }
 
-// Upper bounds of everything the stages take, in the order they take it.  (Generous in places - e.g. the squared, compact and
-// fixed-width images are never all built for one batch - and meant to stay as it is: reserve() only ever grows the arena.)
+// Upper bounds of everything the stages take, in the order they take it (the vertex solver's share: VertexSolverBuilder::arena_bytes).
+// (Generous in places and meant to stay as it is: reserve() only ever grows the arena.)
 size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, int npts) {
     const int dim = b->dim, N = (dim == 2) ? 10 : 20, NT = (dim == 2) ? 9 : 6;
     const int64_t nt = b->nt, nv = b->nv;
@@ -146,7 +145,6 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
     need += size_t(nt) * NT * 8;                                     // d_C
     need += size_t(nnz_max) * 8;                                     // d_val
     need += size_t(ndof_max) * 8 * (1 + 5 * kmax);                   // d_dinv; d_f, x, r, p, q
-    need += size_t(nv + 64) * 8 * 4 * kmax;                          // cz, cres, cd[0], cd[1]
     if (p.want_patch)   // tables + slab (upper bound: a row per element dof, and every patch's block padded to 16 rows)
         need += patch_arena_bytes(nt, ndof_max, p.kmax) + (size_t(nt) * 21 + 64) * kmax * 8;
     need += size_t(kMaxPartialBlocks) * 8 * 8 * 3;                   // part_pq, part_rz (rz0, d_bound and the flags ride on the slack below)
@@ -161,11 +159,7 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
         // instead where the patch operator does not run after all)
         need += size_t(npts + 1) * N * 16;                           // d_ev_at, d_x_ev
     }
-    need += size_t(nv + 64) * 200 * 20 + size_t(nv + 64) * 8;        // squared vertex block (paired Chebyshev steps): sq_col, sq_a, sq_b; sq_rowptr
-    need += size_t(nv + 64) * kCompactPerRow * 16 + size_t(nv + 64) * 8;   // compact vertex block (+ its fp32 values): vb_col, vb_val, c32_val / vb32; vb_rowptr
-    need += size_t(nv + 64) * kEllWidth * 12 + size_t(nv + 64) * 8;  // its fixed-width image: ell_col, ell_val (or c32_ell_val); ell_tail
-    need += size_t(nv + 64) * (4 * 4 * kmax + 8);                    // fp32 Chebyshev chain of the fp64 solve: c32_z, c32_res, c32_d[0], c32_d[1]; c32_dinv
-    if (p.want_amg) need += size_t(nv + 64) * (dim == 2 ? 1536 : 3072) * 2 + (1 << 20);   // multigrid hierarchy of the vertex block + its scratch (amg_setup, amg_to_float)
+    need += VertexSolverBuilder::arena_bytes(dim, nv, kmax, p.want_amg, o.precision == 1);   // the vertex solver's vectors and images, fp32 ones included
     if (b->sens) {   // every forward and adjoint solution stays (sens_take), and the contraction's partial sums
         const size_t ncomp = size_t(b->sigma_comp);
         need += size_t(ndof_max) * 8 * size_t(b->n_rhs + b->sens->n_fun);                                 // keep
@@ -200,10 +194,8 @@ size_t arena_estimate(const remo_batch *b, const remo_opts_t &o, const Plan &p, 
         need += npair * ng * ncomp * 8 + 16 * 256;                                                    // d_dPg (+ the alignment of these takes)
     }
     if (o.precision == 1) {   // fp32 copies of the matrix values and of every PCG vector (mixed_buffers)
-        need += size_t(nv + 64) * 200 * 8;                           // fp32 sq_a, sq_b
         need += size_t(nnz_max) * 4;                                 // v32
         need += size_t(ndof_max) * 4 * (1 + 5 * kmax);               // dinv32; x, r, p, q, f32
-        need += size_t(nv + 64) * 4 * 4 * kmax + (1 << 16);          // cz, cres, cd[0], cd[1]
     }
     return need;
 }
@@ -293,45 +285,10 @@ void assemble_system(const Run &r, System &sys) {
 }
 
 // ---- the solve's buffers and its preconditioner's shape ------------------------------------------------------------------------
-struct ChebDefaults { int degree; double ratio; };
-
-// Degree of the Chebyshev polynomial on the vertex block and the ratio lmax / lmin of its interval, from GPU scans
-// (tools/scan_coarse2d.py, scan_coarse3d.py).
-ChebDefaults cheb_defaults(int dim, int64_t nvfree) {
-    // 3D: the best degree / interval grow with the
-    // vertex count (kappa of the P1 block ~ nv^(2/3), degree ~ sqrt(kappa)): (5, 90) at 12.6 k vertices, (8-10, 150-200) at
-    // 24 k, (12-16, 300-600) at 80 k; fine scan after the first / last step lost their launches (tools/scan_coarse3d_fine.py):
-    // (5, 70-90) at 12.8 k, (8, 120-160) at 27 k (7: +3 %, 9: +4.5 %).  2D (launch-bound steps, paired Chebyshev launches): (16, 600).
-    const double nv_rel = double(nvfree > 0 ? nvfree : 1) / 12600.0;
-    // 2D, round 2 (tools/run_2d_batches.py at the 80 k vertices of config 2 with the 0.35 default mesh scale): (16, 600) 173 ms per four
-    // batches, (24, 1200) 162, (32, 2400) 155, 752 / 561 / 446 steps - the product of degree and steps grows slowly, a launch pair costs
-    // 14 us; (16, 600) was the optimum at 25 k vertices: degree ~ sqrt(vertices), ratio ~ vertices, even degrees (paired launches).
-    // The paired (root-product) form must stay in fp64: in fp32 storage it needs MORE steps at degree 16 and breaks down above.
-    const double nv2 = double(nvfree > 0 ? nvfree : 1) / 25000.0;
-    const int deg2 = 2 * int(std::min(16.0, std::max(8.0, std::floor(8.0 * std::sqrt(nv2) + 0.5))));
-    // round 3, size L with the patch operator (83 k vertices, tools/scan_coarse3d_fine.py L, profiles/r03_scan_coarse_L.log): steps per
-    // four batches 675 / 637 / 638 / 630 / 601 at degrees 11 / 12 / 13 / 14 / 16 - an odd degree above 7 buys nothing over the even one
-    // below it (M: 8 best, 7 and 9 worse) - solve 300 / 289 / 295 / 297 / 294 ms: even degrees from 8 up
-    int deg3 = int(std::min(16.0, std::max(5.0, std::floor(5.0 * std::sqrt(nv_rel) + 0.9))));
-    if (deg3 > 8) deg3 &= ~1;
-    if (dim == 3) return {deg3, std::min(1200.0, std::max(60.0, 90.0 * std::pow(nv_rel, 2.0 / 3.0)))};
-    return {deg2, std::min(2400.0, std::max(600.0, 600.0 * nv2 * 1.25))};
-}
-
-struct Solve {
-    PcgBuffers buf{};
-    bool two_level = false;                  // vertex-block solver + Jacobi (remo_opts_t.preconditioner), else Jacobi alone
-    size_t nc = 0;                           // length of the vertex block's vectors
-    double ratio_default = 0.0;              // cheb_defaults of this batch
-    unsigned long long *d_bound = nullptr;   // spectrum bound of the vertex block (vertex_block_enqueue; taken here: its place in the arena)
-};
-
-void take_pcg_buffers(const Run &r, const Plan &plan, const System &sys, Solve &sv) {
+void take_pcg_buffers(const Run &r, const Plan &plan, const System &sys, PcgBuffers &buf) {
     remo_ctx *ctx = r.ctx;
-    const DeviceSymbolic &sy = r.b->sym;
     const int64_t n = sys.n;
     const int kmax = plan.kmax;
-    PcgBuffers &buf = sv.buf;
     buf.x = plan.x_ev_only ? nullptr : ctx->take<double>(n * kmax);
     buf.r = ctx->take<double>(n * kmax);
     if (plan.p32) buf.p32 = ctx->take<float>(n * kmax + 4);      // (set_launch_shape takes the fp64 vector instead where the patch operator does not run)
@@ -341,16 +298,6 @@ void take_pcg_buffers(const Run &r, const Plan &plan, const System &sys, Solve &
     buf.part_pq = ctx->take<double>(kMaxPartialBlocks * 8);
     buf.part_rz = ctx->take<double>(kMaxPartialBlocks * 8 * 2);
     buf.rz0 = ctx->take<double>(kScalarSlots);
-    sv.two_level = (r.o.preconditioner != 0) && sy.nvfree > 0;
-    buf.nv_coarse = sv.two_level ? sy.nvfree : 0;
-    const ChebDefaults cd = cheb_defaults(r.dim, sy.nvfree);
-    sv.ratio_default = cd.ratio;
-    buf.cheb_degree = sv.two_level ? (r.o.coarse_degree > 0 ? r.o.coarse_degree : cd.degree) : 0;
-    buf.cheb_lmax = buf.cheb_lmin = 0.0;
-    sv.nc = size_t(buf.nv_coarse) * kmax + 2;
-    buf.cz = ctx->take<double>(sv.nc); buf.cres = ctx->take<double>(sv.nc);
-    buf.cd[0] = ctx->take<double>(sv.nc); buf.cd[1] = ctx->take<double>(sv.nc);
-    sv.d_bound = ctx->take<unsigned long long>(2);
 }
 
 // progress records of the PCG and the event pool of remo_opts_t.time_kernels (host objects of the context, grown on demand)
@@ -597,162 +544,48 @@ void field_fetch(const Run &r, Field &f) {
     r.ctx->field_ms[1] = f.ms_eval;
 }
 
-// ---- images of the vertex block for the preconditioner, and the patch tables ---------------------------------------------------
-// Everything that is enqueued before the batch's one synchronisation, with the small results it reads back.  The read-backs land
-// in this struct: it must stay where it is between vertex_block_enqueue and the synchronisation.
-struct VertexBlock {
-    bool want_square = false, want_compact = false;
-    int32_t h_err = 0;                  // ctx->d_err: 1 = mesh / material, 2 = point
-    unsigned long long h_bound = 0;     // bits of the spectrum bound
-    int32_t h_sq[2] = {1, 0};           // squared block: overflow flag, entries
-    int32_t h_vb[2] = {1, 0};           // compact block: overflow flag, entries
-    int32_t h_patch[3] = {1, 0, 0};     // patch tables: overflow flag, largest patch, slab slots
-    int32_t *sq_rowptr = nullptr, *sq_col = nullptr;
-    double *sq_a = nullptr, *sq_b = nullptr;
-    int32_t *vb_rowptr = nullptr, *vb_col = nullptr;
-    double *vb_val = nullptr;
+// ---- the patch tables, enqueued right after the vertex block's images.  The read-back lands in this struct: it must stay where it is until the synchronisation.
+struct PatchBuild {
     PatchTables ptab{};
+    int32_t h_patch[3] = {1, 0, 0};     // overflow flag, largest patch, slab slots
     int32_t *d_pflag = nullptr;         // device side of h_patch
-    size_t patch_mark = 0;              // arena mark in front of the patch tables (patch_tables_one_round)
-    bool amg32_ready = false;
-    VertexBlock() = default;
-    VertexBlock(const VertexBlock &) = delete;
+    size_t patch_mark = 0;              // arena mark in front of the tables (patch_tables_one_round)
+    PatchBuild() = default; PatchBuild(const PatchBuild &) = delete;
 };
 
-void vertex_block_enqueue(const Run &r, const Plan &plan, const System &sys, const Solve &sv, VertexBlock &vb) {
-    remo_ctx *ctx = r.ctx;
-    hipStream_t s = r.s;
-    const DeviceSymbolic &sy = r.b->sym;
-    const PcgBuffers &buf = sv.buf;
-    const CsrView A = sys.view(sy);
-    // paired steps pay off where B stays small: 2D (~19 entries per row: 81 vs 93 us per PCG step); in 3D B has ~65
-    // entries per row and three launches on it cost more than six on A_vv (153 vs 149 us) - forced by tune value 2
-    vb.want_square = sv.two_level && !plan.want_amg && (buf.cheb_degree % 2 == 0) && ((g_tune.square == 1 && r.dim == 2) || g_tune.square == 2);
-    // compact copy of the vertex block for the Chebyshev launches (remo_debug_tune key 13: 0 = read A in place)
-    // measured in the bench (--tune 13=0 against 13=1, one box): 538.9 -> 516.1 ms solve per step at 83 k vertices; at 12.8 k the
-    // launches are latency, not bytes (714 -> 710 ms) and building the copy costs what it saves: larger blocks only (2 forces it)
-    vb.want_compact = !sys.lite && sv.two_level && !vb.want_square && (g_tune.compact == 2 || (g_tune.compact == 1 && buf.nv_coarse > 16384));
-    if (sv.two_level) {  // spectrum bound of the Jacobi-scaled vertex block for the Chebyshev interval
-        HIP_TRY(hipMemsetAsync(sv.d_bound, 0, sizeof(unsigned long long), s));
-        launch_vblock_bound(buf.nv_coarse, A, sys.d_dinv, sv.d_bound, s);
-        HIP_TRY(hipMemcpyAsync(&vb.h_bound, sv.d_bound, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    }
-    if (vb.want_square) {   // B = A_vv D^-1 A_vv for the paired Chebyshev steps (pcg_kernels.hip k_cheb_pair)
-        const int64_t nvc = buf.nv_coarse, cap = nvc * 200;
-        vb.sq_rowptr = ctx->take<int32_t>(size_t(nvc) + 2);
-        vb.sq_col = ctx->take<int32_t>(size_t(cap));
-        vb.sq_a = ctx->take<double>(size_t(cap)); vb.sq_b = ctx->take<double>(size_t(cap));
-        int32_t *d_sqflag = ctx->take<int32_t>(1);
-        HIP_TRY(hipMemsetAsync(d_sqflag, 0, sizeof(int32_t), s));
-        launch_vblock_square(nvc, A, sys.d_dinv, vb.sq_rowptr, vb.sq_col, vb.sq_a, vb.sq_b, cap, d_sqflag, s);
-        HIP_TRY(hipMemcpyAsync(&vb.h_sq[0], d_sqflag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&vb.h_sq[1], vb.sq_rowptr + nvc, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    }
-    if (vb.want_compact) {
-        const int64_t nvc = buf.nv_coarse, cap = (nvc + 64) * kCompactPerRow;
-        vb.vb_rowptr = ctx->take<int32_t>(size_t(nvc) + 2);
-        vb.vb_col = ctx->take<int32_t>(size_t(cap));
-        vb.vb_val = ctx->take<double>(size_t(cap));
-        int32_t *d_vbflag = ctx->take<int32_t>(1);
-        HIP_TRY(hipMemsetAsync(d_vbflag, 0, sizeof(int32_t), s));
-        launch_vblock_compact(nvc, A, vb.vb_rowptr, vb.vb_col, vb.vb_val, cap, d_vbflag, s);
-        HIP_TRY(hipMemcpyAsync(&vb.h_vb[0], d_vbflag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&vb.h_vb[1], vb.vb_rowptr + nvc, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    }
-    // patch operator (patch.hip): its tables are built beside the assembly; their overflow flag and largest patch come
-    // back with the other small read-backs
-    // Two elements per lane (remo_debug_tune key 40) in fp64 storage; the mixed mode's fp32 kernel takes one, and it runs on these tables.
-    if (plan.want_patch) {
-        vb.d_pflag = ctx->take<int32_t>(4);
-        vb.patch_mark = ctx->ar.lo_mark();      // nothing else is taken before the synchronisation: patch_tables_one_round may build them again here
-        build_patch_tables(ctx->ar, s, sy, sys.d_C, plan.kmax, r.o.precision == 0 ? g_tune.patch_rounds : 1, vb.ptab, vb.d_pflag);
-        HIP_TRY(hipMemcpyAsync(vb.h_patch, vb.d_pflag, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipMemcpyAsync(&vb.h_err, ctx->d_err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+// patch operator (patch.hip): its tables are built beside the assembly; their overflow flag and largest patch come
+// back with the other small read-backs
+// Two elements per lane (remo_debug_tune key 40) in fp64 storage; the mixed mode's fp32 kernel takes one, and it runs on these tables.
+void patch_tables_enqueue(const Run &r, const Plan &plan, const System &sys, PatchBuild &pb) {
+    if (!plan.want_patch) return;
+    pb.d_pflag = r.ctx->take<int32_t>(4);
+    pb.patch_mark = r.ctx->ar.lo_mark();      // nothing else is taken before the synchronisation: patch_tables_one_round may build them again here
+    build_patch_tables(r.ctx->ar, r.s, r.b->sym, sys.d_C, plan.kmax, r.o.precision == 0 ? g_tune.patch_rounds : 1, pb.ptab, pb.d_pflag);
+    HIP_TRY(hipMemcpyAsync(pb.h_patch, pb.d_pflag, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, r.s));
 }
 
 // Right after the synchronisation, before anything else is taken from the arena: a batch whose largest patch of two rounds holds
-// more rows than the tables or the kernel's LDS do (vb.h_patch: the flag and the row count the build left on the device) gets
+// more rows than the tables or the kernel's LDS do (pb.h_patch: the flag and the row count the build left on the device) gets
 // tables of one round in the same place - the patch operator stays, and the batch waits once more.
-void patch_tables_one_round(const Run &r, const Plan &plan, const System &sys, VertexBlock &vb) {
-    if (!plan.want_patch || vb.ptab.rounds == 1) return;
-    if (vb.h_patch[0] == 0 && patch_lds_bytes(vb.h_patch[1], plan.kmax) <= kPatchLdsLimit) return;
-    remo_ctx *ctx = r.ctx;
-    ctx->ar.lo_release(vb.patch_mark);
-    build_patch_tables(ctx->ar, r.s, r.b->sym, sys.d_C, plan.kmax, 1, vb.ptab, vb.d_pflag);
-    HIP_TRY(hipMemcpyAsync(vb.h_patch, vb.d_pflag, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, r.s));
+void patch_tables_one_round(const Run &r, const Plan &plan, const System &sys, PatchBuild &pb) {
+    if (!plan.want_patch || pb.ptab.rounds == 1) return;
+    if (pb.h_patch[0] == 0 && patch_lds_bytes(pb.h_patch[1], plan.kmax) <= kPatchLdsLimit) return;
+    r.ctx->ar.lo_release(pb.patch_mark);
+    build_patch_tables(r.ctx->ar, r.s, r.b->sym, sys.d_C, plan.kmax, 1, pb.ptab, pb.d_pflag);
+    HIP_TRY(hipMemcpyAsync(pb.h_patch, pb.d_pflag, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, r.s));
     HIP_TRY(hipStreamSynchronize(r.s));
-}
-
-// After the synchronisation: which images the solve uses (buf), and the ones that are built from the accepted ones.
-int vertex_block_accept(const Run &r, const Plan &plan, const System &sys, Solve &sv, VertexBlock &vb) {
-    remo_ctx *ctx = r.ctx;
-    remo_batch *b = r.b;
-    hipStream_t s = r.s;
-    const remo_opts_t &o = r.o;
-    const DeviceSymbolic &sy = b->sym;
-    PcgBuffers &buf = sv.buf;
-    const int kmax = plan.kmax;
-    if (vb.want_compact && vb.h_vb[0] == 0 && vb.h_vb[1] > 0) { buf.vb_rowptr = vb.vb_rowptr; buf.vb_col = vb.vb_col; buf.vb_val = vb.vb_val; }
-    if (sys.lite && sv.two_level) { buf.vb_rowptr = sy.rowptr; buf.vb_col = sy.col; buf.vb_val = sys.d_val; vb.h_vb[0] = 0; vb.h_vb[1] = int32_t(sy.nnz); }   // the assembled block IS the compact vertex block
-    // fp32 Chebyshev chain inside the fp64 solve (remo_debug_tune key 15: 0 = off): where the chain's launches are HBM streams
-    // (no folded first step: more than 32 k vertex rows) and the compact block exists
-    if (g_tune.chain32 && o.precision == 0 && buf.vb_rowptr && (buf.nv_coarse > 32768 || g_tune.chain32 == 2)) {   // 2: forced (tests)
-        float *v32c = ctx->take<float>(size_t(vb.h_vb[1]) + 4), *d32c = ctx->take<float>(size_t(buf.nv_coarse) + 4);
-        launch_to_float(vb.h_vb[1], buf.vb_val, v32c, s);
-        launch_to_float(buf.nv_coarse, sys.d_dinv, d32c, s);
-        buf.c32_val = v32c; buf.c32_dinv = d32c;
-        buf.c32_z = ctx->take<float>(sv.nc); buf.c32_res = ctx->take<float>(sv.nc);
-        buf.c32_d[0] = ctx->take<float>(sv.nc); buf.c32_d[1] = ctx->take<float>(sv.nc);
-    }
-    // fixed-width image of the vertex block for the polynomial's launches (kernels.hip k_vblock_ell; remo_debug_tune key 24: 0 = off)
-    if (g_tune.ell && sv.two_level && !plan.want_amg && !vb.want_square && r.dim == 3) {
-        const int64_t nvc = buf.nv_coarse;
-        const bool from_block = buf.vb_rowptr != nullptr;
-        int32_t *ell_col = ctx->take<int32_t>(size_t(nvc) * kEllWidth + 8);
-        int32_t *ell_tail = ctx->take<int32_t>(size_t(nvc) * 2 + 8);
-        double *e64 = (o.precision == 0 && !buf.c32_val) ? ctx->take<double>(size_t(nvc) * kEllWidth + 8) : nullptr;
-        float *e32 = (o.precision != 0 || buf.c32_val) ? ctx->take<float>(size_t(nvc) * kEllWidth + 8) : nullptr;
-        launch_vblock_ell(nvc, from_block ? buf.vb_rowptr : sy.rowptr, from_block ? buf.vb_col : sy.col, from_block ? buf.vb_val : sys.d_val,
-                          ell_col, ell_tail, e64, e32, s);
-        buf.ell_col = ell_col; buf.ell_tail = ell_tail; buf.ell_val = e64; buf.c32_ell_val = e32;
-    }
-    if (sv.two_level && plan.want_amg) {   // multigrid cycle on the vertex block instead of the polynomial (amg.hip)
-        std::string why;
-        if (amg_setup(ctx->ar, s, r.dim, buf.nv_coarse, sy.rowptr, sy.col, sys.d_val, kmax, b->amg64, why)) buf.amg = &b->amg64;
-        else if (o.coarse == 2 || g_tune.amg == 2) return fail(ctx, REMO_ERR_NUMERIC, "multigrid hierarchy of the vertex block: " + why);
-    }
-    if (buf.amg && (o.precision == 1 || g_tune.amg32)) {   // fp32 image of the hierarchy: the mixed mode's inner solver, or the cycle of an fp64 solve
-        amg_to_float(ctx->ar, s, b->amg64, kmax, b->amg32);
-        vb.amg32_ready = true;
-        if (o.precision == 0) buf.amg32 = &b->amg32;
-    }
-    r.st->coarse_used = !sv.two_level ? 0 : (buf.amg ? 2 : 1);
-    if (sv.two_level) {
-        double lmax;
-        std::memcpy(&lmax, &vb.h_bound, sizeof lmax);
-        if (!(lmax > 0.0) || !std::isfinite(lmax)) return fail(ctx, REMO_ERR_NUMERIC, "vertex block has no positive spectrum bound");
-        buf.cheb_lmax = lmax;
-        buf.cheb_lmin = lmax / (o.coarse_ratio > 0 ? double(o.coarse_ratio) : sv.ratio_default);
-    }
-    if (vb.want_square && vb.h_sq[0] == 0) {   // otherwise (a vertex of very high valence) the one-step launches stay
-        buf.sq_rowptr = vb.sq_rowptr; buf.sq_col = vb.sq_col; buf.sq_a = vb.sq_a; buf.sq_b = vb.sq_b;
-        const double avg = double(vb.h_sq[1]) / double(buf.nv_coarse > 0 ? buf.nv_coarse : 1);
-        buf.sq_lanes = g_tune.sq_lanes ? g_tune.sq_lanes : (avg > 40.0 ? 32 : (avg > 24.0 ? 16 : 8));   // 2D rows of B hold ~19 entries: 8 lanes (two passes in flight) 145 vs 150 ms with 16
-    }
-    return REMO_OK;
 }
 
 // ---- the operator: patch operator or CSR product --------------------------------------------------------------------------------
 // Leaves the system on the batch (b->A and the pointers the inspection entries read).
-int choose_operator(const Run &r, const Plan &plan, const System &sys, const Solve &sv, VertexBlock &vb, bool &patch_op) {
+int choose_operator(const Run &r, const Plan &plan, const System &sys, const PcgBuffers &buf, PatchBuild &pb, bool &patch_op) {
     remo_ctx *ctx = r.ctx;
     remo_batch *b = r.b;
     const DeviceSymbolic &sy = b->sym;
     const int64_t n = sys.n;
     const int kmax = plan.kmax;
-    PatchTables &ptab = vb.ptab;
-    const int32_t *h_patch = vb.h_patch;
+    PatchTables &ptab = pb.ptab;
+    const int32_t *h_patch = pb.h_patch;
     b->A = sys.view(sy);
     b->A.pair_begin = sys.pair_begin; b->A.pair_end = sys.pair_end;
     b->A.vertex_block_only = sys.lite;
@@ -777,7 +610,7 @@ int choose_operator(const Run &r, const Plan &plan, const System &sys, const Sol
     }
     b->d_val = sys.d_val;
     b->d_dinv = sys.d_dinv;
-    b->d_x = sv.buf.x;
+    b->d_x = buf.x;
     b->d_f = sys.d_f;
     b->d_C = sys.d_C;
     b->k_last = 0;
@@ -791,7 +624,7 @@ void set_launch_shape(const Run &r, const Plan &plan, const System &sys, bool pa
     const int lpr = choose_lanes_per_row(sys.n, b->sym.nnz);
     buf.nb_spmv = spmv_grid(sys.n, lpr);
     buf.nb_vec = vec_grid(sys.n);
-    buf.defer_q = patch_op && g_tune.defer_q && !pcg_update_folds(buf);     // the update launch sums the shared rows of q = A p itself
+    buf.defer_q = patch_op && g_tune.defer_q && !vertex_first_folds(buf.vs);     // the update launch sums the shared rows of q = A p itself
     buf.x_in_direction = g_tune.x_in_direction != 0;
     buf.pq_bins = buf.defer_q && g_tune.dot_bins != 0;
     if (patch_op) b->patch64.dot_bins = buf.pq_bins;
@@ -806,13 +639,12 @@ void set_launch_shape(const Run &r, const Plan &plan, const System &sys, bool pa
 
 // ---- mixed precision: the same solve in fp32 storage ----------------------------------------------------------------------------
 // Derived from the fp64 description: what does not depend on the storage type is copied, the fp32 vectors are taken from the arena
-// and the value arrays converted.
-MixedBuffers mixed_buffers(const Run &r, const Plan &plan, const System &sys, const Solve &sv, const VertexBlock &vb, bool patch_op) {
+// and the value arrays converted (the vertex solver's: VertexSolverBuilder::to_float).
+MixedBuffers mixed_buffers(const Run &r, const Plan &plan, const System &sys, const PcgBuffers &buf, const VertexSolverBuilder &vsb, bool patch_op) {
     remo_ctx *ctx = r.ctx;
     remo_batch *b = r.b;
     hipStream_t s = r.s;
     const DeviceSymbolic &sy = b->sym;
-    const PcgBuffers &buf = sv.buf;
     const size_t nk = size_t(sys.n) * plan.kmax;
     MixedBuffers mx;
     float *v32 = ctx->take<float>(size_t(sy.nnz) + 2);   // same slack as d_val
@@ -827,27 +659,10 @@ MixedBuffers mixed_buffers(const Run &r, const Plan &plan, const System &sys, co
     mx.f32 = ctx->take<float>(nk);
     f.dinv = dinv32;
     f.part_pq = buf.part_pq; f.part_rz = buf.part_rz; f.rz0 = buf.rz0;
-    f.nv_coarse = buf.nv_coarse; f.cheb_degree = buf.cheb_degree; f.cheb_lmax = buf.cheb_lmax; f.cheb_lmin = buf.cheb_lmin;
-    f.cz = ctx->take<float>(sv.nc); f.cres = ctx->take<float>(sv.nc);
-    f.cd[0] = ctx->take<float>(sv.nc); f.cd[1] = ctx->take<float>(sv.nc);
     f.progress = buf.progress; f.progress_len = buf.progress_len;
     f.nb_spmv = buf.nb_spmv; f.nb_vec = buf.nb_vec;
-    if (buf.amg && vb.amg32_ready) f.amg = &b->amg32;
-    if (buf.vb_rowptr) {
-        float *vb32 = ctx->take<float>(size_t(vb.h_vb[1]) + 1);
-        launch_to_float(vb.h_vb[1], buf.vb_val, vb32, s);
-        f.vb_rowptr = buf.vb_rowptr; f.vb_col = buf.vb_col; f.vb_val = vb32;
-    }
-    f.ell_col = buf.ell_col; f.ell_tail = buf.ell_tail; f.ell_val = buf.c32_ell_val;
-    if (buf.sq_rowptr) {
-        float *a32 = ctx->take<float>(size_t(vb.h_sq[1]) + 1), *b32 = ctx->take<float>(size_t(vb.h_sq[1]) + 1);
-        launch_to_float(vb.h_sq[1], buf.sq_a, a32, s);
-        launch_to_float(vb.h_sq[1], buf.sq_b, b32, s);
-        f.sq_rowptr = buf.sq_rowptr; f.sq_col = buf.sq_col; f.sq_a = a32; f.sq_b = b32; f.sq_lanes = buf.sq_lanes;
-    }
-    // The forms of the update / direction launches are the fp64 solve's (set_launch_shape).  defer_q hangs on pcg_update_folds, which
-    // reads amg, cheb_degree, nv_coarse and sq_rowptr: all copied above, and f.amg is set exactly when buf.amg is (a mixed run always
-    // has the hierarchy's fp32 image) - the answer cannot differ between the two buffers, so it is not asked twice.
+    f.vs = vsb.to_float(ctx->ar, s, buf.vs, v32, b->amg32);
+    // the forms of the update / direction launches are the fp64 solve's (set_launch_shape; to_float says why they cannot differ)
     f.defer_q = buf.defer_q; f.x_in_direction = buf.x_in_direction; f.pq_bins = buf.pq_bins;
     if (patch_op) {
         b->patch32 = patch_view32(b->patch64);
@@ -865,7 +680,7 @@ struct RunTotals {
 };
 
 // x_prev != nullptr: the chunk's columns of the previous call (remo_warm_t) - the solve starts from them (run_pcg_warm)
-int solve_chunk(const Run &r, const Plan &plan, const System &sys, const DevicePoints &dp, Solve &sv, MixedBuffers *mx, int k, int q0, int nq,
+int solve_chunk(const Run &r, const Plan &plan, const System &sys, const DevicePoints &dp, PcgBuffers &buf, MixedBuffers *mx, int k, int q0, int nq,
                 std::vector<double> &h_out, RunTotals &tot, double *x_prev = nullptr, const Secondary *sec = nullptr, int chunk = 0) {
     remo_ctx *ctx = r.ctx;
     remo_batch *b = r.b;
@@ -873,7 +688,6 @@ int solve_chunk(const Run &r, const Plan &plan, const System &sys, const DeviceP
     hipStream_t s = r.s;
     const DeviceSymbolic &sy = b->sym;
     const int dim = r.dim, N = r.N;
-    PcgBuffers &buf = sv.buf;
     HIP_TRY(hipEventRecord(ctx->ev[4], s));
     HIP_TRY(hipMemsetAsync(sys.d_f, 0, sizeof(double) * sys.n * k, s));
     if (sec) {   // secondary formulation: no point values in f, no bubble loads of single sources
@@ -1366,12 +1180,15 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         // ---- numbering, then every buffer of the solve (arena order), then the device work up to the one sync --------
         if (int rc = number_dofs(r, plan, t_start)) return rc;
         System sys = take_system(r, plan);
-        Solve sv;
-        take_pcg_buffers(r, plan, sys, sv);
+        PcgBuffers buf{};
+        take_pcg_buffers(r, plan, sys, buf);
+        const VertexSolverInput vin{r.dim, plan.kmax, o, b->sym.nvfree, sys.lite, plan.want_amg};
+        VertexSolverBuilder vsb;
+        vsb.take(ctx->ar, vin, buf.vs);   // degree, the chain's vectors, the bound's slot
         const DevicePoints dp = take_points(r, plan, points);
         take_secondary(r, plan, sec);
         field_take(r, fld);
-        prepare_progress(r, sv.buf);
+        prepare_progress(r, buf);
         HIP_TRY(hipEventRecord(ctx->ev[0], s));
         upload_points(r, points, dp);
         upload_secondary(r, sec);
@@ -1382,18 +1199,21 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         check_secondary_sources(r, sys, sec);
         field_locate_points(r, fld);
         HIP_TRY(hipEventRecord(ctx->ev[3], s));
-        VertexBlock vb;
-        vertex_block_enqueue(r, plan, sys, sv, vb);
+        vsb.enqueue(ctx->ar, s, vin, sys.view(b->sym), sys.d_dinv, buf.vs);
+        PatchBuild pb;
+        patch_tables_enqueue(r, plan, sys, pb);
+        int32_t h_err = 0;                  // ctx->d_err: 1 = mesh / material, 2 = point, 4 = secondary source
+        HIP_TRY(hipMemcpyAsync(&h_err, ctx->d_err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        patch_tables_one_round(r, plan, sys, vb);
+        patch_tables_one_round(r, plan, sys, pb);
 
         // ---- what came back: preconditioner images, mesh / point errors, operator -------------------------------------
-        if (int rc = vertex_block_accept(r, plan, sys, sv, vb)) return rc;
-        if (vb.h_err & 1) return fail(ctx, REMO_ERR_MESH, "degenerate element or material index out of range");
-        if (vb.h_err & 2) return fail(ctx, REMO_ERR_POINT, "source or evaluation point outside the mesh");
-        if (vb.h_err & 4) return fail(ctx, REMO_ERR_POINT, "secondary formulation: a source lies in or on an element whose conductivity differs from sigma0 (the integrand is singular there)");
+        if (int rc = vsb.accept(ctx->ar, s, vin, sys.view(b->sym), sys.d_dinv, b->amg64, b->amg32, buf.vs, &st->coarse_used, ctx->err)) return rc;
+        if (h_err & 1) return fail(ctx, REMO_ERR_MESH, "degenerate element or material index out of range");
+        if (h_err & 2) return fail(ctx, REMO_ERR_POINT, "source or evaluation point outside the mesh");
+        if (h_err & 4) return fail(ctx, REMO_ERR_POINT, "secondary formulation: a source lies in or on an element whose conductivity differs from sigma0 (the integrand is singular there)");
         bool patch_op = false;
-        if (int rc = choose_operator(r, plan, sys, sv, vb, patch_op)) return rc;
+        if (int rc = choose_operator(r, plan, sys, buf, pb, patch_op)) return rc;
         const Sens sens = b->sens ? sens_take(r, sys) : Sens{};
         const bool want_err = b->sens && b->sens->err;
         const ErrEst est = want_err ? err_take(r) : ErrEst{};
@@ -1415,21 +1235,21 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
         // serialize_solves: batches of other contexts may number and assemble beside this PCG, but not run theirs
         std::unique_lock<std::mutex> solve_turn(g_solve_mutex, std::defer_lock);
         if (o.serialize_solves) solve_turn.lock();
-        set_launch_shape(r, plan, sys, patch_op, sv.buf);
+        set_launch_shape(r, plan, sys, patch_op, buf);
         const bool mixed = (o.precision == 1);
         MixedBuffers mx;
-        if (mixed) mx = mixed_buffers(r, plan, sys, sv, vb, patch_op);   // fp32 images of the system for the inner solver
+        if (mixed) mx = mixed_buffers(r, plan, sys, buf, vsb, patch_op);   // fp32 images of the system for the inner solver
         std::vector<double> h_out(npts, std::nan(""));
         RunTotals tot;
         int chunk = 0;
         for (int c0 = 0; c0 < b->n_rhs; c0 += REMO_MAX_RHS, ++chunk) {
             const int k = std::min(b->n_rhs - c0, REMO_MAX_RHS);
             const int q0 = points.chunk_begin[chunk], nq = points.chunk_begin[chunk + 1] - q0;
-            if (b->sens) b->d_x = sv.buf.x = sens.block(sys.n, b->n_rhs, false, chunk);   // the solution is formed where it stays
-            if (int rc = solve_chunk(r, plan, sys, dp, sv, mixed ? &mx : nullptr, k, q0, nq, h_out, tot,
+            if (b->sens) b->d_x = buf.x = sens.block(sys.n, b->n_rhs, false, chunk);   // the solution is formed where it stays
+            if (int rc = solve_chunk(r, plan, sys, dp, buf, mixed ? &mx : nullptr, k, q0, nq, h_out, tot,
                                      warm_hit ? prev.block(sys.n, b->n_rhs, false, chunk) : nullptr, sec.on ? &sec : nullptr, chunk)) return rc;
-            if (b->field) field_eval_chunk(r, sys, dp, sv.buf.x, fld, c0, k, q0, nq);   // while the chunk's solutions are there
-            if (want_err) err_facets_chunk(r, sys, dp, sv.buf.x, est, c0, k, q0, nq);
+            if (b->field) field_eval_chunk(r, sys, dp, buf.x, fld, c0, k, q0, nq);   // while the chunk's solutions are there
+            if (want_err) err_facets_chunk(r, sys, dp, buf.x, est, c0, k, q0, nq);
         }
         if (b->field) field_fetch(r, fld);
         for (int q = 0; q < npts; ++q)
@@ -1438,9 +1258,9 @@ extern "C" int remo_batch_run(remo_ctx_t *ctx, remo_batch_t *b, const remo_opts_
             for (int a0 = 0, ca = 0; a0 < rq->n_fun; a0 += REMO_MAX_RHS, ++ca, ++chunk) {
                 const int k = std::min(rq->n_fun - a0, REMO_MAX_RHS);
                 const int q0 = points.chunk_begin[chunk], nq = points.chunk_begin[chunk + 1] - q0;
-                b->d_x = sv.buf.x = sens.block(sys.n, b->n_rhs, true, ca);
-                if (int rc = solve_chunk(r, plan, sys, dp, sv, nullptr, k, q0, nq, h_out, tot, warm_hit ? prev.block(sys.n, b->n_rhs, true, ca) : nullptr)) return rc;
-                if (want_err) err_facets_chunk(r, sys, dp, sv.buf.x, est, b->n_rhs + a0, k, q0, nq);
+                b->d_x = buf.x = sens.block(sys.n, b->n_rhs, true, ca);
+                if (int rc = solve_chunk(r, plan, sys, dp, buf, nullptr, k, q0, nq, h_out, tot, warm_hit ? prev.block(sys.n, b->n_rhs, true, ca) : nullptr)) return rc;
+                if (want_err) err_facets_chunk(r, sys, dp, buf.x, est, b->n_rhs + a0, k, q0, nq);
             }
             if (warm) {   // a warm chunk left its sum in the object already; a cold run's solutions are copied there whole
                 if (!warm_hit) HIP_TRY(hipMemcpyAsync(warm->d, sens.keep, sizeof(double) * (warm_doubles(sys.n, b->n_rhs, rq->n_fun) - 64), hipMemcpyDeviceToDevice, s));

@@ -1,4 +1,4 @@
-// kernels.h — launchers of the gfx950 kernels (kernels.hip; the PCG step's: pcg_kernels.hip) and the dispatch on the column count
+// kernels.h — launchers of the gfx950 kernels (kernels.hip; the PCG step's: pcg_kernels.hip; the vertex-block solver's: vertex_solver.h) and the dispatch on the column count
 // they share (for_k).  All launches are asynchronous on the given stream; no launcher allocates or synchronises.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -8,6 +8,7 @@
 
 #include "elem_access.h"
 #include "tune.h"
+#include "vertex_solver.h"
 
 namespace remo {
 
@@ -34,6 +35,8 @@ template <class F> void for_k(int k, F &&fn) {
 template <class F> void for_bool(bool b, F &&fn) {
     if (b) fn(std::true_type{}); else fn(std::false_type{});
 }
+// the launches of the PCG step and of the vertex solver: `grid` workgroups of 256 threads, no dynamic LDS
+template <class Kernel, class... Args> void launch256(Kernel kernel, int grid, hipStream_t s, Args... args) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, args...); }
 
 // per-iteration record the PCG kernels write straight into mapped host memory
 struct PcgProgress {
@@ -44,42 +47,13 @@ struct PcgProgress {
 
 // T = storage type of matrix values and vectors: double (product path) or float (inner solver of the
 // mixed-precision mode); scalars and partial sums are double in both
-template <class T> struct AmgT;   // amg.h
-
 template <class T> struct PcgBuffersT {
     T *x, *r, *p, *q;       // [n*k]
     const T *dinv;          // [n]
     double *part_pq;        // [kMaxPartialBlocks*8] per-workgroup partial sums of <p, Ap>
     double *part_rz;        // [2][kMaxPartialBlocks*8] per-workgroup partial sums of <Cr, r> (even / odd step)
     double *rz0;            // [48] totals forwarded between launches: <Cr0,r0>[8] | <p,Ap>[8] | <Cr,r> of even / odd steps [8+8] | done flag [8] | floor of <Cr,r> [8]
-    // two-level preconditioner (vertex-block Chebyshev); cheb_degree = 0 -> Jacobi
-    int64_t nv_coarse;      // free vertex dofs = size of the leading P1 block
-    int cheb_degree;
-    double cheb_lmax, cheb_lmin;
-    T *cz, *cres;           // [nv_coarse*k]
-    T *cd[2];               // [nv_coarse*k] ping-pong Chebyshev directions
-    // paired Chebyshev steps (launch_vblock_square): the vertex block A_vv and B = A_vv D^-1 A_vv on B's pattern;
-    // sq_rowptr = nullptr -> one launch per Chebyshev step on A_vv alone
-    const int32_t *sq_rowptr = nullptr, *sq_col = nullptr;
-    const T *sq_a = nullptr, *sq_b = nullptr;
-    int sq_lanes = 16;      // lanes per row of the paired kernel (8 / 16 / 32 by the average row length of B)
-    // compact copy of the vertex block (launch_vblock_compact): inside the full matrix a vertex row's ~15 leading entries sit
-    // in a row of ~110, so a Chebyshev launch touches three partly used cache lines per row; nullptr -> read A in place
-    const int32_t *vb_rowptr = nullptr, *vb_col = nullptr;
-    const T *vb_val = nullptr;
-    // fp32 Chebyshev chain inside an fp64 solve (vertex blocks above 32 k rows: the launches are HBM streams there, and a
-    // preconditioner may be inexact); nullptr -> the chain runs in T.  Float copies of the compact block's values and of the
-    // vertex rows' Jacobi factors, chain vectors [nv_coarse * k]
-    const float *c32_val = nullptr, *c32_dinv = nullptr;
-    // fixed-width image of the vertex block for the Chebyshev launches (launch_vblock_ell): [nv][kEllWidth] columns and values,
-    // [nv][2] begin / end of a row's further entries in the arrays the chain reads otherwise; nullptr -> rows are walked as CSR
-    const int32_t *ell_col = nullptr, *ell_tail = nullptr;
-    const T *ell_val = nullptr;
-    const float *c32_ell_val = nullptr;
-    float *c32_z = nullptr, *c32_res = nullptr, *c32_d[2] = {nullptr, nullptr};
-    // multigrid cycle on the vertex block instead of the polynomial (amg.h; 2D by default); nullptr -> Chebyshev
-    const AmgT<T> *amg = nullptr;
-    const AmgT<float> *amg32 = nullptr;   // fp64 solves: the cycle in fp32 storage (remo_debug_tune key 17), nullptr -> in T
+    VertexSolverT<T> vs;    // the solver of the P1 (vertex) block of the two-level preconditioner (vertex_solver.h); vs.degree = 0 -> Jacobi
     // patch operator only: q = A p is left WITHOUT the sums of the rows shared by several patches - the update launch, which reads
     // q once anyway, forms them from the boundary slab itself (one launch and one pass over the slab less per step).  Set by the
     // host when the operator is the patch operator and the update launch does not gather q (no folded Chebyshev step).
@@ -192,7 +166,6 @@ template <class T> void launch_spmm(const CsrViewT<T> &A, int k, const T *x, T *
 template <class T> void launch_patch_spmm(const CsrViewT<T> &A, int k, const T *x, T *y, double *part, const double *scal, int nblocks, hipStream_t s, int step, bool defer);   // patch.hip
 // the PCG's q = A p with p in fp32 storage (PcgBuffersT::p32): fp64 product, shared rows left in the slab, partials of <p, A p>; throws where the patch operator does not apply
 void launch_patch_spmm_x32(const CsrViewT<double> &A, int k, const float *x, double *part, const double *scal, int nblocks, hipStream_t s, int step);   // patch.hip
-template <class T> bool pcg_update_folds(const PcgBuffersT<T> &b);   // the update launch takes the first Chebyshev step along (and gathers q)
 
 template <class T> void launch_pcg_init(const CsrViewT<T> &A, int k, const T *f, const PcgBuffersT<T> &b, hipStream_t s);       // + C r0, p0
 template <class T> void launch_pcg_update(const CsrViewT<T> &A, int k, int step, double tol2, const PcgBuffersT<T> &b, hipStream_t s);  // + C r (Chebyshev steps)
@@ -202,29 +175,12 @@ template <class T> void launch_pcg_final(int k, int step, const PcgBuffersT<T> &
 void launch_direction_form(bool flat, int grid, int64_t n, int64_t nv, int k, int step, double tol2, int nb_rz, const double *part_rz_new,
                            double *scal, const double *r, float *p, const double *dinv, double *z, hipStream_t s);
 void set_vector_stamps(long long *stamps);   // probe builds: where k_pcg_direction_flat / k_pcg_update_tile leave their clocks (remo_debug_vector_heads)
-void launch_vblock_bound(int64_t nv, const CsrView &A, const double *dinv, unsigned long long *out_bits, hipStream_t s);
-// B = A_vv D^-1 A_vv (and A_vv itself) on the pattern of B, rows sorted; cnt / rowptr [nv + 1], col / a / b [capacity];
-// *flag (device int, pre-zeroed) is raised when a row has more than kSquareSlots distinct columns or the capacity
-// is too small: the caller then keeps the one-step path
-constexpr int kSquareSlots = 512;
-void launch_vblock_square(int64_t nv, const CsrView &A, const double *dinv, int32_t *sq_rowptr, int32_t *sq_col, double *sq_a, double *sq_b,
-                          int64_t capacity, int32_t *flag, hipStream_t s);
-int cheb_grid(int64_t nv);
 
 // probe of a grid-wide barrier (remo_debug_grid_barrier): nblocks must not exceed what the chip holds at once; counter / fail / mismatch zeroed by the caller
 void launch_barrier_probe(int nblocks, int nbar, unsigned *counter, int *fail, float *buf, int *mismatch, hipStream_t s);
-constexpr int kEllWidth = 24;   // entries per row of the fixed-width image: three per lane at eight lanes per row (3D P1 rows hold ~15)
-// eval64 / eval32: either may be nullptr
-void launch_vblock_ell(int64_t nv, const int32_t *rowptr, const int32_t *col, const double *val, int32_t *ecol, int32_t *tail, double *eval64,
-                       float *eval32, hipStream_t s);
-
 
 // mixed precision: conversions around the fp32 inner solve
 void launch_to_float(int64_t n, const double *src, float *dst, hipStream_t s);
-// compact CSR copy of the leading nv x nv block of A (columns ascend, so the block's entries lead every row); *flag is raised
-// when it does not fit `capacity` entries; vb_rowptr[nv] = entries
-void launch_vblock_compact(int64_t nv, const CsrView &A, int32_t *vb_rowptr, int32_t *vb_col, double *vb_val, int64_t capacity, int32_t *flag,
-                           hipStream_t s);
 void launch_mixed_residual(int64_t n, const double *f, const double *q /* may be null */, float *r32, hipStream_t s);
 void launch_mixed_accumulate(int64_t n, double *x, float *e, int zero_e, hipStream_t s);
 // one PCG step's update with residual replacement (x32 += alpha p; x64 += x32; r32 = f - A64 x64; C r)

@@ -1,8 +1,8 @@
 // kernels.hip — hand-written gfx950 (CDNA4, wave64) kernels of the ReMo3D hot path around the PCG step:
-//   metric terms -> CSR value gather-assembly -> the CSR product q = A p (edge-pair SpMM) -> set-up of the preconditioner's
-//   P1 vertex block (bound, square, compact copy, fixed-width image) -> conversions of the mixed-precision mode ->
-//   axis point location / RHS build / evaluation.
-// The vector kernels of the PCG step and the Chebyshev steps are pcg_kernels.hip, the patch operator patch.hip.
+//   metric terms -> CSR value gather-assembly -> the CSR product q = A p (edge-pair SpMM) -> conversions of the
+//   mixed-precision mode -> axis point location / RHS build / evaluation.
+// The vector kernels of the PCG step are pcg_kernels.hip, the solver of the preconditioner's P1 vertex block with the set-up of its
+// images vertex_solver.hip, the patch operator patch.hip.
 // All of it is HBM/L2-bound sparse work: no MFMA (a sparse row is not a dense contraction); the levers are
 // coalesced CSR streams, DPP (not LDS) cross-lane reductions, XCD-aware row placement and LDS-staged reference
 // tensors.  Reference lines each kernel replaces are cited at the kernel.  Element reads shared with the element passes of the
@@ -609,186 +609,6 @@ template <class T> void launch_spmm(const CsrViewT<T> &A, int k, const T *x, T *
 template void launch_spmm<double>(const CsrViewT<double> &, int, const double *, double *, double *, const double *, int, hipStream_t, int, bool);
 template void launch_spmm<float>(const CsrViewT<float> &, int, const float *, float *, double *, const double *, int, hipStream_t, int, bool);
 
-// ------------------------------------------------------------------------------------------
-// set-up of the two-level preconditioner's vertex block (the PCG's own kernels and launchers: pcg_kernels.hip)
-
-// Gershgorin bound of the Jacobi-scaled vertex block: max_i dinv_i * sum_j |a_ij|, j < nv
-__global__ void __launch_bounds__(256) k_vblock_bound(int64_t nv, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                                                      const double *__restrict__ val, const double *__restrict__ dinv,
-                                                      unsigned long long *out_bits) {
-    double m = 0.0;
-    for (int64_t row = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; row < nv; row += int64_t(gridDim.x) * blockDim.x) {
-        double s = 0.0;
-        for (int32_t p = rowptr[row]; p < rowptr[row + 1]; ++p) {
-            if (col[p] >= nv) break;
-            s += fabs(val[p]);
-        }
-        m = fmax(m, s * dinv[row]);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, 64));
-    if ((threadIdx.x & 63) == 0) atomicMax(out_bits, (unsigned long long)__double_as_longlong(m));  // positive doubles order like their bits
-}
-
-void launch_vblock_bound(int64_t nv, const CsrView &A, const double *dinv, unsigned long long *out_bits, hipStream_t s) {
-    int64_t g = (nv + 255) / 256;
-    if (g > 512) g = 512;
-    if (g < 1) g = 1;
-    hipLaunchKernelGGL(k_vblock_bound, dim3(int(g)), dim3(256), 0, s, nv, A.rowptr, A.col, A.val, dinv, out_bits);
-}
-
-// ------------------------------------------------------------------------------------------
-// Squared vertex block.  A Chebyshev step is a launch of ~5 us on a block of ~1e4 rows: pure launch latency, and
-// there are 6 (3D) / 8 (2D) of them per PCG step.  Two consecutive Richardson factors of the same polynomial,
-//   res'' = (I - b M)(I - a M) res = res - (a + b) M res + a b M^2 res,   M = A_vv D^-1,
-// need M^2, i.e. B = A_vv D^-1 A_vv, once per matrix (a 2-hop pattern, ~65 entries per row in 3D): then ONE launch
-// applies two factors, and the chain is half as long.  The polynomial is the same (product over the Chebyshev
-// roots instead of the three-term recurrence), so the PCG iteration is unchanged up to rounding.
-// One wave per row: distinct 2-hop columns through an LDS hash set, sorted (bitonic, so that the result does
-// not depend on the insertion order), values by sorted-row lookups in a fixed order: bit-reproducible.
-
-__device__ __forceinline__ int32_t lower_bound_col(const int32_t *__restrict__ col, int32_t lo, int32_t hi, int32_t key) {
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (col[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-template <int PASS>   // 0: count the distinct columns of every row; 1: fill (row offsets known)
-__global__ void __launch_bounds__(256) k_vblock_square(int64_t nv, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                                                       const double *__restrict__ val, const double *__restrict__ dinv,
-                                                       int32_t *__restrict__ cnt, const int32_t *__restrict__ sq_rowptr,
-                                                       int32_t *__restrict__ sq_col, double *__restrict__ sq_a, double *__restrict__ sq_b,
-                                                       int64_t capacity, int32_t *flag) {
-    __shared__ int32_t keys[4][kSquareSlots];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t row = int64_t(blockIdx.x) * 4 + wave;
-    const bool active = row < nv;
-    int32_t *K = keys[wave];
-    for (int sl = lane; sl < kSquareSlots; sl += 64) K[sl] = INT_MAX;
-    __syncthreads();
-    int32_t rs = 0, re = 0;
-    bool overflow = false;
-    if (active) {
-        rs = rowptr[row]; re = rowptr[row + 1];
-        for (int32_t p = rs; p < re; ++p) {
-            const int32_t k = col[p];
-            if (k >= nv) break;                       // wave-uniform: the vertex block leads the row
-            const int32_t ke = rowptr[k + 1];
-            for (int32_t q = rowptr[k] + lane; q < ke; q += 64) {
-                const int32_t j = col[q];
-                if (j >= nv) break;
-                uint32_t h = (uint32_t(j) * 2654435761u) >> 23;
-                bool placed = false;
-                for (int probe = 0; probe < kSquareSlots; ++probe) {
-                    const int32_t old = atomicCAS(&K[h], INT_MAX, j);
-                    if (old == INT_MAX || old == j) { placed = true; break; }
-                    h = (h + 1) & (kSquareSlots - 1);
-                }
-                overflow |= !placed;
-            }
-        }
-    }
-    __syncthreads();
-    int c = 0;
-    for (int sl = lane; sl < kSquareSlots; sl += 64) c += K[sl] != INT_MAX;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-    if (__builtin_amdgcn_ballot_w64(overflow) != 0 || c > kSquareSlots - 64) {   // keep the table sparse enough to probe quickly
-        if (lane == 0) atomicOr(flag, 1);
-        c = 0;
-    }
-    if (PASS == 0) {
-        if (active && lane == 0) cnt[row] = c;
-        return;
-    }
-    // bitonic sort of the table (empty slots = INT_MAX end up last); every wave sorts its own table, the
-    // barriers keep the four waves of the block in step
-    for (int size = 2; size <= kSquareSlots; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            __syncthreads();
-            for (int t = lane; t < kSquareSlots / 2; t += 64) {
-                const int lo = 2 * t - (t & (stride - 1));
-                const int hi = lo + stride;
-                const bool up = (lo & size) == 0;
-                const int32_t a = K[lo], b = K[hi];
-                if ((a > b) == up) { K[lo] = b; K[hi] = a; }
-            }
-        }
-    __syncthreads();
-    if (!active || c == 0) return;
-    const int64_t off = sq_rowptr[row];
-    if (off + c > capacity) {
-        if (lane == 0) atomicOr(flag, 2);
-        return;
-    }
-    for (int t = lane; t < c; t += 64) {
-        const int32_t j = K[t];
-        double a = 0.0, b = 0.0;
-        for (int32_t p = rs; p < re; ++p) {           // fixed order over the row's vertex entries
-            const int32_t k = col[p];
-            if (k >= nv) break;
-            if (k == j) a = val[p];
-            const int32_t ks = rowptr[k], ke = rowptr[k + 1];
-            const int32_t q = lower_bound_col(col, ks, ke, j);
-            if (q < ke && col[q] == j) b += val[p] * dinv[k] * val[q];
-        }
-        sq_col[off + t] = j;
-        sq_a[off + t] = a;
-        sq_b[off + t] = b;
-    }
-}
-
-// exclusive scan of cnt[0 .. n) into out[0 .. n]; one workgroup (n is the vertex count)
-__global__ void __launch_bounds__(1024) k_scan_counts(int64_t n, const int32_t *__restrict__ cnt, int32_t *__restrict__ out) {
-    __shared__ int64_t part[1024];
-    const int64_t chunk = (n + 1023) / 1024;
-    const int64_t b = int64_t(threadIdx.x) * chunk, e = (b + chunk < n) ? b + chunk : n;
-    int64_t sum = 0;
-    for (int64_t i = b; i < e; ++i) sum += cnt[i];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t run = 0;
-        for (int t = 0; t < 1024; ++t) { const int64_t v = part[t]; part[t] = run; run += v; }
-        out[n] = int32_t(run < INT_MAX ? run : INT_MAX);
-    }
-    __syncthreads();
-    int64_t run = part[threadIdx.x];
-    for (int64_t i = b; i < e; ++i) { out[i] = int32_t(run < INT_MAX ? run : INT_MAX); run += cnt[i]; }
-}
-
-// compact copy of the vertex block: PASS 0 counts the leading entries (column < nv) of every vertex row, PASS 1 copies them
-template <int PASS>
-__global__ void __launch_bounds__(256) k_vblock_compact(int64_t nv, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                                                        const double *__restrict__ val, int32_t *__restrict__ cnt,
-                                                        const int32_t *__restrict__ vb_rowptr, int32_t *__restrict__ vb_col,
-                                                        double *__restrict__ vb_val, int64_t capacity, int32_t *flag) {
-    const int64_t row = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (row >= nv) return;
-    const int32_t rs = rowptr[row], re = rowptr[row + 1];
-    if (PASS == 0) {
-        cnt[row] = lower_bound_col(col, rs, re, int32_t(nv)) - rs;
-    } else {
-        const int32_t at = vb_rowptr[row], len = vb_rowptr[row + 1] - at;
-        if (int64_t(at) + len > capacity) { if (len > 0) atomicOr(flag, 1); return; }
-        for (int32_t e = 0; e < len; ++e) { vb_col[at + e] = col[rs + e]; vb_val[at + e] = val[rs + e]; }   // vertex rows are plain CSR
-    }
-}
-
-void launch_vblock_compact(int64_t nv, const CsrView &A, int32_t *vb_rowptr, int32_t *vb_col, double *vb_val, int64_t capacity, int32_t *flag,
-                           hipStream_t s) {
-    if (nv <= 0) return;
-    const int g = int((nv + 255) / 256);
-    int32_t *cnt = vb_col;   // the counts live in the (not yet used) column array: capacity >= nv is required by the caller
-    hipLaunchKernelGGL((k_vblock_compact<0>), dim3(g), dim3(256), 0, s, nv, A.rowptr, A.col, A.val, cnt, (const int32_t *)nullptr, (int32_t *)nullptr,
-                       (double *)nullptr, capacity, flag);
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, nv, cnt, vb_rowptr);
-    hipLaunchKernelGGL((k_vblock_compact<1>), dim3(g), dim3(256), 0, s, nv, A.rowptr, A.col, A.val, (int32_t *)nullptr, vb_rowptr, vb_col, vb_val,
-                       capacity, flag);
-}
-
 // ---- grid barrier (probe and, if it pays, the Chebyshev chain as one launch) ---------------------------------------------------
 // Every workgroup of a launch whose workgroups are all resident (grid <= what the chip holds at once: the caller's duty) arrives
 // at a counter that only grows - arrival e of nblocks workgroups waits for e * nblocks - and leaves when all have.  Data that
@@ -833,54 +653,6 @@ __global__ void __launch_bounds__(256) k_barrier_probe(unsigned nblocks, int nba
 
 void launch_barrier_probe(int nblocks, int nbar, unsigned *counter, int *fail, float *buf, int *mismatch, hipStream_t s) {
     hipLaunchKernelGGL(k_barrier_probe, dim3(nblocks), dim3(256), 0, s, unsigned(nblocks), nbar, counter, fail, buf, mismatch);
-}
-
-// Fixed-width image of the vertex block for the Chebyshev launches.  A launch on the CSR form is a chain of dependent round
-// trips per row - row bounds, then columns and values (once per eight entries), then the gathered vector rows - on a block that
-// lives in the caches: latency, not bytes.  Here the first kEllWidth entries of row i sit at [i][0 .. kEllWidth) (padded with
-// (i, 0)), so a lane asks for all its columns and values at once, then for all the vector rows: two trips.  tail[i] = the
-// begin / end of the row's remaining entries in the arrays the image was made from (equal: none - the usual case).
-__global__ void __launch_bounds__(256) k_vblock_ell(int64_t nv, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                                                    const double *__restrict__ val, int32_t *__restrict__ ecol, int32_t *__restrict__ tail,
-                                                    double *__restrict__ eval64, float *__restrict__ eval32) {
-    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= nv * kEllWidth) return;
-    const int64_t row = i / kEllWidth;
-    const int e = int(i - row * kEllWidth);
-    const int32_t rs = rowptr[row], re = rowptr[row + 1];
-    int32_t c = int32_t(row);
-    double v = 0.0;
-    if (rs + e < re) {
-        const int32_t j = col[rs + e];
-        if (j < nv) { c = j; v = val[rs + e]; }     // columns ascend: the vertex block leads a row of the whole matrix
-    }
-    ecol[i] = c;
-    if (eval64) eval64[i] = v;
-    if (eval32) eval32[i] = float(v);
-    if (e == 0) {
-        const int32_t end = lower_bound_col(col, rs, re, int32_t(nv));
-        const bool more = end - rs > kEllWidth;
-        tail[2 * row] = more ? rs + kEllWidth : 0;
-        tail[2 * row + 1] = more ? end : 0;
-    }
-}
-
-void launch_vblock_ell(int64_t nv, const int32_t *rowptr, const int32_t *col, const double *val, int32_t *ecol, int32_t *tail, double *eval64,
-                       float *eval32, hipStream_t s) {
-    if (nv <= 0) return;
-    hipLaunchKernelGGL(k_vblock_ell, dim3(int((nv * kEllWidth + 255) / 256)), dim3(256), 0, s, nv, rowptr, col, val, ecol, tail, eval64, eval32);
-}
-
-void launch_vblock_square(int64_t nv, const CsrView &A, const double *dinv, int32_t *sq_rowptr, int32_t *sq_col, double *sq_a, double *sq_b,
-                          int64_t capacity, int32_t *flag, hipStream_t s) {
-    if (nv <= 0) return;
-    const int g = int((nv + 3) / 4);
-    int32_t *cnt = sq_col;   // the counts live in the (not yet used) column array: capacity >= nv is required by the caller
-    hipLaunchKernelGGL((k_vblock_square<0>), dim3(g), dim3(256), 0, s, nv, A.rowptr, A.col, A.val, dinv, cnt, (const int32_t *)nullptr, (int32_t *)nullptr,
-                       (double *)nullptr, (double *)nullptr, capacity, flag);
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, nv, cnt, sq_rowptr);
-    hipLaunchKernelGGL((k_vblock_square<1>), dim3(g), dim3(256), 0, s, nv, A.rowptr, A.col, A.val, dinv, (int32_t *)nullptr, sq_rowptr, sq_col, sq_a, sq_b,
-                       capacity, flag);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
-// kutil.h — device helpers shared by the kernel files (kernels.hip, pcg_kernels.hip, patch.hip): fixed-order block reductions, the early-exit
-// test of queued PCG launches, and buffer accesses with the hardware range check.
+// kutil.h — device helpers shared by the kernel files (kernels.hip, pcg_kernels.hip, vertex_solver.hip, amg.hip, patch.hip): fixed-order block reductions, the early-exit
+// test of queued PCG launches, the lower bound in a sorted row, and buffer accesses with the hardware range check.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -86,6 +86,15 @@ template <int K> __device__ __forceinline__ double pick(const double (&a)[K], in
 #pragma unroll
     for (int j = 1; j < K; ++j) r = (c == j) ? a[j] : r;
     return r;
+}
+
+// first position in the ascending a[lo .. hi) whose value is not below key (columns of a CSR row: where the leading block ends)
+__device__ __forceinline__ int32_t lower_bound_i32(const int32_t *__restrict__ a, int32_t lo, int32_t hi, int32_t key) {
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (a[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
 }
 
 // scal[kDoneSlot] (as int) is set to s + 1 by the update launch of step s once every column is frozen; the launches of

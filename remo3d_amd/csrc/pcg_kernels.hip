@@ -1,6 +1,6 @@
 // pcg_kernels.hip — the kernels of a PCG step other than the operator, gfx950 (CDNA4, wave64): init, update, direction and final
-// launches, the Chebyshev steps on the P1 vertex block, the residual replacement of the mixed mode, and their launchers
-// (declared in kernels.h).  The operator q = A p is kernels.hip (CSR) or patch.hip (patch operator); the multigrid cycle is amg.hip.
+// launches (k_pcg_update_folded takes the first Chebyshev step along), the residual replacement of the mixed mode, and their launchers (kernels.h).
+// The operator q = A p is kernels.hip (CSR) or patch.hip (patch operator); C r on the P1 vertex block is vertex_solver.hip or amg.hip (cycle).
 // All of it is HBM/L2-bound streaming: the levers are whole-line accesses, loads in flight, few launches per step and, since every
 // form of a launch is a kernel of its own, the occupancy each form's own code allows.
 #include "kernels.h"
@@ -59,20 +59,6 @@ __device__ __forceinline__ void publish_progress(PcgProgress *pr, const double *
 // A column whose <Cr,r> has dropped below tol^2 <Cr0,r0> (or that broke down) is frozen
 // (alpha = beta = 0), which makes post-convergence steps harmless.
 
-// Two-level preconditioner ("multigrid" of the reference, ngsolve_functions.py:46: a lowest-order
-// coarse space plus a smoother on the high-order dofs).  In the hierarchical basis the vertex
-// functions ARE the P1 space and vertex dofs are numbered first, so the coarse problem is the leading
-// nv x nv block of the assembled matrix, read in place (columns are sorted: the block's entries
-// lead every row).  C = blockdiag( q_d(A_vv), D_hh^-1 ): a fixed Chebyshev polynomial of degree d in
-// the Jacobi-scaled vertex block (spectrum bounds [lmax/ratio, lmax], lmax = Gershgorin bound, so
-// q_d is positive definite on the whole spectrum and plain PCG stays valid) and Jacobi on edge/face
-// dofs.  nv = 0 gives plain Jacobi ("local").
-template <class T> struct ChebArgsT {
-    int64_t nv;       // free vertex dofs (0: Jacobi)
-    double inv_theta; // 1 / theta, theta = (lmax + lmin) / 2
-    T *z, *res;       // [nv][K] polynomial value so far / residual of the vertex block system
-    T *d0;            // [nv][K] first Chebyshev direction
-};
 // q = A p of the patch operator with the rows shared by several patches still in the boundary slab (PcgBuffersT::defer_q)
 template <class T> struct QViewT {
     const int32_t *bptr = nullptr, *bslot = nullptr;
@@ -684,125 +670,6 @@ __global__ void __launch_bounds__(256) k_pcg_update_tile(int64_t n, UpdHeadT<T> 
     REMO_VEC_STAMPS(1, t_in, t_head)
 }
 
-// One Chebyshev step on the vertex block, 8 lanes per row:
-//   z += d;  res -= A_vv d;  d' = c1 d + c2 D^-1 res
-// FIRST: z = 0, res = r, d = D^-1 r / theta are formed on the fly from the PCG residual (no set-up
-// pass).  LAST = 1 (degree 1 only): z = d, nothing else.  LAST = 2: the polynomial's last term needs no
-// product of its own (z_final = z + d + d'), so the launch that forms d' also finishes z and leaves the
-// <r, z> partial sums for the PCG scalars: a polynomial of `degree` terms costs degree - 1 launches.
-// TC = storage type of the chain (block values, Jacobi factors, directions, residual, running z): T, or float inside an fp64
-// solve (large vertex blocks: the launches are HBM streams there, and a preconditioner may be applied inexactly - the
-// recurrences of x and r never see it).  r (read) and the finished z (written for the direction kernel) stay in T.
-// ELL: the first kEllWidth entries of a row come from the fixed-width image (ecol, eval; k_vblock_ell) and `rowptr` holds the
-// begin / end PAIRS of the entries beyond them in (col, val).
-template <class T, class TC, int K, bool FIRST, int LAST, bool ELL = false>
-__global__ void __launch_bounds__(256) k_cheb_step(int64_t nv, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                                                   const TC *__restrict__ val, const TC *__restrict__ dinv,
-                                                   const TC *__restrict__ d_old, TC *__restrict__ d_new,
-                                                   TC *__restrict__ zc, TC *__restrict__ res, T *__restrict__ z, double c1_, double c2_, double inv_theta_,
-                                                   T *__restrict__ r, double *__restrict__ part, const double *__restrict__ scal, int commit, int step,
-                                                   const int32_t *__restrict__ ecol = nullptr, const TC *__restrict__ eval = nullptr) {
-    const TC c1 = TC(c1_), c2 = TC(c2_), inv_theta = TC(inv_theta_);
-    constexpr int LPR = 8, RPB = 256 / LPR;
-    constexpr bool SAME = sizeof(T) == sizeof(TC);
-    static_assert(K <= LPR, "one column per lane after the transposing reduction");
-    if (solve_done(scal, step)) return;
-    const int sub = threadIdx.x % LPR, grp = threadIdx.x / LPR;
-    // the kernel is a chain of dependent round trips on a tiny block (launch-latency class): after the
-    // transposing reduction lane `sub` owns column mycol of its row, so the vectors of the update are
-    // requested per lane BEFORE the row is walked and need no round trip of their own
-    int idx[K], own[K];
-    towner_init<K, LPR>(idx, own, sub);
-    const int mycol = idx[0];
-    const bool mine = own[0] != 0;
-    double dot = 0.0;
-    for (int64_t row = int64_t(blockIdx.x) * RPB + grp; row < nv; row += int64_t(gridDim.x) * RPB) {
-        constexpr int NE = ELL ? kEllWidth / LPR : 1;
-        int32_t ej[NE];
-        TC ev[NE];
-        int32_t rs, re;
-        if constexpr (ELL) {
-            const int64_t eb = row * kEllWidth + sub;
-#pragma unroll
-            for (int u = 0; u < NE; ++u) { ej[u] = ecol[eb + u * LPR]; ev[u] = eval[eb + u * LPR]; }
-            rs = rowptr[2 * row]; re = rowptr[2 * row + 1];
-        } else {
-            rs = rowptr[row]; re = rowptr[row + 1];
-        }
-        const int64_t at = row * K + mycol;
-        TC di = TC(0), dold_in = TC(0), z_in = TC(0), res_in = TC(0);
-        T rr = T(0);
-        if (mine) {
-            di = dinv[row];
-            if (SAME && commit) {   // the update launch ran the FIRST step and left the new vertex residual in d_new (free until this
-                rr = T(d_new[at]);  // launch writes it): r could not take it while the neighbours' rows were still gathering r
-                r[at] = rr;
-            } else {
-                rr = r[at];
-            }
-            if (!FIRST) { dold_in = d_old[at]; z_in = zc[at]; res_in = res[at]; }
-        }
-        TC t[K];
-#pragma unroll
-        for (int c = 0; c < K; ++c) t[c] = TC(0);
-        if constexpr (ELL) {
-#pragma unroll
-            for (int u = 0; u < NE; ++u) {
-                const int32_t j = ej[u];
-                const TC v = FIRST ? ev[u] * dinv[j] * inv_theta : ev[u];
-                if (FIRST) {
-                    const T *dj = r + int64_t(j) * K;
-#pragma unroll
-                    for (int c = 0; c < K; ++c) t[c] += v * TC(dj[c]);
-                } else {
-                    const TC *dj = d_old + int64_t(j) * K;
-#pragma unroll
-                    for (int c = 0; c < K; ++c) t[c] += v * dj[c];
-                }
-            }
-        }
-        for (int32_t p = rs + sub; p < re; p += LPR) {
-            const int32_t j = col[p];
-            if (j >= nv) break;  // columns ascend: the vertex block leads the row
-            const TC v = FIRST ? val[p] * dinv[j] * inv_theta : val[p];
-            if (FIRST) {
-                const T *dj = r + int64_t(j) * K;
-#pragma unroll
-                for (int c = 0; c < K; ++c) t[c] += v * TC(dj[c]);
-            } else {
-                const TC *dj = d_old + int64_t(j) * K;
-#pragma unroll
-                for (int c = 0; c < K; ++c) t[c] += v * dj[c];
-            }
-        }
-        TReduce<K, LPR>::run(t, sub);
-        if (mine) {
-            const TC dold = FIRST ? di * TC(rr) * inv_theta : dold_in;
-            TC zi = FIRST ? dold : z_in + dold;
-            const TC ri = (FIRST ? TC(rr) : res_in) - t[0];
-            const TC dn = c1 * dold + c2 * di * ri;
-            if (LAST == 2) zi += dn;
-            if (LAST) z[at] = T(zi / di);   // LAST: stored pre-divided by dinv so the direction kernel treats it like r
-            else {
-                zc[at] = zi;
-                res[at] = ri;
-                d_new[at] = dn;
-            }
-            if (LAST) dot += double(rr) * double(zi);
-        }
-    }
-    if (LAST) {
-        __shared__ double smem[16 * K];
-        double dcol[K];
-#pragma unroll
-        for (int c = 0; c < K; ++c) dcol[c] = (mine && c == mycol) ? dot : 0.0;
-        block_sum<K>(dcol, smem);
-#pragma unroll
-        for (int c = 0; c < K; ++c)
-            if (threadIdx.x == c) part[blockIdx.x * K + c] = dcol[c];
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // The direction launch: beta = <Cr,r>_new/<Cr,r>_old;  p = C r + beta p (and x += alpha p of the step, PcgBuffersT::x_in_direction).
 // Two kernels, chosen by launch_pcg_direction: k_pcg_direction_flat (the vectors as flat arrays, 16 bytes per lane) and
@@ -1089,84 +956,6 @@ __global__ void __launch_bounds__(256) k_pcg_final(int step, int nb_rz, const do
     if (threadIdx.x == 0) publish_progress(progress + (step % (progress_len - 1)), rz, K, step);
 }
 
-// Two Chebyshev (Richardson) factors per launch, 16 lanes per row of B's pattern.  State: z and w = D^-1 res.
-//   t1 = A w, t2 = B w;   z += (a + b) w - a b D^-1 t1;   w' = w - (a + b) D^-1 t1 + a b D^-1 t2
-// FIRST: z = 0, w = D^-1 r formed on the fly; LAST: z is stored divided by dinv (the direction kernel treats it like
-// r) and the <r, z> partial sums are left for the PCG scalars.
-template <class T, int K, int LPR, bool FIRST, bool LAST>
-__global__ void __launch_bounds__(256) k_cheb_pair(int64_t nv, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                                                   const T *__restrict__ va, const T *__restrict__ vb, const T *__restrict__ dinv,
-                                                   const T *__restrict__ w_old, T *__restrict__ w_new, T *__restrict__ z, double ab_sum_, double ab_prod_,
-                                                   const T *__restrict__ r, double *__restrict__ part, const double *__restrict__ scal, int step) {
-    constexpr int RPB = 256 / LPR, U = 2;
-    static_assert(K <= LPR, "one column per lane after the transposing reduction");
-    if (solve_done(scal, step)) return;
-    const T ab_sum = T(ab_sum_), ab_prod = T(ab_prod_);
-    const int sub = threadIdx.x % LPR, grp = threadIdx.x / LPR;
-    int idx[K], own[K];
-    towner_init<K, LPR>(idx, own, sub);
-    const int mycol = idx[0];
-    const bool mine = own[0] != 0;
-    double dot = 0.0;
-    for (int64_t row = int64_t(blockIdx.x) * RPB + grp; row < nv; row += int64_t(gridDim.x) * RPB) {
-        const int32_t rs = rowptr[row], re = rowptr[row + 1];
-        const int64_t at = row * K + mycol;
-        T di = T(0), wi = T(0), zi = T(0), rr = T(0);
-        if (mine) {
-            di = dinv[row];
-            if (FIRST || LAST) rr = r[at];
-            wi = FIRST ? di * rr : w_old[at];
-            if (!FIRST) zi = z[at];
-        }
-        T t1[K], t2[K];
-#pragma unroll
-        for (int c = 0; c < K; ++c) { t1[c] = T(0); t2[c] = T(0); }
-        for (int32_t p0 = rs + sub; p0 < re; p0 += U * LPR) {   // U passes of loads in flight, as in the SpMM
-            int32_t j[U];
-            T a[U], b[U], w[U][K];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int32_t p = p0 + u * LPR;
-                j[u] = -1; a[u] = T(0); b[u] = T(0);
-                if (p < re) { j[u] = col[p]; a[u] = va[p]; b[u] = vb[p]; }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int c = 0; c < K; ++c) w[u][c] = T(0);
-                if (j[u] >= 0) {
-                    const T *wj = (FIRST ? r : w_old) + int64_t(j[u]) * K;
-                    const T dj = FIRST ? dinv[j[u]] : T(1);
-#pragma unroll
-                    for (int c = 0; c < K; ++c) w[u][c] = FIRST ? dj * wj[c] : wj[c];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int c = 0; c < K; ++c) { t1[c] += a[u] * w[u][c]; t2[c] += b[u] * w[u][c]; }
-        }
-        TReduce<K, LPR>::run(t1, sub);
-        TReduce<K, LPR>::run(t2, sub);
-        if (mine) {
-            const T zn = zi + ab_sum * wi - ab_prod * di * t1[0];
-            z[at] = LAST ? zn / di : zn;
-            if (!LAST) w_new[at] = wi - ab_sum * di * t1[0] + ab_prod * di * t2[0];
-            if (LAST) dot += double(rr) * double(zn);
-        }
-    }
-    if (LAST) {
-        __shared__ double smem[16 * K];
-        double dcol[K];
-#pragma unroll
-        for (int c = 0; c < K; ++c) dcol[c] = (mine && c == mycol) ? dot : 0.0;
-        block_sum<K>(dcol, smem);
-#pragma unroll
-        for (int c = 0; c < K; ++c)
-            if (threadIdx.x == c) part[blockIdx.x * K + c] = dcol[c];
-    }
-}
-
 int vec_grid(int64_t n) {
     int64_t g = (n + 255) / 256;
     if (g > kMaxPartialBlocks / 2) g = kMaxPartialBlocks / 2;
@@ -1174,139 +963,16 @@ int vec_grid(int64_t n) {
     return int(g);
 }
 
-int cheb_grid(int64_t nv) {
-    if (nv <= 0) return 0;
-    int64_t g = (nv + 31) / 32;
-    if (g > kMaxPartialBlocks / 2) g = kMaxPartialBlocks / 2;
-    return int(g);
-}
-
-// every launch of this file: `grid` workgroups of 256 threads, no dynamic LDS
-template <class Kernel, class... Args> static void launch256(Kernel kernel, int grid, hipStream_t s, Args... args) {
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, args...);
-}
-
-template <class T> static ChebArgsT<T> cheb_args(const PcgBuffersT<T> &b) {
-    ChebArgsT<T> c;
-    c.nv = b.cheb_degree > 0 ? b.nv_coarse : 0;
-    c.inv_theta = b.cheb_degree > 0 ? 1.0 / (0.5 * (b.cheb_lmax + b.cheb_lmin)) : 0.0;
-    c.z = b.cz; c.res = b.cres; c.d0 = b.cd[0];
-    return c;
-}
-
-// C r for the vertex block: `degree` Chebyshev steps; the last one leaves the <r_v, z_v> partials
-// behind the nb_vec partials of the high-order part (slot = even / odd step buffer)
-// the update launch can take the FIRST step along when the polynomial has launches of its own left to commit the
-// vertex residual (degree >= 3) and is not applied through the squared block (2D)
-template <class T> static bool cheb_first_folds(const PcgBuffersT<T> &b);
-template <class T> bool pcg_update_folds(const PcgBuffersT<T> &b) { return cheb_first_folds(b); }
-template bool pcg_update_folds<double>(const PcgBuffersT<double> &);
-template bool pcg_update_folds<float>(const PcgBuffersT<float> &);
-template <class T> static bool cheb_first_folds(const PcgBuffersT<T> &b) {
-    // measured in the bench, fold on vs off on one box: -2.3 % solve time at 12.8 k vertices, -0.9 % at 27 k, +0.4 % at 83 k
-    // (there the step is real work, not launch latency): small vertex blocks only
-    return g_tune.fold_first && !b.amg && b.cheb_degree >= 3 && b.nv_coarse > 0 && b.nv_coarse <= 32768 && !(b.sq_rowptr && (b.cheb_degree & 1) == 0);
-}
-
-template <class T> static void launch_cheb(const CsrViewT<T> &A, int k, int step, const PcgBuffersT<T> &b, double *part_slot, hipStream_t s, bool first_done = false) {
-    if (b.cheb_degree <= 0 || b.nv_coarse <= 0) return;
-    if (b.amg) {   // multigrid cycle instead of the polynomial (amg.hip)
-        if constexpr (sizeof(T) == 8) {
-            if (b.amg32) {
-                launch_amg_cycle<float, double>(*b.amg32, k, step, (const double *)b.r, b.cz, part_slot + int64_t(b.nb_vec) * k, cheb_grid(b.nv_coarse), (const double *)b.rz0, s);
-                return;
-            }
-        }
-        launch_amg_cycle<T, T>(*b.amg, k, step, (const T *)b.r, b.cz, part_slot + int64_t(b.nb_vec) * k, cheb_grid(b.nv_coarse), (const double *)b.rz0, s);
-        return;
-    }
-    if (b.sq_rowptr && (b.cheb_degree & 1) == 0) {   // two Richardson factors of the Chebyshev polynomial per launch
-        const double theta = 0.5 * (b.cheb_lmax + b.cheb_lmin), delta = 0.5 * (b.cheb_lmax - b.cheb_lmin);
-        const int m = b.cheb_degree, np = m / 2;
-        // 3D rows of B hold ~65 entries (32 lanes per row), 2D rows ~19 (8 lanes)
-        const int g_last = cheb_grid(b.nv_coarse);
-        double *part = part_slot + int64_t(b.nb_vec) * k;
-        for (int j = 0; j < np; ++j) {
-            // roots of the shifted Chebyshev polynomial, paired from the two ends of the interval inwards
-            const double r1 = theta - delta * cos(M_PI * (2.0 * (j + 1) - 1.0) / (2.0 * m));
-            const double r2 = theta - delta * cos(M_PI * (2.0 * (m - j) - 1.0) / (2.0 * m));
-            const double a = 1.0 / r1, bb = 1.0 / r2;
-            const T *wold = b.cd[j & 1];
-            T *wnew = b.cd[(j + 1) & 1];
-            const bool first = (j == 0), last = (j + 1 == np);
-            // only the LAST launch leaves partial sums, so only it is tied to the cheb_grid slots
-            auto grid_for = [&](int lpr) { int64_t gg = (b.nv_coarse + 256 / lpr - 1) / (256 / lpr); if (last && gg > g_last) gg = g_last; if (gg > 4096) gg = 4096; return int(gg); };
-            auto for_lanes = [&](auto fn) {
-                if (b.sq_lanes >= 32) fn(int_c<32>{});
-                else if (b.sq_lanes >= 16) fn(int_c<16>{});
-                else fn(int_c<8>{});
-            };
-            for_k(k, [&](auto kc) { for_lanes([&](auto lc) { for_bool(first, [&](auto fc) { for_bool(last, [&](auto ec) {
-                constexpr int K = decltype(kc)::value, LPR = decltype(lc)::value;
-                launch256(k_cheb_pair<T, K, LPR, decltype(fc)::value, decltype(ec)::value>, grid_for(LPR), s, b.nv_coarse, b.sq_rowptr, b.sq_col, b.sq_a,
-                          b.sq_b, b.dinv, wold, wnew, b.cz, a + bb, a * bb, b.r, part, b.rz0, step);
-            }); }); }); });
-        }
-        return;
-    }
-    const double theta = 0.5 * (b.cheb_lmax + b.cheb_lmin), delta = 0.5 * (b.cheb_lmax - b.cheb_lmin);
-    const double sig = theta / delta, inv_theta = 1.0 / theta;
-    double rho = 1.0 / sig;
-    const int g = cheb_grid(b.nv_coarse);
-    double *part = part_slot + int64_t(b.nb_vec) * k;
-    const int launches = b.cheb_degree > 1 ? b.cheb_degree - 1 : 1;   // the last term rides on the launch before it
-    const int32_t *vrow = b.vb_rowptr ? b.vb_rowptr : A.rowptr, *vcol = b.vb_rowptr ? b.vb_col : A.col;   // compact vertex block if there is one
-    const T *vval = b.vb_rowptr ? b.vb_val : A.val;
-    // fp32 chain inside an fp64 solve: needs the compact block (its float copy), never together with the folded first step
-    const bool chain32 = sizeof(T) == 8 && b.c32_val != nullptr && b.vb_rowptr != nullptr && !first_done;
-    // the fixed-width image of the block (k_vblock_ell) in the storage type of the chain, if the host made one
-    const bool ell = b.ell_col != nullptr && b.ell_tail != nullptr && (chain32 ? b.c32_ell_val != nullptr : b.ell_val != nullptr);
-    for (int j = 0; j < launches; ++j) {
-        const double rho_new = 1.0 / (2.0 * sig - rho);
-        const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
-        rho = rho_new;
-        const T *dold = b.cd[j & 1];
-        T *dnew = b.cd[(j + 1) & 1];
-        const bool first = (j == 0), last = (j + 1 == launches);
-        if (first && first_done) continue;        // k_pcg_update_folded did it (with the c1, c2 of cheb_first_coefficients)
-        const int commit = (first_done && j == 1) ? 1 : 0;
-        // only the launch that leaves partial sums is tied to the cheb_grid slots; the others take one row group per
-        // workgroup slot (at 83 k vertices 512 workgroups walk five row groups each, a chain of five dependent round trips:
-        // 17.9 us per launch under rocprofv3, profiles/r01_f_kernel_stats_sizeL_10depths_before_grid_fix.csv; after: 14.2 us, …_after_grid_fix.csv)
-        const int64_t g_rows = (b.nv_coarse + 31) / 32;
-        const int gl = last ? g : int(g_rows < 8192 ? g_rows : 8192);
-        // k_cheb_step<.., FIRST, LAST, ELL> as the launches of a chain take it: (FIRST, LAST) = (1, 1) the only step of degree 1, (1, 2) the
-        // only launch of a higher degree, (1, 0), (0, 2) and (0, 0) - there is no (0, 1)
-        auto go = [&](auto fc, auto lc) {
-            for_k(k, [&](auto kc) { for_bool(ell, [&](auto ec) {
-                constexpr int K = decltype(kc)::value, LAST = decltype(lc)::value;
-                constexpr bool FIRST = decltype(fc)::value, ELL = decltype(ec)::value;
-                if (chain32)
-                    launch256(k_cheb_step<T, float, K, FIRST, LAST, ELL>, gl, s, b.nv_coarse, ELL ? b.ell_tail : vrow, vcol, b.c32_val, b.c32_dinv,
-                              (const float *)b.c32_d[j & 1], b.c32_d[(j + 1) & 1], b.c32_z, b.c32_res, b.cz, c1, c2, inv_theta, b.r, part, b.rz0, 0, step,
-                              b.ell_col, b.c32_ell_val);
-                else
-                    launch256(k_cheb_step<T, T, K, FIRST, LAST, ELL>, gl, s, b.nv_coarse, ELL ? b.ell_tail : vrow, vcol, vval, b.dinv, dold, dnew,
-                              b.cz, b.cres, b.cz, c1, c2, inv_theta, b.r, part, b.rz0, commit, step, b.ell_col, b.ell_val);
-            }); });
-        };
-        if (first && last) { if (b.cheb_degree == 1) go(std::true_type{}, int_c<1>{}); else go(std::true_type{}, int_c<2>{}); }
-        else if (first) go(std::true_type{}, int_c<0>{});
-        else if (last) go(std::false_type{}, int_c<2>{});
-        else go(std::false_type{}, int_c<0>{});
-    }
-}
-
-template <class T> static int nb_rz(const PcgBuffersT<T> &b) { return b.nb_vec + ((b.cheb_degree > 0 && b.nv_coarse > 0) ? cheb_grid(b.nv_coarse) : 0); }
+template <class T> static int nb_rz(const PcgBuffersT<T> &b) { return b.nb_vec + ((b.vs.degree > 0 && b.vs.nv > 0) ? cheb_grid(b.vs.nv) : 0); }
 
 template <class T> void launch_pcg_init(const CsrViewT<T> &A, int k, const T *f, const PcgBuffersT<T> &b, hipStream_t s) {
     const int64_t n = A.n;
     const int g = b.nb_vec;
-    const ChebArgsT<T> ch = cheb_args(b);
+    const ChebArgsT<T> ch = cheb_args(b.vs);
     auto go = [&](auto *p) {      // p: the search direction in its storage type TP
         using TP = std::remove_pointer_t<decltype(p)>;
         for_k(k, [&](auto kc) { constexpr int K = decltype(kc)::value; launch256(k_pcg_init<T, K, TP>, g, s, n, ch, f, b.dinv, b.x, b.r, p, b.part_rz); });
-        launch_cheb(A, k, 0, b, b.part_rz, s);
+        launch_vertex_solve(b.vs, k, 0, b.r, b.dinv, b.rz0, b.nb_vec, b.part_rz, s);
         if (ch.nv > 0)
             for_k(k, [&](auto kc) { constexpr int K = decltype(kc)::value; launch256(k_pcg_direction_row<T, K, TP>, g, s, n, 1, 0, 0.0, nb_rz(b), ch, b.part_rz, b.rz0, b.r, p, b.dinv, (T *)nullptr); });
     };
@@ -1319,7 +985,7 @@ template <class T> void launch_pcg_init(const CsrViewT<T> &A, int k, const T *f,
 template <class T> static UpdHeadT<T> update_head(const CsrViewT<T> &A, int step, double tol2, const PcgBuffersT<T> &b) {
     UpdHeadT<T> hd;
     // the patch operator's <p, A p> bins: two sets taken in turn by step parity, this launch clears the set of the next step
-    const bool bins = b.pq_bins && b.defer_q && A.patch && !cheb_first_folds(b);
+    const bool bins = b.pq_bins && b.defer_q && A.patch && !vertex_first_folds(b.vs);
     hd.step = step; hd.tol2 = tol2;
     hd.nb_spmv = bins ? kPqBins : b.nb_spmv; hd.nb_rz = nb_rz(b);
     hd.part_pq = bins ? b.part_pq + (step & 1) * (kPqBins * 8) : b.part_pq;
@@ -1336,7 +1002,7 @@ template <class T> void launch_pcg_update(const CsrViewT<T> &A, int k, int step,
     double *nxt = b.part_rz + ((step + 1) & 1) * (kMaxPartialBlocks * 8);
     constexpr uint64_t kBufferLimit = 0xFFFFF000ull;   // what a buffer descriptor's range check covers (kutil.h kOutOfRange)
     // 1. the form
-    const bool folded = cheb_first_folds(b);
+    const bool folded = vertex_first_folds(b.vs);
     const bool slab = b.defer_q && A.patch && !folded;      // the shared rows of q = A p are still in the patch operator's boundary slab
     const bool skip_x = b.x_in_direction;
     uint64_t slab_bytes = 0;
@@ -1352,7 +1018,7 @@ template <class T> void launch_pcg_update(const CsrViewT<T> &A, int k, int step,
     // 2. its arguments
     UpdHeadT<T> hd = update_head(A, step, tol2, b);
     hd.ev = EvSlotsT<T>{b.x_ev_at, b.x_ev, b.x_ev_n};
-    const ChebArgsT<T> ch = cheb_args(b);
+    const ChebArgsT<T> ch = cheb_args(b.vs);
     QViewT<T> qv;
     qv.skip_x = skip_x ? 1 : 0;
     if (slab) { qv.bptr = A.patch->t.bptr; qv.bslot = A.patch->t.bslot; qv.Yb = A.patch->Yb; }
@@ -1372,13 +1038,12 @@ template <class T> void launch_pcg_update(const CsrViewT<T> &A, int k, int step,
         }
         if (folded) {
             FoldArgsT<T> fold;
-            const double theta = 0.5 * (b.cheb_lmax + b.cheb_lmin), delta = 0.5 * (b.cheb_lmax - b.cheb_lmin);
-            const double sig = theta / delta, rho = 1.0 / sig, rho_new = 1.0 / (2.0 * sig - rho);
+            const ChebStep cs = cheb_step(b.vs);      // the chain's first step
             fold.nb_flat = g;
-            fold.rowptr = b.vb_rowptr ? b.vb_rowptr : A.rowptr; fold.col = b.vb_rowptr ? b.vb_col : A.col; fold.val = b.vb_rowptr ? b.vb_val : A.val;
-            fold.d_new = b.cd[1]; fold.stage = b.cd[0];
-            fold.c1 = rho_new * rho; fold.c2 = 2.0 * rho_new / delta;      // the j = 0 coefficients of launch_cheb
-            const int grid = g + int((b.nv_coarse + 31) / 32);   // the vertex workgroups leave no partial sums: one row group each
+            fold.rowptr = b.vs.rowptr; fold.col = b.vs.col; fold.val = b.vs.val;
+            fold.d_new = b.vs.d[1]; fold.stage = b.vs.d[0];
+            fold.c1 = cs.c1; fold.c2 = cs.c2;
+            const int grid = g + int((b.vs.nv + 31) / 32);   // the vertex workgroups leave no partial sums: one row group each
             launch256(k_pcg_update_folded<T, K>, grid, s, n, hd, ch, nxt, b.p, b.q, b.x, b.r, b.dinv, fold, qv.skip_x);
         } else if (tile) {
             if constexpr (sizeof(T) == 8) launch256(k_pcg_update_tile<T, K>, g, s, n, hd, ch.nv, nxt, b.p, b.r, b.dinv, qv);
@@ -1388,7 +1053,7 @@ template <class T> void launch_pcg_update(const CsrViewT<T> &A, int k, int step,
             for_bool(masked, [&](auto mc) { launch256(k_pcg_update<T, K, decltype(mc)::value>, g, s, n, hd, ch.nv, nxt, b.p, b.q, b.x, b.r, b.dinv, qv); });
         }
     });
-    launch_cheb(A, k, step, b, nxt, s, folded);      // (an fp32 direction never goes with the folded step: it needs the slab)
+    launch_vertex_solve(b.vs, k, step, b.r, b.dinv, b.rz0, b.nb_vec, nxt, s, folded);      // (an fp32 direction never goes with the folded step: it needs the slab)
 }
 
 // Residual replacement of the mixed mode, in place of launch_pcg_update at the chosen steps:
@@ -1423,13 +1088,13 @@ void launch_pcg_replace(const CsrViewT<float> &A, const CsrViewT<double> &A64, i
     const int64_t n = A.n;
     const int g = b.nb_vec;
     double *nxt = b.part_rz + ((step + 1) & 1) * (kMaxPartialBlocks * 8);
-    const ChebArgsT<float> ch = cheb_args(b);
+    const ChebArgsT<float> ch = cheb_args(b.vs);
     const UpdHeadT<float> hd = update_head(A, step, tol2, b);
     for_k(k, [&](auto kc) { constexpr int K = decltype(kc)::value; launch256(k_pcg_update_x<float, K>, g, s, n, hd, b.p, b.x); });
     launch_mixed_accumulate(n * k, x64, b.x, 1, s);
     launch_spmm(A64, k, (const double *)x64, q64, (double *)nullptr, (const double *)nullptr, b.nb_spmv, s, 0);
     for_k(k, [&](auto kc) { constexpr int K = decltype(kc)::value; launch256(k_mixed_replace<K>, g, s, n, ch.nv, f64, q64, b.r, b.dinv, nxt, b.rz0, step); });
-    launch_cheb(A, k, step, b, nxt, s);
+    launch_vertex_solve(b.vs, k, step, b.r, b.dinv, b.rz0, b.nb_vec, nxt, s);
 }
 
 // add_x: this launch also forms x += alpha p of the step (b.x_in_direction and the step's update launch left x alone; a residual
@@ -1438,7 +1103,7 @@ template <class T> void launch_pcg_direction(const CsrViewT<T> &A, int k, int st
     const int64_t n = A.n;
     const int g = b.nb_vec;
     const double *nw = b.part_rz + ((step + 1) & 1) * (kMaxPartialBlocks * 8);
-    const ChebArgsT<T> ch = cheb_args(b);
+    const ChebArgsT<T> ch = cheb_args(b.vs);
     T *xp = (add_x && b.x_in_direction) ? b.x : nullptr;
     const bool flat = g_tune.flat_direction && uint64_t(n) * uint64_t(k) * sizeof(T) < 0xFFFFF000ull;
     auto go = [&](auto *p, T *x) {      // p: the search direction in its storage type TP

@@ -14,6 +14,9 @@ pytestmark = pytest.mark.gpu
 
 SRC = [([0.0], [1.0]), ([0.1], [1.0]), ([-0.1, 0.1], [1.0, -1.0])]
 EVAL = [[0.4, 6.4, -2.0], [2.1, 2.6], [0.5, 3.0, 0.0]]
+# test_paired_chebyshev_steps_are_the_same_preconditioner: PCG steps the paired form may differ by from the one-step form.
+# mixed: twice the largest difference seen on the commit before the cell was added (1), and no less than the fp64 margin
+STEP_MARGIN = {"fp64": 2, "mixed": 2}
 
 
 def _oracle_solve(mesh, sigma, condense):
@@ -297,10 +300,18 @@ def test_3d_path_reproduces_the_axisymmetric_solution(gpu_ctx):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("precision", ["fp64", "mixed"])
 @pytest.mark.parametrize("which", ["2d", "3d"])
-def test_paired_chebyshev_steps_are_the_same_preconditioner(which, mesh2d, mesh3d, gpu_ctx):
+def test_paired_chebyshev_steps_are_the_same_preconditioner(which, precision, mesh2d, mesh3d, gpu_ctx):
     """Two Richardson factors of the Chebyshev polynomial per launch on B = A_vv D^-1 A_vv (remo_debug_tune key 6) is
-    the same polynomial as one three-term-recurrence step per launch: same PCG step counts (+-1), same potentials."""
+    the same polynomial as one three-term-recurrence step per launch: same PCG step counts (+-1), same potentials.
+    mixed: the fp32 inner solver takes the paired form on the converted A_vv and B (VertexSolverBuilder::to_float).  Both
+    modes stop on the true fp64 residual at the same rtol, so the bound on the potentials is the fp64 one; the step
+    counts may differ by STEP_MARGIN[precision].  Measured for mixed on the commit before this cell (one-step | paired):
+    2d [88, 88, 90] | [88, 88, 90], potentials 5.6e-10 apart; 3d [220, 219, 177] | [219, 219, 177], 1.4e-11 apart
+    (fp64 there: 2d [87, 87, 89] both, 3d [211, 212, 170] | [211, 210, 170]).  The 3d fixture gets the odd default degree 5, at
+    which the library keeps the one-step launches whatever key 6 says: the 3d cells hold the two runs of the patch operator to
+    each other; the paired form and its fp32 conversion run in the 2d cells."""
     from remo3d_amd import _lib, solver
     mesh = mesh2d if which == "2d" else mesh3d
     L = _lib.load()
@@ -308,13 +319,13 @@ def test_paired_chebyshev_steps_are_the_same_preconditioner(which, mesh2d, mesh3
     try:
         for mode in (0, 2):
             L.remo_debug_tune(6, mode)
-            outs, st, rc = gpu_ctx.solve_batch(mesh, SIGMA3, SRC, EVAL, solver.make_opts(rtol=1e-10, coarse="chebyshev"))
+            outs, st, rc = gpu_ctx.solve_batch(mesh, SIGMA3, SRC, EVAL, solver.make_opts(rtol=1e-10, coarse="chebyshev", precision=precision))
             assert rc == 0 and st["coarse_used"] == 1
             got[mode] = (np.concatenate(outs), st["iterations"][:3])
     finally:
         L.remo_debug_tune(6, 1)
     assert np.max(np.abs(got[0][0] - got[2][0]) / np.abs(got[0][0])) < 1e-7
-    assert max(abs(a - b) for a, b in zip(got[0][1], got[2][1])) <= 2
+    assert max(abs(a - b) for a, b in zip(got[0][1], got[2][1])) <= STEP_MARGIN[precision]
 
 
 @pytest.mark.gpu
@@ -497,7 +508,7 @@ def _hub_mesh(shell=44):
 @pytest.mark.parametrize("precision", ["fp64", "mixed"])
 def test_fixed_width_vertex_block_with_long_rows(precision, gpu_ctx):
     """The Chebyshev launches read the first 24 entries of a vertex row from a fixed-width image and the rest from the CSR form
-    (remo_debug_tune key 24; kernels.hip k_vblock_ell): on a mesh whose hub vertex has ~45 neighbours the image, the CSR form and
+    (remo_debug_tune key 24; vertex_solver.hip k_vblock_ell): on a mesh whose hub vertex has ~45 neighbours the image, the CSR form and
     the oracle give the same potentials, with the block read in place or from its compact copy (key 13) and the first step
     inside the update launch or on its own (key 9)."""
     from remo3d_amd import _lib, solver
