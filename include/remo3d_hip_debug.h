@@ -76,6 +76,16 @@ int remo_debug_direction_bytes(remo_ctx_t *ctx);
 int remo_debug_direction_forms(remo_ctx_t *ctx, int64_t n, int64_t nv, int32_t k, int32_t grid, int32_t step, double tol2, const double *r,
                                const float *p, const double *z, const double *dinv, const double *part_even, const double *part_odd,
                                int32_t nb_rz, const double *scal48, float *p_flat, float *p_row, double *scal_flat, double *scal_row);
+/* ONE sparse product C = X Y of the multigrid hierarchy's setup (amg.hip: k_spgemm count pass, scan, clamp, fill pass) on the caller's
+ * own matrices: X [nx rows] and Y [ny rows] as CSR on the host, the columns of X naming rows of Y, the columns inside a row of Y
+ * distinct; slots = 128 or 512 (the kernel variant: a row of C may hold slots / 2 distinct columns); cap = the capacity of C's arrays.
+ * Out: crp [nx + 1] (clamped to cap), cc and cv [cap + 2] - the arrays as the setup allocates them, every byte 0xFF where the launch
+ * wrote nothing - and flags[0]: bit 1 = a row did not fit its tables (it is left empty), bit 2 = the product outgrew cap.
+ * Row by row C holds the sorted distinct columns, and per column the sum, in the order of X's row and starting from + 0.0, of the
+ * separately rounded products: reproducible bit for bit. */
+int remo_debug_product(remo_ctx_t *ctx, int32_t slots, int64_t cap, int64_t nx, const int32_t *xrp, const int32_t *xc, const double *xv,
+                       int64_t ny, const int32_t *yrp, const int32_t *yc, const double *yv, int32_t *crp, int32_t *cc, double *cv,
+                       int32_t *flags);
 /* Where a workgroup of the PCG's two vector launches spends its time before its first stored value (-DREMO_PROBES builds only):
  * on = 1 makes wave 0 of every workgroup of k_pcg_direction_flat and k_pcg_update_tile leave three clocks (on entry | scalars in
  * LDS | at the end) from now on; on = 0 stops that and reports the LAST launch of each kind that was not a no-op:

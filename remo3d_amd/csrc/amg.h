@@ -45,6 +45,12 @@ bool amg_setup(Arena &ar, hipStream_t s, int dim, int64_t nv, const int32_t *row
 // fp32 image of a hierarchy (values converted, patterns shared, own vectors) for the inner solver of the mixed mode
 void amg_to_float(Arena &ar, hipStream_t s, const AmgT<double> &in, int kmax, AmgT<float> &out);
 
+// ONE sparse product C = X Y of the setup on the caller's host arrays (remo_debug_product): count pass, scan, clamp to `cap` entries, fill
+// pass with 128 or 512 hash slots per row, in device memory of its own that starts out as 0xFF bytes.  crp [nx + 1], cc / cv [cap + 2].
+// Throws on arguments the kernels could not be trusted with.
+void amg_debug_product(hipStream_t s, int slots, int64_t cap, int64_t nx, const int32_t *xrp, const int32_t *xc, const double *xv, int64_t ny,
+                       const int32_t *yrp, const int32_t *yc, const double *yv, int32_t *crp, int32_t *cc, double *cv, int32_t *flags);
+
 // z = V(1,1)-cycle(r) on the vertex rows; the last launch stores cz = z / dinv (the direction kernel treats it like r) and the
 // <r, z> partial sums of `nblocks` workgroups [nblocks][k] in part.  scal / step: early exit of finished solves (kutil.h solve_done)
 // T = storage type of the hierarchy, TR = type of r and cz: <float, double> is the cycle in fp32 inside an fp64 solve (a

@@ -8,7 +8,8 @@
 //   aggregation   distance-2 maximal independent set of the matrix graph by hashed priorities (Bell / Dalton / Olson 2012):
 //                 roots, then their neighbours, then the neighbours' neighbours by the strongest connection
 //   prolongator   P = (I - 4 / (3 lmax) D^-1 A) P0, one generic row-wise sparse product (LDS hash set per wave for the
-//                 pattern, sorted; values by sorted-row lookups in a fixed order),
+//                 pattern, sorted; values: every product of the row formed once, handed to its column through an LDS
+//                 table and added there in the order of the row - a fixed order),
 //                 R = P^T by count / scan / scatter and an LDS sort of every row
 //   coarse matrix A' = R (A P), two more products
 //   coarsest      dense inverse (Gauss-Jordan in LDS, <= 64 rows)
@@ -200,7 +201,13 @@ __global__ void __launch_bounds__(256) k_smoothing_factor(int64_t n, const int32
 
 // ---- generic sparse product C = X Y, one wave per row of X ----------------------------------------------------------------
 // PASS 0 counts the distinct columns of every row; PASS 1 (row offsets known) writes them sorted with their values.
-// Columns of Y rows ascend (binary search); X rows in any order.  flag |= 1: a row does not fit the hash table.
+// Pattern: the columns of the rows of Y that X's row names go into an LDS hash set, are compacted and sorted.  Values: driven by
+// the products, not by lookups - every x_ik y_kj of the row is formed once, finds its output column in the sorted list in LDS and
+// leaves its rounded value in a term table [entry of X's row][output column]; every output column then adds its terms in the
+// order of X's row, starting from + 0.0.  So a value is the sequential sum of the separately rounded products, whatever the
+// round size or the lane that formed a product (the term goes through LDS: nothing is contracted into an fma).
+// The columns inside a row of Y are distinct (one writer per cell); neither X's nor Y's rows need ascend.
+// flag |= 1: a row does not fit the hash table or has more than SLOTS / 2 distinct columns; it is written empty.
 template <int PASS, int SLOTS>
 __global__ void __launch_bounds__(256) k_spgemm(int64_t nx, const int32_t *__restrict__ xrp, const int32_t *__restrict__ xc, const double *__restrict__ xv,
                                                 const int32_t *__restrict__ yrp, const int32_t *__restrict__ yc, const double *__restrict__ yv,
@@ -208,7 +215,10 @@ __global__ void __launch_bounds__(256) k_spgemm(int64_t nx, const int32_t *__res
                                                 double *__restrict__ cv, int32_t *flag) {   // PASS 1: crp has been clamped to the capacity of cc / cv (k_clamp_rowptr)
     __shared__ int32_t keys[4][SLOTS];
     __shared__ int32_t list[4][SLOTS];
-    __shared__ double terms[4][PASS == 1 ? SLOTS / 2 : 1];
+    constexpr int kTerms = SLOTS < 512 ? 512 : 1024;   // cells of a wave's term table: a round takes kTerms / c entries of X (LDS per workgroup: 24 / 52 KB)
+    __shared__ double terms[4][PASS == 1 ? kTerms : 1];
+    __shared__ int32_t pstart[4][PASS == 1 ? 64 : 1], pys[4][PASS == 1 ? 64 : 1];   // per entry of the round: its first product, where its row of Y starts,
+    __shared__ double pxv[4][PASS == 1 ? 64 : 1];                                   // its value
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t row = int64_t(blockIdx.x) * 4 + wave;
     if (row >= nx) return;                      // no block-wide barriers below: a wave works on its own tables
@@ -270,34 +280,59 @@ __global__ void __launch_bounds__(256) k_spgemm(int64_t nx, const int32_t *__res
     const int room = int(crp[row + 1] - crp[row]);   // < c only when the product outgrew its arrays (flagged by k_clamp_rowptr): stay inside them
     if (c > room) c = room;
     if (c <= 0) return;
-    // values: the (output column, entry of X) pairs are spread over the lanes, one sorted-row lookup each, a chunk of X entries at
-    // a time; the terms go through LDS and every output column adds its own in the order of X's row (not found = + 0.0):
-    // the same sums as a serial walk, without its chain of dependent lookups
+    // values, a round of up to npmax entries of X at a time: lane pp fetches entry pp and the bounds of its row of Y, a scan numbers
+    // the round's products, and the lanes take the PRODUCTS (entry pp, entry q of that row): the product's output column t by a
+    // search of the sorted list in LDS, its rounded value into cell (pp, t) of the term table - one writer per cell, the columns of
+    // a row of Y being distinct; a column beyond a clamped list has no cell.  Then the lane of column t adds its cells in the order
+    // of X's row and clears them: a term that does not exist is the + 0.0 of a cleared cell, the same sums as a serial walk.
     double *V = terms[wave];
+    int32_t *PS = pstart[wave], *PY = pys[wave];
+    double *PX = pxv[wave];
     constexpr int NACC = SLOTS / 128;            // output columns per lane: c <= SLOTS / 2
     double acc[NACC];
 #pragma unroll
     for (int a = 0; a < NACC; ++a) acc[a] = 0.0;
-    const int pc = c >= 64 ? 1 : 64 / c;         // entries of X per round
-    for (int32_t p0 = xs; p0 < xe; p0 += pc) {
-        const int np = (xe - p0 < pc) ? int(xe - p0) : pc;
-        for (int idx = lane; idx < c * np; idx += 64) {
-            const int t = idx / np, pp = idx - t * np;
-            const int32_t j = L[t];
-            const int32_t p = p0 + pp;
-            const int32_t k = xc[p];
-            const int32_t ys = yrp[k], ye = yrp[k + 1];
-            const int32_t q = lower_bound_i32(yc, ys, ye, j);
-            V[idx] = (q < ye && yc[q] == j) ? xv[p] * yv[q] : 0.0;
+    const int npmax = kTerms / c < 64 ? kTerms / c : 64;   // entries of X per round: >= 4 (512 slots) or 8 (c <= SLOTS / 2), one per lane at most
+    for (int i = lane; i < c * npmax; i += 64) V[i] = 0.0;
+    for (int32_t p0 = xs; p0 < xe; p0 += npmax) {
+        const int np = (xe - p0 < npmax) ? int(xe - p0) : npmax;
+        int32_t ys = 0, len = 0;
+        double xval = 0.0;
+        if (lane < np) {
+            const int32_t k = xc[p0 + lane];
+            xval = xv[p0 + lane];
+            ys = yrp[k];
+            len = yrp[k + 1] - ys;
+        }
+        int32_t incl = len;                      // products up to and including this lane's entry
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int32_t up = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += up;
+        }
+        const int32_t total = __shfl(incl, 63, 64);
+        if (lane < np) { PS[lane] = incl - len; PY[lane] = ys; PX[lane] = xval; }
+        wave_sync();                             // also: the cells cleared above / by the round before
+        for (int32_t idx = lane; idx < total; idx += 64) {
+            int lo = 1, hi = np;                 // pp = the last entry that starts at or before product idx (empty rows of Y start where the next one does)
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (PS[mid] <= idx) lo = mid + 1; else hi = mid;
+            }
+            const int pp = lo - 1;
+            const int32_t q = PY[pp] + (idx - PS[pp]);
+            const int32_t j = yc[q];
+            const double yval = yv[q];
+            const int t = lower_bound_i32(L, 0, c, j);
+            if (t < c && L[t] == j) V[pp * c + t] = PX[pp] * yval;
         }
         wave_sync();
 #pragma unroll
         for (int a = 0; a < NACC; ++a) {
             const int t = lane + 64 * a;
             if (t < c)
-                for (int pp = 0; pp < np; ++pp) acc[a] += V[t * np + pp];
+                for (int pp = 0; pp < np; ++pp) { acc[a] += V[pp * c + t]; V[pp * c + t] = 0.0; }
         }
-        wave_sync();
     }
 #pragma unroll
     for (int a = 0; a < NACC; ++a) {
@@ -839,6 +874,53 @@ bool amg_setup(Arena &ar, hipStream_t s, int dim, int64_t nv, const int32_t *row
         why = ex.what();
         return false;
     }
+}
+
+void amg_debug_product(hipStream_t s, int slots, int64_t cap, int64_t nx, const int32_t *xrp, const int32_t *xc, const double *xv, int64_t ny,
+                       const int32_t *yrp, const int32_t *yc, const double *yv, int32_t *crp, int32_t *cc, double *cv, int32_t *flags) {
+    if (slots != 128 && slots != 512) throw std::runtime_error("amg_debug_product: 128 or 512 slots");
+    if (nx < 1 || ny < 1 || nx > (1 << 24) || ny > (1 << 24) || cap < 1 || cap > (1 << 28)) throw std::runtime_error("amg_debug_product: sizes out of range");
+    // the kernels trust their inputs: row pointers that ascend from 0, columns of X that name rows of Y
+    auto ascending = [](const int32_t *rp, int64_t n) {
+        if (rp[0] != 0) return false;
+        for (int64_t i = 0; i < n; ++i)
+            if (rp[i + 1] < rp[i]) return false;
+        return rp[n] <= (1 << 28);
+    };
+    if (!ascending(xrp, nx) || !ascending(yrp, ny)) throw std::runtime_error("amg_debug_product: row pointers must ascend from 0");
+    const size_t nnzx = size_t(xrp[nx]), nnzy = size_t(yrp[ny]);
+    for (size_t p = 0; p < nnzx; ++p)
+        if (xc[p] < 0 || xc[p] >= ny) throw std::runtime_error("amg_debug_product: a column of X names no row of Y");
+    for (size_t q = 0; q < nnzy; ++q)
+        if (yc[q] < 0 || yc[q] == INT_MAX) throw std::runtime_error("amg_debug_product: a column of Y out of range");
+    const size_t ints = 2 * (size_t(nx) + size_t(ny) + 4) + nnzx + nnzy + 2 * size_t(nx) + size_t(cap) + 16 + kFlagSlots;
+    const size_t bytes = 4 * ints + 8 * (nnzx + nnzy + size_t(cap) + 8) + 16 * size_t(nx) + (size_t(1) << 20);   // + the scan's storage, + 256 per array
+    DeviceTemp tmp;
+    Arena ar;
+    ar.base = tmp.alloc<char>(bytes);
+    ar.cap = bytes;
+    HIP_TRY(hipMemsetAsync(ar.base, 0xFF, bytes, s));   // what the product does not write stays 0xFF
+    Csr X, Y, C;
+    auto put = [&](Csr &M, int64_t n, size_t nnz, const int32_t *rp, const int32_t *c, const double *v) {
+        M.n = n; M.nnz = int64_t(nnz);
+        M.rowptr = ar.lo<int32_t>(size_t(n) + 2); M.col = ar.lo<int32_t>(nnz + 2); M.val = ar.lo<double>(nnz + 2);
+        HIP_TRY(hipMemcpyAsync(M.rowptr, rp, sizeof(int32_t) * (size_t(n) + 1), hipMemcpyHostToDevice, s));
+        if (nnz) {
+            HIP_TRY(hipMemcpyAsync(M.col, c, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(M.val, v, sizeof(double) * nnz, hipMemcpyHostToDevice, s));
+        }
+    };
+    put(X, nx, nnzx, xrp, xc, xv);
+    put(Y, ny, nnzy, yrp, yc, yv);
+    int32_t *d_flag = ar.lo<int32_t>(kFlagSlots);
+    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int32_t) * kFlagSlots, s));
+    spgemm_async(ar, true, s, X, Y, cap, slots == 128 ? 1 : 2, d_flag, C);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(crp, C.rowptr, sizeof(int32_t) * (size_t(nx) + 1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(cc, C.col, sizeof(int32_t) * (size_t(cap) + 2), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(cv, C.val, sizeof(double) * (size_t(cap) + 2), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(flags, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
 }
 
 void amg_to_float(Arena &ar, hipStream_t s, const AmgT<double> &in, int kmax, AmgT<float> &out) {

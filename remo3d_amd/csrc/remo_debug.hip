@@ -402,6 +402,19 @@ int remo_debug_direction_forms(remo_ctx_t *ctx, int64_t n, int64_t nv, int32_t k
     }
 }
 
+int remo_debug_product(remo_ctx_t *ctx, int32_t slots, int64_t cap, int64_t nx, const int32_t *xrp, const int32_t *xc, const double *xv,
+                       int64_t ny, const int32_t *yrp, const int32_t *yc, const double *yv, int32_t *crp, int32_t *cc, double *cv,
+                       int32_t *flags) {
+    if (!ctx || !xrp || !xc || !xv || !yrp || !yc || !yv || !crp || !cc || !cv || !flags) return REMO_ERR_ARG;
+    try {
+        HIP_TRY(hipSetDevice(ctx->device));
+        amg_debug_product(ctx->stream, slots, cap, nx, xrp, xc, xv, ny, yrp, yc, yv, crp, cc, cv, flags);
+        return REMO_OK;
+    } catch (const std::exception &ex) {
+        return fail(ctx, REMO_ERR_DEVICE, ex.what());
+    }
+}
+
 #ifdef REMO_PROBES
 namespace {
 // remo_debug_vector_heads: the stamp rows of both launches while the probe is on.  One buffer for the process, on the device of the context
