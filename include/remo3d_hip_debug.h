@@ -86,6 +86,24 @@ int remo_debug_direction_forms(remo_ctx_t *ctx, int64_t n, int64_t nv, int32_t k
 int remo_debug_product(remo_ctx_t *ctx, int32_t slots, int64_t cap, int64_t nx, const int32_t *xrp, const int32_t *xc, const double *xv,
                        int64_t ny, const int32_t *yrp, const int32_t *yc, const double *yv, int32_t *crp, int32_t *cc, double *cv,
                        int32_t *flags);
+/* ONE row operation of the multigrid cycle (amg.hip) on the caller's own CSR matrix [n rows, columns in 0 .. nx) and vectors [rows][k]
+ * on the host, by the kernel the cycle launches, in device memory of its own that starts out as 0xFF bytes:
+ *   op 0  y = M x, `lanes` (8, 16, 32 or 64) lanes per row - the restriction's form (the prolongation's is the same sum with 8);
+ *         out = y [n][k]
+ *   op 1  first half sweep: out = z = omega D^-1 r, out2 = t = r - omega A D^-1 r; x holds r; nx = n
+ *   op 2  second half sweep of a coarser level: out = z + omega D^-1 (r - A z); x holds z; nx = n
+ *   op 3  the finest level's second half sweep: out = (z + omega D^-1 (r - A z)) / D^-1 and out2 = the <r, z_new> partial sums of
+ *         `nblocks` workgroups [nblocks][k], whose column sums are the products of the columns; x holds z; nx = n
+ * dinv [n] = D^-1 (ops 1 - 3), r [n][k] (ops 2, 3).  reading: 0 = the sweep walks the CSR rows in 1024-thread workgroups, 1 = op 3
+ * reads the fixed-width image of the matrix in 256-thread workgroups that keep four row groups in flight, as the cycle does where the
+ * image exists (rows beyond the image's width come from its tail list); ops 1 - 3 take 8 lanes.
+ * fp32 = 1: values, factors and the level's vectors are stored in float - out of ops 0 and 2 and out, out2 of op 1 are float arrays -
+ * while r of op 1 and r, out of op 3 stay double, as in an fp64 solve that runs the cycle in fp32; fp32 = 0: everything double.
+ * The partial sums are double.  out and out2 receive the raw bytes of the result arrays and of `guard` (<= 4096) further elements
+ * behind each, which must still be 0xFF bytes.  Sums keep a fixed order: the same call twice gives the same bytes. */
+int remo_debug_row_ops(remo_ctx_t *ctx, int32_t op, int32_t lanes, int32_t reading, int32_t fp32, int64_t n, int64_t nx, int32_t k, const int32_t *rowptr,
+                       const int32_t *col, const double *val, const double *dinv, double omega, const double *x, const double *r, int32_t nblocks,
+                       int32_t guard, void *out, void *out2);
 /* Where a workgroup of the PCG's two vector launches spends its time before its first stored value (-DREMO_PROBES builds only):
  * on = 1 makes wave 0 of every workgroup of k_pcg_direction_flat and k_pcg_update_tile leave three clocks (on entry | scalars in
  * LDS | at the end) from now on; on = 0 stops that and reports the LAST launch of each kind that was not a no-op:
@@ -152,7 +170,9 @@ int remo_debug_pair_groups_timing(remo_ctx_t *ctx, double *out4);
  *    28: 0 = a row of <p, A p> per patch + a folding launch; 32 runs of the patch's list per wave (product: 4); 33: 0 = every
  *    workgroup walks the largest patch's row count; 34: 1 / 2 = the patch operator as persistent workgroups that prefetch the next patch by
  *    LDS-DMA / through registers (round 4: parity-green, 138 / 111.5 us against 112 at size L: DESIGN.md section 8), 35 their number per XCD
- *    (0 = as many as stay resident); 36 extra operator applications per PCG step (results discarded: what more applications would cost).
+ *    (0 = as many as stay resident); 36 extra operator applications per PCG step (results discarded: what more applications would cost);
+ *    44 lanes per row of R in the multigrid cycle's restrictions (8 / 16 / 32 / 64; product: by R's row lengths); 45: 0 = the cycle's
+ *    last sweep walks CSR rows (no fixed-width image of level 0); 46: 1 = the cycle's last sweep on the image in 1024-thread workgroups.
  *    (Keys 19, 23, 37 and 38 - 512-thread workgroups, a row-major slab, unshared rows straight to y, staggered starts of the patch
  *    kernel - left with their code; DESIGN.md section 8 keeps the measurements.)
  *    remo_debug_patch_phases[_p] and remo_debug_grid_barrier also need that build. */

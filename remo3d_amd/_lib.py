@@ -97,7 +97,7 @@ EXPORTS = ["remo_abi_version", "remo_opts_default", "remo_ctx_create", "remo_ctx
            "remo_solve_job", "remo_batch_create_job", "remo_host_point_shapes", "remo_host_secondary_element", "remo_host_error_facet", "remo_host_pair_element"]
 # include/remo3d_hip_debug.h: probes and tuning knobs (tests, tools, bench.py's `box` record) - not part of the boundary
 DEBUG_EXPORTS = ["remo_debug_stream", "remo_debug_clock", "remo_debug_device", "remo_debug_cache_gather", "remo_debug_xcc", "remo_debug_tune", "remo_debug_patch_phases", "remo_debug_patch_phases_p", "remo_debug_grid_barrier", "remo_debug_sens_timing", "remo_debug_sens_group_timing", "remo_debug_field_timing", "remo_debug_point_location", "remo_debug_secondary_timing", "remo_debug_direction_bytes", "remo_debug_pairs_timing", "remo_debug_pair_groups_timing",
-                 "remo_debug_direction_forms", "remo_debug_vector_heads", "remo_debug_product"]
+                 "remo_debug_direction_forms", "remo_debug_vector_heads", "remo_debug_product", "remo_debug_row_ops"]
 
 # The argument lists of the entries that take one (remo_solve_batch<kind>[_tensor], remo_batch_create[_tensor]) as members of
 # RemoJob: ctx and mesh, JOB_HEAD, then the kind's members - for the solves followed by opts and stats.  load() derives the
@@ -239,6 +239,10 @@ def load():
     if hasattr(L, "remo_debug_product"):
         L.remo_debug_product.restype = C.c_int
         L.remo_debug_product.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64, ip, ip, dp, C.c_int64, ip, ip, dp, ip, ip, dp, ip]
+    if hasattr(L, "remo_debug_row_ops"):
+        L.remo_debug_row_ops.restype = C.c_int
+        L.remo_debug_row_ops.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, ip, ip, dp, dp, C.c_double, dp, dp,
+                                         C.c_int32, C.c_int32, vp, vp]
     _lib = L
     return L
 

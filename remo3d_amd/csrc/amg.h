@@ -18,6 +18,7 @@ constexpr int kAmgDenseMax = 64;   // the coarsest operator is inverted densely 
 // and its transpose R, level vectors [n][k].  T = storage type of values and vectors.
 template <class T> struct AmgLevelT {
     int64_t n = 0, nnz = 0, nnz_p = 0;   // rows and entries of A, entries of P (= of R)
+    int r_lanes = 8;                     // lanes per row of R in the restriction (8 / 16 / 32 / 64, by R's row lengths: amg_build)
     const int32_t *rowptr = nullptr, *col = nullptr;
     const T *val = nullptr, *dinv = nullptr;
     const int32_t *p_rowptr = nullptr, *p_col = nullptr;
@@ -25,6 +26,10 @@ template <class T> struct AmgLevelT {
     const int32_t *r_rowptr = nullptr, *r_col = nullptr;
     const T *r_val = nullptr;
     double omega = 0.0;            // damped Jacobi smoother z += omega D^-1 (r - A z)
+    // level 0 only (amg_level0_image): the fixed-width image of A for the last sweep of the cycle - [n][kEllWidth] columns and values,
+    // [n][2] begin / end of a row's further entries in (col, val); nullptr -> that sweep walks the CSR rows like the others
+    const int32_t *ell_col = nullptr, *ell_tail = nullptr;
+    const T *ell_val = nullptr;
     T *r = nullptr, *z = nullptr, *z2 = nullptr, *t = nullptr;
 };
 
@@ -44,6 +49,18 @@ bool amg_setup(Arena &ar, hipStream_t s, int dim, int64_t nv, const int32_t *row
                AmgT<double> &out, std::string &why);
 // fp32 image of a hierarchy (values converted, patterns shared, own vectors) for the inner solver of the mixed mode
 void amg_to_float(Arena &ar, hipStream_t s, const AmgT<double> &in, int kmax, AmgT<float> &out);
+
+// fixed-width image of level 0's operator (launch_vblock_ell, the kernel the polynomial's image comes from) for the last sweep of the
+// cycle (k_amg_post_image): into h64 (values in fp64) when want64, into h32 (which shares the pattern; values in fp32) when h32 is given
+void amg_level0_image(Arena &ar, hipStream_t s, AmgT<double> &h64, bool want64, AmgT<float> *h32);
+
+// ONE row operation of the cycle on the caller's host arrays (remo_debug_row_ops), in device memory of its own that starts out as 0xFF
+// bytes.  op 0: y = M x with `lanes` lanes per row (restriction form); 1: first half sweep (z, t); 2: second half sweep; 3: the finest
+// level's second half sweep, which also leaves the <r, z> partials of `nblocks` workgroups.  ell: op 3 reads the fixed-width image.
+// fp32: values, factors and level vectors in float (r and the finished z of ops 1 and 3 stay double).  out / out2: the raw bytes of
+// the result arrays with `guard` elements behind them (remo3d_hip_debug.h).  Throws on arguments the kernels could not be trusted with.
+void amg_debug_row_ops(hipStream_t s, int op, int lanes, bool ell, bool fp32, int64_t n, int64_t nx, int k, const int32_t *rowptr, const int32_t *col,
+                       const double *val, const double *dinv, double omega, const double *x, const double *r, int nblocks, int guard, void *out, void *out2);
 
 // ONE sparse product C = X Y of the setup on the caller's host arrays (remo_debug_product): count pass, scan, clamp to `cap` entries, fill
 // pass with 128 or 512 hash slots per row, in device memory of its own that starts out as 0xFF bytes.  crp [nx + 1], cc / cv [cap + 2].

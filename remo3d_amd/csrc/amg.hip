@@ -21,6 +21,7 @@
 
 #include <rocprim/device/device_scan.hpp>
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -401,6 +402,24 @@ __global__ void __launch_bounds__(64 * WAVES) k_tr_sort(int64_t nr, const int32_
     for (int t = lane; t < len; t += 64) { rc[rs + t] = K[t]; rv[rs + t] = V[t]; }
 }
 
+// How long R's rows are, for the lanes per row of the restriction: over[i] = rows with more than 16 << i entries (what 8 << i lanes
+// take in one trip of row_product, two entries in flight per lane), i = 0 .. 2.  Integer counts: any order gives the same result.
+__global__ void __launch_bounds__(256) k_row_classes(int64_t n, const int32_t *__restrict__ rowptr, int32_t *__restrict__ over) {
+    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const int32_t len = i < n ? rowptr[i + 1] - rowptr[i] : 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int cnt = __builtin_popcountll(__builtin_amdgcn_ballot_w64(len > (16 << c)));
+        if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&over[c], cnt);
+    }
+}
+// the narrowest group that takes 95 % of the rows in one trip (the rest pay a further trip each); 64 lanes is a whole wave
+int lanes_for_rows(int64_t rows, const int32_t *over) {
+    for (int c = 0; c < 3; ++c)
+        if (int64_t(over[c]) * 20 <= rows) return 8 << c;
+    return 64;
+}
+
 // ---- dense inverse of the coarsest operator: in-place Gauss-Jordan in LDS, no pivoting (symmetric positive definite) --------
 __global__ void __launch_bounds__(256) k_dense_inverse(int n, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                        const double *__restrict__ val, double *__restrict__ inv, int32_t *flag) {
@@ -470,9 +489,63 @@ __device__ __forceinline__ void row_product(int32_t rs, int32_t re, int sub, con
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int c = 0; c < K; ++c) acc[c] += a[u] * xv[u][c];
+            for (int c = 0; c < K; ++c) acc[c] = fma(a[u], xv[u][c], acc[c]);   // spelled out: a sum must not depend on what the compiler contracts at this K
     }
     TReduce<K, LPR>::run(acc, sub);
+}
+
+// The same row sum from the fixed-width image of level 0 (AmgLevelT::ell_*, k_vblock_ell): a lane's kEllWidth / kLpr entries sit at an
+// address known from the row number, so columns, values and the bounds of the row's further entries go out together and the
+// gathers follow at once - two dependent round trips instead of three.  The padding of a short row is (row, 0): a gather that hits.
+// A lane takes entries sub, sub + kLpr, ... in this order, as row_product does.
+struct EllRow {
+    int32_t j[kEllWidth / kLpr];
+    int32_t rs, re;
+};
+template <class T> __device__ __forceinline__ EllRow ell_request(const AmgLevelT<T> &a, int64_t row, int sub, T (&v)[kEllWidth / kLpr]) {
+    EllRow e;
+    const int64_t eb = row * kEllWidth + sub;
+#pragma unroll
+    for (int u = 0; u < kEllWidth / kLpr; ++u) { e.j[u] = a.ell_col[eb + u * kLpr]; v[u] = a.ell_val[eb + u * kLpr]; }
+    e.rs = a.ell_tail[2 * row]; e.re = a.ell_tail[2 * row + 1];
+    return e;
+}
+template <class T, int K, bool SCALE, class TX>
+__device__ __forceinline__ void ell_gather(const AmgLevelT<T> &a, const EllRow &e, T (&v)[kEllWidth / kLpr], const TX *__restrict__ x,
+                                           T (&xv)[kEllWidth / kLpr][K]) {
+#pragma unroll
+    for (int u = 0; u < kEllWidth / kLpr; ++u) {
+        if (SCALE) v[u] *= a.dinv[e.j[u]];
+        const TX *xr = x + int64_t(e.j[u]) * K;
+#pragma unroll
+        for (int c = 0; c < K; ++c) xv[u][c] = T(xr[c]);
+    }
+}
+template <class T, int K, bool SCALE, class TX>
+__device__ __forceinline__ void ell_sum(const AmgLevelT<T> &a, const EllRow &e, const T (&v)[kEllWidth / kLpr], const T (&xv)[kEllWidth / kLpr][K], int sub,
+                                        const TX *__restrict__ x, T (&acc)[K]) {
+#pragma unroll
+    for (int c = 0; c < K; ++c) acc[c] = T(0);
+#pragma unroll
+    for (int u = 0; u < kEllWidth / kLpr; ++u)
+#pragma unroll
+        for (int c = 0; c < K; ++c) acc[c] = fma(v[u], xv[u][c], acc[c]);
+    for (int32_t p = e.rs + sub; p < e.re; p += kLpr) {   // a row longer than the image: the usual case is none
+        const int32_t j = a.col[p];
+        T av = a.val[p];
+        if (SCALE) av *= a.dinv[j];
+        const TX *xr = x + int64_t(j) * K;
+#pragma unroll
+        for (int c = 0; c < K; ++c) acc[c] = fma(av, T(xr[c]), acc[c]);
+    }
+    TReduce<K, kLpr>::run(acc, sub);
+}
+template <class T, int K, bool SCALE, class TX>
+__device__ __forceinline__ void row_product_ell(const AmgLevelT<T> &a, int64_t row, int sub, const TX *__restrict__ x, T (&acc)[K]) {
+    T v[kEllWidth / kLpr], xv[kEllWidth / kLpr][K];
+    const EllRow e = ell_request<T>(a, row, sub, v);
+    ell_gather<T, K, SCALE, TX>(a, e, v, x, xv);
+    ell_sum<T, K, SCALE, TX>(a, e, v, xv, sub, x, acc);
 }
 
 struct Lane {
@@ -497,7 +570,7 @@ template <class T, int K, class TR = T> __device__ __forceinline__ void op_pre(c
         const int64_t at = row * K + ln.mycol;
         const T w = T(a.omega), ri = T(r[at]);
         a.z[at] = w * a.dinv[row] * ri;
-        a.t[at] = ri - w * acc[0];
+        a.t[at] = fma(-w, acc[0], ri);
     }
 }
 // r_next = R t
@@ -512,19 +585,19 @@ template <class T, int K> __device__ __forceinline__ void op_prolong(const AmgLe
     row_product<T, K, false>(a.p_rowptr[row], a.p_rowptr[row + 1], ln.sub, a.p_col, a.p_val, (const T *)nullptr, zn, acc);
     if (ln.mine) a.z[row * K + ln.mycol] += acc[0];
 }
-// second half: zout = z + w D^-1 (r - A z); LAST (finest level): zout / dinv is stored, the return value is r * zout
-template <class T, int K, bool LAST, class TR = T>
-__device__ __forceinline__ double op_post(const AmgLevelT<T> &a, const TR *__restrict__ r, TR *__restrict__ zout, int64_t row, const Lane &ln) {
+// second half: zout = z + w D^-1 (r - A z); LAST (finest level): zout / dinv is stored, the return value is dot + r * zout
+template <class T, int K, bool LAST, class TR = T, bool ELL = false>
+__device__ __forceinline__ double op_post(const AmgLevelT<T> &a, const TR *__restrict__ r, TR *__restrict__ zout, int64_t row, const Lane &ln, double dot = 0.0) {
     T acc[K];
-    row_product<T, K, false>(a.rowptr[row], a.rowptr[row + 1], ln.sub, a.col, a.val, (const T *)nullptr, (const T *)a.z, acc);
-    double dot = 0.0;
+    if constexpr (ELL) row_product_ell<T, K, false, T>(a, row, ln.sub, (const T *)a.z, acc);
+    else row_product<T, K, false>(a.rowptr[row], a.rowptr[row + 1], ln.sub, a.col, a.val, (const T *)nullptr, (const T *)a.z, acc);
     if (ln.mine) {
         const int64_t at = row * K + ln.mycol;
         const TR rr = r[at];
         const T ri = T(rr), di = a.dinv[row];
-        const T zn = a.z[at] + T(a.omega) * di * (ri - acc[0]);
+        const T zn = fma(T(a.omega) * di, ri - acc[0], a.z[at]);
         zout[at] = TR(LAST ? zn / di : zn);
-        dot = double(rr) * double(zn);
+        dot = fma(double(rr), double(zn), dot);
     }
     return dot;
 }
@@ -538,12 +611,13 @@ __global__ void __launch_bounds__(256) k_amg_pre(AmgLevelT<T> a, const TR *__res
     const int64_t row = int64_t(blockIdx.x) * kRpb + threadIdx.x / kLpr;
     if (row < a.n) op_pre<T, K, TR>(a, r, row, ln);
 }
-template <class T, int K>
+// LPR lanes per row of R (AmgLevelT::r_lanes): 256 / LPR rows per workgroup
+template <class T, int K, int LPR>
 __global__ void __launch_bounds__(256) k_amg_restrict(AmgLevelT<T> a, int64_t n_next, T *__restrict__ rn, const double *scal, int step) {
     if (amg_done(scal, step)) return;
-    const Lane ln = lane_of<K>(threadIdx.x);
-    const int64_t row = int64_t(blockIdx.x) * kRpb + threadIdx.x / kLpr;
-    if (row < n_next) op_restrict<T, K>(a, rn, row, ln);
+    const Lane ln = lane_of<K, LPR>(threadIdx.x);
+    const int64_t row = int64_t(blockIdx.x) * (256 / LPR) + threadIdx.x / LPR;
+    if (row < n_next) op_restrict<T, K, LPR>(a, rn, row, ln);
 }
 template <class T, int K>
 __global__ void __launch_bounds__(256) k_amg_prolong(AmgLevelT<T> a, const T *__restrict__ zn, const double *scal, int step) {
@@ -552,9 +626,25 @@ __global__ void __launch_bounds__(256) k_amg_prolong(AmgLevelT<T> a, const T *__
     const int64_t row = int64_t(blockIdx.x) * kRpb + threadIdx.x / kLpr;
     if (row < a.n) op_prolong<T, K>(a, zn, row, ln);
 }
+// <r, z> partials of a workgroup of NW waves, one per column, in a fixed order: the lanes of a wave, then the waves
+template <int K, int NW> __device__ __forceinline__ void post_partials(const Lane &ln, double dot, double *__restrict__ part) {
+    __shared__ double smem[NW * K];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const double x = wave_sum((ln.mine && k == ln.mycol) ? dot : 0.0);
+        if (lane == 0) smem[wave * K + k] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < K) {
+        double t = 0.0;
+        for (int w = 0; w < NW; ++w) t += smem[w * K + threadIdx.x];
+        part[blockIdx.x * K + threadIdx.x] = t;
+    }
+}
 // (prolongation folded into this sweep - P z_next formed on the fly for the row and its neighbours - was measured: 24.7 us
 // against 5.3 + 12 at 80 k rows, the inner loops over P's rows are chains of dependent loads)
-template <class T, int K, bool LAST, int THREADS, class TR>
+template <class T, int K, bool LAST, int THREADS, class TR, bool ELL = false>
 __global__ void __launch_bounds__(THREADS) k_amg_post(AmgLevelT<T> a, const TR *__restrict__ r, TR *__restrict__ zout,
                                                      double *__restrict__ part, const double *scal, int step) {
     if (amg_done(scal, step)) return;
@@ -562,23 +652,51 @@ __global__ void __launch_bounds__(THREADS) k_amg_post(AmgLevelT<T> a, const TR *
     constexpr int RPB = THREADS / kLpr;
     double dot = 0.0;
     for (int64_t row = int64_t(blockIdx.x) * RPB + threadIdx.x / kLpr; row < a.n; row += int64_t(gridDim.x) * RPB)
-        dot += op_post<T, K, LAST, TR>(a, r, zout, row, ln);
-    if (LAST) {   // <r, z> partials of the workgroup, one per column
-        constexpr int NW = THREADS / 64;
-        __shared__ double smem[NW * K];
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        dot = op_post<T, K, LAST, TR, ELL>(a, r, zout, row, ln, dot);
+    if (LAST) post_partials<K, THREADS / 64>(ln, dot, part);
+}
+
+// The finest level's second half sweep on the fixed-width image: the same `nblocks` partial rows, but 256 threads per workgroup (a
+// 1024-thread workgroup needs 16 free wave slots on one CU at once, beside the resident operator workgroups of the other
+// contexts).  A workgroup walks its 128 rows as four row groups.  With the image no address depends on a load, so the requests of all
+// four groups go out before any is used, then all their gathers: the four groups cost one chain of round trips, not four.
+constexpr int kPostGroups = 4, kPostRows = kPostGroups * kRpb;
+template <class T, int K, class TR>
+__global__ void __launch_bounds__(256) k_amg_post_image(AmgLevelT<T> a, const TR *__restrict__ r, TR *__restrict__ zout, double *__restrict__ part,
+                                                        const double *scal, int step) {
+    if (amg_done(scal, step)) return;
+    constexpr int NE = kEllWidth / kLpr;
+    const Lane ln = lane_of<K>(threadIdx.x);
+    double dot = 0.0;
+    for (int64_t row0 = int64_t(blockIdx.x) * kPostRows + threadIdx.x / kLpr; row0 < a.n; row0 += int64_t(gridDim.x) * kPostRows) {
+        int64_t row[kPostGroups];
+        EllRow e[kPostGroups];
+        T v[kPostGroups][NE], xv[kPostGroups][NE][K], zi[kPostGroups], di[kPostGroups];
+        TR rr[kPostGroups];
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const double x = wave_sum((ln.mine && k == ln.mycol) ? dot : 0.0);
-            if (lane == 0) smem[wave * K + k] = x;
+        for (int g = 0; g < kPostGroups; ++g) {   // a group beyond the last row repeats the first one's reads and stores nothing
+            row[g] = row0 + g * kRpb < a.n ? row0 + g * kRpb : row0;
+            e[g] = ell_request<T>(a, row[g], ln.sub, v[g]);
+            rr[g] = TR(0); zi[g] = T(0); di[g] = T(1);
+            if (ln.mine) {
+                const int64_t at = row[g] * K + ln.mycol;
+                rr[g] = r[at]; zi[g] = a.z[at]; di[g] = a.dinv[row[g]];
+            }
         }
-        __syncthreads();
-        if (threadIdx.x < K) {
-            double t = 0.0;
-            for (int w = 0; w < NW; ++w) t += smem[w * K + threadIdx.x];
-            part[blockIdx.x * K + threadIdx.x] = t;
+#pragma unroll
+        for (int g = 0; g < kPostGroups; ++g) ell_gather<T, K, false, T>(a, e[g], v[g], (const T *)a.z, xv[g]);
+#pragma unroll
+        for (int g = 0; g < kPostGroups; ++g) {
+            T acc[K];
+            ell_sum<T, K, false, T>(a, e[g], v[g], xv[g], ln.sub, (const T *)a.z, acc);
+            if (ln.mine && row0 + g * kRpb < a.n) {
+                const T zn = fma(T(a.omega) * di[g], T(rr[g]) - acc[0], zi[g]);
+                zout[row[g] * K + ln.mycol] = TR(zn / di[g]);
+                dot = fma(double(rr[g]), double(zn), dot);
+            }
         }
     }
+    post_partials<K, 4>(ln, dot, part);
 }
 
 template <class T, int K>
@@ -595,19 +713,19 @@ constexpr int kTailLevels = 3;
 constexpr int kTailRows = 128;     // levels of at most this many rows go into the tail kernel (the coarsest one always)
 template <class T> struct AmgTailT {
     int levels;
-    AmgLevelT<T> up;               // the level above the tail: its R and t feed the first restriction (16 lanes per row: R's rows are long)
+    AmgLevelT<T> up;               // the level above the tail: its R and t feed the first restriction (R's rows are long: 16 to 64 lanes per row)
     AmgLevelT<T> lev[kTailLevels];
     const T *inv;
 };
-template <class T, int K>
+template <class T, int K, int LPR0>   // LPR0: lanes per row of the first restriction (the r_lanes of the level above the tail, 16 at least)
 __global__ void __launch_bounds__(1024) k_amg_tail(AmgTailT<T> A, const double *scal, int step) {
     if (amg_done(scal, step)) return;
     const Lane ln = lane_of<K>(threadIdx.x);
     const int g = threadIdx.x / kLpr, ng = 1024 / kLpr;
     const int L = A.levels;
     {
-        const Lane l16 = lane_of<K, 16>(threadIdx.x);
-        for (int64_t row = threadIdx.x / 16; row < A.lev[0].n; row += 1024 / 16) op_restrict<T, K, 16>(A.up, A.lev[0].r, row, l16);
+        const Lane l0 = lane_of<K, LPR0>(threadIdx.x);
+        for (int64_t row = threadIdx.x / LPR0; row < A.lev[0].n; row += 1024 / LPR0) op_restrict<T, K, LPR0>(A.up, A.lev[0].r, row, l0);
         __syncthreads();
     }
     for (int l = 0; l + 1 < L; ++l) {
@@ -634,6 +752,22 @@ __global__ void __launch_bounds__(1024) k_amg_tail(AmgTailT<T> A, const double *
 }
 
 int grid_rows(int64_t n, int per_block) { return int((n + per_block - 1) / per_block); }
+
+template <class T> bool level_image(const AmgLevelT<T> &a) { return a.ell_col && a.ell_tail && a.ell_val; }
+// fn(int_c<LPR>): a kernel's lanes per row from the level's choice
+template <int MIN = 8, class F> void for_lanes(int lanes, F &&fn) {
+    if (lanes >= 64) fn(int_c<64>{});
+    else if (lanes >= 32) fn(int_c<32>{});
+    else if (lanes >= 16 || MIN >= 16) fn(int_c<16>{});
+    else if constexpr (MIN < 16) fn(int_c<8>{});
+}
+#ifdef REMO_PROBES
+template <class T> int restrict_lanes(const AmgLevelT<T> &a) { return g_tune.amg_r_lanes ? g_tune.amg_r_lanes : a.r_lanes; }
+bool post_wide() { return g_tune.amg_post_wide != 0; }
+#else
+template <class T> int restrict_lanes(const AmgLevelT<T> &a) { return a.r_lanes; }
+constexpr bool post_wide() { return false; }
+#endif
 
 // out[0 .. n] = exclusive prefix sums of cnt[0 .. n) (out[n] = total; cnt[n] must be addressable, its value does not matter);
 // the temporary storage comes from the scratch end of the arena and is released by the caller's mark
@@ -681,7 +815,33 @@ void spgemm_async(Arena &ar, bool permanent, hipStream_t s, const Csr &X, const 
 
 std::atomic<int> g_product_hint[2][kAmgMaxLevels][3];   // [2D | 3D matrices][level][S P0, A P, R (A P)]; 0 / 1: 128 slots, 2: 512
 std::atomic<int> g_ap_room[2];                          // log2 of the extra room of A P beyond 4 nnz(A) (0 .. 3)
-constexpr int kFlagSlots = 64;                          // [0] setup flags, [8 + 3 level + product] product flags
+constexpr int kFlagSlots = 64;                          // [0] setup flags, [8 + 3 level + product] product flags, [32 + 4 level + class] row classes of R
+constexpr int kClassSlot = 32;
+static_assert(8 + 3 * kAmgMaxLevels <= kClassSlot && kClassSlot + 4 * kAmgMaxLevels <= kFlagSlots, "flag slots overlap");
+
+// REMO_AMG_DEBUG: per level the row lengths of A, P and R (minimum, median, 95 %, maximum) and the lanes chosen for R - a read-back
+void print_row_lengths(hipStream_t s, const AmgT<double> &H) {
+    auto stats = [&](const char *name, int l, const int32_t *d_rowptr, int64_t n) {
+        if (!d_rowptr || n <= 0) return;
+        std::vector<int32_t> rp(size_t(n) + 1);
+        HIP_TRY(hipMemcpyAsync(rp.data(), d_rowptr, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        std::vector<int32_t> len(static_cast<size_t>(n));
+        for (int64_t i = 0; i < n; ++i) len[size_t(i)] = rp[size_t(i) + 1] - rp[size_t(i)];
+        std::sort(len.begin(), len.end());
+        fprintf(stderr, "amg level %d %s: %lld rows, entries per row min %d median %d 95 %% %d max %d\n", l, name, (long long)n, len.front(),
+                len[size_t(n / 2)], len[size_t((n * 95) / 100)], len.back());
+    };
+    for (int l = 0; l < H.levels; ++l) {
+        const AmgLevelT<double> &a = H.lev[l];
+        stats("A", l, a.rowptr, a.n);
+        if (l + 1 < H.levels) {
+            stats("P", l, a.p_rowptr, a.n);
+            stats("R", l, a.r_rowptr, H.lev[l + 1].n);
+            fprintf(stderr, "amg level %d R: %d lanes per row\n", l, a.r_lanes);
+        }
+    }
+}
 
 // one attempt: 0 = built, 1 = a product outgrew its tables or arrays (the hints have been raised: try again), -1 = failed
 int amg_build(Arena &ar, hipStream_t s, int hs, int64_t nv, const int32_t *rowptr, const int32_t *col, const double *val, int kmax, AmgT<double> &H,
@@ -821,6 +981,7 @@ int amg_build(Arena &ar, hipStream_t s, int hs, int64_t nv, const int32_t *rowpt
             hipLaunchKernelGGL(k_tr_fill, dim3(g), dim3(256), 0, s, n, P.rowptr, P.col, P.val, R.rowptr, cursor, R.col, R.val);
             hipLaunchKernelGGL((k_tr_sort<0, kTrMax, 4>), dim3(grid_rows(nc, 4)), dim3(256), 0, s, nc, R.rowptr, R.col, R.val, d_flag);
             hipLaunchKernelGGL((k_tr_sort<kTrMax, kTrMaxLong, 1>), dim3(grid_rows(nc, 1)), dim3(64), 0, s, nc, R.rowptr, R.col, R.val, d_flag);
+            hipLaunchKernelGGL(k_row_classes, dim3(grid_rows(nc, 256)), dim3(256), 0, s, nc, R.rowptr, d_flag + kClassSlot + 4 * L);
         }
         lv.r_rowptr = R.rowptr; lv.r_col = R.col; lv.r_val = R.val;
         // ---- A' = R (A P): A P in scratch with room for (4 << room) nnz(A) entries, A' at most as many entries as A ----
@@ -840,7 +1001,11 @@ int amg_build(Arena &ar, hipStream_t s, int hs, int64_t nv, const int32_t *rowpt
     const int verdict = check(L);
     if (verdict != 0) return verdict;
     H.lev[L].nnz = h_nnz_a[L];
-    for (int l = 0; l < L; ++l) H.lev[l].nnz_p = h_nnz_p[l];
+    for (int l = 0; l < L; ++l) {
+        H.lev[l].nnz_p = h_nnz_p[l];
+        H.lev[l].r_lanes = lanes_for_rows(H.lev[l + 1].n, h_flags + kClassSlot + 4 * l);
+    }
+    if (getenv("REMO_AMG_DEBUG")) print_row_lengths(s, H);
     H.launches = 4 * (H.levels - 1);   // pre, restrict, prolong, post per level; the tail kernel stands for the last restriction + dense solve
     H.kmax = kmax;
     return 0;
@@ -923,6 +1088,111 @@ void amg_debug_product(hipStream_t s, int slots, int64_t cap, int64_t nx, const 
     HIP_TRY(hipStreamSynchronize(s));
 }
 
+namespace {
+template <class T>
+void debug_row_ops(hipStream_t s, int op, int lanes, bool ell, int64_t n, int64_t nx, int k, const int32_t *rowptr, const int32_t *col, const double *val,
+                   const double *dinv, double omega, const double *x, const double *r, int nblocks, int guard, void *out, void *out2) {
+    const size_t nnz = size_t(rowptr[n]), nk = size_t(n) * k, nxk = size_t(nx) * k, cells = size_t(n) * kEllWidth + 8;
+    const size_t bytes = 4 * (size_t(n) + 2 + nnz + 2 + cells + 2 * size_t(n) + 8) + 8 * (2 * nnz + 4 + size_t(n) + nxk + 4 * nk + 2 * cells) +
+                         8 * (size_t(nblocks) * k + 3 * size_t(guard)) + 256 * 32;
+    DeviceTemp tmp;
+    Arena ar;
+    ar.base = tmp.alloc<char>(bytes);
+    ar.cap = bytes;
+    HIP_TRY(hipMemsetAsync(ar.base, 0xFF, bytes, s));   // what the operation does not write stays 0xFF
+    std::vector<std::vector<char>> keep;                // the converted host arrays live until the synchronisation below
+    auto put = [&](auto tag, const double *src, size_t count) {   // a device array of `count` elements of the tag's type from host doubles
+        using D = decltype(tag);
+        D *d = ar.lo<D>(count + 2);
+        keep.emplace_back(sizeof(D) * (count + 1));
+        D *h = reinterpret_cast<D *>(keep.back().data());
+        for (size_t i = 0; i < count; ++i) h[i] = D(src[i]);
+        if (count) HIP_TRY(hipMemcpyAsync(d, h, sizeof(D) * count, hipMemcpyHostToDevice, s));
+        return d;
+    };
+    int32_t *d_rp = ar.lo<int32_t>(size_t(n) + 2), *d_col = ar.lo<int32_t>(nnz + 2);
+    HIP_TRY(hipMemcpyAsync(d_rp, rowptr, sizeof(int32_t) * (size_t(n) + 1), hipMemcpyHostToDevice, s));
+    if (nnz) HIP_TRY(hipMemcpyAsync(d_col, col, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, s));
+    AmgLevelT<T> a;
+    a.n = n; a.nnz = int64_t(nnz); a.omega = omega;
+    const T *d_val = put(T(0), val, nnz);
+    a.rowptr = d_rp; a.col = d_col; a.val = d_val;
+    if (op != 0) a.dinv = put(T(0), dinv, size_t(n));
+    if (ell) {
+        const double *d_val64 = put(double(0), val, nnz);
+        int32_t *ecol = ar.lo<int32_t>(cells), *tail = ar.lo<int32_t>(size_t(n) * 2 + 8);
+        T *ev = ar.lo<T>(cells);
+        double *e64 = nullptr;
+        float *e32 = nullptr;
+        if constexpr (sizeof(T) == 8) e64 = ev; else e32 = ev;
+        launch_vblock_ell(n, d_rp, d_col, d_val64, ecol, tail, e64, e32, s);
+        a.ell_col = ecol; a.ell_tail = tail; a.ell_val = ev;
+    }
+    // the result arrays last, each with its guard behind it
+    auto result = [&](auto tag, size_t count) { return ar.lo<decltype(tag)>(count + size_t(guard)); };
+    auto fetch = [&](void *dst, const void *src, size_t elem, size_t count) {
+        HIP_TRY(hipMemcpyAsync(dst, src, elem * (count + size_t(guard)), hipMemcpyDeviceToHost, s));
+    };
+    const double *scal = nullptr;
+    for_k(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        if (op == 0) {
+            a.r_rowptr = d_rp; a.r_col = d_col; a.r_val = d_val;
+            a.t = put(T(0), x, nxk);
+            T *rn = result(T(0), nk);
+            for_lanes(lanes, [&](auto lc) {
+                constexpr int LPR = decltype(lc)::value;
+                launch256(k_amg_restrict<T, K, LPR>, grid_rows(n, 256 / LPR), s, a, n, rn, scal, 0);
+            });
+            fetch(out, rn, sizeof(T), nk);
+        } else if (op == 1) {
+            const double *d_r = put(double(0), x, nk);
+            a.z = result(T(0), nk); a.t = result(T(0), nk);
+            launch256(k_amg_pre<T, K, double>, grid_rows(n, kRpb), s, a, d_r, scal, 0);
+            fetch(out, a.z, sizeof(T), nk);
+            fetch(out2, a.t, sizeof(T), nk);
+        } else if (op == 2) {
+            a.z = put(T(0), x, nk);
+            const T *d_r = put(T(0), r, nk);
+            T *zout = result(T(0), nk);
+            launch256(k_amg_post<T, K, false, 256, T>, grid_rows(n, kRpb), s, a, d_r, zout, (double *)nullptr, scal, 0);
+            fetch(out, zout, sizeof(T), nk);
+        } else {
+            a.z = put(T(0), x, nk);
+            const double *d_r = put(double(0), r, nk);
+            double *zout = result(double(0), nk), *part = result(double(0), size_t(nblocks) * k);
+            if (ell) launch256(k_amg_post_image<T, K, double>, nblocks, s, a, d_r, zout, part, scal, 0);
+            else hipLaunchKernelGGL((k_amg_post<T, K, true, 1024, double>), dim3(nblocks), dim3(1024), 0, s, a, d_r, zout, part, scal, 0);
+            fetch(out, zout, sizeof(double), nk);
+            fetch(out2, part, sizeof(double), size_t(nblocks) * k);
+        }
+    });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+}
+}  // namespace
+
+void amg_debug_row_ops(hipStream_t s, int op, int lanes, bool ell, bool fp32, int64_t n, int64_t nx, int k, const int32_t *rowptr, const int32_t *col,
+                       const double *val, const double *dinv, double omega, const double *x, const double *r, int nblocks, int guard, void *out, void *out2) {
+    if (op < 0 || op > 3) throw std::runtime_error("amg_debug_row_ops: op 0 .. 3");
+    if (lanes != 8 && lanes != 16 && lanes != 32 && lanes != 64) throw std::runtime_error("amg_debug_row_ops: 8, 16, 32 or 64 lanes");
+    if (op != 0 && lanes != 8) throw std::runtime_error("amg_debug_row_ops: the sweeps take 8 lanes per row");
+    if (ell && op != 3) throw std::runtime_error("amg_debug_row_ops: only the finest level's second half sweep (op 3) reads the fixed-width image");
+    if (n < 1 || nx < 1 || n > (1 << 22) || nx > (1 << 22) || k < 1 || k > 8 || guard < 0 || guard > 4096) throw std::runtime_error("amg_debug_row_ops: sizes out of range");
+    if (op != 0 && nx != n) throw std::runtime_error("amg_debug_row_ops: a sweep needs a square matrix");
+    if (op == 3 && (nblocks < 1 || nblocks > kMaxPartialBlocks / 2)) throw std::runtime_error("amg_debug_row_ops: workgroups out of range");
+    if (op != 3) nblocks = 0;
+    if (!x || (op != 0 && !dinv) || (op >= 2 && !r) || (op == 1 || op == 3 ? !out2 : false)) throw std::runtime_error("amg_debug_row_ops: an array is missing");
+    // the kernels trust their inputs: row pointers that ascend from 0, columns that name rows of x
+    if (rowptr[0] != 0) throw std::runtime_error("amg_debug_row_ops: row pointers must ascend from 0");
+    for (int64_t i = 0; i < n; ++i)
+        if (rowptr[i + 1] < rowptr[i] || rowptr[i + 1] > (1 << 26)) throw std::runtime_error("amg_debug_row_ops: row pointers must ascend from 0");
+    for (int32_t p = 0; p < rowptr[n]; ++p)
+        if (col[p] < 0 || col[p] >= nx) throw std::runtime_error("amg_debug_row_ops: a column names no row of x");
+    if (fp32) debug_row_ops<float>(s, op, lanes, ell, n, nx, k, rowptr, col, val, dinv, omega, x, r, nblocks, guard, out, out2);
+    else debug_row_ops<double>(s, op, lanes, ell, n, nx, k, rowptr, col, val, dinv, omega, x, r, nblocks, guard, out, out2);
+}
+
 void amg_to_float(Arena &ar, hipStream_t s, const AmgT<double> &in, int kmax, AmgT<float> &out) {
     auto conv = [&](const double *src, size_t count) {
         float *dst = ar.lo<float>(count + 4);
@@ -943,7 +1213,7 @@ void amg_to_float(Arena &ar, hipStream_t s, const AmgT<double> &in, int kmax, Am
         if (l > 0) b.r = ar.lo<float>(size_t(a.n) * kmax + 4);
         if (l + 1 < in.levels) {
             b.p_rowptr = a.p_rowptr; b.p_col = a.p_col; b.r_rowptr = a.r_rowptr; b.r_col = a.r_col;
-            b.nnz_p = a.nnz_p;
+            b.nnz_p = a.nnz_p; b.r_lanes = a.r_lanes;
             b.p_val = conv(a.p_val, size_t(a.nnz_p));
             b.r_val = conv(a.r_val, size_t(a.nnz_p));
         }
@@ -952,19 +1222,36 @@ void amg_to_float(Arena &ar, hipStream_t s, const AmgT<double> &in, int kmax, Am
     out.inv = conv(in.inv, size_t(nc * nc));
 }
 
+void amg_level0_image(Arena &ar, hipStream_t s, AmgT<double> &h64, bool want64, AmgT<float> *h32) {
+    AmgLevelT<double> &a = h64.lev[0];
+    if (h64.levels < 2 || a.n <= 0 || (!want64 && !h32)) return;
+    const size_t cells = size_t(a.n) * kEllWidth + 8;
+    int32_t *ecol = ar.lo<int32_t>(cells), *tail = ar.lo<int32_t>(size_t(a.n) * 2 + 8);
+    double *e64 = want64 ? ar.lo<double>(cells) : nullptr;
+    float *e32 = h32 ? ar.lo<float>(cells) : nullptr;
+    launch_vblock_ell(a.n, a.rowptr, a.col, a.val, ecol, tail, e64, e32, s);   // level 0 is the compact block: every column is a vertex
+    if (want64) { a.ell_col = ecol; a.ell_tail = tail; a.ell_val = e64; }
+    if (h32) { AmgLevelT<float> &b = h32->lev[0]; b.ell_col = ecol; b.ell_tail = tail; b.ell_val = e32; }
+}
+
 template <class T, class TR> void launch_amg_cycle(const AmgT<T> &H, int k, int step, const TR *r, TR *cz, double *part, int nblocks, const double *scal, hipStream_t s) {
     const int L = H.levels;
     auto rows_grid = [&](int64_t n) { return int((n + kRpb - 1) / kRpb); };
     // the levels from `lt` on go into the single-workgroup kernel (always at least the coarsest one)
     int lt = L - 1;
     while (lt > 1 && H.lev[lt - 1].n <= kTailRows && L - (lt - 1) <= kTailLevels) --lt;
+    const bool image = level_image(H.lev[0]);   // level 0's last sweep reads the fixed-width image if the builder made one
     for_k(k, [&](auto kc) {
         constexpr int K = decltype(kc)::value;
         for (int l = 0; l < lt; ++l) {   // down
             const AmgLevelT<T> &a = H.lev[l], &b = H.lev[l + 1];
-            if (l == 0) hipLaunchKernelGGL((k_amg_pre<T, K, TR>), dim3(rows_grid(a.n)), dim3(256), 0, s, a, r, scal, step);
-            else hipLaunchKernelGGL((k_amg_pre<T, K, T>), dim3(rows_grid(a.n)), dim3(256), 0, s, a, (const T *)a.r, scal, step);
-            if (l + 1 < lt) hipLaunchKernelGGL((k_amg_restrict<T, K>), dim3(rows_grid(b.n)), dim3(256), 0, s, a, b.n, b.r, scal, step);
+            if (l == 0) launch256(k_amg_pre<T, K, TR>, rows_grid(a.n), s, a, r, scal, step);   // (from the image: 8.9 us as from the CSR rows, profiles/cycle_rows_ab.txt)
+            else launch256(k_amg_pre<T, K, T>, rows_grid(a.n), s, a, (const T *)a.r, scal, step);
+            if (l + 1 < lt)
+                for_lanes(restrict_lanes(a), [&](auto lc) {
+                    constexpr int LPR = decltype(lc)::value;
+                    launch256(k_amg_restrict<T, K, LPR>, grid_rows(b.n, 256 / LPR), s, a, b.n, b.r, scal, step);
+                });
         }
         {
             AmgTailT<T> tail;
@@ -972,13 +1259,21 @@ template <class T, class TR> void launch_amg_cycle(const AmgT<T> &H, int k, int 
             tail.up = H.lev[lt - 1];
             for (int l = lt; l < L; ++l) tail.lev[l - lt] = H.lev[l];
             tail.inv = H.inv;
-            hipLaunchKernelGGL((k_amg_tail<T, K>), dim3(1), dim3(1024), 0, s, tail, scal, step);
+            for_lanes<16>(restrict_lanes(tail.up), [&](auto lc) {
+                hipLaunchKernelGGL((k_amg_tail<T, K, decltype(lc)::value>), dim3(1), dim3(1024), 0, s, tail, scal, step);
+            });
         }
         for (int l = lt - 1; l >= 0; --l) {   // up
             const AmgLevelT<T> &a = H.lev[l], &b = H.lev[l + 1];
             hipLaunchKernelGGL((k_amg_prolong<T, K>), dim3(rows_grid(a.n)), dim3(256), 0, s, a, (const T *)b.z2, scal, step);
-            if (l == 0)   // the launch that leaves the partial sums is held to `nblocks` workgroups: 128 rows each
-                hipLaunchKernelGGL((k_amg_post<T, K, true, 1024, TR>), dim3(nblocks), dim3(1024), 0, s, a, r, cz, part, scal, step);
+            if (l == 0 && image && !post_wide())   // the launch that leaves the partial sums is held to `nblocks` workgroups: 128 rows each
+                launch256(k_amg_post_image<T, K, TR>, nblocks, s, a, r, cz, part, scal, step);
+#ifdef REMO_PROBES
+            else if (l == 0 && image)   // key 46: the image in 1024-thread workgroups, a row group each
+                hipLaunchKernelGGL((k_amg_post<T, K, true, 1024, TR, true>), dim3(nblocks), dim3(1024), 0, s, a, r, cz, part, scal, step);
+#endif
+            else if (l == 0)
+                hipLaunchKernelGGL((k_amg_post<T, K, true, 1024, TR, false>), dim3(nblocks), dim3(1024), 0, s, a, r, cz, part, scal, step);
             else
                 hipLaunchKernelGGL((k_amg_post<T, K, false, 256, T>), dim3(rows_grid(a.n)), dim3(256), 0, s, a, (const T *)a.r, a.z2, (double *)nullptr, scal, step);
         }

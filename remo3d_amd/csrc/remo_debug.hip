@@ -415,6 +415,19 @@ int remo_debug_product(remo_ctx_t *ctx, int32_t slots, int64_t cap, int64_t nx, 
     }
 }
 
+int remo_debug_row_ops(remo_ctx_t *ctx, int32_t op, int32_t lanes, int32_t reading, int32_t fp32, int64_t n, int64_t nx, int32_t k, const int32_t *rowptr,
+                       const int32_t *col, const double *val, const double *dinv, double omega, const double *x, const double *r, int32_t nblocks,
+                       int32_t guard, void *out, void *out2) {
+    if (!ctx || !rowptr || !col || !val || !x || !out || (reading != 0 && reading != 1)) return REMO_ERR_ARG;
+    try {
+        HIP_TRY(hipSetDevice(ctx->device));
+        amg_debug_row_ops(ctx->stream, op, lanes, reading == 1, fp32 != 0, n, nx, k, rowptr, col, val, dinv, omega, x, r, nblocks, guard, out, out2);
+        return REMO_OK;
+    } catch (const std::exception &ex) {
+        return fail(ctx, REMO_ERR_DEVICE, ex.what());
+    }
+}
+
 #ifdef REMO_PROBES
 namespace {
 // remo_debug_vector_heads: the stamp rows of both launches while the probe is on.  One buffer for the process, on the device of the context
@@ -512,6 +525,9 @@ const TuneKey kTuneKeys[] = {
     {34, &Tune::patch_persist, [](int v) { return (v == 1 || v == 2) ? v : 0; }},
     {35, &Tune::patch_wgs_per_xcd, [](int v) { return v > 0 ? v : 0; }},
     {36, &Tune::extra_apply},
+    {44, &Tune::amg_r_lanes, [](int v) { return (v == 8 || v == 16 || v == 32 || v == 64) ? v : 0; }},
+    {45, &Tune::amg_image},
+    {46, &Tune::amg_post_wide},
 #endif
 };
 }  // namespace

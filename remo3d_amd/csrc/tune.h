@@ -44,6 +44,9 @@ struct Tune {
     int patch_persist = 0;       // key 34 (probe builds): 1 / 2 = persistent forms (patch_persist.inc), 0 = k_patch_apply (default); stored as 0, 1 or 2
     int patch_wgs_per_xcd = 0;   // key 35 (probe builds): workgroups per XCD of the persistent forms (0 = as many as stay resident); tests make small meshes walk several patches per workgroup; stored >= 0
     int extra_apply = 0;         // key 36 (probe builds): extra operator applications (apply + shared-row sums, results discarded) per PCG step: what a step with more applications would cost
+    int amg_r_lanes = 0;         // key 44 (probe builds): lanes per row of R in the cycle's restrictions, 8 / 16 / 32 / 64 (0 = by R's row lengths, AmgLevelT::r_lanes)
+    int amg_image = 1;           // key 45 (probe builds): 0 = no fixed-width image of the cycle's level 0, its last sweep walks CSR rows in 1024-thread workgroups (batches built afterwards)
+    int amg_post_wide = 0;       // key 46 (probe builds): 1 = the cycle's last sweep on the image in 1024-thread workgroups, a row group each (default 0: 256 threads, four row groups in flight)
 #endif
 };
 extern Tune g_tune;

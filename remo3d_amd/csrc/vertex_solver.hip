@@ -519,6 +519,12 @@ static std::pair<int, double> cheb_defaults(int dim, int64_t nvfree) {
     return {deg2, std::min(2400.0, std::max(600.0, 600.0 * nv2 * 1.25))};
 }
 
+#ifdef REMO_PROBES
+static bool amg_wants_image() { return g_tune.amg_image != 0; }   // key 45
+#else
+static constexpr bool amg_wants_image() { return true; }
+#endif
+
 constexpr int64_t kCompactPerRow = 48;   // capacity of the compact copy per vertex (3D P1 rows hold ~15 entries; a copy that does not fit is not used)
 
 size_t VertexSolverBuilder::arena_bytes(int dim, int64_t nv, size_t kmax, bool want_amg, bool mixed) {
@@ -528,6 +534,7 @@ size_t VertexSolverBuilder::arena_bytes(int dim, int64_t nv, size_t kmax, bool w
     need += size_t(nv + 64) * kEllWidth * 12 + size_t(nv + 64) * 8;  // accept: its fixed-width image: ell_col, ell_val (or ell_val32); ell_tail
     need += size_t(nv + 64) * (4 * 4 * kmax + 8);                    // accept: fp32 chain of the fp64 solve: z32, res32, d32[0], d32[1]; dinv32
     if (want_amg) need += size_t(nv + 64) * (dim == 2 ? 1536 : 3072) * 2 + (1 << 20);   // accept: multigrid hierarchy of the block + its scratch (amg_setup, amg_to_float)
+    if (want_amg && dim == 3) need += size_t(nv + 64) * kEllWidth * 16 + size_t(nv + 64) * 8;   // accept: image of its level 0 (amg_level0_image): columns, fp64 and fp32 values; tail
     if (mixed) need += size_t(nv + 64) * 200 * 8 + size_t(nv + 64) * 4 * 4 * kmax + (1 << 16);   // to_float: fp32 sq_a, sq_b; z, res, d[0], d[1]
     return need;
 }
@@ -619,6 +626,10 @@ int VertexSolverBuilder::accept(Arena &ar, hipStream_t s, const VertexSolverInpu
         amg32_ready = true;
         if (in.o.precision == 0) vs.amg32 = &amg32;
     }
+    // fixed-width image of the hierarchy's level 0 for the cycle's last sweep (3D, like the polynomial's image): in the storage
+    // type the cycle will run in - an fp64 solve whose cycle runs in fp32 needs no fp64 image, and the mixed mode cycles only the fp32
+    // hierarchy (run_pcg_mixed takes the fp64 side for products and residuals alone); a hierarchy without an image walks its CSR rows
+    if (vs.amg && in.dim == 3 && amg_wants_image()) amg_level0_image(ar, s, amg64, in.o.precision == 0 && !vs.amg32, amg32_ready ? &amg32 : nullptr);
     *coarse_used = !two_level ? 0 : (vs.amg ? 2 : 1);
     if (two_level) {
         double lmax;
